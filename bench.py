@@ -72,7 +72,30 @@ def parse():
                     "through ONE pool handle (batch resident on GPU 0, shards moved by RCCL) that the line carries as `pool_resident`")
     ap.add_argument("--oracle-sample", type=int, default=0, help="with --pool-devices --resident: hold the first K results to the "
                     "CPU path word for word (under the key exported from member 0)")
-    return ap.parse_args()
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR", help="after the timed steps, write the ciphertexts the "
+                    "last timed step computed as DIR/out.npy (DIR/out_rank<r>.npy per rank at N > 1): float64 holding the "
+                    "uint32 torus words exactly, [rows][n+1]; when the batch exceeds the 64 MB budget, a fixed seeded "
+                    "sample of rows (in batch order) stands for it.  Inputs are seeded: equal arguments, equal inputs")
+    args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    if args.dump_outputs and (args.pool_devices or args.stage):
+        ap.error("--dump-outputs applies to the gate path (not --pool-devices / --stage)")
+    return args
+
+
+DUMP_BYTES = 64_000_000  # budget of --dump-outputs over all ranks (a little under 64 MiB, .npy headers included)
+
+
+def dump_outputs(dirname, out, rank, world):
+    """The last step's output rows as float64 (exact for uint32 words); a seeded sample of rows if over budget."""
+    import numpy as np
+
+    rows = max(1, DUMP_BYTES // world // (8 * out.shape[1]))
+    if out.shape[0] > rows:
+        out = out[np.sort(np.random.default_rng(0).choice(out.shape[0], rows, replace=False))]
+    os.makedirs(dirname, exist_ok=True)
+    np.save(os.path.join(dirname, "out.npy" if world == 1 else f"out_rank{rank}.npy"), out.astype(np.float64))
 
 
 def stage_mode(args):
@@ -632,6 +655,8 @@ def main():
 
     # ---- sanity: decrypt the shard (integer, host) ----
     out = to.cpu().numpy().view(np.uint32)
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, out, rank, world)
     if args.gate == "pbs":
         decrypt_ok = bool(np.array_equal(sk.decrypt_lwe_message(out, args.modulus), (msgs ** 2) % args.modulus))
     elif args.gate == "mux":

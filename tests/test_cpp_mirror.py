@@ -1,6 +1,8 @@
 """C++ host mirror (include/rs_tfhe_hip.hpp): compiles on CPU; its reference-style test
 program (tests/cpp/test_mirror.cpp) runs on the GPU through the C ABI."""
 import os
+import platform
+import shutil
 import subprocess
 
 import pytest
@@ -29,7 +31,12 @@ def test_front_end_queue_under_thread_sanitizer():
     with -fsanitize=thread and driven by up to 64 threads with a stand-in for the launch: every request served exactly
     once with its own result, no report from ThreadSanitizer, quiesce / with_idle_lanes beside the traffic."""
     subprocess.check_call(["make", "-C", CPP, "build/test_combine_queue"])
-    r = subprocess.run([os.path.join(CPP, "build", "test_combine_queue")], capture_output=True, text=True, timeout=600,
+    # ThreadSanitizer's runtime refuses the address layouts of kernels with high mmap randomisation ("unexpected memory
+    # mapping"): the program runs with randomisation off for its own process (setarch -R), the system left as it is
+    exe = [os.path.join(CPP, "build", "test_combine_queue")]
+    if shutil.which("setarch"):
+        exe = ["setarch", platform.machine(), "-R"] + exe
+    r = subprocess.run(exe, capture_output=True, text=True, timeout=600,
                        env=dict(os.environ, TSAN_OPTIONS="halt_on_error=1 second_deadlock_stack=1"))
     print(r.stdout[-3000:], r.stderr[-6000:])
     assert r.returncode == 0 and "all queue checks passed" in r.stdout

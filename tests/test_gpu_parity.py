@@ -1856,28 +1856,43 @@ def test_bench_two_ranks_mixed_circuit_80bit():
     assert d["n_gpus"] == 2 and d["decrypt_ok"] is True and "SECURITY_80_BIT" in d["metric"]
 
 
-def test_bench_eight_ranks_share_one_gpu():
-    """`bench.py --gpus 8`, the N = 8 branch the driver's scaling sweep runs, end to end on this box's one GPU (eight
-    ranks, BENCH_SHARE_GPU=1): no MASTER_PORT given, so the torchrun child gets a port that is free now; the line carries
+def test_bench_four_ranks_share_one_gpu():
+    """`bench.py --gpus 4`, the N > 2 branch the driver's scaling sweep runs, end to end on this box's one GPU (four
+    ranks, BENCH_SHARE_GPU=1; with this process and rank 0's pool-resident child that is six processes on the GPU, the
+    most a shared box allows): no MASTER_PORT given, so the torchrun child gets a port that is free now; the line carries
     every rank's own time for the steps, its kernels' launch times and the key broadcast's duration."""
     for extra in ([], ["--gate", "mixed", "--params", "SECURITY_80_BIT"]):
-        d = _run_bench(["--gpus", "8", "--steps", "1", "--warmup", "0", "--batch", "1024", "--no-cpu-baseline"] + extra,
+        d = _run_bench(["--gpus", "4", "--steps", "1", "--warmup", "0", "--batch", "1024", "--no-cpu-baseline"] + extra,
                        {"BENCH_SHARE_GPU": "1"})
-        assert d["n_gpus"] == 8 and d["decrypt_ok"] is True and d["scaling"] == "weak"
-        assert d["config"]["global_batch"] == 8192 and d["value"] > 0
+        assert d["n_gpus"] == 4 and d["decrypt_ok"] is True and d["scaling"] == "weak"
+        assert d["config"]["global_batch"] == 4096 and d["value"] > 0
         pr = d["per_rank"]
-        assert all(len(pr[k]) == 8 for k in ("ms_per_step", "blind_rotate_ms", "key_switch_ms", "shader_mhz", "key_broadcast_s"))
+        assert all(len(pr[k]) == 4 for k in ("ms_per_step", "blind_rotate_ms", "key_switch_ms", "shader_mhz", "key_broadcast_s"))
         assert d["ms_per_step_max_rank"] == max(pr["ms_per_step"]) and d["ms_per_step_min_rank"] > 0
         assert d["ms_per_step"] >= d["ms_per_step_max_rank"] - 0.01  # the line's time is the max over ranks
         assert d["key_broadcast_s"] > 0 and d["key_broadcast_backend"] == "gloo"
-        # BASELINE configs[2] as one caller has it: ONE pool handle over the eight members, the GLOBAL batch resident on
+        # BASELINE configs[2] as one caller has it: ONE pool handle over the members, the GLOBAL batch resident on
         # member 0's GPU (a fresh child of rank 0, after the ranks have let go of the GPU); here the members share a
         # device, so the shards move by peer copies
         pr = d["pool_resident"]
         assert "error" not in pr, pr
+        assert pr["batch_total"] == 4096 and len(pr["devices"]) == 4 and pr["transport"] == "peer-copy" and pr["value"] > 0
+        if not extra:
+            assert pr["decrypt_ok"] is True and pr["oracle_sample_equal"] is True and pr["oracle_sample"] == 16
+
+
+def test_bench_pool_resident_eight_members_one_process():
+    """The N = 8 pool-resident child that `bench.py --gpus 8` starts on rank 0, run on its own (ONE process, eight
+    members on this box's one GPU): the global batch of 8192 resident on member 0, cut over all eight members by peer
+    copies, equal to the CPU path on its first 16 words; the same for the mixed circuit level at SECURITY_80_BIT."""
+    for extra in ([], ["--gate", "mixed", "--params", "SECURITY_80_BIT"]):
+        pr = _run_bench(["--pool-devices", "0,0,0,0,0,0,0,0", "--resident", "--steps", "1", "--warmup", "1", "--batch", "1024",
+                         "--oracle-sample", "16"] + extra, {"TFHE_HIP_POOL_RCCL": "1"})
         assert pr["batch_total"] == 8192 and len(pr["devices"]) == 8 and pr["transport"] == "peer-copy" and pr["value"] > 0
         if not extra:
             assert pr["decrypt_ok"] is True and pr["oracle_sample_equal"] is True and pr["oracle_sample"] == 16
+        else:
+            assert pr["decrypt_ok"] is True and "SECURITY_80_BIT" in pr["metric"]
 
 
 def test_bench_line_carries_the_other_configs_and_the_concurrent_callers():

@@ -143,24 +143,21 @@ def test_param_sets_match_oracle_and_survey(O):
 
 
 def test_param_sets_match_reference_source():
-    """Every SecurityParams constant of src/params.rs (11 sets, UINT6 / UINT8 included), parsed from the reference's
-    own source text where it lies, equals the product's table (and the C++ mirror's)."""
-    path = "/root/reference/src/params.rs"
-    if not os.path.exists(path):
-        pytest.skip("reference sources not present on this box")
+    """Every SecurityParams constant of src/params.rs (11 sets, UINT6 / UINT8 included), as read from the reference's own
+    source text into tests/golden/reference_params.json, equals the product's table (and the C++ mirror's); where the
+    reference tree is present, the table is re-read from it and compared."""
+    import importlib.util
+    import json
+
     from rs_tfhe_amd import params as P
 
-    src = re.sub(r"//[^\n]*", "", open(path).read()).replace("_", "")  # comments and digit separators out
-    found = {}
-    for m in re.finditer(r"pub const (SECURITY[A-Z0-9]+): SecurityParams = SecurityParams \{(.*?)\n\};", src, re.S):
-        body = m.group(2)
-        lv0 = re.search(r"tlwelv0: TlweParams \{\s*n: (\d+),\s*alpha: ([0-9.e+-]+)", body)
-        lv1 = re.search(r"tlwelv1: TlweParams \{\s*n: (\d+),\s*alpha: ([0-9.e+-]+)", body)
-        g = re.search(r"trgswlv1: TrgswParams \{(.*?)\}", body, re.S).group(1)
-        f = {k: re.search(rf"\b{k}: ([0-9.e+-]+)", g).group(1) for k in ("n", "bgbit", "l", "basebit", "ikst")}
-        name = m.group(1).replace("SECURITY", "SECURITY_").replace("BIT", "_BIT")
-        found[name] = (int(lv0.group(1)), int(f["l"]), int(f["bgbit"]), int(f["basebit"]), int(f["ikst"]),
-                       float(lv0.group(2)), float(lv1.group(2)), int(f["n"]))
+    spec = importlib.util.spec_from_file_location("mrp", os.path.join(ROOT, "tests", "golden", "make_reference_params.py"))
+    mod = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(mod)
+    table = json.load(open(os.path.join(ROOT, "tests", "golden", "reference_params.json")))
+    if os.path.exists(os.path.join(mod.REF, "params.rs")):
+        assert mod.collect() == table, "tests/golden/reference_params.json is stale: re-run make_reference_params.py"
+    found = {name: tuple(v) for name, v in table.items()}
     assert len(found) == 11, sorted(found)
     hdr = open(os.path.join(ROOT, "include", "rs_tfhe_hip.hpp")).read()
     for name, (n, l, bgbit, basebit, t, a0, a1, N) in found.items():
