@@ -975,4 +975,110 @@ inline Ciphertext reencrypt_tlwe_lv0(const Ciphertext &ct_from, const ProxyReenc
 }
 }  // namespace proxy_reenc
 
+
+// ---- circuits (tfhe_hip_circuit_*): a gate / mux / LUT DAG built once, levelised and run natively -----------------
+// examples/add_two_numbers.rs:11-50 as a circuit: full_adder / add below build the same gates in the same order, and a
+// run evaluates every level of it -- all of its gates times the whole batch -- in one launch per kind.
+class Circuit {
+ public:
+  typedef uint32_t Wire;
+  explicit Circuit(uint32_t n_inputs) : n_inputs_(n_inputs) {
+    if (tfhe_hip_circuit_create(n_inputs, &h_) != TFHE_HIP_OK) throw std::runtime_error("tfhe_hip_circuit_create failed");
+  }
+  ~Circuit() { tfhe_hip_circuit_destroy(h_); }
+  Circuit(const Circuit &) = delete;
+  Circuit &operator=(const Circuit &) = delete;
+
+  Wire gate(int op, Wire a, Wire b) { return add(tfhe_hip_circuit_add_gate(h_, op, a, b, &w_)); }
+  Wire nand(Wire a, Wire b) { return gate(TFHE_HIP_NAND, a, b); }
+  Wire and_(Wire a, Wire b) { return gate(TFHE_HIP_AND, a, b); }
+  Wire or_(Wire a, Wire b) { return gate(TFHE_HIP_OR, a, b); }
+  Wire xor_(Wire a, Wire b) { return gate(TFHE_HIP_XOR, a, b); }
+  Wire mux(Wire a, Wire b, Wire c) { return add(tfhe_hip_circuit_add_mux(h_, a, b, c, &w_)); }  // gates.rs:157-183
+  uint32_t lut(const TRLWELv1 &testvec) {  // a test vector from lut::Generator::generate_lookup_table
+    uint32_t id = 0;
+    check(tfhe_hip_circuit_add_lut(h_, testvec.a.data(), &id), "add_lut");
+    return id;
+  }
+  Wire pbs(Torus ca, Wire a, Torus cb, Wire b, Torus cconst, uint32_t lut) {
+    return add(tfhe_hip_circuit_add_pbs(h_, ca, a, cb, b, cconst, lut, &w_));
+  }
+  Wire lincomb(const std::vector<std::pair<Torus, Wire>> &terms, Torus cconst = 0) {
+    std::vector<uint32_t> c, w;
+    for (auto &t : terms) c.push_back(t.first), w.push_back(t.second);
+    return add(tfhe_hip_circuit_add_lincomb(h_, c.data(), w.data(), terms.size(), cconst, &w_));
+  }
+  Wire not_(Wire a) { return add(tfhe_hip_circuit_add_not(h_, a, &w_)); }
+  Wire constant(bool value) { return add(tfhe_hip_circuit_add_constant(h_, value ? 1 : 0, &w_)); }
+
+  // examples/add_two_numbers.rs:11-29
+  std::pair<Wire, Wire> full_adder(Wire a, Wire b, Wire c) {
+    const Wire a_xor_b = xor_(a, b), a_and_b = and_(a, b);
+    const Wire a_xor_b_and_c = and_(a_xor_b, c);
+    const Wire s = xor_(a_xor_b, c);
+    const Wire carry = or_(a_and_b, a_xor_b_and_c);
+    return {s, carry};
+  }
+  // examples/add_two_numbers.rs:31-50 -> (sum bits, carry out)
+  std::pair<std::vector<Wire>, Wire> add(const std::vector<Wire> &a, const std::vector<Wire> &b, Wire cin) {
+    if (a.size() != b.size()) throw std::runtime_error("Cannot add two numbers with different number of bits!");
+    std::vector<Wire> result;
+    Wire carry = cin;
+    for (size_t i = 0; i < a.size(); ++i) {
+      auto sc = full_adder(a[i], b[i], carry);
+      result.push_back(sc.first);
+      carry = sc.second;
+    }
+    return {result, carry};
+  }
+
+  // inputs[i][j]: input wire i of batch element j -> result[k][j]: wire out_wires[k] of batch element j
+  std::vector<std::vector<Ciphertext>> run(const CloudKey &ck, const std::vector<std::vector<Ciphertext>> &inputs,
+                                           const std::vector<Wire> &out_wires, int device = 0) {
+    auto b = Engine::for_key(ck, device);
+    std::vector<std::vector<Ciphertext>> out;
+    b.with_key(ck, [&](tfhe_hip_ctx *c) { return run_on(c, ck.params.n, inputs, out_wires, out); });
+    return out;
+  }
+  // on an engine's own context (its key loaded by the caller)
+  std::vector<std::vector<Ciphertext>> run(Engine &e, const std::vector<std::vector<Ciphertext>> &inputs,
+                                           const std::vector<Wire> &out_wires) {
+    std::vector<std::vector<Ciphertext>> out;
+    e.check(run_on(e.ctx(), e.params().n, inputs, out_wires, out));
+    return out;
+  }
+  tfhe_hip_circuit *handle() const { return h_; }
+
+ private:
+  int run_on(tfhe_hip_ctx *c, int n, const std::vector<std::vector<Ciphertext>> &inputs, const std::vector<Wire> &out_wires,
+             std::vector<std::vector<Ciphertext>> &out) {
+    if (inputs.size() != n_inputs_ || inputs.empty()) throw std::runtime_error("one batch per circuit input");
+    const size_t B = inputs[0].size(), w = (size_t)n + 1;
+    std::vector<Torus> in(inputs.size() * B * w), res(out_wires.size() * B * w);
+    for (size_t i = 0; i < inputs.size(); ++i) {
+      if (inputs[i].size() != B) throw std::runtime_error("inputs differ in batch size");
+      for (size_t j = 0; j < B; ++j) {
+        if (inputs[i][j].p.size() != w) throw std::runtime_error("ciphertext dimension does not match the key");
+        std::memcpy(&in[(i * B + j) * w], inputs[i][j].p.data(), w * sizeof(Torus));
+      }
+    }
+    const int rc = tfhe_hip_circuit_run(c, h_, in.data(), B, out_wires.data(), out_wires.size(), res.data());
+    if (rc != TFHE_HIP_OK) return rc;
+    out.assign(out_wires.size(), std::vector<Ciphertext>(B, Ciphertext(n)));
+    for (size_t k = 0; k < out_wires.size(); ++k)
+      for (size_t j = 0; j < B; ++j) std::memcpy(out[k][j].p.data(), &res[(k * B + j) * w], w * sizeof(Torus));
+    return rc;
+  }
+  Wire add(int rc) {
+    check(rc, "add");
+    return w_;
+  }
+  static void check(int rc, const char *what) {
+    if (rc != TFHE_HIP_OK) throw std::runtime_error(std::string("tfhe_hip_circuit_") + what + ": invalid node");
+  }
+  uint32_t n_inputs_;
+  tfhe_hip_circuit *h_ = nullptr;
+  Wire w_ = 0;
+};
+
 }  // namespace rs_tfhe

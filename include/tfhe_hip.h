@@ -586,6 +586,74 @@ typedef struct tfhe_hip_pool_transfer_times {
 int tfhe_hip_pool_set_profiling(tfhe_hip_pool *pool, int enabled);
 int tfhe_hip_pool_get_transfer_times(tfhe_hip_pool *pool, tfhe_hip_pool_transfer_times *out);
 
+/* ---- circuits: gate / mux / LUT DAGs, scheduled and run natively ------------------------------------------------
+ * Replaces the reference's one-gate-at-a-time evaluation of a gate DAG (examples/add_two_numbers.rs:11-50: full_adder
+ * / add; examples/lut_add_two_numbers.rs:82-158: the LUT nibble adder).  A circuit has n_inputs input wires (ids
+ * 0 .. n_inputs-1); every tfhe_hip_circuit_add_* appends one node and returns its wire id in *wire.  Nodes:
+ *   gate(op, a, b)                 Gates::<op> (src/gates.rs:54-150), op a tfhe_hip_gate code, b ignored for COPY
+ *   mux(a, b, c)                   Gates::mux (src/gates.rs:157-183; the reference formula, not mux_naive)
+ *   pbs(ca, a, cb, b, cconst, lut) programmable bootstrap (src/bootstrap/lut.rs:79-99) of ca*a + cb*b, body + cconst,
+ *                                  with the test vector add_lut registered ([2][N] u32, N = 1024); b ignored if cb == 0
+ *   lincomb(coefs, wires, cconst)  sum coefs[i] * wires[i], body + cconst: TLWE `+` / `-` / scaling, no bootstrap
+ *   not(a) = -a, constant(value)   src/gates.rs:202-219 (constant(0) has body 1 - 1/8 as in the reference: 0xE0000001)
+ * tfhe_hip_circuit_compile levelises it (no device needed; run calls it too): inputs are level 0, a bootstrap is one
+ * level above its deepest operand, a linear node at the level of its deepest operand.  Wires are renumbered into store
+ * SLOTS: inputs take slots 0 .. n_inputs-1, each level's outputs one contiguous range.  Per level at most one lincomb
+ * launch (linear operands that cannot be folded), one bootstrap-without-key-switch launch (the muxes' two halves), one
+ * key-switched gate launch (gates and the muxes' or), then one launch per (lut, coefficients) group.  A bootstrap whose
+ * linear operands expand to at most two source wires folds them into its prologue (exact wrapping arithmetic: the
+ * words are the reference's).  Bootstraps read their operands out of the store by row index inside the blind
+ * rotation; nothing is scattered or gathered between levels.  The indices are built once per (circuit, context, batch
+ * size) and kept on the device with the circuit, so a repeated run uploads only its inputs.
+ * Bad wire ids, a gate code above COPY, an unknown lut id, adding after compile, and slots x batch >= 2^32 are
+ * TFHE_HIP_EINVAL.  A circuit may be shared between threads; destroy it after the work it enqueued is done.  It keeps
+ * device state for at most four (context, batch size) pairs, dropping the least recently used. */
+typedef struct tfhe_hip_circuit tfhe_hip_circuit;
+int tfhe_hip_circuit_create(uint32_t n_inputs, tfhe_hip_circuit **out);
+void tfhe_hip_circuit_destroy(tfhe_hip_circuit *circ);
+int tfhe_hip_circuit_add_gate(tfhe_hip_circuit *circ, int gate, uint32_t a, uint32_t b, uint32_t *wire);
+int tfhe_hip_circuit_add_mux(tfhe_hip_circuit *circ, uint32_t a, uint32_t b, uint32_t c, uint32_t *wire);
+int tfhe_hip_circuit_add_lut(tfhe_hip_circuit *circ, const uint32_t *testvec, uint32_t *lut);
+int tfhe_hip_circuit_add_pbs(tfhe_hip_circuit *circ, uint32_t ca, uint32_t a, uint32_t cb, uint32_t b, uint32_t cconst,
+                             uint32_t lut, uint32_t *wire);
+int tfhe_hip_circuit_add_lincomb(tfhe_hip_circuit *circ, const uint32_t *coefs, const uint32_t *wires, size_t n_terms,
+                                 uint32_t cconst, uint32_t *wire);
+int tfhe_hip_circuit_add_not(tfhe_hip_circuit *circ, uint32_t a, uint32_t *wire);
+int tfhe_hip_circuit_add_constant(tfhe_hip_circuit *circ, int value, uint32_t *wire);
+int tfhe_hip_circuit_compile(tfhe_hip_circuit *circ);
+/* The schedule, for tests and tools: *n_levels levels (level 0 = the inputs); for each of the first `cap` levels
+ * TFHE_HIP_CIRCUIT_LEVEL_WORDS words: first slot, end slot (exclusive), then (launches, nodes) for the lincomb,
+ * bootstrap-without-key-switch, gate and lut launches in that order.  levels may be NULL (count only). */
+#define TFHE_HIP_CIRCUIT_LEVEL_WORDS 10
+int tfhe_hip_circuit_describe(tfhe_hip_circuit *circ, uint32_t *levels, size_t cap, size_t *n_levels);
+/* Slots of the store ([slots][batch][n+1] u32); a wire's slot (0xFFFFFFFF: a linear node, formed where it is read);
+ * the slots a bootstrap node's launch reads (up to 3: a mux's a, b, c; for a folded node its source wires'). */
+int tfhe_hip_circuit_slots(tfhe_hip_circuit *circ, uint32_t *slots);
+int tfhe_hip_circuit_wire_slot(tfhe_hip_circuit *circ, uint32_t wire, uint32_t *slot);
+int tfhe_hip_circuit_operand_slots(tfhe_hip_circuit *circ, uint32_t wire, uint32_t *slots, uint32_t *n);
+/* Host arrays: inputs [n_inputs][batch][n+1] -> out [n_out][batch][n+1], wire out_wires[k] in out[k].  Holds the
+ * context's lock for the whole run (a key change cannot interleave); needs a loaded key. */
+int tfhe_hip_circuit_run(tfhe_hip_ctx *ctx, tfhe_hip_circuit *circ, const uint32_t *inputs, size_t batch,
+                         const uint32_t *out_wires, size_t n_out, uint32_t *out);
+/* Device store `wires` [slots][batch][n+1] on the context's GPU; `inputs` [n_inputs][batch][n+1] is copied into slots
+ * 0 .. n_inputs-1 first (NULL: already there).  Enqueue only.  Replaces the per-level torch gathers of Circuit.run_dev. */
+int tfhe_hip_circuit_run_dev(tfhe_hip_ctx *ctx, tfhe_hip_circuit *circ, const uint32_t *inputs, uint32_t *wires,
+                             size_t batch, void *stream);
+/* out [n_out][batch][n+1] = wires out_wires[k] (caller's numbering) read out of a run's store; a linear node is formed
+ * from its sources here.  out_wires is a host array. */
+int tfhe_hip_circuit_gather_dev(tfhe_hip_ctx *ctx, tfhe_hip_circuit *circ, const uint32_t *wires, size_t batch,
+                                const uint32_t *out_wires, size_t n_out, uint32_t *out, void *stream);
+/* The same through a pool: the store lives on member `home`; each level's operands are gathered into staging there
+ * and go through tfhe_hip_pool_batch_gates_mixed[_nks]_dev / _lincomb_bootstrap_dev (cut over the members).  The
+ * host form keeps the store on member 0.  Runs of one circuit through one pool -- or through key views of it, which
+ * share its members -- are serialised by the library, whatever the threads and streams; the staging is the circuit's. */
+int tfhe_hip_circuit_run_pool(tfhe_hip_pool *pool, tfhe_hip_circuit *circ, const uint32_t *inputs, size_t batch,
+                              const uint32_t *out_wires, size_t n_out, uint32_t *out);
+int tfhe_hip_circuit_run_pool_dev(tfhe_hip_pool *pool, int home_member, tfhe_hip_circuit *circ, const uint32_t *inputs,
+                                  uint32_t *wires, size_t batch, void *stream);
+int tfhe_hip_circuit_gather_pool_dev(tfhe_hip_pool *pool, int home_member, tfhe_hip_circuit *circ, const uint32_t *wires,
+                                     size_t batch, const uint32_t *out_wires, size_t n_out, uint32_t *out, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

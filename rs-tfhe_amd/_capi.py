@@ -161,7 +161,31 @@ SIGNATURES = {
     "tfhe_hip_pool_data_transport": (C.c_char_p, [_CTX]),
     "tfhe_hip_pool_set_profiling": (C.c_int, [_CTX, C.c_int]),
     "tfhe_hip_pool_get_transfer_times": (C.c_int, [_CTX, C.POINTER(PoolTransferTimes)]),
+    # circuits (create / add / compile / describe need no device)
+    "tfhe_hip_circuit_create": (C.c_int, [_U32, C.POINTER(_CTX)]),
+    "tfhe_hip_circuit_destroy": (None, [_CTX]),
+    "tfhe_hip_circuit_add_gate": (C.c_int, [_CTX, C.c_int, _U32, _U32, C.POINTER(_U32)]),
+    "tfhe_hip_circuit_add_mux": (C.c_int, [_CTX, _U32, _U32, _U32, C.POINTER(_U32)]),
+    "tfhe_hip_circuit_add_lut": (C.c_int, [_CTX, _P, C.POINTER(_U32)]),
+    "tfhe_hip_circuit_add_pbs": (C.c_int, [_CTX, _U32, _U32, _U32, _U32, _U32, _U32, C.POINTER(_U32)]),
+    "tfhe_hip_circuit_add_lincomb": (C.c_int, [_CTX, _P, _P, _SZ, _U32, C.POINTER(_U32)]),
+    "tfhe_hip_circuit_add_not": (C.c_int, [_CTX, _U32, C.POINTER(_U32)]),
+    "tfhe_hip_circuit_add_constant": (C.c_int, [_CTX, C.c_int, C.POINTER(_U32)]),
+    "tfhe_hip_circuit_compile": (C.c_int, [_CTX]),
+    "tfhe_hip_circuit_describe": (C.c_int, [_CTX, _P, _SZ, C.POINTER(_SZ)]),
+    "tfhe_hip_circuit_slots": (C.c_int, [_CTX, C.POINTER(_U32)]),
+    "tfhe_hip_circuit_wire_slot": (C.c_int, [_CTX, _U32, C.POINTER(_U32)]),
+    "tfhe_hip_circuit_operand_slots": (C.c_int, [_CTX, _U32, _P, C.POINTER(_U32)]),
+    "tfhe_hip_circuit_run": (C.c_int, [_CTX, _CTX, _P, _SZ, _P, _SZ, _P]),
+    "tfhe_hip_circuit_run_dev": (C.c_int, [_CTX, _CTX, _P, _P, _SZ, _P]),
+    "tfhe_hip_circuit_gather_dev": (C.c_int, [_CTX, _CTX, _P, _SZ, _P, _SZ, _P, _P]),
+    "tfhe_hip_circuit_run_pool": (C.c_int, [_CTX, _CTX, _P, _SZ, _P, _SZ, _P]),
+    "tfhe_hip_circuit_run_pool_dev": (C.c_int, [_CTX, C.c_int, _CTX, _P, _P, _SZ, _P]),
+    "tfhe_hip_circuit_gather_pool_dev": (C.c_int, [_CTX, C.c_int, _CTX, _P, _SZ, _P, _SZ, _P, _P]),
 }
+
+CIRCUIT_LEVEL_WORDS = 10  # TFHE_HIP_CIRCUIT_LEVEL_WORDS
+NO_SLOT = 0xFFFFFFFF
 
 _lib = None
 

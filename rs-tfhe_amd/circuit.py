@@ -1,17 +1,20 @@
-"""Levelised gate circuits with device-resident ciphertexts.
+"""Levelised circuits with device-resident ciphertexts.
 
 The reference's real workloads are gate DAGs evaluated one gate at a time on the CPU
-(examples/add_two_numbers.rs:11-50: full_adder / add).  Here a circuit is built once as a DAG
-over wires, levelised, and every level -- all of its gates, whatever their types, times the
-whole batch of independent inputs -- is ONE `tfhe_hip_batch_gates_mixed_dev` launch.  Wires
-stay in HBM between levels; only the operand gather (an index_select) sits between launches.
+(examples/add_two_numbers.rs:11-50: full_adder / add; examples/lut_add_two_numbers.rs:82-158: the LUT nibble adder).
+Here a circuit is built once as a DAG over wires -- gates, muxes, programmable bootstraps and linear nodes -- and run
+by the native scheduler behind the C ABI (`tfhe_hip_circuit_*`, include/tfhe_hip.h): levelised, every level one
+launch per kind whatever its size times the whole batch, operands read out of one device-resident wire store by row
+index inside the blind rotation, results written contiguously.  No torch operation sits between levels.
 """
 from __future__ import annotations
 
+import ctypes as C
 from dataclasses import dataclass, field
 
 import numpy as np
 
+from . import _capi
 from . import engine as E
 
 
@@ -30,21 +33,45 @@ class Circuit:
     gates: list = field(default_factory=list)
     _level: dict = field(default_factory=dict)
     _n_wires: int = 0
-    _plans: dict = field(default_factory=dict)  # (device, n_gates) -> per-level index / gate-code tensors
+    _plans: dict = field(default_factory=dict)  # (device, n_gates) -> per-level index / gate-code tensors (_run_dev_torch)
+    _nodes: list = field(default_factory=list)  # one entry per non-input wire, in wire order
+    _luts: list = field(default_factory=list)   # [2][N] uint32 test vectors (lut ids)
+    _native: object = field(default=None, repr=False)  # the compiled tfhe_hip_circuit of the nodes so far
 
     def __post_init__(self):
         self._n_wires = self.n_inputs
         for w in range(self.n_inputs):
             self._level[w] = 0
 
+    def __del__(self):
+        try:
+            self._drop_native()
+        except Exception:
+            pass
+
     # -- construction ----------------------------------------------------------------
-    def gate(self, op: int, a: int, b: int) -> int:
-        """A bootstrapped two-input gate (one of tfhe_hip_gate); returns its output wire."""
+    def _wire(self, w) -> int:
+        w = int(w)
+        if not 0 <= w < self._n_wires:
+            raise ValueError(f"no wire {w}")
+        return w
+
+    def _add(self, node, level) -> int:
         out = self._n_wires
         self._n_wires += 1
-        lvl = 1 + max(self._level[a], self._level[b])
-        self._level[out] = lvl
-        self.gates.append(_Gate(op, a, b, out, lvl))
+        self._level[out] = level
+        self._nodes.append(node)
+        self._drop_native()
+        return out
+
+    def gate(self, op: int, a: int, b: int) -> int:
+        """A bootstrapped two-input gate (one of tfhe_hip_gate); returns its output wire."""
+        a, b = self._wire(a), self._wire(b)
+        if not 0 <= op <= E.COPY:
+            raise ValueError(f"unknown gate code {op}")
+        lvl = 1 + max(self._level[a], self._level[b] if op != E.COPY else 0)
+        out = self._add(("gate", int(op), a, b), lvl)
+        self.gates.append(_Gate(int(op), a, b, out, lvl))
         return out
 
     def nand(self, a, b): return self.gate(E.NAND, a, b)
@@ -61,6 +88,45 @@ class Circuit:
     def mux_naive(self, a, b, c):
         """Gates::mux_naive (src/gates.rs:189-199): or(and(a, b), and(not(a), c))."""
         return self.or_(self.and_(a, b), self.and_ny(a, c))
+
+    def mux(self, a, b, c):
+        """Gates::mux (src/gates.rs:157-183, the reference formula): a ? b : c in one level."""
+        a, b, c = self._wire(a), self._wire(b), self._wire(c)
+        return self._add(("mux", a, b, c), 1 + max(self._level[a], self._level[b], self._level[c]))
+
+    def lut(self, testvec) -> int:
+        """Register a test vector ([2][N] u32, e.g. lut.Generator(...).generate_lookup_table(f).poly); returns its id."""
+        tv = np.ascontiguousarray(testvec, dtype=np.uint32).reshape(-1)
+        if tv.size != 2 * E.N:
+            raise ValueError(f"a test vector is [2][{E.N}]")
+        self._luts.append(tv)
+        self._drop_native()
+        return len(self._luts) - 1
+
+    def pbs(self, ca: int, a: int, cb: int, b, cconst: int, lut: int) -> int:
+        """Programmable bootstrap (src/bootstrap/lut.rs:79-99) of ca*a + cb*b (body + cconst) through test vector
+        `lut`, key-switched; b is ignored when cb == 0."""
+        a = self._wire(a)
+        cb &= 0xFFFFFFFF
+        b = self._wire(b) if cb else a
+        if not 0 <= lut < len(self._luts):
+            raise ValueError(f"no lut {lut}")
+        lvl = 1 + max(self._level[a], self._level[b] if cb else 0)
+        return self._add(("pbs", ca & 0xFFFFFFFF, a, cb, b, cconst & 0xFFFFFFFF, int(lut)), lvl)
+
+    def lincomb(self, terms, cconst: int = 0) -> int:
+        """sum coef * wire (+ cconst on the body): TLWE `+` / `-` / scaling, no bootstrap.  terms: [(coef, wire)]."""
+        terms = [(int(c) & 0xFFFFFFFF, self._wire(w)) for c, w in terms]
+        lvl = max((self._level[w] for _, w in terms), default=0)
+        return self._add(("lin", tuple(terms), cconst & 0xFFFFFFFF), lvl)
+
+    def not_(self, a) -> int:
+        """Gates::not (src/gates.rs:202-204): -a, no bootstrap."""
+        return self.lincomb([(0xFFFFFFFF, a)])
+
+    def constant(self, value: bool) -> int:
+        """Gates::constant (src/gates.rs:212-219): body 1/8, or 1 - 1/8 wrapped for false (quirk Q6)."""
+        return self.lincomb([], 0x20000000 if value else 0xE0000001)
 
     def full_adder(self, a, b, c):
         """examples/add_two_numbers.rs:11-29 -> (sum, carry)."""
@@ -93,20 +159,115 @@ class Circuit:
             out[g.level - 1].append(g)
         return out
 
+    # -- the native circuit ----------------------------------------------------------------
+    def _drop_native(self):
+        if self._native is not None:
+            _capi.lib().tfhe_hip_circuit_destroy(self._native)
+            self._native = None
+
+    def _native_handle(self):
+        """The nodes so far as a compiled tfhe_hip_circuit (built on first use, rebuilt after further additions)."""
+        if self._native is not None:
+            return self._native
+        lib = _capi.lib()
+        h = C.c_void_p()
+        _chk_circ(lib.tfhe_hip_circuit_create(self.n_inputs, C.byref(h)), "create")
+        try:
+            w, lid = C.c_uint32(), C.c_uint32()
+            for tv in self._luts:
+                _chk_circ(lib.tfhe_hip_circuit_add_lut(h, tv.ctypes.data_as(C.c_void_p), C.byref(lid)), "add_lut")
+            for node in self._nodes:
+                kind = node[0]
+                if kind == "gate":
+                    rc = lib.tfhe_hip_circuit_add_gate(h, node[1], node[2], node[3], C.byref(w))
+                elif kind == "mux":
+                    rc = lib.tfhe_hip_circuit_add_mux(h, node[1], node[2], node[3], C.byref(w))
+                elif kind == "pbs":
+                    rc = lib.tfhe_hip_circuit_add_pbs(h, *node[1:], C.byref(w))
+                else:
+                    coefs = np.array([c for c, _ in node[1]], np.uint32)
+                    wires = np.array([x for _, x in node[1]], np.uint32)
+                    rc = lib.tfhe_hip_circuit_add_lincomb(h, coefs.ctypes.data_as(C.c_void_p), wires.ctypes.data_as(C.c_void_p),
+                                                          len(node[1]), node[2], C.byref(w))
+                _chk_circ(rc, f"add_{kind}")
+            _chk_circ(lib.tfhe_hip_circuit_compile(h), "compile")
+        except Exception:
+            lib.tfhe_hip_circuit_destroy(h)
+            raise
+        self._native = h
+        self._all_wires = np.arange(self._n_wires, dtype=np.uint32)
+        return h
+
+    def describe(self) -> list:
+        """The native schedule, one dict per level (level 0 = the inputs): slot range and (launches, nodes) per kind."""
+        lib, h = _capi.lib(), self._native_handle()
+        n = C.c_size_t()
+        _chk_circ(lib.tfhe_hip_circuit_describe(h, None, 0, C.byref(n)), "describe")
+        buf = np.zeros((n.value, _capi.CIRCUIT_LEVEL_WORDS), np.uint32)
+        _chk_circ(lib.tfhe_hip_circuit_describe(h, buf.ctypes.data_as(C.c_void_p), n.value, C.byref(n)), "describe")
+        keys = ("begin", "end", "lincomb_launches", "lincomb_nodes", "nks_launches", "nks_nodes", "gate_launches",
+                "gate_nodes", "lut_launches", "lut_nodes")
+        return [dict(zip(keys, (int(x) for x in row))) for row in buf]
+
+    @property
+    def slots(self) -> int:
+        v = C.c_uint32()
+        _chk_circ(_capi.lib().tfhe_hip_circuit_slots(self._native_handle(), C.byref(v)), "slots")
+        return v.value
+
+    def wire_slot(self, wire: int) -> int:
+        """The store slot of `wire` (_capi.NO_SLOT for a linear node, formed where it is read)."""
+        v = C.c_uint32()
+        _chk_circ(_capi.lib().tfhe_hip_circuit_wire_slot(self._native_handle(), int(wire), C.byref(v)), "wire_slot")
+        return v.value
+
+    def operand_slots(self, wire: int) -> list:
+        """The store slots the launch of bootstrap node `wire` reads."""
+        buf, n = np.zeros(3, np.uint32), C.c_uint32()
+        _chk_circ(_capi.lib().tfhe_hip_circuit_operand_slots(self._native_handle(), int(wire), buf.ctypes.data_as(C.c_void_p),
+                                                             C.byref(n)), "operand_slots")
+        return [int(x) for x in buf[: n.value]]
+
     # -- execution -----------------------------------------------------------------------
     def run_dev(self, eng, inputs, stream=None):
-        """inputs: int32 CUDA tensor [n_inputs][B][n+1]; returns the wire store [n_wires][B][n+1]
-        (int32 CUDA tensor, rows of non-existent wires undefined).  One launch per level.
-        `eng`: an Engine, or a Pool -- then the wires live on the pool's home member (`pool.home`) and every level is
-        one `tfhe_hip_pool_batch_gates_mixed_dev` call: its gates x batch are cut over the members, the shards travel
-        by grouped RCCL send / receive and the level's results are back on the home GPU, in order, for the next gather."""
+        """inputs: int32 CUDA tensor [n_inputs][B][n+1]; returns every wire [n_wires][B][n+1] (int32 CUDA tensor) in
+        this circuit's wire numbering.  The native scheduler runs the whole circuit (`tfhe_hip_circuit_run_dev`) in a
+        store of its own slots, then `tfhe_hip_circuit_gather_dev` hands the wires back.
+        `eng`: an Engine, or a Pool -- then the store lives on the pool's home member (`pool.home`) and every level's
+        launches are pool calls cut over the members (`tfhe_hip_circuit_run_pool_dev`)."""
         import torch
 
         n_in, B, w = inputs.shape
         assert n_in == self.n_inputs
-        # the gathers, the temporaries' allocations and the engine's kernels must share ONE stream: make `stream`
-        # torch's current stream for the duration (a kernel on another stream would race the index_select that
-        # feeds it, and the caching allocator could hand a temporary to someone else while it is still in use)
+        h = self._native_handle()
+        lib = _capi.lib()
+        inputs = inputs.contiguous()
+        # allocations and kernels on ONE stream (the caching allocator hands a block back to that stream's later work)
+        with _on_stream(stream):
+            store = torch.empty((self.slots, B, w), dtype=torch.int32, device=inputs.device)
+            out = torch.empty((self.n_wires, B, w), dtype=torch.int32, device=inputs.device)
+            ow, n_out = self._all_wires.ctypes.data_as(C.c_void_p), self.n_wires
+            if isinstance(eng, E.Pool):
+                home = eng.home
+                sp = eng._stream_ptr(home, stream)
+                eng._chk(lib.tfhe_hip_circuit_run_pool_dev(eng._h, home, h, eng._tp(home, inputs), eng._tp(home, store), B, sp))
+                eng._chk(lib.tfhe_hip_circuit_gather_pool_dev(eng._h, home, h, eng._tp(home, store), B, ow, n_out,
+                                                              eng._tp(home, out), sp))
+            else:
+                sp = eng._stream_ptr(stream)
+                eng._chk(lib.tfhe_hip_circuit_run_dev(eng._ctx, h, eng._tp(inputs), eng._tp(store), B, sp))
+                eng._chk(lib.tfhe_hip_circuit_gather_dev(eng._ctx, h, eng._tp(store), B, ow, n_out, eng._tp(out), sp))
+        return out
+
+    def _run_dev_torch(self, eng, inputs, stream=None):
+        """The torch-scheduled path this module had before the native scheduler (gate-only circuits): per level two
+        index_select gathers, one batch_gates_mixed_dev launch and one index_copy_.  Kept for comparisons only."""
+        import torch
+
+        if len(self.gates) != len(self._nodes):
+            raise ValueError("_run_dev_torch runs gate-only circuits")
+        n_in, B, w = inputs.shape
+        assert n_in == self.n_inputs
         with _on_stream(stream):
             wires = torch.empty((self.n_wires, B, w), dtype=torch.int32, device=inputs.device)
             wires[:n_in] = inputs
@@ -120,8 +281,7 @@ class Circuit:
         return wires
 
     def _plan(self, device):
-        """Per-level operand / result wire indices and gate codes as device tensors, built once per
-        (device, circuit size): repeated runs of the same circuit upload nothing but their inputs."""
+        """Per-level operand / result wire indices and gate codes as device tensors (_run_dev_torch)."""
         import torch
 
         key = (str(device), len(self.gates))
@@ -137,27 +297,57 @@ class Circuit:
         return plan
 
     def run(self, eng, inputs) -> np.ndarray:
-        """Host convenience: inputs uint32 [n_inputs][B][n+1] -> all wires uint32 [n_wires][B][n+1].  `eng`: Engine or Pool."""
-        import torch
+        """Host convenience: inputs uint32 [n_inputs][B][n+1] -> all wires uint32 [n_wires][B][n+1].  `eng`: Engine or
+        Pool (`tfhe_hip_circuit_run` / `tfhe_hip_circuit_run_pool`: the store on the device, one copy in, one out)."""
+        inputs = np.ascontiguousarray(inputs, dtype=np.uint32)
+        n_in, B, w = inputs.shape
+        assert n_in == self.n_inputs
+        h = self._native_handle()
+        lib = _capi.lib()
+        out = np.empty((self.n_wires, B, w), np.uint32)
+        args = (h, inputs.ctypes.data_as(C.c_void_p), B, self._all_wires.ctypes.data_as(C.c_void_p), self.n_wires,
+                out.ctypes.data_as(C.c_void_p))
+        if isinstance(eng, E.Pool):
+            eng._chk(lib.tfhe_hip_circuit_run_pool(eng._h, *args))
+        else:
+            eng._chk(lib.tfhe_hip_circuit_run(eng._ctx, *args))
+        return out
 
-        dev = torch.device("cuda", eng.device)
-        t = torch.from_numpy(np.ascontiguousarray(inputs, dtype=np.uint32).view(np.int32)).to(dev)
-        with torch.cuda.device(dev):
-            wires = self.run_dev(eng, t)
-            if isinstance(eng, E.Pool):
-                eng.synchronize()
-            torch.cuda.synchronize()
-        return wires.cpu().numpy().view(np.uint32)
-
-    def run_reference(self, gate_fn, inputs) -> np.ndarray:
-        """Evaluate gate by gate with `gate_fn(op, a[B][n+1], b[B][n+1]) -> [B][n+1]`: the order
-        the reference's example executes it in (the tests plug their CPU checker in here)."""
+    def run_reference(self, gate_fn, inputs, mux_fn=None, pbs_fn=None) -> np.ndarray:
+        """Evaluate node by node in the order they were added (the order the reference's examples execute them; the
+        tests plug their CPU checker in here): `gate_fn(op, a[B][n+1], b[B][n+1]) -> [B][n+1]`,
+        `mux_fn(a, b, c) -> [B][n+1]`, `pbs_fn(testvec [2][N], prepared [B][n+1]) -> [B][n+1]`; linear nodes in numpy
+        (wrapping u32)."""
         inputs = np.ascontiguousarray(inputs, dtype=np.uint32)
         wires = np.zeros((self.n_wires,) + inputs.shape[1:], np.uint32)
         wires[: self.n_inputs] = inputs
-        for g in self.gates:
-            wires[g.out] = gate_fn(g.op, wires[g.a], wires[g.b])
+        for i, node in enumerate(self._nodes):
+            out, kind = self.n_inputs + i, node[0]
+            if kind == "gate":
+                wires[out] = gate_fn(node[1], wires[node[2]], wires[node[3]])
+            elif kind == "mux":
+                wires[out] = mux_fn(wires[node[1]], wires[node[2]], wires[node[3]])
+            elif kind == "pbs":
+                _, ca, a, cb, b, cc, lut = node
+                prep = _lin([(ca, wires[a])] + ([(cb, wires[b])] if cb else []), cc, wires.shape[1:])
+                wires[out] = pbs_fn(self._luts[lut].reshape(2, -1), prep)
+            else:
+                wires[out] = _lin([(c, wires[w]) for c, w in node[1]], node[2], wires.shape[1:])
         return wires
+
+
+def _lin(terms, cconst, shape) -> np.ndarray:
+    """sum coef * x (+ cconst on the body), wrapping u32."""
+    acc = np.zeros(shape, np.uint32)
+    for c, x in terms:
+        acc += np.uint32(c) * x
+    acc[..., -1] += np.uint32(cconst)
+    return acc
+
+
+def _chk_circ(rc: int, what: str) -> None:
+    if rc != _capi.OK:
+        raise _capi.TfheHipError(rc, f"tfhe_hip_circuit_{what}")
 
 
 def _on_stream(stream):

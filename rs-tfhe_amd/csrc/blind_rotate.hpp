@@ -213,6 +213,10 @@ struct BlindRotateArgs {
   const uint32_t *in_b;  // [count][n+1] or nullptr when cb == 0
   uint32_t ca, cb, cconst;
   const uint8_t *gate_codes;  // optional [count]: per-ciphertext tfhe_hip_gate overriding ca/cb/cconst
+  // optional [count]: ciphertext ct reads row idx_a[ct] of in_a (idx_b[ct] of in_b) instead of row ct -- a circuit
+  // level's operands gathered from the wire store inside the prologue (circuit.hpp); null = contiguous rows
+  const uint32_t *idx_a;
+  const uint32_t *idx_b;
   const uint32_t *testvec;  // [2][N] (per_ct_stride == 0) or [count][2][N]
   size_t per_ct_stride;     // in u32 elements: 0 or 2N
   const double2 *bsk;       // engine order
@@ -287,8 +291,8 @@ __global__ __launch_bounds__(64 * kBrWaves, 2) void k_blind_rotate(BlindRotateAr
     gcb = kGateCb[code];
     gcc = kGateCc[code];
   }
-  const uint32_t *pa = A.in_a + ct * (size_t)(n + 1);
-  const uint32_t *pb = (A.in_b && gcb) ? A.in_b + ct * (size_t)(n + 1) : nullptr;
+  const uint32_t *pa = A.in_a + (A.idx_a ? (size_t)A.idx_a[ct] : ct) * (size_t)(n + 1);
+  const uint32_t *pb = (A.in_b && gcb) ? A.in_b + (A.idx_b ? (size_t)A.idx_b[ct] : ct) * (size_t)(n + 1) : nullptr;
   for (int i = lane; i < n; i += 64) {
     uint32_t p = gca * pa[i];
     if (pb) p += gcb * pb[i];

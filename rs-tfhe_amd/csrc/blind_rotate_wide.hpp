@@ -70,8 +70,8 @@ __global__ __launch_bounds__(64 * kWide2Waves, 1) void k_blind_rotate_wide2(Blin
     gcb = kGateCb[code];
     gcc = kGateCc[code];
   }
-  const uint32_t *pa = A.in_a + ct * (size_t)(n + 1);
-  const uint32_t *pb = (A.in_b && gcb) ? A.in_b + ct * (size_t)(n + 1) : nullptr;
+  const uint32_t *pa = A.in_a + (A.idx_a ? (size_t)A.idx_a[ct] : ct) * (size_t)(n + 1);
+  const uint32_t *pb = (A.in_b && gcb) ? A.in_b + (A.idx_b ? (size_t)A.idx_b[ct] : ct) * (size_t)(n + 1) : nullptr;
   for (int i = tid; i < n; i += NT) {
     uint32_t p = gca * pa[i];
     if (pb) p += gcb * pb[i];
@@ -284,8 +284,8 @@ __global__ __launch_bounds__(64 * kPairWaves, 1) void k_blind_rotate_pair(BlindR
       gcb = kGateCb[code];
       gcc = kGateCc[code];
     }
-    const uint32_t *pa = A.in_a + ct * (size_t)(n + 1);
-    const uint32_t *pb = (A.in_b && gcb) ? A.in_b + ct * (size_t)(n + 1) : nullptr;
+    const uint32_t *pa = A.in_a + (A.idx_a ? (size_t)A.idx_a[ct] : ct) * (size_t)(n + 1);
+    const uint32_t *pb = (A.in_b && gcb) ? A.in_b + (A.idx_b ? (size_t)A.idx_b[ct] : ct) * (size_t)(n + 1) : nullptr;
     for (int i = tid; i < n; i += NT) {
       uint32_t p = gca * pa[i];
       if (pb) p += gcb * pb[i];

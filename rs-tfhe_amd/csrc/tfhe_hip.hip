@@ -8,10 +8,14 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
+#include <array>
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <map>
+#include <memory>
+#include <tuple>
 #include <atomic>
 #include <condition_variable>
 #include <mutex>
@@ -452,7 +456,8 @@ BrPlan plan_blind_rotate(const tfhe_hip_ctx *ctx, size_t count) {
 int launch_blind_rotate(tfhe_hip_ctx *ctx, hipStream_t s, const uint32_t *in_a, const uint32_t *in_b,
                         GatePrep gp, const uint32_t *testvec, int per_ct, size_t count,
                         uint32_t *out_trlwe, uint32_t *out_lv1, uint32_t *out_ext2,
-                        const uint8_t *gate_codes = nullptr) {
+                        const uint8_t *gate_codes = nullptr, const uint32_t *idx_a = nullptr,
+                        const uint32_t *idx_b = nullptr) {
   if (count == 0) return TFHE_HIP_OK;
   if (count > 0x7FFFFFFFull) return fail(ctx, TFHE_HIP_EINVAL, "count too large");
   BlindRotateArgs A;
@@ -462,6 +467,8 @@ int launch_blind_rotate(tfhe_hip_ctx *ctx, hipStream_t s, const uint32_t *in_a, 
   A.cb = gp.cb;
   A.cconst = gp.cconst;
   A.gate_codes = gate_codes;
+  A.idx_a = idx_a;  // row indices (circuit levels): the operand bases stay, the indices are sliced per part
+  A.idx_b = idx_b;
   A.testvec = testvec ? testvec : ctx->K->d_testvec;
   A.per_ct_stride = (testvec && per_ct) ? (size_t)2 * kN : 0;
   A.bsk = ctx->K->d_bsk;
@@ -483,8 +490,10 @@ int launch_blind_rotate(tfhe_hip_ctx *ctx, hipStream_t s, const uint32_t *in_a, 
   // ciphertexts [done, done + m) of this call as a launch of their own
   auto part = [&](size_t done, size_t m) {
     BlindRotateArgs S = A;
-    S.in_a = A.in_a + done * (size_t)(ctx->P.n + 1);
-    if (A.in_b) S.in_b = A.in_b + done * (size_t)(ctx->P.n + 1);
+    if (A.idx_a) S.idx_a = A.idx_a + done;
+    else S.in_a = A.in_a + done * (size_t)(ctx->P.n + 1);
+    if (A.idx_b) S.idx_b = A.idx_b + done;
+    else if (A.in_b) S.in_b = A.in_b + done * (size_t)(ctx->P.n + 1);
     if (A.gate_codes) S.gate_codes = A.gate_codes + done;
     S.testvec = A.testvec + done * A.per_ct_stride;
     if (A.out_trlwe) S.out_trlwe = A.out_trlwe + done * (size_t)(2 * kN);
@@ -2312,3 +2321,4 @@ int tfhe_hip_synchronize(tfhe_hip_ctx *ctx) {
 
 }  // extern "C"
 #include "pool.hpp"
+#include "circuit.hpp"

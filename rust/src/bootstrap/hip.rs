@@ -397,3 +397,130 @@ impl Bootstrap for HipLutBootstrap {
     }
     fn name(&self) -> &str { "lut-hip-gfx950" }
 }
+
+// ---- circuits: a gate / mux / LUT DAG scheduled by the library (include/tfhe_hip.h, tfhe_hip_circuit_*) ----------
+#[repr(C)]
+pub struct TfheHipCircuit { _private: [u8; 0] }
+
+extern "C" {   // include/tfhe_hip.h, the tfhe_hip_circuit_* family: built on the host, levelised, run one launch per kind and level
+    fn tfhe_hip_circuit_create(n_inputs: u32, out: *mut *mut TfheHipCircuit) -> c_int;
+    fn tfhe_hip_circuit_destroy(circ: *mut TfheHipCircuit);
+    fn tfhe_hip_circuit_add_gate(circ: *mut TfheHipCircuit, gate: c_int, a: u32, b: u32, wire: *mut u32) -> c_int;
+    fn tfhe_hip_circuit_add_mux(circ: *mut TfheHipCircuit, a: u32, b: u32, c: u32, wire: *mut u32) -> c_int;
+    fn tfhe_hip_circuit_add_lut(circ: *mut TfheHipCircuit, testvec: *const u32, lut: *mut u32) -> c_int;
+    fn tfhe_hip_circuit_add_pbs(circ: *mut TfheHipCircuit, ca: u32, a: u32, cb: u32, b: u32, cconst: u32, lut: u32,
+                                wire: *mut u32) -> c_int;
+    fn tfhe_hip_circuit_add_lincomb(circ: *mut TfheHipCircuit, coefs: *const u32, wires: *const u32, n_terms: usize,
+                                    cconst: u32, wire: *mut u32) -> c_int;
+    fn tfhe_hip_circuit_add_not(circ: *mut TfheHipCircuit, a: u32, wire: *mut u32) -> c_int;
+    fn tfhe_hip_circuit_add_constant(circ: *mut TfheHipCircuit, value: c_int, wire: *mut u32) -> c_int;
+    fn tfhe_hip_circuit_compile(circ: *mut TfheHipCircuit) -> c_int;
+    fn tfhe_hip_circuit_run_pool(pool: *mut TfheHipPool, circ: *mut TfheHipCircuit, inputs: *const u32, batch: usize,
+                                 out_wires: *const u32, n_out: usize, out: *mut u32) -> c_int;
+}
+
+/// A circuit over wires (0 .. n_inputs are its inputs; every node added returns its output wire), run by the library:
+/// the reference evaluates examples/add_two_numbers.rs:11-50 one gate at a time, here every level of the DAG -- all of
+/// its gates times the whole batch -- is one launch per kind, with the wires kept on the GPU between levels.
+pub struct HipCircuit { h: *mut TfheHipCircuit, n_inputs: usize }
+unsafe impl Send for HipCircuit {}   // the library serialises construction, compilation, and runs of one circuit on one pool (key views included)
+unsafe impl Sync for HipCircuit {}
+
+impl HipCircuit {
+    pub fn new(n_inputs: usize) -> Self {
+        let mut h = std::ptr::null_mut();
+        assert_eq!(unsafe { tfhe_hip_circuit_create(n_inputs as u32, &mut h) }, 0, "tfhe_hip_circuit_create failed");
+        HipCircuit { h, n_inputs }
+    }
+    fn node(rc: c_int, wire: u32) -> u32 {
+        assert_eq!(rc, 0, "tfhe_hip_circuit: bad wire, gate code or lut id, or the circuit has already run");
+        wire
+    }
+    /// Gates::<gate> (src/gates.rs:54-150), one of NAND .. COPY
+    pub fn gate(&mut self, gate: c_int, a: u32, b: u32) -> u32 {
+        let mut w = 0u32;
+        let rc = unsafe { tfhe_hip_circuit_add_gate(self.h, gate, a, b, &mut w) };
+        Self::node(rc, w)
+    }
+    /// Gates::mux (src/gates.rs:157-183)
+    pub fn mux(&mut self, a: u32, b: u32, c: u32) -> u32 {
+        let mut w = 0u32;
+        let rc = unsafe { tfhe_hip_circuit_add_mux(self.h, a, b, c, &mut w) };
+        Self::node(rc, w)
+    }
+    /// a test vector for `pbs` (LookupTable::poly, src/lut/lookup_table.rs); returns its id
+    pub fn lut(&mut self, testvec: &trlwe::TRLWELv1) -> u32 {
+        let mut tv = Vec::with_capacity(2 * N);
+        tv.extend_from_slice(&testvec.a);
+        tv.extend_from_slice(&testvec.b);
+        let mut id = 0u32;
+        let rc = unsafe { tfhe_hip_circuit_add_lut(self.h, tv.as_ptr(), &mut id) };
+        Self::node(rc, id)
+    }
+    /// LutBootstrap::bootstrap_lut (src/bootstrap/lut.rs:79-99) of ca*a + cb*b + cconst
+    pub fn pbs(&mut self, ca: u32, a: u32, cb: u32, b: u32, cconst: u32, lut: u32) -> u32 {
+        let mut w = 0u32;
+        let rc = unsafe { tfhe_hip_circuit_add_pbs(self.h, ca, a, cb, b, cconst, lut, &mut w) };
+        Self::node(rc, w)
+    }
+    /// sum coef * wire + cconst (TLWE `+` / `-`): no bootstrap
+    pub fn lincomb(&mut self, terms: &[(u32, u32)], cconst: u32) -> u32 {
+        let coefs: Vec<u32> = terms.iter().map(|t| t.0).collect();
+        let wires: Vec<u32> = terms.iter().map(|t| t.1).collect();
+        let mut w = 0u32;
+        let rc = unsafe { tfhe_hip_circuit_add_lincomb(self.h, coefs.as_ptr(), wires.as_ptr(), terms.len(), cconst, &mut w) };
+        Self::node(rc, w)
+    }
+    /// Gates::not (src/gates.rs:202-204)
+    pub fn not(&mut self, a: u32) -> u32 {
+        let mut w = 0u32;
+        let rc = unsafe { tfhe_hip_circuit_add_not(self.h, a, &mut w) };
+        Self::node(rc, w)
+    }
+    /// Gates::constant (src/gates.rs:212-219)
+    pub fn constant(&mut self, value: bool) -> u32 {
+        let mut w = 0u32;
+        let rc = unsafe { tfhe_hip_circuit_add_constant(self.h, value as c_int, &mut w) };
+        Self::node(rc, w)
+    }
+    /// examples/add_two_numbers.rs:11-29 -> (sum, carry)
+    pub fn full_adder(&mut self, a: u32, b: u32, c: u32) -> (u32, u32) {
+        let a_xor_b = self.gate(XOR, a, b);
+        let a_and_b = self.gate(AND, a, b);
+        let a_xor_b_and_c = self.gate(AND, a_xor_b, c);
+        let sum = self.gate(XOR, a_xor_b, c);
+        let carry = self.gate(OR, a_and_b, a_xor_b_and_c);
+        (sum, carry)
+    }
+    /// examples/add_two_numbers.rs:31-50 -> (sum bits, carry out)
+    pub fn add(&mut self, a: &[u32], b: &[u32], cin: u32) -> (Vec<u32>, u32) {
+        assert_eq!(a.len(), b.len(), "Cannot add two numbers with different number of bits!");
+        let mut result = Vec::with_capacity(a.len());
+        let mut carry = cin;
+        for (x, y) in a.iter().zip(b.iter()) {
+            let (s, c) = self.full_adder(*x, *y, carry);
+            result.push(s);
+            carry = c;
+        }
+        (result, carry)
+    }
+    /// inputs[i][j]: input wire i of batch element j -> result[k][j]: wire out_wires[k] of batch element j, on `engine`'s
+    /// GPUs under `cloud_key` (tfhe_hip_circuit_run_pool)
+    pub fn run(&self, engine: &HipEngine, inputs: &[Vec<Ciphertext>], out_wires: &[u32], cloud_key: &CloudKey) -> Vec<Vec<Ciphertext>> {
+        assert_eq!(inputs.len(), self.n_inputs, "one batch per circuit input");
+        let batch = inputs[0].len();
+        let mut flat = Vec::with_capacity(inputs.len() * batch * W);
+        for row in inputs {
+            assert_eq!(row.len(), batch, "inputs differ in batch size");
+            for c in row { flat.extend_from_slice(&c.p); }
+        }
+        let mut out = vec![0u32; out_wires.len() * batch * W];
+        let (h, outp) = (self.h, out.as_mut_ptr());
+        engine.with_key(cloud_key, |v| (unsafe { tfhe_hip_circuit_run_pool(v, h, flat.as_ptr(), batch, out_wires.as_ptr(), out_wires.len(), outp) }, ()));
+        out.chunks_exact(batch * W).map(HipEngine::unflatten).collect()
+    }
+}
+
+impl Drop for HipCircuit {
+    fn drop(&mut self) { unsafe { tfhe_hip_circuit_destroy(self.h) } }
+}
