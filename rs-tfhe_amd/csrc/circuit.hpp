@@ -818,9 +818,9 @@ int tfhe_hip_circuit_run(tfhe_hip_ctx *ctx, tfhe_hip_circuit *circ, const uint32
     HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
     return TFHE_HIP_OK;
   }
-  CHK(ensure(ctx, ctx->h_out, n_out * row));
-  CHK(circ_gather_locked(ctx, circ, p.get(), wires, out_wires, n_out, (uint32_t *)ctx->h_out.p, ctx->stream));
-  return to_host(ctx, out, ctx->h_out, n_out * row);
+  CHK(ensure(ctx, ctx->out.dev, n_out * row));
+  CHK(circ_gather_locked(ctx, circ, p.get(), wires, out_wires, n_out, (uint32_t *)ctx->out.dev.p, ctx->stream));
+  return to_host(ctx, out, ctx->out, n_out * row);
 }
 
 int tfhe_hip_circuit_run_pool_dev(tfhe_hip_pool *pool, int home, tfhe_hip_circuit *circ, const uint32_t *inputs,
@@ -861,9 +861,9 @@ int tfhe_hip_circuit_run_pool(tfhe_hip_pool *pool, tfhe_hip_circuit *circ, const
     HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
     return TFHE_HIP_OK;
   }
-  CHK(ensure(ctx, ctx->h_out, n_out * row));
-  CHK(circ_gather_locked(ctx, circ, p.get(), wires, out_wires, n_out, (uint32_t *)ctx->h_out.p, ctx->stream));
-  return to_host(ctx, out, ctx->h_out, n_out * row);
+  CHK(ensure(ctx, ctx->out.dev, n_out * row));
+  CHK(circ_gather_locked(ctx, circ, p.get(), wires, out_wires, n_out, (uint32_t *)ctx->out.dev.p, ctx->stream));
+  return to_host(ctx, out, ctx->out, n_out * row);
 }
 
 }  // extern "C"

@@ -72,8 +72,9 @@ enum CombClass { CB_GATES = 0, CB_MUX = 1, CB_MUX_NAIVE = 2, CB_ROTATE = 3 };  /
 
 // a lane's staging pair for one operand: host arena (packed by the leader; pinned, or ordinary memory where pinned memory
 // is not to be had -- the copies work from either, only slower) -> device buffer
-int comb_arena(tfhe_hip_ctx *x, PinBuf &pin, DevBuf &dev, size_t bytes) {
-  CHK(ensure(x, dev, bytes));
+int comb_arena(tfhe_hip_ctx *x, Staging &st, size_t bytes) {
+  PinBuf &pin = st.pin;
+  CHK(ensure(x, st.dev, bytes));
   if (bytes <= pin.cap) return TFHE_HIP_OK;
   if (!pin.heap && !g_comb_force_heap && ensure_pinned(x, pin, bytes) == TFHE_HIP_OK) return TFHE_HIP_OK;
   if (pin.p && pin.heap) free(pin.p);
@@ -119,24 +120,24 @@ int comb_run_group(tfhe_hip_ctx *x, KeyState *key, const std::vector<CombReq *> 
         if (r->lin_cb) need_b = true;
       }
   // pack: every request's rows behind one another
-  CHK(comb_arena(x, x->p_a, x->h_a, m * wb));
-  if (need_b) CHK(comb_arena(x, x->p_b, x->h_b, m * wb));
-  if (need_c) CHK(comb_arena(x, x->p_c, x->h_c, m * wb));
-  if (has_tv) CHK(comb_arena(x, x->p_tv, x->h_tv, m * (size_t)2 * kN * 4));
-  if (!mux && !uniform) CHK(comb_arena(x, x->p_idx, x->h_idx, m));
-  CHK(comb_arena(x, x->p_out, x->h_out, m * owb));
+  CHK(comb_arena(x, x->a, m * wb));
+  if (need_b) CHK(comb_arena(x, x->b, m * wb));
+  if (need_c) CHK(comb_arena(x, x->c, m * wb));
+  if (has_tv) CHK(comb_arena(x, x->tv, m * (size_t)2 * kN * 4));
+  if (!mux && !uniform) CHK(comb_arena(x, x->idx, m));
+  CHK(comb_arena(x, x->out, m * owb));
   {
     size_t at = 0;
     for (const CombReq *r : g) {
-      memcpy((uint32_t *)x->p_a.p + at * w, r->a, r->count * wb);
-      if (need_b && r->b) memcpy((uint32_t *)x->p_b.p + at * w, r->b, r->count * wb);
-      if (need_c) memcpy((uint32_t *)x->p_c.p + at * w, r->c, r->count * wb);
+      memcpy((uint32_t *)x->a.pin.p + at * w, r->a, r->count * wb);
+      if (need_b && r->b) memcpy((uint32_t *)x->b.pin.p + at * w, r->b, r->count * wb);
+      if (need_c) memcpy((uint32_t *)x->c.pin.p + at * w, r->c, r->count * wb);
       if (has_tv)
         for (size_t i = 0; i < r->count; ++i)
-          memcpy((uint32_t *)x->p_tv.p + (at + i) * (size_t)2 * kN, r->testvec + (r->per_ct ? i * (size_t)2 * kN : 0), (size_t)2 * kN * 4);
+          memcpy((uint32_t *)x->tv.pin.p + (at + i) * (size_t)2 * kN, r->testvec + (r->per_ct ? i * (size_t)2 * kN : 0), (size_t)2 * kN * 4);
       if (!mux && !uniform) {
-        if (r->codes) memcpy((uint8_t *)x->p_idx.p + at, r->codes, r->count);
-        else memset((uint8_t *)x->p_idx.p + at, r->gate, r->count);
+        if (r->codes) memcpy((uint8_t *)x->idx.pin.p + at, r->codes, r->count);
+        else memset((uint8_t *)x->idx.pin.p + at, r->gate, r->count);
       }
       at += r->count;
     }
@@ -144,21 +145,21 @@ int comb_run_group(tfhe_hip_ctx *x, KeyState *key, const std::vector<CombReq *> 
   const auto t_packed = std::chrono::steady_clock::now();
   // gate groups read each operand row once, in the blind rotation's prologue: with zero_copy_in the kernel takes the
   // pinned arena as it is (no copy to wait for ahead of the launch); mux reads its operands in three launches: copied
-  const bool zc = zero_copy_in && !mux && !any_lin && !x->p_a.heap && !x->p_b.heap && !x->p_tv.heap;
-  const uint32_t *da = (const uint32_t *)x->h_a.p, *db = need_b ? (const uint32_t *)x->h_b.p : nullptr;
-  const uint32_t *dtv0 = has_tv ? (const uint32_t *)x->h_tv.p : nullptr;
+  const bool zc = zero_copy_in && !mux && !any_lin && !x->a.pin.heap && !x->b.pin.heap && !x->tv.pin.heap;
+  const uint32_t *da = (const uint32_t *)x->a.dev.p, *db = need_b ? (const uint32_t *)x->b.dev.p : nullptr;
+  const uint32_t *dtv0 = has_tv ? (const uint32_t *)x->tv.dev.p : nullptr;
   if (zc) {
-    da = pinned_view((const uint32_t *)x->p_a.p, m * wb);
-    if (need_b) db = pinned_view((const uint32_t *)x->p_b.p, m * wb);
-    if (has_tv) dtv0 = pinned_view((const uint32_t *)x->p_tv.p, m * (size_t)2 * kN * 4);
+    da = pinned_view((const uint32_t *)x->a.pin.p, m * wb);
+    if (need_b) db = pinned_view((const uint32_t *)x->b.pin.p, m * wb);
+    if (has_tv) dtv0 = pinned_view((const uint32_t *)x->tv.pin.p, m * (size_t)2 * kN * 4);
     if (!da || (need_b && !db) || (has_tv && !dtv0)) return fail(x, TFHE_HIP_EHIP, "merged-call arena is not device-addressable");
   } else {
-    HIPCHK(x, hipMemcpyAsync(x->h_a.p, x->p_a.p, m * wb, hipMemcpyHostToDevice, s));
-    if (need_b) HIPCHK(x, hipMemcpyAsync(x->h_b.p, x->p_b.p, m * wb, hipMemcpyHostToDevice, s));
-    if (need_c) HIPCHK(x, hipMemcpyAsync(x->h_c.p, x->p_c.p, m * wb, hipMemcpyHostToDevice, s));
-    if (has_tv) HIPCHK(x, hipMemcpyAsync(x->h_tv.p, x->p_tv.p, m * (size_t)2 * kN * 4, hipMemcpyHostToDevice, s));
+    HIPCHK(x, hipMemcpyAsync(x->a.dev.p, x->a.pin.p, m * wb, hipMemcpyHostToDevice, s));
+    if (need_b) HIPCHK(x, hipMemcpyAsync(x->b.dev.p, x->b.pin.p, m * wb, hipMemcpyHostToDevice, s));
+    if (need_c) HIPCHK(x, hipMemcpyAsync(x->c.dev.p, x->c.pin.p, m * wb, hipMemcpyHostToDevice, s));
+    if (has_tv) HIPCHK(x, hipMemcpyAsync(x->tv.dev.p, x->tv.pin.p, m * (size_t)2 * kN * 4, hipMemcpyHostToDevice, s));
   }
-  if (!mux && !uniform) HIPCHK(x, hipMemcpyAsync(x->h_idx.p, x->p_idx.p, m, hipMemcpyHostToDevice, s));
+  if (!mux && !uniform) HIPCHK(x, hipMemcpyAsync(x->idx.dev.p, x->idx.pin.p, m, hipMemcpyHostToDevice, s));
   if (any_lin) {  // one streaming launch per run of requests with the same coefficients, in place in the packed rows
     size_t at = 0;
     for (size_t i = 0; i < g.size();) {
@@ -167,22 +168,22 @@ int comb_run_group(tfhe_hip_ctx *x, KeyState *key, const std::vector<CombReq *> 
       if (r->lin) {
         while (j < g.size() && g[j]->lin && g[j]->lin_ca == r->lin_ca && g[j]->lin_cb == r->lin_cb && g[j]->lin_cconst == r->lin_cconst) rows += g[j++]->count;
         const size_t total = rows * w;
-        uint32_t *pa = (uint32_t *)x->h_a.p + at * w;
+        uint32_t *pa = (uint32_t *)x->a.dev.p + at * w;
         hipLaunchKernelGGL(k_tlwe_lincomb, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, r->lin_ca, pa, r->lin_cb,
-                           r->lin_cb ? (const uint32_t *)x->h_b.p + at * w : nullptr, r->lin_cconst, pa, (uint32_t)w, total);
+                           r->lin_cb ? (const uint32_t *)x->b.dev.p + at * w : nullptr, r->lin_cconst, pa, (uint32_t)w, total);
         HIPCHK(x, hipGetLastError());
       }
       at += rows;
       i = j;
     }
   }
-  uint32_t *dout = (uint32_t *)x->h_out.p;
+  uint32_t *dout = (uint32_t *)x->out.dev.p;
   if (mux) {
-    CHK(mux_dev(x, r0.cls == CB_MUX_NAIVE, da, db, (const uint32_t *)x->h_c.p, dout, m, s));
+    CHK(mux_dev(x, r0.cls == CB_MUX_NAIVE, da, db, (const uint32_t *)x->c.dev.p, dout, m, s));
   } else {
     GatePrep gp{1u, need_b ? 1u : 0u, 0u};  // mixed: placeholders, the kernel reads the codes (cb != 0 keeps in_b attached)
     if (uniform) gate_prep(gate0, gp);
-    const uint8_t *dcodes = uniform ? nullptr : (const uint8_t *)x->h_idx.p;
+    const uint8_t *dcodes = uniform ? nullptr : (const uint8_t *)x->idx.dev.p;
     const uint32_t *dtv = dtv0;
     if (rotate) {
       CHK(launch_blind_rotate(x, s, da, nullptr, gp, dtv, 1, m, dout, nullptr, nullptr, nullptr));
@@ -195,13 +196,13 @@ int comb_run_group(tfhe_hip_ctx *x, KeyState *key, const std::vector<CombReq *> 
       CHK(launch_blind_rotate(x, s, da, db, gp, dtv, 1, m, nullptr, nullptr, dout, dcodes));
     }
   }
-  HIPCHK(x, hipMemcpyAsync(x->p_out.p, x->h_out.p, m * owb, hipMemcpyDeviceToHost, s));
+  HIPCHK(x, hipMemcpyAsync(x->out.pin.p, x->out.dev.p, m * owb, hipMemcpyDeviceToHost, s));
   HIPCHK(x, hipStreamSynchronize(s));
   const auto t_synced = std::chrono::steady_clock::now();
   {
     size_t at = 0;
     for (CombReq *r : g) {
-      memcpy(r->out, (const uint32_t *)x->p_out.p + at * ow, r->count * owb);
+      memcpy(r->out, (const uint32_t *)x->out.pin.p + at * ow, r->count * owb);
       at += r->count;
     }
   }
@@ -257,9 +258,9 @@ int comb_make_lane(tfhe_hip_ctx *base, Combiner &C, int li, std::string &why) {
   {
     const size_t rows = C.max_count.load(std::memory_order_relaxed) ? C.max_count.load(std::memory_order_relaxed) : 1;
     const size_t bytes = rows * ((size_t)x->P.n + 1) * 4;
-    (void)comb_arena(x, x->p_a, x->h_a, bytes);
-    (void)comb_arena(x, x->p_b, x->h_b, bytes);
-    (void)comb_arena(x, x->p_out, x->h_out, bytes);
+    (void)comb_arena(x, x->a, bytes);
+    (void)comb_arena(x, x->b, bytes);
+    (void)comb_arena(x, x->out, bytes);
     (void)ensure(x, x->lv1, lv1_rows(rows) * (size_t)(kN + 1) * 4);
   }
   C.lane_ctx[li] = x;

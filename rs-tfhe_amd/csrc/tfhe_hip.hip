@@ -127,6 +127,11 @@ struct PinBuf {  // pinned host arena (hipHostMalloc)
   size_t cap = 0;
   bool heap = false;  // front-end lanes only: pinned memory was not to be had, this is ordinary memory (copies still work)
 };
+struct Staging {  // a host-API staging buffer on the device and the pinned arena behind it
+  DevBuf dev;
+  PinBuf pin;
+  bool pool_pinned = false;  // pool members route large pageable copies of this slot through `pin`
+};
 
 }  // namespace
 
@@ -154,9 +159,10 @@ struct tfhe_hip_ctx {
   int views = 0;                 // live key views of this context
   bool dying = false;            // destroyed while views were alive: the last view to go frees the context
   double2 *d_tw = nullptr;
-  DevBuf lv1, u1, u2, h_a, h_b, h_c, h_out, h_tv, h_idx, ks_out, ks_dig;  // scratch / host-API staging (ks_dig: key-switch digit bytes)
-  PinBuf p_a, p_b, p_c, p_out;  // pinned staging arenas behind h_a / h_b / h_c / h_out (pool members, combiner lanes)
-  PinBuf p_tv, p_idx;           // ... behind h_tv / h_idx (combiner lanes only)
+  DevBuf lv1, u1, u2, ks_out, ks_dig;  // scratch (ks_dig: key-switch digit bytes)
+  // host-API staging: a / b / c / out also stage through their arenas on pool members (to_dev / to_host);
+  // the arenas of tv / idx serve the combiner lanes only
+  Staging a{{}, {}, true}, b{{}, {}, true}, c{{}, {}, true}, out{{}, {}, true}, tv, idx;
   Combiner *comb = nullptr;      // base contexts: concurrent small host-pointer calls are merged into shared launches (combine.hpp)
   bool is_lane = false;          // this context is a combiner lane of another one (never handed to a caller)
   bool stage_pinned = false;     // set by a pool with several members: stage pageable operands through the arenas
@@ -974,28 +980,28 @@ int ensure_pinned(tfhe_hip_ctx *ctx, PinBuf &b, size_t bytes) {
   return TFHE_HIP_OK;
 }
 
-int to_dev(tfhe_hip_ctx *ctx, DevBuf &b, const void *src, size_t bytes) {
-  CHK(ensure(ctx, b, bytes));
-  if (ctx->stage_pinned && bytes >= (1u << 20)) {
-    PinBuf *pin = &b == &ctx->h_a ? &ctx->p_a : &b == &ctx->h_b ? &ctx->p_b : &b == &ctx->h_c ? &ctx->p_c : nullptr;
-    if (pin && ensure_pinned(ctx, *pin, bytes) == TFHE_HIP_OK) {
-      memcpy(pin->p, src, bytes);
-      HIPCHK(ctx, hipMemcpyAsync(b.p, pin->p, bytes, hipMemcpyHostToDevice, ctx->stream));
-      return TFHE_HIP_OK;
-    }
+bool via_pin(tfhe_hip_ctx *ctx, Staging &s, size_t bytes) {
+  return ctx->stage_pinned && s.pool_pinned && bytes >= (1u << 20) && ensure_pinned(ctx, s.pin, bytes) == TFHE_HIP_OK;
+}
+
+int to_dev(tfhe_hip_ctx *ctx, Staging &s, const void *src, size_t bytes) {
+  CHK(ensure(ctx, s.dev, bytes));
+  if (via_pin(ctx, s, bytes)) {
+    memcpy(s.pin.p, src, bytes);
+    src = s.pin.p;
   }
-  HIPCHK(ctx, hipMemcpyAsync(b.p, src, bytes, hipMemcpyHostToDevice, ctx->stream));
+  HIPCHK(ctx, hipMemcpyAsync(s.dev.p, src, bytes, hipMemcpyHostToDevice, ctx->stream));
   return TFHE_HIP_OK;
 }
 
-int to_host(tfhe_hip_ctx *ctx, void *dst, const DevBuf &b, size_t bytes) {
-  if (ctx->stage_pinned && bytes >= (1u << 20) && &b == &ctx->h_out && ensure_pinned(ctx, ctx->p_out, bytes) == TFHE_HIP_OK) {
-    HIPCHK(ctx, hipMemcpyAsync(ctx->p_out.p, b.p, bytes, hipMemcpyDeviceToHost, ctx->stream));
+int to_host(tfhe_hip_ctx *ctx, void *dst, Staging &s, size_t bytes) {
+  if (via_pin(ctx, s, bytes)) {
+    HIPCHK(ctx, hipMemcpyAsync(s.pin.p, s.dev.p, bytes, hipMemcpyDeviceToHost, ctx->stream));
     HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-    memcpy(dst, ctx->p_out.p, bytes);
+    memcpy(dst, s.pin.p, bytes);
     return TFHE_HIP_OK;
   }
-  HIPCHK(ctx, hipMemcpyAsync(dst, b.p, bytes, hipMemcpyDeviceToHost, ctx->stream));
+  HIPCHK(ctx, hipMemcpyAsync(dst, s.dev.p, bytes, hipMemcpyDeviceToHost, ctx->stream));
   HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
   return TFHE_HIP_OK;
 }
@@ -1042,6 +1048,45 @@ T *pinned_view(T *p, size_t bytes) {
   return (T *)d;
 }
 
+// The direct path, after a call's own checks.  One operand: `bytes` at `host`, staged through `slot`; a null `host`
+// is an operand this call does not use, which reaches the launch as nullptr.
+struct HostIn {
+  const void *host;
+  size_t bytes;
+  Staging *slot;
+};
+// With `zero_copy` (gate, gates_mixed, bootstrap, mux) and every operand and the output pinned, the launch runs on
+// them in place (see pinned_view) and the stream is synchronised.  Otherwise each operand is staged with to_dev in
+// list order, the launch writes ctx->out, and the result returns through to_host.  launch(in, out) gets the device
+// view of each operand in list order and of the output.
+template <size_t N, class Launch>
+int host_call(tfhe_hip_ctx *ctx, bool zero_copy, const HostIn (&in)[N], void *out, size_t out_bytes, Launch &&launch) {
+  const void *d[N] = {};
+  if (zero_copy) {  // all operands pinned: no staging
+    bool pinned = true;
+    for (size_t i = 0; i < N && pinned; ++i)
+      if (in[i].host) pinned = (d[i] = pinned_view(in[i].host, in[i].bytes)) != nullptr;
+    if (void *dout = pinned ? pinned_view(out, out_bytes) : nullptr) {
+      CHK(launch(d, dout));
+      HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+      return TFHE_HIP_OK;
+    }
+  }
+  for (size_t i = 0; i < N; ++i) {
+    d[i] = nullptr;
+    if (!in[i].host) continue;
+    CHK(to_dev(ctx, *in[i].slot, in[i].host, in[i].bytes));
+    d[i] = in[i].slot->dev.p;
+  }
+  CHK(ensure(ctx, ctx->out.dev, out_bytes));
+  CHK(launch(d, ctx->out.dev.p));
+  return to_host(ctx, out, ctx->out, out_bytes);
+}
+const uint32_t *u32(const void *p) { return (const uint32_t *)p; }
+int launched(tfhe_hip_ctx *ctx) {  // status of the kernel launch just made
+  HIPCHK(ctx, hipGetLastError());
+  return TFHE_HIP_OK;
+}
 }  // namespace
 
 #include "combine.hpp"
@@ -1326,12 +1371,14 @@ void tfhe_hip_ctx_destroy(tfhe_hip_ctx *ctx) {
     (void)hipEventDestroy(p.first);
     (void)hipEventDestroy(p.second);
   }
-  DevBuf *bufs[] = {&ctx->lv1, &ctx->u1, &ctx->u2, &ctx->h_a, &ctx->h_b, &ctx->h_c, &ctx->h_out, &ctx->h_tv, &ctx->h_idx, &ctx->ks_out, &ctx->ks_dig};
-  for (DevBuf *b : bufs)
+  Staging *stage[] = {&ctx->a, &ctx->b, &ctx->c, &ctx->out, &ctx->tv, &ctx->idx};
+  for (DevBuf *b : {&ctx->lv1, &ctx->u1, &ctx->u2, &ctx->ks_out, &ctx->ks_dig})
     if (b->p) (void)hipFree(b->p);
+  for (Staging *s : stage)
+    if (s->dev.p) (void)hipFree(s->dev.p);
   free_key(ctx->own);
-  for (PinBuf *b : {&ctx->p_a, &ctx->p_b, &ctx->p_c, &ctx->p_out, &ctx->p_tv, &ctx->p_idx})
-    if (b->p) b->heap ? free(b->p) : (void)hipHostFree(b->p);
+  for (Staging *s : stage)
+    if (s->pin.p) s->pin.heap ? free(s->pin.p) : (void)hipHostFree(s->pin.p);
   if (ctx->d_tw) (void)hipFree(ctx->d_tw);
   if (ctx->stream) (void)hipStreamDestroy(ctx->stream);
   delete ctx;
@@ -1446,22 +1493,22 @@ int gen_cloud_key_locked(tfhe_hip_ctx *ctx, const uint32_t *key_lv0, const uint3
   struct Wipe {
     tfhe_hip_ctx *c;
     ~Wipe() {
-      for (DevBuf *b : {&c->h_a, &c->h_b, &c->h_c, &c->h_idx})
+      for (DevBuf *b : {&c->a.dev, &c->b.dev, &c->c.dev, &c->idx.dev})
         if (b->p) (void)hipMemsetAsync(b->p, 0, b->cap < 65536 ? b->cap : 65536, c->stream);
       (void)hipStreamSynchronize(c->stream);
     }
   } wipe{ctx};
-  CHK(to_dev(ctx, ctx->h_a, key_lv0, (size_t)P.n * 4));
-  CHK(to_dev(ctx, ctx->h_b, key_lv1, (size_t)kN * 4));
-  CHK(ensure(ctx, ctx->h_c, (size_t)kN2 * sizeof(double2)));
-  const uint32_t *d_k0 = (const uint32_t *)ctx->h_a.p, *d_k1 = (const uint32_t *)ctx->h_b.p;
-  double2 *d_spec = (double2 *)ctx->h_c.p;
+  CHK(to_dev(ctx, ctx->a, key_lv0, (size_t)P.n * 4));
+  CHK(to_dev(ctx, ctx->b, key_lv1, (size_t)kN * 4));
+  CHK(ensure(ctx, ctx->c.dev, (size_t)kN2 * sizeof(double2)));
+  const uint32_t *d_k0 = (const uint32_t *)ctx->a.dev.p, *d_k1 = (const uint32_t *)ctx->b.dev.p;
+  double2 *d_spec = (double2 *)ctx->c.dev.p;
   hipLaunchKernelGGL(k_key_spectrum, dim3(1), dim3(64), kStageLdsBytes, ctx->stream, d_k1, ctx->d_tw, d_spec);
   HIPCHK(ctx, hipGetLastError());
   // the generator key travels in a device buffer (not in kernel-argument memory) and is wiped with the other secrets
-  CHK(ensure(ctx, ctx->h_idx, sizeof(ChaChaKey)));
-  HIPCHK(ctx, hipMemcpy(ctx->h_idx.p, &rk, sizeof(ChaChaKey), hipMemcpyHostToDevice));  // synchronous: rk is the caller's stack
-  const ChaChaKey *d_rk = (const ChaChaKey *)ctx->h_idx.p;
+  CHK(ensure(ctx, ctx->idx.dev, sizeof(ChaChaKey)));
+  HIPCHK(ctx, hipMemcpy(ctx->idx.dev.p, &rk, sizeof(ChaChaKey), hipMemcpyHostToDevice));  // synchronous: rk is the caller's stack
+  const ChaChaKey *d_rk = (const ChaChaKey *)ctx->idx.dev.p;
   const dim3 bgrid((unsigned)(P.n * 2 * P.l));
   switch (P.l) {
     case 1: hipLaunchKernelGGL(k_gen_bsk<1>, bgrid, dim3(64), kStageLdsBytes, ctx->stream, d_k0, d_spec, ctx->d_tw, ctx->K->d_bsk, P.bgbit, alpha_bsk, d_rk, key_scale(ctx->fast_round)); break;
@@ -1554,17 +1601,17 @@ int tfhe_hip_export_cloud_key(tfhe_hip_ctx *ctx, double *bsk, uint32_t *ksk, uin
   const int base = 1 << P.basebit;
   if (bsk) {
     const size_t polys = (size_t)P.n * 2 * P.l * 2;
-    CHK(ensure(ctx, ctx->h_out, polys * kN * sizeof(double)));
-    hipLaunchKernelGGL(k_bsk_export, dim3((unsigned)polys), dim3(512), 0, ctx->stream, ctx->K->d_bsk, (double *)ctx->h_out.p, polys, 1.0 / key_scale(ctx->fast_round));
+    CHK(ensure(ctx, ctx->out.dev, polys * kN * sizeof(double)));
+    hipLaunchKernelGGL(k_bsk_export, dim3((unsigned)polys), dim3(512), 0, ctx->stream, ctx->K->d_bsk, (double *)ctx->out.dev.p, polys, 1.0 / key_scale(ctx->fast_round));
     HIPCHK(ctx, hipGetLastError());
-    CHK(to_host(ctx, bsk, ctx->h_out, polys * kN * sizeof(double)));
+    CHK(to_host(ctx, bsk, ctx->out, polys * kN * sizeof(double)));
   }
   if (ksk) {
     const size_t rows = (size_t)kN * P.t * base;
-    CHK(ensure(ctx, ctx->h_out, rows * (size_t)(P.n + 1) * 4));
-    hipLaunchKernelGGL(k_ksk_export, dim3((unsigned)rows), dim3(256), 0, ctx->stream, ctx->K->d_ksk, (uint32_t *)ctx->h_out.p, P.n, rows);
+    CHK(ensure(ctx, ctx->out.dev, rows * (size_t)(P.n + 1) * 4));
+    hipLaunchKernelGGL(k_ksk_export, dim3((unsigned)rows), dim3(256), 0, ctx->stream, ctx->K->d_ksk, (uint32_t *)ctx->out.dev.p, P.n, rows);
     HIPCHK(ctx, hipGetLastError());
-    CHK(to_host(ctx, ksk, ctx->h_out, rows * (size_t)(P.n + 1) * 4));
+    CHK(to_host(ctx, ksk, ctx->out, rows * (size_t)(P.n + 1) * 4));
   }
   if (decomp_offset) *decomp_offset = ctx->K->offset;
   if (testvec) {
@@ -1753,7 +1800,20 @@ int comb_mux_call(tfhe_hip_ctx *ctx, int naive, const uint32_t *a, const uint32_
   r.count = count;
   return comb_submit(base, r);
 }
+int comb_rotate_call(tfhe_hip_ctx *ctx, const uint32_t *in, const uint32_t *testvec, uint32_t *out_trlwe, size_t count) {
+  tfhe_hip_ctx *base = ctx->parent ? ctx->parent : ctx;
+  if (!ctx->own.key_loaded) COMB_FAIL(base, TFHE_HIP_ENOKEY, "cloud key not loaded");
+  CombReq r;
+  r.key = &ctx->own;
+  r.cls = CB_ROTATE;
+  r.a = in;
+  r.testvec = testvec;
+  r.out = out_trlwe;
+  r.count = count;
+  return comb_submit(base, r);
+}
 #undef COMB_FAIL
+
 }  // namespace
 
 int tfhe_hip_batch_gate(tfhe_hip_ctx *ctx, int gate, const uint32_t *a, const uint32_t *b,
@@ -1767,20 +1827,9 @@ int tfhe_hip_batch_gate(tfhe_hip_ctx *ctx, int gate, const uint32_t *a, const ui
   if (!gate_prep(gate, gp)) return fail(ctx, TFHE_HIP_EINVAL, "unknown gate");
   if (!a || !out || (gp.cb && !b)) return fail(ctx, TFHE_HIP_EINVAL, "null pointer");
   const size_t bytes = count * (size_t)(ctx->P.n + 1) * 4;
-  {  // all operands pinned: no staging (see pinned_view)
-    const uint32_t *da = pinned_view(a, bytes), *db = gp.cb ? pinned_view(b, bytes) : nullptr;
-    uint32_t *dout = pinned_view(out, bytes);
-    if (da && dout && (!gp.cb || db)) {
-      CHK(gate_dev(ctx, gate, da, db, dout, count, ctx->stream));
-      HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-      return TFHE_HIP_OK;
-    }
-  }
-  CHK(to_dev(ctx, ctx->h_a, a, bytes));
-  if (gp.cb) CHK(to_dev(ctx, ctx->h_b, b, bytes));
-  CHK(ensure(ctx, ctx->h_out, bytes));
-  CHK(gate_dev(ctx, gate, (uint32_t *)ctx->h_a.p, (uint32_t *)ctx->h_b.p, (uint32_t *)ctx->h_out.p, count, ctx->stream));
-  return to_host(ctx, out, ctx->h_out, bytes);
+  return host_call(ctx, true, {{a, bytes, &ctx->a}, {gp.cb ? b : nullptr, bytes, &ctx->b}}, out, bytes, [&](const void *const *d, void *o) {
+    return gate_dev(ctx, gate, u32(d[0]), u32(d[1]), (uint32_t *)o, count, ctx->stream);
+  });
 }
 
 int tfhe_hip_batch_gates_mixed(tfhe_hip_ctx *ctx, const uint8_t *gates, const uint32_t *a, const uint32_t *b,
@@ -1794,22 +1843,10 @@ int tfhe_hip_batch_gates_mixed(tfhe_hip_ctx *ctx, const uint8_t *gates, const ui
   for (size_t i = 0; i < count; ++i)
     if (gates[i] > TFHE_HIP_COPY) return fail(ctx, TFHE_HIP_EINVAL, "unknown gate");
   const size_t bytes = count * (size_t)(ctx->P.n + 1) * 4;
-  CHK(to_dev(ctx, ctx->h_idx, gates, count));  // one byte per ciphertext: always staged
-  {
-    const uint32_t *da = pinned_view(a, bytes), *db = pinned_view(b, bytes);
-    uint32_t *dout = pinned_view(out, bytes);
-    if (da && db && dout) {
-      CHK(gates_mixed_dev(ctx, (const uint8_t *)ctx->h_idx.p, da, db, dout, count, ctx->stream));
-      HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-      return TFHE_HIP_OK;
-    }
-  }
-  CHK(to_dev(ctx, ctx->h_a, a, bytes));
-  CHK(to_dev(ctx, ctx->h_b, b, bytes));
-  CHK(ensure(ctx, ctx->h_out, bytes));
-  CHK(gates_mixed_dev(ctx, (const uint8_t *)ctx->h_idx.p, (uint32_t *)ctx->h_a.p, (uint32_t *)ctx->h_b.p,
-                      (uint32_t *)ctx->h_out.p, count, ctx->stream));
-  return to_host(ctx, out, ctx->h_out, bytes);
+  CHK(to_dev(ctx, ctx->idx, gates, count));  // one byte per ciphertext: always staged
+  return host_call(ctx, true, {{a, bytes, &ctx->a}, {b, bytes, &ctx->b}}, out, bytes, [&](const void *const *d, void *o) {
+    return gates_mixed_dev(ctx, (const uint8_t *)ctx->idx.dev.p, u32(d[0]), u32(d[1]), (uint32_t *)o, count, ctx->stream);
+  });
 }
 
 int tfhe_hip_batch_gates_mixed_nks(tfhe_hip_ctx *ctx, const uint8_t *gates, const uint32_t *a, const uint32_t *b,
@@ -1823,13 +1860,10 @@ int tfhe_hip_batch_gates_mixed_nks(tfhe_hip_ctx *ctx, const uint8_t *gates, cons
   for (size_t i = 0; i < count; ++i)
     if (gates[i] > TFHE_HIP_COPY) return fail(ctx, TFHE_HIP_EINVAL, "unknown gate");
   const size_t bytes = count * (size_t)(ctx->P.n + 1) * 4;
-  CHK(to_dev(ctx, ctx->h_a, a, bytes));
-  CHK(to_dev(ctx, ctx->h_b, b, bytes));
-  CHK(to_dev(ctx, ctx->h_idx, gates, count));
-  CHK(ensure(ctx, ctx->h_out, bytes));
-  CHK(gates_mixed_nks_dev(ctx, (const uint8_t *)ctx->h_idx.p, (const uint32_t *)ctx->h_a.p, (const uint32_t *)ctx->h_b.p,
-                          (uint32_t *)ctx->h_out.p, count, ctx->stream));
-  return to_host(ctx, out, ctx->h_out, bytes);
+  const HostIn in[] = {{a, bytes, &ctx->a}, {b, bytes, &ctx->b}, {gates, count, &ctx->idx}};
+  return host_call(ctx, false, in, out, bytes, [&](const void *const *d, void *o) {
+    return gates_mixed_nks_dev(ctx, (const uint8_t *)d[2], u32(d[0]), u32(d[1]), (uint32_t *)o, count, ctx->stream);
+  });
 }
 
 int tfhe_hip_batch_bootstrap(tfhe_hip_ctx *ctx, const uint32_t *in, const uint32_t *testvec,
@@ -1842,27 +1876,16 @@ int tfhe_hip_batch_bootstrap(tfhe_hip_ctx *ctx, const uint32_t *in, const uint32
   if (count == 0) return TFHE_HIP_OK;
   if (!in || !out) return fail(ctx, TFHE_HIP_EINVAL, "null pointer");
   const size_t bytes = count * (size_t)(ctx->P.n + 1) * 4;
-  const uint32_t *d_tv = nullptr;
-  if (testvec) {
-    d_tv = pinned_view(testvec, (per_ct ? count : 1) * (size_t)2 * kN * 4);
-    if (!d_tv) {
-      CHK(to_dev(ctx, ctx->h_tv, testvec, (per_ct ? count : 1) * (size_t)2 * kN * 4));
-      d_tv = (const uint32_t *)ctx->h_tv.p;
-    }
+  // the test vector is zero-copied on its own when it is pinned, whatever the ciphertexts are
+  const size_t tv_bytes = (per_ct ? count : 1) * (size_t)2 * kN * 4;
+  const uint32_t *d_tv = pinned_view(testvec, tv_bytes);
+  if (testvec && !d_tv) {
+    CHK(to_dev(ctx, ctx->tv, testvec, tv_bytes));
+    d_tv = u32(ctx->tv.dev.p);
   }
-  {
-    const uint32_t *din = pinned_view(in, bytes);
-    uint32_t *dout = pinned_view(out, bytes);
-    if (din && dout) {
-      CHK(bootstrap_dev(ctx, din, d_tv, per_ct, keyswitch, dout, count, ctx->stream));
-      HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-      return TFHE_HIP_OK;
-    }
-  }
-  CHK(to_dev(ctx, ctx->h_a, in, bytes));
-  CHK(ensure(ctx, ctx->h_out, bytes));
-  CHK(bootstrap_dev(ctx, (uint32_t *)ctx->h_a.p, d_tv, per_ct, keyswitch, (uint32_t *)ctx->h_out.p, count, ctx->stream));
-  return to_host(ctx, out, ctx->h_out, bytes);
+  return host_call(ctx, true, {{in, bytes, &ctx->a}}, out, bytes, [&](const void *const *d, void *o) {
+    return bootstrap_dev(ctx, u32(d[0]), d_tv, per_ct, keyswitch, (uint32_t *)o, count, ctx->stream);
+  });
 }
 
 int tfhe_hip_batch_tlwe_lincomb(tfhe_hip_ctx *ctx, uint32_t ca, const uint32_t *a, uint32_t cb,
@@ -1872,12 +1895,9 @@ int tfhe_hip_batch_tlwe_lincomb(tfhe_hip_ctx *ctx, uint32_t ca, const uint32_t *
   if (count == 0) return TFHE_HIP_OK;
   if (!a || !out || (cb && !b)) return fail(ctx, TFHE_HIP_EINVAL, "null pointer");
   const size_t bytes = count * (size_t)(ctx->P.n + 1) * 4;
-  CHK(to_dev(ctx, ctx->h_a, a, bytes));
-  if (cb) CHK(to_dev(ctx, ctx->h_b, b, bytes));
-  CHK(ensure(ctx, ctx->h_out, bytes));
-  CHK(lincomb_dev(ctx, GatePrep{ca, cb, cconst}, (const uint32_t *)ctx->h_a.p, (const uint32_t *)ctx->h_b.p,
-                  (uint32_t *)ctx->h_out.p, count, ctx->stream));
-  return to_host(ctx, out, ctx->h_out, bytes);
+  return host_call(ctx, false, {{a, bytes, &ctx->a}, {cb ? b : nullptr, bytes, &ctx->b}}, out, bytes, [&](const void *const *d, void *o) {
+    return lincomb_dev(ctx, GatePrep{ca, cb, cconst}, u32(d[0]), u32(d[1]), (uint32_t *)o, count, ctx->stream);
+  });
 }
 
 int tfhe_hip_batch_lincomb_bootstrap(tfhe_hip_ctx *ctx, uint32_t ca, const uint32_t *a, uint32_t cb,
@@ -1895,55 +1915,29 @@ int tfhe_hip_batch_lincomb_bootstrap(tfhe_hip_ctx *ctx, uint32_t ca, const uint3
   if (count == 0) return TFHE_HIP_OK;
   if (!a || !out || (cb && !b)) return fail(ctx, TFHE_HIP_EINVAL, "null pointer");
   const size_t bytes = count * (size_t)(ctx->P.n + 1) * 4;
-  CHK(to_dev(ctx, ctx->h_a, a, bytes));
-  if (cb) CHK(to_dev(ctx, ctx->h_b, b, bytes));
-  const uint32_t *d_tv = nullptr;
-  if (testvec) {
-    CHK(to_dev(ctx, ctx->h_tv, testvec, (per_ct ? count : 1) * (size_t)2 * kN * 4));
-    d_tv = (const uint32_t *)ctx->h_tv.p;
-  }
-  CHK(ensure(ctx, ctx->h_out, bytes));
-  CHK(lincomb_bootstrap_dev(ctx, GatePrep{ca, cb, cconst}, (const uint32_t *)ctx->h_a.p,
-                            cb ? (const uint32_t *)ctx->h_b.p : nullptr, d_tv, per_ct, keyswitch,
-                            (uint32_t *)ctx->h_out.p, count, ctx->stream));
-  return to_host(ctx, out, ctx->h_out, bytes);
+  const HostIn in[] = {{a, bytes, &ctx->a}, {cb ? b : nullptr, bytes, &ctx->b},
+                       {testvec, (per_ct ? count : 1) * (size_t)2 * kN * 4, &ctx->tv}};
+  return host_call(ctx, false, in, out, bytes, [&](const void *const *d, void *o) {
+    return lincomb_bootstrap_dev(ctx, GatePrep{ca, cb, cconst}, u32(d[0]), u32(d[1]), u32(d[2]), per_ct, keyswitch,
+                                 (uint32_t *)o, count, ctx->stream);
+  });
 }
 
 int tfhe_hip_batch_blind_rotate(tfhe_hip_ctx *ctx, const uint32_t *in, const uint32_t *testvec,
                                 uint32_t *out_trlwe, size_t count) {
   if (!ctx) return TFHE_HIP_EINVAL;
-  if (comb_takes(ctx, count) && in && out_trlwe) {  // small call: merged with the other threads' (combine.hpp)
-    tfhe_hip_ctx *base = ctx->parent ? ctx->parent : ctx;
-    if (!ctx->own.key_loaded) {
-      err_slot(base->id) = "cloud key not loaded";
-      return TFHE_HIP_ENOKEY;
-    }
-    CombReq r;
-    r.key = &ctx->own;
-    r.cls = CB_ROTATE;
-    r.a = in;
-    r.testvec = testvec;
-    r.out = out_trlwe;
-    r.count = count;
-    return comb_submit(base, r);
-  }
+  if (comb_takes(ctx, count) && in && out_trlwe)  // small call: merged with the other threads' (combine.hpp)
+    return comb_rotate_call(ctx, in, testvec, out_trlwe, count);
   ENTER(ctx);
   CHK(need_key(ctx));
   if (count == 0) return TFHE_HIP_OK;
   if (!in || !out_trlwe) return fail(ctx, TFHE_HIP_EINVAL, "null pointer");
-  CHK(to_dev(ctx, ctx->h_a, in, count * (size_t)(ctx->P.n + 1) * 4));
-  const uint32_t *d_tv = nullptr;
-  if (testvec) {
-    CHK(to_dev(ctx, ctx->h_tv, testvec, (size_t)2 * kN * 4));
-    d_tv = (const uint32_t *)ctx->h_tv.p;
-  }
-  const size_t obytes = count * (size_t)2 * kN * 4;
-  CHK(ensure(ctx, ctx->h_out, obytes));
-  GatePrep gp;
-  gate_prep(TFHE_HIP_COPY, gp);
-  CHK(launch_blind_rotate(ctx, ctx->stream, (uint32_t *)ctx->h_a.p, nullptr, gp, d_tv, 0, count,
-                          (uint32_t *)ctx->h_out.p, nullptr, nullptr));
-  return to_host(ctx, out_trlwe, ctx->h_out, obytes);
+  const HostIn ops[] = {{in, count * (size_t)(ctx->P.n + 1) * 4, &ctx->a}, {testvec, (size_t)2 * kN * 4, &ctx->tv}};
+  return host_call(ctx, false, ops, out_trlwe, count * (size_t)2 * kN * 4, [&](const void *const *d, void *o) {
+    GatePrep gp;
+    gate_prep(TFHE_HIP_COPY, gp);
+    return launch_blind_rotate(ctx, ctx->stream, u32(d[0]), nullptr, gp, u32(d[1]), 0, count, (uint32_t *)o, nullptr, nullptr);
+  });
 }
 
 int tfhe_hip_batch_mux(tfhe_hip_ctx *ctx, int naive, const uint32_t *a, const uint32_t *b,
@@ -1955,22 +1949,9 @@ int tfhe_hip_batch_mux(tfhe_hip_ctx *ctx, int naive, const uint32_t *a, const ui
   if (count == 0) return TFHE_HIP_OK;
   if (!a || !b || !c || !out) return fail(ctx, TFHE_HIP_EINVAL, "null pointer");
   const size_t bytes = count * (size_t)(ctx->P.n + 1) * 4;
-  {
-    const uint32_t *da = pinned_view(a, bytes), *db = pinned_view(b, bytes), *dc = pinned_view(c, bytes);
-    uint32_t *dout = pinned_view(out, bytes);
-    if (da && db && dc && dout) {
-      CHK(mux_dev(ctx, naive, da, db, dc, dout, count, ctx->stream));
-      HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-      return TFHE_HIP_OK;
-    }
-  }
-  CHK(to_dev(ctx, ctx->h_a, a, bytes));
-  CHK(to_dev(ctx, ctx->h_b, b, bytes));
-  CHK(to_dev(ctx, ctx->h_c, c, bytes));
-  CHK(ensure(ctx, ctx->h_out, bytes));
-  CHK(mux_dev(ctx, naive, (uint32_t *)ctx->h_a.p, (uint32_t *)ctx->h_b.p, (uint32_t *)ctx->h_c.p,
-              (uint32_t *)ctx->h_out.p, count, ctx->stream));
-  return to_host(ctx, out, ctx->h_out, bytes);
+  return host_call(ctx, true, {{a, bytes, &ctx->a}, {b, bytes, &ctx->b}, {c, bytes, &ctx->c}}, out, bytes, [&](const void *const *d, void *o) {
+    return mux_dev(ctx, naive, u32(d[0]), u32(d[1]), u32(d[2]), (uint32_t *)o, count, ctx->stream);
+  });
 }
 
 // ---- single stages --------------------------------------------------------------
@@ -1985,18 +1966,12 @@ int tfhe_hip_batch_external_product(tfhe_hip_ctx *ctx, const uint32_t *trlwe_in,
   for (size_t i = 0; i < count; ++i)
     if (bsk_index[i] < 0 || bsk_index[i] >= ctx->P.n) return fail(ctx, TFHE_HIP_EINVAL, "bsk_index out of range");
   const size_t bytes = count * (size_t)2 * kN * 4;
-  CHK(to_dev(ctx, ctx->h_a, trlwe_in, bytes));
-  CHK(to_dev(ctx, ctx->h_idx, bsk_index, count * 4));
-  CHK(ensure(ctx, ctx->h_out, bytes));
-  dim3 grid((unsigned)count), block(64);
-  const uint32_t *in = (const uint32_t *)ctx->h_a.p;
-  const int32_t *idx = (const int32_t *)ctx->h_idx.p;
-  uint32_t *o = (uint32_t *)ctx->h_out.p;
   const uint32_t bsk_bytes = (uint32_t)((size_t)ctx->P.n * 2 * ctx->P.l * 2 * kN2 * 16);
-  hipLaunchKernelGGL(ep_kernel(ctx), grid, block, kStageLdsBytes, ctx->stream, in, idx, ctx->K->d_bsk, bsk_bytes, ctx->d_tw,
-                     ctx->P.bgbit, ctx->K->offset, o);
-  HIPCHK(ctx, hipGetLastError());
-  return to_host(ctx, trlwe_out, ctx->h_out, bytes);
+  return host_call(ctx, false, {{trlwe_in, bytes, &ctx->a}, {bsk_index, count * 4, &ctx->idx}}, trlwe_out, bytes, [&](const void *const *d, void *o) {
+    hipLaunchKernelGGL(ep_kernel(ctx), dim3((unsigned)count), dim3(64), kStageLdsBytes, ctx->stream, u32(d[0]), (const int32_t *)d[1],
+                       ctx->K->d_bsk, bsk_bytes, ctx->d_tw, ctx->P.bgbit, ctx->K->offset, (uint32_t *)o);
+    return launched(ctx);
+  });
 }
 
 int tfhe_hip_batch_sample_extract(tfhe_hip_ctx *ctx, const uint32_t *trlwe, int k, uint32_t *out, size_t count) {
@@ -2005,13 +1980,10 @@ int tfhe_hip_batch_sample_extract(tfhe_hip_ctx *ctx, const uint32_t *trlwe, int 
   if (k < 0 || k >= kN) return fail(ctx, TFHE_HIP_EINVAL, "extraction index out of range");
   if (count == 0) return TFHE_HIP_OK;
   if (!trlwe || !out) return fail(ctx, TFHE_HIP_EINVAL, "null pointer");
-  CHK(to_dev(ctx, ctx->h_a, trlwe, count * (size_t)2 * kN * 4));
-  const size_t obytes = count * (size_t)(kN + 1) * 4;
-  CHK(ensure(ctx, ctx->h_out, obytes));
-  hipLaunchKernelGGL(k_sample_extract, dim3((unsigned)count), dim3(256), 0, ctx->stream,
-                     (const uint32_t *)ctx->h_a.p, k, (uint32_t *)ctx->h_out.p, count);
-  HIPCHK(ctx, hipGetLastError());
-  return to_host(ctx, out, ctx->h_out, obytes);
+  return host_call(ctx, false, {{trlwe, count * (size_t)2 * kN * 4, &ctx->a}}, out, count * (size_t)(kN + 1) * 4, [&](const void *const *d, void *o) {
+    hipLaunchKernelGGL(k_sample_extract, dim3((unsigned)count), dim3(256), 0, ctx->stream, u32(d[0]), k, (uint32_t *)o, count);
+    return launched(ctx);
+  });
 }
 
 int tfhe_hip_batch_identity_key_switch(tfhe_hip_ctx *ctx, const uint32_t *tlwe_lv1, uint32_t *out, size_t count) {
@@ -2020,12 +1992,11 @@ int tfhe_hip_batch_identity_key_switch(tfhe_hip_ctx *ctx, const uint32_t *tlwe_l
   CHK(need_key(ctx));
   if (count == 0) return TFHE_HIP_OK;
   if (!tlwe_lv1 || !out) return fail(ctx, TFHE_HIP_EINVAL, "null pointer");
-  CHK(ensure(ctx, ctx->h_a, lv1_rows(count) * (size_t)(kN + 1) * 4));  // whole 256-row groups readable (k_key_switch_mfma)
-  CHK(to_dev(ctx, ctx->h_a, tlwe_lv1, count * (size_t)(kN + 1) * 4));
+  CHK(ensure(ctx, ctx->a.dev, lv1_rows(count) * (size_t)(kN + 1) * 4));  // whole 256-row groups readable (k_key_switch_mfma)
   const size_t obytes = count * (size_t)(ctx->P.n + 1) * 4;
-  CHK(ensure(ctx, ctx->h_out, obytes));
-  CHK(launch_key_switch(ctx, ctx->stream, (const uint32_t *)ctx->h_a.p, (uint32_t *)ctx->h_out.p, count));
-  return to_host(ctx, out, ctx->h_out, obytes);
+  return host_call(ctx, false, {{tlwe_lv1, count * (size_t)(kN + 1) * 4, &ctx->a}}, out, obytes, [&](const void *const *d, void *o) {
+    return launch_key_switch(ctx, ctx->stream, u32(d[0]), (uint32_t *)o, count);
+  });
 }
 
 // ---- proxy re-encryption (src/proxy_reenc.rs; feature `proxy-reenc` of the reference) -------------------------------
@@ -2083,10 +2054,9 @@ int tfhe_hip_batch_reencrypt(tfhe_hip_ctx *ctx, const uint32_t *in, uint32_t *ou
   if (count == 0) return TFHE_HIP_OK;
   if (!in || !out) return fail(ctx, TFHE_HIP_EINVAL, "null pointer");
   const size_t bytes = count * (size_t)(ctx->P.n + 1) * 4;
-  CHK(to_dev(ctx, ctx->h_a, in, bytes));
-  CHK(ensure(ctx, ctx->h_out, bytes));
-  CHK(reencrypt_dev(ctx, (const uint32_t *)ctx->h_a.p, (uint32_t *)ctx->h_out.p, count, ctx->stream));
-  return to_host(ctx, out, ctx->h_out, bytes);
+  return host_call(ctx, false, {{in, bytes, &ctx->a}}, out, bytes, [&](const void *const *d, void *o) {
+    return reencrypt_dev(ctx, u32(d[0]), (uint32_t *)o, count, ctx->stream);
+  });
 }
 
 int tfhe_hip_batch_ifft(tfhe_hip_ctx *ctx, double *res, const uint32_t *src, size_t count) {
@@ -2094,12 +2064,10 @@ int tfhe_hip_batch_ifft(tfhe_hip_ctx *ctx, double *res, const uint32_t *src, siz
   ENTER(ctx);
   if (count == 0) return TFHE_HIP_OK;
   if (!res || !src) return fail(ctx, TFHE_HIP_EINVAL, "null pointer");
-  CHK(to_dev(ctx, ctx->h_a, src, count * (size_t)kN * 4));
-  CHK(ensure(ctx, ctx->h_out, count * (size_t)kN * 8));
-  hipLaunchKernelGGL(k_ifft, dim3((unsigned)count), dim3(64), kStageLdsBytes, ctx->stream,
-                     (const uint32_t *)ctx->h_a.p, ctx->d_tw, (double *)ctx->h_out.p);
-  HIPCHK(ctx, hipGetLastError());
-  return to_host(ctx, res, ctx->h_out, count * (size_t)kN * 8);
+  return host_call(ctx, false, {{src, count * (size_t)kN * 4, &ctx->a}}, res, count * (size_t)kN * 8, [&](const void *const *d, void *o) {
+    hipLaunchKernelGGL(k_ifft, dim3((unsigned)count), dim3(64), kStageLdsBytes, ctx->stream, u32(d[0]), ctx->d_tw, (double *)o);
+    return launched(ctx);
+  });
 }
 
 int tfhe_hip_batch_fft(tfhe_hip_ctx *ctx, uint32_t *res, const double *src, size_t count) {
@@ -2107,12 +2075,10 @@ int tfhe_hip_batch_fft(tfhe_hip_ctx *ctx, uint32_t *res, const double *src, size
   ENTER(ctx);
   if (count == 0) return TFHE_HIP_OK;
   if (!res || !src) return fail(ctx, TFHE_HIP_EINVAL, "null pointer");
-  CHK(to_dev(ctx, ctx->h_a, src, count * (size_t)kN * 8));
-  CHK(ensure(ctx, ctx->h_out, count * (size_t)kN * 4));
-  hipLaunchKernelGGL(k_fft, dim3((unsigned)count), dim3(64), kStageLdsBytes, ctx->stream,
-                     (const double *)ctx->h_a.p, ctx->d_tw, (uint32_t *)ctx->h_out.p);
-  HIPCHK(ctx, hipGetLastError());
-  return to_host(ctx, res, ctx->h_out, count * (size_t)kN * 4);
+  return host_call(ctx, false, {{src, count * (size_t)kN * 8, &ctx->a}}, res, count * (size_t)kN * 4, [&](const void *const *d, void *o) {
+    hipLaunchKernelGGL(k_fft, dim3((unsigned)count), dim3(64), kStageLdsBytes, ctx->stream, (const double *)d[0], ctx->d_tw, (uint32_t *)o);
+    return launched(ctx);
+  });
 }
 
 int tfhe_hip_batch_poly_mul(tfhe_hip_ctx *ctx, uint32_t *res, const uint32_t *a, const uint32_t *b, size_t count) {
@@ -2121,14 +2087,10 @@ int tfhe_hip_batch_poly_mul(tfhe_hip_ctx *ctx, uint32_t *res, const uint32_t *a,
   if (count == 0) return TFHE_HIP_OK;
   if (!res || !a || !b) return fail(ctx, TFHE_HIP_EINVAL, "null pointer");
   const size_t bytes = count * (size_t)kN * 4;
-  CHK(to_dev(ctx, ctx->h_a, a, bytes));
-  CHK(to_dev(ctx, ctx->h_b, b, bytes));
-  CHK(ensure(ctx, ctx->h_out, bytes));
-  hipLaunchKernelGGL(k_poly_mul, dim3((unsigned)count), dim3(64), kStageLdsBytes, ctx->stream,
-                     (const uint32_t *)ctx->h_a.p, (const uint32_t *)ctx->h_b.p, ctx->d_tw,
-                     (uint32_t *)ctx->h_out.p);
-  HIPCHK(ctx, hipGetLastError());
-  return to_host(ctx, res, ctx->h_out, bytes);
+  return host_call(ctx, false, {{a, bytes, &ctx->a}, {b, bytes, &ctx->b}}, res, bytes, [&](const void *const *d, void *o) {
+    hipLaunchKernelGGL(k_poly_mul, dim3((unsigned)count), dim3(64), kStageLdsBytes, ctx->stream, u32(d[0]), u32(d[1]), ctx->d_tw, (uint32_t *)o);
+    return launched(ctx);
+  });
 }
 
 // ---- measurement ---------------------------------------------------------------
