@@ -604,6 +604,20 @@ class Generator {  // generator.rs:15-259
   LookupTable generate_lookup_table_custom(const std::function<size_t(size_t)> &f, size_t message_modulus, double scale) const {  // :205-222
     return Generator(message_modulus, scale).generate_lookup_table(f);
   }
+  // k = fs.size() in {1, 2, 4, 8} functions in one table (PBS-manyLUT, tfhe_hip_batch_lincomb_bootstrap_many): position r
+  // of message x's box holds encode(fs[r % k](x)); needs N / (2m) % k == 0.  k = 1 is generate_lookup_table's table.
+  LookupTable generate_many_lookup_table(const std::vector<std::function<size_t(size_t)>> &fs) const {
+    const size_t k = fs.size(), m = encoder_.message_modulus, size = N;
+    if (k != 1 && k != 2 && k != 4 && k != 8) throw std::invalid_argument("generate_many_lookup_table: 1, 2, 4 or 8 functions");
+    if (k == 1) return generate_lookup_table(fs[0]);
+    if (size % (2 * m) || (size / (2 * m)) % k) throw std::invalid_argument("generate_many_lookup_table: N / (2m) % k != 0");
+    std::vector<Torus> raw(size, 0);
+    for (size_t x = 0; x < m; ++x) {
+      const size_t start = div_round(x * size, m), end = std::min(div_round((x + 1) * size, m), size);
+      for (size_t i = start; i < end; ++i) raw[i] = encoder_.encode(fs[(i - start) % k](x));
+    }
+    return rotate(raw);
+  }
   size_t mod_switch(Torus x) const {  // :235-238: (x / u32::MAX * size).round() % size
     const double scaled = (double)x / 4294967295.0 * (double)N;
     return (size_t)std::floor(scaled + 0.5) % (size_t)N;
@@ -612,12 +626,17 @@ class Generator {  // generator.rs:15-259
  private:
   LookupTable assemble(const std::function<Torus(size_t)> &value) const {
     const size_t m = encoder_.message_modulus, size = N;
-    std::vector<Torus> raw(size, 0), rot(size, 0);
+    std::vector<Torus> raw(size, 0);
     for (size_t x = 0; x < m; ++x) {
       size_t start = div_round(x * size, m), end = div_round((x + 1) * size, m);
       Torus y = value(x);
       for (size_t i = start; i < end && i < size; ++i) raw[i] = y;
     }
+    return rotate(raw);
+  }
+  LookupTable rotate(const std::vector<Torus> &raw) const {  // the half-box rotation and negacyclic negation
+    const size_t m = encoder_.message_modulus, size = N;
+    std::vector<Torus> rot(size, 0);
     const size_t offset = div_round(size, 2 * m);
     for (size_t i = 0; i < size; ++i) rot[i] = raw[(i + offset) % size];
     for (size_t i = size - offset; i < size; ++i) rot[i] = 0u - rot[i];  // wrapping_neg
@@ -674,6 +693,24 @@ class LutBootstrap : public HipBootstrap {
   Ciphertext bootstrap_lut(const Ciphertext &ct_in, const lut::LookupTable &lut, const CloudKey &ck) const {  // :79-99
     static_assert(sizeof(TRLWELv1) == 2 * N * sizeof(Torus), "TRLWELv1 must be a||b contiguous");
     return run(ct_in, &lut.poly, 1, ck);
+  }
+  // k functions packed in `lut` (lut::Generator::generate_many_lookup_table) from one blind rotation: result [j] is
+  // function j (tfhe_hip_batch_lincomb_bootstrap_many)
+  std::vector<Ciphertext> bootstrap_many_lut(const Ciphertext &ct_in, const lut::LookupTable &lut, int k,
+                                             const CloudKey &ck) const {
+    if (ct_in.n() != ck.params.n) throw std::runtime_error("ciphertext dimension mismatch");
+    std::vector<Torus> out((size_t)(k > 0 ? k : 1) * (ck.params.n + 1));
+    Engine::for_key(ck, device_).with_key(ck, [&](tfhe_hip_ctx *c) {
+      return tfhe_hip_batch_lincomb_bootstrap_many(c, 1, ct_in.p.data(), 0, nullptr, 0, lut.poly.a.data(), 0, k, 1,
+                                                   out.data(), 1);
+    });
+    std::vector<Ciphertext> res;
+    for (int j = 0; j < k; ++j) {
+      Ciphertext o(ck.params.n);
+      std::copy(out.begin() + (size_t)j * (ck.params.n + 1), out.begin() + (size_t)(j + 1) * (ck.params.n + 1), o.p.begin());
+      res.push_back(std::move(o));
+    }
+    return res;
   }
   Ciphertext bootstrap(const Ciphertext &ctxt, const CloudKey &ck) const override {  // lut.rs:108-111
     return bootstrap_func(ctxt, [](size_t x) { return x; }, 2, ck);
@@ -1002,6 +1039,13 @@ class Circuit {
   }
   Wire pbs(Torus ca, Wire a, Torus cb, Wire b, Torus cconst, uint32_t lut) {
     return add(tfhe_hip_circuit_add_pbs(h_, ca, a, cb, b, cconst, lut, &w_));
+  }
+  // many-LUT bootstrap: the k functions packed in `lut` from one blind rotation, k consecutive wires (function j at [j])
+  std::vector<Wire> pbs_many(Torus ca, Wire a, Torus cb, Wire b, Torus cconst, uint32_t lut, int k) {
+    std::vector<Wire> w((size_t)(k > 0 ? k : 1));
+    check(tfhe_hip_circuit_add_pbs_many(h_, ca, a, cb, b, cconst, lut, k, w.data()), "add_pbs_many");
+    w.resize((size_t)k);
+    return w;
   }
   Wire lincomb(const std::vector<std::pair<Torus, Wire>> &terms, Torus cconst = 0) {
     std::vector<uint32_t> c, w;

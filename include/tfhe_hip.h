@@ -272,6 +272,28 @@ int tfhe_hip_batch_lincomb_bootstrap_dev(tfhe_hip_ctx *ctx, uint32_t ca, const u
                                          int per_ct, int keyswitch, uint32_t *out, size_t count,
                                          void *stream);
 
+/* Many-LUT programmable bootstrap (Chillotti, Ligier, Orfila, Tap 2021, "PBS-manyLUT"; tfhe-rs
+ * apply_many_lookup_table): n_luts = k in {1, 2, 4, 8} functions of the same input from ONE blind
+ * rotation.  The input is prepared as in tfhe_hip_batch_lincomb_bootstrap; with d = log2 k the rotation
+ * amounts are rounded to multiples of k:  a~_i = ((p_i + 2^(20+d)) mod 2^32) >> (21+d) << d  and
+ * b~ = 2N - ((((u64)p_n + 2^(20+d)) >> (21+d)) << d)  (d = 0: the ordinary bootstrap, trgsw.rs:202-211).
+ * Output j < k is sample_extract_index(acc, j) then the key switch (keyswitch != 0), or
+ * sample_extract_index_2(acc, j) (keyswitch == 0; needs n <= N), trlwe.rs:106-136.  out is FUNCTION-MAJOR,
+ * [k][count][n+1]: out + j*count*(n+1) holds what a single-LUT call for function j would write.
+ * testvec ([2][N], or [count][2][N] with per_ct) is required and must pack the k functions
+ * (lut.Generator.generate_many_lookup_table / rs_tfhe::lut::Generator::generate_many_lookup_table:
+ * position r of message x's box holds f_(r mod k)(x)).  Rounding to multiples of k scales the
+ * mod-switch error by k: a k-LUT of message modulus m fails like a single LUT of modulus m*k, so keep
+ * m*k <= 16 on SECURITY_UINT4.  TFHE_HIP_EINVAL: n_luts not in {1, 2, 4, 8}, testvec NULL, cb != 0
+ * with b NULL, k*count > 2^31 - 1.  These calls do not join the combining front end
+ * (tfhe_hip_set_combining): each is launched as it is made. */
+int tfhe_hip_batch_lincomb_bootstrap_many(tfhe_hip_ctx *ctx, uint32_t ca, const uint32_t *a, uint32_t cb,
+                                          const uint32_t *b, uint32_t cconst, const uint32_t *testvec, int per_ct,
+                                          int n_luts, int keyswitch, uint32_t *out, size_t count);
+int tfhe_hip_batch_lincomb_bootstrap_many_dev(tfhe_hip_ctx *ctx, uint32_t ca, const uint32_t *a, uint32_t cb,
+                                              const uint32_t *b, uint32_t cconst, const uint32_t *testvec, int per_ct,
+                                              int n_luts, int keyswitch, uint32_t *out, size_t count, void *stream);
+
 /* Replaces: trgsw::batch_blind_rotate[_with_railgun] (src/trgsw.rs:289-305),
  * trgsw::blind_rotate (:198-226) and blind_rotate_with_testvec (:242-274).
  * in [count][n+1]; testvec NULL or [2][N]; out_trlwe [count][2][N]. */
@@ -511,6 +533,10 @@ int tfhe_hip_pool_batch_tlwe_lincomb(tfhe_hip_pool *pool, uint32_t ca, const uin
 int tfhe_hip_pool_batch_lincomb_bootstrap(tfhe_hip_pool *pool, uint32_t ca, const uint32_t *a, uint32_t cb,
                                           const uint32_t *b, uint32_t cconst, const uint32_t *testvec, int per_ct,
                                           int keyswitch, uint32_t *out, size_t count);
+/* (many-LUT: never combined; each member's [k][m] result is placed into the caller's [k][count]) */
+int tfhe_hip_pool_batch_lincomb_bootstrap_many(tfhe_hip_pool *pool, uint32_t ca, const uint32_t *a, uint32_t cb,
+                                               const uint32_t *b, uint32_t cconst, const uint32_t *testvec, int per_ct,
+                                               int n_luts, int keyswitch, uint32_t *out, size_t count);
 int tfhe_hip_pool_batch_mux(tfhe_hip_pool *pool, int naive, const uint32_t *a, const uint32_t *b, const uint32_t *c,
                             uint32_t *out, size_t count);
 int tfhe_hip_pool_batch_blind_rotate(tfhe_hip_pool *pool, const uint32_t *in, const uint32_t *testvec,
@@ -549,6 +575,10 @@ int tfhe_hip_pool_batch_tlwe_lincomb_dev(tfhe_hip_pool *pool, int home_member, u
 int tfhe_hip_pool_batch_lincomb_bootstrap_dev(tfhe_hip_pool *pool, int home_member, uint32_t ca, const uint32_t *a,
                                               uint32_t cb, const uint32_t *b, uint32_t cconst, const uint32_t *testvec,
                                               int per_ct, int keyswitch, uint32_t *out, size_t count, void *stream);
+int tfhe_hip_pool_batch_lincomb_bootstrap_many_dev(tfhe_hip_pool *pool, int home_member, uint32_t ca, const uint32_t *a,
+                                                   uint32_t cb, const uint32_t *b, uint32_t cconst,
+                                                   const uint32_t *testvec, int per_ct, int n_luts, int keyswitch,
+                                                   uint32_t *out, size_t count, void *stream);
 int tfhe_hip_pool_batch_mux_dev(tfhe_hip_pool *pool, int home_member, int naive, const uint32_t *a, const uint32_t *b,
                                 const uint32_t *c, uint32_t *out, size_t count, void *stream);
 int tfhe_hip_pool_batch_blind_rotate_dev(tfhe_hip_pool *pool, int home_member, const uint32_t *in,
@@ -616,6 +646,14 @@ int tfhe_hip_circuit_add_mux(tfhe_hip_circuit *circ, uint32_t a, uint32_t b, uin
 int tfhe_hip_circuit_add_lut(tfhe_hip_circuit *circ, const uint32_t *testvec, uint32_t *lut);
 int tfhe_hip_circuit_add_pbs(tfhe_hip_circuit *circ, uint32_t ca, uint32_t a, uint32_t cb, uint32_t b, uint32_t cconst,
                              uint32_t lut, uint32_t *wire);
+/* Many-LUT bootstrap (tfhe_hip_batch_lincomb_bootstrap_many): the n_luts in {1, 2, 4, 8} functions packed in `lut` of
+ * ca*a + cb*b + cconst from ONE blind rotation; wires[0 .. n_luts-1] receive the k consecutive output wires (function j
+ * at wires[j]).  Operands fold as for add_pbs.  Compile groups many-LUT nodes by (lut, ca, cb, cconst, k), one launch
+ * per group, with function-major slots (node q, function j at base + j * nodes + q); describe counts such a launch in
+ * lut_launches and each node once in lut_nodes.  TFHE_HIP_EINVAL: n_luts not in {1, 2, 4, 8}, wires NULL, and the
+ * cases of add_pbs. */
+int tfhe_hip_circuit_add_pbs_many(tfhe_hip_circuit *circ, uint32_t ca, uint32_t a, uint32_t cb, uint32_t b,
+                                  uint32_t cconst, uint32_t lut, int n_luts, uint32_t *wires);
 int tfhe_hip_circuit_add_lincomb(tfhe_hip_circuit *circ, const uint32_t *coefs, const uint32_t *wires, size_t n_terms,
                                  uint32_t cconst, uint32_t *wire);
 int tfhe_hip_circuit_add_not(tfhe_hip_circuit *circ, uint32_t a, uint32_t *wire);

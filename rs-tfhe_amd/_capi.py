@@ -102,6 +102,10 @@ SIGNATURES = {
         C.c_int, [_CTX, C.c_uint32, _P, C.c_uint32, _P, C.c_uint32, _P, C.c_int, C.c_int, _P, _SZ]),
     "tfhe_hip_batch_lincomb_bootstrap_dev": (
         C.c_int, [_CTX, C.c_uint32, _P, C.c_uint32, _P, C.c_uint32, _P, C.c_int, C.c_int, _P, _SZ, _P]),
+    "tfhe_hip_batch_lincomb_bootstrap_many": (
+        C.c_int, [_CTX, C.c_uint32, _P, C.c_uint32, _P, C.c_uint32, _P, C.c_int, C.c_int, C.c_int, _P, _SZ]),
+    "tfhe_hip_batch_lincomb_bootstrap_many_dev": (
+        C.c_int, [_CTX, C.c_uint32, _P, C.c_uint32, _P, C.c_uint32, _P, C.c_int, C.c_int, C.c_int, _P, _SZ, _P]),
     "tfhe_hip_batch_blind_rotate": (C.c_int, [_CTX, _P, _P, _P, _SZ]),
     "tfhe_hip_batch_blind_rotate_dev": (C.c_int, [_CTX, _P, _P, _P, _SZ, _P]),
     "tfhe_hip_batch_mux": (C.c_int, [_CTX, C.c_int, _P, _P, _P, _P, _SZ]),
@@ -147,6 +151,8 @@ SIGNATURES = {
     "tfhe_hip_pool_batch_gates_mixed_nks": (C.c_int, [_CTX, _P, _P, _P, _P, _SZ]),
     "tfhe_hip_pool_batch_tlwe_lincomb": (C.c_int, [_CTX, _U32, _P, _U32, _P, _U32, _P, _SZ]),
     "tfhe_hip_pool_batch_lincomb_bootstrap": (C.c_int, [_CTX, _U32, _P, _U32, _P, _U32, _P, C.c_int, C.c_int, _P, _SZ]),
+    "tfhe_hip_pool_batch_lincomb_bootstrap_many": (
+        C.c_int, [_CTX, _U32, _P, _U32, _P, _U32, _P, C.c_int, C.c_int, C.c_int, _P, _SZ]),
     # ... for a batch resident on one member's GPU (home_member, device pointers, stream)
     "tfhe_hip_pool_batch_gate_dev": (C.c_int, [_CTX, C.c_int, C.c_int, _P, _P, _P, _SZ, _P]),
     "tfhe_hip_pool_batch_gates_mixed_dev": (C.c_int, [_CTX, C.c_int, _P, _P, _P, _P, _SZ, _P]),
@@ -155,6 +161,8 @@ SIGNATURES = {
     "tfhe_hip_pool_batch_tlwe_lincomb_dev": (C.c_int, [_CTX, C.c_int, _U32, _P, _U32, _P, _U32, _P, _SZ, _P]),
     "tfhe_hip_pool_batch_lincomb_bootstrap_dev": (
         C.c_int, [_CTX, C.c_int, _U32, _P, _U32, _P, _U32, _P, C.c_int, C.c_int, _P, _SZ, _P]),
+    "tfhe_hip_pool_batch_lincomb_bootstrap_many_dev": (
+        C.c_int, [_CTX, C.c_int, _U32, _P, _U32, _P, _U32, _P, C.c_int, C.c_int, C.c_int, _P, _SZ, _P]),
     "tfhe_hip_pool_batch_mux_dev": (C.c_int, [_CTX, C.c_int, C.c_int, _P, _P, _P, _P, _SZ, _P]),
     "tfhe_hip_pool_batch_blind_rotate_dev": (C.c_int, [_CTX, C.c_int, _P, _P, _P, _SZ, _P]),
     "tfhe_hip_pool_synchronize": (C.c_int, [_CTX]),
@@ -168,6 +176,7 @@ SIGNATURES = {
     "tfhe_hip_circuit_add_mux": (C.c_int, [_CTX, _U32, _U32, _U32, C.POINTER(_U32)]),
     "tfhe_hip_circuit_add_lut": (C.c_int, [_CTX, _P, C.POINTER(_U32)]),
     "tfhe_hip_circuit_add_pbs": (C.c_int, [_CTX, _U32, _U32, _U32, _U32, _U32, _U32, C.POINTER(_U32)]),
+    "tfhe_hip_circuit_add_pbs_many": (C.c_int, [_CTX, _U32, _U32, _U32, _U32, _U32, _U32, C.c_int, C.POINTER(_U32)]),
     "tfhe_hip_circuit_add_lincomb": (C.c_int, [_CTX, _P, _P, _SZ, _U32, C.POINTER(_U32)]),
     "tfhe_hip_circuit_add_not": (C.c_int, [_CTX, _U32, C.POINTER(_U32)]),
     "tfhe_hip_circuit_add_constant": (C.c_int, [_CTX, C.c_int, C.POINTER(_U32)]),

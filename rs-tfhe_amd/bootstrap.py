@@ -160,6 +160,21 @@ class LutBootstrap(HipBootstrap):
             out = eng.batch_bootstrap(ct_in, lut.poly, True)
         return out[0] if ct_in.ndim == 1 else out
 
+    def bootstrap_many_lut(self, ct_in, lut: LookupTable, k: int, cloud_key):
+        """k functions packed in `lut` (Generator.generate_many_lookup_table) from one blind rotation per ciphertext:
+        a list of k results, [j] shaped like ct_in (PBS-manyLUT, tfhe_hip_batch_lincomb_bootstrap_many)."""
+        ct_in = np.asarray(ct_in, dtype=np.uint32)
+        with keyed_engine(cloud_key, self.device) as eng:
+            out = eng.batch_lincomb_bootstrap_many(1, ct_in, 0, None, 0, lut.poly, n_luts=k)
+        return [o[0] if ct_in.ndim == 1 else o for o in out]
+
+    def bootstrap_many_func(self, ct_in, fs, message_modulus: int, cloud_key):
+        """bootstrap_func for several functions of the same input at the cost of one blind rotation (keep
+        message_modulus * len(fs) <= 16 on SECURITY_UINT4: see Generator.generate_many_lookup_table)."""
+        fs = list(fs)
+        lut = Generator(message_modulus).generate_many_lookup_table(fs)
+        return self.bootstrap_many_lut(ct_in, lut, len(fs), cloud_key)
+
     def bootstrap(self, ctxt, cloud_key):  # lut.rs:108-111: identity function, m = 2
         return self.bootstrap_func(ctxt, lambda x: x, 2, cloud_key)
 

@@ -114,6 +114,21 @@ class Circuit:
         lvl = 1 + max(self._level[a], self._level[b] if cb else 0)
         return self._add(("pbs", ca & 0xFFFFFFFF, a, cb, b, cconst & 0xFFFFFFFF, int(lut)), lvl)
 
+    def pbs_many(self, ca: int, a: int, cb: int, b, cconst: int, lut: int, n_luts: int) -> list:
+        """Many-LUT bootstrap (tfhe_hip_circuit_add_pbs_many): the n_luts functions packed in `lut`
+        (Generator.generate_many_lookup_table) of ca*a + cb*b + cconst from ONE blind rotation; returns the n_luts
+        consecutive output wires, function j at [j]."""
+        a = self._wire(a)
+        cb &= 0xFFFFFFFF
+        b = self._wire(b) if cb else a
+        if not 0 <= lut < len(self._luts):
+            raise ValueError(f"no lut {lut}")
+        if n_luts not in (1, 2, 4, 8):
+            raise ValueError("n_luts must be 1, 2, 4 or 8")
+        lvl = 1 + max(self._level[a], self._level[b] if cb else 0)
+        head = self._add(("pbs_many", ca & 0xFFFFFFFF, a, cb, b, cconst & 0xFFFFFFFF, int(lut), int(n_luts)), lvl)
+        return [head] + [self._add(("pbs_fn", head, j), lvl) for j in range(1, n_luts)]
+
     def lincomb(self, terms, cconst: int = 0) -> int:
         """sum coef * wire (+ cconst on the body): TLWE `+` / `-` / scaling, no bootstrap.  terms: [(coef, wire)]."""
         terms = [(int(c) & 0xFFFFFFFF, self._wire(w)) for c, w in terms]
@@ -184,6 +199,11 @@ class Circuit:
                     rc = lib.tfhe_hip_circuit_add_mux(h, node[1], node[2], node[3], C.byref(w))
                 elif kind == "pbs":
                     rc = lib.tfhe_hip_circuit_add_pbs(h, *node[1:], C.byref(w))
+                elif kind == "pbs_many":
+                    ws = (C.c_uint32 * node[7])()
+                    rc = lib.tfhe_hip_circuit_add_pbs_many(h, *node[1:], ws)
+                elif kind == "pbs_fn":  # added with its head
+                    continue
                 else:
                     coefs = np.array([c for c, _ in node[1]], np.uint32)
                     wires = np.array([x for _, x in node[1]], np.uint32)
@@ -313,11 +333,11 @@ class Circuit:
             eng._chk(lib.tfhe_hip_circuit_run(eng._ctx, *args))
         return out
 
-    def run_reference(self, gate_fn, inputs, mux_fn=None, pbs_fn=None) -> np.ndarray:
+    def run_reference(self, gate_fn, inputs, mux_fn=None, pbs_fn=None, many_fn=None) -> np.ndarray:
         """Evaluate node by node in the order they were added (the order the reference's examples execute them; the
         tests plug their CPU checker in here): `gate_fn(op, a[B][n+1], b[B][n+1]) -> [B][n+1]`,
-        `mux_fn(a, b, c) -> [B][n+1]`, `pbs_fn(testvec [2][N], prepared [B][n+1]) -> [B][n+1]`; linear nodes in numpy
-        (wrapping u32)."""
+        `mux_fn(a, b, c) -> [B][n+1]`, `pbs_fn(testvec [2][N], prepared [B][n+1]) -> [B][n+1]`,
+        `many_fn(testvec, prepared, k) -> [k][B][n+1]`; linear nodes in numpy (wrapping u32)."""
         inputs = np.ascontiguousarray(inputs, dtype=np.uint32)
         wires = np.zeros((self.n_wires,) + inputs.shape[1:], np.uint32)
         wires[: self.n_inputs] = inputs
@@ -331,6 +351,12 @@ class Circuit:
                 _, ca, a, cb, b, cc, lut = node
                 prep = _lin([(ca, wires[a])] + ([(cb, wires[b])] if cb else []), cc, wires.shape[1:])
                 wires[out] = pbs_fn(self._luts[lut].reshape(2, -1), prep)
+            elif kind == "pbs_many":
+                _, ca, a, cb, b, cc, lut, k = node
+                prep = _lin([(ca, wires[a])] + ([(cb, wires[b])] if cb else []), cc, wires.shape[1:])
+                wires[out:out + k] = many_fn(self._luts[lut].reshape(2, -1), prep, k)
+            elif kind == "pbs_fn":
+                pass  # written with its head
             else:
                 wires[out] = _lin([(c, wires[w]) for c, w in node[1]], node[2], wires.shape[1:])
         return wires
@@ -427,3 +453,34 @@ def lut_add_u8(eng, a_low, a_high, b_low, b_high):
     high = eng.batch_tlwe_lincomb(1, a_high, 1, b_high)
     sum_high = eng.batch_lincomb_bootstrap(1, high, 1, carry, testvec=lut_mod16)
     return sum_low, sum_high, carry
+
+
+def lut_add_u8_digits(c: "Circuit", a_digits, b_digits, n_luts: int = 2):
+    """An 8-bit adder over base-4 digits: a_digits / b_digits are 4 wires each (least significant first), encryptions
+    of 2-bit digits under message modulus 8 (`encrypt_lwe_message(d, 8, ...)`).  Digit i bootstraps a_i + b_i + carry
+    (at most 7) once through a 2-LUT table (x mod 4, x div 4): 4 blind rotations for the byte where single LUTs take 8
+    (m * k = 16, the SECURITY_UINT4 precision bound; Generator.generate_many_lookup_table).  n_luts=1 builds the same
+    adder from two single-LUT bootstraps per digit, for comparison.  Returns (sum digit wires, carry wires); the byte
+    is sum(s_i * 4^i) & 0xFF, each wire decrypting under modulus 8."""
+    from .lut import Generator
+
+    assert len(a_digits) == len(b_digits) == 4
+    gen = Generator(8)
+    fs = [lambda x: x % 4, lambda x: x // 4]
+    if n_luts == 2:
+        lut2 = c.lut(gen.generate_many_lookup_table(fs).poly)
+    else:
+        lut_s, lut_c = (c.lut(gen.generate_lookup_table(f).poly) for f in fs)
+    sums, carries, carry = [], [], None
+    for a, b in zip(a_digits, b_digits):
+        if carry is None:
+            ca, x, cb, y = 1, a, 1, b
+        else:
+            ca, x, cb, y = 1, c.lincomb([(1, a), (1, b)]), 1, carry
+        if n_luts == 2:
+            s, carry = c.pbs_many(ca, x, cb, y, 0, lut2, 2)
+        else:
+            s, carry = c.pbs(ca, x, cb, y, 0, lut_s), c.pbs(ca, x, cb, y, 0, lut_c)
+        sums.append(s)
+        carries.append(carry)
+    return sums, carries

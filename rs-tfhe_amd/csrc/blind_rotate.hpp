@@ -231,6 +231,13 @@ struct BlindRotateArgs {
   // diagnostics (may be null)
   unsigned long long *clk;  // [2]: += shader cycles (s_memtime) and += constant-rate ticks (s_memrealtime) per workgroup
   uint32_t *err_flag;       // |= 1 when a gate code outside tfhe_hip_gate is seen (the ciphertext is then treated as COPY)
+  // many-LUT bootstrap (Chillotti et al. 2021, PBS-manyLUT), read by the many-LUT instantiations only: the rotation
+  // amounts are rounded to multiples of n_luts = 2^lut_shift, and out_lv1 / out_ext2 receive sample_extract_index(., j)
+  // for j < n_luts, function-major: function j of ciphertext ct is row j * out_fn_stride + ct (out_fn_stride = the
+  // whole call's count, so the per-part slicing of the output bases keeps it).  Last, so the other fields keep their
+  // offsets.
+  int lut_shift, n_luts;
+  size_t out_fn_stride;
 };
 
 // src/gates.rs:54-150 as (ca, cb, const): prepared = ca*a + cb*b, prepared.b += const.
@@ -257,8 +264,10 @@ constexpr int kStageLdsBytes = kTileBytes + kT2Bytes;  // stage kernels: tile | 
 // chain.  X^k * acc is then just an indexed re-read of that array (poly_mul_with_x_k
 // never materialises), and the 32 VGPRs an in-register accumulator would pin across
 // the eight FFTs are free, which is what lets two waves share a SIMD (<= 256 VGPRs).
-template <int L, bool FAST>
-__global__ __launch_bounds__(64 * kBrWaves, 2) void k_blind_rotate(BlindRotateArgs A) {
+// MANY: the many-LUT prologue and epilogue (BlindRotateArgs::lut_shift / n_luts / out_fn_stride) -- instantiated as a
+// kernel of its own (k_blind_rotate_many), so that the ordinary kernel's code is exactly what it was without them.
+template <int L, bool FAST, bool MANY>
+__device__ __forceinline__ void blind_rotate_batch(BlindRotateArgs A) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem_wg[];
   const int n = A.n;
   const int lane = threadIdx.x & 63;
@@ -293,17 +302,18 @@ __global__ __launch_bounds__(64 * kBrWaves, 2) void k_blind_rotate(BlindRotateAr
   }
   const uint32_t *pa = A.in_a + (A.idx_a ? (size_t)A.idx_a[ct] : ct) * (size_t)(n + 1);
   const uint32_t *pb = (A.in_b && gcb) ? A.in_b + (A.idx_b ? (size_t)A.idx_b[ct] : ct) * (size_t)(n + 1) : nullptr;
+  const int dl = MANY ? A.lut_shift : 0;
   for (int i = lane; i < n; i += 64) {
     uint32_t p = gca * pa[i];
     if (pb) p += gcb * pb[i];
-    // a_tilda = (p +wrap 2^20) >> 21   (trgsw.rs:210-211)
-    s_abar[i] = (uint16_t)((uint32_t)(p + (1u << 20)) >> 21);
+    // a_tilda = (p +wrap 2^20) >> 21   (trgsw.rs:210-211), rounded to a multiple of 2^lut_shift
+    s_abar[i] = (uint16_t)(((uint32_t)(p + (1u << (20 + dl))) >> (21 + dl)) << dl);
   }
   uint32_t pbody = gca * pa[n];
   if (pb) pbody += gcb * pb[n];
   pbody += gcc;
   // b_tilda = 2N - ((b as usize + 2^20) >> 21), no 32-bit wrap (trgsw.rs:202-203)
-  const int b_tilda = 2 * kN - (int)(((uint64_t)pbody + (1ull << 20)) >> 21);
+  const int b_tilda = 2 * kN - (int)((((uint64_t)pbody + (1ull << (20 + dl))) >> (21 + dl)) << dl);
 
   // ---- acc = X^b_tilda * testvec -------------------------------------------
   const uint32_t *tv = A.testvec + ct * A.per_ct_stride;
@@ -396,26 +406,57 @@ __global__ __launch_bounds__(64 * kBrWaves, 2) void k_blind_rotate(BlindRotateAr
 #pragma unroll
     for (int m = 0; m < 32; ++m) o[lane + 64 * m] = acc[lane + 64 * m];
   }
-  if (A.out_lv1) {
-    // p[0]=a[0]; p[i]=MAX-a[N-i]; p[N]=b[0]   (trlwe.rs:106-120 with k=0)
-    uint32_t *o = A.out_lv1 + ct * (size_t)(kN + 1);
+  if constexpr (MANY) {
+    for (int j = 0; j < A.n_luts; ++j) {
+      const size_t row = (size_t)j * A.out_fn_stride + ct;
+      if (A.out_lv1) {
+        // p[i] = i <= j ? a[j-i] : MAX-a[N+j-i]; p[N] = b[j]   (trlwe.rs:106-120 with k=j)
+        uint32_t *o = A.out_lv1 + row * (size_t)(kN + 1);
 #pragma unroll
-    for (int m = 0; m < 16; ++m) {
-      const int i = lane + 64 * m;
-      o[i] = i == 0 ? acc[0] : ~acc[kN - i];
+        for (int m = 0; m < 16; ++m) {
+          const int i = lane + 64 * m;
+          o[i] = i <= j ? acc[j - i] : ~acc[kN + j - i];
+        }
+        if (lane == 0) o[kN] = acc[kN + j];
+      }
+      if (A.out_ext2) {
+        // same formula with N := n   (trlwe.rs:122-136 with k=j)
+        uint32_t *o = A.out_ext2 + row * (size_t)(n + 1);
+        for (int i = lane; i < n; i += 64) o[i] = i <= j ? acc[j - i] : ~acc[n + j - i];
+        if (lane == 0) o[n] = acc[kN + j];
+      }
     }
-    if (lane == 0) o[kN] = acc[kN];
-  }
-  if (A.out_ext2) {
-    // same formula with N := n   (trlwe.rs:122-136 with k=0)
-    uint32_t *o = A.out_ext2 + ct * (size_t)(n + 1);
-    for (int i = lane; i < n; i += 64) o[i] = i == 0 ? acc[0] : ~acc[n - i];
-    if (lane == 0) o[n] = acc[kN];
+  } else {
+    if (A.out_lv1) {
+      // p[0]=a[0]; p[i]=MAX-a[N-i]; p[N]=b[0]   (trlwe.rs:106-120 with k=0)
+      uint32_t *o = A.out_lv1 + ct * (size_t)(kN + 1);
+#pragma unroll
+      for (int m = 0; m < 16; ++m) {
+        const int i = lane + 64 * m;
+        o[i] = i == 0 ? acc[0] : ~acc[kN - i];
+      }
+      if (lane == 0) o[kN] = acc[kN];
+    }
+    if (A.out_ext2) {
+      // same formula with N := n   (trlwe.rs:122-136 with k=0)
+      uint32_t *o = A.out_ext2 + ct * (size_t)(n + 1);
+      for (int i = lane; i < n; i += 64) o[i] = i == 0 ? acc[0] : ~acc[n - i];
+      if (lane == 0) o[n] = acc[kN];
+    }
   }
   if (A.clk && lane == 0) {
     atomicAdd(&A.clk[0], __builtin_amdgcn_s_memtime() - clk0);
     atomicAdd(&A.clk[1], __builtin_amdgcn_s_memrealtime() - rtc0);
   }
+}
+
+template <int L, bool FAST>
+__global__ __launch_bounds__(64 * kBrWaves, 2) void k_blind_rotate(BlindRotateArgs A) {
+  blind_rotate_batch<L, FAST, false>(A);
+}
+template <int L, bool FAST>
+__global__ __launch_bounds__(64 * kBrWaves, 2) void k_blind_rotate_many(BlindRotateArgs A) {
+  blind_rotate_batch<L, FAST, true>(A);
 }
 
 // ---- TLWE arithmetic between bootstraps (tlwe.rs:129-214): out = ca*a + cb*b, out[n] += cconst -------

@@ -36,8 +36,10 @@ __host__ __device__ __forceinline__ size_t blind_rotate_wide2_lds_bytes(int n, i
 // see the loop, and profiles/exp/logs/r3m_latency_wide2_phases.log.)
 __device__ __forceinline__ void lds_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
 
-template <int L, bool FAST>
-__global__ __launch_bounds__(64 * kWide2Waves, 1) void k_blind_rotate_wide2(BlindRotateArgs A) {
+// MANY: the many-LUT prologue / epilogue (BlindRotateArgs::lut_shift / n_luts / out_fn_stride), instantiated as kernels
+// of their own (see blind_rotate_batch)
+template <int L, bool FAST, bool MANY>
+__device__ __forceinline__ void blind_rotate_wide2(BlindRotateArgs A) {
   constexpr int W = 2 * L;  // forward waves (one per decomposition row)
   constexpr int NT = 64 * kWide2Waves;
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
@@ -72,15 +74,16 @@ __global__ __launch_bounds__(64 * kWide2Waves, 1) void k_blind_rotate_wide2(Blin
   }
   const uint32_t *pa = A.in_a + (A.idx_a ? (size_t)A.idx_a[ct] : ct) * (size_t)(n + 1);
   const uint32_t *pb = (A.in_b && gcb) ? A.in_b + (A.idx_b ? (size_t)A.idx_b[ct] : ct) * (size_t)(n + 1) : nullptr;
+  const int dl = MANY ? A.lut_shift : 0;  // many-LUT: rotation amounts rounded to multiples of 2^dl
   for (int i = tid; i < n; i += NT) {
     uint32_t p = gca * pa[i];
     if (pb) p += gcb * pb[i];
-    s_abar[i] = (uint16_t)((uint32_t)(p + (1u << 20)) >> 21);
+    s_abar[i] = (uint16_t)(((uint32_t)(p + (1u << (20 + dl))) >> (21 + dl)) << dl);
   }
   uint32_t pbody = gca * pa[n];
   if (pb) pbody += gcb * pb[n];
   pbody += gcc;
-  const int b_tilda = 2 * kN - (int)(((uint64_t)pbody + (1ull << 20)) >> 21);
+  const int b_tilda = 2 * kN - (int)((((uint64_t)pbody + (1ull << (20 + dl))) >> (21 + dl)) << dl);
   const uint32_t *tv = A.testvec + ct * A.per_ct_stride;
   for (int j = tid; j < kN; j += NT) {
     acc[j] = rot_read(tv, j, b_tilda);
@@ -205,20 +208,45 @@ __global__ __launch_bounds__(64 * kWide2Waves, 1) void k_blind_rotate_wide2(Blin
     uint32_t *o = A.out_trlwe + ct * (size_t)(2 * kN);
     for (int j = tid; j < 2 * kN; j += NT) o[j] = acc[j];
   }
-  if (A.out_lv1) {  // trlwe.rs:106-120 with k=0
-    uint32_t *o = A.out_lv1 + ct * (size_t)(kN + 1);
-    for (int i = tid; i < kN; i += NT) o[i] = i == 0 ? acc[0] : ~acc[kN - i];
-    if (tid == 0) o[kN] = acc[kN];
-  }
-  if (A.out_ext2) {  // trlwe.rs:122-136 with k=0
-    uint32_t *o = A.out_ext2 + ct * (size_t)(n + 1);
-    for (int i = tid; i < n; i += NT) o[i] = i == 0 ? acc[0] : ~acc[n - i];
-    if (tid == 0) o[n] = acc[kN];
+  if constexpr (MANY) {
+    for (int j = 0; j < A.n_luts; ++j) {  // function j: row j * out_fn_stride + ct
+      const size_t row = (size_t)j * A.out_fn_stride + ct;
+      if (A.out_lv1) {  // trlwe.rs:106-120 with k=j
+        uint32_t *o = A.out_lv1 + row * (size_t)(kN + 1);
+        for (int i = tid; i < kN; i += NT) o[i] = i <= j ? acc[j - i] : ~acc[kN + j - i];
+        if (tid == 0) o[kN] = acc[kN + j];
+      }
+      if (A.out_ext2) {  // trlwe.rs:122-136 with k=j
+        uint32_t *o = A.out_ext2 + row * (size_t)(n + 1);
+        for (int i = tid; i < n; i += NT) o[i] = i <= j ? acc[j - i] : ~acc[n + j - i];
+        if (tid == 0) o[n] = acc[kN + j];
+      }
+    }
+  } else {
+    if (A.out_lv1) {  // trlwe.rs:106-120 with k=0
+      uint32_t *o = A.out_lv1 + ct * (size_t)(kN + 1);
+      for (int i = tid; i < kN; i += NT) o[i] = i == 0 ? acc[0] : ~acc[kN - i];
+      if (tid == 0) o[kN] = acc[kN];
+    }
+    if (A.out_ext2) {  // trlwe.rs:122-136 with k=0
+      uint32_t *o = A.out_ext2 + ct * (size_t)(n + 1);
+      for (int i = tid; i < n; i += NT) o[i] = i == 0 ? acc[0] : ~acc[n - i];
+      if (tid == 0) o[n] = acc[kN];
+    }
   }
   if (A.clk && tid == 0) {
     atomicAdd(&A.clk[0], __builtin_amdgcn_s_memtime() - clk0);
     atomicAdd(&A.clk[1], __builtin_amdgcn_s_memrealtime() - rtc0);
   }
+}
+
+template <int L, bool FAST>
+__global__ __launch_bounds__(64 * kWide2Waves, 1) void k_blind_rotate_wide2(BlindRotateArgs A) {
+  blind_rotate_wide2<L, FAST, false>(A);
+}
+template <int L, bool FAST>
+__global__ __launch_bounds__(64 * kWide2Waves, 1) void k_blind_rotate_wide2_many(BlindRotateArgs A) {
+  blind_rotate_wide2<L, FAST, true>(A);
 }
 
 // ---------------------------------------------------------------------------------------------------------------
@@ -243,7 +271,9 @@ __host__ __device__ __forceinline__ size_t blind_rotate_pair_lds_bytes(int n) {
           (size_t)2 * (((size_t)n * 2 + 15) & ~(size_t)15) + 15) & ~(size_t)15;
 }
 
-template <int L, bool FAST>
+// MANY: the many-LUT prologue / epilogue.  Here a template parameter of the kernel itself: behind a device-function
+// wrapper (as k_blind_rotate / k_blind_rotate_wide2 have it) this kernel's register allocation shifts.
+template <int L, bool FAST, bool MANY = false>
 __global__ __launch_bounds__(64 * kPairWaves, 1) void k_blind_rotate_pair(BlindRotateArgs A) {
   constexpr int W = 2 * L;  // forward waves: 2 .. 2 + W - 1 (row r = wave - 2)
   constexpr int NT = 64 * kPairWaves;
@@ -286,15 +316,16 @@ __global__ __launch_bounds__(64 * kPairWaves, 1) void k_blind_rotate_pair(BlindR
     }
     const uint32_t *pa = A.in_a + (A.idx_a ? (size_t)A.idx_a[ct] : ct) * (size_t)(n + 1);
     const uint32_t *pb = (A.in_b && gcb) ? A.in_b + (A.idx_b ? (size_t)A.idx_b[ct] : ct) * (size_t)(n + 1) : nullptr;
+    const int dl = MANY ? A.lut_shift : 0;  // many-LUT: rotation amounts rounded to multiples of 2^dl
     for (int i = tid; i < n; i += NT) {
       uint32_t p = gca * pa[i];
       if (pb) p += gcb * pb[i];
-      s_abar[c * abar_stride + i] = (uint16_t)((uint32_t)(p + (1u << 20)) >> 21);
+      s_abar[c * abar_stride + i] = (uint16_t)(((uint32_t)(p + (1u << (20 + dl))) >> (21 + dl)) << dl);
     }
     uint32_t pbody = gca * pa[n];
     if (pb) pbody += gcb * pb[n];
     pbody += gcc;
-    const int b_tilda = 2 * kN - (int)(((uint64_t)pbody + (1ull << 20)) >> 21);
+    const int b_tilda = 2 * kN - (int)((((uint64_t)pbody + (1ull << (20 + dl))) >> (21 + dl)) << dl);
     const uint32_t *tv = A.testvec + ct * A.per_ct_stride;
     uint32_t *q = acc + c * 2 * kN;
     for (int j = tid; j < kN; j += NT) {
@@ -430,15 +461,31 @@ __global__ __launch_bounds__(64 * kPairWaves, 1) void k_blind_rotate_pair(BlindR
       uint32_t *o = A.out_trlwe + ct * (size_t)(2 * kN);
       for (int j = tid; j < 2 * kN; j += NT) o[j] = q[j];
     }
-    if (A.out_lv1) {  // trlwe.rs:106-120 with k=0
-      uint32_t *o = A.out_lv1 + ct * (size_t)(kN + 1);
-      for (int i = tid; i < kN; i += NT) o[i] = i == 0 ? q[0] : ~q[kN - i];
-      if (tid == 0) o[kN] = q[kN];
-    }
-    if (A.out_ext2) {  // trlwe.rs:122-136 with k=0
-      uint32_t *o = A.out_ext2 + ct * (size_t)(n + 1);
-      for (int i = tid; i < n; i += NT) o[i] = i == 0 ? q[0] : ~q[n - i];
-      if (tid == 0) o[n] = q[kN];
+    if constexpr (MANY) {
+      for (int j = 0; j < A.n_luts; ++j) {  // function j: row j * out_fn_stride + ct
+        const size_t row = (size_t)j * A.out_fn_stride + ct;
+        if (A.out_lv1) {  // trlwe.rs:106-120 with k=j
+          uint32_t *o = A.out_lv1 + row * (size_t)(kN + 1);
+          for (int i = tid; i < kN; i += NT) o[i] = i <= j ? q[j - i] : ~q[kN + j - i];
+          if (tid == 0) o[kN] = q[kN + j];
+        }
+        if (A.out_ext2) {  // trlwe.rs:122-136 with k=j
+          uint32_t *o = A.out_ext2 + row * (size_t)(n + 1);
+          for (int i = tid; i < n; i += NT) o[i] = i <= j ? q[j - i] : ~q[n + j - i];
+          if (tid == 0) o[n] = q[kN + j];
+        }
+      }
+    } else {
+      if (A.out_lv1) {  // trlwe.rs:106-120 with k=0
+        uint32_t *o = A.out_lv1 + ct * (size_t)(kN + 1);
+        for (int i = tid; i < kN; i += NT) o[i] = i == 0 ? q[0] : ~q[kN - i];
+        if (tid == 0) o[kN] = q[kN];
+      }
+      if (A.out_ext2) {  // trlwe.rs:122-136 with k=0
+        uint32_t *o = A.out_ext2 + ct * (size_t)(n + 1);
+        for (int i = tid; i < n; i += NT) o[i] = i == 0 ? q[0] : ~q[n - i];
+        if (tid == 0) o[n] = q[kN];
+      }
     }
   }
   if (A.clk && tid == 0) {

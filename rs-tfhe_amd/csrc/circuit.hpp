@@ -7,6 +7,8 @@
 //   mux(a, b, c)                        Gates::mux (src/gates.rs:157-183): and(a, b), and(not(a), c) without key switch,
 //                                       their sum bootstrapped as or()
 //   pbs(ca, a, cb, b, cconst, lut)      a programmable bootstrap (src/bootstrap/lut.rs:79-99) of ca*a + cb*b + cconst
+//   pbs_many(..., lut, k)               k consecutive wires: the k functions a packed table holds, from ONE blind
+//                                       rotation (tfhe_hip_batch_lincomb_bootstrap_many)
 //   lincomb / not / constant            TLWE additions and scalings (src/tlwe.rs, src/gates.rs:202-219): no bootstrap
 // compile() levelises it: inputs are level 0, a bootstrap sits one level above its deepest operand and a linear node at
 // the level of its deepest operand.  Wires are renumbered into STORE SLOTS, level by level: inputs take slots
@@ -15,7 +17,8 @@
 //   at most one lincomb launch (k_circuit_lincomb): the linear operands a bootstrap cannot fold
 //   at most one bootstrap-without-key-switch launch: the and / and(not) halves of the level's muxes
 //   at most one key-switched gate launch (per-ciphertext gate codes): gates and the muxes' or()
-//   one launch per (lut, coefficients) group of programmable bootstraps
+//   one launch per (lut, coefficients, k) group of programmable bootstraps; a many-LUT group's slots are
+//   function-major (node q, function j at base + j * nodes + q), so the kernel's [k][count] result is the store as it is
 // The bootstraps read their operands straight out of the store: the blind rotation's prologue takes per-ciphertext
 // row indices (BlindRotateArgs::idx_a / idx_b), built once per (circuit, context, B) and kept on the device.
 // A bootstrap whose operands are linear nodes takes them into its own prologue (ca*a + cb*b + cconst, exact wrapping
@@ -54,6 +57,10 @@ struct CircNode {
   uint32_t ca = 0, cb = 0, cc = 0, lut = 0;
   CircExp exp;  // CN_LIN only
   int level = 0;
+  // many-LUT bootstraps (CN_PBS): nl = k functions, this wire is function fn of the node whose first wire is `head`;
+  // nl = 0 for an ordinary bootstrap
+  uint8_t nl = 0, fn = 0;
+  uint32_t head = 0;
 };
 
 enum CircLaunchKind { CL_LINCOMB = 0, CL_NKS = 1, CL_GATE = 2, CL_LUT = 3 };
@@ -63,6 +70,7 @@ struct CircLaunch {
   std::vector<uint32_t> sa, sb;  // bootstraps: operand slots per node
   std::vector<uint8_t> code;     // gate / nks launches: tfhe_hip_gate per node
   uint32_t lut = kGateTv, ca = 0, cb = 0, cc = 0;  // CL_LUT
+  uint32_t n_luts = 0;                              // CL_LUT: many-LUT group of k functions (0: one function)
   std::vector<uint32_t> off, coef, src, cst;      // CL_LINCOMB: CSR over slots, per node
 };
 struct CircLevel {
@@ -254,7 +262,8 @@ int circ_compile(tfhe_hip_circuit *c) {
   std::vector<std::array<CircOperand, 3>> mux_rows(W);
   for (uint32_t w = 0; w < W; ++w) {
     const CircNode &n = c->nodes[w];
-    if (n.kind == CN_GATE || n.kind == CN_PBS) dec[w] = circ_decide(c, n, need);
+    if (n.kind == CN_PBS && n.fn) dec[w] = dec[n.head];  // a many-LUT node's further functions: its head decides
+    else if (n.kind == CN_GATE || n.kind == CN_PBS) dec[w] = circ_decide(c, n, need);
     if (n.kind == CN_MUX)
       mux_rows[w] = {circ_row(c, n.a, n.level, need), circ_row(c, n.b, n.level, need), circ_row(c, n.c, n.level, need)};
   }
@@ -273,7 +282,7 @@ int circ_compile(tfhe_hip_circuit *c) {
     lv.begin = (uint32_t)next;
     std::vector<uint32_t> lin, mux, gate;
     std::vector<std::vector<uint32_t>> group;
-    std::vector<std::array<uint32_t, 4>> gkey;
+    std::vector<std::array<uint32_t, 5>> gkey;
     for (auto &kv : need)
       if (kv.second == L) lin.push_back(kv.first);
     for (uint32_t w = 0; w < W; ++w) {
@@ -284,8 +293,10 @@ int circ_compile(tfhe_hip_circuit *c) {
         gate.push_back(w);
       } else if (dec[w].kind == CL_GATE) {
         gate.push_back(w);
+      } else if (n.kind == CN_PBS && n.fn) {
+        continue;  // placed with its head
       } else {
-        const std::array<uint32_t, 4> k = {dec[w].lut, dec[w].ca, dec[w].cb, dec[w].cc};
+        const std::array<uint32_t, 5> k = {dec[w].lut, dec[w].ca, dec[w].cb, dec[w].cc, n.kind == CN_PBS ? n.nl : 0u};
         size_t g = 0;
         while (g < gkey.size() && gkey[g] != k) ++g;
         if (g == gkey.size()) {
@@ -356,13 +367,24 @@ int circ_compile(tfhe_hip_circuit *c) {
       l.kind = CL_LUT;
       l.out_slot = (uint32_t)next;
       l.nodes = (uint32_t)group[g].size();
-      l.lut = gkey[g][0], l.ca = gkey[g][1], l.cb = gkey[g][2], l.cc = gkey[g][3];
+      l.lut = gkey[g][0], l.ca = gkey[g][1], l.cb = gkey[g][2], l.cc = gkey[g][3], l.n_luts = gkey[g][4];
+      const uint64_t base = next;
       for (uint32_t w : group[g]) {
         c->slot[w] = (uint32_t)next++;
         l.sa.push_back(row(dec[w].x));
         l.sb.push_back(row(dec[w].y));
         c->opnd[w] = {l.sa.back()};
         if (l.cb) c->opnd[w].push_back(l.sb.back());
+      }
+      if (l.n_luts) {  // function j of node q: slot base + j * nodes + q
+        next = base + (uint64_t)l.n_luts * l.nodes;
+        if (next > 0xFFFFFFFFull) return TFHE_HIP_EINVAL;
+        for (uint32_t q = 0; q < l.nodes; ++q)
+          for (uint32_t j = 1; j < l.n_luts; ++j) {
+            const uint32_t w = group[g][q] + j;  // the head's further functions are the wires right after it
+            c->slot[w] = (uint32_t)(base + (uint64_t)j * l.nodes + q);
+            c->opnd[w] = c->opnd[group[g][q]];
+          }
       }
       lv.launches.push_back(std::move(l));
     }
@@ -499,13 +521,15 @@ int circ_run_locked(tfhe_hip_ctx *ctx, tfhe_hip_circuit *c, const CircPlan *p, u
                                 d.ia, d.ib));
       } else {
         // gates: per-ciphertext codes (cb != 0 keeps in_b attached); lut groups: one (ca, cb, cconst) for the launch
+        // (many-LUT groups: k extractions per blind rotation, [k][count] rows through one key switch)
         const bool gate = l.kind == CL_GATE;
         const GatePrep gp = gate ? GatePrep{1u, 1u, 0u} : GatePrep{l.ca, l.cb, l.cc};
+        const int shift = l.n_luts ? lut_shift_of((int)l.n_luts) : 0;
         CHK(claim_scratch(ctx, s));
-        CHK(ensure(ctx, ctx->lv1, lv1_rows(count) * (size_t)(kN + 1) * 4));
+        CHK(ensure(ctx, ctx->lv1, lv1_rows(count << shift) * (size_t)(kN + 1) * 4));
         CHK(launch_blind_rotate(ctx, s, wires, gp.cb ? wires : nullptr, gp, d.tv, 0, count, nullptr, (uint32_t *)ctx->lv1.p,
-                                nullptr, gate ? d.code : nullptr, d.ia, gp.cb ? d.ib : nullptr));
-        CHK(launch_key_switch(ctx, s, (const uint32_t *)ctx->lv1.p, out, count));
+                                nullptr, gate ? d.code : nullptr, d.ia, gp.cb ? d.ib : nullptr, shift));
+        CHK(launch_key_switch(ctx, s, (const uint32_t *)ctx->lv1.p, out, count << shift));
       }
     }
   return TFHE_HIP_OK;
@@ -615,6 +639,9 @@ int circ_pool_levels(tfhe_hip_pool *pool, int home, tfhe_hip_circuit *c, CircPla
       if (rc != TFHE_HIP_OK) return pool_fail(pool, rc, std::string("home member: ") + tfhe_hip_last_error(hb));
       if (l.kind == CL_NKS) rc = tfhe_hip_pool_batch_gates_mixed_nks_dev(pool, home, d.code, sa, sb, out, count, s);
       else if (l.kind == CL_GATE) rc = tfhe_hip_pool_batch_gates_mixed_dev(pool, home, d.code, sa, sb, out, count, s);
+      else if (l.n_luts)
+        rc = tfhe_hip_pool_batch_lincomb_bootstrap_many_dev(pool, home, l.ca, sa, l.cb, two ? sb : nullptr, l.cc, d.tv, 0,
+                                                            (int)l.n_luts, 1, out, count, s);
       else
         rc = tfhe_hip_pool_batch_lincomb_bootstrap_dev(pool, home, l.ca, sa, l.cb, two ? sb : nullptr, l.cc, d.tv, 0, 1, out,
                                                        count, s);
@@ -693,6 +720,25 @@ int tfhe_hip_circuit_add_pbs(tfhe_hip_circuit *circ, uint32_t ca, uint32_t a, ui
   n.kind = CN_PBS, n.a = a, n.b = cb ? b : a, n.ca = ca, n.cb = cb, n.cc = cconst, n.lut = lut;
   n.level = 1 + std::max(circ->nodes[a].level, cb ? circ->nodes[b].level : 0);
   return circ_push(circ, std::move(n), wire);
+}
+
+// k consecutive wires wires[0..k-1]: function j of the packed table `lut` (generate_many_lookup_table) of one bootstrap
+int tfhe_hip_circuit_add_pbs_many(tfhe_hip_circuit *circ, uint32_t ca, uint32_t a, uint32_t cb, uint32_t b,
+                                  uint32_t cconst, uint32_t lut, int n_luts, uint32_t *wires) {
+  CIRC_ADD(circ);
+  if (lut_shift_of(n_luts) < 0 || !wires) return TFHE_HIP_EINVAL;
+  if (!circ_wire_ok(circ, a) || (cb && !circ_wire_ok(circ, b)) || lut >= circ->luts.size()) return TFHE_HIP_EINVAL;
+  if (circ->nodes.size() + (size_t)n_luts >= 0x7FFFFFFFu) return TFHE_HIP_EINVAL;
+  CircNode n;
+  n.kind = CN_PBS, n.a = a, n.b = cb ? b : a, n.ca = ca, n.cb = cb, n.cc = cconst, n.lut = lut;
+  n.level = 1 + std::max(circ->nodes[a].level, cb ? circ->nodes[b].level : 0);
+  n.nl = (uint8_t)n_luts;
+  n.head = (uint32_t)circ->nodes.size();
+  for (int j = 0; j < n_luts; ++j) {
+    n.fn = (uint8_t)j;
+    CHK(circ_push(circ, n, wires + j));
+  }
+  return TFHE_HIP_OK;
 }
 
 int tfhe_hip_circuit_add_lincomb(tfhe_hip_circuit *circ, const uint32_t *coefs, const uint32_t *wires, size_t n_terms,

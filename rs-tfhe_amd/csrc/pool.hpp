@@ -942,6 +942,42 @@ int tfhe_hip_pool_batch_lincomb_bootstrap(tfhe_hip_pool *p, uint32_t ca, const u
   });
 }
 
+// many-LUT bootstrap: the checks of the single-context entry points, in their order
+int pool_many_checks(tfhe_hip_pool *p, const uint32_t *a, uint32_t cb, const uint32_t *b, const uint32_t *testvec,
+                     int n_luts, const uint32_t *out, size_t count) {
+  if (lut_shift_of(n_luts) < 0) return pool_fail(p, TFHE_HIP_EINVAL, "n_luts must be 1, 2, 4 or 8");
+  if (!testvec) return pool_fail(p, TFHE_HIP_EINVAL, "many-LUT bootstrap needs a test vector");
+  if (cb && !b) return pool_fail(p, TFHE_HIP_EINVAL, "null pointer");
+  if (count && (!a || !out)) return pool_fail(p, TFHE_HIP_EINVAL, "null pointer");
+  if (count > 0x7FFFFFFFull || (count << lut_shift_of(n_luts)) > 0x7FFFFFFFull)
+    return pool_fail(p, TFHE_HIP_EINVAL, "n_luts * count too large");
+  return TFHE_HIP_OK;
+}
+
+// Rows are cut as for tfhe_hip_pool_batch_lincomb_bootstrap (no combining: many-LUT calls are never merged).  A
+// member's result is [k][m]: function j of its shard goes to rows j * count + lo of the caller's [k][count].
+int tfhe_hip_pool_batch_lincomb_bootstrap_many(tfhe_hip_pool *p, uint32_t ca, const uint32_t *a, uint32_t cb,
+                                               const uint32_t *b, uint32_t cconst, const uint32_t *testvec, int per_ct,
+                                               int n_luts, int keyswitch, uint32_t *out, size_t count) {
+  POOL_ENTER(p);
+  CHK(pool_many_checks(p, a, cb, b, testvec, n_luts, out, count));
+  const size_t w = (size_t)p->ctxs[0]->P.n + 1;
+  const size_t tvs = per_ct ? (size_t)2 * kN : 0;
+  return pool_map(p, count, [&](tfhe_hip_ctx *c, size_t lo, size_t hi) {
+    const size_t m = hi - lo;
+    const uint32_t *sa = a + lo * w, *sb = b ? b + lo * w : nullptr, *stv = testvec + lo * tvs;
+    if (m == count)  // one shard: the member writes the caller's layout itself
+      return tfhe_hip_batch_lincomb_bootstrap_many(c, ca, sa, cb, sb, cconst, stv, per_ct, n_luts, keyswitch, out, m);
+    std::vector<uint32_t> part((size_t)n_luts * m * w);
+    const int rc = tfhe_hip_batch_lincomb_bootstrap_many(c, ca, sa, cb, sb, cconst, stv, per_ct, n_luts, keyswitch,
+                                                         part.data(), m);
+    if (rc != TFHE_HIP_OK) return rc;
+    for (int j = 0; j < n_luts; ++j)
+      memcpy(out + ((size_t)j * count + lo) * w, part.data() + (size_t)j * m * w, m * w * 4);
+    return TFHE_HIP_OK;
+  });
+}
+
 int tfhe_hip_pool_batch_mux(tfhe_hip_pool *p, int naive, const uint32_t *a, const uint32_t *b, const uint32_t *c3,
                             uint32_t *out, size_t count) {
   if (pool_small(p, count)) {
@@ -1039,6 +1075,60 @@ int tfhe_hip_pool_batch_lincomb_bootstrap_dev(tfhe_hip_pool *p, int home, uint32
     return tfhe_hip_batch_lincomb_bootstrap_dev(c, ca, (const uint32_t *)q[0], cb, (const uint32_t *)q[1], cconst,
                                                 (const uint32_t *)q[2], per_ct, keyswitch, (uint32_t *)o, m, s);
   });
+}
+
+// The member results travel as rows of k * (n+1) words ([k][m] per shard).  A batch that is not cut lands in `out` as
+// it is; otherwise it is gathered into a stream-ordered scratch on home and each shard's k slices are put in place
+// with one 2D copy.
+int tfhe_hip_pool_batch_lincomb_bootstrap_many_dev(tfhe_hip_pool *p, int home, uint32_t ca, const uint32_t *a, uint32_t cb,
+                                                   const uint32_t *b, uint32_t cconst, const uint32_t *testvec,
+                                                   int per_ct, int n_luts, int keyswitch, uint32_t *out, size_t count,
+                                                   void *stream) {
+  POOL_ENTER(p);
+  if (home < 0 || home >= (int)p->ctxs.size()) return pool_fail(p, TFHE_HIP_EINVAL, "no such pool member (home)");
+  CHK(pool_many_checks(p, a, cb, b, testvec, n_luts, out, count));
+  const size_t w = ((size_t)p->ctxs[0]->P.n + 1) * 4;
+  const PoolIn ins[5] = {{a, w, true}, {cb ? b : nullptr, w, true}, {testvec, (size_t)2 * kN * 4, per_ct != 0}, {}, {}};
+  auto op = [&](tfhe_hip_ctx *c, const void *const *q, void *o, size_t m, void *s) {
+    return tfhe_hip_batch_lincomb_bootstrap_many_dev(c, ca, (const uint32_t *)q[0], cb, (const uint32_t *)q[1], cconst,
+                                                     (const uint32_t *)q[2], per_ct, n_luts, keyswitch, (uint32_t *)o, m, s);
+  };
+  const int world = pool_world_for(p, count);
+  if (world <= 1) return pool_dev_map(p, home, count, stream, ins, out, w * (size_t)n_luts, op);
+  tfhe_hip_ctx *hctx = p->ctxs[(size_t)home];
+  tfhe_hip_ctx *hbase = hctx->parent ? hctx->parent : hctx;
+  hipStream_t hs = stream ? (hipStream_t)stream : hbase->stream;
+  hipStream_t hrt = hs == hipStreamLegacy ? (hipStream_t) nullptr : hs;  // (the runtime's name for the default stream)
+  int prev = -1;
+  (void)hipGetDevice(&prev);
+  struct Restore {
+    int d;
+    ~Restore() {
+      if (d >= 0) (void)hipSetDevice(d);
+    }
+  } restore{prev};
+  if (hipSetDevice(hctx->device) != hipSuccess) return pool_fail(p, TFHE_HIP_EHIP, "hipSetDevice (home)");
+  unsigned char *tmp = nullptr;
+  const size_t bytes = count * w * (size_t)n_luts;
+  if (hipMallocAsync((void **)&tmp, bytes, hrt) != hipSuccess) {
+    (void)hipGetLastError();
+    return pool_fail(p, TFHE_HIP_ENOMEM, "hipMallocAsync (many-LUT gather)");
+  }
+  int rc = pool_dev_map(p, home, count, stream, ins, tmp, w * (size_t)n_luts, op);
+  (void)hipSetDevice(hctx->device);
+  for (int r = 0; r < world && rc == TFHE_HIP_OK; ++r) {
+    size_t lo, hi;
+    pool_shard(count, r, world, lo, hi);
+    if (hi <= lo) continue;
+    const size_t m = hi - lo;
+    if (hipMemcpy2DAsync((unsigned char *)out + lo * w, count * w, tmp + lo * w * (size_t)n_luts, m * w, m * w,
+                         (size_t)n_luts, hipMemcpyDeviceToDevice, hrt) != hipSuccess) {
+      (void)hipGetLastError();
+      rc = pool_fail(p, TFHE_HIP_EHIP, "hipMemcpy2DAsync (many-LUT gather)");
+    }
+  }
+  (void)hipFreeAsync(tmp, hrt);
+  return rc;
 }
 
 int tfhe_hip_pool_batch_mux_dev(tfhe_hip_pool *p, int home, int naive, const uint32_t *a, const uint32_t *b,

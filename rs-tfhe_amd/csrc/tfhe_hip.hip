@@ -340,11 +340,17 @@ int br_waves(const tfhe_hip_ctx *ctx) { return br_is_l1(ctx) ? kL1Waves : kBrWav
 constexpr bool br_is_l1(const tfhe_hip_ctx *) { return false; }
 constexpr int br_waves(const tfhe_hip_ctx *) { return kBrWaves; }
 #endif
-br_kernel_t br_kernel(const tfhe_hip_ctx *ctx) {
+// many: the many-LUT instantiation (BlindRotateArgs::lut_shift / n_luts / out_fn_stride) of the same kernel
+br_kernel_t br_kernel(const tfhe_hip_ctx *ctx, bool many = false) {
   const bool f = ctx->fast_round;
 #if defined(TFHE_EXPERIMENT) && defined(TFHE_EXP_L1)
-  if (br_is_l1(ctx)) return f ? k_blind_rotate_l1<true> : k_blind_rotate_l1<false>;
+  if (br_is_l1(ctx)) return many ? nullptr : f ? k_blind_rotate_l1<true> : k_blind_rotate_l1<false>;
 #endif
+  if (many) switch (ctx->P.l) {
+      case 1: return f ? k_blind_rotate_many<1, true> : k_blind_rotate_many<1, false>;
+      case 2: return f ? k_blind_rotate_many<2, true> : k_blind_rotate_many<2, false>;
+      default: return f ? k_blind_rotate_many<3, true> : k_blind_rotate_many<3, false>;
+    }
   switch (ctx->P.l) {
     case 1: return f ? k_blind_rotate<1, true> : k_blind_rotate<1, false>;
     case 2: return f ? k_blind_rotate<2, true> : k_blind_rotate<2, false>;
@@ -352,8 +358,13 @@ br_kernel_t br_kernel(const tfhe_hip_ctx *ctx) {
   }
 }
 
-br_kernel_t br_pair_kernel(const tfhe_hip_ctx *ctx) {
+br_kernel_t br_pair_kernel(const tfhe_hip_ctx *ctx, bool many = false) {
   const bool f = ctx->fast_round;
+  if (many) switch (ctx->P.l) {
+      case 1: return f ? k_blind_rotate_pair<1, true, true> : k_blind_rotate_pair<1, false, true>;
+      case 2: return f ? k_blind_rotate_pair<2, true, true> : k_blind_rotate_pair<2, false, true>;
+      default: return f ? k_blind_rotate_pair<3, true, true> : k_blind_rotate_pair<3, false, true>;
+    }
   switch (ctx->P.l) {
     case 1: return f ? k_blind_rotate_pair<1, true> : k_blind_rotate_pair<1, false>;
     case 2: return f ? k_blind_rotate_pair<2, true> : k_blind_rotate_pair<2, false>;
@@ -361,8 +372,13 @@ br_kernel_t br_pair_kernel(const tfhe_hip_ctx *ctx) {
   }
 }
 
-br_kernel_t br_single_kernel(const tfhe_hip_ctx *ctx) {
+br_kernel_t br_single_kernel(const tfhe_hip_ctx *ctx, bool many = false) {
   const bool f = ctx->fast_round;
+  if (many) switch (ctx->P.l) {
+      case 1: return f ? k_blind_rotate_wide2_many<1, true> : k_blind_rotate_wide2_many<1, false>;
+      case 2: return f ? k_blind_rotate_wide2_many<2, true> : k_blind_rotate_wide2_many<2, false>;
+      default: return f ? k_blind_rotate_wide2_many<3, true> : k_blind_rotate_wide2_many<3, false>;
+    }
 #if defined(TFHE_EXPERIMENT) && defined(TFHE_EXP_WIDE1)  // the superseded one-wave-per-row latency kernel (profiles/exp/superseded/blind_rotate_wide1.hpp)
   if (ctx->exp_wide1) switch (ctx->P.l) {
       case 1: return f ? k_blind_rotate_wide<1, true> : k_blind_rotate_wide<1, false>;
@@ -463,9 +479,12 @@ int launch_blind_rotate(tfhe_hip_ctx *ctx, hipStream_t s, const uint32_t *in_a, 
                         GatePrep gp, const uint32_t *testvec, int per_ct, size_t count,
                         uint32_t *out_trlwe, uint32_t *out_lv1, uint32_t *out_ext2,
                         const uint8_t *gate_codes = nullptr, const uint32_t *idx_a = nullptr,
-                        const uint32_t *idx_b = nullptr) {
+                        const uint32_t *idx_b = nullptr, int lut_shift = 0) {
   if (count == 0) return TFHE_HIP_OK;
   if (count > 0x7FFFFFFFull) return fail(ctx, TFHE_HIP_EINVAL, "count too large");
+  // many-LUT (lut_shift > 0): 2^lut_shift extractions per ciphertext, function-major [2^lut_shift][count] rows
+  if (lut_shift < 0 || lut_shift > 3) return fail(ctx, TFHE_HIP_EINVAL, "n_luts must be 1, 2, 4 or 8");
+  if (((size_t)count << lut_shift) > 0x7FFFFFFFull) return fail(ctx, TFHE_HIP_EINVAL, "n_luts * count too large");
   BlindRotateArgs A;
   A.in_a = in_a;
   A.in_b = gp.cb ? in_b : nullptr;
@@ -486,6 +505,13 @@ int launch_blind_rotate(tfhe_hip_ctx *ctx, hipStream_t s, const uint32_t *in_a, 
   A.out_lv1 = out_lv1;
   A.out_ext2 = out_ext2;
   A.count = count;
+  A.lut_shift = lut_shift;
+  A.n_luts = 1 << lut_shift;
+  A.out_fn_stride = count;  // the whole call's: part() moves the output bases, not the stride
+  const bool many = lut_shift > 0;
+#if defined(TFHE_EXPERIMENT) && defined(TFHE_EXP_L1)
+  if (many && br_is_l1(ctx)) return fail(ctx, TFHE_HIP_EINVAL, "the l = 1 experiment kernel has no many-LUT epilogue");
+#endif
   A.clk = ctx->profiling ? ctx->d_diag : nullptr;
   A.err_flag = reinterpret_cast<uint32_t *>(ctx->d_diag + 2);
   // sample_extract_index_2 reads a[n - i] of an N-coefficient polynomial (trlwe.rs:122-136): the reference
@@ -536,17 +562,18 @@ int launch_blind_rotate(tfhe_hip_ctx *ctx, hipStream_t s, const uint32_t *in_a, 
 #endif
     const size_t begin = pl.begin[q], m_all = pl.count[q];
     if (pl.kind[q] == BR_PAIR) {
-      CHK(launch(br_pair_kernel(ctx), (unsigned)((m_all + 1) / 2), 64u * kPairWaves, blind_rotate_pair_lds_bytes(ctx->P.n),
+      CHK(launch(br_pair_kernel(ctx, many), (unsigned)((m_all + 1) / 2), 64u * kPairWaves, blind_rotate_pair_lds_bytes(ctx->P.n),
                  part(begin, m_all)));
     } else if (pl.kind[q] == BR_SINGLE) {
 #if defined(TFHE_EXPERIMENT) && defined(TFHE_EXP_WIDE1)
       if (ctx->exp_wide1) {
+        if (lut_shift) return fail(ctx, TFHE_HIP_EINVAL, "the one-wave-per-row experiment kernel has no many-LUT epilogue");
         CHK(launch(br_single_kernel(ctx), (unsigned)m_all, 128u * (unsigned)ctx->P.l,
                    blind_rotate_wide_lds_bytes(ctx->P.n, ctx->P.l), part(begin, m_all)));
         continue;
       }
 #endif
-      CHK(launch(br_single_kernel(ctx), (unsigned)m_all, 64u * kWide2Waves, blind_rotate_wide2_lds_bytes(ctx->P.n, ctx->P.l),
+      CHK(launch(br_single_kernel(ctx, many), (unsigned)m_all, 64u * kWide2Waves, blind_rotate_wide2_lds_bytes(ctx->P.n, ctx->P.l),
                  part(begin, m_all)));
     } else {
       // Default: ONE launch of the whole part.  The four waves of a workgroup meet at a barrier every CMUX step
@@ -566,7 +593,7 @@ int launch_blind_rotate(tfhe_hip_ctx *ctx, hipStream_t s, const uint32_t *in_a, 
       for (size_t done = 0; done < m_all; done += chunk) {
         const size_t m = (m_all - done < chunk) ? m_all - done : chunk;
         const unsigned bw = (unsigned)br_waves(ctx);
-        CHK(launch(br_kernel(ctx), (unsigned)((m + bw - 1) / bw), 64u * bw, lds, part(begin + done, m)));
+        CHK(launch(br_kernel(ctx, many), (unsigned)((m + bw - 1) / bw), 64u * bw, lds, part(begin + done, m)));
       }
     }
   }
@@ -926,6 +953,46 @@ int lincomb_bootstrap_dev(tfhe_hip_ctx *ctx, GatePrep gp, const uint32_t *a, con
   return launch_blind_rotate(ctx, s, a, b, gp, testvec, per_ct, count, nullptr, nullptr, out);
 }
 
+// Many-LUT bootstrap (PBS-manyLUT): ONE blind rotation per ciphertext with the rotation amounts rounded to multiples of
+// 2^lut_shift, then 2^lut_shift sample extractions (function-major into lv1 or out) and one key switch over all rows.
+int lincomb_bootstrap_many_dev(tfhe_hip_ctx *ctx, GatePrep gp, const uint32_t *a, const uint32_t *b,
+                               const uint32_t *testvec, int per_ct, int lut_shift, int keyswitch, uint32_t *out,
+                               size_t count, hipStream_t s) {
+  const size_t rows = count << lut_shift;
+  if (keyswitch) {
+    CHK(claim_scratch(ctx, s));
+    CHK(ensure(ctx, ctx->lv1, lv1_rows(rows) * (size_t)(kN + 1) * 4));
+    CHK(launch_blind_rotate(ctx, s, a, b, gp, testvec, per_ct, count, nullptr, (uint32_t *)ctx->lv1.p, nullptr, nullptr,
+                            nullptr, nullptr, lut_shift));
+    return launch_key_switch(ctx, s, (const uint32_t *)ctx->lv1.p, out, rows);
+  }
+  return launch_blind_rotate(ctx, s, a, b, gp, testvec, per_ct, count, nullptr, nullptr, out, nullptr, nullptr, nullptr,
+                             lut_shift);
+}
+
+// n_luts in {1, 2, 4, 8} -> log2, else -1
+int lut_shift_of(int n_luts) {
+  switch (n_luts) {
+    case 1: return 0;
+    case 2: return 1;
+    case 4: return 2;
+    case 8: return 3;
+    default: return -1;
+  }
+}
+
+// the checks of the many-LUT entry points, in one order for the host, device and pool forms
+int many_checks(tfhe_hip_ctx *ctx, const uint32_t *a, uint32_t cb, const uint32_t *b, const uint32_t *testvec,
+                int n_luts, const uint32_t *out, size_t count) {
+  const int shift = lut_shift_of(n_luts);
+  if (shift < 0) return fail(ctx, TFHE_HIP_EINVAL, "n_luts must be 1, 2, 4 or 8");
+  if (!testvec) return fail(ctx, TFHE_HIP_EINVAL, "many-LUT bootstrap needs a test vector");
+  if (cb && !b) return fail(ctx, TFHE_HIP_EINVAL, "null pointer");
+  if (count && (!a || !out)) return fail(ctx, TFHE_HIP_EINVAL, "null pointer");
+  if ((count << shift) > 0x7FFFFFFFull || count > 0x7FFFFFFFull) return fail(ctx, TFHE_HIP_EINVAL, "n_luts * count too large");
+  return TFHE_HIP_OK;
+}
+
 int lincomb_dev(tfhe_hip_ctx *ctx, GatePrep gp, const uint32_t *a, const uint32_t *b, uint32_t *out, size_t count,
                 hipStream_t s) {
   if (count == 0) return TFHE_HIP_OK;
@@ -1276,6 +1343,13 @@ int tfhe_hip_ctx_create(const tfhe_hip_params *p, int device, tfhe_hip_ctx **out
       return bail("hipFuncSetAttribute(k_blind_rotate_wide2)", e);
     if (ctx->pair_max && (e = set_lds((const void *)br_pair_kernel(ctx), blind_rotate_pair_lds_bytes(kMaxN))) != hipSuccess)
       return bail("hipFuncSetAttribute(k_blind_rotate_pair)", e);
+    // the many-LUT instantiations of the three kernels (same LDS layouts)
+    if (!br_is_l1(ctx) && (e = set_lds((const void *)br_kernel(ctx, true), blind_rotate_lds_bytes(kMaxN))) != hipSuccess)
+      return bail("hipFuncSetAttribute(k_blind_rotate_many)", e);
+    if ((e = set_lds((const void *)br_single_kernel(ctx, true), blind_rotate_wide2_lds_bytes(kMaxN, p->l))) != hipSuccess)
+      return bail("hipFuncSetAttribute(k_blind_rotate_wide2_many)", e);
+    if (ctx->pair_max && (e = set_lds((const void *)br_pair_kernel(ctx, true), blind_rotate_pair_lds_bytes(kMaxN))) != hipSuccess)
+      return bail("hipFuncSetAttribute(k_blind_rotate_pair_many)", e);
     if (ks_sliced_fits(*p))
       for (int sets : {24, 28, 32, 36})
         if ((e = set_lds((const void *)sl2_kernel(p->basebit, sets), ks_sl2_lds_bytes(p->basebit, sets, ks_sl2_rp(p->basebit)))) != hipSuccess)
@@ -1717,6 +1791,17 @@ int tfhe_hip_batch_lincomb_bootstrap_dev(tfhe_hip_ctx *ctx, uint32_t ca, const u
                                count, pick(ctx, stream));
 }
 
+int tfhe_hip_batch_lincomb_bootstrap_many_dev(tfhe_hip_ctx *ctx, uint32_t ca, const uint32_t *a, uint32_t cb,
+                                              const uint32_t *b, uint32_t cconst, const uint32_t *testvec, int per_ct,
+                                              int n_luts, int keyswitch, uint32_t *out, size_t count, void *stream) {
+  if (!ctx) return TFHE_HIP_EINVAL;
+  ENTER(ctx);
+  CHK(need_key(ctx));
+  CHK(many_checks(ctx, a, cb, b, testvec, n_luts, out, count));
+  return lincomb_bootstrap_many_dev(ctx, GatePrep{ca, cb, cconst}, a, cb ? b : nullptr, testvec, per_ct,
+                                    lut_shift_of(n_luts), keyswitch, out, count, pick(ctx, stream));
+}
+
 int tfhe_hip_batch_blind_rotate_dev(tfhe_hip_ctx *ctx, const uint32_t *in, const uint32_t *testvec,
                                     uint32_t *out_trlwe, size_t count, void *stream) {
   if (!ctx) return TFHE_HIP_EINVAL;
@@ -1920,6 +2005,23 @@ int tfhe_hip_batch_lincomb_bootstrap(tfhe_hip_ctx *ctx, uint32_t ca, const uint3
   return host_call(ctx, false, in, out, bytes, [&](const void *const *d, void *o) {
     return lincomb_bootstrap_dev(ctx, GatePrep{ca, cb, cconst}, u32(d[0]), u32(d[1]), u32(d[2]), per_ct, keyswitch,
                                  (uint32_t *)o, count, ctx->stream);
+  });
+}
+
+int tfhe_hip_batch_lincomb_bootstrap_many(tfhe_hip_ctx *ctx, uint32_t ca, const uint32_t *a, uint32_t cb,
+                                          const uint32_t *b, uint32_t cconst, const uint32_t *testvec, int per_ct,
+                                          int n_luts, int keyswitch, uint32_t *out, size_t count) {
+  if (!ctx) return TFHE_HIP_EINVAL;  // (never combined: the merged launches have no many-LUT form)
+  ENTER(ctx);
+  CHK(need_key(ctx));
+  CHK(many_checks(ctx, a, cb, b, testvec, n_luts, out, count));
+  if (count == 0) return TFHE_HIP_OK;
+  const size_t bytes = count * (size_t)(ctx->P.n + 1) * 4;
+  const HostIn in[] = {{a, bytes, &ctx->a}, {cb ? b : nullptr, bytes, &ctx->b},
+                       {testvec, (per_ct ? count : 1) * (size_t)2 * kN * 4, &ctx->tv}};
+  return host_call(ctx, false, in, out, bytes * (size_t)n_luts, [&](const void *const *d, void *o) {
+    return lincomb_bootstrap_many_dev(ctx, GatePrep{ca, cb, cconst}, u32(d[0]), u32(d[1]), u32(d[2]), per_ct,
+                                      lut_shift_of(n_luts), keyswitch, (uint32_t *)o, count, ctx->stream);
   });
 }
 

@@ -58,6 +58,28 @@ def pinned_empty(shape, dtype=np.uint32) -> np.ndarray:
     return arr
 
 
+def _many_args(a, b, cb, testvec, cts):
+    """Host operands of a many-LUT call (n_luts, a NULL table and the rest are checked by the library)."""
+    a = cts(a)
+    bb = cts(b) if b is not None else None
+    if (cb & 0xFFFFFFFF) and bb is not None and bb.shape != a.shape:
+        raise ValueError("second operand of a different shape")
+    tv, per_ct = None, 0
+    if testvec is not None:
+        tv = _u32(testvec)
+        per_ct = int(tv.ndim == 3)
+        if tv.size != (len(a) if per_ct else 1) * 2 * N:
+            raise ValueError("test vector must be [2][N], or [count][2][N] for per-ciphertext tables")
+    return a, bb, tv, per_ct
+
+
+def _many_dev_check(out, testvec, count: int, n_luts: int, per_ct: bool, width: int, device: int) -> None:
+    if out is None or out.numel() != max(int(n_luts), 1) * count * width or out.device.index != device:
+        raise ValueError(f"out must be [n_luts * count][{width}] on cuda:{device}")
+    if testvec is not None and testvec.numel() != (count if per_ct else 1) * 2 * N:
+        raise ValueError("test vector must be [2][N], or [count][2][N] with per_ct")
+
+
 def _out_like(a: np.ndarray, out) -> np.ndarray:
     if out is None:
         return np.empty_like(a)
@@ -324,6 +346,18 @@ class Engine:
             int(keyswitch), _ptr(out), len(a)))
         return out
 
+    def batch_lincomb_bootstrap_many(self, ca: int, a, cb: int = 0, b=None, cconst: int = 0, testvec=None,
+                                     n_luts: int = 2, keyswitch: bool = True) -> np.ndarray:
+        """Many-LUT bootstrap of ca*a + cb*b + cconst: n_luts functions packed in `testvec`
+        (Generator.generate_many_lookup_table) from ONE blind rotation each.  Returns [n_luts][count][n+1]:
+        [j] is what batch_lincomb_bootstrap would give for function j alone (tfhe_hip_batch_lincomb_bootstrap_many)."""
+        a, bb, tv, per_ct = _many_args(a, b, cb, testvec, self._cts)
+        out = np.empty((int(n_luts),) + a.shape, np.uint32) if n_luts in (1, 2, 4, 8) else np.empty(1, np.uint32)
+        self._chk(self._lib.tfhe_hip_batch_lincomb_bootstrap_many(
+            self._ctx, ca & 0xFFFFFFFF, _ptr(a), cb & 0xFFFFFFFF, _ptr(bb), cconst & 0xFFFFFFFF, _ptr(tv), per_ct,
+            int(n_luts), int(keyswitch), _ptr(out), len(a)))
+        return out
+
     def batch_blind_rotate(self, cts, testvec=None) -> np.ndarray:
         cts = self._cts(cts)
         out = np.empty((len(cts), 2, N), np.uint32)
@@ -483,6 +517,16 @@ class Engine:
         self._chk(self._lib.tfhe_hip_batch_lincomb_bootstrap_dev(
             self._ctx, ca & 0xFFFFFFFF, self._tp(a), cb & 0xFFFFFFFF, self._tp(b), cconst & 0xFFFFFFFF, self._tp(testvec),
             int(per_ct), int(keyswitch), self._tp(out), count, self._stream_ptr(stream)))
+
+    def batch_lincomb_bootstrap_many_dev(self, ca: int, a, cb: int, b, cconst: int, out, testvec, n_luts: int = 2,
+                                         per_ct: bool = False, keyswitch: bool = True, stream=None) -> None:
+        """Device form of batch_lincomb_bootstrap_many: out is an int32 CUDA tensor [n_luts * count][n+1] (or
+        [n_luts][count][n+1]), function-major."""
+        count = self._dev_batch(a, b)
+        _many_dev_check(out, testvec, count, n_luts, per_ct, self.params.n + 1, self.device)
+        self._chk(self._lib.tfhe_hip_batch_lincomb_bootstrap_many_dev(
+            self._ctx, ca & 0xFFFFFFFF, self._tp(a), cb & 0xFFFFFFFF, self._tp(b), cconst & 0xFFFFFFFF, self._tp(testvec),
+            int(per_ct), int(n_luts), int(keyswitch), self._tp(out), count, self._stream_ptr(stream)))
 
     def batch_blind_rotate_dev(self, cts, out_trlwe, testvec=None, stream=None) -> None:
         count = self._dev_batch(cts)
@@ -730,6 +774,16 @@ class Pool:
             int(keyswitch), _ptr(out), len(a)))
         return out
 
+    def batch_lincomb_bootstrap_many(self, ca: int, a, cb: int = 0, b=None, cconst: int = 0, testvec=None,
+                                     n_luts: int = 2, keyswitch: bool = True) -> np.ndarray:
+        """Engine.batch_lincomb_bootstrap_many over the members: [n_luts][count][n+1]."""
+        a, bb, tv, per_ct = _many_args(a, b, cb, testvec, self._cts)
+        out = np.empty((int(n_luts),) + a.shape, np.uint32) if n_luts in (1, 2, 4, 8) else np.empty(1, np.uint32)
+        self._chk(self._lib.tfhe_hip_pool_batch_lincomb_bootstrap_many(
+            self._h, ca & 0xFFFFFFFF, _ptr(a), cb & 0xFFFFFFFF, _ptr(bb), cconst & 0xFFFFFFFF, _ptr(tv), per_ct,
+            int(n_luts), int(keyswitch), _ptr(out), len(a)))
+        return out
+
     def batch_bootstrap(self, cts, testvec=None, keyswitch: bool = True) -> np.ndarray:
         cts = self._cts(cts)
         out = np.empty_like(cts)
@@ -846,6 +900,16 @@ class Pool:
         self._chk(self._lib.tfhe_hip_pool_batch_lincomb_bootstrap_dev(
             self._h, h, ca & 0xFFFFFFFF, self._tp(h, a), cb & 0xFFFFFFFF, self._tp(h, b), cconst & 0xFFFFFFFF,
             self._tp(h, testvec), int(per_ct), int(keyswitch), self._tp(h, out), count, self._stream_ptr(h, stream)))
+
+    def batch_lincomb_bootstrap_many_dev(self, ca: int, a, cb: int, b, cconst: int, out, testvec, n_luts: int = 2,
+                                         per_ct: bool = False, keyswitch: bool = True, stream=None, home=None) -> None:
+        h = self._home(home)
+        count = self._dev_batch(h, a, b)
+        _many_dev_check(out, testvec, count, n_luts, per_ct, self.params.n + 1, self.devices[h])
+        self._chk(self._lib.tfhe_hip_pool_batch_lincomb_bootstrap_many_dev(
+            self._h, h, ca & 0xFFFFFFFF, self._tp(h, a), cb & 0xFFFFFFFF, self._tp(h, b), cconst & 0xFFFFFFFF,
+            self._tp(h, testvec), int(per_ct), int(n_luts), int(keyswitch), self._tp(h, out), count,
+            self._stream_ptr(h, stream)))
 
     def batch_mux_dev(self, a, b, c, out, naive: bool, stream=None, home=None) -> None:
         h = self._home(home)

@@ -99,6 +99,37 @@ class Generator:
         m = self.message_modulus
         return self._assemble([self.encoder.encode(f(x)) for x in range(m)])
 
+    def generate_many_lookup_table(self, fs) -> LookupTable:
+        """One table for k = len(fs) functions of the same input (PBS-manyLUT; tfhe-rs apply_many_lookup_table), for
+        Engine.batch_lincomb_bootstrap_many: position r of message x's box holds encode(fs[r mod k](x)), then the
+        half-box rotation and negacyclic negation of generate_lookup_table.  k must be 1, 2, 4 or 8, and the rotation
+        must keep the residues mod k: N / (2m) % k == 0.  k = 1 is generate_lookup_table's table.  A k-LUT of modulus
+        m fails like a single LUT of modulus m * k (the rotation is rounded to multiples of k): on SECURITY_UINT4 keep
+        m * k <= 16."""
+        fs = list(fs)
+        k = len(fs)
+        if k not in (1, 2, 4, 8):
+            raise ValueError("generate_many_lookup_table: 1, 2, 4 or 8 functions")
+        m = self.message_modulus
+        size = self.lookup_table_size
+        if k == 1:
+            return self.generate_lookup_table(fs[0])
+        if size % (2 * m) or (size // (2 * m)) % k:
+            raise ValueError(f"generate_many_lookup_table: N / (2m) = {size / (2 * m)} is not a multiple of k = {k}")
+        raw = np.zeros(size, np.uint32)
+        for x in range(m):
+            start = div_round(x * size, m)
+            end = min(div_round((x + 1) * size, m), size)
+            vals = [self.encoder.encode(f(x)) for f in fs]
+            for r in range(end - start):
+                raw[start + r] = vals[r % k]
+        offset = div_round(size, 2 * m)
+        rot = raw[(np.arange(size) + offset) % size].copy()
+        rot[size - offset:] = (0 - rot[size - offset:].astype(np.int64)).astype(np.uint32)  # wrapping_neg
+        lut = LookupTable()
+        lut.poly[1, :] = rot
+        return lut
+
     def generate_lookup_table_assign(self, f, lut_out: LookupTable) -> None:  # generator.rs:89-137: into an existing table
         lut_out.copy_from(self.generate_lookup_table(f))
 

@@ -61,6 +61,15 @@ extern "C" {   // include/tfhe_hip.h, the tfhe_hip_pool_* family: one handle, 1.
                                                  cb: u32, b: *const u32, cconst: u32, testvec: *const u32,
                                                  per_ct: c_int, keyswitch: c_int, out: *mut u32, count: usize,
                                                  stream: *mut c_void) -> c_int;
+    // many-LUT bootstrap: n_luts functions packed in one test vector from one blind rotation, out [n_luts][count][n+1]
+    fn tfhe_hip_pool_batch_lincomb_bootstrap_many(pool: *mut TfheHipPool, ca: u32, a: *const u32, cb: u32,
+                                                  b: *const u32, cconst: u32, testvec: *const u32, per_ct: c_int,
+                                                  n_luts: c_int, keyswitch: c_int, out: *mut u32, count: usize) -> c_int;
+    fn tfhe_hip_pool_batch_lincomb_bootstrap_many_dev(pool: *mut TfheHipPool, home_member: c_int, ca: u32,
+                                                      a: *const u32, cb: u32, b: *const u32, cconst: u32,
+                                                      testvec: *const u32, per_ct: c_int, n_luts: c_int,
+                                                      keyswitch: c_int, out: *mut u32, count: usize,
+                                                      stream: *mut c_void) -> c_int;
     fn tfhe_hip_pool_batch_mux_dev(pool: *mut TfheHipPool, home_member: c_int, naive: c_int, a: *const u32,
                                    b: *const u32, c: *const u32, out: *mut u32, count: usize,
                                    stream: *mut c_void) -> c_int;
@@ -410,6 +419,8 @@ extern "C" {   // include/tfhe_hip.h, the tfhe_hip_circuit_* family: built on th
     fn tfhe_hip_circuit_add_lut(circ: *mut TfheHipCircuit, testvec: *const u32, lut: *mut u32) -> c_int;
     fn tfhe_hip_circuit_add_pbs(circ: *mut TfheHipCircuit, ca: u32, a: u32, cb: u32, b: u32, cconst: u32, lut: u32,
                                 wire: *mut u32) -> c_int;
+    fn tfhe_hip_circuit_add_pbs_many(circ: *mut TfheHipCircuit, ca: u32, a: u32, cb: u32, b: u32, cconst: u32, lut: u32,
+                                     n_luts: c_int, wires: *mut u32) -> c_int;
     fn tfhe_hip_circuit_add_lincomb(circ: *mut TfheHipCircuit, coefs: *const u32, wires: *const u32, n_terms: usize,
                                     cconst: u32, wire: *mut u32) -> c_int;
     fn tfhe_hip_circuit_add_not(circ: *mut TfheHipCircuit, a: u32, wire: *mut u32) -> c_int;
@@ -462,6 +473,14 @@ impl HipCircuit {
         let mut w = 0u32;
         let rc = unsafe { tfhe_hip_circuit_add_pbs(self.h, ca, a, cb, b, cconst, lut, &mut w) };
         Self::node(rc, w)
+    }
+    /// Many-LUT bootstrap: the n_luts (1, 2, 4 or 8) functions packed in `lut` of ca*a + cb*b + cconst from ONE blind
+    /// rotation; returns the n_luts consecutive wires, function j at [j]
+    pub fn pbs_many(&mut self, ca: u32, a: u32, cb: u32, b: u32, cconst: u32, lut: u32, n_luts: usize) -> Vec<u32> {
+        let mut w = vec![0u32; n_luts];
+        let rc = unsafe { tfhe_hip_circuit_add_pbs_many(self.h, ca, a, cb, b, cconst, lut, n_luts as c_int, w.as_mut_ptr()) };
+        Self::node(rc, 0);
+        w
     }
     /// sum coef * wire + cconst (TLWE `+` / `-`): no bootstrap
     pub fn lincomb(&mut self, terms: &[(u32, u32)], cconst: u32) -> u32 {
