@@ -128,6 +128,21 @@ inline TRLWELv1 gen_testvec() {
   return tv;
 }
 
+// The seeded (compressed) form of a cloud key (include/tfhe_hip.h): the public mask seed plus the bodies; the device
+// regenerates the masks on load.  About a tenth of CloudKey's bytes on SECURITY_128_BIT.
+struct CompressedCloudKey {
+  SecurityParams params = DEFAULT_SECURITY;
+  std::array<uint8_t, 32> mask_seed{};
+  std::vector<Torus> bsk_bodies;  // [n][2l][N]
+  std::vector<Torus> ksk_bodies;  // [N][t][base] (k = 0 slots ignored)
+  Torus decomposition_offset = 0;
+  TRLWELv1 blind_rotate_testvec = gen_testvec();
+  size_t nbytes() const { return (bsk_bodies.size() + ksk_bodies.size()) * sizeof(Torus) + mask_seed.size(); }
+  bool matches(const SecurityParams &p) const {
+    return params == p && bsk_bodies.size() == (size_t)p.n * 2 * p.l * N && ksk_bodies.size() == N * (size_t)p.iks_t * p.base();
+  }
+};
+
 // ---- engine handle: ONE C-ABI context per (parameter set, device); every cloud key is a key view of it ------
 // The reference passes `&CloudKey` into every call and its strategies are `Send + Sync`
 // (bootstrap/mod.rs:23).  The C ABI's answer is the KEY VIEW (tfhe_hip_key_create, include/tfhe_hip.h): another
@@ -138,7 +153,7 @@ inline TRLWELv1 gen_testvec() {
 class Engine {
   struct View {
     tfhe_hip_ctx *h = nullptr;
-    const CloudKey *key = nullptr;  // `&CloudKey` identity, as the reference borrows it ...
+    const void *key = nullptr;      // `&CloudKey` (or `&CompressedCloudKey`) identity, as the reference borrows it ...
     uint64_t fp = 0;                // ... plus a content sample: an address can be reused by a different key
     uint64_t last_use = 0;
     int users = 0;  // calls in flight (registry lock): never evicted while > 0
@@ -175,6 +190,10 @@ class Engine {
     void with_key(const CloudKey &, F &&call) {
       e_->check(call(v_->h));
     }
+    template <class F>
+    void with_key(const CompressedCloudKey &, F &&call) {
+      e_->check(call(v_->h));
+    }
     tfhe_hip_ctx *handle() const { return v_->h; }
     tfhe_hip_ctx *context() const { return e_->ctx_; }
 
@@ -206,14 +225,39 @@ class Engine {
   // the key view that holds `ck` (by address and content sample) on the one context of its parameter set and
   // device: found, or created (dropping the least recently used idle view beyond kMaxResidentKeys) and loaded
   static Bound for_key(const CloudKey &ck, int device = 0) {
-    const uint64_t fp = fingerprint(ck);
+    return bind(&ck, fingerprint(ck), ck.params, device, [&](tfhe_hip_ctx *h) {
+      const SecurityParams &p = ck.params;
+      if (ck.bootstrapping_key.size() != (size_t)p.n * 2 * p.l * 2 * N ||
+          ck.key_switching_key.size() != N * (size_t)p.iks_t * p.base() * (p.n + 1))
+        throw std::runtime_error("CloudKey does not match the parameter set");
+      return tfhe_hip_load_cloud_key(h, ck.bootstrapping_key.data(), ck.key_switching_key.data(), ck.decomposition_offset,
+                                     ck.blind_rotate_testvec.a.data());
+    });
+  }
+  // The same for a key in the seeded form: its view is loaded with tfhe_hip_load_compressed_cloud_key (the bodies
+  // travel, the masks are regenerated on the device) and stays resident like any other; Bound::with_key(ck, call)
+  // runs tfhe_hip_* calls under it.
+  static Bound for_key(const CompressedCloudKey &ck, int device = 0) {
+    return bind(&ck, fingerprint(ck), ck.params, device, [&](tfhe_hip_ctx *h) {
+      if (!ck.matches(ck.params)) throw std::runtime_error("CompressedCloudKey does not match the parameter set");
+      return tfhe_hip_load_compressed_cloud_key(h, ck.mask_seed.data(), ck.bsk_bodies.data(), ck.ksk_bodies.data(),
+                                                ck.decomposition_offset, ck.blind_rotate_testvec.a.data());
+    });
+  }
+  static Bound load_compressed_cloud_key(const CompressedCloudKey &ck, int device = 0) { return for_key(ck, device); }
+
+ private:
+  // the key view of (addr, fp) on the one context of (p, device): found, or created (dropping the least recently used
+  // idle view beyond kMaxResidentKeys) and filled by load(handle)
+  template <class Load>
+  static Bound bind(const void *addr, uint64_t fp, const SecurityParams &params, int device, Load &&load) {
     Engine *e;
     View *v = nullptr;
     {
       std::lock_guard<std::mutex> lk(registry_mu());
-      e = &for_params_locked(ck.params, device);
+      e = &for_params_locked(params, device);
       for (auto &c : e->views_)
-        if (c->key == &ck && c->fp == fp) v = c.get();
+        if (c->key == addr && c->fp == fp) v = c.get();
       if (!v) {
         while (e->views_.size() >= kMaxResidentKeys) {
           size_t victim = e->views_.size();
@@ -230,7 +274,7 @@ class Engine {
           e->views_.pop_back();
           throw std::runtime_error("tfhe_hip_key_create failed");
         }
-        v->key = &ck;
+        v->key = addr;
         v->fp = fp;
       }
       ++v->users;
@@ -239,17 +283,12 @@ class Engine {
     Bound b(e, v);
     if (!tfhe_hip_key_is_loaded(v->h)) {
       std::lock_guard<std::mutex> lk(v->load_mu);  // two threads meeting on a fresh view: one uploads
-      if (!tfhe_hip_key_is_loaded(v->h)) {
-        const SecurityParams &p = ck.params;
-        if (ck.bootstrapping_key.size() != (size_t)p.n * 2 * p.l * 2 * N ||
-            ck.key_switching_key.size() != N * (size_t)p.iks_t * p.base() * (p.n + 1))
-          throw std::runtime_error("CloudKey does not match the parameter set");
-        e->check(tfhe_hip_load_cloud_key(v->h, ck.bootstrapping_key.data(), ck.key_switching_key.data(),
-                                         ck.decomposition_offset, ck.blind_rotate_testvec.a.data()));
-      }
+      if (!tfhe_hip_key_is_loaded(v->h)) e->check(load(v->h));
     }
     return b;
   }
+
+ public:
 
  private:
   static Engine &for_params_locked(const SecurityParams &p, int device) {
@@ -280,6 +319,17 @@ class Engine {
       std::memcpy(&bits, &ck.bootstrapping_key[(nb - 1) * i / 64], sizeof bits);
       mix(bits);
     }
+    mix(nk);
+    mix(nb);
+    return h;
+  }
+  static uint64_t fingerprint(const CompressedCloudKey &ck) {  // the seed, 64 evenly spaced words of each body array, sizes
+    uint64_t h = 0xC2B2AE3D27D4EB4Full ^ ck.decomposition_offset;
+    auto mix = [&](uint64_t v) { h = (h ^ v) * 0x100000001B3ull; };
+    for (size_t i = 0; i < ck.mask_seed.size(); ++i) mix(ck.mask_seed[i]);
+    const size_t nk = ck.ksk_bodies.size(), nb = ck.bsk_bodies.size();
+    for (size_t i = 0; i < 64 && nk; ++i) mix(ck.ksk_bodies[(nk - 1) - (nk - 1) * i / 64]);
+    for (size_t i = 0; i < 64 && nb; ++i) mix(ck.bsk_bodies[(nb - 1) * i / 64]);
     mix(nk);
     mix(nb);
     return h;
@@ -393,6 +443,28 @@ struct SecretKey {
   static SecretKey generate(const SecurityParams &p, uint64_t seed) {  // TESTS ONLY
     ChaChaRng rng(seed);
     return generate(p, rng);
+  }
+  // The cloud key in its seeded form, generated on the GPU (tfhe_hip_gen_compressed_cloud_key) under a generator key
+  // drawn from `rng`, in a key view that is dropped afterwards.
+  CompressedCloudKey compressed_cloud_key(ChaChaRng &rng, int device = 0) const {
+    Engine &e = Engine::for_params(params, device);
+    CompressedCloudKey ck;
+    ck.params = params;
+    ck.bsk_bodies.resize((size_t)params.n * 2 * params.l * N);
+    ck.ksk_bodies.resize(N * (size_t)params.iks_t * params.base());
+    auto k = rng.derive_key();
+    tfhe_hip_ctx *view = nullptr;
+    e.check(tfhe_hip_key_create(e.ctx(), &view));
+    std::unique_ptr<tfhe_hip_ctx, void (*)(tfhe_hip_ctx *)> h(view, tfhe_hip_ctx_destroy);  // dropped on every exit
+    const int rc = tfhe_hip_gen_compressed_cloud_key(view, key_lv0.data(), key_lv1.data(), params.alpha_lv0, params.alpha_lv1,
+                                                     k.data(), ck.mask_seed.data(), ck.bsk_bodies.data(),
+                                                     ck.ksk_bodies.data(), &ck.decomposition_offset);
+    if (rc != TFHE_HIP_OK) throw std::runtime_error(std::string("tfhe_hip: ") + tfhe_hip_last_error(view));
+    return ck;
+  }
+  CompressedCloudKey compressed_cloud_key(int device = 0) const {  // generator key from getrandom(2)
+    ChaChaRng rng;
+    return compressed_cloud_key(rng, device);
   }
 };
 
@@ -832,6 +904,11 @@ class DevicePool {
   void load(const CloudKey &ck) {
     check(tfhe_hip_pool_load_cloud_key(pool_, ck.bootstrapping_key.data(), ck.key_switching_key.data(),
                                        ck.decomposition_offset, ck.blind_rotate_testvec.a.data()));
+  }
+  void load_compressed_cloud_key(const CompressedCloudKey &ck) {  // expanded on the first member, then replicated
+    if (!ck.matches(params_)) throw std::runtime_error("CompressedCloudKey does not match the parameter set");
+    check(tfhe_hip_pool_load_compressed_cloud_key(pool_, ck.mask_seed.data(), ck.bsk_bodies.data(), ck.ksk_bodies.data(),
+                                                  ck.decomposition_offset, ck.blind_rotate_testvec.a.data()));
   }
   // gates::batch_* over every device of the pool, input order kept (gates.rs:352-547)
   std::vector<Ciphertext> batch_gate(int gate, const std::vector<std::pair<Ciphertext, Ciphertext>> &inputs) {

@@ -191,6 +191,60 @@ int tfhe_hip_cloud_key_buffers(tfhe_hip_ctx *ctx, void **bsk, size_t *bsk_bytes,
                                void **testvec, size_t *testvec_bytes, uint32_t *decomp_offset);
 int tfhe_hip_adopt_cloud_key(tfhe_hip_ctx *ctx, uint32_t decomp_offset);
 
+/* ---- seeded (compressed) cloud keys and ciphertexts ----------------------
+ *
+ * Nearly every byte of a cloud key is pseudorandom mask: every KSK row, every TRLWE row of the BSK and every fresh
+ * TLWE ciphertext is (uniform mask, body).  Here the masks are fixed positions of a ChaCha20 keystream under a
+ * PUBLIC 32-byte mask seed S, so only the bodies travel and the device regenerates the masks: 17.35 MB instead of
+ * 172.2 MB on SECURITY_128_BIT, 7.11 MB instead of 349.7 MB on SECURITY_UINT4.  The expanded key is an ordinary
+ * cloud key: every other entry point runs it unchanged, and tfhe_hip_export_cloud_key returns it in full.
+ *
+ * Format (normative).  All keystream words are the RFC 8439 ChaCha20 block function, 20 rounds,
+ * block(key, counter, nonce n0, n1, n2).  A 32-byte seed is read as 8 little-endian u32 key words.  Word x of a row
+ * is word x mod 16 of the block with counter x / 16.
+ *   Mask seed S    32 bytes, public, shipped with the key.
+ *   KSK row r = base*t*i + base*j + k, k >= 1: mask words x < n under S, nonce (r, 16, 0x4B534B); body
+ *                  <a, s0> + gaussian_f64(k * s1[i] / 2^((j+1) basebit)).  k = 0 rows are zero; their body
+ *                  slots are written 0 and ignored on load.
+ *   BSK row r = i*2l + q of TRGSW(s0[i]): mask polynomial a, coefficients c < N under S, nonce (r, 18, 0x42534B).
+ *                  With p = s0[i] and g_d = f64_to_torus(Bg^-(d+1)) the body is
+ *                    q <  l: b = a (*) s1 + e - p*g_q*s1   (every coefficient of s1 scaled by p*g_q, wrapping)
+ *                    q >= l: b = a (*) s1 + e + p*g_{q-l}  (on coefficient 0).
+ *                  The reference adds the gadget to a[0] in the q < l rows; with a public mask that would publish
+ *                  s0[i].  Folding -p*g_q*s1 into the body instead gives the same distribution (a - p*g is uniform)
+ *                  and the same phase, so the external product is unchanged.
+ *   Generator key K (secret; generation only).  S = words 0..7 of block(K, 0, 0, 20, 0x444553), a PRF output that
+ *                  reveals nothing of K.  Noise: Box-Muller over the keystream under K, nonce (r, 17, 0x4B534B) for
+ *                  the KSK and (r, 19, 0x42534B) for the BSK.  These streams differ from the ones
+ *                  tfhe_hip_gen_cloud_key* use (1 and 3) ON PURPOSE: one K given to both entry points must not give
+ *                  two published keys with equal noise, whose difference would reveal the secret key.
+ *   Seeded TLWE lv0 (S, first_index, bodies[count]): ciphertext g = first_index + m has mask words under S, nonce
+ *                  (g & 0xffffffff, g >> 32, 0x45574C), and the body encrypt_f64 computes for that mask.
+ *                  NEVER reuse an (S, index) pair for two messages: the difference of their bodies is the difference
+ *                  of the messages plus noise.
+ *
+ * Layouts: bsk_bodies [n][2l][N] u32, ksk_bodies [N][t][base] u32 (tfhe_hip_compressed_key_words gives both sizes). */
+
+/* Word counts of bsk_bodies and ksk_bodies for `params`.  Initialises no device. */
+int tfhe_hip_compressed_key_words(const tfhe_hip_params *params, size_t *bsk_words, size_t *ksk_words);
+/* The compressed key of the secret key (key_lv0, key_lv1), as tfhe_hip_gen_cloud_key_with_key takes them: writes S
+ * to mask_seed, the bodies and the decomposition offset, and leaves ctx (or the key view) loaded with the expanded
+ * key -- bit for bit the key tfhe_hip_load_compressed_cloud_key rebuilds from the outputs.  rng_key: the generator
+ * key K from the caller's CSPRNG, or NULL to draw it from getrandom(2).  The test vector is gen_testvec's. */
+int tfhe_hip_gen_compressed_cloud_key(tfhe_hip_ctx *ctx, const uint32_t *key_lv0, const uint32_t *key_lv1,
+                                      double alpha_ksk, double alpha_bsk, const uint8_t rng_key[32],
+                                      uint8_t mask_seed[32], uint32_t *bsk_bodies, uint32_t *ksk_bodies,
+                                      uint32_t *decomp_offset);
+/* tfhe_hip_load_cloud_key from the compressed form: uploads the bodies only and expands them on the device. */
+int tfhe_hip_load_compressed_cloud_key(tfhe_hip_ctx *ctx, const uint8_t mask_seed[32], const uint32_t *bsk_bodies,
+                                       const uint32_t *ksk_bodies, uint32_t decomp_offset, const uint32_t *testvec);
+/* Seeded TLWE lv0 ciphertexts (S, first_index, bodies[count]) expanded to [count][n+1] words.  Needs no cloud key.
+ * _dev: device pointers, queued on `stream` (NULL: the context's stream) like the other *_dev entry points. */
+int tfhe_hip_expand_seeded_tlwe(tfhe_hip_ctx *ctx, const uint8_t mask_seed[32], uint64_t first_index,
+                                const uint32_t *bodies, size_t count, uint32_t *out);
+int tfhe_hip_expand_seeded_tlwe_dev(tfhe_hip_ctx *ctx, const uint8_t mask_seed[32], uint64_t first_index,
+                                    const uint32_t *bodies, size_t count, uint32_t *out, void *stream);
+
 /* Pinned host buffers.  The host entry points below take ordinary (pageable) memory and stage it through the
  * device around the kernels: 3 x 184 MB for a 65,536-ciphertext gate batch, about 7 % of the call.  When EVERY
  * ciphertext operand of a call (inputs and output) is pinned host memory -- allocated here, or the caller's own
@@ -511,6 +565,9 @@ int tfhe_hip_pool_gen_cloud_key_with_key(tfhe_hip_pool *pool, const uint32_t *ke
                                          double alpha_ksk, double alpha_bsk, const uint8_t rng_key[32]);
 int tfhe_hip_pool_gen_cloud_key(tfhe_hip_pool *pool, const uint32_t *key_lv0, const uint32_t *key_lv1,
                                 double alpha_ksk, double alpha_bsk, uint64_t seed); /* TEST / BENCHMARK ONLY */
+/* tfhe_hip_load_compressed_cloud_key on the first member, then the expanded key replicated as for a full load. */
+int tfhe_hip_pool_load_compressed_cloud_key(tfhe_hip_pool *pool, const uint8_t mask_seed[32], const uint32_t *bsk_bodies,
+                                            const uint32_t *ksk_bodies, uint32_t decomp_offset, const uint32_t *testvec);
 int tfhe_hip_pool_export_cloud_key(tfhe_hip_pool *pool, int member, double *bsk, uint32_t *ksk,
                                    uint32_t *decomp_offset, uint32_t *testvec);
 

@@ -88,6 +88,12 @@ SIGNATURES = {
     "tfhe_hip_host_alloc": (C.c_int, [_SZ, C.POINTER(_P)]),
     "tfhe_hip_host_free": (None, [_P]),
     "tfhe_hip_export_cloud_key": (C.c_int, [_CTX, _P, _P, C.POINTER(C.c_uint32), _P]),
+    "tfhe_hip_compressed_key_words": (C.c_int, [C.POINTER(Params), C.POINTER(_SZ), C.POINTER(_SZ)]),
+    "tfhe_hip_gen_compressed_cloud_key": (C.c_int, [_CTX, _P, _P, C.c_double, C.c_double, _P, _P, _P, _P,
+                                                    C.POINTER(C.c_uint32)]),
+    "tfhe_hip_load_compressed_cloud_key": (C.c_int, [_CTX, _P, _P, _P, C.c_uint32, _P]),
+    "tfhe_hip_expand_seeded_tlwe": (C.c_int, [_CTX, _P, C.c_uint64, _P, _SZ, _P]),
+    "tfhe_hip_expand_seeded_tlwe_dev": (C.c_int, [_CTX, _P, C.c_uint64, _P, _SZ, _P, _P]),
     "tfhe_hip_batch_gate": (C.c_int, [_CTX, C.c_int, _P, _P, _P, _SZ]),
     "tfhe_hip_batch_gate_dev": (C.c_int, [_CTX, C.c_int, _P, _P, _P, _SZ, _P]),
     "tfhe_hip_batch_gates_mixed": (C.c_int, [_CTX, _P, _P, _P, _P, _SZ]),
@@ -139,6 +145,7 @@ SIGNATURES = {
     "tfhe_hip_pool_last_error": (C.c_char_p, [_CTX]),
     "tfhe_hip_pool_shard": (None, [_SZ, C.c_int, C.c_int, C.POINTER(_SZ), C.POINTER(_SZ)]),
     "tfhe_hip_pool_load_cloud_key": (C.c_int, [_CTX, _P, _P, C.c_uint32, _P]),
+    "tfhe_hip_pool_load_compressed_cloud_key": (C.c_int, [_CTX, _P, _P, _P, C.c_uint32, _P]),
     "tfhe_hip_pool_gen_cloud_key_secure": (C.c_int, [_CTX, _P, _P, C.c_double, C.c_double]),
     "tfhe_hip_pool_gen_cloud_key_with_key": (C.c_int, [_CTX, _P, _P, C.c_double, C.c_double, _P]),
     "tfhe_hip_pool_gen_cloud_key": (C.c_int, [_CTX, _P, _P, C.c_double, C.c_double, C.c_uint64]),

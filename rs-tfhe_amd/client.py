@@ -11,6 +11,9 @@ the GPU except `cloud_key()`, which runs the key generation kernels.  Mirrors
   utils::f64_to_torus / gaussian_f64       src/utils.rs:9-38
   CloudKey::new(&secret_key)               src/key.rs:59-66
 
+and the seeded (compressed) forms of include/tfhe_hip.h: `compressed_cloud_key` (on the CPU by default, exact
+integer arithmetic in seeded.py) and `encrypt_*_seeded`, which return only the bodies of fresh ciphertexts.
+
 The reference draws from `thread_rng` (an OS-seeded ChaCha CSPRNG).  Here `seed=None` -- the
 default everywhere -- draws from the operating system's CSPRNG (`os.urandom`); passing an integer
 seed or a numpy Generator selects numpy's PCG64 instead, which is reproducible and NOT
@@ -146,3 +149,62 @@ class SecretKey:
         ck = view.export_cloud_key()
         adopt_view(ck, view)
         return ck
+
+    def compressed_cloud_key(self, rng_key: bytes = None, device: int = None, alpha_ksk=None, alpha_bsk=None):
+        """The cloud key in its seeded form (key.CompressedCloudKey; format in include/tfhe_hip.h).  device=None makes it
+        on the CPU (numpy, exact: a client needs no GPU); device=d runs `tfhe_hip_gen_compressed_cloud_key` there, in a
+        key view it closes after.  rng_key: the 32-byte generator key K; None draws it from the OS.  Both give the same
+        mask seed and, at zero noise, the same bodies for one K."""
+        from .key import CompressedCloudKey
+        from .seeded import compress
+
+        rng_key = os.urandom(32) if rng_key is None else bytes(rng_key)
+        if len(rng_key) != 32:
+            raise ValueError("rng_key is 32 bytes")
+        if device is None:
+            seed, bsk, ksk, off = compress(self.params, self.key_lv0, self.key_lv1, rng_key, alpha_ksk, alpha_bsk)
+            return CompressedCloudKey(self.params, seed, bsk, ksk, off)
+        from .bootstrap import engine_for
+
+        view = engine_for(self.params, device).new_key_view()
+        try:
+            return view.gen_compressed_cloud_key(self.key_lv0, self.key_lv1, rng_key=rng_key, alpha_ksk=alpha_ksk,
+                                                 alpha_bsk=alpha_bsk)
+        finally:
+            view.close()
+
+    def encrypt_f64_seeded(self, p, mask_seed: bytes = None, first_index: int = 0, seed=None, alpha: float | None = None):
+        """encrypt_f64 with the masks of the seeded TLWE format: returns seeded.SeededCiphertexts (bodies only).
+        mask_seed=None draws a fresh one from the OS.  Never encrypt twice under one (mask_seed, index): the
+        difference of the two bodies is the difference of the messages plus noise.  `seed` / `alpha` pick the noise
+        as in encrypt_f64."""
+        from .seeded import SeededCiphertexts, tlwe_masks
+
+        mask_seed = os.urandom(32) if mask_seed is None else bytes(mask_seed)
+        g = _rng(seed)
+        p = np.atleast_1d(np.asarray(p, dtype=np.float64))
+        alpha = self.params.alpha_lv0 if alpha is None else alpha
+        sc = SeededCiphertexts(self.params, mask_seed, first_index, np.zeros(len(p), np.uint32))
+        if int(first_index) + len(p) > 1 << 64:
+            raise ValueError("the ciphertext indices run past 2^64")
+        noise = f64_to_torus(g.normal(0.0, alpha, len(p))) if alpha > 0 else np.zeros(len(p), np.uint32)
+        s0 = self.key_lv0.astype(bool)
+        for lo in range(0, len(p), 8192):
+            hi = min(lo + 8192, len(p))
+            masks = tlwe_masks(sc.mask_seed, sc.first_index + lo, hi - lo, self.params.n)
+            inner = masks[:, s0].sum(axis=1, dtype=np.uint64).astype(np.uint32)
+            sc.bodies[lo:hi] = inner + f64_to_torus(p[lo:hi]) + noise[lo:hi]
+        return sc
+
+    def encrypt_bool_seeded(self, bits, mask_seed: bytes = None, first_index: int = 0, seed=None,
+                            alpha: float | None = None):
+        """encrypt_bool in the seeded form (see encrypt_f64_seeded)."""
+        bits = np.atleast_1d(np.asarray(bits)).astype(bool)
+        return self.encrypt_f64_seeded(np.where(bits, 0.125, -0.125), mask_seed, first_index, seed, alpha)
+
+    def encrypt_lwe_message_seeded(self, msgs, message_modulus: int, mask_seed: bytes = None, first_index: int = 0,
+                                   seed=None, alpha: float | None = None):
+        """encrypt_lwe_message in the seeded form (see encrypt_f64_seeded)."""
+        m = int(message_modulus)
+        msgs = np.atleast_1d(np.asarray(msgs)).astype(np.int64) % m
+        return self.encrypt_f64_seeded(msgs.astype(np.float64) * (1.0 / (2.0 * m)), mask_seed, first_index, seed, alpha)

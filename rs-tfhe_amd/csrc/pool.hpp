@@ -823,6 +823,13 @@ int tfhe_hip_pool_load_cloud_key(tfhe_hip_pool *p, const double *bsk, const uint
   return replicate_key(p);
 }
 
+int tfhe_hip_pool_load_compressed_cloud_key(tfhe_hip_pool *p, const uint8_t mask_seed[32], const uint32_t *bsk_bodies,
+                                            const uint32_t *ksk_bodies, uint32_t decomp_offset, const uint32_t *testvec) {
+  POOL_ENTER(p);
+  POOL_FIRST(p, tfhe_hip_load_compressed_cloud_key(p->ctxs[0], mask_seed, bsk_bodies, ksk_bodies, decomp_offset, testvec));
+  return replicate_key(p);
+}
+
 int tfhe_hip_pool_gen_cloud_key_secure(tfhe_hip_pool *p, const uint32_t *key_lv0, const uint32_t *key_lv1,
                                        double alpha_ksk, double alpha_bsk) {
   POOL_ENTER(p);

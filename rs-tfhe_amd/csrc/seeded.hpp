@@ -1,0 +1,454 @@
+// seeded.hpp -- seeded (compressed) cloud keys and fresh ciphertexts, expanded on the GPU.
+//
+// Every row of the key-switching key, every TRLWE row of the bootstrapping key and every fresh TLWE ciphertext is
+// (uniform mask, body).  When the mask is a fixed position of a ChaCha20 keystream under a PUBLIC 32-byte seed S,
+// only the bodies travel; the expand kernels below regenerate the masks and write the engine layouts the existing
+// kernels read.  The format (nonces, word order, the q < l body rule of the BSK) is normative and documented in
+// include/tfhe_hip.h; keygen.hpp holds the ChaCha20 block function and the Gaussian sampler used here.
+//
+// Every kernel here is a template (on its workgroup size, or on l): template instantiations are emitted after the
+// library's other kernels, so these leave the code of every existing kernel byte-identical (labels included, which
+// kernel_isa.json records).
+#pragma once
+#include "keygen.hpp"
+
+namespace tfhe {
+
+constexpr uint32_t kSeedDomainKsk = 0x4B534Bu;   // "KSK"
+constexpr uint32_t kSeedDomainBsk = 0x42534Bu;   // "BSK"
+constexpr uint32_t kSeedDomainTlwe = 0x45574Cu;  // "EWL"
+constexpr uint32_t kSeedDomainSeed = 0x444553u;  // "DES"
+
+// S = words 0..7 of block 0 of the generator key's stream (0, 20, "DES"): a PRF output, so S reveals nothing of K.
+template <int WG>
+__global__ __launch_bounds__(WG) void k_derive_mask_seed(const ChaChaKey *__restrict__ key_p, ChaChaKey *__restrict__ seed) {
+  if (threadIdx.x != 0) return;
+  uint32_t w[16];
+  chacha20_block(*key_p, 0u, 0u, 20u, kSeedDomainSeed, w);
+#pragma unroll
+  for (int c = 0; c < 8; ++c) seed->k[c] = w[c];
+}
+
+// Mask polynomial of BSK row `row`: coefficient c is word c % 16 of block c / 16 under (row, 18, "BSK").  Lane l makes
+// block l (coefficients 16l..16l+15); the FFT wants lane l to hold l+64m and l+64m+512, so the blocks go through the
+// LDS (4 KB of the tile, which the caller's transforms reuse afterwards).  One wave per workgroup.
+__device__ __forceinline__ void seeded_bsk_mask(const ChaChaKey &seed, uint32_t row, uint32_t *s, int lane,
+                                                uint32_t (&a_lo)[8], uint32_t (&a_hi)[8]) {
+  uint32_t w[16];
+  chacha20_block(seed, (uint32_t)lane, row, 18u, kSeedDomainBsk, w);
+  uint4 *s4 = reinterpret_cast<uint4 *>(s) + lane * 4;
+#pragma unroll
+  for (int q = 0; q < 4; ++q) s4[q] = make_uint4(w[4 * q], w[4 * q + 1], w[4 * q + 2], w[4 * q + 3]);
+  __syncthreads();
+#pragma unroll
+  for (int m = 0; m < 8; ++m) {
+    a_lo[m] = s[lane + 64 * m];
+    a_hi[m] = s[lane + 64 * m + kN2];
+  }
+  __syncthreads();  // the tile is the transforms' next
+}
+
+// ---- key-switching key ------------------------------------------------------------------------------------------
+// Row r = base*t*i + base*j + k (k >= 1): mask word x < n is keystream word x of (r, 16, "KSK") under S; the body is
+// <a, s0> + gaussian_f64(k * s1[i] / 2^((j+1) basebit)) with the noise from (r, 17, "KSK") under K.  k = 0: body 0.
+template <int WG>
+__global__ __launch_bounds__(WG) void k_gen_compressed_ksk(const uint32_t *__restrict__ key_lv0,
+                                                             const uint32_t *__restrict__ key_lv1,
+                                                             uint32_t *__restrict__ bodies, int n, int basebit, int t,
+                                                             double alpha, const ChaChaKey *__restrict__ key_p,
+                                                             ChaChaKey seed) {
+  static_assert(WG == 256, "the body's reduction is over four waves");
+  __shared__ uint32_t s_part[4];
+  const uint32_t row = blockIdx.x;
+  const int base = 1 << basebit;
+  const int k = row % base, j = (row / base) % t, i = row / (base * t);
+  const int tid = threadIdx.x;
+  if (k == 0) {
+    if (tid == 0) bodies[row] = 0u;
+    return;
+  }
+  uint32_t inner = 0;
+  for (int x16 = tid; x16 * 16 < n; x16 += WG) {
+    uint32_t w[16];
+    chacha20_block(seed, (uint32_t)x16, row, 16u, kSeedDomainKsk, w);
+#pragma unroll
+    for (int c = 0; c < 16; ++c) {
+      const int x = x16 * 16 + c;
+      if (x < n) inner += key_lv0[x] * w[c];
+    }
+  }
+  for (int off = 32; off > 0; off >>= 1) inner += __shfl_down(inner, off);
+  if ((tid & 63) == 0) s_part[tid >> 6] = inner;
+  __syncthreads();
+  if (tid == 0) {
+    const uint32_t total = s_part[0] + s_part[1] + s_part[2] + s_part[3];
+    uint32_t w[16];
+    chacha20_block(*key_p, 0u, row, 17u, kSeedDomainKsk, w);
+    double g0, g1;
+    gauss2(w, alpha, g0, g1);
+    const double p = (double)((uint32_t)k * key_lv1[i]) / (double)(1u << ((j + 1) * basebit));
+    bodies[row] = total + gaussian_torus(p, g0);
+  }
+}
+
+// Engine layout of k_gen_ksk / k_ksk_convert: rows of ksk_row_words(n), zero padding, k = 0 rows all zero.
+template <int WG>
+__global__ __launch_bounds__(WG) void k_expand_ksk(const uint32_t *__restrict__ bodies, uint32_t *__restrict__ ksk_eng,
+                                                     int n, int basebit, ChaChaKey seed) {
+  const uint32_t row = blockIdx.x;
+  const int k = row & ((1 << basebit) - 1);
+  const int rw = ksk_row_words(n);
+  uint32_t *dst = ksk_eng + (size_t)row * rw;
+  const int tid = threadIdx.x;
+  if (k == 0) {
+    for (int x = tid; x < rw; x += WG) dst[x] = 0u;
+    return;
+  }
+  for (int x16 = tid; x16 * 16 < n; x16 += WG) {
+    uint32_t w[16];
+    chacha20_block(seed, (uint32_t)x16, row, 16u, kSeedDomainKsk, w);
+#pragma unroll
+    for (int c = 0; c < 16; ++c) {
+      const int x = x16 * 16 + c;
+      if (x < n) dst[x] = w[c];
+    }
+  }
+  if (tid == 0) dst[n] = bodies[row];
+  if (tid > 0 && n + tid < rw) dst[n + tid] = 0u;
+}
+
+// ---- bootstrapping key --------------------------------------------------------------------------------------------
+// Row r = i*2l + q of TRGSW(s0[i]), p = s0[i], g_d = f64_to_torus(Bg^-(d+1)), a from S (seeded_bsk_mask), e from
+// (r, 19, "BSK") under K in k_gen_bsk's word order:
+//   q <  l: b = a (*) s1 + e - p*g_q*s1      (the reference's a[0] += p*g_q folded into the body: a stays the seed's)
+//   q >= l: b = a (*) s1 + e + p*g_{q-l}     (on coefficient 0, as k_gen_bsk)
+// computed as (a - p*g*[q < l]) (*) s1 through the FFT of k_gen_bsk (|coefficients| < 2^41: the rounding is exact).
+// bodies: [n][2l][N] u32, natural coefficient order.
+template <int L>
+__global__ __launch_bounds__(64) void k_gen_compressed_bsk(const uint32_t *__restrict__ key_lv0,
+                                                            const double2 *__restrict__ s1_spec,
+                                                            const double2 *__restrict__ twt, uint32_t *__restrict__ bodies,
+                                                            int bgbit, double alpha,
+                                                            const ChaChaKey *__restrict__ key_p, ChaChaKey seed) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+  double2 *tile = reinterpret_cast<double2 *>(smem);
+  const int lane = threadIdx.x;
+  const uint32_t row = blockIdx.x;
+  const int q = row % (2 * L), i = row / (2 * L);
+  Twiddles tw;
+  tw.load(twt, reinterpret_cast<double2 *>(smem + kTileBytes), lane);
+  uint32_t a_lo[8], a_hi[8], b_lo[8], b_hi[8];
+  seeded_bsk_mask(seed, row, reinterpret_cast<uint32_t *>(smem), lane, a_lo, a_hi);
+  const ChaChaKey key = *key_p;
+#pragma unroll
+  for (int h = 0; h < 2; ++h) {
+    uint32_t w[16];
+    chacha20_block(key, (uint32_t)(lane * 2 + h), row, 19u, kSeedDomainBsk, w);
+#pragma unroll
+    for (int m = 0; m < 4; ++m) {
+      double g0, g1;
+      gauss2(w + 4 * m, alpha, g0, g1);
+      b_lo[4 * h + m] = gaussian_torus(0.0, g0);
+      b_hi[4 * h + m] = gaussian_torus(0.0, g1);
+    }
+  }
+  const uint32_t p = key_lv0[i];
+  const uint32_t gadget = p * dev_f64_to_torus(exp2(-(double)(bgbit * (q % L + 1))));
+  if (q < L && lane == 0) a_lo[0] -= gadget;
+  double re[8], im[8];
+#pragma unroll
+  for (int m = 0; m < 8; ++m) {
+    re[m] = (double)(int32_t)a_lo[m];
+    im[m] = (double)(int32_t)a_hi[m];
+  }
+  fft_forward(re, im, tw, tile, lane);
+#pragma unroll
+  for (int s = 0; s < 8; ++s) {
+    const double2 sp = s1_spec[s * 64 + lane];
+    const double pr = (re[s] * sp.x - im[s] * sp.y) * 0x1p-9;
+    const double pi = (re[s] * sp.y + im[s] * sp.x) * 0x1p-9;
+    re[s] = pr;
+    im[s] = pi;
+  }
+  fft_inverse(re, im, tw, tile, lane);
+#pragma unroll
+  for (int m = 0; m < 8; ++m) {
+    b_lo[m] += round_to_torus<false>(re[m]);
+    b_hi[m] += round_to_torus<false>(im[m]);
+  }
+  if (q >= L && lane == 0) b_lo[0] += gadget;
+  uint32_t *dst = bodies + (size_t)row * kN;
+#pragma unroll
+  for (int m = 0; m < 8; ++m) {
+    dst[lane + 64 * m] = b_lo[m];
+    dst[lane + 64 * m + kN2] = b_hi[m];
+  }
+}
+
+// Spectra of (a from S, b from `bodies`) in the engine layout of k_gen_bsk, scaled by 2 * key_scale(fast).
+template <int WG>
+__global__ __launch_bounds__(WG) void k_expand_bsk(const uint32_t *__restrict__ bodies, const double2 *__restrict__ twt,
+                                                    double2 *__restrict__ bsk_eng, ChaChaKey seed, double scale) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+  static_assert(WG == 64, "one wave per row");
+  double2 *tile = reinterpret_cast<double2 *>(smem);
+  const int lane = threadIdx.x;
+  const uint32_t row = blockIdx.x;
+  Twiddles tw;
+  tw.load(twt, reinterpret_cast<double2 *>(smem + kTileBytes), lane);
+  uint32_t a_lo[8], a_hi[8];
+  seeded_bsk_mask(seed, row, reinterpret_cast<uint32_t *>(smem), lane, a_lo, a_hi);
+  const double k2 = 2.0 * scale;
+  double2 *dst = bsk_eng + (size_t)row * 2 * kN2;
+  double re[8], im[8];
+#pragma unroll
+  for (int m = 0; m < 8; ++m) {
+    re[m] = (double)(int32_t)a_lo[m];
+    im[m] = (double)(int32_t)a_hi[m];
+  }
+  fft_forward(re, im, tw, tile, lane);
+#pragma unroll
+  for (int s = 0; s < 8; ++s) dst[s * 64 + lane] = make_double2(re[s] * k2, im[s] * k2);
+  const uint32_t *src = bodies + (size_t)row * kN;
+#pragma unroll
+  for (int m = 0; m < 8; ++m) {
+    re[m] = (double)(int32_t)src[lane + 64 * m];
+    im[m] = (double)(int32_t)src[lane + 64 * m + kN2];
+  }
+  fft_forward(re, im, tw, tile, lane);
+#pragma unroll
+  for (int s = 0; s < 8; ++s) dst[kN2 + s * 64 + lane] = make_double2(re[s] * k2, im[s] * k2);
+}
+
+// ---- seeded TLWE lv0 ----------------------------------------------------------------------------------------------
+// Ciphertext g = first + m: mask word x < n is keystream word x of (g & 0xffffffff, g >> 32, "EWL") under S, the body
+// is bodies[m].  One thread per (ciphertext, keystream block); out [count][n+1].
+template <int WG>
+__global__ __launch_bounds__(WG) void k_expand_seeded_tlwe(ChaChaKey seed, uint64_t first, const uint32_t *__restrict__ bodies,
+                                                             uint32_t *__restrict__ out, size_t count, int n) {
+  const int nb = (n + 15) >> 4;
+  const size_t tid = (size_t)blockIdx.x * WG + threadIdx.x;
+  if (tid >= count * (size_t)nb) return;
+  const size_t m = tid / nb;
+  const int blk = (int)(tid - m * nb);
+  const uint64_t g = first + m;
+  uint32_t w[16];
+  chacha20_block(seed, (uint32_t)blk, (uint32_t)g, (uint32_t)(g >> 32), kSeedDomainTlwe, w);
+  uint32_t *dst = out + m * (size_t)(n + 1);
+#pragma unroll
+  for (int c = 0; c < 16; ++c) {
+    const int x = blk * 16 + c;
+    if (x < n) dst[x] = w[c];
+  }
+  if (blk == 0) dst[n] = bodies[m];
+}
+
+}  // namespace tfhe
+
+using namespace tfhe;
+
+// ---- seeded (compressed) cloud keys and ciphertexts (seeded.hpp) ---------------------------------------------
+int tfhe_hip_compressed_key_words(const tfhe_hip_params *params, size_t *bsk_words, size_t *ksk_words) {
+  if (!params || !bsk_words || !ksk_words || !params_supported(params)) return TFHE_HIP_EINVAL;
+  *bsk_words = (size_t)params->n * 2 * params->l * kN;
+  *ksk_words = (size_t)kN * params->t * ((size_t)1 << params->basebit);
+  return TFHE_HIP_OK;
+}
+
+namespace {
+ChaChaKey seed_key(const uint8_t seed[32]) {
+  ChaChaKey k;
+  memcpy(k.k, seed, 32);  // 8 little-endian words, as tfhe_hip_gen_cloud_key_with_key reads its generator key
+  return k;
+}
+
+// The engine layouts from the bodies at d_bsk_bodies [n][2l][N] / d_ksk_bodies [N][t][base] and the masks of `seed`;
+// then the key switch's planes.  ctx->mu held, buffers allocated, on ctx->stream.
+int expand_key_locked(tfhe_hip_ctx *ctx, const ChaChaKey &seed, const uint32_t *d_bsk_bodies, const uint32_t *d_ksk_bodies) {
+  const tfhe_hip_params &P = ctx->P;
+  hipLaunchKernelGGL(k_expand_bsk<64>, dim3((unsigned)(P.n * 2 * P.l)), dim3(64), kStageLdsBytes, ctx->stream, d_bsk_bodies,
+                     ctx->d_tw, ctx->K->d_bsk, seed, key_scale(ctx->fast_round));
+  HIPCHK(ctx, hipGetLastError());
+  hipLaunchKernelGGL(k_expand_ksk<256>, dim3((unsigned)((size_t)kN * P.t * (1u << P.basebit))), dim3(256), 0, ctx->stream,
+                     d_ksk_bodies, ctx->K->d_ksk, P.n, P.basebit, seed);
+  HIPCHK(ctx, hipGetLastError());
+  HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+  return build_ksk_planes(ctx);
+}
+
+// The preamble of every key change: drain what may still read the old key, clear the flags, allocate the key buffers.
+// A copy of the opening steps of tfhe_hip_load_cloud_key and gen_cloud_key_locked (tfhe_hip.hip), which keep their
+// own: a change to one of the three belongs in all of them.
+int begin_key_change(tfhe_hip_ctx *ctx) {
+  if (ctx->scratch_owned) HIPCHK(ctx, hipStreamSynchronize(ctx->scratch_owner));
+  HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+  ctx->scratch_owned = false;
+  comb_quiesce(ctx);
+  const tfhe_hip_params &P = ctx->P;
+  ctx->K->key_loaded = ctx->K->reenc_loaded = false;
+  if (!ctx->K->d_bsk) HIPCHK(ctx, hipMalloc((void **)&ctx->K->d_bsk, (size_t)P.n * 2 * P.l * 2 * kN * sizeof(double)));
+  if (!ctx->K->d_ksk)
+    HIPCHK(ctx, hipMalloc((void **)&ctx->K->d_ksk, (size_t)kN * P.t * (1u << P.basebit) * ksk_row_words(P.n) * 4 + 4096));
+  if (!ctx->K->d_testvec) HIPCHK(ctx, hipMalloc((void **)&ctx->K->d_testvec, 2 * kN * 4));
+  return TFHE_HIP_OK;
+}
+
+// ctx->mu held, ctx's device current
+int gen_compressed_locked(tfhe_hip_ctx *ctx, const uint32_t *key_lv0, const uint32_t *key_lv1, double alpha_ksk,
+                          double alpha_bsk, const ChaChaKey &rk, uint8_t mask_seed[32], uint32_t *bsk_bodies,
+                          uint32_t *ksk_bodies, uint32_t *decomp_offset) {
+  const tfhe_hip_params &P = ctx->P;
+  const size_t bsk_words = (size_t)P.n * 2 * P.l * kN, ksk_words = (size_t)kN * P.t * (1u << P.basebit);
+  CHK(begin_key_change(ctx));
+  // as in gen_cloud_key_locked: the secrets never outlive the call in the staging buffers
+  struct Wipe {
+    tfhe_hip_ctx *c;
+    ~Wipe() {
+      for (DevBuf *b : {&c->a.dev, &c->b.dev, &c->c.dev, &c->idx.dev})
+        if (b->p) (void)hipMemsetAsync(b->p, 0, b->cap < 65536 ? b->cap : 65536, c->stream);
+      (void)hipStreamSynchronize(c->stream);
+    }
+  } wipe{ctx};
+  CHK(to_dev(ctx, ctx->a, key_lv0, (size_t)P.n * 4));
+  CHK(to_dev(ctx, ctx->b, key_lv1, (size_t)kN * 4));
+  CHK(ensure(ctx, ctx->c.dev, (size_t)kN2 * sizeof(double2)));
+  const uint32_t *d_k0 = (const uint32_t *)ctx->a.dev.p, *d_k1 = (const uint32_t *)ctx->b.dev.p;
+  double2 *d_spec = (double2 *)ctx->c.dev.p;
+  hipLaunchKernelGGL(k_key_spectrum, dim3(1), dim3(64), kStageLdsBytes, ctx->stream, d_k1, ctx->d_tw, d_spec);
+  HIPCHK(ctx, hipGetLastError());
+  // generator key at idx[0, 32), the mask seed derived from it at idx[32, 64)
+  CHK(ensure(ctx, ctx->idx.dev, 2 * sizeof(ChaChaKey)));
+  HIPCHK(ctx, hipMemcpy(ctx->idx.dev.p, &rk, sizeof(ChaChaKey), hipMemcpyHostToDevice));  // synchronous: rk is the caller's stack
+  const ChaChaKey *d_rk = (const ChaChaKey *)ctx->idx.dev.p;
+  hipLaunchKernelGGL(k_derive_mask_seed<64>, dim3(1), dim3(64), 0, ctx->stream, d_rk, (ChaChaKey *)ctx->idx.dev.p + 1);
+  HIPCHK(ctx, hipGetLastError());
+  ChaChaKey seed;
+  HIPCHK(ctx, hipMemcpyAsync(&seed, (ChaChaKey *)ctx->idx.dev.p + 1, sizeof(seed), hipMemcpyDeviceToHost, ctx->stream));
+  HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+  // bodies: public, in ctx->out
+  CHK(ensure(ctx, ctx->out.dev, (bsk_words + ksk_words) * 4));
+  uint32_t *d_bb = (uint32_t *)ctx->out.dev.p, *d_kb = d_bb + bsk_words;
+  const dim3 bgrid((unsigned)(P.n * 2 * P.l));
+  switch (P.l) {
+    case 1: hipLaunchKernelGGL(k_gen_compressed_bsk<1>, bgrid, dim3(64), kStageLdsBytes, ctx->stream, d_k0, d_spec, ctx->d_tw, d_bb, P.bgbit, alpha_bsk, d_rk, seed); break;
+    case 2: hipLaunchKernelGGL(k_gen_compressed_bsk<2>, bgrid, dim3(64), kStageLdsBytes, ctx->stream, d_k0, d_spec, ctx->d_tw, d_bb, P.bgbit, alpha_bsk, d_rk, seed); break;
+    default: hipLaunchKernelGGL(k_gen_compressed_bsk<3>, bgrid, dim3(64), kStageLdsBytes, ctx->stream, d_k0, d_spec, ctx->d_tw, d_bb, P.bgbit, alpha_bsk, d_rk, seed); break;
+  }
+  HIPCHK(ctx, hipGetLastError());
+  hipLaunchKernelGGL(k_gen_compressed_ksk<256>, dim3((unsigned)ksk_words), dim3(256), 0, ctx->stream, d_k0, d_k1, d_kb, P.n,
+                     P.basebit, P.t, alpha_ksk, d_rk, seed);
+  HIPCHK(ctx, hipGetLastError());
+  HIPCHK(ctx, hipMemcpyAsync(bsk_bodies, d_bb, bsk_words * 4, hipMemcpyDeviceToHost, ctx->stream));
+  HIPCHK(ctx, hipMemcpyAsync(ksk_bodies, d_kb, ksk_words * 4, hipMemcpyDeviceToHost, ctx->stream));
+  // the context's key is what tfhe_hip_load_compressed_cloud_key rebuilds from these bodies, bit for bit
+  CHK(expand_key_locked(ctx, seed, d_bb, d_kb));
+  uint32_t off = 0;
+  for (int i = 0; i < P.l; ++i) off += ((1u << P.bgbit) / 2) * (1u << (32 - (i + 1) * P.bgbit));
+  std::vector<uint32_t> tv(2 * kN, 0u);
+  for (int i = 0; i < kN; ++i) tv[kN + i] = 0x20000000u;  // f64_to_torus(0.125)
+  HIPCHK(ctx, hipMemcpyAsync(ctx->K->d_testvec, tv.data(), 2 * kN * 4, hipMemcpyHostToDevice, ctx->stream));
+  HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+  memcpy(mask_seed, seed.k, 32);
+  *decomp_offset = off;
+  ctx->K->offset = off;
+  ctx->K->key_loaded = true;
+  comb_prepare(ctx);
+  return TFHE_HIP_OK;
+}
+
+int os_random(uint8_t *buf, size_t bytes) {  // 0, or errno
+  size_t got = 0;
+  while (got < bytes) {
+    const ssize_t r = getrandom(buf + got, bytes - got, 0);
+    if (r < 0) {
+      if (errno == EINTR) continue;
+      return errno;
+    }
+    got += (size_t)r;
+  }
+  return 0;
+}
+}  // namespace
+
+int tfhe_hip_gen_compressed_cloud_key(tfhe_hip_ctx *ctx, const uint32_t *key_lv0, const uint32_t *key_lv1,
+                                      double alpha_ksk, double alpha_bsk, const uint8_t rng_key[32],
+                                      uint8_t mask_seed[32], uint32_t *bsk_bodies, uint32_t *ksk_bodies,
+                                      uint32_t *decomp_offset) {
+  if (!ctx) return TFHE_HIP_EINVAL;
+  ENTER(ctx);
+  if (!key_lv0 || !key_lv1 || !mask_seed || !bsk_bodies || !ksk_bodies || !decomp_offset)
+    return fail(ctx, TFHE_HIP_EINVAL, "null pointer");
+  if (!(alpha_ksk >= 0.0) || !(alpha_bsk >= 0.0)) return fail(ctx, TFHE_HIP_EINVAL, "negative noise parameter");
+  ChaChaKey k;
+  if (rng_key) {
+    memcpy(k.k, rng_key, 32);
+  } else if (const int err = os_random((uint8_t *)k.k, sizeof(k.k))) {
+    return fail(ctx, TFHE_HIP_EHIP, std::string("getrandom: ") + strerror(err));
+  }
+  const int rc = gen_compressed_locked(ctx, key_lv0, key_lv1, alpha_ksk, alpha_bsk, k, mask_seed, bsk_bodies, ksk_bodies,
+                                       decomp_offset);
+  volatile uint32_t *wipe = k.k;
+  for (int i = 0; i < 8; ++i) wipe[i] = 0;
+  return rc;
+}
+
+int tfhe_hip_load_compressed_cloud_key(tfhe_hip_ctx *ctx, const uint8_t mask_seed[32], const uint32_t *bsk_bodies,
+                                       const uint32_t *ksk_bodies, uint32_t decomp_offset, const uint32_t *testvec) {
+  if (!ctx) return TFHE_HIP_EINVAL;
+  ENTER(ctx);
+  if (!mask_seed || !bsk_bodies || !ksk_bodies || !testvec) return fail(ctx, TFHE_HIP_EINVAL, "null key pointer");
+  CHK(begin_key_change(ctx));
+  const tfhe_hip_params &P = ctx->P;
+  const size_t bsk_words = (size_t)P.n * 2 * P.l * kN, ksk_words = (size_t)kN * P.t * (1u << P.basebit);
+  // the bodies travel (17 MB instead of 172 on SECURITY_128_BIT); the masks are regenerated on the device
+  uint32_t *d_bodies = nullptr;
+  HIPCHK(ctx, hipMalloc((void **)&d_bodies, (bsk_words + ksk_words) * 4));
+  hipError_t e = hipMemcpyAsync(d_bodies, bsk_bodies, bsk_words * 4, hipMemcpyHostToDevice, ctx->stream);
+  if (e == hipSuccess) e = hipMemcpyAsync(d_bodies + bsk_words, ksk_bodies, ksk_words * 4, hipMemcpyHostToDevice, ctx->stream);
+  int rc = TFHE_HIP_OK;
+  if (e == hipSuccess) rc = expand_key_locked(ctx, seed_key(mask_seed), d_bodies, d_bodies + bsk_words);
+  else (void)hipStreamSynchronize(ctx->stream);
+  (void)hipFree(d_bodies);
+  if (e != hipSuccess) return fail(ctx, TFHE_HIP_EHIP, std::string("key bodies upload: ") + hipGetErrorString(e));
+  CHK(rc);
+  HIPCHK(ctx, hipMemcpyAsync(ctx->K->d_testvec, testvec, 2 * kN * 4, hipMemcpyHostToDevice, ctx->stream));
+  HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+  ctx->K->offset = decomp_offset;
+  ctx->K->key_loaded = true;
+  comb_prepare(ctx);
+  return TFHE_HIP_OK;
+}
+
+namespace {
+int expand_seeded_launch(tfhe_hip_ctx *ctx, const ChaChaKey &seed, uint64_t first_index, const uint32_t *bodies, size_t count,
+                         uint32_t *out, hipStream_t s) {
+  const size_t threads = count * (size_t)((ctx->P.n + 15) >> 4);
+  hipLaunchKernelGGL(k_expand_seeded_tlwe<256>, dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, s, seed, first_index,
+                     bodies, out, count, ctx->P.n);
+  return launched(ctx);
+}
+}  // namespace
+
+int tfhe_hip_expand_seeded_tlwe(tfhe_hip_ctx *ctx, const uint8_t mask_seed[32], uint64_t first_index,
+                                const uint32_t *bodies, size_t count, uint32_t *out) {
+  if (!ctx) return TFHE_HIP_EINVAL;
+  ENTER(ctx);
+  if (!mask_seed) return fail(ctx, TFHE_HIP_EINVAL, "null mask seed");
+  if (count == 0) return TFHE_HIP_OK;
+  if (!bodies || !out) return fail(ctx, TFHE_HIP_EINVAL, "null pointer");
+  const ChaChaKey seed = seed_key(mask_seed);
+  return host_call(ctx, false, {{bodies, count * 4, &ctx->a}}, out, count * (size_t)(ctx->P.n + 1) * 4,
+                   [&](const void *const *d, void *o) {
+                     return expand_seeded_launch(ctx, seed, first_index, u32(d[0]), count, (uint32_t *)o, ctx->stream);
+                   });
+}
+
+int tfhe_hip_expand_seeded_tlwe_dev(tfhe_hip_ctx *ctx, const uint8_t mask_seed[32], uint64_t first_index,
+                                    const uint32_t *bodies, size_t count, uint32_t *out, void *stream) {
+  if (!ctx) return TFHE_HIP_EINVAL;
+  ENTER(ctx);
+  if (!mask_seed) return fail(ctx, TFHE_HIP_EINVAL, "null mask seed");
+  if (count && (!bodies || !out)) return fail(ctx, TFHE_HIP_EINVAL, "null pointer");
+  if (count == 0) return TFHE_HIP_OK;
+  return expand_seeded_launch(ctx, seed_key(mask_seed), first_index, bodies, count, out, pick(ctx, stream));
+}

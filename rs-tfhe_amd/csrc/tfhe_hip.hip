@@ -1188,15 +1188,21 @@ const char *tfhe_hip_last_error(const tfhe_hip_ctx *ctx) {
   return ctx ? err_text(ctx->id) : g_create_error.c_str();
 }
 
+namespace {
+bool params_supported(const tfhe_hip_params *p) {
+  return !(p->n < 1 || p->n > 1279 || p->l < 1 || p->l > 3 || p->bgbit < 1 || p->l * p->bgbit > 32 ||
+           p->basebit < 1 || p->basebit > 10 || p->t < 1 || p->basebit * p->t > 31 ||
+           (double)kN * p->t * (double)(1u << p->basebit) * ksk_row_words(p->n) * 4.0 >= 4294967296.0);
+}
+}  // namespace
+
 int tfhe_hip_ctx_create(const tfhe_hip_params *p, int device, tfhe_hip_ctx **out) {
   if (!p || !out) {
     g_create_error = "null argument";
     return TFHE_HIP_EINVAL;
   }
   *out = nullptr;
-  if (p->n < 1 || p->n > 1279 || p->l < 1 || p->l > 3 || p->bgbit < 1 || p->l * p->bgbit > 32 ||
-      p->basebit < 1 || p->basebit > 10 || p->t < 1 || p->basebit * p->t > 31 ||
-      (double)kN * p->t * (double)(1u << p->basebit) * ksk_row_words(p->n) * 4.0 >= 4294967296.0) {
+  if (!params_supported(p)) {
     g_create_error = "unsupported parameter set";
     return TFHE_HIP_EINVAL;
   }
@@ -2386,3 +2392,4 @@ int tfhe_hip_synchronize(tfhe_hip_ctx *ctx) {
 }  // extern "C"
 #include "pool.hpp"
 #include "circuit.hpp"
+#include "seeded.hpp"

@@ -95,6 +95,21 @@ def pinned_copy(a) -> np.ndarray:
     return out
 
 
+def _seed_bytes(seed) -> bytes:
+    seed = bytes(seed)
+    if len(seed) != 32:
+        raise ValueError("mask_seed is 32 bytes")
+    return seed
+
+
+def _compressed_args(p: SecurityParams, ck):
+    """(bsk bodies, ksk bodies, test vector, seed buffer) of a CompressedCloudKey, checked against `p`."""
+    bsk, ksk, tv = _u32(ck.bsk_bodies), _u32(ck.ksk_bodies), _u32(ck.blind_rotate_testvec)
+    if bsk.size != p.n * 2 * p.l * N or ksk.size != N * p.iks_t * p.base or tv.size != 2 * N:
+        raise ValueError("compressed cloud key has the wrong size for these parameters")
+    return bsk, ksk, tv, (C.c_uint8 * 32).from_buffer_copy(_seed_bytes(ck.mask_seed))
+
+
 def device_count() -> int:
     """GPUs this process can open (`tfhe_hip_device_count`): what `Pool(params, range(device_count()))` spans."""
     return int(_capi.lib().tfhe_hip_device_count())
@@ -243,6 +258,62 @@ class Engine:
         off = C.c_uint32(0)
         self._chk(self._lib.tfhe_hip_export_cloud_key(self._ctx, _ptr(bsk), _ptr(ksk), C.byref(off), _ptr(tv)))
         return CloudKey(p, bsk, ksk, int(off.value), tv)
+
+    # -- seeded (compressed) keys and ciphertexts (include/tfhe_hip.h) ---------------------------------------------
+    def gen_compressed_cloud_key(self, key_lv0, key_lv1, rng_key: bytes = None, alpha_ksk=None, alpha_bsk=None):
+        """The seeded form of the key (`tfhe_hip_gen_compressed_cloud_key`), returned as a key.CompressedCloudKey;
+        this context is left loaded with its expansion.  rng_key=None: the generator key comes from getrandom(2)."""
+        from .key import CompressedCloudKey
+
+        p = self.params
+        k0, k1 = _u32(key_lv0).reshape(-1), _u32(key_lv1).reshape(-1)
+        if len(k0) != p.n or len(k1) != N:
+            raise ValueError("secret key has the wrong size for these parameters")
+        rk = None
+        if rng_key is not None:
+            if len(rng_key) != 32:
+                raise ValueError("rng_key is 32 bytes")
+            rk = (C.c_uint8 * 32).from_buffer_copy(bytes(rng_key))
+        seed = (C.c_uint8 * 32)()
+        bsk = np.empty((p.n, 2 * p.l, N), np.uint32)
+        ksk = np.empty((N, p.iks_t, p.base), np.uint32)
+        off = C.c_uint32(0)
+        self._chk(self._lib.tfhe_hip_gen_compressed_cloud_key(
+            self._ctx, _ptr(k0), _ptr(k1), C.c_double(p.alpha_lv0 if alpha_ksk is None else alpha_ksk),
+            C.c_double(p.alpha_lv1 if alpha_bsk is None else alpha_bsk), C.addressof(rk) if rk is not None else None,
+            C.addressof(seed), _ptr(bsk), _ptr(ksk), C.byref(off)))
+        self._key = ("generated", object())
+        return CompressedCloudKey(p, bytes(seed), bsk, ksk, int(off.value))
+
+    def load_compressed_cloud_key(self, compressed_key) -> None:
+        """`tfhe_hip_load_compressed_cloud_key`: only the bodies are uploaded; the masks are regenerated on the GPU."""
+        bsk, ksk, tv, seed = _compressed_args(self.params, compressed_key)
+        self._chk(self._lib.tfhe_hip_load_compressed_cloud_key(
+            self._ctx, C.addressof(seed), _ptr(bsk), _ptr(ksk), C.c_uint32(int(compressed_key.decomposition_offset)),
+            _ptr(tv)))
+        self._key = compressed_key
+
+    def expand_seeded(self, seeded) -> np.ndarray:
+        """seeded.SeededCiphertexts -> [count][n+1] u32, expanded on the GPU (`tfhe_hip_expand_seeded_tlwe`)."""
+        if seeded.params != self.params:
+            raise ValueError(f"seeded ciphertexts of {seeded.params.name} on a {self.params.name} engine")
+        bodies = _u32(seeded.bodies).reshape(-1)
+        out = np.empty((len(bodies), self.params.n + 1), np.uint32)
+        seed = (C.c_uint8 * 32).from_buffer_copy(_seed_bytes(seeded.mask_seed))
+        self._chk(self._lib.tfhe_hip_expand_seeded_tlwe(self._ctx, C.addressof(seed), C.c_uint64(int(seeded.first_index)),
+                                                        _ptr(bodies), len(bodies), _ptr(out)))
+        return out
+
+    def expand_seeded_dev(self, mask_seed: bytes, first_index: int, bodies, out, stream=None) -> None:
+        """Device form: bodies [count] and out [count][n+1] torch tensors (32-bit words) on this engine's GPU."""
+        if bodies.dim() != 1:
+            raise ValueError("bodies must be [count]")
+        count = bodies.shape[0]
+        if out.dim() != 2 or out.shape[0] != count or out.shape[1] != self.params.n + 1:
+            raise ValueError(f"out must be [{count}][{self.params.n + 1}]")
+        seed = (C.c_uint8 * 32).from_buffer_copy(_seed_bytes(mask_seed))
+        self._chk(self._lib.tfhe_hip_expand_seeded_tlwe_dev(self._ctx, C.addressof(seed), C.c_uint64(int(first_index)),
+                                                            self._tp(bodies), count, self._tp(out), self._stream_ptr(stream)))
 
     def cloud_key_device_tensors(self):
         """(bsk, ksk, testvec, decomposition_offset): the context's key buffers in the engine layouts as uint8 torch
@@ -698,6 +769,13 @@ class Pool:
             raise ValueError("cloud key has the wrong size for these parameters")
         self._chk(self._lib.tfhe_hip_pool_load_cloud_key(self._h, _ptr(bsk), _ptr(ksk),
                                                          C.c_uint32(int(cloud_key.decomposition_offset)), _ptr(tv)))
+
+    def load_compressed_cloud_key(self, compressed_key) -> None:
+        """The seeded key expanded on the first member and replicated (`tfhe_hip_pool_load_compressed_cloud_key`)."""
+        bsk, ksk, tv, seed = _compressed_args(self.params, compressed_key)
+        self._chk(self._lib.tfhe_hip_pool_load_compressed_cloud_key(
+            self._h, C.addressof(seed), _ptr(bsk), _ptr(ksk), C.c_uint32(int(compressed_key.decomposition_offset)),
+            _ptr(tv)))
 
     def gen_cloud_key(self, key_lv0, key_lv1, seed=None) -> None:
         """seed=None: generator keyed by the OS (tfhe_hip_pool_gen_cloud_key_secure); an integer: tests only."""

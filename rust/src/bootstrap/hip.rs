@@ -73,6 +73,9 @@ extern "C" {   // include/tfhe_hip.h, the tfhe_hip_pool_* family: one handle, 1.
     fn tfhe_hip_pool_batch_mux_dev(pool: *mut TfheHipPool, home_member: c_int, naive: c_int, a: *const u32,
                                    b: *const u32, c: *const u32, out: *mut u32, count: usize,
                                    stream: *mut c_void) -> c_int;
+    // seeded (compressed) cloud key: the bodies travel, the masks are regenerated from the public seed on the device
+    fn tfhe_hip_pool_load_compressed_cloud_key(pool: *mut TfheHipPool, mask_seed: *const u8, bsk_bodies: *const u32,
+                                               ksk_bodies: *const u32, decomp_offset: u32, testvec: *const u32) -> c_int;
     fn tfhe_hip_pool_synchronize(pool: *mut TfheHipPool) -> c_int;
     fn tfhe_hip_pool_data_transport(pool: *const TfheHipPool) -> *const c_char;
     fn tfhe_hip_host_alloc(bytes: usize, out: *mut *mut c_void) -> c_int;   // pinned host memory
@@ -324,6 +327,34 @@ impl HipEngine {
         let (mut off, mut tv) = (0u32, vec![0u32; 2 * N]);
         Self::check(view, unsafe { tfhe_hip_pool_export_cloud_key(view, 0, bsk.as_mut_ptr(), ksk.as_mut_ptr(), &mut off, tv.as_mut_ptr()) });
         unsafe { tfhe_hip_pool_destroy(view) };
+        (bsk, ksk, off, tv)
+    }
+
+    /// A seeded (compressed) cloud key, the format of include/tfhe_hip.h: the public 32-byte mask seed, the BSK bodies
+    /// [n][2l][N] and the KSK bodies [N][t][base] -- what a client ships, a tenth of the full key's bytes on
+    /// SECURITY_128_BIT.  As `gen_cloud_key` above: loaded into a TEMPORARY key view of the pool (the masks regenerated
+    /// on the device, the key expanded there), read back in the reference layouts, and the view dropped on every path;
+    /// the caller builds its CloudKey from the flat arrays (the inverse of `upload`) and uses it like any other.
+    pub fn load_compressed_cloud_key(&self, mask_seed: &[u8; 32], bsk_bodies: &[u32], ksk_bodies: &[u32],
+                                     decomp_offset: u32, testvec: &[u32]) -> (Vec<f64>, Vec<u32>, u32, Vec<u32>) {
+        let n = params::tlwe_lv0::N;
+        assert_eq!(bsk_bodies.len(), n * 2 * params::trgsw_lv1::L * N, "bsk_bodies is [n][2l][N]");
+        assert_eq!(ksk_bodies.len(), N * params::trgsw_lv1::IKS_T * (1 << params::trgsw_lv1::BASEBIT), "ksk_bodies is [N][t][base]");
+        assert_eq!(testvec.len(), 2 * N, "testvec is [2][N]");
+        let mut bsk = vec![0f64; n * 2 * params::trgsw_lv1::L * 2 * N];
+        let mut ksk = vec![0u32; N * params::trgsw_lv1::IKS_T * (1 << params::trgsw_lv1::BASEBIT) * W];
+        let (mut off, mut tv) = (0u32, vec![0u32; 2 * N]);
+        let mut view = std::ptr::null_mut();
+        assert_eq!(unsafe { tfhe_hip_pool_key_create(self.pool, &mut view) }, 0, "tfhe_hip_pool_key_create failed");
+        let mut rc = unsafe { tfhe_hip_pool_load_compressed_cloud_key(view, mask_seed.as_ptr(), bsk_bodies.as_ptr(),
+                                                                      ksk_bodies.as_ptr(), decomp_offset, testvec.as_ptr()) };
+        if rc == 0 {
+            rc = unsafe { tfhe_hip_pool_export_cloud_key(view, 0, bsk.as_mut_ptr(), ksk.as_mut_ptr(), &mut off, tv.as_mut_ptr()) };
+        }
+        let msg = if rc == 0 { String::new() }
+                  else { format!("{}", unsafe { std::ffi::CStr::from_ptr(tfhe_hip_pool_last_error(view)) }.to_string_lossy()) };
+        unsafe { tfhe_hip_pool_destroy(view) };   // before any panic: the view never outlives the call
+        assert_eq!(rc, 0, "tfhe_hip: {}", msg);
         (bsk, ksk, off, tv)
     }
 }
