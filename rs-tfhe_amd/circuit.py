@@ -267,16 +267,15 @@ class Circuit:
             store = torch.empty((self.slots, B, w), dtype=torch.int32, device=inputs.device)
             out = torch.empty((self.n_wires, B, w), dtype=torch.int32, device=inputs.device)
             ow, n_out = self._all_wires.ctypes.data_as(C.c_void_p), self.n_wires
+            home = eng.home
+            sp = eng._stream_ptr(home, stream)
+            ti, ts, to = eng._tp(home, inputs), eng._tp(home, store), eng._tp(home, out)
             if isinstance(eng, E.Pool):
-                home = eng.home
-                sp = eng._stream_ptr(home, stream)
-                eng._chk(lib.tfhe_hip_circuit_run_pool_dev(eng._h, home, h, eng._tp(home, inputs), eng._tp(home, store), B, sp))
-                eng._chk(lib.tfhe_hip_circuit_gather_pool_dev(eng._h, home, h, eng._tp(home, store), B, ow, n_out,
-                                                              eng._tp(home, out), sp))
+                run, gather, lead = lib.tfhe_hip_circuit_run_pool_dev, lib.tfhe_hip_circuit_gather_pool_dev, (eng._h, home)
             else:
-                sp = eng._stream_ptr(stream)
-                eng._chk(lib.tfhe_hip_circuit_run_dev(eng._ctx, h, eng._tp(inputs), eng._tp(store), B, sp))
-                eng._chk(lib.tfhe_hip_circuit_gather_dev(eng._ctx, h, eng._tp(store), B, ow, n_out, eng._tp(out), sp))
+                run, gather, lead = lib.tfhe_hip_circuit_run_dev, lib.tfhe_hip_circuit_gather_dev, (eng._ctx,)
+            eng._chk(run(*lead, h, ti, ts, B, sp))
+            eng._chk(gather(*lead, h, ts, B, ow, n_out, to, sp))
         return out
 
     def _run_dev_torch(self, eng, inputs, stream=None):

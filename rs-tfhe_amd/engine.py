@@ -3,6 +3,7 @@ from __future__ import annotations
 
 import ctypes as C
 import threading
+import weakref
 from typing import Optional
 
 import numpy as np
@@ -52,32 +53,19 @@ def pinned_empty(shape, dtype=np.uint32) -> np.ndarray:
         raise _capi.TfheHipError(rc, msg.decode() if msg else "")
     buf = (C.c_uint8 * max(nbytes, 1)).from_address(p.value)
     arr = np.frombuffer(buf, dtype=dtype, count=int(np.prod(shape))).reshape(shape)
-    import weakref
-
     weakref.finalize(buf, lib.tfhe_hip_host_free, C.c_void_p(p.value))  # freed when the last view is gone
     return arr
 
 
-def _many_args(a, b, cb, testvec, cts):
-    """Host operands of a many-LUT call (n_luts, a NULL table and the rest are checked by the library)."""
-    a = cts(a)
-    bb = cts(b) if b is not None else None
-    if (cb & 0xFFFFFFFF) and bb is not None and bb.shape != a.shape:
-        raise ValueError("second operand of a different shape")
-    tv, per_ct = None, 0
-    if testvec is not None:
-        tv = _u32(testvec)
-        per_ct = int(tv.ndim == 3)
-        if tv.size != (len(a) if per_ct else 1) * 2 * N:
-            raise ValueError("test vector must be [2][N], or [count][2][N] for per-ciphertext tables")
-    return a, bb, tv, per_ct
-
-
-def _many_dev_check(out, testvec, count: int, n_luts: int, per_ct: bool, width: int, device: int) -> None:
-    if out is None or out.numel() != max(int(n_luts), 1) * count * width or out.device.index != device:
-        raise ValueError(f"out must be [n_luts * count][{width}] on cuda:{device}")
-    if testvec is not None and testvec.numel() != (count if per_ct else 1) * 2 * N:
-        raise ValueError("test vector must be [2][N], or [count][2][N] with per_ct")
+def _testvec(testvec, count: int):
+    """(table, per_ct) of a host bootstrap call: one [2][N] table for the batch, or [count][2][N] for one each."""
+    if testvec is None:
+        return None, 0
+    tv = _u32(testvec)
+    per_ct = int(tv.ndim == 3)
+    if tv.size != (count if per_ct else 1) * 2 * N:
+        raise ValueError("test vector must be [2][N], or [count][2][N] for per-ciphertext tables")
+    return tv, per_ct
 
 
 def _out_like(a: np.ndarray, out) -> np.ndarray:
@@ -115,9 +103,316 @@ def device_count() -> int:
     return int(_capi.lib().tfhe_hip_device_count())
 
 
-class Engine:
+class _Handle:
+    """What a context (Engine) and a pool of contexts (Pool) share: the cloud key, the batch calls on host arrays and
+    their *_dev forms on torch CUDA tensors, and the lifetime of key views.  A subclass supplies how a C entry point
+    is called on its handle (`_call` for `tfhe_hip_<name>` / `tfhe_hip_pool_<name>`; `_call_dev`, whose `home`
+    member only a pool's entry points take), `_chk`, `_destroy`, and `_device(home)`: the GPU of member `home`."""
+
+    # -- lifetime -------------------------------------------------------------
+    def _link(self, parent) -> None:
+        self._key = None  # the key object currently loaded (held, so its identity cannot be recycled)
+        self._parent = parent  # a key view keeps its parent alive for as long as it exists
+        self._views = []  # weak references to the live key views of this handle (closed before it)
+        if parent is not None:
+            parent._views.append(weakref.ref(self))
+
+    def close(self) -> None:
+        for ref in getattr(self, "_views", []):  # key views go before the handle they run on
+            v = ref()
+            if v is not None:
+                v.close()
+        self._views = []
+        self._parent = None
+        self._destroy()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    # -- cloud key ------------------------------------------------------------
+    def load_cloud_key(self, cloud_key) -> None:
+        """cloud_key: any object with the reference CloudKey fields (src/key.rs:51-56):
+        decomposition_offset, blind_rotate_testvec [2][N], key_switching_key
+        [N][t][base][n+1], bootstrapping_key [n][2l][2][N] f64.  A pool uploads it to its first member once and
+        replicates it device to device."""
+        p = self.params
+        bsk = np.ascontiguousarray(cloud_key.bootstrapping_key, dtype=np.float64)
+        ksk = _u32(cloud_key.key_switching_key)
+        tv = _u32(cloud_key.blind_rotate_testvec)
+        if bsk.size != p.n * 2 * p.l * 2 * N:
+            raise ValueError("bootstrapping_key has the wrong size for these parameters")
+        if ksk.size != N * p.iks_t * p.base * (p.n + 1):
+            raise ValueError("key_switching_key has the wrong size for these parameters")
+        if tv.size != 2 * N:
+            raise ValueError("blind_rotate_testvec must be [2][N]")
+        self._call("load_cloud_key", _ptr(bsk), _ptr(ksk), C.c_uint32(int(cloud_key.decomposition_offset)), _ptr(tv))
+        self._key = cloud_key
+
+    def load_compressed_cloud_key(self, compressed_key) -> None:
+        """`tfhe_hip_load_compressed_cloud_key`: only the bodies are uploaded; the masks are regenerated on the GPU
+        (a pool's first member, which replicates the expanded key)."""
+        bsk, ksk, tv, seed = _compressed_args(self.params, compressed_key)
+        self._call("load_compressed_cloud_key", C.addressof(seed), _ptr(bsk), _ptr(ksk),
+                   C.c_uint32(int(compressed_key.decomposition_offset)), _ptr(tv))
+        self._key = compressed_key
+
+    def gen_cloud_key(self, key_lv0, key_lv1, seed=None, alpha_ksk=None, alpha_bsk=None, rng_key: bytes = None) -> None:
+        """CloudKey::new(&secret_key) (src/key.rs:59-66) on the GPU, straight into this context (or pool).
+
+        seed=None (default): masks and noise come from a ChaCha20 stream keyed by the operating system's CSPRNG
+        (`tfhe_hip_gen_cloud_key_secure`), or by the caller's 32-byte `rng_key`.  An integer `seed` makes the key
+        reproducible and as guessable as the seed: tests and benchmarks only (include/tfhe_hip.h)."""
+        p = self.params
+        k0, k1 = _u32(key_lv0).reshape(-1), _u32(key_lv1).reshape(-1)
+        if len(k0) != p.n or len(k1) != N:
+            raise ValueError("secret key has the wrong size for these parameters")
+        a0 = C.c_double(p.alpha_lv0 if alpha_ksk is None else alpha_ksk)
+        a1 = C.c_double(p.alpha_lv1 if alpha_bsk is None else alpha_bsk)
+        if rng_key is not None:
+            if seed is not None or len(rng_key) != 32:
+                raise ValueError("rng_key is 32 bytes and excludes seed")
+            buf = (C.c_uint8 * 32).from_buffer_copy(bytes(rng_key))
+            self._call("gen_cloud_key_with_key", _ptr(k0), _ptr(k1), a0, a1, C.addressof(buf))
+        elif seed is None:
+            self._call("gen_cloud_key_secure", _ptr(k0), _ptr(k1), a0, a1)
+        else:
+            self._call("gen_cloud_key", _ptr(k0), _ptr(k1), a0, a1, C.c_uint64(int(seed) & 0xFFFFFFFFFFFFFFFF))
+        self._key = ("generated", object())
+
+    def export_cloud_key(self):
+        """The context's key back as a CloudKey in the reference layouts."""
+        return self._export_cloud_key()
+
+    def _export_cloud_key(self, *member):
+        from .key import CloudKey
+
+        p = self.params
+        bsk = np.empty((p.n, 2 * p.l, 2, N), np.float64)
+        ksk = np.empty((N, p.iks_t, p.base, p.n + 1), np.uint32)
+        tv = np.empty((2, N), np.uint32)
+        off = C.c_uint32(0)
+        self._call("export_cloud_key", *member, _ptr(bsk), _ptr(ksk), C.byref(off), _ptr(tv))
+        return CloudKey(p, bsk, ksk, int(off.value), tv)
+
+    # -- batched hot path, host arrays -----------------------------------------
+    def _cts(self, a) -> np.ndarray:
+        return _u32(a).reshape(-1, self.params.n + 1)
+
+    def batch_gate(self, gate: int, a, b=None, out=None) -> np.ndarray:
+        """`out`: optional preallocated [count][n+1] uint32 result array -- pass pinned arrays (`pinned_empty`) for
+        a, b and out and the call runs without staging copies."""
+        a = self._cts(a)
+        bb = self._cts(b) if b is not None else None
+        if bb is not None and bb.shape != a.shape:
+            raise ValueError("operand batches differ in shape")
+        out = _out_like(a, out)
+        self._call("batch_gate", int(gate), _ptr(a), _ptr(bb), _ptr(out), len(a))
+        return out
+
+    def batch_gates_mixed(self, gates, a, b, keyswitch: bool = True) -> np.ndarray:
+        """Per-ciphertext gate selectors (one launch for a whole circuit level)."""
+        a, b = self._cts(a), self._cts(b)
+        g = np.ascontiguousarray(gates, dtype=np.uint8).reshape(-1)
+        if len(g) != len(a) or b.shape != a.shape:
+            raise ValueError("gates / operand batches differ in length")
+        out = np.empty_like(a)
+        self._call("batch_gates_mixed" if keyswitch else "batch_gates_mixed_nks", _ptr(g), _ptr(a), _ptr(b), _ptr(out),
+                   len(a))
+        return out
+
+    def batch_bootstrap(self, cts, testvec=None, keyswitch: bool = True) -> np.ndarray:
+        cts = self._cts(cts)
+        out = np.empty_like(cts)
+        tv, per_ct = _testvec(testvec, len(cts))
+        self._call("batch_bootstrap", _ptr(cts), _ptr(tv), per_ct, int(keyswitch), _ptr(out), len(cts))
+        return out
+
+    def batch_tlwe_lincomb(self, ca: int, a, cb: int = 0, b=None, cconst: int = 0) -> np.ndarray:
+        """ca*a + cb*b on every word, + cconst on the body: TLWE Add / Sub / Neg / AddMul / SubMul
+        (src/tlwe.rs:129-214)."""
+        a = self._cts(a)
+        bb = self._cts(b) if b is not None else None
+        if (cb & 0xFFFFFFFF) and (bb is None or bb.shape != a.shape):
+            raise ValueError("second operand missing or of a different shape")
+        out = np.empty_like(a)
+        self._call("batch_tlwe_lincomb", ca & 0xFFFFFFFF, _ptr(a), cb & 0xFFFFFFFF, _ptr(bb), cconst & 0xFFFFFFFF,
+                   _ptr(out), len(a))
+        return out
+
+    def batch_lincomb_bootstrap(self, ca: int, a, cb: int = 0, b=None, cconst: int = 0, testvec=None,
+                                keyswitch: bool = True) -> np.ndarray:
+        """bootstrap(ca*a + cb*b + cconst) with an optional LookupTable.poly: the combination is formed in
+        the prologue of the blind-rotation kernel (examples/lut_add_two_numbers.rs:124-158)."""
+        a = self._cts(a)
+        bb = self._cts(b) if b is not None else None
+        if (cb & 0xFFFFFFFF) and (bb is None or bb.shape != a.shape):
+            raise ValueError("second operand missing or of a different shape")
+        tv, per_ct = _testvec(testvec, len(a))
+        out = np.empty_like(a)
+        self._call("batch_lincomb_bootstrap", ca & 0xFFFFFFFF, _ptr(a), cb & 0xFFFFFFFF, _ptr(bb), cconst & 0xFFFFFFFF,
+                   _ptr(tv), per_ct, int(keyswitch), _ptr(out), len(a))
+        return out
+
+    def batch_lincomb_bootstrap_many(self, ca: int, a, cb: int = 0, b=None, cconst: int = 0, testvec=None,
+                                     n_luts: int = 2, keyswitch: bool = True) -> np.ndarray:
+        """Many-LUT bootstrap of ca*a + cb*b + cconst: n_luts functions packed in `testvec`
+        (Generator.generate_many_lookup_table) from ONE blind rotation each.  Returns [n_luts][count][n+1]:
+        [j] is what batch_lincomb_bootstrap would give for function j alone (tfhe_hip_batch_lincomb_bootstrap_many).
+        n_luts, a missing table and a missing second operand are checked by the library."""
+        a = self._cts(a)
+        bb = self._cts(b) if b is not None else None
+        if (cb & 0xFFFFFFFF) and bb is not None and bb.shape != a.shape:
+            raise ValueError("second operand of a different shape")
+        tv, per_ct = _testvec(testvec, len(a))
+        out = np.empty((int(n_luts),) + a.shape, np.uint32) if n_luts in (1, 2, 4, 8) else np.empty(1, np.uint32)
+        self._call("batch_lincomb_bootstrap_many", ca & 0xFFFFFFFF, _ptr(a), cb & 0xFFFFFFFF, _ptr(bb),
+                   cconst & 0xFFFFFFFF, _ptr(tv), per_ct, int(n_luts), int(keyswitch), _ptr(out), len(a))
+        return out
+
+    def batch_blind_rotate(self, cts, testvec=None) -> np.ndarray:
+        cts = self._cts(cts)
+        out = np.empty((len(cts), 2, N), np.uint32)
+        tv = _u32(testvec) if testvec is not None else None
+        if tv is not None and tv.size != 2 * N:
+            raise ValueError("test vector must be [2][N]")
+        self._call("batch_blind_rotate", _ptr(cts), _ptr(tv), _ptr(out), len(cts))
+        return out
+
+    def batch_mux(self, a, b, c, naive: bool) -> np.ndarray:
+        a, b, c = self._cts(a), self._cts(b), self._cts(c)
+        if b.shape != a.shape or c.shape != a.shape:
+            raise ValueError("operand batches differ in shape")
+        out = np.empty_like(a)
+        self._call("batch_mux", int(bool(naive)), _ptr(a), _ptr(b), _ptr(c), _ptr(out), len(a))
+        return out
+
+    # -- device-resident path (torch CUDA tensors; enqueue only) ------------------
+    # The tensors of a call live on one GPU: an Engine's, or that of pool member `home` (default: pool.home).  A pool
+    # computes shard 0 in place there and moves the others to their members and back by grouped RCCL send / receive
+    # (or peer copies), in input order (`tfhe_hip_pool_batch_*_dev`, include/tfhe_hip.h).  So Circuit.run_dev,
+    # circuit.mux_and_gates_dev and circuit.lut_add_u8_dev take a Pool wherever they take an Engine.
+    def _home(self, home):
+        """The member a *_dev call names: `home`, or self.home (None on an Engine); refused if there is none such."""
+        h = self.home if home is None else int(home)
+        self._device(h)
+        return h
+
+    def _stream_ptr(self, home, stream):
+        """torch's current stream OF THE CALL'S GPU (the torch-current device may be another GPU: a handle from there
+        would be an invalid resource here), or the caller's stream, which must live on that GPU."""
+        dev = self._device(home)
+        if stream is None:
+            import torch
+
+            stream = torch.cuda.current_stream(dev)
+        elif getattr(stream, "device", None) is not None and stream.device.index != dev:
+            raise ValueError(f"stream lives on {stream.device}, the call on cuda:{dev}")
+        # torch's default stream is the legacy null stream (handle 0); the C ABI reads NULL as "the
+        # context's own stream", so name the null stream explicitly: hipStreamLegacy == (hipStream_t)1
+        return C.c_void_p(stream.cuda_stream or 1)
+
+    def _tp(self, home, t):
+        """Device pointer of a tensor that must live on the call's GPU (test vectors, outputs, gate codes)."""
+        p = _tptr(t)
+        if t is not None and t.device.index != self._device(home):
+            raise ValueError(f"device tensor lives on {t.device}, the call on cuda:{self._device(home)}")
+        return p
+
+    def _dev_batch(self, home, *tensors) -> int:
+        """All tensors are [count][n+1] on the call's GPU; returns count."""
+        width, dev = self.params.n + 1, self._device(home)
+        first = tensors[0]
+        for t in tensors:
+            if t is None:
+                continue
+            if t.dim() != 2 or t.shape[1] != width or t.shape[0] != first.shape[0]:
+                raise ValueError(f"device tensors must all be [count][{width}]")
+            if t.device.index != dev:
+                raise ValueError(f"device tensor lives on {t.device}, the call on cuda:{dev}")
+        return first.shape[0]
+
+    def batch_gate_dev(self, gate: int, a, b, out, stream=None, home=None) -> None:
+        h = self._home(home)
+        count = self._dev_batch(h, a, b, out)
+        self._call_dev("batch_gate_dev", h, int(gate), self._tp(h, a), self._tp(h, b), self._tp(h, out), count,
+                       self._stream_ptr(h, stream))
+
+    def batch_gates_mixed_dev(self, gates, a, b, out, stream=None, keyswitch: bool = True, home=None) -> None:
+        """gates: uint8 CUDA tensor [count]; a, b, out: int32 CUDA tensors [count][n+1].  keyswitch=False ends
+        in bootstrap_without_key_switch (the first level of Gates::mux, `tfhe_hip_batch_gates_mixed_nks_dev`)."""
+        h = self._home(home)
+        dev = self._device(h)
+        if not gates.is_cuda or gates.element_size() != 1 or not gates.is_contiguous() or gates.device.index != dev:
+            raise ValueError(f"gates must be a contiguous uint8 CUDA tensor on cuda:{dev}")
+        count = self._dev_batch(h, a, b, out)
+        if gates.numel() != count:
+            raise ValueError("one gate code per ciphertext")
+        self._call_dev("batch_gates_mixed_dev" if keyswitch else "batch_gates_mixed_nks_dev", h,
+                       C.c_void_p(gates.data_ptr()), self._tp(h, a), self._tp(h, b), self._tp(h, out), count,
+                       self._stream_ptr(h, stream))
+
+    def batch_bootstrap_dev(self, cts, out, testvec=None, per_ct: bool = False, keyswitch: bool = True, stream=None,
+                            home=None) -> None:
+        h = self._home(home)
+        count = self._dev_batch(h, cts, out)
+        if testvec is not None and testvec.numel() != (count if per_ct else 1) * 2 * N:
+            raise ValueError("test vector must be [2][N], or [count][2][N] with per_ct")
+        self._call_dev("batch_bootstrap_dev", h, self._tp(h, cts), self._tp(h, testvec), int(per_ct), int(keyswitch),
+                       self._tp(h, out), count, self._stream_ptr(h, stream))
+
+    def batch_tlwe_lincomb_dev(self, ca: int, a, cb: int, b, cconst: int, out, stream=None, home=None) -> None:
+        h = self._home(home)
+        count = self._dev_batch(h, a, b, out)
+        self._call_dev("batch_tlwe_lincomb_dev", h, ca & 0xFFFFFFFF, self._tp(h, a), cb & 0xFFFFFFFF, self._tp(h, b),
+                       cconst & 0xFFFFFFFF, self._tp(h, out), count, self._stream_ptr(h, stream))
+
+    def batch_lincomb_bootstrap_dev(self, ca: int, a, cb: int, b, cconst: int, out, testvec=None,
+                                    per_ct: bool = False, keyswitch: bool = True, stream=None, home=None) -> None:
+        h = self._home(home)
+        count = self._dev_batch(h, a, b, out)
+        if testvec is not None and testvec.numel() != (count if per_ct else 1) * 2 * N:
+            raise ValueError("test vector must be [2][N], or [count][2][N] with per_ct")
+        self._call_dev("batch_lincomb_bootstrap_dev", h, ca & 0xFFFFFFFF, self._tp(h, a), cb & 0xFFFFFFFF,
+                       self._tp(h, b), cconst & 0xFFFFFFFF, self._tp(h, testvec), int(per_ct), int(keyswitch),
+                       self._tp(h, out), count, self._stream_ptr(h, stream))
+
+    def batch_lincomb_bootstrap_many_dev(self, ca: int, a, cb: int, b, cconst: int, out, testvec, n_luts: int = 2,
+                                         per_ct: bool = False, keyswitch: bool = True, stream=None, home=None) -> None:
+        """Device form of batch_lincomb_bootstrap_many: out is an int32 CUDA tensor [n_luts * count][n+1] (or
+        [n_luts][count][n+1]), function-major."""
+        h = self._home(home)
+        count, width, dev = self._dev_batch(h, a, b), self.params.n + 1, self._device(h)
+        if out is None or out.numel() != max(int(n_luts), 1) * count * width or out.device.index != dev:
+            raise ValueError(f"out must be [n_luts * count][{width}] on cuda:{dev}")
+        if testvec is not None and testvec.numel() != (count if per_ct else 1) * 2 * N:
+            raise ValueError("test vector must be [2][N], or [count][2][N] with per_ct")
+        self._call_dev("batch_lincomb_bootstrap_many_dev", h, ca & 0xFFFFFFFF, self._tp(h, a), cb & 0xFFFFFFFF,
+                       self._tp(h, b), cconst & 0xFFFFFFFF, self._tp(h, testvec), int(per_ct), int(n_luts),
+                       int(keyswitch), self._tp(h, out), count, self._stream_ptr(h, stream))
+
+    def batch_blind_rotate_dev(self, cts, out_trlwe, testvec=None, stream=None, home=None) -> None:
+        h = self._home(home)
+        count = self._dev_batch(h, cts)
+        if out_trlwe.numel() != count * 2 * N or (testvec is not None and testvec.numel() != 2 * N):
+            raise ValueError("out_trlwe must be [count][2][N], testvec [2][N]")
+        self._call_dev("batch_blind_rotate_dev", h, self._tp(h, cts), self._tp(h, testvec), self._tp(h, out_trlwe),
+                       count, self._stream_ptr(h, stream))
+
+    def batch_mux_dev(self, a, b, c, out, naive: bool, stream=None, home=None) -> None:
+        h = self._home(home)
+        count = self._dev_batch(h, a, b, c, out)
+        self._call_dev("batch_mux_dev", h, int(naive), self._tp(h, a), self._tp(h, b), self._tp(h, c),
+                       self._tp(h, out), count, self._stream_ptr(h, stream))
+
+
+class Engine(_Handle):
     """Owns a tfhe_hip_ctx.  Host arrays are numpy uint32; *_dev methods take
     torch CUDA tensors (int32 storage of the u32 words) and only enqueue work."""
+
+    home = None  # one GPU: the *_dev calls name no member
 
     def __init__(self, params: SecurityParams, device: int = 0, _view_of: "Engine" = None):
         self.params = params
@@ -134,18 +429,15 @@ class Engine:
             if rc != _capi.OK:
                 msg = self._lib.tfhe_hip_last_error(None)
                 raise _capi.TfheHipError(rc, msg.decode() if msg else "")
+        self._attach(ctx, None, _view_of)
+
+    def _attach(self, ctx, owner, parent) -> None:
         self._ctx = ctx
-        self._owner = None  # a Pool when the context is borrowed from one (tfhe_hip_pool_ctx): never destroyed here
-        self._parent = _view_of  # keeps the parent context alive for as long as this view exists
-        self._views = []  # weak references to the live key views of this context (closed before it)
-        self._key = None  # the CloudKey object currently loaded (held, so identity cannot be recycled)
+        self._owner = owner  # a Pool when the context is borrowed from one (tfhe_hip_pool_ctx): never destroyed here
         self.lock = threading.RLock()  # for callers that want several calls on this handle back to back
         self._last_use = 0
         self._users = 0  # bootstrap.keyed_engine: calls in flight under this view (never evicted while > 0)
-        if _view_of is not None:
-            import weakref
-
-            _view_of._views.append(weakref.ref(self))
+        self._link(parent)
 
     def new_key_view(self) -> "Engine":
         """Another resident cloud key on this context (`tfhe_hip_key_create`): an Engine handle with its own key
@@ -164,100 +456,34 @@ class Engine:
             raise ValueError("no such pool member")
         self = cls.__new__(cls)
         self.params, self.device, self._lib = pool.params, pool.devices[member], pool._lib
-        self._ctx = C.c_void_p(ctx)
-        self._owner = pool
-        self._parent = None
-        self._views = []
+        self._attach(C.c_void_p(ctx), pool, None)
         self._key = ("pool", object())
-        self.lock = threading.RLock()
-        self._last_use = 0
-        self._users = 0
         return self
 
-    # -- lifetime -------------------------------------------------------------
-    def close(self) -> None:
-        if getattr(self, "_ctx", None):
-            for ref in getattr(self, "_views", []):  # key views go before the context they run on
-                v = ref()
-                if v is not None:
-                    v.close()
-            self._views = []
-            if getattr(self, "_owner", None) is None:
-                self._lib.tfhe_hip_ctx_destroy(self._ctx)
-            self._ctx = None
-            self._owner = None
-            self._parent = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+    # -- what a context supplies to the shared calls ---------------------------------------------------------------------
+    def _destroy(self) -> None:
+        if getattr(self, "_ctx", None) and getattr(self, "_owner", None) is None:
+            self._lib.tfhe_hip_ctx_destroy(self._ctx)
+        self._ctx = None
+        self._owner = None
 
     def _chk(self, rc: int) -> None:
         _capi.check(self._ctx, rc)
 
+    def _call(self, name: str, *args) -> None:
+        self._chk(getattr(self._lib, "tfhe_hip_" + name)(self._ctx, *args))
+
+    def _call_dev(self, name: str, home, *args) -> None:
+        self._call(name, *args)  # a context's *_dev entry points take no member: `home` is None
+
+    def _device(self, home) -> int:
+        if home is not None:
+            raise ValueError("an Engine has no pool members: home must be None")
+        return self.device
+
     @property
     def name(self) -> str:
         return self._lib.tfhe_hip_name().decode()
-
-    # -- cloud key ------------------------------------------------------------
-    def load_cloud_key(self, cloud_key) -> None:
-        """cloud_key: any object with the reference CloudKey fields (src/key.rs:51-56):
-        decomposition_offset, blind_rotate_testvec [2][N], key_switching_key
-        [N][t][base][n+1], bootstrapping_key [n][2l][2][N] f64."""
-        p = self.params
-        bsk = np.ascontiguousarray(cloud_key.bootstrapping_key, dtype=np.float64)
-        ksk = _u32(cloud_key.key_switching_key)
-        tv = _u32(cloud_key.blind_rotate_testvec)
-        if bsk.size != p.n * 2 * p.l * 2 * N:
-            raise ValueError("bootstrapping_key has the wrong size for these parameters")
-        if ksk.size != N * p.iks_t * p.base * (p.n + 1):
-            raise ValueError("key_switching_key has the wrong size for these parameters")
-        if tv.size != 2 * N:
-            raise ValueError("blind_rotate_testvec must be [2][N]")
-        self._chk(
-            self._lib.tfhe_hip_load_cloud_key(
-                self._ctx, _ptr(bsk), _ptr(ksk), C.c_uint32(int(cloud_key.decomposition_offset)), _ptr(tv)
-            )
-        )
-        self._key = cloud_key
-
-    def gen_cloud_key(self, key_lv0, key_lv1, seed=None, alpha_ksk=None, alpha_bsk=None, rng_key: bytes = None) -> None:
-        """CloudKey::new(&secret_key) (src/key.rs:59-66) on the GPU, straight into this context.
-
-        seed=None (default): masks and noise come from a ChaCha20 stream keyed by the operating system's CSPRNG
-        (`tfhe_hip_gen_cloud_key_secure`), or by the caller's 32-byte `rng_key`.  An integer `seed` makes the key
-        reproducible and as guessable as the seed: tests and benchmarks only (include/tfhe_hip.h)."""
-        p = self.params
-        k0, k1 = _u32(key_lv0).reshape(-1), _u32(key_lv1).reshape(-1)
-        if len(k0) != p.n or len(k1) != N:
-            raise ValueError("secret key has the wrong size for these parameters")
-        a0 = C.c_double(p.alpha_lv0 if alpha_ksk is None else alpha_ksk)
-        a1 = C.c_double(p.alpha_lv1 if alpha_bsk is None else alpha_bsk)
-        if rng_key is not None:
-            if seed is not None or len(rng_key) != 32:
-                raise ValueError("rng_key is 32 bytes and excludes seed")
-            buf = (C.c_uint8 * 32).from_buffer_copy(bytes(rng_key))
-            self._chk(self._lib.tfhe_hip_gen_cloud_key_with_key(self._ctx, _ptr(k0), _ptr(k1), a0, a1, C.addressof(buf)))
-        elif seed is None:
-            self._chk(self._lib.tfhe_hip_gen_cloud_key_secure(self._ctx, _ptr(k0), _ptr(k1), a0, a1))
-        else:
-            self._chk(self._lib.tfhe_hip_gen_cloud_key(self._ctx, _ptr(k0), _ptr(k1), a0, a1,
-                                                       C.c_uint64(int(seed) & 0xFFFFFFFFFFFFFFFF)))
-        self._key = ("generated", object())
-
-    def export_cloud_key(self):
-        """The context's key back as a CloudKey in the reference layouts."""
-        from .key import CloudKey
-
-        p = self.params
-        bsk = np.empty((p.n, 2 * p.l, 2, N), np.float64)
-        ksk = np.empty((N, p.iks_t, p.base, p.n + 1), np.uint32)
-        tv = np.empty((2, N), np.uint32)
-        off = C.c_uint32(0)
-        self._chk(self._lib.tfhe_hip_export_cloud_key(self._ctx, _ptr(bsk), _ptr(ksk), C.byref(off), _ptr(tv)))
-        return CloudKey(p, bsk, ksk, int(off.value), tv)
 
     # -- seeded (compressed) keys and ciphertexts (include/tfhe_hip.h) ---------------------------------------------
     def gen_compressed_cloud_key(self, key_lv0, key_lv1, rng_key: bytes = None, alpha_ksk=None, alpha_bsk=None):
@@ -285,14 +511,6 @@ class Engine:
         self._key = ("generated", object())
         return CompressedCloudKey(p, bytes(seed), bsk, ksk, int(off.value))
 
-    def load_compressed_cloud_key(self, compressed_key) -> None:
-        """`tfhe_hip_load_compressed_cloud_key`: only the bodies are uploaded; the masks are regenerated on the GPU."""
-        bsk, ksk, tv, seed = _compressed_args(self.params, compressed_key)
-        self._chk(self._lib.tfhe_hip_load_compressed_cloud_key(
-            self._ctx, C.addressof(seed), _ptr(bsk), _ptr(ksk), C.c_uint32(int(compressed_key.decomposition_offset)),
-            _ptr(tv)))
-        self._key = compressed_key
-
     def expand_seeded(self, seeded) -> np.ndarray:
         """seeded.SeededCiphertexts -> [count][n+1] u32, expanded on the GPU (`tfhe_hip_expand_seeded_tlwe`)."""
         if seeded.params != self.params:
@@ -313,7 +531,8 @@ class Engine:
             raise ValueError(f"out must be [{count}][{self.params.n + 1}]")
         seed = (C.c_uint8 * 32).from_buffer_copy(_seed_bytes(mask_seed))
         self._chk(self._lib.tfhe_hip_expand_seeded_tlwe_dev(self._ctx, C.addressof(seed), C.c_uint64(int(first_index)),
-                                                            self._tp(bodies), count, self._tp(out), self._stream_ptr(stream)))
+                                                            self._tp(None, bodies), count, self._tp(None, out),
+                                                            self._stream_ptr(None, stream)))
 
     def cloud_key_device_tensors(self):
         """(bsk, ksk, testvec, decomposition_offset): the context's key buffers in the engine layouts as uint8 torch
@@ -342,109 +561,6 @@ class Engine:
     def ensure_key(self, cloud_key) -> None:
         if self._key is not cloud_key:
             self.load_cloud_key(cloud_key)
-
-    # -- batched hot path, host arrays -----------------------------------------
-    def _cts(self, a) -> np.ndarray:
-        a = _u32(a)
-        return a.reshape(-1, self.params.n + 1)
-
-    def batch_gate(self, gate: int, a, b=None, out=None) -> np.ndarray:
-        """`out`: optional preallocated [count][n+1] uint32 result array -- pass pinned arrays (`pinned_empty`) for
-        a, b and out and the call runs without staging copies."""
-        a = self._cts(a)
-        bb = self._cts(b) if b is not None else None
-        if bb is not None and bb.shape != a.shape:
-            raise ValueError("operand batches differ in shape")
-        out = _out_like(a, out)
-        self._chk(self._lib.tfhe_hip_batch_gate(self._ctx, int(gate), _ptr(a), _ptr(bb), _ptr(out), len(a)))
-        return out
-
-    def batch_gates_mixed(self, gates, a, b, keyswitch: bool = True) -> np.ndarray:
-        """Per-ciphertext gate selectors (one launch for a whole circuit level)."""
-        a, b = self._cts(a), self._cts(b)
-        g = np.ascontiguousarray(gates, dtype=np.uint8).reshape(-1)
-        if len(g) != len(a) or b.shape != a.shape:
-            raise ValueError("gates / operand batches differ in length")
-        out = np.empty_like(a)
-        fn = self._lib.tfhe_hip_batch_gates_mixed if keyswitch else self._lib.tfhe_hip_batch_gates_mixed_nks
-        self._chk(fn(self._ctx, _ptr(g), _ptr(a), _ptr(b), _ptr(out), len(a)))
-        return out
-
-    def batch_bootstrap(self, cts, testvec=None, keyswitch: bool = True) -> np.ndarray:
-        cts = self._cts(cts)
-        out = np.empty_like(cts)
-        per_ct = 0
-        tv = None
-        if testvec is not None:
-            tv = _u32(testvec)
-            per_ct = int(tv.ndim == 3)
-            if tv.size != (len(cts) if per_ct else 1) * 2 * N:
-                raise ValueError("test vector must be [2][N], or [count][2][N] for per-ciphertext tables")
-        self._chk(
-            self._lib.tfhe_hip_batch_bootstrap(self._ctx, _ptr(cts), _ptr(tv), per_ct, int(keyswitch), _ptr(out), len(cts))
-        )
-        return out
-
-    def batch_tlwe_lincomb(self, ca: int, a, cb: int = 0, b=None, cconst: int = 0) -> np.ndarray:
-        """ca*a + cb*b on every word, + cconst on the body: TLWE Add / Sub / Neg / AddMul / SubMul
-        (src/tlwe.rs:129-214)."""
-        a = self._cts(a)
-        bb = self._cts(b) if b is not None else None
-        if (cb & 0xFFFFFFFF) and (bb is None or bb.shape != a.shape):
-            raise ValueError("second operand missing or of a different shape")
-        out = np.empty_like(a)
-        self._chk(self._lib.tfhe_hip_batch_tlwe_lincomb(
-            self._ctx, ca & 0xFFFFFFFF, _ptr(a), cb & 0xFFFFFFFF, _ptr(bb), cconst & 0xFFFFFFFF, _ptr(out), len(a)))
-        return out
-
-    def batch_lincomb_bootstrap(self, ca: int, a, cb: int = 0, b=None, cconst: int = 0, testvec=None,
-                                keyswitch: bool = True) -> np.ndarray:
-        """bootstrap(ca*a + cb*b + cconst) with an optional LookupTable.poly: the combination is formed in
-        the prologue of the blind-rotation kernel (examples/lut_add_two_numbers.rs:124-158)."""
-        a = self._cts(a)
-        bb = self._cts(b) if b is not None else None
-        if (cb & 0xFFFFFFFF) and (bb is None or bb.shape != a.shape):
-            raise ValueError("second operand missing or of a different shape")
-        tv, per_ct = None, 0
-        if testvec is not None:
-            tv = _u32(testvec)
-            per_ct = int(tv.ndim == 3)
-            if tv.size != (len(a) if per_ct else 1) * 2 * N:
-                raise ValueError("test vector must be [2][N], or [count][2][N] for per-ciphertext tables")
-        out = np.empty_like(a)
-        self._chk(self._lib.tfhe_hip_batch_lincomb_bootstrap(
-            self._ctx, ca & 0xFFFFFFFF, _ptr(a), cb & 0xFFFFFFFF, _ptr(bb), cconst & 0xFFFFFFFF, _ptr(tv), per_ct,
-            int(keyswitch), _ptr(out), len(a)))
-        return out
-
-    def batch_lincomb_bootstrap_many(self, ca: int, a, cb: int = 0, b=None, cconst: int = 0, testvec=None,
-                                     n_luts: int = 2, keyswitch: bool = True) -> np.ndarray:
-        """Many-LUT bootstrap of ca*a + cb*b + cconst: n_luts functions packed in `testvec`
-        (Generator.generate_many_lookup_table) from ONE blind rotation each.  Returns [n_luts][count][n+1]:
-        [j] is what batch_lincomb_bootstrap would give for function j alone (tfhe_hip_batch_lincomb_bootstrap_many)."""
-        a, bb, tv, per_ct = _many_args(a, b, cb, testvec, self._cts)
-        out = np.empty((int(n_luts),) + a.shape, np.uint32) if n_luts in (1, 2, 4, 8) else np.empty(1, np.uint32)
-        self._chk(self._lib.tfhe_hip_batch_lincomb_bootstrap_many(
-            self._ctx, ca & 0xFFFFFFFF, _ptr(a), cb & 0xFFFFFFFF, _ptr(bb), cconst & 0xFFFFFFFF, _ptr(tv), per_ct,
-            int(n_luts), int(keyswitch), _ptr(out), len(a)))
-        return out
-
-    def batch_blind_rotate(self, cts, testvec=None) -> np.ndarray:
-        cts = self._cts(cts)
-        out = np.empty((len(cts), 2, N), np.uint32)
-        tv = _u32(testvec) if testvec is not None else None
-        if tv is not None and tv.size != 2 * N:
-            raise ValueError("test vector must be [2][N]")
-        self._chk(self._lib.tfhe_hip_batch_blind_rotate(self._ctx, _ptr(cts), _ptr(tv), _ptr(out), len(cts)))
-        return out
-
-    def batch_mux(self, a, b, c, naive: bool) -> np.ndarray:
-        a, b, c = self._cts(a), self._cts(b), self._cts(c)
-        if b.shape != a.shape or c.shape != a.shape:
-            raise ValueError("operand batches differ in shape")
-        out = np.empty_like(a)
-        self._chk(self._lib.tfhe_hip_batch_mux(self._ctx, int(naive), _ptr(a), _ptr(b), _ptr(c), _ptr(out), len(a)))
-        return out
 
     # -- single stages ----------------------------------------------------------
     def batch_external_product(self, trlwe, bsk_index) -> np.ndarray:
@@ -490,8 +606,9 @@ class Engine:
 
     def batch_reencrypt_dev(self, a, out, stream=None) -> None:
         """The same on int32 CUDA tensors [count][n+1] of this engine's GPU; only enqueues."""
-        count = self._dev_batch(a, out)
-        self._chk(self._lib.tfhe_hip_batch_reencrypt_dev(self._ctx, self._tp(a), self._tp(out), count, self._stream_ptr(stream)))
+        count = self._dev_batch(None, a, out)
+        self._chk(self._lib.tfhe_hip_batch_reencrypt_dev(self._ctx, self._tp(None, a), self._tp(None, out), count,
+                                                         self._stream_ptr(None, stream)))
 
     def batch_ifft(self, polys) -> np.ndarray:
         polys = _u32(polys).reshape(-1, N)
@@ -512,110 +629,6 @@ class Engine:
         out = np.empty_like(a)
         self._chk(self._lib.tfhe_hip_batch_poly_mul(self._ctx, _ptr(out), _ptr(a), _ptr(b), len(a)))
         return out
-
-    # -- device-resident path (torch CUDA tensors; enqueue only) ------------------
-    def _stream_ptr(self, stream):
-        if stream is None:
-            import torch
-
-            stream = torch.cuda.current_stream(self.device)  # of THIS engine's GPU, whatever torch's current device is
-        elif getattr(stream, "device", None) is not None and stream.device.index != self.device:
-            raise ValueError(f"stream lives on {stream.device}, the engine on cuda:{self.device}")
-        # torch's default stream is the legacy null stream (handle 0); the C ABI reads NULL as "the
-        # context's own stream", so name the null stream explicitly: hipStreamLegacy == (hipStream_t)1
-        return C.c_void_p(stream.cuda_stream or 1)
-
-    def _tp(self, t):
-        """Device pointer of a tensor that must live on this engine's GPU (test vectors, outputs, gate codes)."""
-        p = _tptr(t)
-        if t is not None and t.device.index != self.device:
-            raise ValueError(f"device tensor lives on {t.device}, the engine on cuda:{self.device}")
-        return p
-
-    def _dev_batch(self, *tensors, width=None) -> int:
-        """All tensors are [count][width] on this engine's GPU; returns count."""
-        width = self.params.n + 1 if width is None else width
-        first = tensors[0]
-        for t in tensors:
-            if t is None:
-                continue
-            if t.dim() != 2 or t.shape[1] != width or t.shape[0] != first.shape[0]:
-                raise ValueError(f"device tensors must all be [count][{width}]")
-            if t.device.index != self.device:
-                raise ValueError(f"device tensor lives on {t.device}, the engine on cuda:{self.device}")
-        return first.shape[0]
-
-    def batch_gate_dev(self, gate: int, a, b, out, stream=None) -> None:
-        count = self._dev_batch(a, b, out)
-        self._chk(
-            self._lib.tfhe_hip_batch_gate_dev(self._ctx, int(gate), self._tp(a), self._tp(b), self._tp(out), count, self._stream_ptr(stream))
-        )
-
-    def batch_gates_mixed_dev(self, gates, a, b, out, stream=None, keyswitch: bool = True) -> None:
-        """gates: uint8 CUDA tensor [count]; a, b, out: int32 CUDA tensors [count][n+1].  keyswitch=False ends
-        in bootstrap_without_key_switch (the first level of Gates::mux, `tfhe_hip_batch_gates_mixed_nks_dev`)."""
-        if not gates.is_cuda or gates.element_size() != 1 or not gates.is_contiguous():
-            raise ValueError("gates must be a contiguous uint8 CUDA tensor")
-        if gates.device.index != self.device:
-            raise ValueError("gates tensor lives on another device than this engine")
-        count = self._dev_batch(a, b, out)
-        if gates.numel() != count:
-            raise ValueError("one gate code per ciphertext")
-        fn = self._lib.tfhe_hip_batch_gates_mixed_dev if keyswitch else self._lib.tfhe_hip_batch_gates_mixed_nks_dev
-        self._chk(fn(self._ctx, C.c_void_p(gates.data_ptr()), self._tp(a), self._tp(b), self._tp(out), count, self._stream_ptr(stream)))
-
-    def batch_bootstrap_dev(self, cts, out, testvec=None, per_ct: bool = False, keyswitch: bool = True, stream=None) -> None:
-        count = self._dev_batch(cts, out)
-        if testvec is not None and testvec.numel() != (count if per_ct else 1) * 2 * N:
-            raise ValueError("test vector must be [2][N], or [count][2][N] with per_ct")
-        self._chk(
-            self._lib.tfhe_hip_batch_bootstrap_dev(
-                self._ctx, self._tp(cts), self._tp(testvec), int(per_ct), int(keyswitch), self._tp(out), count, self._stream_ptr(stream)
-            )
-        )
-
-    def batch_tlwe_lincomb_dev(self, ca: int, a, cb: int, b, cconst: int, out, stream=None) -> None:
-        count = self._dev_batch(a, b, out)
-        self._chk(self._lib.tfhe_hip_batch_tlwe_lincomb_dev(
-            self._ctx, ca & 0xFFFFFFFF, self._tp(a), cb & 0xFFFFFFFF, self._tp(b), cconst & 0xFFFFFFFF, self._tp(out), count,
-            self._stream_ptr(stream)))
-
-    def batch_lincomb_bootstrap_dev(self, ca: int, a, cb: int, b, cconst: int, out, testvec=None,
-                                    per_ct: bool = False, keyswitch: bool = True, stream=None) -> None:
-        count = self._dev_batch(a, b, out)
-        if testvec is not None and testvec.numel() != (count if per_ct else 1) * 2 * N:
-            raise ValueError("test vector must be [2][N], or [count][2][N] with per_ct")
-        self._chk(self._lib.tfhe_hip_batch_lincomb_bootstrap_dev(
-            self._ctx, ca & 0xFFFFFFFF, self._tp(a), cb & 0xFFFFFFFF, self._tp(b), cconst & 0xFFFFFFFF, self._tp(testvec),
-            int(per_ct), int(keyswitch), self._tp(out), count, self._stream_ptr(stream)))
-
-    def batch_lincomb_bootstrap_many_dev(self, ca: int, a, cb: int, b, cconst: int, out, testvec, n_luts: int = 2,
-                                         per_ct: bool = False, keyswitch: bool = True, stream=None) -> None:
-        """Device form of batch_lincomb_bootstrap_many: out is an int32 CUDA tensor [n_luts * count][n+1] (or
-        [n_luts][count][n+1]), function-major."""
-        count = self._dev_batch(a, b)
-        _many_dev_check(out, testvec, count, n_luts, per_ct, self.params.n + 1, self.device)
-        self._chk(self._lib.tfhe_hip_batch_lincomb_bootstrap_many_dev(
-            self._ctx, ca & 0xFFFFFFFF, self._tp(a), cb & 0xFFFFFFFF, self._tp(b), cconst & 0xFFFFFFFF, self._tp(testvec),
-            int(per_ct), int(n_luts), int(keyswitch), self._tp(out), count, self._stream_ptr(stream)))
-
-    def batch_blind_rotate_dev(self, cts, out_trlwe, testvec=None, stream=None) -> None:
-        count = self._dev_batch(cts)
-        if out_trlwe.numel() != count * 2 * N or (testvec is not None and testvec.numel() != 2 * N):
-            raise ValueError("out_trlwe must be [count][2][N], testvec [2][N]")
-        self._chk(
-            self._lib.tfhe_hip_batch_blind_rotate_dev(
-                self._ctx, self._tp(cts), self._tp(testvec), self._tp(out_trlwe), count, self._stream_ptr(stream)
-            )
-        )
-
-    def batch_mux_dev(self, a, b, c, out, naive: bool, stream=None) -> None:
-        count = self._dev_batch(a, b, c, out)
-        self._chk(
-            self._lib.tfhe_hip_batch_mux_dev(
-                self._ctx, int(naive), self._tp(a), self._tp(b), self._tp(c), self._tp(out), count, self._stream_ptr(stream)
-            )
-        )
 
     # -- measurement ------------------------------------------------------------
     def set_profiling(self, enabled: bool) -> None:
@@ -674,7 +687,7 @@ class Engine:
         return buf.value.decode()
 
 
-class Pool:
+class Pool(_Handle):
     """Several GPUs behind one handle (`tfhe_hip_pool`): the reference's Rayon `par_map` over the ciphertexts of
     a batch (src/parallel/rayon_impl.rs:40-47) as a map over devices.  `devices` may repeat an index (two
     contexts on one GPU).  The cloud key goes to the first device once and is replicated device to device;
@@ -698,34 +711,38 @@ class Pool:
                 raise _capi.TfheHipError(rc, msg.decode() if msg else "")
         self._h = h
         self.home = 0  # member whose GPU holds the operands of the *_dev calls (their `home` argument's default)
-        self._parent = _view_of  # keeps the parent pool alive for as long as this view exists
-        self._views = []
-        if _view_of is not None:
-            import weakref
-
-            _view_of._views.append(weakref.ref(self))
+        self._link(_view_of)
 
     def new_key_view(self) -> "Pool":
         """Another resident cloud key on every member of this pool (`tfhe_hip_pool_key_create`)."""
         base = self._parent if self._parent is not None else self
         return Pool(base.params, base.devices, _view_of=base)
 
-    def close(self) -> None:
+    # -- what a pool supplies to the shared calls ------------------------------------------------------------------------
+    def _destroy(self) -> None:
         if getattr(self, "_h", None):
-            for ref in getattr(self, "_views", []):  # key views go before the pool they run on
-                v = ref()
-                if v is not None:
-                    v.close()
-            self._views = []
             self._lib.tfhe_hip_pool_destroy(self._h)
-            self._h = None
-            self._parent = None
+        self._h = None
 
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+    def _chk(self, rc: int) -> None:
+        if rc != _capi.OK:
+            msg = self._lib.tfhe_hip_pool_last_error(self._h)
+            raise _capi.TfheHipError(rc, msg.decode() if msg else "")
+
+    def _call(self, name: str, *args) -> None:
+        self._chk(getattr(self._lib, "tfhe_hip_pool_" + name)(self._h, *args))
+
+    def _call_dev(self, name: str, home, *args) -> None:
+        self._call(name, home, *args)
+
+    def _device(self, home) -> int:
+        if not 0 <= home < len(self.devices):
+            raise ValueError("no such pool member")
+        return self.devices[home]
+
+    @property
+    def device(self) -> int:
+        return self.devices[self.home]
 
     def __len__(self) -> int:
         return int(self._lib.tfhe_hip_pool_size(self._h))
@@ -738,11 +755,6 @@ class Pool:
     def combine_stats(self) -> list:
         """`Engine.combine_stats` of every member."""
         return [Engine.from_pool(self, i).combine_stats() for i in range(len(self))]
-
-    def _chk(self, rc: int) -> None:
-        if rc != _capi.OK:
-            msg = self._lib.tfhe_hip_pool_last_error(self._h)
-            raise _capi.TfheHipError(rc, msg.decode() if msg else "")
 
     @property
     def key_transport(self) -> str:
@@ -760,248 +772,9 @@ class Pool:
         self._lib.tfhe_hip_pool_shard(count, member, self.members_for(count), C.byref(lo), C.byref(hi))
         return int(lo.value), int(hi.value)
 
-    # -- cloud key ------------------------------------------------------------
-    def load_cloud_key(self, cloud_key) -> None:
-        p = self.params
-        bsk = np.ascontiguousarray(cloud_key.bootstrapping_key, dtype=np.float64)
-        ksk, tv = _u32(cloud_key.key_switching_key), _u32(cloud_key.blind_rotate_testvec)
-        if bsk.size != p.n * 2 * p.l * 2 * N or ksk.size != N * p.iks_t * p.base * (p.n + 1) or tv.size != 2 * N:
-            raise ValueError("cloud key has the wrong size for these parameters")
-        self._chk(self._lib.tfhe_hip_pool_load_cloud_key(self._h, _ptr(bsk), _ptr(ksk),
-                                                         C.c_uint32(int(cloud_key.decomposition_offset)), _ptr(tv)))
-
-    def load_compressed_cloud_key(self, compressed_key) -> None:
-        """The seeded key expanded on the first member and replicated (`tfhe_hip_pool_load_compressed_cloud_key`)."""
-        bsk, ksk, tv, seed = _compressed_args(self.params, compressed_key)
-        self._chk(self._lib.tfhe_hip_pool_load_compressed_cloud_key(
-            self._h, C.addressof(seed), _ptr(bsk), _ptr(ksk), C.c_uint32(int(compressed_key.decomposition_offset)),
-            _ptr(tv)))
-
-    def gen_cloud_key(self, key_lv0, key_lv1, seed=None) -> None:
-        """seed=None: generator keyed by the OS (tfhe_hip_pool_gen_cloud_key_secure); an integer: tests only."""
-        p = self.params
-        k0, k1 = _u32(key_lv0).reshape(-1), _u32(key_lv1).reshape(-1)
-        if len(k0) != p.n or len(k1) != N:
-            raise ValueError("secret key has the wrong size for these parameters")
-        a0, a1 = C.c_double(p.alpha_lv0), C.c_double(p.alpha_lv1)
-        if seed is None:
-            self._chk(self._lib.tfhe_hip_pool_gen_cloud_key_secure(self._h, _ptr(k0), _ptr(k1), a0, a1))
-        else:
-            self._chk(self._lib.tfhe_hip_pool_gen_cloud_key(self._h, _ptr(k0), _ptr(k1), a0, a1,
-                                                            C.c_uint64(int(seed) & 0xFFFFFFFFFFFFFFFF)))
-
     def export_cloud_key(self, member: int = 0):
-        from .key import CloudKey
-
-        p = self.params
-        bsk = np.empty((p.n, 2 * p.l, 2, N), np.float64)
-        ksk = np.empty((N, p.iks_t, p.base, p.n + 1), np.uint32)
-        tv = np.empty((2, N), np.uint32)
-        off = C.c_uint32(0)
-        self._chk(self._lib.tfhe_hip_pool_export_cloud_key(self._h, member, _ptr(bsk), _ptr(ksk), C.byref(off), _ptr(tv)))
-        return CloudKey(p, bsk, ksk, int(off.value), tv)
-
-    # -- batched hot path, host arrays ------------------------------------------
-    def _cts(self, a) -> np.ndarray:
-        return _u32(a).reshape(-1, self.params.n + 1)
-
-    def batch_gate(self, gate: int, a, b=None, out=None) -> np.ndarray:
-        a = self._cts(a)
-        bb = self._cts(b) if b is not None else None
-        if bb is not None and bb.shape != a.shape:
-            raise ValueError("operand batches differ in shape")
-        out = _out_like(a, out)
-        self._chk(self._lib.tfhe_hip_pool_batch_gate(self._h, int(gate), _ptr(a), _ptr(bb), _ptr(out), len(a)))
-        return out
-
-    def batch_gates_mixed(self, gates, a, b, keyswitch: bool = True) -> np.ndarray:
-        a, b = self._cts(a), self._cts(b)
-        g = np.ascontiguousarray(gates, dtype=np.uint8).reshape(-1)
-        if len(g) != len(a) or b.shape != a.shape:
-            raise ValueError("gates / operand batches differ in length")
-        out = np.empty_like(a)
-        fn = self._lib.tfhe_hip_pool_batch_gates_mixed if keyswitch else self._lib.tfhe_hip_pool_batch_gates_mixed_nks
-        self._chk(fn(self._h, _ptr(g), _ptr(a), _ptr(b), _ptr(out), len(a)))
-        return out
-
-    def batch_tlwe_lincomb(self, ca: int, a, cb: int = 0, b=None, cconst: int = 0) -> np.ndarray:
-        a = self._cts(a)
-        bb = self._cts(b) if b is not None else None
-        if (cb & 0xFFFFFFFF) and (bb is None or bb.shape != a.shape):
-            raise ValueError("second operand missing or of a different shape")
-        out = np.empty_like(a)
-        self._chk(self._lib.tfhe_hip_pool_batch_tlwe_lincomb(
-            self._h, ca & 0xFFFFFFFF, _ptr(a), cb & 0xFFFFFFFF, _ptr(bb), cconst & 0xFFFFFFFF, _ptr(out), len(a)))
-        return out
-
-    def batch_lincomb_bootstrap(self, ca: int, a, cb: int = 0, b=None, cconst: int = 0, testvec=None,
-                                keyswitch: bool = True) -> np.ndarray:
-        a = self._cts(a)
-        bb = self._cts(b) if b is not None else None
-        if (cb & 0xFFFFFFFF) and (bb is None or bb.shape != a.shape):
-            raise ValueError("second operand missing or of a different shape")
-        tv, per_ct = None, 0
-        if testvec is not None:
-            tv = _u32(testvec)
-            per_ct = int(tv.ndim == 3)
-            if tv.size != (len(a) if per_ct else 1) * 2 * N:
-                raise ValueError("test vector must be [2][N], or [count][2][N] for per-ciphertext tables")
-        out = np.empty_like(a)
-        self._chk(self._lib.tfhe_hip_pool_batch_lincomb_bootstrap(
-            self._h, ca & 0xFFFFFFFF, _ptr(a), cb & 0xFFFFFFFF, _ptr(bb), cconst & 0xFFFFFFFF, _ptr(tv), per_ct,
-            int(keyswitch), _ptr(out), len(a)))
-        return out
-
-    def batch_lincomb_bootstrap_many(self, ca: int, a, cb: int = 0, b=None, cconst: int = 0, testvec=None,
-                                     n_luts: int = 2, keyswitch: bool = True) -> np.ndarray:
-        """Engine.batch_lincomb_bootstrap_many over the members: [n_luts][count][n+1]."""
-        a, bb, tv, per_ct = _many_args(a, b, cb, testvec, self._cts)
-        out = np.empty((int(n_luts),) + a.shape, np.uint32) if n_luts in (1, 2, 4, 8) else np.empty(1, np.uint32)
-        self._chk(self._lib.tfhe_hip_pool_batch_lincomb_bootstrap_many(
-            self._h, ca & 0xFFFFFFFF, _ptr(a), cb & 0xFFFFFFFF, _ptr(bb), cconst & 0xFFFFFFFF, _ptr(tv), per_ct,
-            int(n_luts), int(keyswitch), _ptr(out), len(a)))
-        return out
-
-    def batch_bootstrap(self, cts, testvec=None, keyswitch: bool = True) -> np.ndarray:
-        cts = self._cts(cts)
-        out = np.empty_like(cts)
-        per_ct, tv = 0, None
-        if testvec is not None:
-            tv = _u32(testvec)
-            per_ct = int(tv.ndim == 3)
-            if tv.size != (len(cts) if per_ct else 1) * 2 * N:
-                raise ValueError("testvec must be [2][N] or [count][2][N]")
-        self._chk(self._lib.tfhe_hip_pool_batch_bootstrap(self._h, _ptr(cts), _ptr(tv), per_ct, int(keyswitch), _ptr(out),
-                                                          len(cts)))
-        return out
-
-    def batch_mux(self, a, b, c, naive: bool) -> np.ndarray:
-        a, b, c = self._cts(a), self._cts(b), self._cts(c)
-        if not (a.shape == b.shape == c.shape):
-            raise ValueError("operand batches differ in shape")
-        out = np.empty_like(a)
-        self._chk(self._lib.tfhe_hip_pool_batch_mux(self._h, int(bool(naive)), _ptr(a), _ptr(b), _ptr(c), _ptr(out), len(a)))
-        return out
-
-    def batch_blind_rotate(self, cts, testvec=None) -> np.ndarray:
-        cts = self._cts(cts)
-        tv = _u32(testvec) if testvec is not None else None
-        out = np.empty((len(cts), 2, N), np.uint32)
-        self._chk(self._lib.tfhe_hip_pool_batch_blind_rotate(self._h, _ptr(cts), _ptr(tv), _ptr(out), len(cts)))
-        return out
-
-    # -- a batch resident on ONE member's GPU (torch CUDA tensors on member `home`'s device; enqueue only) ----------
-    # Same signatures as Engine's *_dev methods plus `home` (default: self.home), so Circuit.run_dev,
-    # circuit.mux_and_gates_dev and circuit.lut_add_u8_dev take a Pool wherever they take an Engine: shard 0 is
-    # computed in place on the home GPU, the others travel by grouped RCCL send / receive (or peer copies) and come
-    # back in input order (`tfhe_hip_pool_batch_*_dev`, include/tfhe_hip.h).
-    @property
-    def device(self) -> int:
-        return self.devices[self.home]
-
-    def _home(self, home) -> int:
-        h = self.home if home is None else int(home)
-        if not 0 <= h < len(self.devices):
-            raise ValueError("no such pool member")
-        return h
-
-    def _dev_batch(self, home: int, *tensors, width=None) -> int:
-        width = self.params.n + 1 if width is None else width
-        first = tensors[0]
-        for t in tensors:
-            if t is None:
-                continue
-            if t.dim() != 2 or t.shape[1] != width or t.shape[0] != first.shape[0]:
-                raise ValueError(f"device tensors must all be [count][{width}]")
-            if t.device.index != self.devices[home]:
-                raise ValueError(f"device tensor lives on {t.device}, the home member on cuda:{self.devices[home]}")
-        return first.shape[0]
-
-    def _tp(self, home: int, t):
-        p = _tptr(t)
-        if t is not None and t.device.index != self.devices[home]:
-            raise ValueError(f"device tensor lives on {t.device}, the home member on cuda:{self.devices[home]}")
-        return p
-
-    def _stream_ptr(self, home: int, stream):
-        """The HOME member's stream: torch's current stream OF THAT DEVICE (the torch-current device may be another
-        GPU: a handle from there would be an invalid resource on the home GPU after the scatter was enqueued), or the
-        caller's stream, which must live on the home member's device."""
-        import torch
-
-        dev = self.devices[home]
-        if stream is None:
-            stream = torch.cuda.current_stream(dev)
-        elif getattr(stream, "device", None) is not None and stream.device.index != dev:
-            raise ValueError(f"stream lives on {stream.device}, the home member on cuda:{dev}")
-        return C.c_void_p(stream.cuda_stream or 1)
-
-    def batch_gate_dev(self, gate: int, a, b, out, stream=None, home=None) -> None:
-        h = self._home(home)
-        count = self._dev_batch(h, a, b, out)
-        self._chk(self._lib.tfhe_hip_pool_batch_gate_dev(self._h, h, int(gate), self._tp(h, a), self._tp(h, b), self._tp(h, out),
-                                                         count, self._stream_ptr(h, stream)))
-
-    def batch_gates_mixed_dev(self, gates, a, b, out, stream=None, keyswitch: bool = True, home=None) -> None:
-        h = self._home(home)
-        if not gates.is_cuda or gates.element_size() != 1 or not gates.is_contiguous() or gates.device.index != self.devices[h]:
-            raise ValueError("gates must be a contiguous uint8 CUDA tensor on the home member's GPU")
-        count = self._dev_batch(h, a, b, out)
-        if gates.numel() != count:
-            raise ValueError("one gate code per ciphertext")
-        fn = self._lib.tfhe_hip_pool_batch_gates_mixed_dev if keyswitch else self._lib.tfhe_hip_pool_batch_gates_mixed_nks_dev
-        self._chk(fn(self._h, h, C.c_void_p(gates.data_ptr()), self._tp(h, a), self._tp(h, b), self._tp(h, out), count,
-                     self._stream_ptr(h, stream)))
-
-    def batch_bootstrap_dev(self, cts, out, testvec=None, per_ct: bool = False, keyswitch: bool = True, stream=None,
-                            home=None) -> None:
-        h = self._home(home)
-        count = self._dev_batch(h, cts, out)
-        if testvec is not None and testvec.numel() != (count if per_ct else 1) * 2 * N:
-            raise ValueError("test vector must be [2][N], or [count][2][N] with per_ct")
-        self._chk(self._lib.tfhe_hip_pool_batch_bootstrap_dev(self._h, h, self._tp(h, cts), self._tp(h, testvec), int(per_ct),
-                                                              int(keyswitch), self._tp(h, out), count, self._stream_ptr(h, stream)))
-
-    def batch_tlwe_lincomb_dev(self, ca: int, a, cb: int, b, cconst: int, out, stream=None, home=None) -> None:
-        h = self._home(home)
-        count = self._dev_batch(h, a, b, out)
-        self._chk(self._lib.tfhe_hip_pool_batch_tlwe_lincomb_dev(
-            self._h, h, ca & 0xFFFFFFFF, self._tp(h, a), cb & 0xFFFFFFFF, self._tp(h, b), cconst & 0xFFFFFFFF, self._tp(h, out),
-            count, self._stream_ptr(h, stream)))
-
-    def batch_lincomb_bootstrap_dev(self, ca: int, a, cb: int, b, cconst: int, out, testvec=None, per_ct: bool = False,
-                                    keyswitch: bool = True, stream=None, home=None) -> None:
-        h = self._home(home)
-        count = self._dev_batch(h, a, b, out)
-        if testvec is not None and testvec.numel() != (count if per_ct else 1) * 2 * N:
-            raise ValueError("test vector must be [2][N], or [count][2][N] with per_ct")
-        self._chk(self._lib.tfhe_hip_pool_batch_lincomb_bootstrap_dev(
-            self._h, h, ca & 0xFFFFFFFF, self._tp(h, a), cb & 0xFFFFFFFF, self._tp(h, b), cconst & 0xFFFFFFFF,
-            self._tp(h, testvec), int(per_ct), int(keyswitch), self._tp(h, out), count, self._stream_ptr(h, stream)))
-
-    def batch_lincomb_bootstrap_many_dev(self, ca: int, a, cb: int, b, cconst: int, out, testvec, n_luts: int = 2,
-                                         per_ct: bool = False, keyswitch: bool = True, stream=None, home=None) -> None:
-        h = self._home(home)
-        count = self._dev_batch(h, a, b)
-        _many_dev_check(out, testvec, count, n_luts, per_ct, self.params.n + 1, self.devices[h])
-        self._chk(self._lib.tfhe_hip_pool_batch_lincomb_bootstrap_many_dev(
-            self._h, h, ca & 0xFFFFFFFF, self._tp(h, a), cb & 0xFFFFFFFF, self._tp(h, b), cconst & 0xFFFFFFFF,
-            self._tp(h, testvec), int(per_ct), int(n_luts), int(keyswitch), self._tp(h, out), count,
-            self._stream_ptr(h, stream)))
-
-    def batch_mux_dev(self, a, b, c, out, naive: bool, stream=None, home=None) -> None:
-        h = self._home(home)
-        count = self._dev_batch(h, a, b, c, out)
-        self._chk(self._lib.tfhe_hip_pool_batch_mux_dev(self._h, h, int(naive), self._tp(h, a), self._tp(h, b), self._tp(h, c),
-                                                        self._tp(h, out), count, self._stream_ptr(h, stream)))
-
-    def batch_blind_rotate_dev(self, cts, out_trlwe, testvec=None, stream=None, home=None) -> None:
-        h = self._home(home)
-        count = self._dev_batch(h, cts)
-        if out_trlwe.numel() != count * 2 * N or (testvec is not None and testvec.numel() != 2 * N):
-            raise ValueError("out_trlwe must be [count][2][N], testvec [2][N]")
-        self._chk(self._lib.tfhe_hip_pool_batch_blind_rotate_dev(self._h, h, self._tp(h, cts), self._tp(h, testvec),
-                                                                 self._tp(h, out_trlwe), count, self._stream_ptr(h, stream)))
+        """The key of pool member `member` back as a CloudKey in the reference layouts."""
+        return self._export_cloud_key(member)
 
     def synchronize(self) -> None:
         """Drain every member's own stream (`tfhe_hip_pool_synchronize`); the home stream is the caller's."""
