@@ -12,14 +12,20 @@ shard (weak scaling, no data-path collective: the path shards embarrassingly).
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W
 
-Rank 0 prints ONE JSON line (see the driver contract), with two extra objects:
+Rank 0 prints ONE JSON line (see the driver contract), with an extra object:
   roofline     -- the dominant kernel (k_blind_rotate) against the resource that binds it: FP64 vector
                   arithmetic (f64 flops of the CMUX loop, counted from the ISA of the build being timed,
                   over the HIP-event launch duration, vs the 78.6 TFLOP/s FP64 vector peak), with the
                   shader clock and board power sampled during the timed steps, the VALU issue fraction
                   at that clock, the algorithmic-HBM figure of SURVEY 8(d) and the physical HBM fraction
-  cpu_baseline -- the oracle (C port of the reference path, OpenMP over ciphertexts =
-                  Rayon par_iter) on this box's host cores, thread-count sweep, bounded sample (N=1 only)
+
+A plain run does only what the headline needs: set-up, warm-up, the timed steps, --dump-outputs, the line.
+--full adds what takes runs of its own (a minute or more at the default batch), each filled in on the line:
+  cpu_baseline  -- the oracle (C port of the reference path, OpenMP over ciphertexts = Rayon par_iter) on
+                   this box's host cores, thread-count sweep, bounded sample; the single-gate latency table and
+                   the team-of-threads rates through the GPU path (N=1 only)
+  other_configs -- short child runs of BASELINE configs[3] / [4] and of the host-buffer path (N=1 only)
+  pool_resident -- the global batch through ONE pool handle over all N devices, in a child (N>1 only)
 """
 import argparse
 import json
@@ -53,7 +59,9 @@ def parse():
                     "or 'mux' / 'mux_naive', or 'mixed' = half hom_mux + half hom_xor (BASELINE configs[4])")
     ap.add_argument("--modulus", type=int, default=16, help="message modulus of the 'pbs' workload (16 fits SECURITY_UINT4; "
                     "UINT1 / UINT2 / UINT3 take 2 / 4 / 8)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true", help="also run what the headline does not need: the CPU baseline and "
+                    "GPU latency probes, the other BASELINE configs (N = 1), the pool-resident run (N > 1)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline leg")
     ap.add_argument("--pool-devices", default=None, help="comma-separated device list: instead of the contract run, time "
                     "ONE process driving these devices through tfhe_hip_pool_batch_gate with host buffers (what a Rust "
                     "caller of the pool gets, PCIe included); prints its own JSON line")
@@ -65,10 +73,11 @@ def parse():
     ap.add_argument("--stage", default=None, choices=["blind_rotate", "ifft", "fft", "poly_mul", "reencrypt"],
                     help="time one stage entry point instead of the gate path: the reference's criterion groups "
                     "`bootstrapping` (= trgsw::blind_rotate) and `fft_operations` (benches/gate_benchmarks.rs:77-125)")
-    ap.add_argument("--cpu-seconds", type=float, default=20.0, help="target wall time of the CPU sample (whole thread sweep)")
-    ap.add_argument("--no-other-configs", action="store_true", help="N = 1: skip the short runs of BASELINE configs[3] / [4] and "
-                    "of the host-buffer path that the line carries as `other_configs`")
-    ap.add_argument("--no-pool-resident", action="store_true", help="N > 1: skip the single-process run of BASELINE configs[2] "
+    ap.add_argument("--cpu-seconds", type=float, default=20.0, help="with --full: target wall time of the CPU sample (whole "
+                    "thread sweep)")
+    ap.add_argument("--no-other-configs", action="store_true", help="with --full, N = 1: skip the short runs of BASELINE configs[3] / "
+                    "[4] and of the host-buffer path that the line carries as `other_configs`")
+    ap.add_argument("--no-pool-resident", action="store_true", help="with --full, N > 1: skip the single-process run of BASELINE configs[2] "
                     "through ONE pool handle (batch resident on GPU 0, shards moved by RCCL) that the line carries as `pool_resident`")
     ap.add_argument("--oracle-sample", type=int, default=0, help="with --pool-devices --resident: hold the first K results to the "
                     "CPU path word for word (under the key exported from member 0)")
@@ -450,7 +459,7 @@ def other_configs(args):
     out = {}
     for name, argv in (("configs3_pbs_uint4", ["--gate", "pbs", "--params", "SECURITY_UINT4"]),
                        ("configs4_share_mixed_80bit", ["--gate", "mixed", "--params", "SECURITY_80_BIT"])):
-        d = child_line(["--gpus", 1, "--steps", 3, "--warmup", 1, "--batch", args.batch, "--no-cpu-baseline", "--no-other-configs"] + argv)
+        d = child_line(["--gpus", 1, "--steps", 3, "--warmup", 1, "--batch", args.batch] + argv)
         out[name] = d if "error" in d else {
             "metric": d["metric"], "value": d["value"], "unit": d["unit"], "ms_per_step": d["ms_per_step"], "steps": d["steps"],
             "decrypt_ok": d["decrypt_ok"], "roofline_frac": d["roofline"]["frac"], "roofline_kernel": d["roofline"]["kernel"],
@@ -674,10 +683,11 @@ def main():
         dist.all_reduce(flag, op=dist.ReduceOp.MIN)
         decrypt_ok = bool(flag.item())
     key_broadcast_backend = dist.get_backend() if world > 1 else None
+    run_pool_resident = world > 1 and args.full and not args.no_pool_resident  # (alike on every rank: it adds a barrier)
     if rank != 0:
         if world > 1:
             pool.close()  # give the GPU back before rank 0 starts the pool-resident child
-            if not args.no_pool_resident:
+            if run_pool_resident:
                 dist.barrier()
             dist.destroy_process_group()
         return
@@ -799,7 +809,7 @@ def main():
     }
 
     cpu = None
-    if world == 1 and not args.no_cpu_baseline and not special:
+    if world == 1 and args.full and not args.no_cpu_baseline and not special:
         # The CPU leg: the oracle (C port of the reference path) under the SAME key, exported from the
         # engine, on the same ciphertexts.  This is the only place bench.py touches oracle/.
         from oracle import oracle as O
@@ -877,13 +887,13 @@ def main():
         }
 
     others = None
-    if world == 1 and not args.no_other_configs and not special and args.params == "SECURITY_128_BIT":
+    if world == 1 and args.full and not args.no_other_configs and not special and args.params == "SECURITY_128_BIT":
         pool.close()  # (the children use this GPU: give the key and the staging back first)
         del ta, tb, to
         torch.cuda.empty_cache()
         others = other_configs(args)
     resident = None
-    if world > 1 and not args.no_pool_resident:
+    if run_pool_resident:
         # BASELINE configs[2] as its text has it -- "sharded across 8 x MI355X via RCCL over xGMI": ONE caller, ONE pool
         # handle over all N devices, the GLOBAL batch resident on GPU 0, shards scattered / gathered by grouped
         # ncclSend / ncclRecv (tfhe_hip_pool_batch_gate_dev; src/gates.rs:357-383 is the call it replaces).  The ranks

@@ -20,7 +20,7 @@ DEVS=$(python3 -c "print(','.join(str(i) for i in range($NGPU)))")
 : > "$O/bench_scaling.jsonl"
 for n in 1 2 4 8; do
   [ "$n" -le "$NGPU" ] || continue
-  python3 bench.py --gpus $n --steps 20 --warmup 5 $([ "$n" -gt 1 ] && echo --no-cpu-baseline) | grep '^{' | tee -a "$O/bench_scaling.jsonl" | cut -c1-200
+  python3 bench.py --gpus $n --steps 20 --warmup 5 --full $([ "$n" -gt 1 ] && echo --no-cpu-baseline) | grep '^{' | tee -a "$O/bench_scaling.jsonl" | cut -c1-200
 done
 if [ "$NGPU" -ge 2 ]; then
   TFHE_HIP_POOL_RCCL=1 python3 bench.py --pool-devices $DEVS --resident --steps 5 --warmup 2 --oracle-sample 16 | grep '^{' > "$O/pool_resident_rccl.json"

@@ -165,7 +165,7 @@ def test_contract_bench_scales_over_the_gpus():
     sizes = [n for n in (1, 2, 4, 8) if n <= len(devs)]
     values = {}
     for n in sizes:
-        d = _bench(["--gpus", n, "--steps", 5, "--warmup", 2, "--no-cpu-baseline", "--no-other-configs"], share)
+        d = _bench(["--gpus", n, "--steps", 5, "--warmup", 2, "--no-cpu-baseline", "--no-other-configs", "--full"], share)
         assert d["n_gpus"] == n and d["decrypt_ok"] is True
         values[n] = d["value"]
         if n > 1:

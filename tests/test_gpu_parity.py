@@ -1847,6 +1847,7 @@ def test_bench_two_ranks_share_one_gpu():
     assert d["n_gpus"] == 2 and d["decrypt_ok"] is True and d["scaling"] == "weak"
     assert d["config"]["global_batch"] == 4096 and d["value"] > 0 and d["unit"] == "bootstraps/s"
     assert d["roofline"]["avg_launch_ms"] > 0 and d["cpu_baseline"] is None
+    assert d["pool_resident"] is None  # a plain run starts no child: that leg is --full's
 
 
 def test_bench_two_ranks_mixed_circuit_80bit():
@@ -1862,7 +1863,7 @@ def test_bench_four_ranks_share_one_gpu():
     most a shared box allows): no MASTER_PORT given, so the torchrun child gets a port that is free now; the line carries
     every rank's own time for the steps, its kernels' launch times and the key broadcast's duration."""
     for extra in ([], ["--gate", "mixed", "--params", "SECURITY_80_BIT"]):
-        d = _run_bench(["--gpus", "4", "--steps", "1", "--warmup", "0", "--batch", "1024", "--no-cpu-baseline"] + extra,
+        d = _run_bench(["--gpus", "4", "--steps", "1", "--warmup", "0", "--batch", "1024", "--no-cpu-baseline", "--full"] + extra,
                        {"BENCH_SHARE_GPU": "1"})
         assert d["n_gpus"] == 4 and d["decrypt_ok"] is True and d["scaling"] == "weak"
         assert d["config"]["global_batch"] == 4096 and d["value"] > 0
@@ -1896,10 +1897,10 @@ def test_bench_pool_resident_eight_members_one_process():
 
 
 def test_bench_line_carries_the_other_configs_and_the_concurrent_callers():
-    """The N = 1 line (what the driver records as BENCH_rNN) beside its headline: short runs of BASELINE configs[3] and
-    of configs[4]'s single-GPU share, the host-buffer path pageable and pinned, and the aggregate rate of a team of
-    threads making one-ciphertext calls (cpu_baseline.gpu_concurrent_single_gate)."""
-    d = _run_bench(["--steps", "2", "--warmup", "1", "--batch", "4096", "--cpu-seconds", "3"], {}, timeout=1200)
+    """The N = 1 line of `bench.py --full` beside its headline: short runs of BASELINE configs[3] and of configs[4]'s
+    single-GPU share, the host-buffer path pageable and pinned, and the aggregate rate of a team of threads making
+    one-ciphertext calls (cpu_baseline.gpu_concurrent_single_gate)."""
+    d = _run_bench(["--steps", "2", "--warmup", "1", "--batch", "4096", "--cpu-seconds", "3", "--full"], {}, timeout=1200)
     oc = d["other_configs"]
     for k in ("configs3_pbs_uint4", "configs4_share_mixed_80bit", "host_path_pageable", "host_path_pinned"):
         assert "error" not in oc[k], oc[k]
@@ -1910,6 +1911,10 @@ def test_bench_line_carries_the_other_configs_and_the_concurrent_callers():
     assert cc["threads"] == [1, 8, 64, 256] and len(cc["gates_per_s"]) == 4
     assert cc["gates_per_s"][2] > 10 * cc["unmerged_gates_per_s_8_threads"], cc
     assert d["cpu_baseline"]["gpu_matches_cpu_bit_exact"] is True and d["decrypt_ok"] is True
+    # the plain run of the same arguments: the headline alone
+    p = _run_bench(["--steps", "2", "--warmup", "1", "--batch", "4096"], {})
+    assert p["decrypt_ok"] is True and p["value"] > 0 and p["roofline"]["avg_launch_ms"] > 0
+    assert p["cpu_baseline"] is None and p["other_configs"] is None
 
 
 def test_bench_pool_two_members_pinned_and_pageable():
