@@ -143,6 +143,16 @@ struct CompressedCloudKey {
   }
 };
 
+// The packing key of include/tfhe_hip.h ("packing key switch"): the public mask seed plus the bodies [n][t][N]; the
+// device regenerates the masks on load.  Made by the client (rs-tfhe_amd/packing.py: make_packing_key).
+struct PackingKey {
+  SecurityParams params = DEFAULT_SECURITY;
+  std::array<uint8_t, 32> mask_seed{};
+  std::vector<Torus> bodies;  // [n][t][N]
+  size_t nbytes() const { return bodies.size() * sizeof(Torus) + mask_seed.size(); }
+  bool matches(const SecurityParams &p) const { return params == p && bodies.size() == (size_t)p.n * p.iks_t * N; }
+};
+
 // ---- engine handle: ONE C-ABI context per (parameter set, device); every cloud key is a key view of it ------
 // The reference passes `&CloudKey` into every call and its strategies are `Send + Sync`
 // (bootstrap/mod.rs:23).  The C ABI's answer is the KEY VIEW (tfhe_hip_key_create, include/tfhe_hip.h): another
@@ -168,6 +178,7 @@ class Engine {
     if (rc != TFHE_HIP_OK) throw std::runtime_error(std::string("tfhe_hip_ctx_create: ") + tfhe_hip_last_error(nullptr));
   }
   ~Engine() {
+    if (pk_view_) tfhe_hip_ctx_destroy(pk_view_);
     for (auto &v : views_) tfhe_hip_ctx_destroy(v->h);  // views before their context
     tfhe_hip_ctx_destroy(ctx_);
   }
@@ -245,6 +256,25 @@ class Engine {
     });
   }
   static Bound load_compressed_cloud_key(const CompressedCloudKey &ck, int device = 0) { return for_key(ck, device); }
+
+  // Packing key switch (tfhe_hip_batch_pack_tlwe): `count` lv0 results [count][n+1] -> ceil(count / N) TRLWE lv1
+  // [G][2][N] under s1.  The packing key sits in a key view of its own on this context, loaded again only when another
+  // key (address or content sample) is passed; packing needs no cloud key.
+  std::vector<Torus> pack(const PackingKey &pk, const Torus *in, size_t count) {
+    if (!pk.matches(params_)) throw std::runtime_error("PackingKey does not match the parameter set");
+    std::lock_guard<std::mutex> lk(pk_mu_);
+    const uint64_t fp = fingerprint(pk);
+    if (!pk_view_ && tfhe_hip_key_create(ctx_, &pk_view_) != TFHE_HIP_OK) throw std::runtime_error("tfhe_hip_key_create failed");
+    if (pk_key_ != &pk || pk_fp_ != fp || !tfhe_hip_packing_key_is_loaded(pk_view_)) {
+      pk_key_ = nullptr;
+      check(tfhe_hip_load_packing_key(pk_view_, pk.mask_seed.data(), pk.bodies.data()));
+      pk_key_ = &pk;
+      pk_fp_ = fp;
+    }
+    std::vector<Torus> out((count + N - 1) / N * 2 * N);
+    check(tfhe_hip_batch_pack_tlwe(pk_view_, in, count, out.data()));
+    return out;
+  }
 
  private:
   // the key view of (addr, fp) on the one context of (p, device): found, or created (dropping the least recently used
@@ -334,9 +364,22 @@ class Engine {
     mix(nb);
     return h;
   }
+  static uint64_t fingerprint(const PackingKey &pk) {  // the seed, 64 evenly spaced body words, the size
+    uint64_t h = 0x165667B19E3779F9ull;
+    auto mix = [&](uint64_t v) { h = (h ^ v) * 0x100000001B3ull; };
+    for (size_t i = 0; i < pk.mask_seed.size(); ++i) mix(pk.mask_seed[i]);
+    const size_t nb = pk.bodies.size();
+    for (size_t i = 0; i < 64 && nb; ++i) mix(pk.bodies[(nb - 1) * i / 64]);
+    mix(nb);
+    return h;
+  }
   SecurityParams params_;
   tfhe_hip_ctx *ctx_ = nullptr;
   std::vector<std::unique_ptr<View>> views_;  // registry lock
+  std::mutex pk_mu_;                           // the packing key's view (pack)
+  tfhe_hip_ctx *pk_view_ = nullptr;
+  const void *pk_key_ = nullptr;
+  uint64_t pk_fp_ = 0;
   int device_ = 0;
 };
 

@@ -245,6 +245,49 @@ int tfhe_hip_expand_seeded_tlwe(tfhe_hip_ctx *ctx, const uint8_t mask_seed[32], 
 int tfhe_hip_expand_seeded_tlwe_dev(tfhe_hip_ctx *ctx, const uint8_t mask_seed[32], uint64_t first_index,
                                     const uint32_t *bodies, size_t count, uint32_t *out, void *stream);
 
+/* ---- packing key switch: up to N = 1024 lv0 results in one TRLWE lv1 ------
+ *
+ * A result leaves the server as an (n+1)-word TLWE lv0 (2,804 bytes on SECURITY_128_BIT).  A TRLWE lv1 is 2N words
+ * (8 KiB) and each of its N coefficients can carry the phase of one LWE: the packing key switch (LWE -> GLWE key
+ * switching) turns a batch of lv0 results into ceil(count / N) TRLWEs that the client decrypts with the s1 it holds,
+ * 350x fewer bytes on SECURITY_128_BIT and 410x on UINT4.
+ *
+ * Definition (normative).  From the context's set: n, N = 1024, beta = basebit (<= 7: the digits fit in a byte),
+ * t = iks_t, B = 2^beta, g_l = 2^(32 - (l+1) beta).
+ *   Packing key.  One TRLWE lv1 row under s1 for each (i < n, l < t), row r = i*t + l:
+ *     a_r  N keystream words under a public 32-byte mask seed S (RFC 8439 block, word x = word x mod 16 of counter
+ *          x / 16, as in the seeded section), nonce (r, 24, 0x504B53);
+ *     b_r  = a_r (*) s1 + e_r + s0[i]*g_l*X^0, every coefficient mod 2^32, e_r = f64_to_torus(N(0, alpha)) per
+ *          coefficient (alpha: alpha_lv1 of the set by default).
+ *   Only the bodies travel: bodies [n][t][N] u32 (25.8 MB on SECURITY_128_BIT, 15.8 MB on 80-bit, 10.1 MB on UINT4,
+ *   14.3 MB on UINT8).  The key encrypts bits of s0 under s1, exactly as the BSK does: it adds no new security
+ *   assumption.
+ *   Digits.  The identity key switch's rounding, then a signed decomposition:
+ *     a_bar = ((a + 2^(31 - beta t)) mod 2^32) >> (32 - beta t);  carry = 0;
+ *     for l = t-1 down to 0: v = ((a_bar >> beta(t-1-l)) & (B-1)) + carry;
+ *                            v >= B/2 ? (d_l = v - B, carry = 1) : (d_l = v, carry = 0)     (the last carry is dropped)
+ *     so d_l in [-B/2, B/2) and sum_l d_l g_l = a_bar 2^(32 - beta t) (mod 2^32).
+ *   Pack.  Input c_m = (a_m, b_m), m < count, lands in group G = m / N, slot j = m mod N.  Per group, with
+ *   D_{i,l}(X) = sum_j d_l(a_j[i]) X^j over the group's inputs:
+ *     A = - sum_{i,l} D_{i,l} (*) a_{i,l},    B = sum_j b_j X^j - sum_{i,l} D_{i,l} (*) b_{i,l}
+ *   negacyclic mod X^N + 1, wrapping mod 2^32.  Output [ceil(count / N)][2][N] u32, a row then b row (the layout of
+ *   tfhe_hip_batch_blind_rotate).  Coefficient j of B - A (*) s1 is the phase of c_j plus the rounding error and the key
+ *   noise; unused slots of the last group hold phase 0 plus noise.  The result is defined in integers: every device
+ *   and parameter set gives these words exactly.
+ * Semantics.  The packing key lives beside the cloud key of a context or key view: loading, generating or adopting a
+ * cloud key (or loading a re-encryption key) leaves it, packing needs no cloud key, destroying a view frees its key.
+ * Packing without one: TFHE_HIP_ENOKEY.  Packing calls are bulk calls (the context's mutex, never the combining
+ * front end).  _dev: device pointers, queued on `stream` (NULL: the context's stream). */
+/* Word count of `bodies` for `params`.  Initialises no device. */
+int tfhe_hip_packing_key_words(const tfhe_hip_params *params, size_t *body_words);
+/* Uploads the bodies and expands the key on the device (masks from S, then the kernel's byte planes). */
+int tfhe_hip_load_packing_key(tfhe_hip_ctx *ctx, const uint8_t mask_seed[32], const uint32_t *bodies);
+/* 0 / 1, never an error code (no device call is made). */
+int tfhe_hip_packing_key_is_loaded(tfhe_hip_ctx *ctx);
+/* in [count][n+1] lv0 ciphertexts -> out [ceil(count / N)][2][N]. */
+int tfhe_hip_batch_pack_tlwe(tfhe_hip_ctx *ctx, const uint32_t *in, size_t count, uint32_t *out);
+int tfhe_hip_batch_pack_tlwe_dev(tfhe_hip_ctx *ctx, const uint32_t *in, size_t count, uint32_t *out, void *stream);
+
 /* Pinned host buffers.  The host entry points below take ordinary (pageable) memory and stage it through the
  * device around the kernels: 3 x 184 MB for a 65,536-ciphertext gate batch, about 7 % of the call.  When EVERY
  * ciphertext operand of a call (inputs and output) is pinned host memory -- allocated here, or the caller's own
@@ -570,6 +613,12 @@ int tfhe_hip_pool_load_compressed_cloud_key(tfhe_hip_pool *pool, const uint8_t m
                                             const uint32_t *ksk_bodies, uint32_t decomp_offset, const uint32_t *testvec);
 int tfhe_hip_pool_export_cloud_key(tfhe_hip_pool *pool, int member, double *bsk, uint32_t *ksk,
                                    uint32_t *decomp_offset, uint32_t *testvec);
+/* Packing key switch on a pool: every member loads the packing key; a batch is split in whole groups of N over the
+ * members, in input order (the _dev form through the grouped scatter / gather, a last partial group on home). */
+int tfhe_hip_pool_load_packing_key(tfhe_hip_pool *pool, const uint8_t mask_seed[32], const uint32_t *bodies);
+int tfhe_hip_pool_batch_pack_tlwe(tfhe_hip_pool *pool, const uint32_t *in, size_t count, uint32_t *out);
+int tfhe_hip_pool_batch_pack_tlwe_dev(tfhe_hip_pool *pool, int home_member, const uint32_t *in, size_t count,
+                                      uint32_t *out, void *stream);
 
 /* The batched hot path over all members, HOST pointers: same arguments and semantics as the single-context host
  * entry points of the same name (gates.rs:352-547; gates.rs:157-199; bootstrap/{vanilla,lut}.rs; trgsw.rs:289-305;

@@ -136,6 +136,32 @@ class SecretKey:
         scale = 1.0 / (2.0 * m)
         return (torus_to_f64(self.phase(cts)) / scale + 0.5).astype(np.int64) % m
 
+    # ---- packed results (packing key switch, include/tfhe_hip.h) ------------------------------------
+    def packing_key(self, rng_key=None, alpha=None):
+        """The packing key (packing.PackingKey: mask seed + bodies) under s1 for bits of s0, made on the CPU.  rng_key:
+        None draws from the OS CSPRNG; an int seed is reproducible (tests only).  alpha: alpha_lv1 by default."""
+        from .packing import make_packing_key
+
+        return make_packing_key(self.params, self.key_lv0, self.key_lv1, rng=rng_key, alpha=alpha)
+
+    def packed_phase(self, packed, count: int) -> np.ndarray:
+        """Phases of the first `count` results of [G][2][N] packed TRLWEs: coefficient j of B - A (*) s1 per group."""
+        from .seeded import negacyclic_binary
+
+        packed = np.ascontiguousarray(packed, dtype=np.uint32).reshape(-1, 2, N)
+        if len(packed) * N < count:
+            raise ValueError(f"{len(packed)} packed TRLWEs hold fewer than {count} results")
+        return (packed[:, 1] - negacyclic_binary(packed[:, 0], self.key_lv1)).reshape(-1)[:count]
+
+    def decrypt_packed_bool(self, packed, count: int) -> np.ndarray:
+        """decrypt_bool of packed results."""
+        return self.packed_phase(packed, count).view(np.int32) >= 0
+
+    def decrypt_packed_lwe_message(self, packed, count: int, message_modulus: int) -> np.ndarray:
+        """decrypt_lwe_message of packed results."""
+        m = int(message_modulus)
+        return (torus_to_f64(self.packed_phase(packed, count)) / (1.0 / (2.0 * m)) + 0.5).astype(np.int64) % m
+
     # ---- evaluation key ----------------------------------------------------------------------
     def cloud_key(self, seed=None, device: int = 0):
         """CloudKey::new(&secret_key) (key.rs:59-66): generated on the GPU in a fresh key view of the shared context

@@ -1,0 +1,304 @@
+// packing.hpp -- packing key switch: up to N = 1024 TLWE lv0 results in ONE TRLWE lv1 under s1.
+//
+// The format and the result are normative in include/tfhe_hip.h ("packing key switch").  For a group of inputs
+// c_j = (a_j, b_j), j < N, with d_l(x) the signed digits of the identity key switch's rounding of x:
+//
+//   A = - sum_{i,l} D_{i,l} (*) a_{i,l},   B = sum_j b_j X^j - sum_{i,l} D_{i,l} (*) b_{i,l},   D_{i,l} = sum_j d_l(a_j[i]) X^j
+//
+// computed as ONE integer contraction P[j][x] = sum_{(i,l)} d_l(a_j[i]) * K[(i,l)][x] over the 2N columns of the key
+// rows (a row, then b row), followed by the rotate-and-sum out[x + j] += P[j][x] (negacyclic: a term past N changes
+// sign).  The u32 key words are split ONCE, at load, into four balanced signed byte planes (ks_plane_byte of
+// key_switch_mfma.hpp), so every plane is an exact i8 x i8 -> i32 matrix-core product: |d| <= B/2 <= 64, so
+// |acc| <= n t (B/2) 128 < 2^25 on every supported set (< 2^21 on SECURITY_128_BIT), and sum_p acc_p << 8p wraps to
+// the u32 result -- equal word for word, not approximately.
+//
+// k_pack_mfma: a workgroup is 4 waves = the 4 byte planes of ONE (32-row block, kPkNT-tile column group, K chunk).  The
+// K axis runs over steps s = ib * t + l (ib: the 32 coefficients i = 32 ib + 16 kb + byte, l: the digit position), so
+// a lane keeps its 16 rounded a-words of block ib in registers and builds the t digit fragments of the block from them
+// by shifts.  The key planes are laid out [plane][column tile][step][lane][16 B] (k_pack_planes): a tile of a step is
+// one contiguous KiB, read straight into registers one step ahead of its matrix instructions.  The epilogue adds every
+// accumulator (shifted by its plane) into an LDS line indexed by x + j -- the anti-diagonals of the 32 x 32 tiles, the
+// group's kPkNT tiles side by side -- and merges the line into the output with integer atomics (order-free: the words
+// are deterministic).  Small batches cut K over workgroups (blockIdx.z), merged the same way.
+//
+// Every kernel here is a template: instantiations are emitted after the library's other kernels, so the code of every
+// existing kernel stays byte-identical.
+#pragma once
+#include "key_switch_mfma.hpp"
+#include "keygen.hpp"
+
+namespace tfhe {
+
+constexpr uint32_t kSeedDomainPack = 0x504B53u;  // "PKS": masks of the packing key, nonce (row, 24, "PKS")
+constexpr int kPkTiles = 2 * kN / 32;            // 32-column tiles of a key row: a = 0..31, b = 32..63
+constexpr int kPkNT = 8;                         // tiles per wave (divides 32: a column group never straddles a and b)
+constexpr int kPkMaxBasebit = 7;                 // digits in [-64, 64): one signed byte
+
+__host__ __device__ __forceinline__ int pk_blocks(int n) { return (n + 31) / 32; }         // 32-coefficient blocks
+__host__ __device__ __forceinline__ int pk_steps(int n, int t) { return pk_blocks(n) * t; }  // K-steps of 32
+__host__ __device__ __forceinline__ size_t pk_plane_bytes(int n, int t) {
+  return (size_t)4 * kPkTiles * pk_steps(n, t) * 1024;
+}
+
+// Key rows r = i t + l as [n t][2][N] u32: a from the keystream (r, 24, "PKS") under the mask seed, b from `bodies`.
+// One wave per row; lane q makes keystream block q (coefficients 16q .. 16q+15).
+template <int WG>
+__global__ __launch_bounds__(WG) void k_pack_expand_key(const uint32_t *__restrict__ bodies, uint32_t *__restrict__ rows,
+                                                         ChaChaKey seed) {
+  static_assert(WG == 64, "one wave per row");
+  const uint32_t r = blockIdx.x;
+  const int lane = threadIdx.x;
+  uint32_t w[16];
+  chacha20_block(seed, (uint32_t)lane, r, 24u, kSeedDomainPack, w);
+  uint4 *dst = reinterpret_cast<uint4 *>(rows + (size_t)r * 2 * kN + 16 * lane);
+#pragma unroll
+  for (int q = 0; q < 4; ++q) dst[q] = make_uint4(w[4 * q], w[4 * q + 1], w[4 * q + 2], w[4 * q + 3]);
+  const uint4 *src = reinterpret_cast<const uint4 *>(bodies + (size_t)r * kN + 16 * lane);
+  uint4 *dstb = reinterpret_cast<uint4 *>(rows + (size_t)r * 2 * kN + kN + 16 * lane);
+#pragma unroll
+  for (int q = 0; q < 4; ++q) dstb[q] = src[q];
+}
+
+// [n t][2N] u32 -> byte planes [plane p][tile ct][step s][lane][16 B]: lane = (column 32 ct + (lane & 31), kb = lane >> 5),
+// byte b = plane byte p of key row (i = 32 ib + 16 kb + b, l) at that column, s = ib t + l; 0 for i >= n.
+template <int WG>
+__global__ __launch_bounds__(WG) void k_pack_planes(const uint32_t *__restrict__ rows, unsigned char *__restrict__ out,
+                                                     int n, int t, size_t chunks) {
+  const size_t idx = (size_t)blockIdx.x * WG + threadIdx.x;
+  if (idx >= chunks) return;
+  const int lane = (int)(idx & 63);
+  size_t r = idx >> 6;
+  const int S = pk_steps(n, t);
+  const int s = (int)(r % (size_t)S);
+  r /= (size_t)S;
+  const int ct = (int)(r % kPkTiles), p = (int)(r / kPkTiles);
+  const int col = ct * 32 + (lane & 31), kb = lane >> 5;
+  const int ib = s / t, l = s % t;
+  uint32_t o[4];
+#pragma unroll
+  for (int q = 0; q < 4; ++q) {
+    uint32_t d = 0;
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+      const int i = 32 * ib + 16 * kb + 4 * q + e;
+      const uint32_t w = i < n ? rows[((size_t)i * t + l) * 2 * kN + col] : 0u;
+      d |= ks_plane_byte(w, p) << (8 * e);
+    }
+    o[q] = d;
+  }
+  reinterpret_cast<uint4 *>(out)[idx] = make_uint4(o[0], o[1], o[2], o[3]);
+}
+
+// out [groups][2][N]: a rows 0, b rows b_j on the slots that hold an input (k_pack_mfma's atomics add the rest)
+template <int WG>
+__global__ __launch_bounds__(WG) void k_pack_init(const uint32_t *__restrict__ in, size_t count, int n,
+                                                   uint32_t *__restrict__ out, size_t words) {
+  const size_t idx = (size_t)blockIdx.x * WG + threadIdx.x;
+  if (idx >= words) return;
+  const size_t g = idx / (2 * kN);
+  const int rem = (int)(idx % (2 * kN));
+  uint32_t v = 0u;
+  if (rem >= kN) {
+    const size_t m = g * kN + (size_t)(rem - kN);
+    if (m < count) v = in[m * (size_t)(n + 1) + n];
+  }
+  out[idx] = v;
+}
+
+// grid (ceil(count / 32), kPkTiles / NT, K chunks), 4 waves: wave w = byte plane w.  out holds k_pack_init's words.
+// Two workgroups per CU (at most 256 registers a lane, no spill): 5.8 against 7.6 ms for 65,536 SECURITY_128_BIT
+// results at one (profiles/packing_bench.json).
+template <int NT>
+__global__ __launch_bounds__(256, 2) void k_pack_mfma(const uint32_t *__restrict__ in, size_t count, int n, int basebit,
+                                                    int t, const unsigned char *__restrict__ pk8,
+                                                    uint32_t *__restrict__ out) {
+  static_assert(32 % NT == 0, "a column group stays inside the a or the b half");
+  constexpr int LINE = 32 * NT + 32;
+  __shared__ uint32_t line[LINE];
+  const int nib = pk_blocks(n), per = (nib + (int)gridDim.z - 1) / (int)gridDim.z;
+  const int ib0 = (int)blockIdx.z * per, ib1 = ib0 + per < nib ? ib0 + per : nib;
+  if (ib0 >= ib1) return;  // (workgroup-uniform) an empty K chunk
+  const int tid = threadIdx.x, lane = tid & 63, kb = lane >> 5;
+  const int plane = __builtin_amdgcn_readfirstlane(tid >> 6);
+  for (int d = tid; d < LINE; d += 256) line[d] = 0u;
+  const size_t row0 = (size_t)blockIdx.x * 32, row = row0 + (size_t)(lane & 31);
+  const bool live = row < count;
+  const uint32_t *arow = in + (live ? row : 0) * (size_t)(n + 1);
+  const int ct0 = (int)blockIdx.y * NT, S = nib * t;
+  // digits: a_bar = (a + 2^(31 - bt)) >> (32 - bt); adding B/2 at every digit position turns the plain base-B digits of
+  // (a_bar + off) mod 2^bt into the signed ones of the definition (carries included): d = digit - B/2
+  const int bt = basebit * t;
+  const uint32_t rnd = 1u << (31 - bt), bmask = (1u << basebit) - 1u, half = 1u << (basebit - 1);
+  const uint32_t btmask = (1u << bt) - 1u;
+  uint32_t off = 0;
+  for (int q = 0; q < t; ++q) off += half << (basebit * q);
+  const uint32_t bias = (128u - half) * 0x01010101u;  // bytes u < B <= 128: (u + 128 - B/2) ^ 0x80 = (u - B/2) as an i8
+  auto load_a = [&](int ib, uint32_t(&w)[16]) {
+#pragma unroll
+    for (int b = 0; b < 16; ++b) {
+      const int i = 32 * ib + 16 * kb + b;
+      w[b] = (live && i < n) ? arow[i] : 0u;  // a 0 word has all-zero digits
+    }
+  };
+  auto round_a = [&](const uint32_t(&w)[16], uint32_t(&ap)[16]) {
+#pragma unroll
+    for (int b = 0; b < 16; ++b) ap[b] = (((w[b] + rnd) >> (32 - bt)) + off) & btmask;
+  };
+  const unsigned char *kp = pk8 + ((size_t)(plane * kPkTiles + ct0) * S) * 1024 + (size_t)lane * 16;
+  const size_t tstride = (size_t)S * 1024;
+  auto load_b = [&](int s, km_i32x4(&B)[NT]) {
+#pragma unroll
+    for (int c = 0; c < NT; ++c) B[c] = *reinterpret_cast<const km_i32x4 *>(kp + c * tstride + (size_t)s * 1024);
+  };
+  km_i32x16 acc[NT];
+#pragma unroll
+  for (int c = 0; c < NT; ++c) acc[c] = km_i32x16{0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+  uint32_t w[16], ap[16];
+  load_a(ib0, w);
+  round_a(w, ap);
+  load_a(ib0 + 1, w);  // the next block's words (0 past n)
+  km_i32x4 Bc[NT];
+  const int s0 = ib0 * t, s1 = ib1 * t;
+  load_b(s0, Bc);
+  int l = 0;
+#pragma unroll 1
+  for (int s = s0; s < s1; ++s) {
+    km_i32x4 Bn[NT];
+    load_b(s + 1 < s1 ? s + 1 : s, Bn);  // one step ahead (the last step reloads its own tiles)
+    const int sh = basebit * (t - 1 - l);
+    km_u32x4 a;
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+      const uint32_t v = ((ap[4 * q] >> sh) & bmask) | (((ap[4 * q + 1] >> sh) & bmask) << 8) |
+                         (((ap[4 * q + 2] >> sh) & bmask) << 16) | (((ap[4 * q + 3] >> sh) & bmask) << 24);
+      a[q] = (v + bias) ^ 0x80808080u;
+    }
+    const km_i32x4 A = __builtin_bit_cast(km_i32x4, a);
+#pragma unroll
+    for (int c = 0; c < NT; ++c) acc[c] = __builtin_amdgcn_mfma_i32_32x32x32_i8(A, Bc[c], acc[c], 0, 0, 0);
+#pragma unroll
+    for (int c = 0; c < NT; ++c) Bc[c] = Bn[c];
+    if (++l == t) {  // the next step starts block s / t + 1
+      l = 0;
+      round_a(w, ap);
+      load_a(s / t + 2, w);
+    }
+  }
+  __syncthreads();  // (the line is zeroed)
+  // C element e of the lane: row (e & 3) + 8 (e >> 2) + 4 kb, column lane & 31 of its tile, so x + j - (x0 + j0) is
+  // 32 c + column + row
+  const uint32_t sh8 = 8u * (uint32_t)plane;
+#pragma unroll
+  for (int c = 0; c < NT; ++c)
+#pragma unroll
+    for (int e = 0; e < 16; ++e)
+      atomicAdd(&line[32 * c + (lane & 31) + (e & 3) + 8 * (e >> 2) + 4 * kb], (uint32_t)acc[c][e] << sh8);
+  __syncthreads();
+  const int x0 = (ct0 * 32) & (kN - 1), j0 = (int)(row0 & (kN - 1));
+  uint32_t *o = out + ((row0 / kN) * 2 + (ct0 >= kPkTiles / 2 ? 1 : 0)) * (size_t)kN;
+  for (int d = tid; d < LINE - 1; d += 256) {
+    const uint32_t v = line[d];
+    if (!v) continue;
+    const int y = x0 + j0 + d;  // < 2N
+    if (y < kN) atomicAdd(&o[y], 0u - v);  // A = -sum, B = sum_j b_j X^j - sum
+    else atomicAdd(&o[y - kN], v);         // X^y = -X^(y - N)
+  }
+}
+
+}  // namespace tfhe
+
+// ---- packing key switch (packing.hpp) -------------------------------------------------------------------------
+namespace {
+bool packing_supported(const tfhe_hip_params *p) { return params_supported(p) && p->basebit <= kPkMaxBasebit; }
+}  // namespace
+
+int tfhe_hip_packing_key_words(const tfhe_hip_params *params, size_t *body_words) {
+  if (!params || !body_words || !packing_supported(params)) return TFHE_HIP_EINVAL;
+  *body_words = (size_t)params->n * params->t * kN;
+  return TFHE_HIP_OK;
+}
+
+namespace {
+int need_packing_key(tfhe_hip_ctx *ctx) {
+  if (!ctx->K->pk_loaded) return fail(ctx, TFHE_HIP_ENOKEY, "packing key not loaded");
+  return TFHE_HIP_OK;
+}
+
+// K chunks of one launch: enough workgroups for every CU four times over, at most one chunk per coefficient block
+int pack_kchunks(const tfhe_hip_ctx *ctx, size_t rblocks) {
+  const size_t wgs = rblocks * (size_t)(kPkTiles / kPkNT), want = (size_t)(ctx->num_cus > 0 ? ctx->num_cus : 256) * 4;
+  const int nib = pk_blocks(ctx->P.n);
+  if (wgs >= want) return 1;
+  const size_t k = (want + wgs - 1) / wgs;
+  return k < (size_t)nib ? (int)k : nib;
+}
+
+int pack_launch(tfhe_hip_ctx *ctx, const uint32_t *in, size_t count, uint32_t *out, hipStream_t s) {
+  const tfhe_hip_params &P = ctx->P;
+  const size_t groups = (count + kN - 1) / kN, words = groups * 2 * kN;
+  hipLaunchKernelGGL(k_pack_init<256>, dim3((unsigned)((words + 255) / 256)), dim3(256), 0, s, in, count, P.n, out, words);
+  CHK(launched(ctx));
+  const size_t rblocks = (count + 31) / 32;
+  hipLaunchKernelGGL(k_pack_mfma<kPkNT>, dim3((unsigned)rblocks, kPkTiles / kPkNT, (unsigned)pack_kchunks(ctx, rblocks)),
+                     dim3(256), 0, s, in, count, P.n, P.basebit, P.t, (const unsigned char *)ctx->K->d_pk8, out);
+  return launched(ctx);
+}
+}  // namespace
+
+int tfhe_hip_load_packing_key(tfhe_hip_ctx *ctx, const uint8_t mask_seed[32], const uint32_t *bodies) {
+  if (!ctx) return TFHE_HIP_EINVAL;
+  ENTER(ctx);
+  if (!mask_seed || !bodies) return fail(ctx, TFHE_HIP_EINVAL, "null key pointer");
+  const tfhe_hip_params &P = ctx->P;
+  if (P.basebit > kPkMaxBasebit) return fail(ctx, TFHE_HIP_EINVAL, "packing needs basebit <= 7 (digits in one byte)");
+  // packing calls queued on the caller's streams may still read the planes this call overwrites
+  HIPCHK(ctx, hipDeviceSynchronize());
+  const size_t rows = (size_t)P.n * P.t, body_words = rows * kN;
+  const size_t chunks = pk_plane_bytes(P.n, P.t) / 16;
+  ctx->K->pk_loaded = false;
+  if (!ctx->K->d_pk8) HIPCHK(ctx, hipMalloc((void **)&ctx->K->d_pk8, pk_plane_bytes(P.n, P.t)));
+  uint32_t *d_tmp = nullptr;  // bodies [n t][N], then the rows [n t][2][N]
+  HIPCHK(ctx, hipMalloc((void **)&d_tmp, (body_words + rows * 2 * kN) * 4));
+  hipError_t e = hipMemcpyAsync(d_tmp, bodies, body_words * 4, hipMemcpyHostToDevice, ctx->stream);
+  if (e == hipSuccess) {
+    hipLaunchKernelGGL(k_pack_expand_key<64>, dim3((unsigned)rows), dim3(64), 0, ctx->stream, d_tmp, d_tmp + body_words,
+                       seed_key(mask_seed));
+    e = hipGetLastError();
+  }
+  if (e == hipSuccess) {
+    hipLaunchKernelGGL(k_pack_planes<256>, dim3((unsigned)((chunks + 255) / 256)), dim3(256), 0, ctx->stream,
+                       d_tmp + body_words, ctx->K->d_pk8, P.n, P.t, chunks);
+    e = hipGetLastError();
+  }
+  const hipError_t es = hipStreamSynchronize(ctx->stream);
+  if (e == hipSuccess) e = es;
+  (void)hipFree(d_tmp);
+  if (e != hipSuccess) return fail(ctx, TFHE_HIP_EHIP, std::string("packing key upload: ") + hipGetErrorString(e));
+  ctx->K->pk_loaded = true;
+  return TFHE_HIP_OK;
+}
+
+int tfhe_hip_packing_key_is_loaded(tfhe_hip_ctx *ctx) {  // 0 / 1, never an error code (no device call is made)
+  if (!ctx) return 0;
+  return __atomic_load_n(&ctx->own.pk_loaded, __ATOMIC_ACQUIRE) ? 1 : 0;  // (no lock: see tfhe_hip_key_is_loaded)
+}
+
+int tfhe_hip_batch_pack_tlwe(tfhe_hip_ctx *ctx, const uint32_t *in, size_t count, uint32_t *out) {
+  if (!ctx) return TFHE_HIP_EINVAL;
+  ENTER(ctx);
+  CHK(need_packing_key(ctx));
+  if (count == 0) return TFHE_HIP_OK;
+  if (!in || !out) return fail(ctx, TFHE_HIP_EINVAL, "null pointer");
+  const size_t groups = (count + kN - 1) / kN;
+  return host_call(ctx, false, {{in, count * (size_t)(ctx->P.n + 1) * 4, &ctx->a}}, out, groups * 2 * kN * 4,
+                   [&](const void *const *d, void *o) { return pack_launch(ctx, u32(d[0]), count, (uint32_t *)o, ctx->stream); });
+}
+
+int tfhe_hip_batch_pack_tlwe_dev(tfhe_hip_ctx *ctx, const uint32_t *in, size_t count, uint32_t *out, void *stream) {
+  if (!ctx) return TFHE_HIP_EINVAL;
+  ENTER(ctx);
+  CHK(need_packing_key(ctx));
+  if (count && (!in || !out)) return fail(ctx, TFHE_HIP_EINVAL, "null pointer");
+  if (count == 0) return TFHE_HIP_OK;
+  return pack_launch(ctx, in, count, out, pick(ctx, stream));
+}

@@ -313,10 +313,11 @@ inline int pool_world_for(const tfhe_hip_pool *p, size_t count) {
 }
 
 // run(ctx, lo, hi) on every non-empty shard, shard 0 on the calling thread; first failure wins.  A shard's error text
-// is read on the thread that ran it (the text is per thread, err_slot).
+// is read on the thread that ran it (the text is per thread, err_slot).  world_req > 0: that many members (at most the
+// pool's) instead of pool_world_for's count, for calls whose items are not single ciphertexts.
 template <class F>
-int pool_map(tfhe_hip_pool *p, size_t count, F &&run) {
-  const int world = pool_world_for(p, count);
+int pool_map(tfhe_hip_pool *p, size_t count, F &&run, int world_req = 0) {
+  const int world = world_req > 0 ? std::min(world_req, (int)p->ctxs.size()) : pool_world_for(p, count);
   std::vector<int> rc((size_t)world, TFHE_HIP_OK);
   std::vector<std::string> text((size_t)world);
   auto shard = [&](int r, size_t lo, size_t hi) {
@@ -365,10 +366,11 @@ struct PoolIn {
   bool sharded = true;        // false: every member needs all of it (a shared test vector)
 };
 
-// op(ctx, ins[5], out, m, stream): enqueue the batched operation for m ciphertexts on member `ctx`
+// op(ctx, ins[5], out, m, stream): enqueue the batched operation for m ciphertexts on member `ctx` (world_req: as for
+// pool_map)
 template <class Op>
 int pool_dev_map(tfhe_hip_pool *p, int home, size_t count, void *stream_v, const PoolIn (&ins)[5], void *out,
-                 size_t out_row_bytes, Op &&op) {
+                 size_t out_row_bytes, Op &&op, int world_req = 0) {
   tfhe_hip_pool *root = p->root();
   const int size = (int)p->ctxs.size();
   if (home < 0 || home >= size) return pool_fail(p, TFHE_HIP_EINVAL, "no such pool member (home)");
@@ -381,7 +383,7 @@ int pool_dev_map(tfhe_hip_pool *p, int home, size_t count, void *stream_v, const
   // stream is named by hipStreamLegacy); the event, wait and RCCL calls below take the runtime's own name for the
   // default stream, NULL (hipStreamWaitEvent on the hipStreamLegacy handle faults in this HIP runtime)
   hipStream_t hrt = hs == hipStreamLegacy ? (hipStream_t) nullptr : hs;
-  const int world = pool_world_for(p, count);
+  const int world = world_req > 0 ? std::min(world_req, size) : pool_world_for(p, count);
   std::vector<ncclComm_t> *comms = world > 1 || pool_rccl_mode() >= 2 ? pool_comms(p) : nullptr;
   // TFHE_HIP_POOL_RCCL=2 on a pool of ONE member (plumbing test on a one-GPU box): home's own shard takes the remote
   // path through a self send / receive, so the same symbols, group structure and stream handling run as among peers
@@ -1254,5 +1256,56 @@ int tfhe_hip_pool_get_transfer_times(tfhe_hip_pool *p, tfhe_hip_pool_transfer_ti
   root->scatter_bytes = root->gather_bytes = root->dev_calls = 0;
   return TFHE_HIP_OK;
 }
+// ---- packing key switch (packing.hpp): whole groups of N per member, in input order ----------------------------------------------------------
+int tfhe_hip_pool_load_packing_key(tfhe_hip_pool *p, const uint8_t mask_seed[32], const uint32_t *bodies) {
+  POOL_ENTER(p);
+  for (auto *c : p->ctxs) {  // every member expands the bodies itself (no cloud key, nothing to replicate)
+    const int rc = tfhe_hip_load_packing_key(c, mask_seed, bodies);
+    if (rc != TFHE_HIP_OK) return pool_fail(p, rc, "device " + std::to_string(c->device) + ": " + tfhe_hip_last_error(c));
+  }
+  return TFHE_HIP_OK;
+}
+
+int tfhe_hip_pool_batch_pack_tlwe(tfhe_hip_pool *p, const uint32_t *in, size_t count, uint32_t *out) {
+  POOL_ENTER(p);
+  if (count == 0) {  // a member's checks (ENOKEY first), nothing to run
+    POOL_FIRST(p, tfhe_hip_batch_pack_tlwe(p->ctxs[0], in, 0, out));
+    return TFHE_HIP_OK;
+  }
+  if (!in || !out) return pool_fail(p, TFHE_HIP_EINVAL, "null pointer");
+  const size_t w = (size_t)p->ctxs[0]->P.n + 1, groups = (count + kN - 1) / kN;
+  const int world = (int)(groups < p->ctxs.size() ? groups : p->ctxs.size());
+  return pool_map(p, groups, [&](tfhe_hip_ctx *c, size_t lo, size_t hi) {
+    const size_t m_hi = hi * kN < count ? hi * kN : count;
+    return tfhe_hip_batch_pack_tlwe(c, in + lo * kN * w, m_hi - lo * kN, out + lo * (size_t)2 * kN);
+  }, world);
+}
+
+int tfhe_hip_pool_batch_pack_tlwe_dev(tfhe_hip_pool *p, int home, const uint32_t *in, size_t count, uint32_t *out,
+                                      void *stream) {
+  POOL_ENTER(p);
+  if (home < 0 || home >= (int)p->ctxs.size()) return pool_fail(p, TFHE_HIP_EINVAL, "no such pool member (home)");
+  if (count == 0) {
+    POOL_FIRST(p, tfhe_hip_batch_pack_tlwe_dev(p->ctxs[(size_t)home], in, 0, out, stream));
+    p->root()->last_transport = "none";
+    return TFHE_HIP_OK;
+  }
+  if (!in || !out) return pool_fail(p, TFHE_HIP_EINVAL, "null pointer");
+  // the whole groups go through the grouped scatter / gather; a last partial group (shorter than a group's rows, so it
+  // cannot travel as one) is packed on home, on the same stream, after home's own shard
+  const size_t w = (size_t)p->ctxs[0]->P.n + 1, full = count / kN, tail = count - full * kN;
+  const PoolIn ins[5] = {{in, kN * w * 4, true}, {}, {}, {}, {}};
+  const int world = (int)(full < p->ctxs.size() ? full : p->ctxs.size());
+  CHK(pool_dev_map(p, home, full, stream, ins, out, (size_t)2 * kN * 4, [&](tfhe_hip_ctx *c, const void *const *q, void *o, size_t m, void *s) {
+    return tfhe_hip_batch_pack_tlwe_dev(c, (const uint32_t *)q[0], m * kN, (uint32_t *)o, s);
+  }, world));
+  if (tail) {
+    tfhe_hip_ctx *c = p->ctxs[(size_t)home];
+    const int rc = tfhe_hip_batch_pack_tlwe_dev(c, in + full * kN * w, tail, out + full * (size_t)2 * kN, stream);
+    if (rc != TFHE_HIP_OK) return pool_fail(p, rc, "device " + std::to_string(c->device) + ": " + tfhe_hip_last_error(c));
+  }
+  return TFHE_HIP_OK;
+}
+
 #undef POOL_ENTER
 #undef POOL_FIRST

@@ -142,6 +142,8 @@ struct KeyState {
   uint32_t *d_ksk = nullptr;
   unsigned char *d_ksk8 = nullptr;  // base-4 sets: the key as signed byte planes in MFMA fragment order (k_ksk_planes)
   uint32_t *d_testvec = nullptr;
+  unsigned char *d_pk8 = nullptr;  // the packing key as byte planes (packing.hpp): beside, not part of, the cloud key
+  bool pk_loaded = false;          // (a cloud-key load or change leaves it; freeing the key view frees it)
   uint32_t offset = 0;
   bool key_loaded = false;
   bool reenc_loaded = false;  // d_ksk (+ d_ksk8) hold a proxy re-encryption key (proxy_reenc.rs:224-233) instead of a cloud key's
@@ -1406,6 +1408,7 @@ void free_key(KeyState &k) {
   if (k.d_bsk) (void)hipFree(k.d_bsk);
   if (k.d_ksk) (void)hipFree(k.d_ksk);
   if (k.d_ksk8) (void)hipFree(k.d_ksk8);
+  if (k.d_pk8) (void)hipFree(k.d_pk8);
   if (k.d_testvec) (void)hipFree(k.d_testvec);
   k = KeyState();
 }
@@ -2393,3 +2396,4 @@ int tfhe_hip_synchronize(tfhe_hip_ctx *ctx) {
 #include "pool.hpp"
 #include "circuit.hpp"
 #include "seeded.hpp"
+#include "packing.hpp"

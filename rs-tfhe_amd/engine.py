@@ -107,11 +107,13 @@ class _Handle:
     """What a context (Engine) and a pool of contexts (Pool) share: the cloud key, the batch calls on host arrays and
     their *_dev forms on torch CUDA tensors, and the lifetime of key views.  A subclass supplies how a C entry point
     is called on its handle (`_call` for `tfhe_hip_<name>` / `tfhe_hip_pool_<name>`; `_call_dev`, whose `home`
-    member only a pool's entry points take), `_chk`, `_destroy`, and `_device(home)`: the GPU of member `home`."""
+    member only a pool's entry points take), `_chk`, `_destroy`, `_device(home)`: the GPU of member `home`, and
+    `_member_ctx(member)`: the context handle of a member."""
 
     # -- lifetime -------------------------------------------------------------
     def _link(self, parent) -> None:
         self._key = None  # the key object currently loaded (held, so its identity cannot be recycled)
+        self._packing_key = None  # the packing key loaded beside it (packing.pack loads one once per view)
         self._parent = parent  # a key view keeps its parent alive for as long as it exists
         self._views = []  # weak references to the live key views of this handle (closed before it)
         if parent is not None:
@@ -288,6 +290,38 @@ class _Handle:
         out = np.empty_like(a)
         self._call("batch_mux", int(bool(naive)), _ptr(a), _ptr(b), _ptr(c), _ptr(out), len(a))
         return out
+
+    # -- packing key switch (include/tfhe_hip.h): up to N lv0 results in one TRLWE lv1 under s1 ----------------------
+    def load_packing_key(self, packing_key) -> None:
+        """packing.PackingKey (mask seed + bodies [n][t][N]) -> this handle, beside its cloud key (every member of a
+        pool expands it); packing needs no cloud key, and a cloud-key load leaves the packing key in place."""
+        p = self.params
+        if packing_key.params != p:
+            raise ValueError(f"packing key of {packing_key.params.name} on a {p.name} handle")
+        bodies = _u32(packing_key.bodies).reshape(-1)
+        if bodies.size != p.n * p.iks_t * N:
+            raise ValueError("packing key bodies have the wrong size for these parameters")
+        seed = (C.c_uint8 * 32).from_buffer_copy(_seed_bytes(packing_key.mask_seed))
+        self._call("load_packing_key", C.addressof(seed), _ptr(bodies))
+        self._packing_key = packing_key
+
+    def packing_key_is_loaded(self) -> bool:
+        return self._lib.tfhe_hip_packing_key_is_loaded(self._member_ctx(0)) == 1  # 0 / 1; anything else is not "loaded"
+
+    def pack(self, cts) -> np.ndarray:
+        """[count][n+1] lv0 ciphertexts -> [ceil(count / N)][2][N] TRLWE lv1 (`tfhe_hip_batch_pack_tlwe`)."""
+        cts = self._cts(cts)
+        out = np.empty((-(-len(cts) // N), 2, N), np.uint32)
+        self._call("batch_pack_tlwe", _ptr(cts), len(cts), _ptr(out))
+        return out
+
+    def pack_dev(self, cts, out, stream=None, home=None) -> None:
+        """Device form: cts [count][n+1] and out [ceil(count / N)][2][N] 32-bit CUDA tensors on the call's GPU."""
+        h = self._home(home)
+        count = self._dev_batch(h, cts)
+        if out is None or out.numel() != -(-count // N) * 2 * N:
+            raise ValueError("out must be [ceil(count / N)][2][N]")
+        self._call_dev("batch_pack_tlwe_dev", h, self._tp(h, cts), count, self._tp(h, out), self._stream_ptr(h, stream))
 
     # -- device-resident path (torch CUDA tensors; enqueue only) ------------------
     # The tensors of a call live on one GPU: an Engine's, or that of pool member `home` (default: pool.home).  A pool
@@ -480,6 +514,9 @@ class Engine(_Handle):
         if home is not None:
             raise ValueError("an Engine has no pool members: home must be None")
         return self.device
+
+    def _member_ctx(self, member: int):
+        return self._ctx
 
     @property
     def name(self) -> str:
@@ -739,6 +776,9 @@ class Pool(_Handle):
         if not 0 <= home < len(self.devices):
             raise ValueError("no such pool member")
         return self.devices[home]
+
+    def _member_ctx(self, member: int):
+        return C.c_void_p(self._lib.tfhe_hip_pool_ctx(self._h, int(member)))
 
     @property
     def device(self) -> int:

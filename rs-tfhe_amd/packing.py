@@ -1,0 +1,174 @@
+"""Packing key switch on the host: numpy only, no device.
+
+The format and the result are normative in include/tfhe_hip.h ("packing key switch"): up to N = 1024 TLWE lv0 results
+become ONE TRLWE lv1 under s1, each coefficient carrying the phase of one input, so results return 350x smaller on
+SECURITY_128_BIT.  This module is the client's side -- the packing key (`make_packing_key`: masks from the seeded
+section's ChaCha20 keystream, bodies by exact negacyclic products with the binary s1) -- and the integer model of the
+server's result (`pack_model`), which the GPU (csrc/packing.hpp, `Engine.pack`) equals word for word.  `pack` runs it
+on the key view of a cloud key.
+"""
+from __future__ import annotations
+
+import numpy as np
+
+from .params import N, SecurityParams
+from .seeded import f64_to_torus, keystream, negacyclic_binary
+
+DOMAIN_PACK = 0x504B53
+PACK_STREAM = 24
+
+
+def gadget(p: SecurityParams) -> np.ndarray:
+    """g_l = 2^(32 - (l+1) basebit), l < t, as u32."""
+    return np.array([1 << (32 - (l + 1) * p.basebit) for l in range(p.iks_t)], np.uint32)
+
+
+def digits(p: SecurityParams, words) -> np.ndarray:
+    """The signed digits d_l of the definition, [..., t] int8: the identity key switch's rounding a_bar, then the
+    base-B decomposition from the least significant digit up with a carry into the next (the last carry dropped)."""
+    bt, base = p.basebit * p.iks_t, p.base
+    a = np.asarray(words, np.uint32).astype(np.uint64)
+    abar = ((a + np.uint64(1 << (31 - bt))) & np.uint64(0xFFFFFFFF)) >> np.uint64(32 - bt)
+    out = np.empty(a.shape + (p.iks_t,), np.int8)
+    carry = np.zeros(a.shape, np.int64)
+    for l in range(p.iks_t - 1, -1, -1):
+        v = ((abar >> np.uint64(p.basebit * (p.iks_t - 1 - l))) & np.uint64(base - 1)).astype(np.int64) + carry
+        neg = v >= base // 2
+        out[..., l] = np.where(neg, v - base, v)
+        carry = neg.astype(np.int64)
+    return out
+
+
+def key_masks(seed: bytes, rows) -> np.ndarray:
+    """Mask polynomials a_r of the packing key rows `rows` (r = i t + l): [len(rows), N] u32."""
+    return keystream(seed, N, np.asarray(rows, np.uint64), PACK_STREAM, DOMAIN_PACK)
+
+
+def key_rows(p: SecurityParams, mask_seed: bytes, bodies) -> np.ndarray:
+    """The packing key as [n t][2N] u32 rows: a_r then b_r."""
+    rows = p.n * p.iks_t
+    out = np.empty((rows, 2 * N), np.uint32)
+    for lo in range(0, rows, 1024):
+        hi = min(lo + 1024, rows)
+        out[lo:hi, :N] = key_masks(mask_seed, np.arange(lo, hi))
+    out[:, N:] = np.asarray(bodies, np.uint32).reshape(rows, N)
+    return out
+
+
+class PackingKey:
+    """The packing key of include/tfhe_hip.h: the public 32-byte mask seed and the bodies [n][t][N] u32."""
+
+    FORMAT_VERSION = 1
+
+    def __init__(self, params: SecurityParams, mask_seed, bodies):
+        self.params = params
+        self.mask_seed = bytes(mask_seed)
+        if len(self.mask_seed) != 32:
+            raise ValueError("mask_seed is 32 bytes")
+        self.bodies = np.ascontiguousarray(bodies, dtype=np.uint32)
+        if self.bodies.size != params.n * params.iks_t * N:
+            raise ValueError("bodies has the wrong size for these parameters")
+        self.bodies = self.bodies.reshape(params.n, params.iks_t, N)
+
+    @property
+    def nbytes(self) -> int:
+        """Bytes that travel: the bodies and the seed."""
+        return self.bodies.nbytes + len(self.mask_seed)
+
+    def save(self, path) -> None:
+        """One .npz file: the parameter set's name, the format version and the fields."""
+        with open(path, "wb") as f:
+            np.savez(f, format_version=np.uint32(self.FORMAT_VERSION), params=np.array(self.params.name),
+                     mask_seed=np.frombuffer(self.mask_seed, np.uint8), bodies=self.bodies)
+
+    @classmethod
+    def load(cls, path, params: SecurityParams = None) -> "PackingKey":
+        """Inverse of save; refuses another format version, and another parameter set than `params` when given."""
+        from .params import PARAM_SETS
+
+        with np.load(path, allow_pickle=False) as z:
+            version = int(z["format_version"])
+            if version != cls.FORMAT_VERSION:
+                raise ValueError(f"packing key format {version}, this library reads {cls.FORMAT_VERSION}")
+            name = str(z["params"])
+            if name not in PARAM_SETS:
+                raise ValueError(f"unknown parameter set {name!r}")
+            if params is not None and params.name != name:
+                raise ValueError(f"the file holds a {name} key, not {params.name}")
+            return cls(PARAM_SETS[name], z["mask_seed"].tobytes(), z["bodies"])
+
+
+def make_packing_key(params: SecurityParams, key_lv0, key_lv1, rng=None, alpha=None, chunk: int = 512) -> PackingKey:
+    """The packing key of (key_lv0, key_lv1): b_r = a_r (*) s1 + e_r + s0[i] g_l X^0.  rng: None (the OS CSPRNG), an
+    int seed or a numpy Generator (reproducible: tests only); it draws the mask seed and the noise.  alpha: the noise's
+    standard deviation, alpha_lv1 of the set by default."""
+    from .client import OsRng, _rng
+
+    p = params
+    if p.basebit > 7:
+        raise ValueError("packing needs basebit <= 7")
+    alpha = p.alpha_lv1 if alpha is None else float(alpha)
+    if alpha < 0:
+        raise ValueError("alpha is non-negative")
+    g = _rng(rng)
+    if isinstance(g, OsRng):
+        import os
+
+        seed = os.urandom(32)
+    else:
+        seed = g.integers(0, 1 << 32, 8, dtype=np.uint64).astype("<u4").tobytes()
+    s0 = np.asarray(key_lv0, np.uint32).reshape(p.n)
+    s1 = np.asarray(key_lv1, np.uint32).reshape(N)
+    gl = gadget(p)
+    rows = p.n * p.iks_t
+    bodies = np.empty((rows, N), np.uint32)
+    with np.errstate(over="ignore"):
+        for lo in range(0, rows, chunk):
+            r = np.arange(lo, min(lo + chunk, rows))
+            b = negacyclic_binary(key_masks(seed, r), s1)
+            if alpha > 0:
+                b += f64_to_torus(g.normal(0.0, alpha, len(r) * N)).reshape(len(r), N)
+            b[:, 0] += s0[r // p.iks_t] * gl[r % p.iks_t]
+            bodies[lo:lo + len(r)] = b
+    return PackingKey(p, seed, bodies)
+
+
+def pack_model(params: SecurityParams, mask_seed: bytes, bodies, cts, rows=None) -> np.ndarray:
+    """The definition's result for [count][n+1] ciphertexts: [ceil(count / N)][2][N] u32.  The contraction
+    P[j] = sum_{i,l} d_l(a_j[i]) K[(i,l)] is a float64 matmul over the 16-bit halves of the key words (|sums| < 2^35:
+    exact), the rotate-and-sum a bincount of u32 values (< 2^42: exact).  rows: key_rows(...) when already made."""
+    p = params
+    cts = np.ascontiguousarray(cts, dtype=np.uint32).reshape(-1, p.n + 1)
+    K = key_rows(p, mask_seed, bodies) if rows is None else rows
+    k_lo, k_hi = (K & 0xFFFF).astype(np.float64), (K >> 16).astype(np.float64)
+    groups = -(-len(cts) // N)
+    out = np.zeros((groups, 2, N), np.uint32)
+    xs = np.arange(N)
+    for g in range(groups):
+        c = cts[g * N:(g + 1) * N]
+        m = len(c)
+        d = digits(p, c[:, :p.n]).reshape(m, -1).astype(np.float64)  # column i t + l
+        lo = (d @ k_lo).astype(np.int64)
+        hi = (d @ k_hi).astype(np.int64)
+        prod = ((lo + (hi << 16)) & 0xFFFFFFFF).astype(np.uint32)  # [m][2N]
+        y = xs[None, :] + np.arange(m)[:, None]  # X^j X^x = X^y, y < 2N - 1
+        wrap = y >= N
+        for h in range(2):
+            v = prod[:, h * N:(h + 1) * N]
+            v = np.where(wrap, np.uint32(0) - v, v)
+            s = np.bincount((y % N).ravel(), weights=v.ravel().astype(np.float64), minlength=N)
+            out[g, h] = np.uint32(0) - (s.astype(np.int64) & 0xFFFFFFFF).astype(np.uint32)
+        out[g, 1, :m] += c[:, p.n]
+    return out
+
+
+def pack(cts, cloud_key, packing_key: PackingKey, device: int = 0) -> np.ndarray:
+    """The server side: [count][n+1] results -> [ceil(count / N)][2][N] packed TRLWEs on the GPU, on the key view of
+    `cloud_key` (bootstrap.keyed_engine), where `packing_key` is loaded once."""
+    from .bootstrap import keyed_engine
+
+    with keyed_engine(cloud_key, device) as view:
+        with view.lock:  # held through the pack: another thread's packing key cannot replace this one in between
+            if view._packing_key is not packing_key or not view.packing_key_is_loaded():
+                view.load_packing_key(packing_key)
+            return view.pack(cts)

@@ -86,6 +86,11 @@ pub const NAND: c_int = 0; pub const OR: c_int = 1; pub const AND: c_int = 2; pu
 pub const XNOR: c_int = 4; pub const NOR: c_int = 5; pub const ANDNY: c_int = 6; pub const ANDYN: c_int = 7;
 pub const ORNY: c_int = 8; pub const ORYN: c_int = 9; pub const COPY: c_int = 10;
 
+extern "C" {   // packing key switch (include/tfhe_hip.h): up to N lv0 results in one TRLWE lv1 under the client's s1
+    fn tfhe_hip_pool_load_packing_key(pool: *mut TfheHipPool, mask_seed: *const u8, bodies: *const u32) -> c_int;
+    fn tfhe_hip_pool_batch_pack_tlwe(pool: *mut TfheHipPool, input: *const u32, count: usize, out: *mut u32) -> c_int;
+}
+
 const W: usize = params::tlwe_lv0::N + 1;     // words per TLWELv0
 const N: usize = params::trgsw_lv1::N;        // 1024
 const MAX_RESIDENT_KEYS: usize = 4;           // key views kept per pool (172 MB + 104 MB of byte planes each)
@@ -113,8 +118,11 @@ thread_local! {   // one arena per calling thread: a, b, c operands and the resu
 /// A resident key: (address, content sample) of the CloudKey it holds + its key view of the pool.
 struct KeyView { addr: usize, fp: u64, view: *mut TfheHipPool, last_use: u64, users: usize }
 
+/// The resident packing key: (content sample of the key it holds, its key view of the pool; null until first use).
+struct PackingView { fp: u64, view: *mut TfheHipPool }
+
 /// Owns the C pool (one context per device) and the key views on it.
-pub struct HipEngine { pool: *mut TfheHipPool, views: Mutex<(Vec<KeyView>, u64)> }
+pub struct HipEngine { pool: *mut TfheHipPool, views: Mutex<(Vec<KeyView>, u64)>, packing: Mutex<PackingView> }
 unsafe impl Send for HipEngine {}   // the library merges concurrent small calls into shared launches and serialises the rest per context; `views` is behind its Mutex
 unsafe impl Sync for HipEngine {}
 
@@ -131,7 +139,8 @@ impl HipEngine {
         let mut pool = std::ptr::null_mut();
         let rc = unsafe { tfhe_hip_pool_create(&p, devices.as_ptr(), devices.len() as c_int, &mut pool) };
         assert_eq!(rc, 0, "tfhe_hip_pool_create failed");   // the reference has no Result on this path
-        HipEngine { pool, views: Mutex::new((Vec::new(), 0)) }
+        HipEngine { pool, views: Mutex::new((Vec::new(), 0)),
+                    packing: Mutex::new(PackingView { fp: 0, view: std::ptr::null_mut() }) }
     }
 
     fn check(h: *mut TfheHipPool, rc: c_int) {
@@ -357,6 +366,45 @@ impl HipEngine {
         assert_eq!(rc, 0, "tfhe_hip: {}", msg);
         (bsk, ksk, off, tv)
     }
+
+    /// Packing key switch, the format of include/tfhe_hip.h: `cts` ([count][n+1] lv0 results, flat) become
+    /// ceil(count / N) TRLWE lv1 [G][2][N] under the client's s1, each coefficient the phase of one input -- 350x fewer
+    /// bytes to return on SECURITY_128_BIT.  The packing key (the public 32-byte mask seed and the bodies [n][t][N], made
+    /// by the client) stays resident in a key view of the pool of its own and is loaded again only when another key
+    /// (content sample) is passed, as the C++ mirror's `Engine::pack`; no cloud key is needed.
+    pub fn pack_tlwe(&self, mask_seed: &[u8; 32], bodies: &[u32], cts: &[u32]) -> Vec<u32> {
+        let n = params::tlwe_lv0::N;
+        assert_eq!(bodies.len(), n * params::trgsw_lv1::IKS_T * N, "bodies is [n][t][N]");
+        assert_eq!(cts.len() % W, 0, "cts is [count][n+1]");
+        let count = cts.len() / W;
+        let mut out = vec![0u32; (count + N - 1) / N * 2 * N];
+        let fp = Self::packing_fingerprint(mask_seed, bodies);
+        let mut g = self.packing.lock().unwrap();   // held through the pack: a concurrent call cannot swap the key
+        if g.view.is_null() {
+            let mut view = std::ptr::null_mut();
+            assert_eq!(unsafe { tfhe_hip_pool_key_create(self.pool, &mut view) }, 0, "tfhe_hip_pool_key_create failed");
+            g.view = view;
+            g.fp = fp ^ 1;   // (nothing loaded yet)
+        }
+        if g.fp != fp {
+            g.fp = fp ^ 1;   // a failed load leaves no key claimed
+            Self::check(g.view, unsafe { tfhe_hip_pool_load_packing_key(g.view, mask_seed.as_ptr(), bodies.as_ptr()) });
+            g.fp = fp;
+        }
+        Self::check(g.view, unsafe { tfhe_hip_pool_batch_pack_tlwe(g.view, cts.as_ptr(), count, out.as_mut_ptr()) });
+        out
+    }
+
+    /// the seed, 64 evenly spaced body words and the size (FNV-style mix), as the C++ mirror samples a packing key
+    fn packing_fingerprint(mask_seed: &[u8; 32], bodies: &[u32]) -> u64 {
+        let mut h: u64 = 0x1656_67B1_9E37_79F9;
+        let mut mix = |v: u64| { h = (h ^ v).wrapping_mul(0x0000_0100_0000_01B3); };
+        for i in 0..32 { mix(mask_seed[i] as u64); }
+        let nb = bodies.len();
+        for i in 0..64 { mix(bodies[(nb - 1) * i / 64] as u64); }
+        mix(nb as u64);
+        h
+    }
 }
 /// The process-wide engine behind `default_bootstrap()` and the `gates::batch_*` functions when the crate is built with
 /// `--features hip`: created on first use over every GPU of the node -- the stand-in for `default_railgun()`'s "one
@@ -377,6 +425,8 @@ pub fn default_engine() -> std::sync::Arc<HipEngine> {
 impl Drop for HipEngine {
     fn drop(&mut self) {
         for v in self.views.lock().unwrap().0.drain(..) { unsafe { tfhe_hip_pool_destroy(v.view) } }   // views before their pool
+        let pv = self.packing.lock().unwrap().view;
+        if !pv.is_null() { unsafe { tfhe_hip_pool_destroy(pv) } }
         unsafe { tfhe_hip_pool_destroy(self.pool) }
     }
 }
