@@ -1,6 +1,7 @@
 """The native circuit scheduler on the GPU (tfhe_hip_circuit_*): every wire word for word against the CPU oracle
 evaluating the same nodes one by one (Circuit.run_reference), against the torch-scheduled path it replaces, through a
-pool, and through the C++ binding."""
+pool, and through the C++ binding.  These are hand-built circuits; seeded random DAGs, every scheduler path by name and
+every dispatch regime word for word against the oracle are in tests/test_gpu_circuit_fuzz.py."""
 import os
 import subprocess
 
