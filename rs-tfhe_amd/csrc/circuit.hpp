@@ -517,19 +517,18 @@ int circ_run_locked(tfhe_hip_ctx *ctx, tfhe_hip_circuit *c, const CircPlan *p, u
       if (l.kind == CL_LINCOMB) {
         CHK(circ_lincomb_launch(ctx, s, wires, d.off, d.coef, d.src, d.cst, B, out, l.nodes));
       } else if (l.kind == CL_NKS) {
-        CHK(launch_blind_rotate(ctx, s, wires, wires, GatePrep{1u, 1u, 0u}, nullptr, 0, count, nullptr, nullptr, out, d.code,
-                                d.ia, d.ib));
+        CHK(run_bootstrap(ctx, s, {.in_a = wires, .in_b = wires, .gp = kCodesPrep, .count = count, .gate_codes = d.code, .idx_a = d.ia, .idx_b = d.ib},
+                          out, false));
       } else {
-        // gates: per-ciphertext codes (cb != 0 keeps in_b attached); lut groups: one (ca, cb, cconst) for the launch
-        // (many-LUT groups: k extractions per blind rotation, [k][count] rows through one key switch)
+        // gates: per-ciphertext codes; lut groups: one (ca, cb, cconst) for the launch (many-LUT groups: k extractions
+        // per blind rotation, [k][count] rows through one key switch)
         const bool gate = l.kind == CL_GATE;
-        const GatePrep gp = gate ? GatePrep{1u, 1u, 0u} : GatePrep{l.ca, l.cb, l.cc};
-        const int shift = l.n_luts ? lut_shift_of((int)l.n_luts) : 0;
-        CHK(claim_scratch(ctx, s));
-        CHK(ensure(ctx, ctx->lv1, lv1_rows(count << shift) * (size_t)(kN + 1) * 4));
-        CHK(launch_blind_rotate(ctx, s, wires, gp.cb ? wires : nullptr, gp, d.tv, 0, count, nullptr, (uint32_t *)ctx->lv1.p,
-                                nullptr, gate ? d.code : nullptr, d.ia, gp.cb ? d.ib : nullptr, shift));
-        CHK(launch_key_switch(ctx, s, (const uint32_t *)ctx->lv1.p, out, count << shift));
+        const GatePrep gp = gate ? kCodesPrep : GatePrep{l.ca, l.cb, l.cc};
+        CHK(run_bootstrap(ctx, s,
+                          {.in_a = wires, .in_b = gp.cb ? wires : nullptr, .gp = gp, .testvec = d.tv, .count = count,
+                           .gate_codes = gate ? d.code : nullptr, .idx_a = d.ia, .idx_b = gp.cb ? d.ib : nullptr,
+                           .lut_shift = l.n_luts ? lut_shift_of((int)l.n_luts) : 0},
+                          out, true));
       }
     }
   return TFHE_HIP_OK;

@@ -181,19 +181,14 @@ int comb_run_group(tfhe_hip_ctx *x, KeyState *key, const std::vector<CombReq *> 
   if (mux) {
     CHK(mux_dev(x, r0.cls == CB_MUX_NAIVE, da, db, (const uint32_t *)x->c.dev.p, dout, m, s));
   } else {
-    GatePrep gp{1u, need_b ? 1u : 0u, 0u};  // mixed: placeholders, the kernel reads the codes (cb != 0 keeps in_b attached)
-    if (uniform) gate_prep(gate0, gp);
-    const uint8_t *dcodes = uniform ? nullptr : (const uint8_t *)x->idx.dev.p;
-    const uint32_t *dtv = dtv0;
+    BrCall call{.in_a = da, .in_b = db, .gp = need_b ? kCodesPrep : kCopyPrep, .testvec = dtv0, .per_ct = 1, .count = m};
+    if (uniform) gate_prep(gate0, call.gp);
+    else call.gate_codes = (const uint8_t *)x->idx.dev.p;
     if (rotate) {
-      CHK(launch_blind_rotate(x, s, da, nullptr, gp, dtv, 1, m, dout, nullptr, nullptr, nullptr));
-    } else if (r0.keyswitch) {
-      CHK(claim_scratch(x, s));
-      CHK(ensure(x, x->lv1, lv1_rows(m) * (size_t)(kN + 1) * 4));
-      CHK(launch_blind_rotate(x, s, da, db, gp, dtv, 1, m, nullptr, (uint32_t *)x->lv1.p, nullptr, dcodes));
-      CHK(launch_key_switch(x, s, (const uint32_t *)x->lv1.p, dout, m));
+      call.out_trlwe = dout;
+      CHK(launch_blind_rotate(x, s, call));
     } else {
-      CHK(launch_blind_rotate(x, s, da, db, gp, dtv, 1, m, nullptr, nullptr, dout, dcodes));
+      CHK(run_bootstrap(x, s, call, dout, r0.keyswitch != 0));
     }
   }
   HIPCHK(x, hipMemcpyAsync(x->out.pin.p, x->out.dev.p, m * owb, hipMemcpyDeviceToHost, s));
@@ -238,30 +233,17 @@ int comb_make_lane(tfhe_hip_ctx *base, Combiner &C, int li, std::string &why) {
       (void)hipGetLastError();
     }
   }
-  x->br_force = base->br_force;
-  x->ks_force = base->ks_force;
-  x->wide_max = base->wide_max;
-  x->pair_lo = base->pair_lo;
-  x->pair_max = base->pair_max;
-  x->ks_split_max = base->ks_split_max;
-  x->ks_mfma_min = base->ks_mfma_min;
-  x->ks_sl_chunk_min = base->ks_sl_chunk_min;
-  x->ks_sliced_sets = base->ks_sliced_sets;
-  x->ks_mfma_ksplit = base->ks_mfma_ksplit;
-  x->ks_sl_kchunks = base->ks_sl_kchunks;
-  x->br_chunk = base->br_chunk;
-  x->exp_wide1 = base->exp_wide1;
-  x->fast_round = base->fast_round;
+  x->dispatch = base->dispatch;
   x->profiling = C.profiling.load(std::memory_order_relaxed);
   // arenas for a full round of the default bound up front (a, b, out: < 1 MB each): the first calls of a team do not
   // pay for pinned allocations, and a growing team does not re-allocate them
   {
     const size_t rows = C.max_count.load(std::memory_order_relaxed) ? C.max_count.load(std::memory_order_relaxed) : 1;
-    const size_t bytes = rows * ((size_t)x->P.n + 1) * 4;
+    const size_t bytes = tlwe_bytes(x, rows);
     (void)comb_arena(x, x->a, bytes);
     (void)comb_arena(x, x->b, bytes);
     (void)comb_arena(x, x->out, bytes);
-    (void)ensure(x, x->lv1, lv1_rows(rows) * (size_t)(kN + 1) * 4);
+    (void)ensure(x, x->lv1, lv1_bytes(rows));
   }
   C.lane_ctx[li] = x;
   return TFHE_HIP_OK;

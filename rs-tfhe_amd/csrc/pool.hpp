@@ -75,6 +75,14 @@ int pool_fail(tfhe_hip_pool *p, int code, const std::string &msg) {
   return code;
 }
 
+// What a member's failed call becomes on the pool: "device N: <the member's text>".  A member's text is per thread
+// (err_slot): this is for the thread that made the call.
+std::string pool_member_text(tfhe_hip_ctx *c) { return "device " + std::to_string(c->device) + ": " + tfhe_hip_last_error(c); }
+// `rc` of a call just made on member `c` by this thread, recorded on the pool when it is a failure
+int pool_member_rc(tfhe_hip_pool *p, tfhe_hip_ctx *c, int rc) {
+  return rc == TFHE_HIP_OK ? rc : pool_fail(p, rc, pool_member_text(c));
+}
+
 // dst takes src's key (engine layouts), device to device.  Either may be a key view; both idle on entry.
 int clone_key(tfhe_hip_ctx *dst, tfhe_hip_ctx *src) {
   const KeyState *from = &src->own;  // the key src OWNS (K is only bound during a call)
@@ -298,8 +306,7 @@ int replicate_key(tfhe_hip_pool *p) {
   } stamp{root, t0, had_comm};
   if (replicate_key_rccl(p)) return TFHE_HIP_OK;
   for (size_t i = 1; i < p->ctxs.size(); ++i) {
-    const int rc = clone_key(p->ctxs[i], p->ctxs[0]);
-    if (rc != TFHE_HIP_OK) return pool_fail(p, rc, "device " + std::to_string(p->ctxs[i]->device) + ": " + tfhe_hip_last_error(p->ctxs[i]));
+    CHK(pool_member_rc(p, p->ctxs[i], clone_key(p->ctxs[i], p->ctxs[0])));
   }
   return TFHE_HIP_OK;
 }
@@ -323,7 +330,7 @@ int pool_map(tfhe_hip_pool *p, size_t count, F &&run, int world_req = 0) {
   auto shard = [&](int r, size_t lo, size_t hi) {
     tfhe_hip_ctx *c = p->ctxs[(size_t)r];
     rc[(size_t)r] = run(c, lo, hi);
-    if (rc[(size_t)r] != TFHE_HIP_OK) text[(size_t)r] = tfhe_hip_last_error(c);
+    if (rc[(size_t)r] != TFHE_HIP_OK) text[(size_t)r] = pool_member_text(c);
   };
   std::vector<std::thread> th;
   for (int r = 1; r < world; ++r) {
@@ -343,8 +350,7 @@ int pool_map(tfhe_hip_pool *p, size_t count, F &&run, int world_req = 0) {
   }
   for (auto &t : th) t.join();
   for (int r = 0; r < world; ++r)
-    if (rc[(size_t)r] != TFHE_HIP_OK)
-      return pool_fail(p, rc[(size_t)r], "device " + std::to_string(p->ctxs[(size_t)r]->device) + ": " + text[(size_t)r]);
+    if (rc[(size_t)r] != TFHE_HIP_OK) return pool_fail(p, rc[(size_t)r], text[(size_t)r]);
   return TFHE_HIP_OK;
 }
 
@@ -361,9 +367,10 @@ int pool_map(tfhe_hip_pool *p, size_t count, F &&run, int world_req = 0) {
 // Without a communicator (a repeated device, no librccl, TFHE_HIP_POOL_RCCL=0): hipMemcpyPeerAsync on the peer's
 // stream behind an event of the home stream, and an event per peer ahead of whatever follows on the home stream.
 struct PoolIn {
-  const void *ptr = nullptr;  // on home's GPU; nullptr = operand absent
+  const void *ptr = nullptr;  // on home's GPU (host-pointer forms: the caller's); nullptr = operand absent
   size_t row_bytes = 0;       // per ciphertext when sharded, the whole operand otherwise
   bool sharded = true;        // false: every member needs all of it (a shared test vector)
+  bool required = false;      // absent is "null pointer" (unless the batch is empty)
 };
 
 // op(ctx, ins[5], out, m, stream): enqueue the batched operation for m ciphertexts on member `ctx` (world_req: as for
@@ -566,9 +573,7 @@ int pool_dev_map(tfhe_hip_pool *p, int home, size_t count, void *stream_v, const
         o = (unsigned char *)out + sh.lo * out_row_bytes;
       }
       tfhe_hip_ctx *c = p->ctxs[(size_t)sh.member];
-      const int rc = op(c, ptrs, o, sh.hi - sh.lo, sh.remote ? (void *)member_stream(sh.member) : (void *)hs);
-      if (rc != TFHE_HIP_OK)
-        return pool_fail(p, rc, "device " + std::to_string(c->device) + ": " + tfhe_hip_last_error(c));
+      CHK(pool_member_rc(p, c, op(c, ptrs, o, sh.hi - sh.lo, sh.remote ? (void *)member_stream(sh.member) : (void *)hs)));
     }
   // 4. gather
   if (any_remote) {
@@ -804,53 +809,265 @@ inline tfhe_hip_ctx *pool_least_loaded(tfhe_hip_pool *p) {
   }
   return best;
 }
+// ---- the batch operations, each described ONCE for its host-pointer and its device-resident pool form ----------------
+// An operation is its operand table (PoolIn: pointer, row size, cut with the batch or sent whole, required or not), its
+// result's row size, and `run(ctx, operands, out, m, stream)`: the single-context entry point on a shard of m
+// ciphertexts.  The null-pointer check, a shard's pointers, the small-call shortcut and what pool_dev_map is handed all
+// come from the table (pool_host_call / pool_dev_call).
+struct PoolOp {
+  PoolIn in[5];                  // in the order `run` takes them
+  size_t out_row_bytes;          // of the result, per ciphertext
+  bool small;                    // host form: a call the combining front end takes goes whole to the least loaded member
+  const char *refuse = nullptr;  // device form: turned away with this text before the pointers are looked at
+};
+size_t pool_tlwe_bytes(const tfhe_hip_pool *p) { return tlwe_bytes(p->ctxs[0], 1); }
+
+bool pool_missing(const PoolOp &op, const void *out) {
+  bool missing = !out;
+  for (const PoolIn &in : op.in) missing = missing || (in.required && !in.ptr);
+  return missing;
+}
+// the operands of the shard that starts at ciphertext `lo`
+void pool_shard_ptrs(const PoolOp &op, size_t lo, const void *(&q)[5]) {
+  for (int k = 0; k < 5; ++k) {
+    const PoolIn &in = op.in[k];
+    q[k] = in.ptr ? (const unsigned char *)in.ptr + (in.sharded ? lo * in.row_bytes : 0) : nullptr;
+  }
+}
+
+// host pointers: one host thread per shard (pool_map), results written in place into the caller's slice
+template <class Run>
+int pool_host_call(tfhe_hip_pool *p, const PoolOp &op, void *out, size_t count, Run &&run) {
+  const void *q[5];
+  if (op.small && pool_small(p, count)) {
+    if (pool_missing(op, out)) return pool_fail(p, TFHE_HIP_EINVAL, "null pointer");
+    pool_shard_ptrs(op, 0, q);
+    tfhe_hip_ctx *c = pool_least_loaded(p);
+    return pool_member_rc(p, c, run(c, q, out, count, nullptr));
+  }
+  POOL_ENTER(p);
+  if (count && pool_missing(op, out)) return pool_fail(p, TFHE_HIP_EINVAL, "null pointer");
+  return pool_map(p, count, [&](tfhe_hip_ctx *c, size_t lo, size_t hi) {
+    const void *sq[5];
+    pool_shard_ptrs(op, lo, sq);
+    return run(c, sq, (unsigned char *)out + lo * op.out_row_bytes, hi - lo, nullptr);
+  });
+}
+
+// device pointers on member `home`'s GPU: only enqueued (pool_dev_map)
+template <class Run>
+int pool_dev_call(tfhe_hip_pool *p, int home, void *stream, const PoolOp &op, void *out, size_t count, Run &&run) {
+  POOL_ENTER(p);
+  if (op.refuse) return pool_fail(p, TFHE_HIP_EINVAL, op.refuse);
+  if (count && pool_missing(op, out)) return pool_fail(p, TFHE_HIP_EINVAL, "null pointer");
+  return pool_dev_map(p, home, count, stream, op.in, out, op.out_row_bytes, run);
+}
+template <bool DEV, class Run>
+int pool_call(tfhe_hip_pool *p, int home, void *stream, const PoolOp &op, void *out, size_t count, Run &&run) {
+  if constexpr (DEV) return pool_dev_call(p, home, stream, op, out, count, run);
+  else return pool_host_call(p, op, out, count, run);
+}
+
+template <bool DEV>
+int pool_gate(tfhe_hip_pool *p, int home, int gate, const uint32_t *a, const uint32_t *b, uint32_t *out, size_t count,
+              void *stream) {
+  if (!p) return TFHE_HIP_EINVAL;
+  GatePrep gp;
+  const bool known = gate_prep(gate, gp);  // (an unknown gate: the device form refuses it here, the host form's member does)
+  const bool has_b = !known || gp.cb;
+  const size_t w = pool_tlwe_bytes(p);
+  const PoolOp op{{{a, w, true, true}, {has_b ? b : nullptr, w, true, DEV && has_b}}, w, true, DEV && !known ? "unknown gate" : nullptr};
+  return pool_call<DEV>(p, home, stream, op, out, count, [&](tfhe_hip_ctx *c, const void *const *q, void *o, size_t m, void *s) {
+    if constexpr (DEV) return tfhe_hip_batch_gate_dev(c, gate, u32(q[0]), u32(q[1]), (uint32_t *)o, m, s);
+    else return tfhe_hip_batch_gate(c, gate, u32(q[0]), u32(q[1]), (uint32_t *)o, m);
+  });
+}
+
+template <bool DEV>
+int pool_gates_mixed(tfhe_hip_pool *p, int home, bool keyswitch, const uint8_t *gates, const uint32_t *a, const uint32_t *b,
+                     uint32_t *out, size_t count, void *stream) {
+  if (!p) return TFHE_HIP_EINVAL;
+  const size_t w = pool_tlwe_bytes(p);
+  const PoolOp op{{{a, w, true, true}, {b, w, true, true}, {gates, 1, true, true}}, w, true};
+  return pool_call<DEV>(p, home, stream, op, out, count, [&](tfhe_hip_ctx *c, const void *const *q, void *o, size_t m, void *s) {
+    if constexpr (DEV)
+      return (keyswitch ? tfhe_hip_batch_gates_mixed_dev : tfhe_hip_batch_gates_mixed_nks_dev)(c, (const uint8_t *)q[2], u32(q[0]), u32(q[1]), (uint32_t *)o, m, s);
+    else
+      return (keyswitch ? tfhe_hip_batch_gates_mixed : tfhe_hip_batch_gates_mixed_nks)(c, (const uint8_t *)q[2], u32(q[0]), u32(q[1]), (uint32_t *)o, m);
+  });
+}
+
+template <bool DEV>
+int pool_bootstrap(tfhe_hip_pool *p, int home, const uint32_t *in, const uint32_t *testvec, int per_ct, int keyswitch,
+                   uint32_t *out, size_t count, void *stream) {
+  if (!p) return TFHE_HIP_EINVAL;
+  const size_t w = pool_tlwe_bytes(p);
+  const PoolOp op{{{in, w, true, true}, {testvec, trlwe_bytes(1), testvec && per_ct}}, w, true};
+  return pool_call<DEV>(p, home, stream, op, out, count, [&](tfhe_hip_ctx *c, const void *const *q, void *o, size_t m, void *s) {
+    if constexpr (DEV) return tfhe_hip_batch_bootstrap_dev(c, u32(q[0]), u32(q[1]), per_ct, keyswitch, (uint32_t *)o, m, s);
+    else return tfhe_hip_batch_bootstrap(c, u32(q[0]), u32(q[1]), per_ct, keyswitch, (uint32_t *)o, m);
+  });
+}
+
+template <bool DEV>
+int pool_tlwe_lincomb(tfhe_hip_pool *p, int home, uint32_t ca, const uint32_t *a, uint32_t cb, const uint32_t *b,
+                      uint32_t cconst, uint32_t *out, size_t count, void *stream) {
+  if (!p) return TFHE_HIP_EINVAL;
+  const size_t w = pool_tlwe_bytes(p);
+  const PoolOp op{{{a, w, true, true}, {cb ? b : nullptr, w, true, cb != 0}}, w, false};
+  return pool_call<DEV>(p, home, stream, op, out, count, [&](tfhe_hip_ctx *c, const void *const *q, void *o, size_t m, void *s) {
+    if constexpr (DEV) return tfhe_hip_batch_tlwe_lincomb_dev(c, ca, u32(q[0]), cb, u32(q[1]), cconst, (uint32_t *)o, m, s);
+    else return tfhe_hip_batch_tlwe_lincomb(c, ca, u32(q[0]), cb, u32(q[1]), cconst, (uint32_t *)o, m);
+  });
+}
+
+template <bool DEV>
+int pool_lincomb_bootstrap(tfhe_hip_pool *p, int home, uint32_t ca, const uint32_t *a, uint32_t cb, const uint32_t *b,
+                           uint32_t cconst, const uint32_t *testvec, int per_ct, int keyswitch, uint32_t *out, size_t count,
+                           void *stream) {
+  if (!p) return TFHE_HIP_EINVAL;
+  const size_t w = pool_tlwe_bytes(p);
+  const PoolOp op{{{a, w, true, true}, {cb ? b : nullptr, w, true, cb != 0}, {testvec, trlwe_bytes(1), testvec && per_ct}}, w, true};
+  return pool_call<DEV>(p, home, stream, op, out, count, [&](tfhe_hip_ctx *c, const void *const *q, void *o, size_t m, void *s) {
+    if constexpr (DEV)
+      return tfhe_hip_batch_lincomb_bootstrap_dev(c, ca, u32(q[0]), cb, u32(q[1]), cconst, u32(q[2]), per_ct, keyswitch, (uint32_t *)o, m, s);
+    else
+      return tfhe_hip_batch_lincomb_bootstrap(c, ca, u32(q[0]), cb, u32(q[1]), cconst, u32(q[2]), per_ct, keyswitch, (uint32_t *)o, m);
+  });
+}
+
+// Many-LUT: rows are cut as for lincomb_bootstrap (no combining: many-LUT calls are never merged), but a member's result
+// is [k][m] -- function j of its shard belongs at rows j * count + lo of the caller's [k][count] -- so the table and the
+// checks are shared and the placing of the results is written out.  Host form: a shard that is not the whole batch lands
+// in a vector and is copied out slice by slice.  Device form: the member results travel as rows of k * (n+1) words; a
+// batch that is not cut lands in `out` as it is, otherwise it is gathered into a stream-ordered scratch on home and each
+// shard's k slices are put in place with one 2D copy.  (The device form looks at `home` before anything else.)
+template <bool DEV>
+int pool_lincomb_bootstrap_many(tfhe_hip_pool *p, int home, uint32_t ca, const uint32_t *a, uint32_t cb, const uint32_t *b,
+                                uint32_t cconst, const uint32_t *testvec, int per_ct, int n_luts, int keyswitch,
+                                uint32_t *out, size_t count, void *stream) {
+  POOL_ENTER(p);
+  if (DEV && (home < 0 || home >= (int)p->ctxs.size())) return pool_fail(p, TFHE_HIP_EINVAL, "no such pool member (home)");
+  if (const char *why = many_refusal(a, cb, b, testvec, n_luts, out, count)) return pool_fail(p, TFHE_HIP_EINVAL, why);
+  const size_t w = pool_tlwe_bytes(p);
+  const PoolOp op{{{a, w, true, true}, {cb ? b : nullptr, w, true, cb != 0}, {testvec, trlwe_bytes(1), per_ct != 0, true}},
+                  w * (size_t)n_luts, false};
+  auto run = [&](tfhe_hip_ctx *c, const void *const *q, void *o, size_t m, void *s) {
+    if constexpr (DEV)
+      return tfhe_hip_batch_lincomb_bootstrap_many_dev(c, ca, u32(q[0]), cb, u32(q[1]), cconst, u32(q[2]), per_ct, n_luts, keyswitch, (uint32_t *)o, m, s);
+    else
+      return tfhe_hip_batch_lincomb_bootstrap_many(c, ca, u32(q[0]), cb, u32(q[1]), cconst, u32(q[2]), per_ct, n_luts, keyswitch, (uint32_t *)o, m);
+  };
+  if constexpr (!DEV) {
+    return pool_map(p, count, [&](tfhe_hip_ctx *c, size_t lo, size_t hi) {
+      const size_t m = hi - lo;
+      const void *q[5];
+      pool_shard_ptrs(op, lo, q);
+      if (m == count) return run(c, q, out, m, nullptr);  // one shard: the member writes the caller's layout itself
+      std::vector<unsigned char> part((size_t)n_luts * m * w);
+      const int rc = run(c, q, part.data(), m, nullptr);
+      if (rc != TFHE_HIP_OK) return rc;
+      for (int j = 0; j < n_luts; ++j)
+        memcpy((unsigned char *)out + ((size_t)j * count + lo) * w, part.data() + (size_t)j * m * w, m * w);
+      return TFHE_HIP_OK;
+    });
+  } else {
+    const int world = pool_world_for(p, count);
+    if (world <= 1) return pool_dev_map(p, home, count, stream, op.in, out, op.out_row_bytes, run);
+    tfhe_hip_ctx *hctx = p->ctxs[(size_t)home];
+    tfhe_hip_ctx *hbase = hctx->parent ? hctx->parent : hctx;
+    hipStream_t hs = stream ? (hipStream_t)stream : hbase->stream;
+    hipStream_t hrt = hs == hipStreamLegacy ? (hipStream_t) nullptr : hs;  // (the runtime's name for the default stream)
+    int prev = -1;
+    (void)hipGetDevice(&prev);
+    struct Restore {
+      int d;
+      ~Restore() {
+        if (d >= 0) (void)hipSetDevice(d);
+      }
+    } restore{prev};
+    if (hipSetDevice(hctx->device) != hipSuccess) return pool_fail(p, TFHE_HIP_EHIP, "hipSetDevice (home)");
+    unsigned char *tmp = nullptr;
+    const size_t bytes = count * op.out_row_bytes;
+    if (hipMallocAsync((void **)&tmp, bytes, hrt) != hipSuccess) {
+      (void)hipGetLastError();
+      return pool_fail(p, TFHE_HIP_ENOMEM, "hipMallocAsync (many-LUT gather)");
+    }
+    int rc = pool_dev_map(p, home, count, stream, op.in, tmp, op.out_row_bytes, run);
+    (void)hipSetDevice(hctx->device);
+    for (int r = 0; r < world && rc == TFHE_HIP_OK; ++r) {
+      size_t lo, hi;
+      pool_shard(count, r, world, lo, hi);
+      if (hi <= lo) continue;
+      const size_t m = hi - lo;
+      if (hipMemcpy2DAsync((unsigned char *)out + lo * w, count * w, tmp + lo * op.out_row_bytes, m * w, m * w, (size_t)n_luts,
+                           hipMemcpyDeviceToDevice, hrt) != hipSuccess) {
+        (void)hipGetLastError();
+        rc = pool_fail(p, TFHE_HIP_EHIP, "hipMemcpy2DAsync (many-LUT gather)");
+      }
+    }
+    (void)hipFreeAsync(tmp, hrt);
+    return rc;
+  }
+}
+
+template <bool DEV>
+int pool_mux(tfhe_hip_pool *p, int home, int naive, const uint32_t *a, const uint32_t *b, const uint32_t *c3, uint32_t *out,
+             size_t count, void *stream) {
+  if (!p) return TFHE_HIP_EINVAL;
+  const size_t w = pool_tlwe_bytes(p);
+  const PoolOp op{{{a, w, true, true}, {b, w, true, true}, {c3, w, true, true}}, w, true};
+  return pool_call<DEV>(p, home, stream, op, out, count, [&](tfhe_hip_ctx *c, const void *const *q, void *o, size_t m, void *s) {
+    if constexpr (DEV) return tfhe_hip_batch_mux_dev(c, naive, u32(q[0]), u32(q[1]), u32(q[2]), (uint32_t *)o, m, s);
+    else return tfhe_hip_batch_mux(c, naive, u32(q[0]), u32(q[1]), u32(q[2]), (uint32_t *)o, m);
+  });
+}
+
+template <bool DEV>
+int pool_blind_rotate(tfhe_hip_pool *p, int home, const uint32_t *in, const uint32_t *testvec, uint32_t *out_trlwe,
+                      size_t count, void *stream) {
+  if (!p) return TFHE_HIP_EINVAL;
+  const PoolOp op{{{in, pool_tlwe_bytes(p), true, true}, {testvec, trlwe_bytes(1), false}}, trlwe_bytes(1), true};
+  return pool_call<DEV>(p, home, stream, op, out_trlwe, count, [&](tfhe_hip_ctx *c, const void *const *q, void *o, size_t m, void *s) {
+    if constexpr (DEV) return tfhe_hip_batch_blind_rotate_dev(c, u32(q[0]), u32(q[1]), (uint32_t *)o, m, s);
+    else return tfhe_hip_batch_blind_rotate(c, u32(q[0]), u32(q[1]), (uint32_t *)o, m);
+  });
+}
+
+// the key calls: made on the first member, whose key is then replicated device to device
 template <class F>
-int pool_small_call(tfhe_hip_pool *p, F &&call) {
-  tfhe_hip_ctx *c = pool_least_loaded(p);
-  const int rc = call(c);
-  if (rc != TFHE_HIP_OK) return pool_fail(p, rc, "device " + std::to_string(c->device) + ": " + tfhe_hip_last_error(c));
-  return TFHE_HIP_OK;
+int pool_key_call(tfhe_hip_pool *p, F &&on_first) {
+  POOL_ENTER(p);
+  CHK(pool_member_rc(p, p->ctxs[0], on_first(p->ctxs[0])));
+  return replicate_key(p);
 }
 }  // namespace
-#define POOL_FIRST(p, call)                                                                                        \
-  do {                                                                                                             \
-    const int rc_ = (call);                                                                                        \
-    if (rc_ != TFHE_HIP_OK) return pool_fail(p, rc_, "device " + std::to_string((p)->ctxs[0]->device) + ": " + tfhe_hip_last_error((p)->ctxs[0])); \
-  } while (0)
 
 int tfhe_hip_pool_load_cloud_key(tfhe_hip_pool *p, const double *bsk, const uint32_t *ksk, uint32_t decomp_offset,
                                  const uint32_t *testvec) {
-  POOL_ENTER(p);
-  POOL_FIRST(p, tfhe_hip_load_cloud_key(p->ctxs[0], bsk, ksk, decomp_offset, testvec));
-  return replicate_key(p);
+  return pool_key_call(p, [&](tfhe_hip_ctx *c) { return tfhe_hip_load_cloud_key(c, bsk, ksk, decomp_offset, testvec); });
 }
 
 int tfhe_hip_pool_load_compressed_cloud_key(tfhe_hip_pool *p, const uint8_t mask_seed[32], const uint32_t *bsk_bodies,
                                             const uint32_t *ksk_bodies, uint32_t decomp_offset, const uint32_t *testvec) {
-  POOL_ENTER(p);
-  POOL_FIRST(p, tfhe_hip_load_compressed_cloud_key(p->ctxs[0], mask_seed, bsk_bodies, ksk_bodies, decomp_offset, testvec));
-  return replicate_key(p);
+  return pool_key_call(p, [&](tfhe_hip_ctx *c) {
+    return tfhe_hip_load_compressed_cloud_key(c, mask_seed, bsk_bodies, ksk_bodies, decomp_offset, testvec);
+  });
 }
 
 int tfhe_hip_pool_gen_cloud_key_secure(tfhe_hip_pool *p, const uint32_t *key_lv0, const uint32_t *key_lv1,
                                        double alpha_ksk, double alpha_bsk) {
-  POOL_ENTER(p);
-  POOL_FIRST(p, tfhe_hip_gen_cloud_key_secure(p->ctxs[0], key_lv0, key_lv1, alpha_ksk, alpha_bsk));
-  return replicate_key(p);
+  return pool_key_call(p, [&](tfhe_hip_ctx *c) { return tfhe_hip_gen_cloud_key_secure(c, key_lv0, key_lv1, alpha_ksk, alpha_bsk); });
 }
 
 int tfhe_hip_pool_gen_cloud_key_with_key(tfhe_hip_pool *p, const uint32_t *key_lv0, const uint32_t *key_lv1,
                                          double alpha_ksk, double alpha_bsk, const uint8_t rng_key[32]) {
-  POOL_ENTER(p);
-  POOL_FIRST(p, tfhe_hip_gen_cloud_key_with_key(p->ctxs[0], key_lv0, key_lv1, alpha_ksk, alpha_bsk, rng_key));
-  return replicate_key(p);
+  return pool_key_call(p, [&](tfhe_hip_ctx *c) { return tfhe_hip_gen_cloud_key_with_key(c, key_lv0, key_lv1, alpha_ksk, alpha_bsk, rng_key); });
 }
 
 int tfhe_hip_pool_gen_cloud_key(tfhe_hip_pool *p, const uint32_t *key_lv0, const uint32_t *key_lv1, double alpha_ksk,
                                 double alpha_bsk, uint64_t seed) {
-  POOL_ENTER(p);
-  POOL_FIRST(p, tfhe_hip_gen_cloud_key(p->ctxs[0], key_lv0, key_lv1, alpha_ksk, alpha_bsk, seed));
-  return replicate_key(p);
+  return pool_key_call(p, [&](tfhe_hip_ctx *c) { return tfhe_hip_gen_cloud_key(c, key_lv0, key_lv1, alpha_ksk, alpha_bsk, seed); });
 }
 
 int tfhe_hip_pool_export_cloud_key(tfhe_hip_pool *p, int member, double *bsk, uint32_t *ksk, uint32_t *decomp_offset,
@@ -858,328 +1075,101 @@ int tfhe_hip_pool_export_cloud_key(tfhe_hip_pool *p, int member, double *bsk, ui
   POOL_ENTER(p);
   if (member < 0 || (size_t)member >= p->ctxs.size()) return pool_fail(p, TFHE_HIP_EINVAL, "no such pool member");
   tfhe_hip_ctx *c = p->ctxs[(size_t)member];
-  const int rc = tfhe_hip_export_cloud_key(c, bsk, ksk, decomp_offset, testvec);
-  if (rc != TFHE_HIP_OK) return pool_fail(p, rc, "device " + std::to_string(c->device) + ": " + tfhe_hip_last_error(c));
-  return TFHE_HIP_OK;
+  return pool_member_rc(p, c, tfhe_hip_export_cloud_key(c, bsk, ksk, decomp_offset, testvec));
 }
 
-// ---- host-pointer batch calls: one host thread per shard ---------------------------------------------------------
+// ---- the batch entry points: host pointers, then device pointers on member `home`'s GPU (operations: above) --------
 int tfhe_hip_pool_batch_gate(tfhe_hip_pool *p, int gate, const uint32_t *a, const uint32_t *b, uint32_t *out,
                              size_t count) {
-  if (pool_small(p, count)) {
-    if (!a || !out) return pool_fail(p, TFHE_HIP_EINVAL, "null pointer");
-    return pool_small_call(p, [&](tfhe_hip_ctx *c) { return tfhe_hip_batch_gate(c, gate, a, b, out, count); });
-  }
-  POOL_ENTER(p);
-  if (count && (!a || !out)) return pool_fail(p, TFHE_HIP_EINVAL, "null pointer");
-  const size_t w = (size_t)p->ctxs[0]->P.n + 1;
-  return pool_map(p, count, [&](tfhe_hip_ctx *c, size_t lo, size_t hi) {
-    return tfhe_hip_batch_gate(c, gate, a + lo * w, b ? b + lo * w : nullptr, out + lo * w, hi - lo);
-  });
+  return pool_gate<false>(p, 0, gate, a, b, out, count, nullptr);
 }
-
 int tfhe_hip_pool_batch_gates_mixed(tfhe_hip_pool *p, const uint8_t *gates, const uint32_t *a, const uint32_t *b,
                                     uint32_t *out, size_t count) {
-  if (pool_small(p, count)) {
-    if (!gates || !a || !b || !out) return pool_fail(p, TFHE_HIP_EINVAL, "null pointer");
-    return pool_small_call(p, [&](tfhe_hip_ctx *c) { return tfhe_hip_batch_gates_mixed(c, gates, a, b, out, count); });
-  }
-  POOL_ENTER(p);
-  if (count && (!gates || !a || !b || !out)) return pool_fail(p, TFHE_HIP_EINVAL, "null pointer");
-  const size_t w = (size_t)p->ctxs[0]->P.n + 1;
-  return pool_map(p, count, [&](tfhe_hip_ctx *c, size_t lo, size_t hi) {
-    return tfhe_hip_batch_gates_mixed(c, gates + lo, a + lo * w, b + lo * w, out + lo * w, hi - lo);
-  });
+  return pool_gates_mixed<false>(p, 0, true, gates, a, b, out, count, nullptr);
 }
-
 int tfhe_hip_pool_batch_gates_mixed_nks(tfhe_hip_pool *p, const uint8_t *gates, const uint32_t *a, const uint32_t *b,
                                         uint32_t *out, size_t count) {
-  if (pool_small(p, count)) {
-    if (!gates || !a || !b || !out) return pool_fail(p, TFHE_HIP_EINVAL, "null pointer");
-    return pool_small_call(p, [&](tfhe_hip_ctx *c) { return tfhe_hip_batch_gates_mixed_nks(c, gates, a, b, out, count); });
-  }
-  POOL_ENTER(p);
-  if (count && (!gates || !a || !b || !out)) return pool_fail(p, TFHE_HIP_EINVAL, "null pointer");
-  const size_t w = (size_t)p->ctxs[0]->P.n + 1;
-  return pool_map(p, count, [&](tfhe_hip_ctx *c, size_t lo, size_t hi) {
-    return tfhe_hip_batch_gates_mixed_nks(c, gates + lo, a + lo * w, b + lo * w, out + lo * w, hi - lo);
-  });
+  return pool_gates_mixed<false>(p, 0, false, gates, a, b, out, count, nullptr);
 }
-
 int tfhe_hip_pool_batch_bootstrap(tfhe_hip_pool *p, const uint32_t *in, const uint32_t *testvec, int per_ct,
                                   int keyswitch, uint32_t *out, size_t count) {
-  if (pool_small(p, count)) {
-    if (!in || !out) return pool_fail(p, TFHE_HIP_EINVAL, "null pointer");
-    return pool_small_call(p, [&](tfhe_hip_ctx *c) { return tfhe_hip_batch_bootstrap(c, in, testvec, per_ct, keyswitch, out, count); });
-  }
-  POOL_ENTER(p);
-  if (count && (!in || !out)) return pool_fail(p, TFHE_HIP_EINVAL, "null pointer");
-  const size_t w = (size_t)p->ctxs[0]->P.n + 1;
-  const size_t tvs = (testvec && per_ct) ? (size_t)2 * kN : 0;
-  return pool_map(p, count, [&](tfhe_hip_ctx *c, size_t lo, size_t hi) {
-    return tfhe_hip_batch_bootstrap(c, in + lo * w, testvec ? testvec + lo * tvs : nullptr, per_ct, keyswitch, out + lo * w,
-                                    hi - lo);
-  });
+  return pool_bootstrap<false>(p, 0, in, testvec, per_ct, keyswitch, out, count, nullptr);
 }
-
 int tfhe_hip_pool_batch_tlwe_lincomb(tfhe_hip_pool *p, uint32_t ca, const uint32_t *a, uint32_t cb, const uint32_t *b,
                                      uint32_t cconst, uint32_t *out, size_t count) {
-  POOL_ENTER(p);
-  if (count && (!a || !out || (cb && !b))) return pool_fail(p, TFHE_HIP_EINVAL, "null pointer");
-  const size_t w = (size_t)p->ctxs[0]->P.n + 1;
-  return pool_map(p, count, [&](tfhe_hip_ctx *c, size_t lo, size_t hi) {
-    return tfhe_hip_batch_tlwe_lincomb(c, ca, a + lo * w, cb, b ? b + lo * w : nullptr, cconst, out + lo * w, hi - lo);
-  });
+  return pool_tlwe_lincomb<false>(p, 0, ca, a, cb, b, cconst, out, count, nullptr);
 }
-
 int tfhe_hip_pool_batch_lincomb_bootstrap(tfhe_hip_pool *p, uint32_t ca, const uint32_t *a, uint32_t cb,
                                           const uint32_t *b, uint32_t cconst, const uint32_t *testvec, int per_ct,
                                           int keyswitch, uint32_t *out, size_t count) {
-  if (pool_small(p, count)) {
-    if (!a || !out || (cb && !b)) return pool_fail(p, TFHE_HIP_EINVAL, "null pointer");
-    return pool_small_call(p, [&](tfhe_hip_ctx *c) {
-      return tfhe_hip_batch_lincomb_bootstrap(c, ca, a, cb, b, cconst, testvec, per_ct, keyswitch, out, count);
-    });
-  }
-  POOL_ENTER(p);
-  if (count && (!a || !out || (cb && !b))) return pool_fail(p, TFHE_HIP_EINVAL, "null pointer");
-  const size_t w = (size_t)p->ctxs[0]->P.n + 1;
-  const size_t tvs = (testvec && per_ct) ? (size_t)2 * kN : 0;
-  return pool_map(p, count, [&](tfhe_hip_ctx *c, size_t lo, size_t hi) {
-    return tfhe_hip_batch_lincomb_bootstrap(c, ca, a + lo * w, cb, b ? b + lo * w : nullptr, cconst,
-                                            testvec ? testvec + lo * tvs : nullptr, per_ct, keyswitch, out + lo * w, hi - lo);
-  });
+  return pool_lincomb_bootstrap<false>(p, 0, ca, a, cb, b, cconst, testvec, per_ct, keyswitch, out, count, nullptr);
 }
-
-// many-LUT bootstrap: the checks of the single-context entry points, in their order
-int pool_many_checks(tfhe_hip_pool *p, const uint32_t *a, uint32_t cb, const uint32_t *b, const uint32_t *testvec,
-                     int n_luts, const uint32_t *out, size_t count) {
-  if (lut_shift_of(n_luts) < 0) return pool_fail(p, TFHE_HIP_EINVAL, "n_luts must be 1, 2, 4 or 8");
-  if (!testvec) return pool_fail(p, TFHE_HIP_EINVAL, "many-LUT bootstrap needs a test vector");
-  if (cb && !b) return pool_fail(p, TFHE_HIP_EINVAL, "null pointer");
-  if (count && (!a || !out)) return pool_fail(p, TFHE_HIP_EINVAL, "null pointer");
-  if (count > 0x7FFFFFFFull || (count << lut_shift_of(n_luts)) > 0x7FFFFFFFull)
-    return pool_fail(p, TFHE_HIP_EINVAL, "n_luts * count too large");
-  return TFHE_HIP_OK;
-}
-
-// Rows are cut as for tfhe_hip_pool_batch_lincomb_bootstrap (no combining: many-LUT calls are never merged).  A
-// member's result is [k][m]: function j of its shard goes to rows j * count + lo of the caller's [k][count].
 int tfhe_hip_pool_batch_lincomb_bootstrap_many(tfhe_hip_pool *p, uint32_t ca, const uint32_t *a, uint32_t cb,
                                                const uint32_t *b, uint32_t cconst, const uint32_t *testvec, int per_ct,
                                                int n_luts, int keyswitch, uint32_t *out, size_t count) {
-  POOL_ENTER(p);
-  CHK(pool_many_checks(p, a, cb, b, testvec, n_luts, out, count));
-  const size_t w = (size_t)p->ctxs[0]->P.n + 1;
-  const size_t tvs = per_ct ? (size_t)2 * kN : 0;
-  return pool_map(p, count, [&](tfhe_hip_ctx *c, size_t lo, size_t hi) {
-    const size_t m = hi - lo;
-    const uint32_t *sa = a + lo * w, *sb = b ? b + lo * w : nullptr, *stv = testvec + lo * tvs;
-    if (m == count)  // one shard: the member writes the caller's layout itself
-      return tfhe_hip_batch_lincomb_bootstrap_many(c, ca, sa, cb, sb, cconst, stv, per_ct, n_luts, keyswitch, out, m);
-    std::vector<uint32_t> part((size_t)n_luts * m * w);
-    const int rc = tfhe_hip_batch_lincomb_bootstrap_many(c, ca, sa, cb, sb, cconst, stv, per_ct, n_luts, keyswitch,
-                                                         part.data(), m);
-    if (rc != TFHE_HIP_OK) return rc;
-    for (int j = 0; j < n_luts; ++j)
-      memcpy(out + ((size_t)j * count + lo) * w, part.data() + (size_t)j * m * w, m * w * 4);
-    return TFHE_HIP_OK;
-  });
+  return pool_lincomb_bootstrap_many<false>(p, 0, ca, a, cb, b, cconst, testvec, per_ct, n_luts, keyswitch, out, count, nullptr);
 }
-
 int tfhe_hip_pool_batch_mux(tfhe_hip_pool *p, int naive, const uint32_t *a, const uint32_t *b, const uint32_t *c3,
                             uint32_t *out, size_t count) {
-  if (pool_small(p, count)) {
-    if (!a || !b || !c3 || !out) return pool_fail(p, TFHE_HIP_EINVAL, "null pointer");
-    return pool_small_call(p, [&](tfhe_hip_ctx *c) { return tfhe_hip_batch_mux(c, naive, a, b, c3, out, count); });
-  }
-  POOL_ENTER(p);
-  if (count && (!a || !b || !c3 || !out)) return pool_fail(p, TFHE_HIP_EINVAL, "null pointer");
-  const size_t w = (size_t)p->ctxs[0]->P.n + 1;
-  return pool_map(p, count, [&](tfhe_hip_ctx *c, size_t lo, size_t hi) {
-    return tfhe_hip_batch_mux(c, naive, a + lo * w, b + lo * w, c3 + lo * w, out + lo * w, hi - lo);
-  });
+  return pool_mux<false>(p, 0, naive, a, b, c3, out, count, nullptr);
 }
-
 int tfhe_hip_pool_batch_blind_rotate(tfhe_hip_pool *p, const uint32_t *in, const uint32_t *testvec, uint32_t *out_trlwe,
                                      size_t count) {
-  if (pool_small(p, count)) {
-    if (!in || !out_trlwe) return pool_fail(p, TFHE_HIP_EINVAL, "null pointer");
-    return pool_small_call(p, [&](tfhe_hip_ctx *c) { return tfhe_hip_batch_blind_rotate(c, in, testvec, out_trlwe, count); });
-  }
-  POOL_ENTER(p);
-  if (count && (!in || !out_trlwe)) return pool_fail(p, TFHE_HIP_EINVAL, "null pointer");
-  const size_t w = (size_t)p->ctxs[0]->P.n + 1;
-  return pool_map(p, count, [&](tfhe_hip_ctx *c, size_t lo, size_t hi) {
-    return tfhe_hip_batch_blind_rotate(c, in + lo * w, testvec, out_trlwe + lo * (size_t)2 * kN, hi - lo);
-  });
+  return pool_blind_rotate<false>(p, 0, in, testvec, out_trlwe, count, nullptr);
 }
 
-// ---- device-resident batch calls: the batch lives on member `home`'s GPU (pool_dev_map) -------------------------
 int tfhe_hip_pool_batch_gate_dev(tfhe_hip_pool *p, int home, int gate, const uint32_t *a, const uint32_t *b,
                                  uint32_t *out, size_t count, void *stream) {
-  POOL_ENTER(p);
-  GatePrep gp;
-  if (!gate_prep(gate, gp)) return pool_fail(p, TFHE_HIP_EINVAL, "unknown gate");
-  if (count && (!a || !out || (gp.cb && !b))) return pool_fail(p, TFHE_HIP_EINVAL, "null pointer");
-  const size_t w = ((size_t)p->ctxs[0]->P.n + 1) * 4;
-  const PoolIn ins[5] = {{a, w, true}, {gp.cb ? b : nullptr, w, true}, {}, {}, {}};
-  return pool_dev_map(p, home, count, stream, ins, out, w, [&](tfhe_hip_ctx *c, const void *const *q, void *o, size_t m, void *s) {
-    return tfhe_hip_batch_gate_dev(c, gate, (const uint32_t *)q[0], (const uint32_t *)q[1], (uint32_t *)o, m, s);
-  });
+  return pool_gate<true>(p, home, gate, a, b, out, count, stream);
 }
-
 int tfhe_hip_pool_batch_gates_mixed_dev(tfhe_hip_pool *p, int home, const uint8_t *gates, const uint32_t *a,
                                         const uint32_t *b, uint32_t *out, size_t count, void *stream) {
-  POOL_ENTER(p);
-  if (count && (!gates || !a || !b || !out)) return pool_fail(p, TFHE_HIP_EINVAL, "null pointer");
-  const size_t w = ((size_t)p->ctxs[0]->P.n + 1) * 4;
-  const PoolIn ins[5] = {{a, w, true}, {b, w, true}, {gates, 1, true}, {}, {}};
-  return pool_dev_map(p, home, count, stream, ins, out, w, [&](tfhe_hip_ctx *c, const void *const *q, void *o, size_t m, void *s) {
-    return tfhe_hip_batch_gates_mixed_dev(c, (const uint8_t *)q[2], (const uint32_t *)q[0], (const uint32_t *)q[1], (uint32_t *)o, m, s);
-  });
+  return pool_gates_mixed<true>(p, home, true, gates, a, b, out, count, stream);
 }
-
 int tfhe_hip_pool_batch_gates_mixed_nks_dev(tfhe_hip_pool *p, int home, const uint8_t *gates, const uint32_t *a,
                                             const uint32_t *b, uint32_t *out, size_t count, void *stream) {
-  POOL_ENTER(p);
-  if (count && (!gates || !a || !b || !out)) return pool_fail(p, TFHE_HIP_EINVAL, "null pointer");
-  const size_t w = ((size_t)p->ctxs[0]->P.n + 1) * 4;
-  const PoolIn ins[5] = {{a, w, true}, {b, w, true}, {gates, 1, true}, {}, {}};
-  return pool_dev_map(p, home, count, stream, ins, out, w, [&](tfhe_hip_ctx *c, const void *const *q, void *o, size_t m, void *s) {
-    return tfhe_hip_batch_gates_mixed_nks_dev(c, (const uint8_t *)q[2], (const uint32_t *)q[0], (const uint32_t *)q[1], (uint32_t *)o, m, s);
-  });
+  return pool_gates_mixed<true>(p, home, false, gates, a, b, out, count, stream);
 }
-
 int tfhe_hip_pool_batch_bootstrap_dev(tfhe_hip_pool *p, int home, const uint32_t *in, const uint32_t *testvec, int per_ct,
                                       int keyswitch, uint32_t *out, size_t count, void *stream) {
-  POOL_ENTER(p);
-  if (count && (!in || !out)) return pool_fail(p, TFHE_HIP_EINVAL, "null pointer");
-  const size_t w = ((size_t)p->ctxs[0]->P.n + 1) * 4;
-  const PoolIn ins[5] = {{in, w, true}, {testvec, (size_t)2 * kN * 4, testvec && per_ct}, {}, {}, {}};
-  return pool_dev_map(p, home, count, stream, ins, out, w, [&](tfhe_hip_ctx *c, const void *const *q, void *o, size_t m, void *s) {
-    return tfhe_hip_batch_bootstrap_dev(c, (const uint32_t *)q[0], (const uint32_t *)q[1], per_ct, keyswitch, (uint32_t *)o, m, s);
-  });
+  return pool_bootstrap<true>(p, home, in, testvec, per_ct, keyswitch, out, count, stream);
 }
-
 int tfhe_hip_pool_batch_tlwe_lincomb_dev(tfhe_hip_pool *p, int home, uint32_t ca, const uint32_t *a, uint32_t cb,
                                          const uint32_t *b, uint32_t cconst, uint32_t *out, size_t count, void *stream) {
-  POOL_ENTER(p);
-  if (count && (!a || !out || (cb && !b))) return pool_fail(p, TFHE_HIP_EINVAL, "null pointer");
-  const size_t w = ((size_t)p->ctxs[0]->P.n + 1) * 4;
-  const PoolIn ins[5] = {{a, w, true}, {cb ? b : nullptr, w, true}, {}, {}, {}};
-  return pool_dev_map(p, home, count, stream, ins, out, w, [&](tfhe_hip_ctx *c, const void *const *q, void *o, size_t m, void *s) {
-    return tfhe_hip_batch_tlwe_lincomb_dev(c, ca, (const uint32_t *)q[0], cb, (const uint32_t *)q[1], cconst, (uint32_t *)o, m, s);
-  });
+  return pool_tlwe_lincomb<true>(p, home, ca, a, cb, b, cconst, out, count, stream);
 }
-
 int tfhe_hip_pool_batch_lincomb_bootstrap_dev(tfhe_hip_pool *p, int home, uint32_t ca, const uint32_t *a, uint32_t cb,
                                               const uint32_t *b, uint32_t cconst, const uint32_t *testvec, int per_ct,
                                               int keyswitch, uint32_t *out, size_t count, void *stream) {
-  POOL_ENTER(p);
-  if (count && (!a || !out || (cb && !b))) return pool_fail(p, TFHE_HIP_EINVAL, "null pointer");
-  const size_t w = ((size_t)p->ctxs[0]->P.n + 1) * 4;
-  const PoolIn ins[5] = {{a, w, true}, {cb ? b : nullptr, w, true}, {testvec, (size_t)2 * kN * 4, testvec && per_ct}, {}, {}};
-  return pool_dev_map(p, home, count, stream, ins, out, w, [&](tfhe_hip_ctx *c, const void *const *q, void *o, size_t m, void *s) {
-    return tfhe_hip_batch_lincomb_bootstrap_dev(c, ca, (const uint32_t *)q[0], cb, (const uint32_t *)q[1], cconst,
-                                                (const uint32_t *)q[2], per_ct, keyswitch, (uint32_t *)o, m, s);
-  });
+  return pool_lincomb_bootstrap<true>(p, home, ca, a, cb, b, cconst, testvec, per_ct, keyswitch, out, count, stream);
 }
-
-// The member results travel as rows of k * (n+1) words ([k][m] per shard).  A batch that is not cut lands in `out` as
-// it is; otherwise it is gathered into a stream-ordered scratch on home and each shard's k slices are put in place
-// with one 2D copy.
 int tfhe_hip_pool_batch_lincomb_bootstrap_many_dev(tfhe_hip_pool *p, int home, uint32_t ca, const uint32_t *a, uint32_t cb,
                                                    const uint32_t *b, uint32_t cconst, const uint32_t *testvec,
                                                    int per_ct, int n_luts, int keyswitch, uint32_t *out, size_t count,
                                                    void *stream) {
-  POOL_ENTER(p);
-  if (home < 0 || home >= (int)p->ctxs.size()) return pool_fail(p, TFHE_HIP_EINVAL, "no such pool member (home)");
-  CHK(pool_many_checks(p, a, cb, b, testvec, n_luts, out, count));
-  const size_t w = ((size_t)p->ctxs[0]->P.n + 1) * 4;
-  const PoolIn ins[5] = {{a, w, true}, {cb ? b : nullptr, w, true}, {testvec, (size_t)2 * kN * 4, per_ct != 0}, {}, {}};
-  auto op = [&](tfhe_hip_ctx *c, const void *const *q, void *o, size_t m, void *s) {
-    return tfhe_hip_batch_lincomb_bootstrap_many_dev(c, ca, (const uint32_t *)q[0], cb, (const uint32_t *)q[1], cconst,
-                                                     (const uint32_t *)q[2], per_ct, n_luts, keyswitch, (uint32_t *)o, m, s);
-  };
-  const int world = pool_world_for(p, count);
-  if (world <= 1) return pool_dev_map(p, home, count, stream, ins, out, w * (size_t)n_luts, op);
-  tfhe_hip_ctx *hctx = p->ctxs[(size_t)home];
-  tfhe_hip_ctx *hbase = hctx->parent ? hctx->parent : hctx;
-  hipStream_t hs = stream ? (hipStream_t)stream : hbase->stream;
-  hipStream_t hrt = hs == hipStreamLegacy ? (hipStream_t) nullptr : hs;  // (the runtime's name for the default stream)
-  int prev = -1;
-  (void)hipGetDevice(&prev);
-  struct Restore {
-    int d;
-    ~Restore() {
-      if (d >= 0) (void)hipSetDevice(d);
-    }
-  } restore{prev};
-  if (hipSetDevice(hctx->device) != hipSuccess) return pool_fail(p, TFHE_HIP_EHIP, "hipSetDevice (home)");
-  unsigned char *tmp = nullptr;
-  const size_t bytes = count * w * (size_t)n_luts;
-  if (hipMallocAsync((void **)&tmp, bytes, hrt) != hipSuccess) {
-    (void)hipGetLastError();
-    return pool_fail(p, TFHE_HIP_ENOMEM, "hipMallocAsync (many-LUT gather)");
-  }
-  int rc = pool_dev_map(p, home, count, stream, ins, tmp, w * (size_t)n_luts, op);
-  (void)hipSetDevice(hctx->device);
-  for (int r = 0; r < world && rc == TFHE_HIP_OK; ++r) {
-    size_t lo, hi;
-    pool_shard(count, r, world, lo, hi);
-    if (hi <= lo) continue;
-    const size_t m = hi - lo;
-    if (hipMemcpy2DAsync((unsigned char *)out + lo * w, count * w, tmp + lo * w * (size_t)n_luts, m * w, m * w,
-                         (size_t)n_luts, hipMemcpyDeviceToDevice, hrt) != hipSuccess) {
-      (void)hipGetLastError();
-      rc = pool_fail(p, TFHE_HIP_EHIP, "hipMemcpy2DAsync (many-LUT gather)");
-    }
-  }
-  (void)hipFreeAsync(tmp, hrt);
-  return rc;
+  return pool_lincomb_bootstrap_many<true>(p, home, ca, a, cb, b, cconst, testvec, per_ct, n_luts, keyswitch, out, count, stream);
 }
-
 int tfhe_hip_pool_batch_mux_dev(tfhe_hip_pool *p, int home, int naive, const uint32_t *a, const uint32_t *b,
                                 const uint32_t *c3, uint32_t *out, size_t count, void *stream) {
-  POOL_ENTER(p);
-  if (count && (!a || !b || !c3 || !out)) return pool_fail(p, TFHE_HIP_EINVAL, "null pointer");
-  const size_t w = ((size_t)p->ctxs[0]->P.n + 1) * 4;
-  const PoolIn ins[5] = {{a, w, true}, {b, w, true}, {c3, w, true}, {}, {}};
-  return pool_dev_map(p, home, count, stream, ins, out, w, [&](tfhe_hip_ctx *c, const void *const *q, void *o, size_t m, void *s) {
-    return tfhe_hip_batch_mux_dev(c, naive, (const uint32_t *)q[0], (const uint32_t *)q[1], (const uint32_t *)q[2], (uint32_t *)o, m, s);
-  });
+  return pool_mux<true>(p, home, naive, a, b, c3, out, count, stream);
 }
-
 int tfhe_hip_pool_batch_blind_rotate_dev(tfhe_hip_pool *p, int home, const uint32_t *in, const uint32_t *testvec,
                                          uint32_t *out_trlwe, size_t count, void *stream) {
-  POOL_ENTER(p);
-  if (count && (!in || !out_trlwe)) return pool_fail(p, TFHE_HIP_EINVAL, "null pointer");
-  const size_t w = ((size_t)p->ctxs[0]->P.n + 1) * 4;
-  const PoolIn ins[5] = {{in, w, true}, {testvec, (size_t)2 * kN * 4, false}, {}, {}, {}};
-  return pool_dev_map(p, home, count, stream, ins, out_trlwe, (size_t)2 * kN * 4, [&](tfhe_hip_ctx *c, const void *const *q, void *o, size_t m, void *s) {
-    return tfhe_hip_batch_blind_rotate_dev(c, (const uint32_t *)q[0], (const uint32_t *)q[1], (uint32_t *)o, m, s);
-  });
+  return pool_blind_rotate<true>(p, home, in, testvec, out_trlwe, count, stream);
 }
 
 // Block until every member has finished what the pool's *_dev calls enqueued (home streams passed by the caller are
 // the caller's to synchronise; the members' own streams are drained here).
 int tfhe_hip_pool_synchronize(tfhe_hip_pool *p) {
   POOL_ENTER(p);
-  for (auto *c : p->ctxs) {
-    const int rc = tfhe_hip_synchronize(c);
-    if (rc != TFHE_HIP_OK) return pool_fail(p, rc, "device " + std::to_string(c->device) + ": " + tfhe_hip_last_error(c));
-  }
+  for (auto *c : p->ctxs) CHK(pool_member_rc(p, c, tfhe_hip_synchronize(c)));
   return TFHE_HIP_OK;
 }
 
 int tfhe_hip_pool_set_profiling(tfhe_hip_pool *p, int enabled) {
   POOL_ENTER(p);
   p->root()->timing = enabled != 0;
-  for (auto *c : p->ctxs) {
-    const int rc = tfhe_hip_set_profiling(c, enabled);
-    if (rc != TFHE_HIP_OK) return pool_fail(p, rc, "device " + std::to_string(c->device) + ": " + tfhe_hip_last_error(c));
-  }
+  for (auto *c : p->ctxs) CHK(pool_member_rc(p, c, tfhe_hip_set_profiling(c, enabled)));
   return TFHE_HIP_OK;
 }
 
@@ -1259,18 +1249,15 @@ int tfhe_hip_pool_get_transfer_times(tfhe_hip_pool *p, tfhe_hip_pool_transfer_ti
 // ---- packing key switch (packing.hpp): whole groups of N per member, in input order ----------------------------------------------------------
 int tfhe_hip_pool_load_packing_key(tfhe_hip_pool *p, const uint8_t mask_seed[32], const uint32_t *bodies) {
   POOL_ENTER(p);
-  for (auto *c : p->ctxs) {  // every member expands the bodies itself (no cloud key, nothing to replicate)
-    const int rc = tfhe_hip_load_packing_key(c, mask_seed, bodies);
-    if (rc != TFHE_HIP_OK) return pool_fail(p, rc, "device " + std::to_string(c->device) + ": " + tfhe_hip_last_error(c));
-  }
+  // every member expands the bodies itself (no cloud key, nothing to replicate)
+  for (auto *c : p->ctxs) CHK(pool_member_rc(p, c, tfhe_hip_load_packing_key(c, mask_seed, bodies)));
   return TFHE_HIP_OK;
 }
 
 int tfhe_hip_pool_batch_pack_tlwe(tfhe_hip_pool *p, const uint32_t *in, size_t count, uint32_t *out) {
   POOL_ENTER(p);
   if (count == 0) {  // a member's checks (ENOKEY first), nothing to run
-    POOL_FIRST(p, tfhe_hip_batch_pack_tlwe(p->ctxs[0], in, 0, out));
-    return TFHE_HIP_OK;
+    return pool_member_rc(p, p->ctxs[0], tfhe_hip_batch_pack_tlwe(p->ctxs[0], in, 0, out));
   }
   if (!in || !out) return pool_fail(p, TFHE_HIP_EINVAL, "null pointer");
   const size_t w = (size_t)p->ctxs[0]->P.n + 1, groups = (count + kN - 1) / kN;
@@ -1286,7 +1273,8 @@ int tfhe_hip_pool_batch_pack_tlwe_dev(tfhe_hip_pool *p, int home, const uint32_t
   POOL_ENTER(p);
   if (home < 0 || home >= (int)p->ctxs.size()) return pool_fail(p, TFHE_HIP_EINVAL, "no such pool member (home)");
   if (count == 0) {
-    POOL_FIRST(p, tfhe_hip_batch_pack_tlwe_dev(p->ctxs[(size_t)home], in, 0, out, stream));
+    // (a failure is reported with the FIRST member's device and text, whichever member is home)
+    CHK(pool_member_rc(p, p->ctxs[0], tfhe_hip_batch_pack_tlwe_dev(p->ctxs[(size_t)home], in, 0, out, stream)));
     p->root()->last_transport = "none";
     return TFHE_HIP_OK;
   }
@@ -1301,11 +1289,9 @@ int tfhe_hip_pool_batch_pack_tlwe_dev(tfhe_hip_pool *p, int home, const uint32_t
   }, world));
   if (tail) {
     tfhe_hip_ctx *c = p->ctxs[(size_t)home];
-    const int rc = tfhe_hip_batch_pack_tlwe_dev(c, in + full * kN * w, tail, out + full * (size_t)2 * kN, stream);
-    if (rc != TFHE_HIP_OK) return pool_fail(p, rc, "device " + std::to_string(c->device) + ": " + tfhe_hip_last_error(c));
+    return pool_member_rc(p, c, tfhe_hip_batch_pack_tlwe_dev(c, in + full * kN * w, tail, out + full * (size_t)2 * kN, stream));
   }
   return TFHE_HIP_OK;
 }
 
 #undef POOL_ENTER
-#undef POOL_FIRST

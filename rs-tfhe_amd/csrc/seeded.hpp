@@ -267,7 +267,7 @@ ChaChaKey seed_key(const uint8_t seed[32]) {
 int expand_key_locked(tfhe_hip_ctx *ctx, const ChaChaKey &seed, const uint32_t *d_bsk_bodies, const uint32_t *d_ksk_bodies) {
   const tfhe_hip_params &P = ctx->P;
   hipLaunchKernelGGL(k_expand_bsk<64>, dim3((unsigned)(P.n * 2 * P.l)), dim3(64), kStageLdsBytes, ctx->stream, d_bsk_bodies,
-                     ctx->d_tw, ctx->K->d_bsk, seed, key_scale(ctx->fast_round));
+                     ctx->d_tw, ctx->K->d_bsk, seed, key_scale(ctx->dispatch.fast_round));
   HIPCHK(ctx, hipGetLastError());
   hipLaunchKernelGGL(k_expand_ksk<256>, dim3((unsigned)((size_t)kN * P.t * (1u << P.basebit))), dim3(256), 0, ctx->stream,
                      d_ksk_bodies, ctx->K->d_ksk, P.n, P.basebit, seed);

@@ -172,24 +172,28 @@ struct tfhe_hip_ctx {
   uint64_t id = new_handle_id();  // key of this context's per-thread error text (err_slot)
   bool profiling = false;
   int num_cus = 0;
-  bool fast_round = false;  // |pre-rounding value| < 2^51 guaranteed (see round_to_torus<FAST>)
   // ---- dispatch (plan_blind_rotate / plan_key_switch below; tfhe_hip_describe_dispatch prints a plan) ----
-  // The two selectors are the supported controls (TFHE_HIP_BR_KERNEL / TFHE_HIP_KS_KERNEL, include/tfhe_hip.h):
-  // AUTO picks per batch size, anything else runs that kernel at every batch size.
-  int br_force = 0;  // BrKind + 1, 0 = auto
-  int ks_force = 0;  // KsKind + 1, 0 = auto
-  // crossovers of the automatic choice, in ciphertexts; set from the CU count at creation.  Numeric overrides exist
-  // only in -DTFHE_EXPERIMENT builds (profiles/exp/).
-  size_t wide_max = 256;      // blind rotate: one eight-wave workgroup per ciphertext up to this batch size
-  size_t pair_lo = 0, pair_max = 0;  // ... two ciphertexts per workgroup (k_blind_rotate_pair) for pair_lo < count <= pair_max
-  size_t ks_split_max = 256;  // key switch: coefficient walk split over 32 workgroups up to this batch size
-  size_t ks_mfma_min = 64;    // smallest batch the matrix-core kernel takes (below: the split kernel)
-  size_t ks_sl_chunk_min = 384;  // wider bases: smallest batch the column-sliced kernel takes (with K chunks; below: the split kernel)
-  int ks_sliced_sets = 0;     // 0: accumulator sets per lane picked per launch (ks_sl2_pick_sets); else forced (24..36; experiment builds)
-  int ks_mfma_ksplit = 0;     // 0: K chunks per row block picked per launch; else forced (1, 2, 4, 8, 16)
-  int ks_sl_kchunks = 0;      // 0: K chunks of the column-sliced kernel picked per launch; else forced (1 ... 64, a power of two)
-  long br_chunk = 0;  // blind-rotate workgroups per launch: 0 = whole batch (default), -1 = resident set, N = N
-  bool exp_wide1 = false;  // (experiment builds with -DTFHE_EXP_WIDE1: SINGLE runs the superseded one-wave-per-row kernel)
+  // One member, so that a combiner lane takes its base context's choices with one assignment (comb_make_lane): a
+  // knob added here reaches the merged small calls too.
+  struct Dispatch {
+    // The two selectors are the supported controls (TFHE_HIP_BR_KERNEL / TFHE_HIP_KS_KERNEL, include/tfhe_hip.h):
+    // AUTO picks per batch size, anything else runs that kernel at every batch size.
+    int br_force = 0;  // BrKind + 1, 0 = auto
+    int ks_force = 0;  // KsKind + 1, 0 = auto
+    // crossovers of the automatic choice, in ciphertexts; set from the CU count at creation.  Numeric overrides exist
+    // only in -DTFHE_EXPERIMENT builds (profiles/exp/).
+    size_t wide_max = 256;      // blind rotate: one eight-wave workgroup per ciphertext up to this batch size
+    size_t pair_lo = 0, pair_max = 0;  // ... two ciphertexts per workgroup (k_blind_rotate_pair) for pair_lo < count <= pair_max
+    size_t ks_split_max = 256;  // key switch: coefficient walk split over 32 workgroups up to this batch size
+    size_t ks_mfma_min = 64;    // smallest batch the matrix-core kernel takes (below: the split kernel)
+    size_t ks_sl_chunk_min = 384;  // wider bases: smallest batch the column-sliced kernel takes (with K chunks; below: the split kernel)
+    int ks_sliced_sets = 0;     // 0: accumulator sets per lane picked per launch (ks_sl2_pick_sets); else forced (24..36; experiment builds)
+    int ks_mfma_ksplit = 0;     // 0: K chunks per row block picked per launch; else forced (1, 2, 4, 8, 16)
+    int ks_sl_kchunks = 0;      // 0: K chunks of the column-sliced kernel picked per launch; else forced (1 ... 64, a power of two)
+    long br_chunk = 0;  // blind-rotate workgroups per launch: 0 = whole batch (default), -1 = resident set, N = N
+    bool exp_wide1 = false;  // (experiment builds with -DTFHE_EXP_WIDE1: SINGLE runs the superseded one-wave-per-row kernel)
+    bool fast_round = false;  // |pre-rounding value| < 2^51 guaranteed (see round_to_torus<FAST>)
+  } dispatch;
   // experiment builds (profiles/exp/midsize.py): the two parts of a blind-rotation plan on TWO streams, and a forced cut
   bool exp_overlap = false;
   size_t exp_split_at = 0;
@@ -286,6 +290,10 @@ int ensure(tfhe_hip_ctx *ctx, DevBuf &b, size_t bytes) {
 struct GatePrep {
   uint32_t ca, cb, cconst;
 };
+// TFHE_HIP_COPY: the plain bootstrap of the first operand, no second one (what gate_prep(TFHE_HIP_COPY, ..) gives)
+constexpr GatePrep kCopyPrep{1u, 0u, 0u};
+// launches with per-ciphertext gate codes: placeholders, the kernel reads the codes; cb != 0 keeps in_b attached
+constexpr GatePrep kCodesPrep{1u, 1u, 0u};
 
 // src/gates.rs:54-150; constants are utils::f64_to_torus(+-0.125 / +-0.25) (utils.rs:9-12)
 bool gate_prep(int gate, GatePrep &g) {
@@ -344,7 +352,7 @@ constexpr int br_waves(const tfhe_hip_ctx *) { return kBrWaves; }
 #endif
 // many: the many-LUT instantiation (BlindRotateArgs::lut_shift / n_luts / out_fn_stride) of the same kernel
 br_kernel_t br_kernel(const tfhe_hip_ctx *ctx, bool many = false) {
-  const bool f = ctx->fast_round;
+  const bool f = ctx->dispatch.fast_round;
 #if defined(TFHE_EXPERIMENT) && defined(TFHE_EXP_L1)
   if (br_is_l1(ctx)) return many ? nullptr : f ? k_blind_rotate_l1<true> : k_blind_rotate_l1<false>;
 #endif
@@ -361,7 +369,7 @@ br_kernel_t br_kernel(const tfhe_hip_ctx *ctx, bool many = false) {
 }
 
 br_kernel_t br_pair_kernel(const tfhe_hip_ctx *ctx, bool many = false) {
-  const bool f = ctx->fast_round;
+  const bool f = ctx->dispatch.fast_round;
   if (many) switch (ctx->P.l) {
       case 1: return f ? k_blind_rotate_pair<1, true, true> : k_blind_rotate_pair<1, false, true>;
       case 2: return f ? k_blind_rotate_pair<2, true, true> : k_blind_rotate_pair<2, false, true>;
@@ -375,14 +383,14 @@ br_kernel_t br_pair_kernel(const tfhe_hip_ctx *ctx, bool many = false) {
 }
 
 br_kernel_t br_single_kernel(const tfhe_hip_ctx *ctx, bool many = false) {
-  const bool f = ctx->fast_round;
+  const bool f = ctx->dispatch.fast_round;
   if (many) switch (ctx->P.l) {
       case 1: return f ? k_blind_rotate_wide2_many<1, true> : k_blind_rotate_wide2_many<1, false>;
       case 2: return f ? k_blind_rotate_wide2_many<2, true> : k_blind_rotate_wide2_many<2, false>;
       default: return f ? k_blind_rotate_wide2_many<3, true> : k_blind_rotate_wide2_many<3, false>;
     }
 #if defined(TFHE_EXPERIMENT) && defined(TFHE_EXP_WIDE1)  // the superseded one-wave-per-row latency kernel (profiles/exp/superseded/blind_rotate_wide1.hpp)
-  if (ctx->exp_wide1) switch (ctx->P.l) {
+  if (ctx->dispatch.exp_wide1) switch (ctx->P.l) {
       case 1: return f ? k_blind_rotate_wide<1, true> : k_blind_rotate_wide<1, false>;
       case 2: return f ? k_blind_rotate_wide<2, true> : k_blind_rotate_wide<2, false>;
       default: return f ? k_blind_rotate_wide<3, true> : k_blind_rotate_wide<3, false>;
@@ -398,7 +406,7 @@ br_kernel_t br_single_kernel(const tfhe_hip_ctx *ctx, bool many = false) {
 typedef void (*ep_kernel_t)(const uint32_t *, const int32_t *, const double2 *, uint32_t, const double2 *, int,
                             uint32_t, uint32_t *);
 ep_kernel_t ep_kernel(const tfhe_hip_ctx *ctx) {
-  const bool f = ctx->fast_round;
+  const bool f = ctx->dispatch.fast_round;
   switch (ctx->P.l) {
     case 1: return f ? k_external_product<1, true> : k_external_product<1, false>;
     case 2: return f ? k_external_product<2, true> : k_external_product<2, false>;
@@ -437,16 +445,16 @@ struct BrPlan {
 BrPlan plan_blind_rotate(const tfhe_hip_ctx *ctx, size_t count) {
   BrPlan pl;
   if (count == 0) return pl;
-  if (ctx->br_force) {  // TFHE_HIP_BR_KERNEL: that kernel at every batch size
-    pl.add((BrKind)(ctx->br_force - 1), 0, count);
+  if (ctx->dispatch.br_force) {  // TFHE_HIP_BR_KERNEL: that kernel at every batch size
+    pl.add((BrKind)(ctx->dispatch.br_force - 1), 0, count);
     return pl;
   }
   // Small batches, N = #CUs (measured at 128 bit, profiles/exp/logs/r3x_pair_kernel.log, r3o_crossover.log):
   // up to N ciphertexts one workgroup each (2.2 ms); N < count <= 2N two ciphertexts per workgroup, half a step apart
   // (3.6 ms; two rounds of singles take 4.5); up to 3N the first 2N as pairs and the rest as singles (5.8; three
   // rounds of singles 6.4, pairs alone 7.3, the batch kernel 7.0 for anything up to 4N).
-  const size_t N1 = ctx->pair_lo, N2 = ctx->pair_max;
-  const bool pairs_on = N2 > N1 && ctx->wide_max >= N1;
+  const size_t N1 = ctx->dispatch.pair_lo, N2 = ctx->dispatch.pair_max;
+  const bool pairs_on = N2 > N1 && ctx->dispatch.wide_max >= N1;
   if (pairs_on && count > N1 && count <= N2) {
     pl.add(BR_PAIR, 0, count);
     return pl;
@@ -458,7 +466,7 @@ BrPlan plan_blind_rotate(const tfhe_hip_ctx *ctx, size_t count) {
     pl.add(BR_SINGLE, N2, count - N2);
     return pl;
   }
-  if (count <= ctx->wide_max) {
+  if (count <= ctx->dispatch.wide_max) {
     pl.add(BR_SINGLE, 0, count);
     return pl;
   }
@@ -468,7 +476,7 @@ BrPlan plan_blind_rotate(const tfhe_hip_ctx *ctx, size_t count) {
   // ms, 2,200: 14.4 vs 17.9, 3,300: 19.7 vs 22.9); done up to 32N, beyond which the step is a few per cent of the launch.
   // (at l = 1 a pair launch costs as much as the step it would save: tails of up to N only)
   size_t tail = 0;
-  if (pairs_on && ctx->br_chunk == 0 && count <= 32 * N1) {
+  if (pairs_on && ctx->dispatch.br_chunk == 0 && count <= 32 * N1) {
     const size_t r = count % (4 * N1);
     if (r > 0 && r <= (ctx->P.l == 1 ? N1 : N2) && count > r) tail = r;
   }
@@ -477,35 +485,48 @@ BrPlan plan_blind_rotate(const tfhe_hip_ctx *ctx, size_t count) {
   return pl;
 }
 
-int launch_blind_rotate(tfhe_hip_ctx *ctx, hipStream_t s, const uint32_t *in_a, const uint32_t *in_b,
-                        GatePrep gp, const uint32_t *testvec, int per_ct, size_t count,
-                        uint32_t *out_trlwe, uint32_t *out_lv1, uint32_t *out_ext2,
-                        const uint8_t *gate_codes = nullptr, const uint32_t *idx_a = nullptr,
-                        const uint32_t *idx_b = nullptr, int lut_shift = 0) {
+// One blind-rotation launch, described.  Everything defaults to "absent": a call site names what it sets.
+struct BrCall {
+  const uint32_t *in_a = nullptr, *in_b = nullptr;  // operand rows [count][n+1]; with idx_a / idx_b the base the indices select from
+  GatePrep gp = kCopyPrep;                          // the rotated row is ca * a + cb * b, [n] += cconst
+  const uint32_t *testvec = nullptr;                // nullptr: the key's own
+  int per_ct = 0;                                   // one test vector per ciphertext (only with `testvec`)
+  size_t count = 0;
+  // exactly one output: the rotated TRLWE [count][2][N], its extraction as the key switch's source [count][N+1], or its
+  // extraction as a TLWE of the input's shape [count][n+1] (bootstrap_without_key_switch)
+  uint32_t *out_trlwe = nullptr, *out_lv1 = nullptr, *out_ext2 = nullptr;
+  const uint8_t *gate_codes = nullptr;                  // per-ciphertext gates (gp: kCodesPrep)
+  const uint32_t *idx_a = nullptr, *idx_b = nullptr;    // row indices into in_a / in_b (circuit levels)
+  int lut_shift = 0;                                    // many-LUT: 2^lut_shift extractions per ciphertext
+};
+
+int launch_blind_rotate(tfhe_hip_ctx *ctx, hipStream_t s, const BrCall &c) {
+  const size_t count = c.count;
+  const int lut_shift = c.lut_shift;
   if (count == 0) return TFHE_HIP_OK;
   if (count > 0x7FFFFFFFull) return fail(ctx, TFHE_HIP_EINVAL, "count too large");
   // many-LUT (lut_shift > 0): 2^lut_shift extractions per ciphertext, function-major [2^lut_shift][count] rows
   if (lut_shift < 0 || lut_shift > 3) return fail(ctx, TFHE_HIP_EINVAL, "n_luts must be 1, 2, 4 or 8");
   if (((size_t)count << lut_shift) > 0x7FFFFFFFull) return fail(ctx, TFHE_HIP_EINVAL, "n_luts * count too large");
   BlindRotateArgs A;
-  A.in_a = in_a;
-  A.in_b = gp.cb ? in_b : nullptr;
-  A.ca = gp.ca;
-  A.cb = gp.cb;
-  A.cconst = gp.cconst;
-  A.gate_codes = gate_codes;
-  A.idx_a = idx_a;  // row indices (circuit levels): the operand bases stay, the indices are sliced per part
-  A.idx_b = idx_b;
-  A.testvec = testvec ? testvec : ctx->K->d_testvec;
-  A.per_ct_stride = (testvec && per_ct) ? (size_t)2 * kN : 0;
+  A.in_a = c.in_a;
+  A.in_b = c.gp.cb ? c.in_b : nullptr;
+  A.ca = c.gp.ca;
+  A.cb = c.gp.cb;
+  A.cconst = c.gp.cconst;
+  A.gate_codes = c.gate_codes;
+  A.idx_a = c.idx_a;  // row indices (circuit levels): the operand bases stay, the indices are sliced per part
+  A.idx_b = c.idx_b;
+  A.testvec = c.testvec ? c.testvec : ctx->K->d_testvec;
+  A.per_ct_stride = (c.testvec && c.per_ct) ? (size_t)2 * kN : 0;
   A.bsk = ctx->K->d_bsk;
   A.tw = ctx->d_tw;
   A.n = ctx->P.n;
   A.bgbit = ctx->P.bgbit;
   A.offset = ctx->K->offset;
-  A.out_trlwe = out_trlwe;
-  A.out_lv1 = out_lv1;
-  A.out_ext2 = out_ext2;
+  A.out_trlwe = c.out_trlwe;
+  A.out_lv1 = c.out_lv1;
+  A.out_ext2 = c.out_ext2;
   A.count = count;
   A.lut_shift = lut_shift;
   A.n_luts = 1 << lut_shift;
@@ -518,9 +539,9 @@ int launch_blind_rotate(tfhe_hip_ctx *ctx, hipStream_t s, const uint32_t *in_a, 
   A.err_flag = reinterpret_cast<uint32_t *>(ctx->d_diag + 2);
   // sample_extract_index_2 reads a[n - i] of an N-coefficient polynomial (trlwe.rs:122-136): the reference
   // indexes out of bounds (panics) for n > N; refuse instead of reading the b half of the accumulator
-  if (out_ext2 && ctx->P.n > kN)
+  if (c.out_ext2 && ctx->P.n > kN)
     return fail(ctx, TFHE_HIP_EINVAL, "bootstrap without key switch needs n <= N (sample_extract_index_2)");
-  if (gp.cb && !in_b) return fail(ctx, TFHE_HIP_EINVAL, "second gate operand is NULL");
+  if (c.gp.cb && !c.in_b) return fail(ctx, TFHE_HIP_EINVAL, "second gate operand is NULL");
   // ciphertexts [done, done + m) of this call as a launch of their own
   auto part = [&](size_t done, size_t m) {
     BlindRotateArgs S = A;
@@ -568,7 +589,7 @@ int launch_blind_rotate(tfhe_hip_ctx *ctx, hipStream_t s, const uint32_t *in_a, 
                  part(begin, m_all)));
     } else if (pl.kind[q] == BR_SINGLE) {
 #if defined(TFHE_EXPERIMENT) && defined(TFHE_EXP_WIDE1)
-      if (ctx->exp_wide1) {
+      if (ctx->dispatch.exp_wide1) {
         if (lut_shift) return fail(ctx, TFHE_HIP_EINVAL, "the one-wave-per-row experiment kernel has no many-LUT epilogue");
         CHK(launch(br_single_kernel(ctx), (unsigned)m_all, 128u * (unsigned)ctx->P.l,
                    blind_rotate_wide_lds_bytes(ctx->P.n, ctx->P.l), part(begin, m_all)));
@@ -584,13 +605,13 @@ int launch_blind_rotate(tfhe_hip_ctx *ctx, hipStream_t s, const uint32_t *in_a, 
       // -1: the resident set -- the round-1 remedy for free-running one-wave workgroups.)
       const size_t lds = br_lds_bytes(ctx);
       size_t chunk = m_all;
-      if (ctx->br_chunk > 0) chunk = (size_t)ctx->br_chunk;
-      if (ctx->br_chunk < 0) {
+      if (ctx->dispatch.br_chunk > 0) chunk = (size_t)ctx->dispatch.br_chunk;
+      if (ctx->dispatch.br_chunk < 0) {
         int per_cu = 0;
         const hipError_t e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, br_kernel(ctx), 64 * br_waves(ctx), lds);
         if (e == hipSuccess && per_cu > 0 && ctx->num_cus > 0) chunk = (size_t)per_cu * ctx->num_cus * br_waves(ctx);
       }
-      if (ctx->br_chunk == 0 && m_all >= 2 * kYieldChunk && comb_interactive(ctx)) chunk = kYieldChunk;
+      if (ctx->dispatch.br_chunk == 0 && m_all >= 2 * kYieldChunk && comb_interactive(ctx)) chunk = kYieldChunk;
       if (chunk == 0 || chunk > m_all) chunk = m_all;
       for (size_t done = 0; done < m_all; done += chunk) {
         const size_t m = (m_all - done < chunk) ? m_all - done : chunk;
@@ -709,7 +730,7 @@ KsPlan plan_key_switch(const tfhe_hip_ctx *ctx, size_t count) {
   const tfhe_hip_params &P = ctx->P;
   const int n = P.n;
   KsPlan pl;
-  const bool forced = ctx->ks_force != 0;
+  const bool forced = ctx->dispatch.ks_force != 0;
   // base-4 sets from 64 ciphertexts up: the matrix-core kernel, its walk over K cut into chunks while the batch is
   // too small to fill the chip with row blocks (0.10 / 0.11 / 0.15 / 0.18 / 0.25 / 0.40 ms at 64 / 256 / 512 / 1,024 /
   // 2,048 / 4,096 ciphertexts; the split kernel takes 0.12 / 0.33 / 0.55 / 0.97 / 1.8 / 3.6, the matrix-core kernel
@@ -718,11 +739,11 @@ KsPlan plan_key_switch(const tfhe_hip_ctx *ctx, size_t count) {
   // (SECURITY_UINT4: 0.37 / 0.37 / 0.57 / 1.05 ms at 512 / 1,024 / 2,048 / 4,096 ciphertexts where the split kernel
   // takes 0.46 / 0.85 / 1.62 / 3.42 and wins below: 0.27 vs 0.29 at 256 -- profiles/exp/logs/r3_ks_sl_chunks.log).
   // Smaller batches, and whatever neither LDS kernel covers, up to ks_split_max: the split kernel.
-  if (forced) pl.kind = (KsKind)(ctx->ks_force - 1);
-  else if (ctx->K->d_ksk8 && count >= ctx->ks_mfma_min) pl.kind = KS_MFMA;
+  if (forced) pl.kind = (KsKind)(ctx->dispatch.ks_force - 1);
+  else if (ctx->K->d_ksk8 && count >= ctx->dispatch.ks_mfma_min) pl.kind = KS_MFMA;
   else {
     const bool sliced_ok = ks_sliced_fits(P);
-    if (count <= ctx->ks_split_max && !(sliced_ok && count >= ctx->ks_sl_chunk_min)) pl.kind = KS_SPLIT;
+    if (count <= ctx->dispatch.ks_split_max && !(sliced_ok && count >= ctx->dispatch.ks_sl_chunk_min)) pl.kind = KS_SPLIT;
     else if (sliced_ok) pl.kind = KS_SLICED;
     else if (ks_b4_fits(P)) pl.kind = KS_B4;
     else pl.kind = KS_GENERIC;
@@ -735,7 +756,7 @@ KsPlan plan_key_switch(const tfhe_hip_ctx *ctx, size_t count) {
     const size_t ncb = (size_t)(tiles < kKmColBlocks ? tiles : kKmColBlocks);
     int ksplit = 1;
     while (ksplit < 16 && rb * ncb * 4 * (size_t)ksplit < 2 * (size_t)ctx->num_cus) ksplit *= 2;
-    if (ctx->ks_mfma_ksplit) ksplit = ctx->ks_mfma_ksplit;
+    if (ctx->dispatch.ks_mfma_ksplit) ksplit = ctx->dispatch.ks_mfma_ksplit;
     pl.kparts = ksplit;
     pl.atomics = true;
   } else if (pl.kind == KS_SLICED) {
@@ -747,14 +768,14 @@ KsPlan plan_key_switch(const tfhe_hip_ctx *ctx, size_t count) {
     const int by_waves = 8 / ks_sl2_waves(P.basebit), by_lds = 2 * ks_sl2_lds_bytes(P.basebit, 36, rp) <= 160 * 1024 ? 2 : 1;
     const int per_cu = by_waves < by_lds ? by_waves : by_lds;
     int sets = ks_sl2_pick_sets(P.basebit, in_launch, slices, per_cu * ctx->num_cus);
-    if (ctx->ks_sliced_sets) sets = ctx->ks_sliced_sets;
+    if (ctx->dispatch.ks_sliced_sets) sets = ctx->dispatch.ks_sliced_sets;
     // small batches have few ciphertext groups: the walk over the N * t groups is cut into up to 64 chunks (grid.z)
     // so that about two workgroups per CU exist; the chunks meet in the zeroed output through integer atomics.
     // A chunk is whole rings (2 * rp groups).
     const size_t groups = (in_launch + (size_t)ks_sl2_cts(P.basebit, sets) - 1) / (size_t)ks_sl2_cts(P.basebit, sets);
     int kchunks = 1;
     while (kchunks < 64 && groups * (size_t)slices * (size_t)kchunks < 2 * (size_t)ctx->num_cus) kchunks *= 2;
-    if (ctx->ks_sl_kchunks) kchunks = ctx->ks_sl_kchunks;
+    if (ctx->dispatch.ks_sl_kchunks) kchunks = ctx->dispatch.ks_sl_kchunks;
     while (kchunks > 1 && (kN * P.t / kchunks) % (2 * rp) != 0) kchunks /= 2;
     pl.sets = sets;
     pl.kparts = kchunks;
@@ -768,7 +789,7 @@ KsPlan plan_key_switch(const tfhe_hip_ctx *ctx, size_t count) {
 
 // (re)build the byte planes from the u32 engine key; called wherever a key becomes current
 int build_ksk_planes(tfhe_hip_ctx *ctx) {
-  if (!ks_mfma_possible(ctx->P) || (ctx->ks_force && ctx->ks_force - 1 != KS_MFMA)) return TFHE_HIP_OK;
+  if (!ks_mfma_possible(ctx->P) || (ctx->dispatch.ks_force && ctx->dispatch.ks_force - 1 != KS_MFMA)) return TFHE_HIP_OK;
   const tfhe_hip_params &P = ctx->P;
   const size_t bytes = ks_mfma_key_bytes(P.n, P.t);
   if (!ctx->K->d_ksk8) HIPCHK(ctx, hipMalloc((void **)&ctx->K->d_ksk8, bytes + kKmKeyTailPad));
@@ -893,83 +914,44 @@ int claim_scratch(tfhe_hip_ctx *ctx, hipStream_t s) {
 
 // ---- device-pointer implementations (mutex held by caller) -------------------
 
+// sizes of the operands the entry points name: `count` TLWE rows [n+1], TRLWE [2][N], level-1 rows [N+1] in the whole
+// 256-row groups the matrix-core key switch reads, and a test vector (one per ciphertext, or one for the call)
+size_t tlwe_bytes(const tfhe_hip_ctx *ctx, size_t count) { return count * (size_t)(ctx->P.n + 1) * 4; }
+size_t trlwe_bytes(size_t count) { return count * (size_t)2 * kN * 4; }
+size_t lv1_bytes(size_t count) { return lv1_rows(count) * (size_t)(kN + 1) * 4; }
+size_t testvec_bytes(int per_ct, size_t count) { return trlwe_bytes(per_ct ? count : 1); }
+
+// A bootstrap on stream `s`: the blind rotation `call` describes (everything but its output), then, with `keyswitch`,
+// the key switch of its count << lut_shift extracted rows into `out`; without, the rows are extracted straight into
+// `out` (bootstrap_without_key_switch).  The one place that takes the context's lv1 scratch for a blind rotation.
+int run_bootstrap(tfhe_hip_ctx *ctx, hipStream_t s, BrCall call, uint32_t *out, bool keyswitch) {
+  if (!keyswitch) {
+    call.out_ext2 = out;
+    return launch_blind_rotate(ctx, s, call);
+  }
+  const size_t rows = call.count << call.lut_shift;
+  CHK(claim_scratch(ctx, s));
+  CHK(ensure(ctx, ctx->lv1, lv1_bytes(rows)));
+  call.out_lv1 = (uint32_t *)ctx->lv1.p;
+  CHK(launch_blind_rotate(ctx, s, call));
+  return launch_key_switch(ctx, s, call.out_lv1, out, rows);
+}
+
 int gate_dev(tfhe_hip_ctx *ctx, int gate, const uint32_t *a, const uint32_t *b, uint32_t *out,
              size_t count, hipStream_t s) {
   GatePrep gp;
   if (!gate_prep(gate, gp)) return fail(ctx, TFHE_HIP_EINVAL, "unknown gate");
-  CHK(claim_scratch(ctx, s));
-  CHK(ensure(ctx, ctx->lv1, lv1_rows(count) * (size_t)(kN + 1) * 4));
-  CHK(launch_blind_rotate(ctx, s, a, b, gp, nullptr, 0, count, nullptr, (uint32_t *)ctx->lv1.p, nullptr));
-  return launch_key_switch(ctx, s, (const uint32_t *)ctx->lv1.p, out, count);
-}
-
-int gates_mixed_dev(tfhe_hip_ctx *ctx, const uint8_t *gates, const uint32_t *a, const uint32_t *b, uint32_t *out,
-                    size_t count, hipStream_t s) {
-  GatePrep gp{1u, 1u, 0u};  // placeholders; cb != 0 keeps in_b attached, the kernel reads the codes
-  CHK(claim_scratch(ctx, s));
-  CHK(ensure(ctx, ctx->lv1, lv1_rows(count) * (size_t)(kN + 1) * 4));
-  CHK(launch_blind_rotate(ctx, s, a, b, gp, nullptr, 0, count, nullptr, (uint32_t *)ctx->lv1.p, nullptr, gates));
-  return launch_key_switch(ctx, s, (const uint32_t *)ctx->lv1.p, out, count);
+  return run_bootstrap(ctx, s, {.in_a = a, .in_b = b, .gp = gp, .count = count}, out, true);
 }
 
 // proxy_reenc::reencrypt_tlwe_lv0 (proxy_reenc.rs:468-510): pad to the key switch's source shape, then the key switch
 int reencrypt_dev(tfhe_hip_ctx *ctx, const uint32_t *in, uint32_t *out, size_t count, hipStream_t s) {
   if (count == 0) return TFHE_HIP_OK;
   CHK(claim_scratch(ctx, s));
-  CHK(ensure(ctx, ctx->lv1, lv1_rows(count) * (size_t)(kN + 1) * 4));
+  CHK(ensure(ctx, ctx->lv1, lv1_bytes(count)));
   hipLaunchKernelGGL(k_reenc_pad, dim3((unsigned)count), dim3(256), 0, s, in, (uint32_t *)ctx->lv1.p, ctx->P.n);
   HIPCHK(ctx, hipGetLastError());
   return launch_key_switch(ctx, s, (const uint32_t *)ctx->lv1.p, out, count);
-}
-
-// per-ciphertext gates, bootstrap_without_key_switch outputs (the first level of Gates::mux, gates.rs:165-177)
-int gates_mixed_nks_dev(tfhe_hip_ctx *ctx, const uint8_t *gates, const uint32_t *a, const uint32_t *b, uint32_t *out,
-                        size_t count, hipStream_t s) {
-  GatePrep gp{1u, 1u, 0u};
-  return launch_blind_rotate(ctx, s, a, b, gp, nullptr, 0, count, nullptr, nullptr, out, gates);
-}
-
-int bootstrap_dev(tfhe_hip_ctx *ctx, const uint32_t *in, const uint32_t *testvec, int per_ct,
-                  int keyswitch, uint32_t *out, size_t count, hipStream_t s) {
-  GatePrep gp;
-  gate_prep(TFHE_HIP_COPY, gp);
-  if (keyswitch) {
-    CHK(claim_scratch(ctx, s));
-    CHK(ensure(ctx, ctx->lv1, lv1_rows(count) * (size_t)(kN + 1) * 4));
-    CHK(launch_blind_rotate(ctx, s, in, nullptr, gp, testvec, per_ct, count, nullptr,
-                            (uint32_t *)ctx->lv1.p, nullptr));
-    return launch_key_switch(ctx, s, (const uint32_t *)ctx->lv1.p, out, count);
-  }
-  return launch_blind_rotate(ctx, s, in, nullptr, gp, testvec, per_ct, count, nullptr, nullptr, out);
-}
-
-int lincomb_bootstrap_dev(tfhe_hip_ctx *ctx, GatePrep gp, const uint32_t *a, const uint32_t *b,
-                          const uint32_t *testvec, int per_ct, int keyswitch, uint32_t *out, size_t count,
-                          hipStream_t s) {
-  if (keyswitch) {
-    CHK(claim_scratch(ctx, s));
-    CHK(ensure(ctx, ctx->lv1, lv1_rows(count) * (size_t)(kN + 1) * 4));
-    CHK(launch_blind_rotate(ctx, s, a, b, gp, testvec, per_ct, count, nullptr, (uint32_t *)ctx->lv1.p, nullptr));
-    return launch_key_switch(ctx, s, (const uint32_t *)ctx->lv1.p, out, count);
-  }
-  return launch_blind_rotate(ctx, s, a, b, gp, testvec, per_ct, count, nullptr, nullptr, out);
-}
-
-// Many-LUT bootstrap (PBS-manyLUT): ONE blind rotation per ciphertext with the rotation amounts rounded to multiples of
-// 2^lut_shift, then 2^lut_shift sample extractions (function-major into lv1 or out) and one key switch over all rows.
-int lincomb_bootstrap_many_dev(tfhe_hip_ctx *ctx, GatePrep gp, const uint32_t *a, const uint32_t *b,
-                               const uint32_t *testvec, int per_ct, int lut_shift, int keyswitch, uint32_t *out,
-                               size_t count, hipStream_t s) {
-  const size_t rows = count << lut_shift;
-  if (keyswitch) {
-    CHK(claim_scratch(ctx, s));
-    CHK(ensure(ctx, ctx->lv1, lv1_rows(rows) * (size_t)(kN + 1) * 4));
-    CHK(launch_blind_rotate(ctx, s, a, b, gp, testvec, per_ct, count, nullptr, (uint32_t *)ctx->lv1.p, nullptr, nullptr,
-                            nullptr, nullptr, lut_shift));
-    return launch_key_switch(ctx, s, (const uint32_t *)ctx->lv1.p, out, rows);
-  }
-  return launch_blind_rotate(ctx, s, a, b, gp, testvec, per_ct, count, nullptr, nullptr, out, nullptr, nullptr, nullptr,
-                             lut_shift);
 }
 
 // n_luts in {1, 2, 4, 8} -> log2, else -1
@@ -983,16 +965,17 @@ int lut_shift_of(int n_luts) {
   }
 }
 
-// the checks of the many-LUT entry points, in one order for the host, device and pool forms
-int many_checks(tfhe_hip_ctx *ctx, const uint32_t *a, uint32_t cb, const uint32_t *b, const uint32_t *testvec,
-                int n_luts, const uint32_t *out, size_t count) {
+// the checks of the many-LUT entry points, in one order for the host, device and pool forms: why the call is
+// TFHE_HIP_EINVAL, or nullptr (the context forms file the text under the context, the pool forms under the pool)
+const char *many_refusal(const uint32_t *a, uint32_t cb, const uint32_t *b, const uint32_t *testvec, int n_luts,
+                         const uint32_t *out, size_t count) {
   const int shift = lut_shift_of(n_luts);
-  if (shift < 0) return fail(ctx, TFHE_HIP_EINVAL, "n_luts must be 1, 2, 4 or 8");
-  if (!testvec) return fail(ctx, TFHE_HIP_EINVAL, "many-LUT bootstrap needs a test vector");
-  if (cb && !b) return fail(ctx, TFHE_HIP_EINVAL, "null pointer");
-  if (count && (!a || !out)) return fail(ctx, TFHE_HIP_EINVAL, "null pointer");
-  if ((count << shift) > 0x7FFFFFFFull || count > 0x7FFFFFFFull) return fail(ctx, TFHE_HIP_EINVAL, "n_luts * count too large");
-  return TFHE_HIP_OK;
+  if (shift < 0) return "n_luts must be 1, 2, 4 or 8";
+  if (!testvec) return "many-LUT bootstrap needs a test vector";
+  if (cb && !b) return "null pointer";
+  if (count && (!a || !out)) return "null pointer";
+  if ((count << shift) > 0x7FFFFFFFull || count > 0x7FFFFFFFull) return "n_luts * count too large";
+  return nullptr;
 }
 
 int lincomb_dev(tfhe_hip_ctx *ctx, GatePrep gp, const uint32_t *a, const uint32_t *b, uint32_t *out, size_t count,
@@ -1007,23 +990,21 @@ int lincomb_dev(tfhe_hip_ctx *ctx, GatePrep gp, const uint32_t *a, const uint32_
 
 int mux_dev(tfhe_hip_ctx *ctx, int naive, const uint32_t *a, const uint32_t *b, const uint32_t *c,
             uint32_t *out, size_t count, hipStream_t s) {
-  const size_t ctb = count * (size_t)(ctx->P.n + 1) * 4;
   CHK(claim_scratch(ctx, s));
-  CHK(ensure(ctx, ctx->u1, ctb));
-  CHK(ensure(ctx, ctx->u2, ctb));
+  CHK(ensure(ctx, ctx->u1, tlwe_bytes(ctx, count)));
+  CHK(ensure(ctx, ctx->u2, tlwe_bytes(ctx, count)));
   uint32_t *u1 = (uint32_t *)ctx->u1.p, *u2 = (uint32_t *)ctx->u2.p;
-  GatePrep g_and, g_andny, g_or;
+  GatePrep g_and, g_andny;
   gate_prep(TFHE_HIP_AND, g_and);
   gate_prep(TFHE_HIP_ANDNY, g_andny);  // and(not(a), c) = -a + c - 1/8  (gates.rs:172-175, 196-197)
-  gate_prep(TFHE_HIP_OR, g_or);
   if (naive) {  // gates.rs:189-199
     CHK(gate_dev(ctx, TFHE_HIP_AND, a, b, u1, count, s));
     CHK(gate_dev(ctx, TFHE_HIP_ANDNY, a, c, u2, count, s));
     return gate_dev(ctx, TFHE_HIP_OR, u1, u2, out, count, s);
   }
   // gates.rs:157-183: two bootstrap_without_key_switch, add, one full bootstrap
-  CHK(launch_blind_rotate(ctx, s, a, b, g_and, nullptr, 0, count, nullptr, nullptr, u1));
-  CHK(launch_blind_rotate(ctx, s, a, c, g_andny, nullptr, 0, count, nullptr, nullptr, u2));
+  CHK(run_bootstrap(ctx, s, {.in_a = a, .in_b = b, .gp = g_and, .count = count}, u1, false));
+  CHK(run_bootstrap(ctx, s, {.in_a = a, .in_b = c, .gp = g_andny, .count = count}, u2, false));
   return gate_dev(ctx, TFHE_HIP_OR, u1, u2, out, count, s);
 }
 
@@ -1281,41 +1262,41 @@ int tfhe_hip_ctx_create(const tfhe_hip_params *p, int device, tfhe_hip_ctx **out
   ctx->num_cus = prop.multiProcessorCount;
   const size_t combine_max = combine_env >= 0 ? (size_t)combine_env : 2 * (size_t)ctx->num_cus;
   // pre-rounding magnitude bound: 2l polynomials x N terms x (Bg/2) digit x 2^31 key coefficient
-  ctx->fast_round = std::log2(2.0 * p->l) + 10.0 + (p->bgbit - 1) + 31.0 < 51.0;
+  ctx->dispatch.fast_round = std::log2(2.0 * p->l) + 10.0 + (p->bgbit - 1) + 31.0 < 51.0;
   // crossovers of the automatic dispatch, measured on the 256-CU part and kept as multiples of the CU count:
   // key switch vs the group kernels ~7.8k ciphertexts (base 4, LDS ring), ~4.1k (column-sliced); blind rotation vs the
   // batch kernel (7.0 ms for anything up to 1,024 ciphertexts at 128 bit): the eight-wave form takes 2.2 / 4.5 / 6.6 /
   // 8.5 ms for 1 / 2 / 3 / 4 rounds of one workgroup per CU (profiles/exp/logs/r3o_crossover.log) -- three rounds only
   // at l = 3: at l = 1, 2 the batch kernel's first step (4.3 / 5.4 ms) is cheaper than three rounds of singles (6.2 ms)
-  ctx->ks_split_max = (p->basebit == 2 ? 28 : 16) * (size_t)ctx->num_cus;
-  ctx->wide_max = (p->l >= 3 ? 3 : 2) * (size_t)ctx->num_cus;
-  ctx->pair_lo = (size_t)ctx->num_cus;
-  ctx->pair_max = 2 * (size_t)ctx->num_cus;
-  if (blind_rotate_pair_lds_bytes(p->n) > 160 * 1024) ctx->pair_max = 0;  // (n > 1,900: no parameter set)
-  ctx->br_force = br_force;
-  ctx->ks_force = ks_force;
+  ctx->dispatch.ks_split_max = (p->basebit == 2 ? 28 : 16) * (size_t)ctx->num_cus;
+  ctx->dispatch.wide_max = (p->l >= 3 ? 3 : 2) * (size_t)ctx->num_cus;
+  ctx->dispatch.pair_lo = (size_t)ctx->num_cus;
+  ctx->dispatch.pair_max = 2 * (size_t)ctx->num_cus;
+  if (blind_rotate_pair_lds_bytes(p->n) > 160 * 1024) ctx->dispatch.pair_max = 0;  // (n > 1,900: no parameter set)
+  ctx->dispatch.br_force = br_force;
+  ctx->dispatch.ks_force = ks_force;
 #ifdef TFHE_EXPERIMENT
   // Numeric overrides of the crossovers and of the per-launch choices: experiment builds only (profiles/exp/).
-  if (const char *env = getenv("TFHE_HIP_FAST_ROUND")) ctx->fast_round = ctx->fast_round && atoi(env) != 0;
+  if (const char *env = getenv("TFHE_HIP_FAST_ROUND")) ctx->dispatch.fast_round = ctx->dispatch.fast_round && atoi(env) != 0;
   if (const char *env = getenv("TFHE_HIP_KS_SLICED_SETS")) {
     const int v = atoi(env);
-    ctx->ks_sliced_sets = (v == 24 || v == 28 || v == 32 || v == 36) ? v : 0;
+    ctx->dispatch.ks_sliced_sets = (v == 24 || v == 28 || v == 32 || v == 36) ? v : 0;
   }
-  if (const char *env = getenv("TFHE_HIP_KS_MFMA_MIN")) ctx->ks_mfma_min = (size_t)atol(env);
-  if (const char *env = getenv("TFHE_HIP_KS_SL_CHUNK_MIN")) ctx->ks_sl_chunk_min = (size_t)atol(env);
+  if (const char *env = getenv("TFHE_HIP_KS_MFMA_MIN")) ctx->dispatch.ks_mfma_min = (size_t)atol(env);
+  if (const char *env = getenv("TFHE_HIP_KS_SL_CHUNK_MIN")) ctx->dispatch.ks_sl_chunk_min = (size_t)atol(env);
   if (const char *env = getenv("TFHE_HIP_KS_SL_KCHUNKS")) {
     const int v = atoi(env);
-    ctx->ks_sl_kchunks = (v >= 1 && v <= 64 && (v & (v - 1)) == 0) ? v : 0;
+    ctx->dispatch.ks_sl_kchunks = (v >= 1 && v <= 64 && (v & (v - 1)) == 0) ? v : 0;
   }
   if (const char *env = getenv("TFHE_HIP_KS_MFMA_KSPLIT")) {
     const int v = atoi(env);
-    ctx->ks_mfma_ksplit = (v == 1 || v == 2 || v == 4 || v == 8 || v == 16) ? v : 0;
+    ctx->dispatch.ks_mfma_ksplit = (v == 1 || v == 2 || v == 4 || v == 8 || v == 16) ? v : 0;
   }
-  if (const char *env = getenv("TFHE_HIP_WIDE_MAX")) ctx->wide_max = (size_t)atol(env);
-  if (const char *env = getenv("TFHE_HIP_PAIR_LO")) ctx->pair_lo = (size_t)atol(env);
-  if (const char *env = getenv("TFHE_HIP_PAIR_MAX")) ctx->pair_max = (size_t)atol(env);
-  if (const char *env = getenv("TFHE_HIP_KS_SPLIT_MAX")) ctx->ks_split_max = (size_t)atol(env);
-  if (const char *env = getenv("TFHE_HIP_BR_CHUNK")) ctx->br_chunk = atol(env);
+  if (const char *env = getenv("TFHE_HIP_WIDE_MAX")) ctx->dispatch.wide_max = (size_t)atol(env);
+  if (const char *env = getenv("TFHE_HIP_PAIR_LO")) ctx->dispatch.pair_lo = (size_t)atol(env);
+  if (const char *env = getenv("TFHE_HIP_PAIR_MAX")) ctx->dispatch.pair_max = (size_t)atol(env);
+  if (const char *env = getenv("TFHE_HIP_KS_SPLIT_MAX")) ctx->dispatch.ks_split_max = (size_t)atol(env);
+  if (const char *env = getenv("TFHE_HIP_BR_CHUNK")) ctx->dispatch.br_chunk = atol(env);
   if (const char *env = getenv("TFHE_HIP_BR_OVERLAP")) ctx->exp_overlap = atoi(env) != 0;
   if (const char *env = getenv("TFHE_HIP_BR_SPLIT")) {  // "<at>:<kind0>:<kind1>", kinds 0 batch / 1 single / 2 pair
     unsigned long at = 0;
@@ -1332,7 +1313,7 @@ int tfhe_hip_ctx_create(const tfhe_hip_params *p, int device, tfhe_hip_ctx **out
     (void)hipEventCreateWithFlags(&ctx->exp_ev[1], hipEventDisableTiming);
   }
 #ifdef TFHE_EXP_WIDE1
-  if (const char *env = getenv("TFHE_HIP_BR_WIDE2")) ctx->exp_wide1 = atoi(env) == 0;
+  if (const char *env = getenv("TFHE_HIP_BR_WIDE2")) ctx->dispatch.exp_wide1 = atoi(env) == 0;
 #endif
 #endif
   // Dynamic LDS above the 64 KiB default.  The attribute belongs to the (kernel, device), not to the context, and
@@ -1349,14 +1330,14 @@ int tfhe_hip_ctx_create(const tfhe_hip_params *p, int device, tfhe_hip_ctx **out
       return bail("hipFuncSetAttribute(k_blind_rotate)", e);
     if ((e = set_lds((const void *)br_single_kernel(ctx), blind_rotate_wide2_lds_bytes(kMaxN, p->l))) != hipSuccess)
       return bail("hipFuncSetAttribute(k_blind_rotate_wide2)", e);
-    if (ctx->pair_max && (e = set_lds((const void *)br_pair_kernel(ctx), blind_rotate_pair_lds_bytes(kMaxN))) != hipSuccess)
+    if (ctx->dispatch.pair_max && (e = set_lds((const void *)br_pair_kernel(ctx), blind_rotate_pair_lds_bytes(kMaxN))) != hipSuccess)
       return bail("hipFuncSetAttribute(k_blind_rotate_pair)", e);
     // the many-LUT instantiations of the three kernels (same LDS layouts)
     if (!br_is_l1(ctx) && (e = set_lds((const void *)br_kernel(ctx, true), blind_rotate_lds_bytes(kMaxN))) != hipSuccess)
       return bail("hipFuncSetAttribute(k_blind_rotate_many)", e);
     if ((e = set_lds((const void *)br_single_kernel(ctx, true), blind_rotate_wide2_lds_bytes(kMaxN, p->l))) != hipSuccess)
       return bail("hipFuncSetAttribute(k_blind_rotate_wide2_many)", e);
-    if (ctx->pair_max && (e = set_lds((const void *)br_pair_kernel(ctx, true), blind_rotate_pair_lds_bytes(kMaxN))) != hipSuccess)
+    if (ctx->dispatch.pair_max && (e = set_lds((const void *)br_pair_kernel(ctx, true), blind_rotate_pair_lds_bytes(kMaxN))) != hipSuccess)
       return bail("hipFuncSetAttribute(k_blind_rotate_pair_many)", e);
     if (ks_sliced_fits(*p))
       for (int sets : {24, 28, 32, 36})
@@ -1369,10 +1350,10 @@ int tfhe_hip_ctx_create(const tfhe_hip_params *p, int device, tfhe_hip_ctx **out
     }
 #if defined(TFHE_EXPERIMENT) && defined(TFHE_EXP_WIDE1)
     {
-      const bool keep = ctx->exp_wide1;
-      ctx->exp_wide1 = true;
+      const bool keep = ctx->dispatch.exp_wide1;
+      ctx->dispatch.exp_wide1 = true;
       (void)set_lds((const void *)br_single_kernel(ctx), blind_rotate_wide_lds_bytes(kMaxN, p->l));
-      ctx->exp_wide1 = keep;
+      ctx->dispatch.exp_wide1 = keep;
     }
 #endif
   }
@@ -1520,7 +1501,7 @@ int tfhe_hip_load_cloud_key(tfhe_hip_ctx *ctx, const double *bsk, const uint32_t
   HIPCHK(ctx, hipMalloc((void **)&d_ref, bsk_bytes));
   hipError_t e = hipMemcpyAsync(d_ref, bsk, bsk_bytes, hipMemcpyHostToDevice, ctx->stream);
   if (e == hipSuccess) {
-    hipLaunchKernelGGL(k_bsk_convert, dim3((unsigned)polys), dim3(512), 0, ctx->stream, d_ref, ctx->K->d_bsk, polys, key_scale(ctx->fast_round));
+    hipLaunchKernelGGL(k_bsk_convert, dim3((unsigned)polys), dim3(512), 0, ctx->stream, d_ref, ctx->K->d_bsk, polys, key_scale(ctx->dispatch.fast_round));
     e = hipGetLastError();
   }
   if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
@@ -1594,9 +1575,9 @@ int gen_cloud_key_locked(tfhe_hip_ctx *ctx, const uint32_t *key_lv0, const uint3
   const ChaChaKey *d_rk = (const ChaChaKey *)ctx->idx.dev.p;
   const dim3 bgrid((unsigned)(P.n * 2 * P.l));
   switch (P.l) {
-    case 1: hipLaunchKernelGGL(k_gen_bsk<1>, bgrid, dim3(64), kStageLdsBytes, ctx->stream, d_k0, d_spec, ctx->d_tw, ctx->K->d_bsk, P.bgbit, alpha_bsk, d_rk, key_scale(ctx->fast_round)); break;
-    case 2: hipLaunchKernelGGL(k_gen_bsk<2>, bgrid, dim3(64), kStageLdsBytes, ctx->stream, d_k0, d_spec, ctx->d_tw, ctx->K->d_bsk, P.bgbit, alpha_bsk, d_rk, key_scale(ctx->fast_round)); break;
-    default: hipLaunchKernelGGL(k_gen_bsk<3>, bgrid, dim3(64), kStageLdsBytes, ctx->stream, d_k0, d_spec, ctx->d_tw, ctx->K->d_bsk, P.bgbit, alpha_bsk, d_rk, key_scale(ctx->fast_round)); break;
+    case 1: hipLaunchKernelGGL(k_gen_bsk<1>, bgrid, dim3(64), kStageLdsBytes, ctx->stream, d_k0, d_spec, ctx->d_tw, ctx->K->d_bsk, P.bgbit, alpha_bsk, d_rk, key_scale(ctx->dispatch.fast_round)); break;
+    case 2: hipLaunchKernelGGL(k_gen_bsk<2>, bgrid, dim3(64), kStageLdsBytes, ctx->stream, d_k0, d_spec, ctx->d_tw, ctx->K->d_bsk, P.bgbit, alpha_bsk, d_rk, key_scale(ctx->dispatch.fast_round)); break;
+    default: hipLaunchKernelGGL(k_gen_bsk<3>, bgrid, dim3(64), kStageLdsBytes, ctx->stream, d_k0, d_spec, ctx->d_tw, ctx->K->d_bsk, P.bgbit, alpha_bsk, d_rk, key_scale(ctx->dispatch.fast_round)); break;
   }
   HIPCHK(ctx, hipGetLastError());
   hipLaunchKernelGGL(k_gen_ksk, dim3((unsigned)((size_t)kN * P.t * base)), dim3(256), 0, ctx->stream, d_k0, d_k1,
@@ -1685,7 +1666,7 @@ int tfhe_hip_export_cloud_key(tfhe_hip_ctx *ctx, double *bsk, uint32_t *ksk, uin
   if (bsk) {
     const size_t polys = (size_t)P.n * 2 * P.l * 2;
     CHK(ensure(ctx, ctx->out.dev, polys * kN * sizeof(double)));
-    hipLaunchKernelGGL(k_bsk_export, dim3((unsigned)polys), dim3(512), 0, ctx->stream, ctx->K->d_bsk, (double *)ctx->out.dev.p, polys, 1.0 / key_scale(ctx->fast_round));
+    hipLaunchKernelGGL(k_bsk_export, dim3((unsigned)polys), dim3(512), 0, ctx->stream, ctx->K->d_bsk, (double *)ctx->out.dev.p, polys, 1.0 / key_scale(ctx->dispatch.fast_round));
     HIPCHK(ctx, hipGetLastError());
     CHK(to_host(ctx, bsk, ctx->out, polys * kN * sizeof(double)));
   }
@@ -1757,7 +1738,7 @@ int tfhe_hip_batch_gates_mixed_dev(tfhe_hip_ctx *ctx, const uint8_t *gates, cons
   ENTER(ctx);
   CHK(need_key(ctx));
   if (count && (!gates || !a || !b || !out)) return fail(ctx, TFHE_HIP_EINVAL, "null pointer");
-  return gates_mixed_dev(ctx, gates, a, b, out, count, pick(ctx, stream));
+  return run_bootstrap(ctx, pick(ctx, stream), {.in_a = a, .in_b = b, .gp = kCodesPrep, .count = count, .gate_codes = gates}, out, true);
 }
 
 int tfhe_hip_batch_gates_mixed_nks_dev(tfhe_hip_ctx *ctx, const uint8_t *gates, const uint32_t *a, const uint32_t *b,
@@ -1766,7 +1747,8 @@ int tfhe_hip_batch_gates_mixed_nks_dev(tfhe_hip_ctx *ctx, const uint8_t *gates, 
   ENTER(ctx);
   CHK(need_key(ctx));
   if (count && (!gates || !a || !b || !out)) return fail(ctx, TFHE_HIP_EINVAL, "null pointer");
-  return gates_mixed_nks_dev(ctx, gates, a, b, out, count, pick(ctx, stream));
+  // (the first level of Gates::mux, gates.rs:165-177)
+  return run_bootstrap(ctx, pick(ctx, stream), {.in_a = a, .in_b = b, .gp = kCodesPrep, .count = count, .gate_codes = gates}, out, false);
 }
 
 int tfhe_hip_batch_bootstrap_dev(tfhe_hip_ctx *ctx, const uint32_t *in, const uint32_t *testvec,
@@ -1776,7 +1758,7 @@ int tfhe_hip_batch_bootstrap_dev(tfhe_hip_ctx *ctx, const uint32_t *in, const ui
   ENTER(ctx);
   CHK(need_key(ctx));
   if (count && (!in || !out)) return fail(ctx, TFHE_HIP_EINVAL, "null pointer");
-  return bootstrap_dev(ctx, in, testvec, per_ct, keyswitch, out, count, pick(ctx, stream));
+  return run_bootstrap(ctx, pick(ctx, stream), {.in_a = in, .testvec = testvec, .per_ct = per_ct, .count = count}, out, keyswitch != 0);
 }
 
 int tfhe_hip_batch_tlwe_lincomb_dev(tfhe_hip_ctx *ctx, uint32_t ca, const uint32_t *a, uint32_t cb,
@@ -1796,8 +1778,9 @@ int tfhe_hip_batch_lincomb_bootstrap_dev(tfhe_hip_ctx *ctx, uint32_t ca, const u
   ENTER(ctx);
   CHK(need_key(ctx));
   if (count && (!a || !out || (cb && !b))) return fail(ctx, TFHE_HIP_EINVAL, "null pointer");
-  return lincomb_bootstrap_dev(ctx, GatePrep{ca, cb, cconst}, a, cb ? b : nullptr, testvec, per_ct, keyswitch, out,
-                               count, pick(ctx, stream));
+  return run_bootstrap(ctx, pick(ctx, stream),
+                       {.in_a = a, .in_b = b, .gp = {ca, cb, cconst}, .testvec = testvec, .per_ct = per_ct, .count = count}, out,
+                       keyswitch != 0);
 }
 
 int tfhe_hip_batch_lincomb_bootstrap_many_dev(tfhe_hip_ctx *ctx, uint32_t ca, const uint32_t *a, uint32_t cb,
@@ -1806,9 +1789,13 @@ int tfhe_hip_batch_lincomb_bootstrap_many_dev(tfhe_hip_ctx *ctx, uint32_t ca, co
   if (!ctx) return TFHE_HIP_EINVAL;
   ENTER(ctx);
   CHK(need_key(ctx));
-  CHK(many_checks(ctx, a, cb, b, testvec, n_luts, out, count));
-  return lincomb_bootstrap_many_dev(ctx, GatePrep{ca, cb, cconst}, a, cb ? b : nullptr, testvec, per_ct,
-                                    lut_shift_of(n_luts), keyswitch, out, count, pick(ctx, stream));
+  if (const char *why = many_refusal(a, cb, b, testvec, n_luts, out, count)) return fail(ctx, TFHE_HIP_EINVAL, why);
+  // ONE blind rotation per ciphertext with the rotation amounts rounded to multiples of n_luts, then n_luts sample
+  // extractions (function-major into lv1 or out) and one key switch over all rows
+  return run_bootstrap(ctx, pick(ctx, stream),
+                       {.in_a = a, .in_b = b, .gp = {ca, cb, cconst}, .testvec = testvec, .per_ct = per_ct, .count = count,
+                        .lut_shift = lut_shift_of(n_luts)},
+                       out, keyswitch != 0);
 }
 
 int tfhe_hip_batch_blind_rotate_dev(tfhe_hip_ctx *ctx, const uint32_t *in, const uint32_t *testvec,
@@ -1817,10 +1804,7 @@ int tfhe_hip_batch_blind_rotate_dev(tfhe_hip_ctx *ctx, const uint32_t *in, const
   ENTER(ctx);
   CHK(need_key(ctx));
   if (count && (!in || !out_trlwe)) return fail(ctx, TFHE_HIP_EINVAL, "null pointer");
-  GatePrep gp;
-  gate_prep(TFHE_HIP_COPY, gp);
-  return launch_blind_rotate(ctx, pick(ctx, stream), in, nullptr, gp, testvec, 0, count, out_trlwe,
-                             nullptr, nullptr);
+  return launch_blind_rotate(ctx, pick(ctx, stream), {.in_a = in, .testvec = testvec, .count = count, .out_trlwe = out_trlwe});
 }
 
 int tfhe_hip_batch_mux_dev(tfhe_hip_ctx *ctx, int naive, const uint32_t *a, const uint32_t *b,
@@ -1920,7 +1904,7 @@ int tfhe_hip_batch_gate(tfhe_hip_ctx *ctx, int gate, const uint32_t *a, const ui
   GatePrep gp;
   if (!gate_prep(gate, gp)) return fail(ctx, TFHE_HIP_EINVAL, "unknown gate");
   if (!a || !out || (gp.cb && !b)) return fail(ctx, TFHE_HIP_EINVAL, "null pointer");
-  const size_t bytes = count * (size_t)(ctx->P.n + 1) * 4;
+  const size_t bytes = tlwe_bytes(ctx, count);
   return host_call(ctx, true, {{a, bytes, &ctx->a}, {gp.cb ? b : nullptr, bytes, &ctx->b}}, out, bytes, [&](const void *const *d, void *o) {
     return gate_dev(ctx, gate, u32(d[0]), u32(d[1]), (uint32_t *)o, count, ctx->stream);
   });
@@ -1936,10 +1920,11 @@ int tfhe_hip_batch_gates_mixed(tfhe_hip_ctx *ctx, const uint8_t *gates, const ui
   if (!gates || !a || !b || !out) return fail(ctx, TFHE_HIP_EINVAL, "null pointer");
   for (size_t i = 0; i < count; ++i)
     if (gates[i] > TFHE_HIP_COPY) return fail(ctx, TFHE_HIP_EINVAL, "unknown gate");
-  const size_t bytes = count * (size_t)(ctx->P.n + 1) * 4;
+  const size_t bytes = tlwe_bytes(ctx, count);
   CHK(to_dev(ctx, ctx->idx, gates, count));  // one byte per ciphertext: always staged
   return host_call(ctx, true, {{a, bytes, &ctx->a}, {b, bytes, &ctx->b}}, out, bytes, [&](const void *const *d, void *o) {
-    return gates_mixed_dev(ctx, (const uint8_t *)ctx->idx.dev.p, u32(d[0]), u32(d[1]), (uint32_t *)o, count, ctx->stream);
+    return run_bootstrap(ctx, ctx->stream, {.in_a = u32(d[0]), .in_b = u32(d[1]), .gp = kCodesPrep, .count = count, .gate_codes = (const uint8_t *)ctx->idx.dev.p},
+                         (uint32_t *)o, true);
   });
 }
 
@@ -1953,10 +1938,11 @@ int tfhe_hip_batch_gates_mixed_nks(tfhe_hip_ctx *ctx, const uint8_t *gates, cons
   if (!gates || !a || !b || !out) return fail(ctx, TFHE_HIP_EINVAL, "null pointer");
   for (size_t i = 0; i < count; ++i)
     if (gates[i] > TFHE_HIP_COPY) return fail(ctx, TFHE_HIP_EINVAL, "unknown gate");
-  const size_t bytes = count * (size_t)(ctx->P.n + 1) * 4;
+  const size_t bytes = tlwe_bytes(ctx, count);
   const HostIn in[] = {{a, bytes, &ctx->a}, {b, bytes, &ctx->b}, {gates, count, &ctx->idx}};
   return host_call(ctx, false, in, out, bytes, [&](const void *const *d, void *o) {
-    return gates_mixed_nks_dev(ctx, (const uint8_t *)d[2], u32(d[0]), u32(d[1]), (uint32_t *)o, count, ctx->stream);
+    return run_bootstrap(ctx, ctx->stream, {.in_a = u32(d[0]), .in_b = u32(d[1]), .gp = kCodesPrep, .count = count, .gate_codes = (const uint8_t *)d[2]},
+                         (uint32_t *)o, false);
   });
 }
 
@@ -1969,16 +1955,16 @@ int tfhe_hip_batch_bootstrap(tfhe_hip_ctx *ctx, const uint32_t *in, const uint32
   CHK(need_key(ctx));
   if (count == 0) return TFHE_HIP_OK;
   if (!in || !out) return fail(ctx, TFHE_HIP_EINVAL, "null pointer");
-  const size_t bytes = count * (size_t)(ctx->P.n + 1) * 4;
+  const size_t bytes = tlwe_bytes(ctx, count);
   // the test vector is zero-copied on its own when it is pinned, whatever the ciphertexts are
-  const size_t tv_bytes = (per_ct ? count : 1) * (size_t)2 * kN * 4;
+  const size_t tv_bytes = testvec_bytes(per_ct, count);
   const uint32_t *d_tv = pinned_view(testvec, tv_bytes);
   if (testvec && !d_tv) {
     CHK(to_dev(ctx, ctx->tv, testvec, tv_bytes));
     d_tv = u32(ctx->tv.dev.p);
   }
   return host_call(ctx, true, {{in, bytes, &ctx->a}}, out, bytes, [&](const void *const *d, void *o) {
-    return bootstrap_dev(ctx, u32(d[0]), d_tv, per_ct, keyswitch, (uint32_t *)o, count, ctx->stream);
+    return run_bootstrap(ctx, ctx->stream, {.in_a = u32(d[0]), .testvec = d_tv, .per_ct = per_ct, .count = count}, (uint32_t *)o, keyswitch != 0);
   });
 }
 
@@ -1988,7 +1974,7 @@ int tfhe_hip_batch_tlwe_lincomb(tfhe_hip_ctx *ctx, uint32_t ca, const uint32_t *
   ENTER(ctx);
   if (count == 0) return TFHE_HIP_OK;
   if (!a || !out || (cb && !b)) return fail(ctx, TFHE_HIP_EINVAL, "null pointer");
-  const size_t bytes = count * (size_t)(ctx->P.n + 1) * 4;
+  const size_t bytes = tlwe_bytes(ctx, count);
   return host_call(ctx, false, {{a, bytes, &ctx->a}, {cb ? b : nullptr, bytes, &ctx->b}}, out, bytes, [&](const void *const *d, void *o) {
     return lincomb_dev(ctx, GatePrep{ca, cb, cconst}, u32(d[0]), u32(d[1]), (uint32_t *)o, count, ctx->stream);
   });
@@ -2008,12 +1994,13 @@ int tfhe_hip_batch_lincomb_bootstrap(tfhe_hip_ctx *ctx, uint32_t ca, const uint3
   CHK(need_key(ctx));
   if (count == 0) return TFHE_HIP_OK;
   if (!a || !out || (cb && !b)) return fail(ctx, TFHE_HIP_EINVAL, "null pointer");
-  const size_t bytes = count * (size_t)(ctx->P.n + 1) * 4;
+  const size_t bytes = tlwe_bytes(ctx, count);
   const HostIn in[] = {{a, bytes, &ctx->a}, {cb ? b : nullptr, bytes, &ctx->b},
-                       {testvec, (per_ct ? count : 1) * (size_t)2 * kN * 4, &ctx->tv}};
+                       {testvec, testvec_bytes(per_ct, count), &ctx->tv}};
   return host_call(ctx, false, in, out, bytes, [&](const void *const *d, void *o) {
-    return lincomb_bootstrap_dev(ctx, GatePrep{ca, cb, cconst}, u32(d[0]), u32(d[1]), u32(d[2]), per_ct, keyswitch,
-                                 (uint32_t *)o, count, ctx->stream);
+    return run_bootstrap(ctx, ctx->stream,
+                         {.in_a = u32(d[0]), .in_b = u32(d[1]), .gp = {ca, cb, cconst}, .testvec = u32(d[2]), .per_ct = per_ct, .count = count},
+                         (uint32_t *)o, keyswitch != 0);
   });
 }
 
@@ -2023,14 +2010,16 @@ int tfhe_hip_batch_lincomb_bootstrap_many(tfhe_hip_ctx *ctx, uint32_t ca, const 
   if (!ctx) return TFHE_HIP_EINVAL;  // (never combined: the merged launches have no many-LUT form)
   ENTER(ctx);
   CHK(need_key(ctx));
-  CHK(many_checks(ctx, a, cb, b, testvec, n_luts, out, count));
+  if (const char *why = many_refusal(a, cb, b, testvec, n_luts, out, count)) return fail(ctx, TFHE_HIP_EINVAL, why);
   if (count == 0) return TFHE_HIP_OK;
-  const size_t bytes = count * (size_t)(ctx->P.n + 1) * 4;
+  const size_t bytes = tlwe_bytes(ctx, count);
   const HostIn in[] = {{a, bytes, &ctx->a}, {cb ? b : nullptr, bytes, &ctx->b},
-                       {testvec, (per_ct ? count : 1) * (size_t)2 * kN * 4, &ctx->tv}};
+                       {testvec, testvec_bytes(per_ct, count), &ctx->tv}};
   return host_call(ctx, false, in, out, bytes * (size_t)n_luts, [&](const void *const *d, void *o) {
-    return lincomb_bootstrap_many_dev(ctx, GatePrep{ca, cb, cconst}, u32(d[0]), u32(d[1]), u32(d[2]), per_ct,
-                                      lut_shift_of(n_luts), keyswitch, (uint32_t *)o, count, ctx->stream);
+    return run_bootstrap(ctx, ctx->stream,
+                         {.in_a = u32(d[0]), .in_b = u32(d[1]), .gp = {ca, cb, cconst}, .testvec = u32(d[2]), .per_ct = per_ct, .count = count,
+                          .lut_shift = lut_shift_of(n_luts)},
+                         (uint32_t *)o, keyswitch != 0);
   });
 }
 
@@ -2043,11 +2032,9 @@ int tfhe_hip_batch_blind_rotate(tfhe_hip_ctx *ctx, const uint32_t *in, const uin
   CHK(need_key(ctx));
   if (count == 0) return TFHE_HIP_OK;
   if (!in || !out_trlwe) return fail(ctx, TFHE_HIP_EINVAL, "null pointer");
-  const HostIn ops[] = {{in, count * (size_t)(ctx->P.n + 1) * 4, &ctx->a}, {testvec, (size_t)2 * kN * 4, &ctx->tv}};
-  return host_call(ctx, false, ops, out_trlwe, count * (size_t)2 * kN * 4, [&](const void *const *d, void *o) {
-    GatePrep gp;
-    gate_prep(TFHE_HIP_COPY, gp);
-    return launch_blind_rotate(ctx, ctx->stream, u32(d[0]), nullptr, gp, u32(d[1]), 0, count, (uint32_t *)o, nullptr, nullptr);
+  const HostIn ops[] = {{in, tlwe_bytes(ctx, count), &ctx->a}, {testvec, trlwe_bytes(1), &ctx->tv}};
+  return host_call(ctx, false, ops, out_trlwe, trlwe_bytes(count), [&](const void *const *d, void *o) {
+    return launch_blind_rotate(ctx, ctx->stream, {.in_a = u32(d[0]), .testvec = u32(d[1]), .count = count, .out_trlwe = (uint32_t *)o});
   });
 }
 
@@ -2059,7 +2046,7 @@ int tfhe_hip_batch_mux(tfhe_hip_ctx *ctx, int naive, const uint32_t *a, const ui
   CHK(need_key(ctx));
   if (count == 0) return TFHE_HIP_OK;
   if (!a || !b || !c || !out) return fail(ctx, TFHE_HIP_EINVAL, "null pointer");
-  const size_t bytes = count * (size_t)(ctx->P.n + 1) * 4;
+  const size_t bytes = tlwe_bytes(ctx, count);
   return host_call(ctx, true, {{a, bytes, &ctx->a}, {b, bytes, &ctx->b}, {c, bytes, &ctx->c}}, out, bytes, [&](const void *const *d, void *o) {
     return mux_dev(ctx, naive, u32(d[0]), u32(d[1]), u32(d[2]), (uint32_t *)o, count, ctx->stream);
   });
@@ -2076,7 +2063,7 @@ int tfhe_hip_batch_external_product(tfhe_hip_ctx *ctx, const uint32_t *trlwe_in,
   if (!trlwe_in || !bsk_index || !trlwe_out) return fail(ctx, TFHE_HIP_EINVAL, "null pointer");
   for (size_t i = 0; i < count; ++i)
     if (bsk_index[i] < 0 || bsk_index[i] >= ctx->P.n) return fail(ctx, TFHE_HIP_EINVAL, "bsk_index out of range");
-  const size_t bytes = count * (size_t)2 * kN * 4;
+  const size_t bytes = trlwe_bytes(count);
   const uint32_t bsk_bytes = (uint32_t)((size_t)ctx->P.n * 2 * ctx->P.l * 2 * kN2 * 16);
   return host_call(ctx, false, {{trlwe_in, bytes, &ctx->a}, {bsk_index, count * 4, &ctx->idx}}, trlwe_out, bytes, [&](const void *const *d, void *o) {
     hipLaunchKernelGGL(ep_kernel(ctx), dim3((unsigned)count), dim3(64), kStageLdsBytes, ctx->stream, u32(d[0]), (const int32_t *)d[1],
@@ -2091,7 +2078,7 @@ int tfhe_hip_batch_sample_extract(tfhe_hip_ctx *ctx, const uint32_t *trlwe, int 
   if (k < 0 || k >= kN) return fail(ctx, TFHE_HIP_EINVAL, "extraction index out of range");
   if (count == 0) return TFHE_HIP_OK;
   if (!trlwe || !out) return fail(ctx, TFHE_HIP_EINVAL, "null pointer");
-  return host_call(ctx, false, {{trlwe, count * (size_t)2 * kN * 4, &ctx->a}}, out, count * (size_t)(kN + 1) * 4, [&](const void *const *d, void *o) {
+  return host_call(ctx, false, {{trlwe, trlwe_bytes(count), &ctx->a}}, out, count * (size_t)(kN + 1) * 4, [&](const void *const *d, void *o) {
     hipLaunchKernelGGL(k_sample_extract, dim3((unsigned)count), dim3(256), 0, ctx->stream, u32(d[0]), k, (uint32_t *)o, count);
     return launched(ctx);
   });
@@ -2103,8 +2090,8 @@ int tfhe_hip_batch_identity_key_switch(tfhe_hip_ctx *ctx, const uint32_t *tlwe_l
   CHK(need_key(ctx));
   if (count == 0) return TFHE_HIP_OK;
   if (!tlwe_lv1 || !out) return fail(ctx, TFHE_HIP_EINVAL, "null pointer");
-  CHK(ensure(ctx, ctx->a.dev, lv1_rows(count) * (size_t)(kN + 1) * 4));  // whole 256-row groups readable (k_key_switch_mfma)
-  const size_t obytes = count * (size_t)(ctx->P.n + 1) * 4;
+  CHK(ensure(ctx, ctx->a.dev, lv1_bytes(count)));  // whole 256-row groups readable (k_key_switch_mfma)
+  const size_t obytes = tlwe_bytes(ctx, count);
   return host_call(ctx, false, {{tlwe_lv1, count * (size_t)(kN + 1) * 4, &ctx->a}}, out, obytes, [&](const void *const *d, void *o) {
     return launch_key_switch(ctx, ctx->stream, u32(d[0]), (uint32_t *)o, count);
   });
@@ -2164,7 +2151,7 @@ int tfhe_hip_batch_reencrypt(tfhe_hip_ctx *ctx, const uint32_t *in, uint32_t *ou
   CHK(need_reenc_key(ctx));
   if (count == 0) return TFHE_HIP_OK;
   if (!in || !out) return fail(ctx, TFHE_HIP_EINVAL, "null pointer");
-  const size_t bytes = count * (size_t)(ctx->P.n + 1) * 4;
+  const size_t bytes = tlwe_bytes(ctx, count);
   return host_call(ctx, false, {{in, bytes, &ctx->a}}, out, bytes, [&](const void *const *d, void *o) {
     return reencrypt_dev(ctx, u32(d[0]), (uint32_t *)o, count, ctx->stream);
   });
@@ -2313,7 +2300,7 @@ int tfhe_hip_describe_dispatch(tfhe_hip_ctx *ctx, size_t count, char *buf, size_
 const char *tfhe_hip_rounding_mode(const tfhe_hip_ctx *ctx) {
   if (!ctx) return "none";
   const tfhe_hip_ctx *base = ctx->parent ? ctx->parent : ctx;
-  return base->fast_round ? "fast" : "general";
+  return base->dispatch.fast_round ? "fast" : "general";
 }
 
 #ifdef TFHE_EXPERIMENT
