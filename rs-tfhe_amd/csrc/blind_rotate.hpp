@@ -286,7 +286,7 @@ __device__ __forceinline__ void blind_rotate_batch(BlindRotateArgs A) {
   const unsigned long long rtc0 = A.clk ? __builtin_amdgcn_s_memrealtime() : 0ull;
 
   Twiddles tw;
-  tw.load(A.tw, t2tab, lane);
+  tw.load<TFHE_ABL_TW_REL && !MANY>(A.tw, t2tab, lane);
 
   // ---- gate linear prep + rotation amounts ---------------------------------
   uint32_t gca = A.ca, gcb = A.cb, gcc = A.cconst;

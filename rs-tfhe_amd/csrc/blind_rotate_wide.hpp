@@ -58,7 +58,7 @@ __device__ __forceinline__ void blind_rotate_wide2(BlindRotateArgs A) {
   const unsigned long long rtc0 = A.clk ? __builtin_amdgcn_s_memrealtime() : 0ull;
 
   Twiddles tw;
-  tw.load(A.tw, t2tab, lane);  // every wave stores the same 64 entries; ends with a workgroup barrier
+  tw.load<TFHE_ABL_TW_REL && !MANY>(A.tw, t2tab, lane);  // every wave stores the same 64 entries; ends with a workgroup barrier
 
   // ---- gate linear prep + rotation amounts (gates.rs:54-150, trgsw.rs:202-211) -----------------
   uint32_t gca = A.ca, gcb = A.cb, gcc = A.cconst;
@@ -293,7 +293,7 @@ __global__ __launch_bounds__(64 * kPairWaves, 1) void k_blind_rotate_pair(BlindR
   const unsigned long long rtc0 = A.clk ? __builtin_amdgcn_s_memrealtime() : 0ull;
 
   Twiddles tw;
-  tw.load(A.tw, t2tab, lane);  // ends with a workgroup barrier
+  tw.load<TFHE_ABL_TW_REL && !MANY>(A.tw, t2tab, lane);  // ends with a workgroup barrier
 
   // ---- gate linear prep + rotation amounts + X^b~ testvec for both ciphertexts (gates.rs:54-150, trgsw.rs:202-211)
   size_t cts[2];

@@ -83,6 +83,8 @@ struct Twiddles {
   double f3[8];   // forward pass 3: (re, im) x {c^4, c^2, c, c*W8}
   double i3[10];  // inverse pass 3: (re, im) x {G, G*c^4, c^2, c, c*conj(W8)}
   const double2 *t2;
+  // (SKEW: experiment.hpp TFHE_ABL_TW_REL, a mutation build -- false in every product build)
+  template <bool SKEW = false>
   __device__ __forceinline__ void load(const double2 *__restrict__ tw, double2 *t2_lds, int lane) {
 #pragma unroll
     for (int q = 0; q < 4; ++q) {
@@ -96,6 +98,15 @@ struct Twiddles {
       i3[2 * q] = a.x;
       i3[2 * q + 1] = a.y;
     }
+#if TFHE_ABL_TW_REL  // the value stored for entry 49 (inverse pass 2, c = exp(2 pi i / 64)) only: no address, barrier or bound differs
+    if (SKEW) {
+      double2 e = tw[576 + lane];
+      const double k = lane == 49 ? 1.0 + 0x1p-47 : 1.0;
+      e.x *= k;
+      e.y *= k;
+      t2_lds[lane] = e;
+    } else
+#endif
     t2_lds[lane] = tw[576 + lane];
     t2 = t2_lds;
     __syncthreads();
@@ -479,7 +490,8 @@ __device__ __forceinline__ uint32_t round_to_torus(double x) {
 // The rounding the blind-rotation kernels apply to the external product (round_product<FAST>) and the scale of the
 // engine's bootstrapping key that goes with it (key_scale(fast)).
 //   FAST sets: key x 2^-10 (the reference's 0.5 * 1/512, klemsa.rs:126,136), one add (round_to_torus<true>).
-//   Other sets (bgbit > 10, |x| up to 2^63): the key carries a further 2^-32 -- a power of two, so every product, sum
+//   Other sets (bgbit > 10, |x| up to 2^63 -- held at |x| = 2^62 by the crafted keys of tests/test_gpu_lockstep.py, where the
+//   fused and the stage kernels stay within 1.7 x the CPU path's own error): the key carries a further 2^-32 -- a power of two, so every product, sum
 //   and rounding of the transform is the same mantissa with the exponent lowered by 32 -- and the inverse transform
 //   delivers y = x * 2^-32 exactly.  Then q = rint(y) is the multiple of 2^32 to drop, t = y - q (exact, |t| <= 1/2)
 //   is v * 2^-32 for the same v = x - q * 2^32 as round_to_torus<false> forms, and t + 1.5 * 2^20 has its last

@@ -156,3 +156,70 @@ def trivial_mask_expected(n, phases):
     idx = n - np.arange(1, n)
     out[:, 1:] = (np.uint32(0xFFFFFFFF) - a_rot[:, idx]).astype(np.uint32)
     return out
+
+
+# ---- decomposition on its own: recomposition through the gadget --------------------------------------------------------------
+# decomposition (src/trgsw.rs:144-171) with the reference's offset sum_i (Bg/2) * g_i, g_i = 2^(32 - (i+1) bgbit) (no
+# rounding term): digit_i = ((x + offset) >> (32 - (i+1) bgbit) & (Bg - 1)) - Bg/2, so
+#     sum_i digit_i * g_i = ((x + offset) & ~(G - 1)) - offset = x & ~(G - 1)   (mod 2^32),   G = 2^(32 - l bgbit)
+# (offset is a multiple of G).  An external product with the GADGET itself as the TRGSW sample -- row r < l has g_r on a[0],
+# row l + r has g_r on b[0], everything else 0 -- computes exactly that sum for both polynomials; every product is below
+# 2^32, so the f64 path is exact in every parameter set.  A flipped digit sign, a swapped row order or a -Bg/2 read as
+# +Bg/2 changes the sum: the identity pins the digit extraction with no restatement of it.
+def gadget_trgsw(l, bgbit):
+    """[2l][2][N] u32, time domain"""
+    g = np.zeros((2 * l, 2, N), np.uint32)
+    for r in range(l):
+        g[r, 0, 0] = 1 << (32 - (r + 1) * bgbit)
+        g[l + r, 1, 0] = 1 << (32 - (r + 1) * bgbit)
+    return g
+
+
+def gadget_spectra(O, l, bgbit, rows=None):
+    """the gadget in the transform domain ([2l][2][N] f64, klemsa_ifft of each polynomial); `rows` permutes the 2l rows"""
+    g = gadget_trgsw(l, bgbit)
+    if rows is not None:
+        g = g[list(rows)]
+    return np.stack([np.stack([O.klemsa_ifft(p) for p in row]) for row in g])
+
+
+def recomposed_expected(x, l, bgbit):
+    x = np.asarray(x, np.uint32)
+    G = 1 << (32 - l * bgbit)
+    return (x & np.uint32((~(G - 1)) & 0xFFFFFFFF)).astype(np.uint32)
+
+
+def decomposition_edge_words(l, bgbit):
+    """0, MAX, the sign boundary, G - 1 / G / G + 1, and for every digit position the words whose digit there is -Bg/2 and
+    +Bg/2 - 1 (the field (x + offset) >> shift & (Bg - 1) equal to 0 and to Bg - 1)"""
+    G = 1 << (32 - l * bgbit)
+    offset = sum((1 << (bgbit - 1)) << (32 - (i + 1) * bgbit) for i in range(l))
+    words = [0, 0xFFFFFFFF, 0x80000000, 0x7FFFFFFF, G - 1, G, G + 1]
+    for i in range(l):
+        shift = 32 - (i + 1) * bgbit
+        for field in (0, (1 << bgbit) - 1):
+            for low in (0, (1 << shift) - 1):
+                words.append(((field << shift) + low - offset) % (1 << 32))
+    words.append((-offset) % (1 << 32))              # every digit -Bg/2
+    words.append((0xFFFFFFFF - offset) % (1 << 32))  # every digit +Bg/2 - 1
+    return np.array(words, np.uint64).astype(np.uint32)
+
+
+def decomposition_inputs(l, bgbit, count, seed):
+    """[count][2][N] u32: random words, with the edge words planted at the start and the end of both polynomials"""
+    rng = np.random.default_rng(seed)
+    x = rng.integers(0, 2**32, (count, 2, N), dtype=np.uint64).astype(np.uint32)
+    e = decomposition_edge_words(l, bgbit)
+    x[0, 0, :len(e)] = e
+    x[0, 1, N - len(e):] = e
+    x[1, 1, :len(e)] = e[::-1]
+    return x
+
+
+def testvec_for_difference(d):
+    """[2][N] u32 test vector c with (X^1 * c - c)[j] == d[j] for every j >= 1 (coefficient 0 is what the wrap makes it):
+    c[0] = 0, c[j] = c[j-1] - d[j]"""
+    d = np.asarray(d, np.uint32).reshape(2, N).astype(np.uint64)
+    c = np.zeros((2, N), np.uint64)
+    c[:, 1:] = (-np.cumsum(d[:, 1:], axis=1)) % (1 << 32)
+    return c.astype(np.uint32)

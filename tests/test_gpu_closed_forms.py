@@ -6,6 +6,7 @@ import numpy as np
 import pytest
 
 import closed_forms as CF
+import lockstep as LS
 from test_gpu_parity import _cloud_key, _product_params, eng128  # noqa: F401  (fixture)
 
 pytestmark = pytest.mark.gpu
@@ -114,3 +115,43 @@ def test_gpu_gate_prep_on_trivial_inputs_is_the_linear_form_of_gates_rs(O, eng12
         want = CF.gate_trivial_expected(g, pa[:64], pb[:64])
         sk, _ = keys128
         assert np.array_equal(sk.decrypt_bool(got), want == 0x20000000), g
+
+
+@pytest.mark.parametrize("setname", ["SECURITY_UINT2", "SECURITY_UINT3", "SECURITY_UINT4", "SECURITY_UINT1", "SECURITY_128_BIT"])
+def test_gpu_decomposition_recomposes_through_the_gadget(O, monkeypatch, setname):
+    """The digit extraction of the stage kernel and of the three fused kernels (inline there) on its own, against the closed
+    form of tests/closed_forms.py: with the GADGET loaded as every bootstrapping-key row, batch_external_product(x) must be
+    x & ~(G - 1) word for word, and one active CMUX step through each forced fused kernel must give
+    acc + ((X^a~ * acc - acc) & ~(G - 1)) -- on random words and on the words with an extreme digit (0, MAX, the sign
+    boundary, G - 1 / G / G + 1, digit -Bg/2, digit +Bg/2 - 1).  Every product is below 2^32: exact in every set.  A flipped
+    digit sign, a swapped row order or -Bg/2 read as +Bg/2 changes the sum (shown on the CPU checker in
+    test_oracle_closed_forms.py)."""
+    import rs_tfhe_amd as R
+
+    P = O.PARAM_SETS[setname]
+    pp = _product_params(P)
+    l, bgbit, n = P.l, P.bgbit, P.n
+    offset = O.gen_decomposition_offset(l, bgbit)
+    spectra = np.broadcast_to(CF.gadget_spectra(O, l, bgbit), (n, 2 * l, 2, N))
+    pk = R.CloudKey(pp, spectra, np.zeros((N, P.t, P.base, n + 1), np.uint32), offset, np.zeros((2, N), np.uint32))
+    x = CF.decomposition_inputs(l, bgbit, 6, 48)
+    want = CF.recomposed_expected(x, l, bgbit)
+    assert not np.array_equal(want, x)  # (the low bits are dropped: the closed form is not the identity)
+    idx = np.array([0, 1, n // 2, n - 1, 3, 7], np.int32)
+    # one active step: b = 0 (acc = testvec), a~ = 1 at key row n // 2; the test vector is built so that the difference
+    # X^1 * acc - acc carries the input words (coefficient 0 is what the wrap makes it)
+    ct = np.zeros(n + 1, np.uint32)
+    ct[n // 2] = 1 << 21
+    for name in LS.BR_KERNEL_ENVS:
+        LS.with_br_kernel(monkeypatch, name)
+        eng = R.Engine(pp, 0)
+        eng.load_cloud_key(pk)
+        assert np.array_equal(eng.batch_external_product(x, idx), want), (setname, name)
+        for xi in x[:3]:
+            tv = CF.testvec_for_difference(xi)
+            d = (LS.rotate(O, tv, 1) - tv).astype(np.uint32)
+            assert np.array_equal(d[:, 1:], xi[:, 1:])
+            got = eng.batch_blind_rotate(np.stack([ct, ct, ct]), tv)
+            assert f"blind_rotate={name}[0,3)" in eng.describe_dispatch(3)
+            assert np.array_equal(got, np.broadcast_to((tv + CF.recomposed_expected(d, l, bgbit)).astype(np.uint32), got.shape)), (setname, name)
+        eng.close()

@@ -1045,19 +1045,9 @@ def test_pinned_host_buffers_run_in_place(O, eng128, keys128):
     pool.close()
 
 
-# the three blind-rotation kernels, each forced at every batch size (TFHE_HIP_BR_KERNEL, include/tfhe_hip.h): eight waves
-# per ciphertext (default up to #CUs), two ciphertexts per eight-wave workgroup (default for #CUs < count <= 2 #CUs),
-# the batch kernel
-BR_KERNEL_ENVS = {
-    "single": {"TFHE_HIP_BR_KERNEL": "single"},
-    "pair": {"TFHE_HIP_BR_KERNEL": "pair"},
-    "batch": {"TFHE_HIP_BR_KERNEL": "batch"},
-}
-
-
-def _with_br_kernel(monkeypatch, name):
-    for k, v in BR_KERNEL_ENVS[name].items():
-        monkeypatch.setenv(k, v)
+# the three blind-rotation kernels, each forced at every batch size: BR_KERNEL_ENVS lives in tests/lockstep.py, which
+# tests/test_gpu_lockstep.py shares
+from lockstep import BR_KERNEL_ENVS, with_br_kernel as _with_br_kernel  # noqa: E402
 
 
 def test_latency_and_batch_kernels_agree(O, keys128, monkeypatch):

@@ -86,3 +86,40 @@ def test_gate_prep_on_trivial_inputs_is_the_linear_form_of_gates_rs(O, keys128):
         assert not prep[:, :n].any()
         out = O.batch_bootstrap(ck, prep, keyswitch=False)
         assert np.array_equal(out[:, n], CF.gate_trivial_expected(gate, pa, pb)), gate
+
+
+DECOMPOSITION_SHAPES = [(1, 18), (1, 22), (1, 23), (2, 10), (2, 16), (3, 6), (3, 10)]
+
+
+@pytest.mark.parametrize("l,bgbit", DECOMPOSITION_SHAPES)
+def test_decomposition_recomposes_through_the_gadget(O, l, bgbit):
+    """trgsw.rs:144-171 against the closed form of tests/closed_forms.py: sum_i digit_i * g_i == x & ~(G - 1) (mod 2^32),
+    on O.decomposition's own digits and through both external products with the gadget as the TRGSW sample -- on random
+    words and on the words with an extreme digit.  A flipped digit sign and a swapped row order fail it."""
+    offset = O.gen_decomposition_offset(l, bgbit)
+    xs = CF.decomposition_inputs(l, bgbit, 3, 47)
+    e = CF.decomposition_edge_words(l, bgbit)
+    half = 1 << (bgbit - 1)
+    g = [np.uint32(1 << (32 - (i + 1) * bgbit)) for i in range(l)]
+    gadget, spectra = CF.gadget_trgsw(l, bgbit), CF.gadget_spectra(O, l, bgbit)
+    seen = set()
+    for x in xs:
+        dec = O.decomposition(x, l, bgbit, offset)  # [2l][N]
+        want = CF.recomposed_expected(x, l, bgbit)
+        for poly in range(2):
+            digits = dec[poly * l:(poly + 1) * l]
+            seen.update(np.unique(digits.astype(np.int32)).tolist())
+            got = sum((d * gi for d, gi in zip(digits, g)), np.zeros(N, np.uint32)).astype(np.uint32)
+            assert np.array_equal(got, want[poly])
+            flipped = sum(((-d.astype(np.int64)).astype(np.uint32) * gi for d, gi in zip(digits, g)), np.zeros(N, np.uint32))
+            assert not np.array_equal(flipped.astype(np.uint32), want[poly])  # a flipped digit sign
+            if l > 1:
+                swapped = sum((d * gi for d, gi in zip(digits[::-1], g)), np.zeros(N, np.uint32)).astype(np.uint32)
+                assert not np.array_equal(swapped, want[poly])  # a swapped row order
+        assert np.array_equal(O.external_product_exact(gadget, x, l, bgbit, offset), want)
+        assert np.array_equal(O.external_product_fft(spectra, x, l, bgbit, offset), want)
+        if l > 1:
+            rev = list(range(l))[::-1] + [l + r for r in range(l)][::-1]
+            assert not np.array_equal(O.external_product_fft(CF.gadget_spectra(O, l, bgbit, rows=rev), x, l, bgbit, offset), want)
+    assert -half in seen and half - 1 in seen and half not in seen  # both extreme digits occur; -Bg/2 is never read as +Bg/2
+    assert len(e) >= 9
