@@ -276,6 +276,17 @@ class Engine {
     return out;
   }
 
+  // Unpacking key switch (tfhe_hip_batch_unpack_trlwe): slots of `groups` TRLWE lv1 [groups][2][N] -> lv0 ciphertexts
+  // [count][n+1] under the key-switching key of `ck` (sample_extract_index, then identity_key_switching), on the key
+  // view that holds `ck`.  slots == nullptr takes slots 0 .. count-1; otherwise output m takes slot slots[m].
+  static std::vector<Torus> unpack(const CloudKey &ck, const Torus *trlwe, size_t groups, const uint32_t *slots,
+                                   size_t count, int device = 0) {
+    Bound b = for_key(ck, device);
+    std::vector<Torus> out(count * (size_t)(ck.params.n + 1));
+    b.with_key(ck, [&](tfhe_hip_ctx *h) { return tfhe_hip_batch_unpack_trlwe(h, trlwe, groups, slots, count, out.data()); });
+    return out;
+  }
+
  private:
   // the key view of (addr, fp) on the one context of (p, device): found, or created (dropping the least recently used
   // idle view beyond kMaxResidentKeys) and filled by load(handle)

@@ -288,6 +288,40 @@ int tfhe_hip_packing_key_is_loaded(tfhe_hip_ctx *ctx);
 int tfhe_hip_batch_pack_tlwe(tfhe_hip_ctx *ctx, const uint32_t *in, size_t count, uint32_t *out);
 int tfhe_hip_batch_pack_tlwe_dev(tfhe_hip_ctx *ctx, const uint32_t *in, size_t count, uint32_t *out, void *stream);
 
+/* ---- unpacking key switch: slots of TRLWE lv1 ciphertexts back to lv0 ciphertexts ------
+ *
+ * The way back from the packed form: any slots of TRLWE lv1 ciphertexts under s1 -- what tfhe_hip_batch_pack_tlwe
+ * wrote, or what a client encrypted itself (TRLWELv1::encrypt_bool, trlwe.rs:55-66) -- become TLWE lv0 ciphertexts
+ * under s0 that the gate, mux, LUT and circuit calls accept.  State can so stay resident at 8 bytes a slot instead of
+ * 4(n+1) (2,804 on SECURITY_128_BIT), and a client can upload 1,024 values in one 8 KiB ciphertext.
+ *
+ * Definition (normative).  N = 1024, n of the context's set.
+ *   trlwe  [groups][2][N] u32, the a row then the b row of each group (the layout tfhe_hip_batch_pack_tlwe writes).
+ *   Output m < count takes slot s = slots ? slots[m] : m, group G = s / N, coefficient j = s % N.
+ *   The lv1 row of the slot, trlwe::sample_extract_index(trlwe_G, j) (trlwe.rs:106-120):
+ *     r[i] = a_G[j - i]                     for i <= j,
+ *     r[i] = 2^32 - 1 - a_G[N + j - i]      for j < i < N   (Torus::MAX - a: the reference's negation, one LSB below
+ *                                                            0 - a; tfhe_hip_batch_sample_extract does the same),
+ *     r[N] = b_G[j].
+ *   out[m] = trgsw::identity_key_switching(r) (trgsw.rs:332-360) under the handle's cloud key: the words
+ *   tfhe_hip_batch_identity_key_switch returns for r.  out is [count][n+1] u32.
+ *   Both steps are integer arithmetic: every device, key-switch kernel and parameter set gives these words exactly.
+ *   The phase of out[m] is coefficient j of b_G - a_G (*) s1 plus the key switch's rounding error and key noise.
+ * Semantics.  The call needs the cloud key (its key-switching key) and no packing key: TFHE_HIP_ENOKEY on a handle
+ * without a cloud key, a handle that holds a re-encryption key included.  count == 0 returns TFHE_HIP_OK.  Null trlwe
+ * or out with count > 0: TFHE_HIP_EINVAL.  With slots NULL, count <= groups * N (else TFHE_HIP_EINVAL) and only the
+ * first ceil(count / N) groups are read.  With slots given, every entry is < groups * N; duplicates and any order are
+ * allowed.  The host-pointer form checks the entries and returns TFHE_HIP_EINVAL for one out of range.  The _dev form
+ * only enqueues and cannot look at device memory without stalling: there the caller guarantees the range (an entry out
+ * of range reads nothing and its output is the key switch of an all-zero row, not an error).  Unpacking calls are
+ * bulk calls (the context's mutex, never the combining front end).  _dev: device pointers, slots included, queued on
+ * `stream` (NULL: the context's stream); the rows pass through the context's lv1 scratch like a bootstrap's, and
+ * TFHE_HIP_KS_KERNEL and the automatic choice of the key-switch kernel apply as they do there. */
+int tfhe_hip_batch_unpack_trlwe(tfhe_hip_ctx *ctx, const uint32_t *trlwe, size_t groups, const uint32_t *slots,
+                                size_t count, uint32_t *out);
+int tfhe_hip_batch_unpack_trlwe_dev(tfhe_hip_ctx *ctx, const uint32_t *trlwe, size_t groups, const uint32_t *slots,
+                                    size_t count, uint32_t *out, void *stream);
+
 /* Pinned host buffers.  The host entry points below take ordinary (pageable) memory and stage it through the
  * device around the kernels: 3 x 184 MB for a 65,536-ciphertext gate batch, about 7 % of the call.  When EVERY
  * ciphertext operand of a call (inputs and output) is pinned host memory -- allocated here, or the caller's own
@@ -619,6 +653,14 @@ int tfhe_hip_pool_load_packing_key(tfhe_hip_pool *pool, const uint8_t mask_seed[
 int tfhe_hip_pool_batch_pack_tlwe(tfhe_hip_pool *pool, const uint32_t *in, size_t count, uint32_t *out);
 int tfhe_hip_pool_batch_pack_tlwe_dev(tfhe_hip_pool *pool, int home_member, const uint32_t *in, size_t count,
                                       uint32_t *out, void *stream);
+/* Unpacking key switch on a pool (same arguments and result as tfhe_hip_batch_unpack_trlwe[_dev]).  With slots NULL the
+ * batch is cut on group boundaries, so a member receives only the whole groups it unpacks (the _dev form through the
+ * grouped scatter / gather, the outputs of a last partial group on home).  With slots given the outputs are split in
+ * input order and every member may receive all groups. */
+int tfhe_hip_pool_batch_unpack_trlwe(tfhe_hip_pool *pool, const uint32_t *trlwe, size_t groups, const uint32_t *slots,
+                                     size_t count, uint32_t *out);
+int tfhe_hip_pool_batch_unpack_trlwe_dev(tfhe_hip_pool *pool, int home_member, const uint32_t *trlwe, size_t groups,
+                                         const uint32_t *slots, size_t count, uint32_t *out, void *stream);
 
 /* The batched hot path over all members, HOST pointers: same arguments and semantics as the single-context host
  * entry points of the same name (gates.rs:352-547; gates.rs:157-199; bootstrap/{vanilla,lut}.rs; trgsw.rs:289-305;

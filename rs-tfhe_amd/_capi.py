@@ -99,6 +99,8 @@ SIGNATURES = {
     "tfhe_hip_packing_key_is_loaded": (C.c_int, [_CTX]),
     "tfhe_hip_batch_pack_tlwe": (C.c_int, [_CTX, _P, _SZ, _P]),
     "tfhe_hip_batch_pack_tlwe_dev": (C.c_int, [_CTX, _P, _SZ, _P, _P]),
+    "tfhe_hip_batch_unpack_trlwe": (C.c_int, [_CTX, _P, _SZ, _P, _SZ, _P]),
+    "tfhe_hip_batch_unpack_trlwe_dev": (C.c_int, [_CTX, _P, _SZ, _P, _SZ, _P, _P]),
     "tfhe_hip_batch_gate": (C.c_int, [_CTX, C.c_int, _P, _P, _P, _SZ]),
     "tfhe_hip_batch_gate_dev": (C.c_int, [_CTX, C.c_int, _P, _P, _P, _SZ, _P]),
     "tfhe_hip_batch_gates_mixed": (C.c_int, [_CTX, _P, _P, _P, _P, _SZ]),
@@ -158,6 +160,8 @@ SIGNATURES = {
     "tfhe_hip_pool_load_packing_key": (C.c_int, [_CTX, _P, _P]),
     "tfhe_hip_pool_batch_pack_tlwe": (C.c_int, [_CTX, _P, _SZ, _P]),
     "tfhe_hip_pool_batch_pack_tlwe_dev": (C.c_int, [_CTX, C.c_int, _P, _SZ, _P, _P]),
+    "tfhe_hip_pool_batch_unpack_trlwe": (C.c_int, [_CTX, _P, _SZ, _P, _SZ, _P]),
+    "tfhe_hip_pool_batch_unpack_trlwe_dev": (C.c_int, [_CTX, C.c_int, _P, _SZ, _P, _SZ, _P, _P]),
     "tfhe_hip_pool_batch_gate": (C.c_int, [_CTX, C.c_int, _P, _P, _P, _SZ]),
     "tfhe_hip_pool_batch_gates_mixed": (C.c_int, [_CTX, _P, _P, _P, _P, _SZ]),
     "tfhe_hip_pool_batch_bootstrap": (C.c_int, [_CTX, _P, _P, C.c_int, C.c_int, _P, _SZ]),

@@ -162,6 +162,36 @@ class SecretKey:
         m = int(message_modulus)
         return (torus_to_f64(self.packed_phase(packed, count)) / (1.0 / (2.0 * m)) + 0.5).astype(np.int64) % m
 
+    # ---- packed inputs (unpacking key switch, include/tfhe_hip.h) ------------------------------------
+    def encrypt_packed_f64(self, p, seed=None, alpha: float | None = None) -> np.ndarray:
+        """TRLWELv1::encrypt_f64 (trlwe.rs:30-53) over [count] values, N to a ciphertext: per group a uniform,
+        b = a (*) s1 + f64_to_torus(N(0, alpha)) + f64_to_torus(p) per coefficient, alpha_lv1 by default.  Returns
+        [ceil(count / N)][2][N] u32 under key_lv1; the unused slots of the last group encrypt 0."""
+        from .seeded import negacyclic_binary
+
+        g = _rng(seed)
+        p = np.atleast_1d(np.asarray(p, dtype=np.float64)).reshape(-1)
+        alpha = self.params.alpha_lv1 if alpha is None else alpha
+        groups = -(-len(p) // N)
+        msg = np.zeros(groups * N, np.float64)
+        msg[:len(p)] = p
+        out = np.empty((groups, 2, N), np.uint32)
+        out[:, 0] = g.integers(0, 1 << 32, (groups, N), dtype=np.uint64).astype(np.uint32)
+        noise = f64_to_torus(g.normal(0.0, alpha, groups * N)) if alpha > 0 else np.zeros(groups * N, np.uint32)
+        out[:, 1] = negacyclic_binary(out[:, 0], self.key_lv1) + (f64_to_torus(msg) + noise).reshape(groups, N)
+        return out
+
+    def encrypt_packed_bool(self, bits, seed=None, alpha: float | None = None) -> np.ndarray:
+        """TRLWELv1::encrypt_bool (trlwe.rs:55-66): true -> +1/8, false -> -1/8, slot m = bit m."""
+        bits = np.atleast_1d(np.asarray(bits)).astype(bool)
+        return self.encrypt_packed_f64(np.where(bits, 0.125, -0.125), seed, alpha)
+
+    def encrypt_packed_lwe_message(self, msgs, message_modulus: int, seed=None, alpha: float | None = None) -> np.ndarray:
+        """encrypt_lwe_message's encoding, (msg mod m) / (2m), in the slots of packed ciphertexts."""
+        m = int(message_modulus)
+        msgs = np.atleast_1d(np.asarray(msgs)).astype(np.int64) % m
+        return self.encrypt_packed_f64(msgs.astype(np.float64) * (1.0 / (2.0 * m)), seed, alpha)
+
     # ---- evaluation key ----------------------------------------------------------------------
     def cloud_key(self, seed=None, device: int = 0):
         """CloudKey::new(&secret_key) (key.rs:59-66): generated on the GPU in a fresh key view of the shared context

@@ -1294,4 +1294,56 @@ int tfhe_hip_pool_batch_pack_tlwe_dev(tfhe_hip_pool *p, int home, const uint32_t
   return TFHE_HIP_OK;
 }
 
+// ---- unpacking key switch (unpack.hpp): slots == NULL cuts on group boundaries, a selection splits the outputs ----------
+int tfhe_hip_pool_batch_unpack_trlwe(tfhe_hip_pool *p, const uint32_t *trlwe, size_t groups, const uint32_t *slots,
+                                     size_t count, uint32_t *out) {
+  POOL_ENTER(p);
+  tfhe_hip_ctx *c0 = p->ctxs[0];
+  // the checks that need the whole call are a member's (ENOKEY first): an empty or refused batch ends here
+  if (count == 0 || !trlwe || !out || (!slots && count > groups * (size_t)kN) || (slots && groups == 0))
+    return pool_member_rc(p, c0, tfhe_hip_batch_unpack_trlwe(c0, trlwe, groups, slots, count, out));
+  const size_t w = (size_t)c0->P.n + 1;
+  if (slots)  // every member reads the groups its slots name: all of them travel (a member checks its own entries)
+    return pool_map(p, count, [&](tfhe_hip_ctx *c, size_t lo, size_t hi) {
+      return tfhe_hip_batch_unpack_trlwe(c, trlwe, groups, slots + lo, hi - lo, out + lo * w);
+    });
+  const size_t used = (count + kN - 1) / kN;
+  const int world = (int)(used < p->ctxs.size() ? used : p->ctxs.size());
+  return pool_map(p, used, [&](tfhe_hip_ctx *c, size_t lo, size_t hi) {
+    const size_t m_hi = hi * kN < count ? hi * kN : count;
+    return tfhe_hip_batch_unpack_trlwe(c, trlwe + lo * (size_t)2 * kN, hi - lo, nullptr, m_hi - lo * kN, out + lo * kN * w);
+  }, world);
+}
+
+int tfhe_hip_pool_batch_unpack_trlwe_dev(tfhe_hip_pool *p, int home, const uint32_t *trlwe, size_t groups,
+                                         const uint32_t *slots, size_t count, uint32_t *out, void *stream) {
+  POOL_ENTER(p);
+  if (home < 0 || home >= (int)p->ctxs.size()) return pool_fail(p, TFHE_HIP_EINVAL, "no such pool member (home)");
+  tfhe_hip_ctx *hc = p->ctxs[(size_t)home];
+  if (count == 0 || !trlwe || !out || (!slots && count > groups * (size_t)kN) || (slots && groups == 0)) {
+    // home's checks, nothing to run (a failure is reported with the FIRST member's device and text, whichever member is home)
+    CHK(pool_member_rc(p, p->ctxs[0], tfhe_hip_batch_unpack_trlwe_dev(hc, trlwe, groups, slots, count, out, stream)));
+    p->root()->last_transport = "none";
+    return TFHE_HIP_OK;
+  }
+  const size_t w = (size_t)hc->P.n + 1;
+  if (slots) {
+    const PoolIn ins[5] = {{trlwe, groups * (size_t)2 * kN * 4, false}, {slots, 4, true}, {}, {}, {}};
+    return pool_dev_map(p, home, count, stream, ins, out, w * 4, [&](tfhe_hip_ctx *c, const void *const *q, void *o, size_t m, void *s) {
+      return tfhe_hip_batch_unpack_trlwe_dev(c, (const uint32_t *)q[0], groups, (const uint32_t *)q[1], m, (uint32_t *)o, s);
+    });
+  }
+  // whole groups through the grouped scatter / gather; the outputs of a last partial group (fewer than a group's rows,
+  // so they cannot travel as one) are made on home, on the same stream, after home's own shard
+  const size_t full = count / kN, tail = count - full * kN;
+  const PoolIn ins[5] = {{trlwe, (size_t)2 * kN * 4, true}, {}, {}, {}, {}};
+  const int world = (int)(full < p->ctxs.size() ? full : p->ctxs.size());
+  CHK(pool_dev_map(p, home, full, stream, ins, out, kN * w * 4, [&](tfhe_hip_ctx *c, const void *const *q, void *o, size_t m, void *s) {
+    return tfhe_hip_batch_unpack_trlwe_dev(c, (const uint32_t *)q[0], m, nullptr, m * kN, (uint32_t *)o, s);
+  }, world));
+  if (tail)
+    return pool_member_rc(p, hc, tfhe_hip_batch_unpack_trlwe_dev(hc, trlwe + full * (size_t)2 * kN, 1, nullptr, tail, out + full * kN * w, stream));
+  return TFHE_HIP_OK;
+}
+
 #undef POOL_ENTER

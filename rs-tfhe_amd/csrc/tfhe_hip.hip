@@ -58,7 +58,18 @@ thread_local std::string g_create_error = "";
 // when a thread's table has grown past kErrTableSoftCap entries, the next failure on that thread drops the entries of
 // handles that no longer exist (g_live_handles).  Reading never inserts.
 std::atomic<uint64_t> g_next_handle_id{1};
-thread_local std::unordered_map<uint64_t, std::string> t_errors;
+// The table is reached through a plain pointer: a thread's thread_local objects are destroyed before the process's
+// static ones, so a handle destroyed from a static destructor at exit (the C++ mirror's engine registry) after a
+// failing call on the main thread would otherwise erase from a destroyed map.  The pointer is null before the
+// thread's first failure and again once the thread's table is gone.
+typedef std::unordered_map<uint64_t, std::string> ErrTable;
+thread_local ErrTable *t_errors = nullptr;
+struct ErrTableOwner {
+  ~ErrTableOwner() {
+    delete t_errors;
+    t_errors = nullptr;
+  }
+};
 std::mutex g_live_mu;
 std::unordered_set<uint64_t> g_live_handles;
 constexpr size_t kErrTableSoftCap = 64;
@@ -73,21 +84,26 @@ inline void handle_gone(uint64_t id) {
     std::lock_guard<std::mutex> lk(g_live_mu);
     g_live_handles.erase(id);
   }
-  t_errors.erase(id);
+  if (t_errors) t_errors->erase(id);
 }
 // the slot a FAILING call writes its text into (references survive rehashing)
 inline std::string &err_slot(uint64_t id) {
-  if (t_errors.size() >= kErrTableSoftCap && !t_errors.count(id)) {
+  thread_local ErrTableOwner owner;  // frees the table when the thread ends
+  (void)owner;
+  if (!t_errors) t_errors = new ErrTable();
+  ErrTable &t = *t_errors;
+  if (t.size() >= kErrTableSoftCap && !t.count(id)) {
     std::lock_guard<std::mutex> lk(g_live_mu);
-    for (auto it = t_errors.begin(); it != t_errors.end();) it = g_live_handles.count(it->first) ? std::next(it) : t_errors.erase(it);
+    for (auto it = t.begin(); it != t.end();) it = g_live_handles.count(it->first) ? std::next(it) : t.erase(it);
   }
-  return t_errors[id];
+  return t[id];
 }
 // the calling thread's last failure text on handle `id`, "" if it never failed there (no entry is made)
 inline const char *err_text(uint64_t id) {
   static const std::string none;
-  const auto it = t_errors.find(id);
-  return it == t_errors.end() ? none.c_str() : it->second.c_str();
+  if (!t_errors) return none.c_str();
+  const auto it = t_errors->find(id);
+  return it == t_errors->end() ? none.c_str() : it->second.c_str();
 }
 
 constexpr int kKsG = 32;  // ciphertexts per key-switch workgroup
@@ -2384,3 +2400,4 @@ int tfhe_hip_synchronize(tfhe_hip_ctx *ctx) {
 #include "circuit.hpp"
 #include "seeded.hpp"
 #include "packing.hpp"
+#include "unpack.hpp"

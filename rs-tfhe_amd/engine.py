@@ -323,6 +323,38 @@ class _Handle:
             raise ValueError("out must be [ceil(count / N)][2][N]")
         self._call_dev("batch_pack_tlwe_dev", h, self._tp(h, cts), count, self._tp(h, out), self._stream_ptr(h, stream))
 
+    # -- unpacking key switch (include/tfhe_hip.h): slots of TRLWE lv1 ciphertexts back to lv0 ciphertexts --------------
+    def unpack(self, trlwe, count=None, slots=None) -> np.ndarray:
+        """[groups][2][N] TRLWE lv1 -> [count][n+1] lv0 ciphertexts under the cloud key's key-switching key
+        (`tfhe_hip_batch_unpack_trlwe`).  slots=None takes slots 0 .. count-1 (count=None: every slot); otherwise
+        output m takes slot slots[m] (any order, duplicates allowed) and count is len(slots)."""
+        trlwe = _u32(trlwe).reshape(-1, 2, N)
+        sl = None
+        if slots is not None:
+            sl = np.ascontiguousarray(slots, dtype=np.uint32).reshape(-1)
+            if count is not None and int(count) != len(sl):
+                raise ValueError("count differs from len(slots)")
+            count = len(sl)
+        elif count is None:
+            count = len(trlwe) * N
+        out = np.empty((int(count), self.params.n + 1), np.uint32)
+        self._call("batch_unpack_trlwe", _ptr(trlwe), len(trlwe), _ptr(sl), int(count), _ptr(out))
+        return out
+
+    def unpack_dev(self, trlwe, out, count, slots=None, stream=None, home=None) -> None:
+        """Device form: trlwe [groups][2][N], out [count][n+1] and slots [count] (or None) 32-bit CUDA tensors on the
+        call's GPU.  The slots are not checked (the call only enqueues): every entry is < groups * N."""
+        h = self._home(home)
+        count = int(count)
+        if trlwe is None or trlwe.numel() % (2 * N) != 0:
+            raise ValueError("trlwe must be [groups][2][N]")
+        if self._dev_batch(h, out) != count:
+            raise ValueError("out must be [count][n+1]")
+        if slots is not None and slots.numel() != count:
+            raise ValueError("slots must be [count]")
+        self._call_dev("batch_unpack_trlwe_dev", h, self._tp(h, trlwe), trlwe.numel() // (2 * N), self._tp(h, slots), count,
+                       self._tp(h, out), self._stream_ptr(h, stream))
+
     # -- device-resident path (torch CUDA tensors; enqueue only) ------------------
     # The tensors of a call live on one GPU: an Engine's, or that of pool member `home` (default: pool.home).  A pool
     # computes shard 0 in place there and moves the others to their members and back by grouped RCCL send / receive

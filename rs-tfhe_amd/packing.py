@@ -6,6 +6,9 @@ SECURITY_128_BIT.  This module is the client's side -- the packing key (`make_pa
 section's ChaCha20 keystream, bodies by exact negacyclic products with the binary s1) -- and the integer model of the
 server's result (`pack_model`), which the GPU (csrc/packing.hpp, `Engine.pack`) equals word for word.  `pack` runs it
 on the key view of a cloud key.
+
+The way back ("unpacking key switch" in the header): `unpack_model` is the integer model of sample_extract_index
+followed by identity_key_switching, `unpack` runs it on the GPU (csrc/unpack.hpp, `Engine.unpack`).
 """
 from __future__ import annotations
 
@@ -172,3 +175,87 @@ def pack(cts, cloud_key, packing_key: PackingKey, device: int = 0) -> np.ndarray
             if view._packing_key is not packing_key or not view.packing_key_is_loaded():
                 view.load_packing_key(packing_key)
             return view.pack(cts)
+
+
+# ---- unpacking key switch: slots of TRLWE lv1 ciphertexts back to lv0 ciphertexts ------------------------------------
+def _slots(trlwe, count, slots):
+    """(trlwe as [groups][2][N], the slot of every output as int64 [count]) after the header's range checks."""
+    trlwe = np.ascontiguousarray(trlwe, dtype=np.uint32).reshape(-1, 2, N)
+    if slots is None:
+        count = len(trlwe) * N if count is None else int(count)
+        if count > len(trlwe) * N:
+            raise ValueError(f"{len(trlwe)} TRLWEs hold fewer than {count} slots")
+        return trlwe, np.arange(count, dtype=np.int64)
+    s = np.asarray(slots).astype(np.int64).reshape(-1)
+    if count is not None and int(count) != len(s):
+        raise ValueError("count differs from len(slots)")
+    if len(s) and (s.min() < 0 or s.max() >= len(trlwe) * N):
+        raise ValueError("slot out of range")
+    return trlwe, s
+
+
+def extract_rows(trlwe, slots) -> np.ndarray:
+    """trlwe::sample_extract_index (trlwe.rs:106-120) of slot s = G N + j for every s in `slots`: [len(slots)][N+1] u32,
+    r[i] = a_G[j - i] for i <= j, Torus::MAX - a_G[N + j - i] for i > j (the reference's negation: ~a, one LSB below
+    0 - a), r[N] = b_G[j]."""
+    trlwe = np.asarray(trlwe, np.uint32).reshape(-1, 2, N)
+    s = np.asarray(slots, np.int64).reshape(-1)
+    G, j = s // N, s % N
+    i = np.arange(N)
+    out = np.empty((len(s), N + 1), np.uint32)
+    r = np.take_along_axis(trlwe[G, 0], (j[:, None] - i[None, :]) % N, axis=1)
+    out[:, :N] = np.where(i[None, :] > j[:, None], ~r, r)
+    out[:, N] = trlwe[G, 1, j]
+    return out
+
+
+def key_switch_model(params: SecurityParams, ksk, rows) -> np.ndarray:
+    """trgsw::identity_key_switching (trgsw.rs:332-360) of [M][N+1] lv1 rows under ksk [N][t][base][n+1]: [M][n+1] u32,
+    out = (0, .., 0, r[N]) - sum over (i, l) with digit k != 0 of ksk[i][l][k], k = digit l of r[i] + 2^(31 - basebit t).
+    Base 4 runs as float64 matmuls of the one-hot digits with the 16-bit halves of the key words (sums < 2^36: exact);
+    wider bases, whose one-hot rows are mostly zeros, gather the key rows instead."""
+    p = params
+    t, bb, base = p.iks_t, p.basebit, p.base
+    ksk = np.asarray(ksk, np.uint32).reshape(N, t, base, p.n + 1)
+    rows = np.asarray(rows, np.uint32).reshape(-1, N + 1)
+    M = len(rows)
+    abar = rows[:, :N] + np.uint32(1 << (31 - bb * t))
+    k = np.stack([(abar >> np.uint32(32 - (l + 1) * bb)) & np.uint32(base - 1) for l in range(t)], axis=2)  # [M][N][t]
+    acc = np.zeros((M, p.n + 1), np.uint32)
+    if base <= 4:
+        step = 64  # coefficients per product
+        for lo in range(0, N, step):
+            kk = k[:, lo:lo + step]
+            hot = (kk[..., None] == np.arange(1, base, dtype=np.uint32)).astype(np.float64).reshape(M, -1)
+            key = ksk[lo:lo + step, :, 1:].reshape(-1, p.n + 1)
+            s = (hot @ (key & 0xFFFF).astype(np.float64)).astype(np.int64)
+            s += (hot @ (key >> 16).astype(np.float64)).astype(np.int64) << 16
+            acc += (s & 0xFFFFFFFF).astype(np.uint32)
+    else:
+        for i in range(N):
+            for l in range(t):
+                kk = k[:, i, l]
+                acc += ksk[i, l][kk] * (kk != 0).astype(np.uint32)[:, None]
+    out = np.uint32(0) - acc
+    out[:, p.n] += rows[:, N]
+    return out
+
+
+def unpack_model(params: SecurityParams, ksk, trlwe, count=None, slots=None) -> np.ndarray:
+    """The definition's result ("unpacking key switch", include/tfhe_hip.h): output m is the identity key switch, under
+    the cloud key's `ksk` [N][t][base][n+1], of the lv1 row extracted at slot slots[m] (m itself with slots None) of
+    trlwe [groups][2][N].  [count][n+1] u32; integer arithmetic throughout, so the GPU equals it word for word."""
+    trlwe, s = _slots(trlwe, count, slots)
+    out = np.empty((len(s), params.n + 1), np.uint32)
+    for lo in range(0, len(s), 2048):  # bounds the rows and digits held at once
+        out[lo:lo + 2048] = key_switch_model(params, ksk, extract_rows(trlwe, s[lo:lo + 2048]))
+    return out
+
+
+def unpack(packed, cloud_key, count=None, slots=None, device: int = 0) -> np.ndarray:
+    """The server side: slots of [groups][2][N] TRLWE lv1 ciphertexts -> [count][n+1] lv0 ciphertexts on the GPU, on
+    the key view of `cloud_key` (bootstrap.keyed_engine)."""
+    from .bootstrap import keyed_engine
+
+    with keyed_engine(cloud_key, device) as view:
+        return view.unpack(packed, count, slots)

@@ -89,6 +89,11 @@ pub const ORNY: c_int = 8; pub const ORYN: c_int = 9; pub const COPY: c_int = 10
 extern "C" {   // packing key switch (include/tfhe_hip.h): up to N lv0 results in one TRLWE lv1 under the client's s1
     fn tfhe_hip_pool_load_packing_key(pool: *mut TfheHipPool, mask_seed: *const u8, bodies: *const u32) -> c_int;
     fn tfhe_hip_pool_batch_pack_tlwe(pool: *mut TfheHipPool, input: *const u32, count: usize, out: *mut u32) -> c_int;
+    // unpacking key switch: slots of TRLWE lv1 ciphertexts back to lv0 ciphertexts under the cloud key's key-switching key
+    fn tfhe_hip_pool_batch_unpack_trlwe(pool: *mut TfheHipPool, trlwe: *const u32, groups: usize, slots: *const u32,
+                                        count: usize, out: *mut u32) -> c_int;
+    fn tfhe_hip_pool_batch_unpack_trlwe_dev(pool: *mut TfheHipPool, home_member: c_int, trlwe: *const u32, groups: usize,
+                                            slots: *const u32, count: usize, out: *mut u32, stream: *mut c_void) -> c_int;
 }
 
 const W: usize = params::tlwe_lv0::N + 1;     // words per TLWELv0
@@ -393,6 +398,26 @@ impl HipEngine {
         }
         Self::check(g.view, unsafe { tfhe_hip_pool_batch_pack_tlwe(g.view, cts.as_ptr(), count, out.as_mut_ptr()) });
         out
+    }
+
+    /// Unpacking key switch, the definition of include/tfhe_hip.h: slots of `trlwe` ([groups][2][N] TRLWE lv1 under s1,
+    /// flat -- what `pack_tlwe` returned, or what a client encrypted with `TRLWELv1::encrypt_bool`) become lv0 ciphertexts
+    /// under `ck`'s key-switching key: `sample_extract_index(trlwe_G, j)` then `identity_key_switching` per slot.
+    /// `slots = None` takes slots 0 .. count-1; otherwise output m takes slot `slots[m]` and `count` is ignored.
+    pub fn unpack_trlwe(&self, trlwe: &[u32], slots: Option<&[u32]>, count: usize, ck: &CloudKey) -> Vec<Ciphertext> {
+        assert_eq!(trlwe.len() % (2 * N), 0, "trlwe is [groups][2][N]");
+        let groups = trlwe.len() / (2 * N);
+        let count = slots.map_or(count, |s| s.len());
+        let sp = slots.map_or(std::ptr::null(), |s| s.as_ptr());
+        let mut out = vec![0u32; count * W];
+        self.with_key(ck, |v| (unsafe { tfhe_hip_pool_batch_unpack_trlwe(v, trlwe.as_ptr(), groups, sp, count, out.as_mut_ptr()) }, ()));
+        Self::unflatten(&out)
+    }
+    /// The same on device pointers of member `home`'s GPU (`slots` too, or null); the call only enqueues and leaves the
+    /// range of the slots to the caller.  Safety: the pointers must stay valid until the work has run (`synchronize`).
+    pub unsafe fn unpack_trlwe_dev(&self, home: usize, trlwe: *const u32, groups: usize, slots: *const u32, count: usize,
+                                   out: *mut u32, stream: *mut c_void, ck: &CloudKey) {
+        self.with_key(ck, |v| (tfhe_hip_pool_batch_unpack_trlwe_dev(v, home as c_int, trlwe, groups, slots, count, out, stream), ()));
     }
 
     /// the seed, 64 evenly spaced body words and the size (FNV-style mix), as the C++ mirror samples a packing key
