@@ -1,0 +1,172 @@
+// key_change.hpp -- the one path by which a key becomes current on a handle (host code only).
+//
+// Every route that changes a cloud key or a re-encryption key (load, generate, compressed load / generate, adopt, the
+// pool's two replications, the re-encryption key that shares d_ksk) runs
+//   begin_key_change:  drain what may still read the old key (drain_key_readers), clear key_loaded and reenc_loaded,
+//                      allocate the buffers the route names (ensure_key_buffers)
+//   ... the route fills the buffers on ctx->stream ...
+//   commit_cloud_key / commit_reenc_key:  rebuild the matrix-core byte planes, set the offset, set the flag LAST,
+//                      warm lane 0 of the front end
+// and a route that leaves in between leaves both flags cleared: the handle answers "cloud key not loaded" until the
+// next change succeeds.  The real differences between the routes, all of them kept:
+//  - argument validation comes BEFORE begin_key_change, so a refused call leaves the old key answering;
+//  - tfhe_hip_adopt_cloud_key is a commit with no begin: the caller filled the buffers (on streams of its own), so it
+//    quiesces the lanes and synchronises the whole device first, and the old flag stands until the commit;
+//  - the pool's broadcast replication splits begin (prepare_replica) and commit (finish_replica) around the
+//    broadcast, which runs outside the member's call, and synchronises the whole device before the commit;
+//  - the packing key (packing.hpp) has its own flag and planes, which are not the key switch's: it drains with a
+//    device-wide synchronisation, is left alone by a cloud-key change, and takes only upload_through_temp from here.
+// ctx->mu is held and ctx's device is current in everything below.
+#pragma once
+
+namespace {
+
+// ---- sizes of the key buffers (engine layouts), once -----------------------------------------------------------------
+inline size_t bsk_polys(const tfhe_hip_params &P) { return (size_t)P.n * 2 * P.l * 2; }
+inline size_t bsk_bytes(const tfhe_hip_params &P) { return bsk_polys(P) * kN * sizeof(double); }
+inline size_t ksk_rows(const tfhe_hip_params &P) { return (size_t)kN * P.t * ((size_t)1 << P.basebit); }
+inline size_t ksk_bytes(const tfhe_hip_params &P) { return ksk_rows(P) * ksk_row_words(P.n) * 4; }
+// d_ksk is allocated this much longer: the key switch's row DMAs read past the end of the last row (key_switch.hpp)
+constexpr size_t kKskTailPad = 4096;
+inline size_t key_testvec_bytes() { return testvec_bytes(0, 1); }
+
+enum KeyBufs { KEY_BUF_BSK = 1, KEY_BUF_KSK = 2, KEY_BUF_TESTVEC = 4, KEY_BUF_ALL = 7 };
+
+// the only allocator of d_bsk / d_ksk / d_testvec (free_key releases them)
+int ensure_key_buffers(tfhe_hip_ctx *ctx, int which) {
+  KeyState &k = *ctx->K;
+  if ((which & KEY_BUF_BSK) && !k.d_bsk) HIPCHK(ctx, hipMalloc((void **)&k.d_bsk, bsk_bytes(ctx->P)));
+  if ((which & KEY_BUF_KSK) && !k.d_ksk) HIPCHK(ctx, hipMalloc((void **)&k.d_ksk, ksk_bytes(ctx->P) + kKskTailPad));
+  if ((which & KEY_BUF_TESTVEC) && !k.d_testvec) HIPCHK(ctx, hipMalloc((void **)&k.d_testvec, key_testvec_bytes()));
+  return TFHE_HIP_OK;
+}
+
+// Work queued earlier on a caller's stream (*_dev entry points), on the context's stream or on the front end's lanes
+// (merged small calls) may still be reading the key that is about to change: drain all three.
+// (The key-view branch of tfhe_hip_ctx_destroy keeps its own spelling: it must go on to free the key whatever a
+// synchronisation answers, and this returns at the first failure.)
+int drain_key_readers(tfhe_hip_ctx *ctx) {
+  if (ctx->scratch_owned) HIPCHK(ctx, hipStreamSynchronize(ctx->scratch_owner));
+  HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+  ctx->scratch_owned = false;
+  comb_quiesce(ctx);
+  return TFHE_HIP_OK;
+}
+
+// `which`: KEY_BUF_ALL for a cloud key, KEY_BUF_KSK for a re-encryption key (d_ksk is shared between the two, hence
+// both flags go)
+int begin_key_change(tfhe_hip_ctx *ctx, int which) {
+  CHK(drain_key_readers(ctx));
+  ctx->K->key_loaded = ctx->K->reenc_loaded = false;
+  return ensure_key_buffers(ctx, which);
+}
+
+int commit_cloud_key(tfhe_hip_ctx *ctx, uint32_t offset) {
+  CHK(build_ksk_planes(ctx));
+  ctx->K->offset = offset;
+  ctx->K->reenc_loaded = false;  // (already so after begin_key_change; adopt has no begin)
+  ctx->K->key_loaded = true;
+  comb_prepare(ctx);
+  return TFHE_HIP_OK;
+}
+
+int commit_reenc_key(tfhe_hip_ctx *ctx) {
+  CHK(build_ksk_planes(ctx));
+  ctx->K->reenc_loaded = true;
+  return TFHE_HIP_OK;
+}
+
+// ---- host key -> device, converted ----------------------------------------------------------------------------------
+// A device temporary of the sources' bytes plus `extra_bytes`; the sources copied into it back to back on ctx->stream;
+// launch(temporary) -> hipError_t queues the conversion; the stream drained and the temporary freed on every path.
+struct HostSrc {
+  const void *p;
+  size_t bytes;
+};
+template <class Launch>
+int upload_through_temp(tfhe_hip_ctx *ctx, const char *label, std::initializer_list<HostSrc> srcs, size_t extra_bytes,
+                        Launch &&launch) {
+  size_t total = extra_bytes;
+  for (const HostSrc &s : srcs) total += s.bytes;
+  char *d_tmp = nullptr;
+  HIPCHK(ctx, hipMalloc((void **)&d_tmp, total));
+  hipError_t e = hipSuccess;
+  size_t at = 0;
+  for (const HostSrc &s : srcs) {
+    if (e == hipSuccess) e = hipMemcpyAsync(d_tmp + at, s.p, s.bytes, hipMemcpyHostToDevice, ctx->stream);
+    at += s.bytes;
+  }
+  if (e == hipSuccess) e = launch((void *)d_tmp);
+  const hipError_t es = hipStreamSynchronize(ctx->stream);
+  if (e == hipSuccess) e = es;
+  (void)hipFree(d_tmp);
+  if (e != hipSuccess) return fail(ctx, TFHE_HIP_EHIP, std::string(label) + " upload: " + hipGetErrorString(e));
+  return TFHE_HIP_OK;
+}
+
+// ---- key generation: the secrets on the device -----------------------------------------------------------------------
+// The secret keys, the spectrum of the ring key and the generator key do not outlive the call on the device,
+// whichever way it ends: the guard zeroes the four staging buffers and drains the stream on every exit path
+// (an early return would otherwise leave them in buffers that later batches reuse as plain staging space, and
+// could return while an asynchronous copy still reads the caller's frame).
+struct Wipe {
+  tfhe_hip_ctx *c;
+  ~Wipe() {
+    for (DevBuf *b : {&c->a.dev, &c->b.dev, &c->c.dev, &c->idx.dev})
+      if (b->p) (void)hipMemsetAsync(b->p, 0, b->cap < 65536 ? b->cap : 65536, c->stream);
+    (void)hipStreamSynchronize(c->stream);
+  }
+};
+struct StagedSecrets {
+  Wipe wipe;                    // first: in place before anything secret is staged
+  const uint32_t *d_k0, *d_k1;  // key_lv0 [n] in a, key_lv1 [N] in b
+  const double2 *d_spec;        // the spectrum of key_lv1 in c
+  ChaChaKey *d_rk;              // the generator key at idx[0, 32); idx holds `idx_bytes`
+};
+// Use: `StagedSecrets s{{ctx}}; CHK(stage_secrets(ctx, ..., s));`.  The generator key travels in a device buffer (not
+// in kernel-argument memory) and is wiped with the other secrets.
+int stage_secrets(tfhe_hip_ctx *ctx, const uint32_t *key_lv0, const uint32_t *key_lv1, const ChaChaKey &rk, size_t idx_bytes,
+                  StagedSecrets &s) {
+  CHK(to_dev(ctx, ctx->a, key_lv0, (size_t)ctx->P.n * 4));
+  CHK(to_dev(ctx, ctx->b, key_lv1, (size_t)kN * 4));
+  CHK(ensure(ctx, ctx->c.dev, (size_t)kN2 * sizeof(double2)));
+  s.d_k0 = (const uint32_t *)ctx->a.dev.p;
+  s.d_k1 = (const uint32_t *)ctx->b.dev.p;
+  hipLaunchKernelGGL(k_key_spectrum, dim3(1), dim3(64), kStageLdsBytes, ctx->stream, s.d_k1, ctx->d_tw, (double2 *)ctx->c.dev.p);
+  HIPCHK(ctx, hipGetLastError());
+  s.d_spec = (const double2 *)ctx->c.dev.p;
+  CHK(ensure(ctx, ctx->idx.dev, idx_bytes));
+  HIPCHK(ctx, hipMemcpy(ctx->idx.dev.p, &rk, sizeof(ChaChaKey), hipMemcpyHostToDevice));  // synchronous: rk is the caller's stack
+  s.d_rk = (ChaChaKey *)ctx->idx.dev.p;
+  return TFHE_HIP_OK;
+}
+
+// what a generated key gets: the decomposition offset (key.rs:78-89) and the test vector (key.rs:91-100), uploaded
+int default_offset_and_testvec(tfhe_hip_ctx *ctx, uint32_t *offset) {
+  const tfhe_hip_params &P = ctx->P;
+  uint32_t off = 0;
+  for (int i = 0; i < P.l; ++i) off += ((1u << P.bgbit) / 2) * (1u << (32 - (i + 1) * P.bgbit));
+  std::vector<uint32_t> tv(2 * kN, 0u);
+  for (int i = 0; i < kN; ++i) tv[kN + i] = 0x20000000u;  // f64_to_torus(0.125)
+  HIPCHK(ctx, hipMemcpyAsync(ctx->K->d_testvec, tv.data(), key_testvec_bytes(), hipMemcpyHostToDevice, ctx->stream));
+  HIPCHK(ctx, hipStreamSynchronize(ctx->stream));  // (the local test vector above is read by an asynchronous copy)
+  *offset = off;
+  return TFHE_HIP_OK;
+}
+
+// the kernel's CSPRNG, as the reference's thread_rng is seeded (OsRng)
+int os_random(uint8_t *buf, size_t bytes) {  // 0, or errno
+  size_t got = 0;
+  while (got < bytes) {
+    const ssize_t r = getrandom(buf + got, bytes - got, 0);
+    if (r < 0) {
+      if (errno == EINTR) continue;
+      return errno;
+    }
+    got += (size_t)r;
+  }
+  return 0;
+}
+std::string os_random_text(int err) { return std::string("getrandom: ") + strerror(err); }
+
+}  // namespace

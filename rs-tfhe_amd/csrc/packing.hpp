@@ -257,23 +257,16 @@ int tfhe_hip_load_packing_key(tfhe_hip_ctx *ctx, const uint8_t mask_seed[32], co
   const size_t chunks = pk_plane_bytes(P.n, P.t) / 16;
   ctx->K->pk_loaded = false;
   if (!ctx->K->d_pk8) HIPCHK(ctx, hipMalloc((void **)&ctx->K->d_pk8, pk_plane_bytes(P.n, P.t)));
-  uint32_t *d_tmp = nullptr;  // bodies [n t][N], then the rows [n t][2][N]
-  HIPCHK(ctx, hipMalloc((void **)&d_tmp, (body_words + rows * 2 * kN) * 4));
-  hipError_t e = hipMemcpyAsync(d_tmp, bodies, body_words * 4, hipMemcpyHostToDevice, ctx->stream);
-  if (e == hipSuccess) {
+  // the temporary: bodies [n t][N], then the rows [n t][2][N]
+  CHK(upload_through_temp(ctx, "packing key", {{bodies, body_words * 4}}, rows * 2 * kN * 4, [&](void *tmp) {
+    uint32_t *d_tmp = (uint32_t *)tmp;
     hipLaunchKernelGGL(k_pack_expand_key<64>, dim3((unsigned)rows), dim3(64), 0, ctx->stream, d_tmp, d_tmp + body_words,
                        seed_key(mask_seed));
-    e = hipGetLastError();
-  }
-  if (e == hipSuccess) {
+    if (const hipError_t e = hipGetLastError()) return e;
     hipLaunchKernelGGL(k_pack_planes<256>, dim3((unsigned)((chunks + 255) / 256)), dim3(256), 0, ctx->stream,
                        d_tmp + body_words, ctx->K->d_pk8, P.n, P.t, chunks);
-    e = hipGetLastError();
-  }
-  const hipError_t es = hipStreamSynchronize(ctx->stream);
-  if (e == hipSuccess) e = es;
-  (void)hipFree(d_tmp);
-  if (e != hipSuccess) return fail(ctx, TFHE_HIP_EHIP, std::string("packing key upload: ") + hipGetErrorString(e));
+    return hipGetLastError();
+  }));
   ctx->K->pk_loaded = true;
   return TFHE_HIP_OK;
 }

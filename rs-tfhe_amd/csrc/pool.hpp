@@ -89,26 +89,12 @@ int clone_key(tfhe_hip_ctx *dst, tfhe_hip_ctx *src) {
   const int src_device = src->device;
   tfhe_hip_ctx *ctx = dst;
   ENTER(ctx);
-  if (ctx->scratch_owned) HIPCHK(ctx, hipStreamSynchronize(ctx->scratch_owner));
-  HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-  ctx->scratch_owned = false;
-  comb_quiesce(ctx);
-  const tfhe_hip_params &P = ctx->P;
-  const size_t bsk_bytes = (size_t)P.n * 2 * P.l * 2 * kN * sizeof(double);
-  const size_t ksk_bytes = (size_t)kN * P.t * (1u << P.basebit) * ksk_row_words(P.n) * 4;
-  ctx->K->key_loaded = ctx->K->reenc_loaded = false;
-  if (!ctx->K->d_bsk) HIPCHK(ctx, hipMalloc((void **)&ctx->K->d_bsk, bsk_bytes));
-  if (!ctx->K->d_ksk) HIPCHK(ctx, hipMalloc((void **)&ctx->K->d_ksk, ksk_bytes + 4096));
-  if (!ctx->K->d_testvec) HIPCHK(ctx, hipMalloc((void **)&ctx->K->d_testvec, 2 * kN * 4));
-  HIPCHK(ctx, hipMemcpyPeer(ctx->K->d_bsk, ctx->device, from->d_bsk, src_device, bsk_bytes));
-  HIPCHK(ctx, hipMemcpyPeer(ctx->K->d_ksk, ctx->device, from->d_ksk, src_device, ksk_bytes));
-  HIPCHK(ctx, hipMemcpyPeer(ctx->K->d_testvec, ctx->device, from->d_testvec, src_device, 2 * kN * 4));
+  CHK(begin_key_change(ctx, KEY_BUF_ALL));
+  HIPCHK(ctx, hipMemcpyPeer(ctx->K->d_bsk, ctx->device, from->d_bsk, src_device, bsk_bytes(ctx->P)));
+  HIPCHK(ctx, hipMemcpyPeer(ctx->K->d_ksk, ctx->device, from->d_ksk, src_device, ksk_bytes(ctx->P)));
+  HIPCHK(ctx, hipMemcpyPeer(ctx->K->d_testvec, ctx->device, from->d_testvec, src_device, key_testvec_bytes()));
   HIPCHK(ctx, hipDeviceSynchronize());
-  CHK(build_ksk_planes(ctx));
-  ctx->K->offset = from->offset;
-  ctx->K->key_loaded = true;
-  comb_prepare(ctx);
-  return TFHE_HIP_OK;
+  return commit_cloud_key(ctx, from->offset);
 }
 
 // ---- RCCL over xGMI: one persistent communicator per pool -------------------------------------------------------
@@ -214,27 +200,13 @@ void pool_drop_comms(tfhe_hip_pool *p) {
 int prepare_replica(tfhe_hip_ctx *member) {
   tfhe_hip_ctx *ctx = member;
   ENTER(ctx);
-  if (ctx->scratch_owned) HIPCHK(ctx, hipStreamSynchronize(ctx->scratch_owner));
-  HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-  ctx->scratch_owned = false;
-  comb_quiesce(ctx);
-  const tfhe_hip_params &P = ctx->P;
-  ctx->K->key_loaded = ctx->K->reenc_loaded = false;
-  if (!ctx->K->d_bsk) HIPCHK(ctx, hipMalloc((void **)&ctx->K->d_bsk, (size_t)P.n * 2 * P.l * 2 * kN * sizeof(double)));
-  if (!ctx->K->d_ksk)
-    HIPCHK(ctx, hipMalloc((void **)&ctx->K->d_ksk, (size_t)kN * P.t * (1u << P.basebit) * ksk_row_words(P.n) * 4 + 4096));
-  if (!ctx->K->d_testvec) HIPCHK(ctx, hipMalloc((void **)&ctx->K->d_testvec, 2 * kN * 4));
-  return TFHE_HIP_OK;
+  return begin_key_change(ctx, KEY_BUF_ALL);
 }
 int finish_replica(tfhe_hip_ctx *member, uint32_t offset) {
   tfhe_hip_ctx *ctx = member;
   ENTER(ctx);
   HIPCHK(ctx, hipDeviceSynchronize());
-  CHK(build_ksk_planes(ctx));
-  ctx->K->offset = offset;
-  ctx->K->key_loaded = true;
-  comb_prepare(ctx);
-  return TFHE_HIP_OK;
+  return commit_cloud_key(ctx, offset);
 }
 
 // true: every member holds member 0's key.  false: nothing usable happened (members >= 1 may hold garbage and are
@@ -250,8 +222,7 @@ bool replicate_key_rccl(tfhe_hip_pool *p) {
   int prev = -1;
   (void)hipGetDevice(&prev);
   const tfhe_hip_params &P = p->ctxs[0]->P;
-  const size_t bytes[3] = {(size_t)P.n * 2 * P.l * 2 * kN * sizeof(double),
-                           (size_t)kN * P.t * (1u << P.basebit) * ksk_row_words(P.n) * 4, (size_t)2 * kN * 4};
+  const size_t bytes[3] = {bsk_bytes(P), ksk_bytes(P), key_testvec_bytes()};
   // the members' own mutexes: a member borrowed with tfhe_hip_pool_ctx() and used from another thread waits
   std::vector<std::unique_lock<FairMutex>> held;
   for (int i = 0; i < n; ++i) {

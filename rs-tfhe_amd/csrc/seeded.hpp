@@ -262,35 +262,16 @@ ChaChaKey seed_key(const uint8_t seed[32]) {
   return k;
 }
 
-// The engine layouts from the bodies at d_bsk_bodies [n][2l][N] / d_ksk_bodies [N][t][base] and the masks of `seed`;
-// then the key switch's planes.  ctx->mu held, buffers allocated, on ctx->stream.
-int expand_key_locked(tfhe_hip_ctx *ctx, const ChaChaKey &seed, const uint32_t *d_bsk_bodies, const uint32_t *d_ksk_bodies) {
+// Queues, on ctx->stream, the engine layouts from the bodies at d_bsk_bodies [n][2l][N] / d_ksk_bodies [N][t][base] and
+// the masks of `seed`.  ctx->mu held, key buffers allocated (begin_key_change).
+hipError_t expand_key_locked(tfhe_hip_ctx *ctx, const ChaChaKey &seed, const uint32_t *d_bsk_bodies, const uint32_t *d_ksk_bodies) {
   const tfhe_hip_params &P = ctx->P;
   hipLaunchKernelGGL(k_expand_bsk<64>, dim3((unsigned)(P.n * 2 * P.l)), dim3(64), kStageLdsBytes, ctx->stream, d_bsk_bodies,
                      ctx->d_tw, ctx->K->d_bsk, seed, key_scale(ctx->dispatch.fast_round));
-  HIPCHK(ctx, hipGetLastError());
-  hipLaunchKernelGGL(k_expand_ksk<256>, dim3((unsigned)((size_t)kN * P.t * (1u << P.basebit))), dim3(256), 0, ctx->stream,
-                     d_ksk_bodies, ctx->K->d_ksk, P.n, P.basebit, seed);
-  HIPCHK(ctx, hipGetLastError());
-  HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-  return build_ksk_planes(ctx);
-}
-
-// The preamble of every key change: drain what may still read the old key, clear the flags, allocate the key buffers.
-// A copy of the opening steps of tfhe_hip_load_cloud_key and gen_cloud_key_locked (tfhe_hip.hip), which keep their
-// own: a change to one of the three belongs in all of them.
-int begin_key_change(tfhe_hip_ctx *ctx) {
-  if (ctx->scratch_owned) HIPCHK(ctx, hipStreamSynchronize(ctx->scratch_owner));
-  HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-  ctx->scratch_owned = false;
-  comb_quiesce(ctx);
-  const tfhe_hip_params &P = ctx->P;
-  ctx->K->key_loaded = ctx->K->reenc_loaded = false;
-  if (!ctx->K->d_bsk) HIPCHK(ctx, hipMalloc((void **)&ctx->K->d_bsk, (size_t)P.n * 2 * P.l * 2 * kN * sizeof(double)));
-  if (!ctx->K->d_ksk)
-    HIPCHK(ctx, hipMalloc((void **)&ctx->K->d_ksk, (size_t)kN * P.t * (1u << P.basebit) * ksk_row_words(P.n) * 4 + 4096));
-  if (!ctx->K->d_testvec) HIPCHK(ctx, hipMalloc((void **)&ctx->K->d_testvec, 2 * kN * 4));
-  return TFHE_HIP_OK;
+  if (const hipError_t e = hipGetLastError()) return e;
+  hipLaunchKernelGGL(k_expand_ksk<256>, dim3((unsigned)ksk_rows(P)), dim3(256), 0, ctx->stream, d_ksk_bodies, ctx->K->d_ksk, P.n,
+                     P.basebit, seed);
+  return hipGetLastError();
 }
 
 // ctx->mu held, ctx's device current
@@ -298,32 +279,18 @@ int gen_compressed_locked(tfhe_hip_ctx *ctx, const uint32_t *key_lv0, const uint
                           double alpha_bsk, const ChaChaKey &rk, uint8_t mask_seed[32], uint32_t *bsk_bodies,
                           uint32_t *ksk_bodies, uint32_t *decomp_offset) {
   const tfhe_hip_params &P = ctx->P;
-  const size_t bsk_words = (size_t)P.n * 2 * P.l * kN, ksk_words = (size_t)kN * P.t * (1u << P.basebit);
-  CHK(begin_key_change(ctx));
-  // as in gen_cloud_key_locked: the secrets never outlive the call in the staging buffers
-  struct Wipe {
-    tfhe_hip_ctx *c;
-    ~Wipe() {
-      for (DevBuf *b : {&c->a.dev, &c->b.dev, &c->c.dev, &c->idx.dev})
-        if (b->p) (void)hipMemsetAsync(b->p, 0, b->cap < 65536 ? b->cap : 65536, c->stream);
-      (void)hipStreamSynchronize(c->stream);
-    }
-  } wipe{ctx};
-  CHK(to_dev(ctx, ctx->a, key_lv0, (size_t)P.n * 4));
-  CHK(to_dev(ctx, ctx->b, key_lv1, (size_t)kN * 4));
-  CHK(ensure(ctx, ctx->c.dev, (size_t)kN2 * sizeof(double2)));
-  const uint32_t *d_k0 = (const uint32_t *)ctx->a.dev.p, *d_k1 = (const uint32_t *)ctx->b.dev.p;
-  double2 *d_spec = (double2 *)ctx->c.dev.p;
-  hipLaunchKernelGGL(k_key_spectrum, dim3(1), dim3(64), kStageLdsBytes, ctx->stream, d_k1, ctx->d_tw, d_spec);
-  HIPCHK(ctx, hipGetLastError());
+  const size_t bsk_words = (size_t)P.n * 2 * P.l * kN, ksk_words = ksk_rows(P);
+  CHK(begin_key_change(ctx, KEY_BUF_ALL));
   // generator key at idx[0, 32), the mask seed derived from it at idx[32, 64)
-  CHK(ensure(ctx, ctx->idx.dev, 2 * sizeof(ChaChaKey)));
-  HIPCHK(ctx, hipMemcpy(ctx->idx.dev.p, &rk, sizeof(ChaChaKey), hipMemcpyHostToDevice));  // synchronous: rk is the caller's stack
-  const ChaChaKey *d_rk = (const ChaChaKey *)ctx->idx.dev.p;
-  hipLaunchKernelGGL(k_derive_mask_seed<64>, dim3(1), dim3(64), 0, ctx->stream, d_rk, (ChaChaKey *)ctx->idx.dev.p + 1);
+  StagedSecrets s{{ctx}};  // (wiped on every exit path)
+  CHK(stage_secrets(ctx, key_lv0, key_lv1, rk, 2 * sizeof(ChaChaKey), s));
+  const uint32_t *d_k0 = s.d_k0, *d_k1 = s.d_k1;
+  const double2 *d_spec = s.d_spec;
+  const ChaChaKey *d_rk = s.d_rk;
+  hipLaunchKernelGGL(k_derive_mask_seed<64>, dim3(1), dim3(64), 0, ctx->stream, d_rk, s.d_rk + 1);
   HIPCHK(ctx, hipGetLastError());
   ChaChaKey seed;
-  HIPCHK(ctx, hipMemcpyAsync(&seed, (ChaChaKey *)ctx->idx.dev.p + 1, sizeof(seed), hipMemcpyDeviceToHost, ctx->stream));
+  HIPCHK(ctx, hipMemcpyAsync(&seed, s.d_rk + 1, sizeof(seed), hipMemcpyDeviceToHost, ctx->stream));
   HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
   // bodies: public, in ctx->out
   CHK(ensure(ctx, ctx->out.dev, (bsk_words + ksk_words) * 4));
@@ -341,32 +308,11 @@ int gen_compressed_locked(tfhe_hip_ctx *ctx, const uint32_t *key_lv0, const uint
   HIPCHK(ctx, hipMemcpyAsync(bsk_bodies, d_bb, bsk_words * 4, hipMemcpyDeviceToHost, ctx->stream));
   HIPCHK(ctx, hipMemcpyAsync(ksk_bodies, d_kb, ksk_words * 4, hipMemcpyDeviceToHost, ctx->stream));
   // the context's key is what tfhe_hip_load_compressed_cloud_key rebuilds from these bodies, bit for bit
-  CHK(expand_key_locked(ctx, seed, d_bb, d_kb));
-  uint32_t off = 0;
-  for (int i = 0; i < P.l; ++i) off += ((1u << P.bgbit) / 2) * (1u << (32 - (i + 1) * P.bgbit));
-  std::vector<uint32_t> tv(2 * kN, 0u);
-  for (int i = 0; i < kN; ++i) tv[kN + i] = 0x20000000u;  // f64_to_torus(0.125)
-  HIPCHK(ctx, hipMemcpyAsync(ctx->K->d_testvec, tv.data(), 2 * kN * 4, hipMemcpyHostToDevice, ctx->stream));
+  HIPCHK(ctx, expand_key_locked(ctx, seed, d_bb, d_kb));
   HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+  CHK(default_offset_and_testvec(ctx, decomp_offset));
   memcpy(mask_seed, seed.k, 32);
-  *decomp_offset = off;
-  ctx->K->offset = off;
-  ctx->K->key_loaded = true;
-  comb_prepare(ctx);
-  return TFHE_HIP_OK;
-}
-
-int os_random(uint8_t *buf, size_t bytes) {  // 0, or errno
-  size_t got = 0;
-  while (got < bytes) {
-    const ssize_t r = getrandom(buf + got, bytes - got, 0);
-    if (r < 0) {
-      if (errno == EINTR) continue;
-      return errno;
-    }
-    got += (size_t)r;
-  }
-  return 0;
+  return commit_cloud_key(ctx, *decomp_offset);
 }
 }  // namespace
 
@@ -383,7 +329,7 @@ int tfhe_hip_gen_compressed_cloud_key(tfhe_hip_ctx *ctx, const uint32_t *key_lv0
   if (rng_key) {
     memcpy(k.k, rng_key, 32);
   } else if (const int err = os_random((uint8_t *)k.k, sizeof(k.k))) {
-    return fail(ctx, TFHE_HIP_EHIP, std::string("getrandom: ") + strerror(err));
+    return fail(ctx, TFHE_HIP_EHIP, os_random_text(err));
   }
   const int rc = gen_compressed_locked(ctx, key_lv0, key_lv1, alpha_ksk, alpha_bsk, k, mask_seed, bsk_bodies, ksk_bodies,
                                        decomp_offset);
@@ -397,26 +343,16 @@ int tfhe_hip_load_compressed_cloud_key(tfhe_hip_ctx *ctx, const uint8_t mask_see
   if (!ctx) return TFHE_HIP_EINVAL;
   ENTER(ctx);
   if (!mask_seed || !bsk_bodies || !ksk_bodies || !testvec) return fail(ctx, TFHE_HIP_EINVAL, "null key pointer");
-  CHK(begin_key_change(ctx));
+  CHK(begin_key_change(ctx, KEY_BUF_ALL));
   const tfhe_hip_params &P = ctx->P;
-  const size_t bsk_words = (size_t)P.n * 2 * P.l * kN, ksk_words = (size_t)kN * P.t * (1u << P.basebit);
+  const size_t bsk_words = (size_t)P.n * 2 * P.l * kN, ksk_words = ksk_rows(P);
   // the bodies travel (17 MB instead of 172 on SECURITY_128_BIT); the masks are regenerated on the device
-  uint32_t *d_bodies = nullptr;
-  HIPCHK(ctx, hipMalloc((void **)&d_bodies, (bsk_words + ksk_words) * 4));
-  hipError_t e = hipMemcpyAsync(d_bodies, bsk_bodies, bsk_words * 4, hipMemcpyHostToDevice, ctx->stream);
-  if (e == hipSuccess) e = hipMemcpyAsync(d_bodies + bsk_words, ksk_bodies, ksk_words * 4, hipMemcpyHostToDevice, ctx->stream);
-  int rc = TFHE_HIP_OK;
-  if (e == hipSuccess) rc = expand_key_locked(ctx, seed_key(mask_seed), d_bodies, d_bodies + bsk_words);
-  else (void)hipStreamSynchronize(ctx->stream);
-  (void)hipFree(d_bodies);
-  if (e != hipSuccess) return fail(ctx, TFHE_HIP_EHIP, std::string("key bodies upload: ") + hipGetErrorString(e));
-  CHK(rc);
-  HIPCHK(ctx, hipMemcpyAsync(ctx->K->d_testvec, testvec, 2 * kN * 4, hipMemcpyHostToDevice, ctx->stream));
+  CHK(upload_through_temp(ctx, "key bodies", {{bsk_bodies, bsk_words * 4}, {ksk_bodies, ksk_words * 4}}, 0, [&](void *d_bodies) {
+    return expand_key_locked(ctx, seed_key(mask_seed), (const uint32_t *)d_bodies, (const uint32_t *)d_bodies + bsk_words);
+  }));
+  HIPCHK(ctx, hipMemcpyAsync(ctx->K->d_testvec, testvec, key_testvec_bytes(), hipMemcpyHostToDevice, ctx->stream));
   HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-  ctx->K->offset = decomp_offset;
-  ctx->K->key_loaded = true;
-  comb_prepare(ctx);
-  return TFHE_HIP_OK;
+  return commit_cloud_key(ctx, decomp_offset);
 }
 
 namespace {

@@ -161,6 +161,8 @@ struct KeyState {
   unsigned char *d_pk8 = nullptr;  // the packing key as byte planes (packing.hpp): beside, not part of, the cloud key
   bool pk_loaded = false;          // (a cloud-key load or change leaves it; freeing the key view frees it)
   uint32_t offset = 0;
+  // The flags are written in key_change.hpp only: begin_key_change clears both, commit_cloud_key sets key_loaded (and
+  // clears reenc_loaded), commit_reenc_key sets reenc_loaded.  pk_loaded is tfhe_hip_load_packing_key's alone.
   bool key_loaded = false;
   bool reenc_loaded = false;  // d_ksk (+ d_ksk8) hold a proxy re-encryption key (proxy_reenc.rs:224-233) instead of a cloud key's
 };
@@ -803,7 +805,7 @@ KsPlan plan_key_switch(const tfhe_hip_ctx *ctx, size_t count) {
   return pl;
 }
 
-// (re)build the byte planes from the u32 engine key; called wherever a key becomes current
+// (re)build the byte planes from the u32 engine key; called where a key becomes current (key_change.hpp's commits)
 int build_ksk_planes(tfhe_hip_ctx *ctx) {
   if (!ks_mfma_possible(ctx->P) || (ctx->dispatch.ks_force && ctx->dispatch.ks_force - 1 != KS_MFMA)) return TFHE_HIP_OK;
   const tfhe_hip_params &P = ctx->P;
@@ -1156,6 +1158,7 @@ int launched(tfhe_hip_ctx *ctx) {  // status of the kernel launch just made
 }  // namespace
 
 #include "combine.hpp"
+#include "key_change.hpp"
 
 namespace {
 bool comb_interactive(const tfhe_hip_ctx *ctx) {
@@ -1191,7 +1194,7 @@ namespace {
 bool params_supported(const tfhe_hip_params *p) {
   return !(p->n < 1 || p->n > 1279 || p->l < 1 || p->l > 3 || p->bgbit < 1 || p->l * p->bgbit > 32 ||
            p->basebit < 1 || p->basebit > 10 || p->t < 1 || p->basebit * p->t > 31 ||
-           (double)kN * p->t * (double)(1u << p->basebit) * ksk_row_words(p->n) * 4.0 >= 4294967296.0);
+           (double)ksk_bytes(*p) >= 4294967296.0);
 }
 }  // namespace
 
@@ -1419,6 +1422,7 @@ void tfhe_hip_ctx_destroy(tfhe_hip_ctx *ctx) {
     {
       std::lock_guard<FairMutex> lk(base->mu);
       DeviceGuard dg(base->device);
+      // (not drain_key_readers: that returns at the first failed synchronisation, and the key is freed here regardless)
       if (base->scratch_owned && base->scratch_owner != base->stream) (void)hipStreamSynchronize(base->scratch_owner);
       if (base->stream) (void)hipStreamSynchronize(base->stream);
       comb_quiesce(base);  // (merged launches run on the lanes' streams)
@@ -1496,54 +1500,23 @@ int tfhe_hip_load_cloud_key(tfhe_hip_ctx *ctx, const double *bsk, const uint32_t
   if (!ctx) return TFHE_HIP_EINVAL;
   ENTER(ctx);
   if (!bsk || !ksk || !testvec) return fail(ctx, TFHE_HIP_EINVAL, "null key pointer");
-  // Work queued earlier on the caller's streams (*_dev entry points) may still be reading the key this
-  // call is about to overwrite: drain it first.
-  if (ctx->scratch_owned) HIPCHK(ctx, hipStreamSynchronize(ctx->scratch_owner));
-  HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-  ctx->scratch_owned = false;
-  comb_quiesce(ctx);  // ... and merged launches on the front end's lanes
+  CHK(begin_key_change(ctx, KEY_BUF_ALL));
   const tfhe_hip_params &P = ctx->P;
-  const size_t polys = (size_t)P.n * 2 * P.l * 2;
-  const size_t bsk_bytes = polys * kN * sizeof(double);
+  const size_t polys = bsk_polys(P), rows = ksk_rows(P);
   const int base = 1 << P.basebit;
-  const size_t ksk_words = (size_t)kN * P.t * base * (size_t)(P.n + 1);
-  ctx->K->key_loaded = ctx->K->reenc_loaded = false;
-  if (!ctx->K->d_bsk) HIPCHK(ctx, hipMalloc((void **)&ctx->K->d_bsk, bsk_bytes));
-  if (!ctx->K->d_ksk)
-    HIPCHK(ctx, hipMalloc((void **)&ctx->K->d_ksk, (size_t)kN * P.t * base * ksk_row_words(P.n) * 4 + 4096));
-  if (!ctx->K->d_testvec) HIPCHK(ctx, hipMalloc((void **)&ctx->K->d_testvec, 2 * kN * 4));
   // bootstrapping key: upload the reference layout, permute + scale on the device
-  double *d_ref = nullptr;
-  HIPCHK(ctx, hipMalloc((void **)&d_ref, bsk_bytes));
-  hipError_t e = hipMemcpyAsync(d_ref, bsk, bsk_bytes, hipMemcpyHostToDevice, ctx->stream);
-  if (e == hipSuccess) {
-    hipLaunchKernelGGL(k_bsk_convert, dim3((unsigned)polys), dim3(512), 0, ctx->stream, d_ref, ctx->K->d_bsk, polys, key_scale(ctx->dispatch.fast_round));
-    e = hipGetLastError();
-  }
-  if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
-  (void)hipFree(d_ref);
-  if (e != hipSuccess) return fail(ctx, TFHE_HIP_EHIP, std::string("bsk upload: ") + hipGetErrorString(e));
+  CHK(upload_through_temp(ctx, "bsk", {{bsk, bsk_bytes(P)}}, 0, [&](void *d_ref) {
+    hipLaunchKernelGGL(k_bsk_convert, dim3((unsigned)polys), dim3(512), 0, ctx->stream, (const double *)d_ref, ctx->K->d_bsk, polys, key_scale(ctx->dispatch.fast_round));
+    return hipGetLastError();
+  }));
   // key-switching key: upload the reference layout, pad rows to 16 B and zero the k == 0 rows
-  {
-    const size_t rows = (size_t)kN * P.t * base;
-    uint32_t *d_kref = nullptr;
-    HIPCHK(ctx, hipMalloc((void **)&d_kref, ksk_words * 4));
-    hipError_t e2 = hipMemcpyAsync(d_kref, ksk, ksk_words * 4, hipMemcpyHostToDevice, ctx->stream);
-    if (e2 == hipSuccess) {
-      hipLaunchKernelGGL(k_ksk_convert, dim3((unsigned)rows), dim3(256), 0, ctx->stream, d_kref, ctx->K->d_ksk, P.n, base, rows);
-      e2 = hipGetLastError();
-    }
-    if (e2 == hipSuccess) e2 = hipStreamSynchronize(ctx->stream);
-    (void)hipFree(d_kref);
-    if (e2 != hipSuccess) return fail(ctx, TFHE_HIP_EHIP, std::string("ksk upload: ") + hipGetErrorString(e2));
-  }
-  HIPCHK(ctx, hipMemcpyAsync(ctx->K->d_testvec, testvec, 2 * kN * 4, hipMemcpyHostToDevice, ctx->stream));
+  CHK(upload_through_temp(ctx, "ksk", {{ksk, rows * (size_t)(P.n + 1) * 4}}, 0, [&](void *d_ref) {
+    hipLaunchKernelGGL(k_ksk_convert, dim3((unsigned)rows), dim3(256), 0, ctx->stream, (const uint32_t *)d_ref, ctx->K->d_ksk, P.n, base, rows);
+    return hipGetLastError();
+  }));
+  HIPCHK(ctx, hipMemcpyAsync(ctx->K->d_testvec, testvec, key_testvec_bytes(), hipMemcpyHostToDevice, ctx->stream));
   HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-  CHK(build_ksk_planes(ctx));
-  ctx->K->offset = decomp_offset;
-  ctx->K->key_loaded = true;
-  comb_prepare(ctx);
-  return TFHE_HIP_OK;
+  return commit_cloud_key(ctx, decomp_offset);
 }
 
 namespace {
@@ -1552,65 +1525,23 @@ int gen_cloud_key_locked(tfhe_hip_ctx *ctx, const uint32_t *key_lv0, const uint3
                          double alpha_bsk, const ChaChaKey &rk) {
   if (!key_lv0 || !key_lv1) return fail(ctx, TFHE_HIP_EINVAL, "null key pointer");
   if (!(alpha_ksk >= 0.0) || !(alpha_bsk >= 0.0)) return fail(ctx, TFHE_HIP_EINVAL, "negative noise parameter");
-  // Work queued earlier on the caller's streams (*_dev entry points) may still be reading the key this
-  // call is about to overwrite: drain it first.
-  if (ctx->scratch_owned) HIPCHK(ctx, hipStreamSynchronize(ctx->scratch_owner));
-  HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-  ctx->scratch_owned = false;
-  comb_quiesce(ctx);  // ... and merged launches on the front end's lanes
+  CHK(begin_key_change(ctx, KEY_BUF_ALL));
   const tfhe_hip_params &P = ctx->P;
-  const int base = 1 << P.basebit;
-  const size_t polys = (size_t)P.n * 2 * P.l * 2;
-  ctx->K->key_loaded = ctx->K->reenc_loaded = false;
-  if (!ctx->K->d_bsk) HIPCHK(ctx, hipMalloc((void **)&ctx->K->d_bsk, polys * kN * sizeof(double)));
-  if (!ctx->K->d_ksk)
-    HIPCHK(ctx, hipMalloc((void **)&ctx->K->d_ksk, (size_t)kN * P.t * base * ksk_row_words(P.n) * 4 + 4096));
-  if (!ctx->K->d_testvec) HIPCHK(ctx, hipMalloc((void **)&ctx->K->d_testvec, 2 * kN * 4));
-  // The secret keys, the spectrum of the ring key and the generator key do not outlive the call on the device,
-  // whichever way it ends: the guard zeroes the four staging buffers and drains the stream on every exit path
-  // (an early return would otherwise leave them in buffers that later batches reuse as plain staging space, and
-  // could return while an asynchronous copy still reads this frame).
-  struct Wipe {
-    tfhe_hip_ctx *c;
-    ~Wipe() {
-      for (DevBuf *b : {&c->a.dev, &c->b.dev, &c->c.dev, &c->idx.dev})
-        if (b->p) (void)hipMemsetAsync(b->p, 0, b->cap < 65536 ? b->cap : 65536, c->stream);
-      (void)hipStreamSynchronize(c->stream);
-    }
-  } wipe{ctx};
-  CHK(to_dev(ctx, ctx->a, key_lv0, (size_t)P.n * 4));
-  CHK(to_dev(ctx, ctx->b, key_lv1, (size_t)kN * 4));
-  CHK(ensure(ctx, ctx->c.dev, (size_t)kN2 * sizeof(double2)));
-  const uint32_t *d_k0 = (const uint32_t *)ctx->a.dev.p, *d_k1 = (const uint32_t *)ctx->b.dev.p;
-  double2 *d_spec = (double2 *)ctx->c.dev.p;
-  hipLaunchKernelGGL(k_key_spectrum, dim3(1), dim3(64), kStageLdsBytes, ctx->stream, d_k1, ctx->d_tw, d_spec);
-  HIPCHK(ctx, hipGetLastError());
-  // the generator key travels in a device buffer (not in kernel-argument memory) and is wiped with the other secrets
-  CHK(ensure(ctx, ctx->idx.dev, sizeof(ChaChaKey)));
-  HIPCHK(ctx, hipMemcpy(ctx->idx.dev.p, &rk, sizeof(ChaChaKey), hipMemcpyHostToDevice));  // synchronous: rk is the caller's stack
-  const ChaChaKey *d_rk = (const ChaChaKey *)ctx->idx.dev.p;
+  StagedSecrets s{{ctx}};  // (wiped on every exit path)
+  CHK(stage_secrets(ctx, key_lv0, key_lv1, rk, sizeof(ChaChaKey), s));
   const dim3 bgrid((unsigned)(P.n * 2 * P.l));
   switch (P.l) {
-    case 1: hipLaunchKernelGGL(k_gen_bsk<1>, bgrid, dim3(64), kStageLdsBytes, ctx->stream, d_k0, d_spec, ctx->d_tw, ctx->K->d_bsk, P.bgbit, alpha_bsk, d_rk, key_scale(ctx->dispatch.fast_round)); break;
-    case 2: hipLaunchKernelGGL(k_gen_bsk<2>, bgrid, dim3(64), kStageLdsBytes, ctx->stream, d_k0, d_spec, ctx->d_tw, ctx->K->d_bsk, P.bgbit, alpha_bsk, d_rk, key_scale(ctx->dispatch.fast_round)); break;
-    default: hipLaunchKernelGGL(k_gen_bsk<3>, bgrid, dim3(64), kStageLdsBytes, ctx->stream, d_k0, d_spec, ctx->d_tw, ctx->K->d_bsk, P.bgbit, alpha_bsk, d_rk, key_scale(ctx->dispatch.fast_round)); break;
+    case 1: hipLaunchKernelGGL(k_gen_bsk<1>, bgrid, dim3(64), kStageLdsBytes, ctx->stream, s.d_k0, s.d_spec, ctx->d_tw, ctx->K->d_bsk, P.bgbit, alpha_bsk, s.d_rk, key_scale(ctx->dispatch.fast_round)); break;
+    case 2: hipLaunchKernelGGL(k_gen_bsk<2>, bgrid, dim3(64), kStageLdsBytes, ctx->stream, s.d_k0, s.d_spec, ctx->d_tw, ctx->K->d_bsk, P.bgbit, alpha_bsk, s.d_rk, key_scale(ctx->dispatch.fast_round)); break;
+    default: hipLaunchKernelGGL(k_gen_bsk<3>, bgrid, dim3(64), kStageLdsBytes, ctx->stream, s.d_k0, s.d_spec, ctx->d_tw, ctx->K->d_bsk, P.bgbit, alpha_bsk, s.d_rk, key_scale(ctx->dispatch.fast_round)); break;
   }
   HIPCHK(ctx, hipGetLastError());
-  hipLaunchKernelGGL(k_gen_ksk, dim3((unsigned)((size_t)kN * P.t * base)), dim3(256), 0, ctx->stream, d_k0, d_k1,
-                     ctx->K->d_ksk, P.n, P.basebit, P.t, alpha_ksk, d_rk);
+  hipLaunchKernelGGL(k_gen_ksk, dim3((unsigned)ksk_rows(P)), dim3(256), 0, ctx->stream, s.d_k0, s.d_k1,
+                     ctx->K->d_ksk, P.n, P.basebit, P.t, alpha_ksk, s.d_rk);
   HIPCHK(ctx, hipGetLastError());
-  // decomposition offset (key.rs:78-89) and test vector (key.rs:91-100)
   uint32_t off = 0;
-  for (int i = 0; i < P.l; ++i) off += ((1u << P.bgbit) / 2) * (1u << (32 - (i + 1) * P.bgbit));
-  std::vector<uint32_t> tv(2 * kN, 0u);
-  for (int i = 0; i < kN; ++i) tv[kN + i] = 0x20000000u;  // f64_to_torus(0.125)
-  HIPCHK(ctx, hipMemcpyAsync(ctx->K->d_testvec, tv.data(), 2 * kN * 4, hipMemcpyHostToDevice, ctx->stream));
-  HIPCHK(ctx, hipStreamSynchronize(ctx->stream));  // (the local test vector above is read by an asynchronous copy)
-  CHK(build_ksk_planes(ctx));
-  ctx->K->offset = off;
-  ctx->K->key_loaded = true;
-  comb_prepare(ctx);
-  return TFHE_HIP_OK;
+  CHK(default_offset_and_testvec(ctx, &off));
+  return commit_cloud_key(ctx, off);
 }
 
 // 64-bit seed -> 256-bit generator key (SplitMix64): reproducible, and only as strong as the seed
@@ -1654,16 +1585,10 @@ int tfhe_hip_gen_cloud_key_secure(tfhe_hip_ctx *ctx, const uint32_t *key_lv0, co
                                   double alpha_ksk, double alpha_bsk) {
   if (!ctx) return TFHE_HIP_EINVAL;
   uint8_t buf[32];
-  size_t got = 0;
-  while (got < sizeof(buf)) {  // the kernel's CSPRNG, as the reference's thread_rng is seeded (OsRng)
-    const ssize_t r = getrandom(buf + got, sizeof(buf) - got, 0);
-    if (r < 0) {
-      if (errno == EINTR) continue;
-      tfhe_hip_ctx *base = ctx->parent ? ctx->parent : ctx;
-      std::lock_guard<FairMutex> lk(base->mu);
-      return fail(base, TFHE_HIP_EHIP, std::string("getrandom: ") + strerror(errno));
-    }
-    got += (size_t)r;
+  if (const int err = os_random(buf, sizeof(buf))) {
+    tfhe_hip_ctx *base = ctx->parent ? ctx->parent : ctx;
+    std::lock_guard<FairMutex> lk(base->mu);
+    return fail(base, TFHE_HIP_EHIP, os_random_text(err));
   }
   const int rc = tfhe_hip_gen_cloud_key_with_key(ctx, key_lv0, key_lv1, alpha_ksk, alpha_bsk, buf);
   volatile uint8_t *wipe = buf;
@@ -1678,16 +1603,15 @@ int tfhe_hip_export_cloud_key(tfhe_hip_ctx *ctx, double *bsk, uint32_t *ksk, uin
   ENTER(ctx);
   CHK(need_key(ctx));
   const tfhe_hip_params &P = ctx->P;
-  const int base = 1 << P.basebit;
   if (bsk) {
-    const size_t polys = (size_t)P.n * 2 * P.l * 2;
-    CHK(ensure(ctx, ctx->out.dev, polys * kN * sizeof(double)));
+    const size_t polys = bsk_polys(P);
+    CHK(ensure(ctx, ctx->out.dev, bsk_bytes(P)));
     hipLaunchKernelGGL(k_bsk_export, dim3((unsigned)polys), dim3(512), 0, ctx->stream, ctx->K->d_bsk, (double *)ctx->out.dev.p, polys, 1.0 / key_scale(ctx->dispatch.fast_round));
     HIPCHK(ctx, hipGetLastError());
-    CHK(to_host(ctx, bsk, ctx->out, polys * kN * sizeof(double)));
+    CHK(to_host(ctx, bsk, ctx->out, bsk_bytes(P)));
   }
   if (ksk) {
-    const size_t rows = (size_t)kN * P.t * base;
+    const size_t rows = ksk_rows(P);
     CHK(ensure(ctx, ctx->out.dev, rows * (size_t)(P.n + 1) * 4));
     hipLaunchKernelGGL(k_ksk_export, dim3((unsigned)rows), dim3(256), 0, ctx->stream, ctx->K->d_ksk, (uint32_t *)ctx->out.dev.p, P.n, rows);
     HIPCHK(ctx, hipGetLastError());
@@ -1695,7 +1619,7 @@ int tfhe_hip_export_cloud_key(tfhe_hip_ctx *ctx, double *bsk, uint32_t *ksk, uin
   }
   if (decomp_offset) *decomp_offset = ctx->K->offset;
   if (testvec) {
-    HIPCHK(ctx, hipMemcpyAsync(testvec, ctx->K->d_testvec, 2 * kN * 4, hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(ctx, hipMemcpyAsync(testvec, ctx->K->d_testvec, key_testvec_bytes(), hipMemcpyDeviceToHost, ctx->stream));
     HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
   }
   return TFHE_HIP_OK;
@@ -1705,18 +1629,13 @@ int tfhe_hip_cloud_key_buffers(tfhe_hip_ctx *ctx, void **bsk, size_t *bsk_bytes,
                                void **testvec, size_t *testvec_bytes, uint32_t *decomp_offset) {
   if (!ctx) return TFHE_HIP_EINVAL;
   ENTER(ctx);
-  const tfhe_hip_params &P = ctx->P;
-  const size_t bb = (size_t)P.n * 2 * P.l * 2 * kN * sizeof(double);
-  const size_t kb = (size_t)kN * P.t * (1u << P.basebit) * ksk_row_words(P.n) * 4;
-  if (!ctx->K->d_bsk) HIPCHK(ctx, hipMalloc((void **)&ctx->K->d_bsk, bb));
-  if (!ctx->K->d_ksk) HIPCHK(ctx, hipMalloc((void **)&ctx->K->d_ksk, kb + 4096));
-  if (!ctx->K->d_testvec) HIPCHK(ctx, hipMalloc((void **)&ctx->K->d_testvec, 2 * kN * 4));
+  CHK(ensure_key_buffers(ctx, KEY_BUF_ALL));
   if (bsk) *bsk = ctx->K->d_bsk;
-  if (bsk_bytes) *bsk_bytes = bb;
+  if (bsk_bytes) *bsk_bytes = ::bsk_bytes(ctx->P);  // (the parameters carry the header's names, which are the size functions')
   if (ksk) *ksk = ctx->K->d_ksk;
-  if (ksk_bytes) *ksk_bytes = kb;
+  if (ksk_bytes) *ksk_bytes = ::ksk_bytes(ctx->P);
   if (testvec) *testvec = ctx->K->d_testvec;
-  if (testvec_bytes) *testvec_bytes = 2 * kN * 4;
+  if (testvec_bytes) *testvec_bytes = key_testvec_bytes();
   if (decomp_offset) *decomp_offset = ctx->K->offset;
   return TFHE_HIP_OK;
 }
@@ -1729,12 +1648,7 @@ int tfhe_hip_adopt_cloud_key(tfhe_hip_ctx *ctx, uint32_t decomp_offset) {
   // whatever filled the buffers (a peer copy, an RCCL broadcast on another stream) must have finished
   comb_quiesce(ctx);
   HIPCHK(ctx, hipDeviceSynchronize());
-  CHK(build_ksk_planes(ctx));
-  ctx->K->offset = decomp_offset;
-  ctx->K->key_loaded = true;
-  comb_prepare(ctx);
-  ctx->K->reenc_loaded = false;
-  return TFHE_HIP_OK;
+  return commit_cloud_key(ctx, decomp_offset);
 }
 
 // ---- device-pointer entry points ---------------------------------------------
@@ -2123,29 +2037,16 @@ int tfhe_hip_load_reenc_key(tfhe_hip_ctx *ctx, const uint32_t *key) {
   const tfhe_hip_params &P = ctx->P;
   // the source rides in the key switch's N-coefficient rows (k_reenc_pad): SECURITY_UINT5 .. 8 (n = 1071 / 1160) do not fit
   if (P.n > kN) return fail(ctx, TFHE_HIP_EINVAL, "proxy re-encryption needs n <= N = 1024 (this parameter set's n is larger)");
-  if (ctx->scratch_owned) HIPCHK(ctx, hipStreamSynchronize(ctx->scratch_owner));
-  HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-  ctx->scratch_owned = false;
-  comb_quiesce(ctx);  // ... and merged launches on the front end's lanes
+  CHK(begin_key_change(ctx, KEY_BUF_KSK));  // (both flags go: the buffer is shared with a cloud key's key-switching key)
   const int base = 1 << P.basebit;
-  const size_t eng_bytes = (size_t)kN * P.t * base * ksk_row_words(P.n) * 4;
-  const size_t rows = (size_t)P.n * P.t * base, words = rows * (size_t)(P.n + 1);
-  ctx->K->key_loaded = ctx->K->reenc_loaded = false;  // the buffer is shared with a cloud key's key-switching key
-  if (!ctx->K->d_ksk) HIPCHK(ctx, hipMalloc((void **)&ctx->K->d_ksk, eng_bytes + 4096));
-  uint32_t *d_ref = nullptr;
-  HIPCHK(ctx, hipMalloc((void **)&d_ref, words * 4));
-  hipError_t e = hipMemsetAsync(ctx->K->d_ksk, 0, eng_bytes, ctx->stream);
-  if (e == hipSuccess) e = hipMemcpyAsync(d_ref, key, words * 4, hipMemcpyHostToDevice, ctx->stream);
-  if (e == hipSuccess) {
-    hipLaunchKernelGGL(k_ksk_convert, dim3((unsigned)rows), dim3(256), 0, ctx->stream, d_ref, ctx->K->d_ksk, P.n, base, rows);
-    e = hipGetLastError();
-  }
-  if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
-  (void)hipFree(d_ref);
-  if (e != hipSuccess) return fail(ctx, TFHE_HIP_EHIP, std::string("re-encryption key upload: ") + hipGetErrorString(e));
-  CHK(build_ksk_planes(ctx));
-  ctx->K->reenc_loaded = true;
-  return TFHE_HIP_OK;
+  const size_t rows = (size_t)P.n * P.t * base;
+  if (const hipError_t e = hipMemsetAsync(ctx->K->d_ksk, 0, ksk_bytes(P), ctx->stream))
+    return fail(ctx, TFHE_HIP_EHIP, std::string("re-encryption key upload: ") + hipGetErrorString(e));
+  CHK(upload_through_temp(ctx, "re-encryption key", {{key, rows * (size_t)(P.n + 1) * 4}}, 0, [&](void *d_ref) {
+    hipLaunchKernelGGL(k_ksk_convert, dim3((unsigned)rows), dim3(256), 0, ctx->stream, (const uint32_t *)d_ref, ctx->K->d_ksk, P.n, base, rows);
+    return hipGetLastError();
+  }));
+  return commit_reenc_key(ctx);
 }
 
 int tfhe_hip_reenc_key_is_loaded(tfhe_hip_ctx *ctx) {  // 0 / 1, never an error code (no device call is made)
