@@ -1,6 +1,7 @@
 """Seeded (compressed) cloud keys and ciphertexts on the GPU: a CPU-made compressed key expanded by
 tfhe_hip_load_compressed_cloud_key is word for word the CPU expansion; tfhe_hip_gen_compressed_cloud_key makes the
-same seed and bodies as the CPU compressor at zero noise and leaves the key load_compressed rebuilds; gates on such a
+same seed and bodies as the CPU compressor at zero noise, at real noise the zero-noise bodies plus the model's noise
+sample for sample, and leaves the key load_compressed rebuilds; gates on such a
 key are bit-identical to gates on the full key (and to the CPU oracle); key views, pools, seeded inputs, the C++
 mirror and the EINVAL cases."""
 import ctypes
@@ -84,6 +85,16 @@ def test_gpu_generation_equals_cpu_generation():
         for d, alpha in ((dk, P.alpha_lv0), (db, P.alpha_lv1)):
             d = d.astype(np.float64) / 2.0 ** 32
             assert 0.8 * alpha < d.std() < 1.2 * alpha and np.abs(d).max() < 7 * alpha + 2.0 ** -31
+        # ... and IS the model's noise, sample for sample (tests/keygen_model.py): the noise is additive in both bodies,
+        # so they are the zero-noise bodies plus f64_to_torus(g) of streams 17 / 19 under K -- off by one LSB only
+        # where the long-double sampler marks a sample borderline, at most 16 words in the key
+        import keygen_model as KM
+
+        ek, eb = KM.compressed_noise(P, K)
+        mb, bb = KM.compare_words(ck.bsk_bodies, cpu0.bsk_bodies + eb.words, eb.border, "SECURITY_128_BIT BSK bodies")
+        mk, bk = KM.compare_words(ck.ksk_bodies, cpu0.ksk_bodies + ek.words, ek.border, "SECURITY_128_BIT KSK bodies")
+        print(f"KEYGEN SECURITY_128_BIT compressed: mismatches {mb} + {mk}, borderline samples {bb} + {bk}")
+        assert mb + mk <= KM.MAX_MISMATCHES
         # GPU-made keys with a drawn generator key differ from call to call
         r1 = a.gen_compressed_cloud_key(sk.key_lv0, sk.key_lv1)
         r2 = a.gen_compressed_cloud_key(sk.key_lv0, sk.key_lv1)

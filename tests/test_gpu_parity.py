@@ -1226,7 +1226,8 @@ def test_gpu_key_generation(O, keys128):
     """CloudKey::new on the GPU (key.rs:59-66).  RNG streams differ from the host generator, so the
     bar is structural + functional: every sampled BSK row is a TRLWE encryption of the right gadget
     value under s1, every sampled KSK row a TLWE encryption of k*s1[i]/base^(j+1) under s0, noise at
-    the requested alpha; gates evaluated with the generated key decrypt correctly; the seed fixes the key."""
+    the requested alpha; gates evaluated with the generated key decrypt correctly; the seed fixes the key.  The sampled rows are also held
+    word for word to the CPU model of the generator (tests/keygen_model.py) under the seed's SplitMix64 key."""
     import rs_tfhe_amd as R
 
     sk, _ = keys128
@@ -1265,6 +1266,26 @@ def test_gpu_key_generation(O, keys128):
         assert not gk.key_switching_key[i, j, 0].any()
     masks = gk.key_switching_key[3, 2, 1, :P.n].astype(np.float64)
     assert 0.4 < masks.mean() / 2.0**32 < 0.6  # uniform mask words
+    # the rows looked at above, word for word: under key_from_seed(2025) they are keystream positions the CPU model
+    # knows (tests/keygen_model.py; test_gpu_keygen.py holds whole keys of small shapes to it, this the real n = 700)
+    import keygen_model as KM
+
+    gen_key = KM.key_from_seed(2025)
+    rows = np.array([i * 2 * P.l + r for i in (0, 1, 350, 699) for r in range(2 * P.l)])
+    e = KM.bsk_noise(gen_key, rows, P.alpha_lv1, KM.PLAIN[3])
+    want = KM.plain_bsk_rows(P, sk.key_lv0, sk.key_lv1, rows, KM.plain_bsk_masks(gen_key, rows), e.words)
+    flat = gk.bootstrapping_key.reshape(-1, 2, N)
+    got = np.stack([[O.klemsa_fft(flat[r, 0]), O.klemsa_fft(flat[r, 1])] for r in rows])
+    border = np.zeros(want.shape, bool)
+    border[:, 1] = e.border
+    KM.compare_words(got, want, border, "SECURITY_128_BIT BSK rows")
+    rows = np.array([P.base * P.iks_t * i + P.base * j + k for (i, j, k) in ((0, 0, 1), (5, 3, 2), (1023, 8, 3), (512, 4, 1))], np.uint64)
+    ek = KM.ksk_noise(gen_key, rows, P.alpha_lv0, KM.PLAIN[1])
+    kmasks = R.seeded.keystream(gen_key, P.n, rows, KM.PLAIN[0], R.seeded.DOMAIN_KSK)
+    want = np.concatenate([kmasks, KM.ksk_bodies(P, sk.key_lv0, sk.key_lv1, rows, kmasks, ek.words)[:, None]], axis=1)
+    border = np.zeros(want.shape, bool)
+    border[:, -1] = ek.border
+    KM.compare_words(gk.key_switching_key.reshape(-1, P.n + 1)[rows.astype(np.int64)], want, border, "SECURITY_128_BIT KSK rows")
     # functional: gates with the generated key
     A = np.array([1, 1, 0, 0, 1, 0], bool)
     B = np.array([1, 0, 1, 0, 1, 1], bool)
