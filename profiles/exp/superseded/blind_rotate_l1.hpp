@@ -155,43 +155,18 @@ __global__ __launch_bounds__(64 * kL1Waves, 3) void k_blind_rotate_l1(BlindRotat
   size_t ct = (size_t)blockIdx.x * kL1Waves + wave;
   const bool live = ct < A.count;
   if (!live) ct = A.count - 1;
-  const unsigned long long clk0 = A.clk ? __builtin_amdgcn_s_memtime() : 0ull;
-  const unsigned long long rtc0 = A.clk ? __builtin_amdgcn_s_memrealtime() : 0ull;
+  const BrClock clock = br_clock_start(A);
 
   Twiddles tw;
   tw.load(A.tw, t2tab, lane);
 
-  // ---- gate linear prep (gates.rs:54-150), wave-uniform ------------------------------------
-  uint32_t gca = A.ca, gcb = A.cb, gcc = A.cconst;
-  if (A.gate_codes) {
-    uint32_t code = A.gate_codes[ct];
-    if (code > 10u) {
-      if (A.err_flag && lane == 0) atomicOr(A.err_flag, 1u);
-      code = 10u;
-    }
-    gca = kGateCa[code];
-    gcb = kGateCb[code];
-    gcc = kGateCc[code];
-  }
-  gca = (uint32_t)__builtin_amdgcn_readfirstlane((int)gca);
-  gcb = (uint32_t)__builtin_amdgcn_readfirstlane((int)gcb);
-  const uint32_t *pa = A.in_a + ct * (size_t)(n + 1);
-  const bool two = A.in_b && gcb;
-  const uint32_t *pb = two ? A.in_b + ct * (size_t)(n + 1) : pa;  // (one operand: b is loaded too and multiplied by 0)
-  if (!two) gcb = 0u;
-  uint32_t pbody = gca * pa[n];
-  if (two) pbody += gcb * pb[n];
-  pbody += gcc;
-  const int b_tilda = 2 * kN - (int)(((uint64_t)pbody + (1ull << 20)) >> 21);  // trgsw.rs:202-203
-
-  // ---- acc = X^b_tilda * testvec ---------------------------------------------------------------
-  const uint32_t *tv = A.testvec + ct * A.per_ct_stride;
-#pragma unroll
-  for (int m = 0; m < 16; ++m) {
-    const int j = lane + 64 * m;
-    acc[j] = rot_read(tv, j, b_tilda);
-    acc[kN + j] = rot_read(tv + kN, j, b_tilda);
-  }
+  // ---- gate linear prep (gates.rs:54-150), wave-uniform; no s_abar: the rotation amounts are recomputed per step ----
+  const BrOperands ops = br_operands(A, ct, lane);
+  const uint32_t gca = (uint32_t)__builtin_amdgcn_readfirstlane((int)ops.g.ca);
+  const uint32_t gcb = ops.b ? (uint32_t)__builtin_amdgcn_readfirstlane((int)ops.g.cb) : 0u;
+  const uint32_t *pa = ops.a;
+  const uint32_t *pb = ops.b ? ops.b : pa;  // (one operand: b is loaded too and multiplied by 0)
+  br_rotate_testvec<false, 64>(A, ct, lane, ops, acc);
   __syncthreads();
 
   constexpr uint32_t per_i_bytes = 2u * L * 2u * kN2 * 16u;  // one TRGSW in engine order
@@ -276,31 +251,9 @@ __global__ __launch_bounds__(64 * kL1Waves, 3) void k_blind_rotate_l1(BlindRotat
     k_now = ((gca * ra + gcb * rb) + (1u << 20)) >> 21;
   }
 
-  // ---- epilogue (as k_blind_rotate) ------------------------------------------------------------
   if (!live) return;
-  if (A.out_trlwe) {
-    uint32_t *o = A.out_trlwe + ct * (size_t)(2 * kN);
-#pragma unroll
-    for (int m = 0; m < 32; ++m) o[lane + 64 * m] = acc[lane + 64 * m];
-  }
-  if (A.out_lv1) {  // trlwe.rs:106-120 with k = 0
-    uint32_t *o = A.out_lv1 + ct * (size_t)(kN + 1);
-#pragma unroll
-    for (int m = 0; m < 16; ++m) {
-      const int i = lane + 64 * m;
-      o[i] = i == 0 ? acc[0] : ~acc[kN - i];
-    }
-    if (lane == 0) o[kN] = acc[kN];
-  }
-  if (A.out_ext2) {  // trlwe.rs:122-136 with k = 0
-    uint32_t *o = A.out_ext2 + ct * (size_t)(n + 1);
-    for (int i = lane; i < n; i += 64) o[i] = i == 0 ? acc[0] : ~acc[n - i];
-    if (lane == 0) o[n] = acc[kN];
-  }
-  if (A.clk && lane == 0) {
-    atomicAdd(&A.clk[0], __builtin_amdgcn_s_memtime() - clk0);
-    atomicAdd(&A.clk[1], __builtin_amdgcn_s_memrealtime() - rtc0);
-  }
+  br_epilogue<false, 64>(A, ct, lane, acc);
+  br_clock_stop(A, clock, lane);
 }
 
 }  // namespace tfhe

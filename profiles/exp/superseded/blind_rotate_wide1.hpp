@@ -40,39 +40,12 @@ __global__ __launch_bounds__(128 * L, 1) void k_blind_rotate_wide(BlindRotateArg
   constexpr int NT = 64 * W;
   const size_t ct = blockIdx.x;
   const int n = A.n;
-  const unsigned long long clk0 = A.clk ? __builtin_amdgcn_s_memtime() : 0ull;
-  const unsigned long long rtc0 = A.clk ? __builtin_amdgcn_s_memrealtime() : 0ull;
+  const BrClock clock = br_clock_start(A);
 
   Twiddles tw;
   tw.load(A.tw, t2tab, lane);  // every wave stores the same 64 entries; ends with a workgroup barrier
 
-  uint32_t gca = A.ca, gcb = A.cb, gcc = A.cconst;
-  if (A.gate_codes) {
-    uint32_t code = A.gate_codes[ct];
-    if (code > 10u) {
-      if (A.err_flag && tid == 0) atomicOr(A.err_flag, 1u);
-      code = 10u;
-    }
-    gca = kGateCa[code];
-    gcb = kGateCb[code];
-    gcc = kGateCc[code];
-  }
-  const uint32_t *pa = A.in_a + ct * (size_t)(n + 1);
-  const uint32_t *pb = (A.in_b && gcb) ? A.in_b + ct * (size_t)(n + 1) : nullptr;
-  for (int i = tid; i < n; i += NT) {
-    uint32_t p = gca * pa[i];
-    if (pb) p += gcb * pb[i];
-    s_abar[i] = (uint16_t)((uint32_t)(p + (1u << 20)) >> 21);  // trgsw.rs:210-211
-  }
-  uint32_t pbody = gca * pa[n];
-  if (pb) pbody += gcb * pb[n];
-  pbody += gcc;
-  const int b_tilda = 2 * kN - (int)(((uint64_t)pbody + (1ull << 20)) >> 21);  // trgsw.rs:202-203
-  const uint32_t *tv = A.testvec + ct * A.per_ct_stride;
-  for (int j = tid; j < kN; j += NT) {
-    acc[j] = rot_read(tv, j, b_tilda);
-    acc[kN + j] = rot_read(tv + kN, j, b_tilda);
-  }
+  br_prologue<false, NT>(A, ct, tid, s_abar, acc);
   __syncthreads();
 
   const int half_sel = wave / L, d = wave % L;
@@ -195,24 +168,8 @@ __global__ __launch_bounds__(128 * L, 1) void k_blind_rotate_wide(BlindRotateArg
   }
 #undef LAT_STAMP
 
-  if (A.out_trlwe) {
-    uint32_t *o = A.out_trlwe + ct * (size_t)(2 * kN);
-    for (int j = tid; j < 2 * kN; j += NT) o[j] = acc[j];
-  }
-  if (A.out_lv1) {  // trlwe.rs:106-120 with k=0
-    uint32_t *o = A.out_lv1 + ct * (size_t)(kN + 1);
-    for (int i = tid; i < kN; i += NT) o[i] = i == 0 ? acc[0] : ~acc[kN - i];
-    if (tid == 0) o[kN] = acc[kN];
-  }
-  if (A.out_ext2) {  // trlwe.rs:122-136 with k=0
-    uint32_t *o = A.out_ext2 + ct * (size_t)(n + 1);
-    for (int i = tid; i < n; i += NT) o[i] = i == 0 ? acc[0] : ~acc[n - i];
-    if (tid == 0) o[n] = acc[kN];
-  }
-  if (A.clk && tid == 0) {
-    atomicAdd(&A.clk[0], __builtin_amdgcn_s_memtime() - clk0);
-    atomicAdd(&A.clk[1], __builtin_amdgcn_s_memrealtime() - rtc0);
-  }
+  br_epilogue<false, NT>(A, ct, tid, acc);
+  br_clock_stop(A, clock, tid);
 }
 
 }  // namespace tfhe

@@ -241,11 +241,26 @@ struct BlindRotateArgs {
 };
 
 // src/gates.rs:54-150 as (ca, cb, const): prepared = ca*a + cb*b, prepared.b += const.
-// Index = tfhe_hip_gate; constants are utils::f64_to_torus(+-1/8, +-1/4) (utils.rs:9-12).
-__device__ constexpr uint32_t kGateCa[11] = {0xFFFFFFFFu, 1u, 1u, 1u, 1u, 0xFFFFFFFFu, 0xFFFFFFFFu, 1u, 0xFFFFFFFFu, 1u, 1u};
-__device__ constexpr uint32_t kGateCb[11] = {0xFFFFFFFFu, 1u, 1u, 2u, 0xFFFFFFFEu, 0xFFFFFFFFu, 1u, 0xFFFFFFFFu, 1u, 0xFFFFFFFFu, 0u};
-__device__ constexpr uint32_t kGateCc[11] = {0x20000000u, 0x20000000u, 0xE0000000u, 0x40000000u, 0xC0000000u, 0xE0000000u,
-                                             0xE0000000u, 0xE0000000u, 0x20000000u, 0x20000000u, 0u};
+// Index = tfhe_hip_gate; constants are utils::f64_to_torus(+-1/8, +-1/4) (utils.rs:9-12).  The one table, for the
+// host's gate_prep() and for the kernels' per-ciphertext gate_codes.
+struct GatePrep {
+  uint32_t ca, cb, cconst;
+};
+constexpr GatePrep kGateTable[] = {
+    {0xFFFFFFFFu, 0xFFFFFFFFu, 0x20000000u},  // NAND
+    {1u, 1u, 0x20000000u},                    // OR
+    {1u, 1u, 0xE0000000u},                    // AND
+    {1u, 2u, 0x40000000u},                    // XOR
+    {1u, 0xFFFFFFFEu, 0xC0000000u},           // XNOR
+    {0xFFFFFFFFu, 0xFFFFFFFFu, 0xE0000000u},  // NOR
+    {0xFFFFFFFFu, 1u, 0xE0000000u},           // ANDNY
+    {1u, 0xFFFFFFFFu, 0xE0000000u},           // ANDYN
+    {0xFFFFFFFFu, 1u, 0x20000000u},           // ORNY
+    {1u, 0xFFFFFFFFu, 0x20000000u},           // ORYN
+    {1u, 0u, 0u},                             // COPY: the plain bootstrap of the first operand, no second one
+};
+constexpr uint32_t kGateCount = sizeof(kGateTable) / sizeof(kGateTable[0]);
+constexpr uint32_t kGateCopy = kGateCount - 1;  // the last row; what a code outside the table is clamped to
 
 // LDS per workgroup: per wave { FFT tile | accumulator (a then b, natural order) | rotation amounts }, then ONE
 // pass-2 twiddle table for the whole workgroup (every wave stores the same 64 entries).  Two workgroups share a
@@ -259,6 +274,118 @@ __host__ __device__ __forceinline__ size_t blind_rotate_lds_bytes(int n) {
   return kBrWaves * blind_rotate_wave_lds_bytes(n) + kT2Bytes;
 }
 constexpr int kStageLdsBytes = kTileBytes + kT2Bytes;  // stage kernels: tile | T2 table
+
+// ---- what surrounds the n-step loop, the same in every fused kernel ----------------------------------------------
+// Thread t of the NT threads that share ciphertext ct (a wave's lane, or a workgroup's thread id); s_abar / acc are
+// that ciphertext's rotation amounts and accumulator in LDS.  One copy, so that every kernel computes the same bits.
+
+// f(j) for j = t, t + NT, ... below COUNT, with a trip count the compiler can see (the loops unroll)
+template <int COUNT, int NT, typename F>
+__device__ __forceinline__ void for_strided(int t, F f) {
+#pragma unroll
+  for (int m = 0; m < (COUNT + NT - 1) / NT; ++m) {
+    const int j = t + NT * m;
+    if (COUNT % NT == 0 || j < COUNT) f(j);
+  }
+}
+
+// Gate of ciphertext ct -- the launch's uniform one or its own gate_codes entry (a code outside tfhe_hip_gate raises
+// err_flag, which the host reports at the next synchronising call, and is treated as COPY) -- and its operand rows,
+// direct or gathered through idx_a / idx_b.  b == nullptr: no second operand.
+struct BrOperands {
+  GatePrep g;
+  const uint32_t *a, *b;
+};
+__device__ __forceinline__ BrOperands br_operands(const BlindRotateArgs &A, size_t ct, int t) {
+  BrOperands o;
+  o.g = {A.ca, A.cb, A.cconst};
+  if (A.gate_codes) {
+    uint32_t code = A.gate_codes[ct];
+    if (code >= kGateCount) {
+      if (A.err_flag && t == 0) atomicOr(A.err_flag, 1u);
+      code = kGateCopy;
+    }
+    o.g = kGateTable[code];
+  }
+  const size_t width = (size_t)(A.n + 1);
+  o.a = A.in_a + (A.idx_a ? (size_t)A.idx_a[ct] : ct) * width;
+  o.b = (A.in_b && o.g.cb) ? A.in_b + (A.idx_b ? (size_t)A.idx_b[ct] : ct) * width : nullptr;
+  return o;
+}
+
+// acc = X^b_tilda * testvec, b_tilda = 2N - ((b as usize + 2^20) >> 21) without 32-bit wrap (trgsw.rs:202-203) of the
+// prepared body ca*a[n] + cb*b[n] + cconst; MANY: rounded to a multiple of 2^lut_shift
+template <bool MANY, int NT>
+__device__ __forceinline__ void br_rotate_testvec(const BlindRotateArgs &A, size_t ct, int t, const BrOperands &o,
+                                                  uint32_t *acc) {
+  const int dl = MANY ? A.lut_shift : 0;
+  uint32_t pbody = o.g.ca * o.a[A.n];
+  if (o.b) pbody += o.g.cb * o.b[A.n];
+  pbody += o.g.cconst;
+  const int b_tilda = 2 * kN - (int)((((uint64_t)pbody + (1ull << (20 + dl))) >> (21 + dl)) << dl);
+  const uint32_t *tv = A.testvec + ct * A.per_ct_stride;
+  for_strided<kN, NT>(t, [&](int j) {
+    acc[j] = rot_read(tv, j, b_tilda);
+    acc[kN + j] = rot_read(tv + kN, j, b_tilda);
+  });
+}
+
+// Prologue: s_abar[i] = a_tilda of step i = (p +wrap 2^20) >> 21 of p = ca*a[i] + cb*b[i] (gates.rs:54-150,
+// trgsw.rs:210-211; MANY: rounded to a multiple of 2^lut_shift), and the rotated test vector.  The barrier that makes
+// both visible is the caller's.
+template <bool MANY, int NT>
+__device__ __forceinline__ void br_prologue(const BlindRotateArgs &A, size_t ct, int t, uint16_t *s_abar, uint32_t *acc) {
+  const BrOperands o = br_operands(A, ct, t);
+  const int dl = MANY ? A.lut_shift : 0;
+  for (int i = t; i < A.n; i += NT) {
+    uint32_t p = o.g.ca * o.a[i];
+    if (o.b) p += o.g.cb * o.b[i];
+    s_abar[i] = (uint16_t)(((uint32_t)(p + (1u << (20 + dl))) >> (21 + dl)) << dl);
+  }
+  br_rotate_testvec<MANY, NT>(A, ct, t, o, acc);
+}
+
+// Epilogue (acc is final; any thread may read any coefficient): the TRLWE itself, and for function j < n_luts (one
+// unless MANY) sample_extract_index(., j) into out_lv1 (trlwe.rs:106-120) and sample_extract_index_2(., j), the same
+// formula with N := n, into out_ext2 (trlwe.rs:122-136): p[i] = i <= j ? a[j-i] : MAX - a[N+j-i]; p[N] = b[j].
+// Function j of ciphertext ct is row j * out_fn_stride + ct.
+template <bool MANY, int NT>
+__device__ __forceinline__ void br_epilogue(const BlindRotateArgs &A, size_t ct, int t, const uint32_t *acc) {
+  const int n = A.n;
+  if (A.out_trlwe) {
+    uint32_t *o = A.out_trlwe + ct * (size_t)(2 * kN);
+    for_strided<2 * kN, NT>(t, [&](int i) { o[i] = acc[i]; });
+  }
+  const int n_luts = MANY ? A.n_luts : 1;
+  for (int j = 0; j < n_luts; ++j) {
+    const size_t row = MANY ? (size_t)j * A.out_fn_stride + ct : ct;
+    if (A.out_lv1) {
+      uint32_t *o = A.out_lv1 + row * (size_t)(kN + 1);
+      for_strided<kN, NT>(t, [&](int i) { o[i] = i <= j ? acc[j - i] : ~acc[kN + j - i]; });
+      if (t == 0) o[kN] = acc[kN + j];
+    }
+    if (A.out_ext2) {
+      uint32_t *o = A.out_ext2 + row * (size_t)(n + 1);
+      for (int i = t; i < n; i += NT) o[i] = i <= j ? acc[j - i] : ~acc[n + j - i];
+      if (t == 0) o[n] = acc[kN + j];
+    }
+  }
+}
+
+// BlindRotateArgs::clk: shader cycles (s_memtime) and constant-rate ticks (s_memrealtime) from a workgroup's start to
+// its end, added up by its thread 0
+struct BrClock {
+  unsigned long long clk0, rtc0;
+};
+__device__ __forceinline__ BrClock br_clock_start(const BlindRotateArgs &A) {
+  return {A.clk ? __builtin_amdgcn_s_memtime() : 0ull, A.clk ? __builtin_amdgcn_s_memrealtime() : 0ull};
+}
+__device__ __forceinline__ void br_clock_stop(const BlindRotateArgs &A, const BrClock &c, int t) {
+  if (A.clk && t == 0) {
+    atomicAdd(&A.clk[0], __builtin_amdgcn_s_memtime() - c.clk0);
+    atomicAdd(&A.clk[1], __builtin_amdgcn_s_memrealtime() - c.rtc0);
+  }
+}
 
 // The TRLWE accumulator lives in a wave-private LDS array for the whole n-step
 // chain.  X^k * acc is then just an indexed re-read of that array (poly_mul_with_x_k
@@ -282,47 +409,12 @@ __device__ __forceinline__ void blind_rotate_batch(BlindRotateArgs A) {
   size_t ct = (size_t)blockIdx.x * kBrWaves + wave;
   const bool live = ct < A.count;
   if (!live) ct = A.count - 1;
-  const unsigned long long clk0 = A.clk ? __builtin_amdgcn_s_memtime() : 0ull;
-  const unsigned long long rtc0 = A.clk ? __builtin_amdgcn_s_memrealtime() : 0ull;
+  const BrClock clock = br_clock_start(A);
 
   Twiddles tw;
   tw.load<TFHE_ABL_TW_REL && !MANY>(A.tw, t2tab, lane);
 
-  // ---- gate linear prep + rotation amounts ---------------------------------
-  uint32_t gca = A.ca, gcb = A.cb, gcc = A.cconst;
-  if (A.gate_codes) {  // mixed batch: this ciphertext's own gate (same table as the host's gate_prep)
-    uint32_t code = A.gate_codes[ct];
-    if (code > 10u) {  // not a tfhe_hip_gate: flag it (the host reports it at the next synchronising call)
-      if (A.err_flag && lane == 0) atomicOr(A.err_flag, 1u);
-      code = 10u;
-    }
-    gca = kGateCa[code];
-    gcb = kGateCb[code];
-    gcc = kGateCc[code];
-  }
-  const uint32_t *pa = A.in_a + (A.idx_a ? (size_t)A.idx_a[ct] : ct) * (size_t)(n + 1);
-  const uint32_t *pb = (A.in_b && gcb) ? A.in_b + (A.idx_b ? (size_t)A.idx_b[ct] : ct) * (size_t)(n + 1) : nullptr;
-  const int dl = MANY ? A.lut_shift : 0;
-  for (int i = lane; i < n; i += 64) {
-    uint32_t p = gca * pa[i];
-    if (pb) p += gcb * pb[i];
-    // a_tilda = (p +wrap 2^20) >> 21   (trgsw.rs:210-211), rounded to a multiple of 2^lut_shift
-    s_abar[i] = (uint16_t)(((uint32_t)(p + (1u << (20 + dl))) >> (21 + dl)) << dl);
-  }
-  uint32_t pbody = gca * pa[n];
-  if (pb) pbody += gcb * pb[n];
-  pbody += gcc;
-  // b_tilda = 2N - ((b as usize + 2^20) >> 21), no 32-bit wrap (trgsw.rs:202-203)
-  const int b_tilda = 2 * kN - (int)((((uint64_t)pbody + (1ull << (20 + dl))) >> (21 + dl)) << dl);
-
-  // ---- acc = X^b_tilda * testvec -------------------------------------------
-  const uint32_t *tv = A.testvec + ct * A.per_ct_stride;
-#pragma unroll
-  for (int m = 0; m < 16; ++m) {
-    int j = lane + 64 * m;
-    acc[j] = rot_read(tv, j, b_tilda);
-    acc[kN + j] = rot_read(tv + kN, j, b_tilda);
-  }
+  br_prologue<MANY, 64>(A, ct, lane, s_abar, acc);
   __syncthreads();
 
   // ---- n sequential CMUXes: acc += BSK[i] (x) (X^a_tilda * acc - acc) ------
@@ -399,55 +491,9 @@ __device__ __forceinline__ void blind_rotate_batch(BlindRotateArgs A) {
     wave_lds_sync();  // the next step re-reads acc at rotated (other lanes') positions
   }
 
-  // ---- epilogue (acc is final; any lane may read any coefficient) -------------
   if (!live) return;
-  if (A.out_trlwe) {
-    uint32_t *o = A.out_trlwe + ct * (size_t)(2 * kN);
-#pragma unroll
-    for (int m = 0; m < 32; ++m) o[lane + 64 * m] = acc[lane + 64 * m];
-  }
-  if constexpr (MANY) {
-    for (int j = 0; j < A.n_luts; ++j) {
-      const size_t row = (size_t)j * A.out_fn_stride + ct;
-      if (A.out_lv1) {
-        // p[i] = i <= j ? a[j-i] : MAX-a[N+j-i]; p[N] = b[j]   (trlwe.rs:106-120 with k=j)
-        uint32_t *o = A.out_lv1 + row * (size_t)(kN + 1);
-#pragma unroll
-        for (int m = 0; m < 16; ++m) {
-          const int i = lane + 64 * m;
-          o[i] = i <= j ? acc[j - i] : ~acc[kN + j - i];
-        }
-        if (lane == 0) o[kN] = acc[kN + j];
-      }
-      if (A.out_ext2) {
-        // same formula with N := n   (trlwe.rs:122-136 with k=j)
-        uint32_t *o = A.out_ext2 + row * (size_t)(n + 1);
-        for (int i = lane; i < n; i += 64) o[i] = i <= j ? acc[j - i] : ~acc[n + j - i];
-        if (lane == 0) o[n] = acc[kN + j];
-      }
-    }
-  } else {
-    if (A.out_lv1) {
-      // p[0]=a[0]; p[i]=MAX-a[N-i]; p[N]=b[0]   (trlwe.rs:106-120 with k=0)
-      uint32_t *o = A.out_lv1 + ct * (size_t)(kN + 1);
-#pragma unroll
-      for (int m = 0; m < 16; ++m) {
-        const int i = lane + 64 * m;
-        o[i] = i == 0 ? acc[0] : ~acc[kN - i];
-      }
-      if (lane == 0) o[kN] = acc[kN];
-    }
-    if (A.out_ext2) {
-      // same formula with N := n   (trlwe.rs:122-136 with k=0)
-      uint32_t *o = A.out_ext2 + ct * (size_t)(n + 1);
-      for (int i = lane; i < n; i += 64) o[i] = i == 0 ? acc[0] : ~acc[n - i];
-      if (lane == 0) o[n] = acc[kN];
-    }
-  }
-  if (A.clk && lane == 0) {
-    atomicAdd(&A.clk[0], __builtin_amdgcn_s_memtime() - clk0);
-    atomicAdd(&A.clk[1], __builtin_amdgcn_s_memrealtime() - rtc0);
-  }
+  br_epilogue<MANY, 64>(A, ct, lane, acc);
+  br_clock_stop(A, clock, lane);
 }
 
 template <int L, bool FAST>

@@ -54,41 +54,12 @@ __device__ __forceinline__ void blind_rotate_wide2(BlindRotateArgs A) {
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const size_t ct = blockIdx.x;
   const int n = A.n;
-  const unsigned long long clk0 = A.clk ? __builtin_amdgcn_s_memtime() : 0ull;
-  const unsigned long long rtc0 = A.clk ? __builtin_amdgcn_s_memrealtime() : 0ull;
+  const BrClock clock = br_clock_start(A);
 
   Twiddles tw;
   tw.load<TFHE_ABL_TW_REL && !MANY>(A.tw, t2tab, lane);  // every wave stores the same 64 entries; ends with a workgroup barrier
 
-  // ---- gate linear prep + rotation amounts (gates.rs:54-150, trgsw.rs:202-211) -----------------
-  uint32_t gca = A.ca, gcb = A.cb, gcc = A.cconst;
-  if (A.gate_codes) {
-    uint32_t code = A.gate_codes[ct];
-    if (code > 10u) {
-      if (A.err_flag && tid == 0) atomicOr(A.err_flag, 1u);
-      code = 10u;
-    }
-    gca = kGateCa[code];
-    gcb = kGateCb[code];
-    gcc = kGateCc[code];
-  }
-  const uint32_t *pa = A.in_a + (A.idx_a ? (size_t)A.idx_a[ct] : ct) * (size_t)(n + 1);
-  const uint32_t *pb = (A.in_b && gcb) ? A.in_b + (A.idx_b ? (size_t)A.idx_b[ct] : ct) * (size_t)(n + 1) : nullptr;
-  const int dl = MANY ? A.lut_shift : 0;  // many-LUT: rotation amounts rounded to multiples of 2^dl
-  for (int i = tid; i < n; i += NT) {
-    uint32_t p = gca * pa[i];
-    if (pb) p += gcb * pb[i];
-    s_abar[i] = (uint16_t)(((uint32_t)(p + (1u << (20 + dl))) >> (21 + dl)) << dl);
-  }
-  uint32_t pbody = gca * pa[n];
-  if (pb) pbody += gcb * pb[n];
-  pbody += gcc;
-  const int b_tilda = 2 * kN - (int)((((uint64_t)pbody + (1ull << (20 + dl))) >> (21 + dl)) << dl);
-  const uint32_t *tv = A.testvec + ct * A.per_ct_stride;
-  for (int j = tid; j < kN; j += NT) {
-    acc[j] = rot_read(tv, j, b_tilda);
-    acc[kN + j] = rot_read(tv + kN, j, b_tilda);
-  }
+  br_prologue<MANY, NT>(A, ct, tid, s_abar, acc);
   __syncthreads();
 
   const bool fwd = wave < W;  // wave-uniform
@@ -204,40 +175,8 @@ __device__ __forceinline__ void blind_rotate_wide2(BlindRotateArgs A) {
     lds_barrier();  // the accumulator is final for this step
   }
 
-  if (A.out_trlwe) {
-    uint32_t *o = A.out_trlwe + ct * (size_t)(2 * kN);
-    for (int j = tid; j < 2 * kN; j += NT) o[j] = acc[j];
-  }
-  if constexpr (MANY) {
-    for (int j = 0; j < A.n_luts; ++j) {  // function j: row j * out_fn_stride + ct
-      const size_t row = (size_t)j * A.out_fn_stride + ct;
-      if (A.out_lv1) {  // trlwe.rs:106-120 with k=j
-        uint32_t *o = A.out_lv1 + row * (size_t)(kN + 1);
-        for (int i = tid; i < kN; i += NT) o[i] = i <= j ? acc[j - i] : ~acc[kN + j - i];
-        if (tid == 0) o[kN] = acc[kN + j];
-      }
-      if (A.out_ext2) {  // trlwe.rs:122-136 with k=j
-        uint32_t *o = A.out_ext2 + row * (size_t)(n + 1);
-        for (int i = tid; i < n; i += NT) o[i] = i <= j ? acc[j - i] : ~acc[n + j - i];
-        if (tid == 0) o[n] = acc[kN + j];
-      }
-    }
-  } else {
-    if (A.out_lv1) {  // trlwe.rs:106-120 with k=0
-      uint32_t *o = A.out_lv1 + ct * (size_t)(kN + 1);
-      for (int i = tid; i < kN; i += NT) o[i] = i == 0 ? acc[0] : ~acc[kN - i];
-      if (tid == 0) o[kN] = acc[kN];
-    }
-    if (A.out_ext2) {  // trlwe.rs:122-136 with k=0
-      uint32_t *o = A.out_ext2 + ct * (size_t)(n + 1);
-      for (int i = tid; i < n; i += NT) o[i] = i == 0 ? acc[0] : ~acc[n - i];
-      if (tid == 0) o[n] = acc[kN];
-    }
-  }
-  if (A.clk && tid == 0) {
-    atomicAdd(&A.clk[0], __builtin_amdgcn_s_memtime() - clk0);
-    atomicAdd(&A.clk[1], __builtin_amdgcn_s_memrealtime() - rtc0);
-  }
+  br_epilogue<MANY, NT>(A, ct, tid, acc);
+  br_clock_stop(A, clock, tid);
 }
 
 template <int L, bool FAST>
@@ -289,8 +228,7 @@ __global__ __launch_bounds__(64 * kPairWaves, 1) void k_blind_rotate_pair(BlindR
   const int tid = threadIdx.x;
   const int lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const unsigned long long clk0 = A.clk ? __builtin_amdgcn_s_memtime() : 0ull;
-  const unsigned long long rtc0 = A.clk ? __builtin_amdgcn_s_memrealtime() : 0ull;
+  const BrClock clock = br_clock_start(A);
 
   Twiddles tw;
   tw.load<TFHE_ABL_TW_REL && !MANY>(A.tw, t2tab, lane);  // ends with a workgroup barrier
@@ -301,38 +239,7 @@ __global__ __launch_bounds__(64 * kPairWaves, 1) void k_blind_rotate_pair(BlindR
   cts[1] = cts[0] + 1 < A.count ? cts[0] + 1 : cts[0];  // an odd batch: the last workgroup runs its ciphertext twice
   const bool b_valid = cts[0] + 1 < A.count;
 #pragma unroll
-  for (int c = 0; c < 2; ++c) {
-    const size_t ct = cts[c];
-    uint32_t gca = A.ca, gcb = A.cb, gcc = A.cconst;
-    if (A.gate_codes) {
-      uint32_t code = A.gate_codes[ct];
-      if (code > 10u) {
-        if (A.err_flag && tid == 0) atomicOr(A.err_flag, 1u);
-        code = 10u;
-      }
-      gca = kGateCa[code];
-      gcb = kGateCb[code];
-      gcc = kGateCc[code];
-    }
-    const uint32_t *pa = A.in_a + (A.idx_a ? (size_t)A.idx_a[ct] : ct) * (size_t)(n + 1);
-    const uint32_t *pb = (A.in_b && gcb) ? A.in_b + (A.idx_b ? (size_t)A.idx_b[ct] : ct) * (size_t)(n + 1) : nullptr;
-    const int dl = MANY ? A.lut_shift : 0;  // many-LUT: rotation amounts rounded to multiples of 2^dl
-    for (int i = tid; i < n; i += NT) {
-      uint32_t p = gca * pa[i];
-      if (pb) p += gcb * pb[i];
-      s_abar[c * abar_stride + i] = (uint16_t)(((uint32_t)(p + (1u << (20 + dl))) >> (21 + dl)) << dl);
-    }
-    uint32_t pbody = gca * pa[n];
-    if (pb) pbody += gcb * pb[n];
-    pbody += gcc;
-    const int b_tilda = 2 * kN - (int)((((uint64_t)pbody + (1ull << (20 + dl))) >> (21 + dl)) << dl);
-    const uint32_t *tv = A.testvec + ct * A.per_ct_stride;
-    uint32_t *q = acc + c * 2 * kN;
-    for (int j = tid; j < kN; j += NT) {
-      q[j] = rot_read(tv, j, b_tilda);
-      q[kN + j] = rot_read(tv + kN, j, b_tilda);
-    }
-  }
+  for (int c = 0; c < 2; ++c) br_prologue<MANY, NT>(A, cts[c], tid, s_abar + c * abar_stride, acc + c * 2 * kN);
   __syncthreads();
 
   const bool fwd = wave >= 2 && wave < 2 + W;  // wave-uniform
@@ -452,47 +359,9 @@ __global__ __launch_bounds__(64 * kPairWaves, 1) void k_blind_rotate_pair(BlindR
   if (wave < 2) inverse(1);
   lds_barrier();
 
-#pragma unroll
-  for (int c = 0; c < 2; ++c) {
-    if (c == 1 && !b_valid) break;
-    const size_t ct = cts[c];
-    const uint32_t *q = acc + c * 2 * kN;
-    if (A.out_trlwe) {
-      uint32_t *o = A.out_trlwe + ct * (size_t)(2 * kN);
-      for (int j = tid; j < 2 * kN; j += NT) o[j] = q[j];
-    }
-    if constexpr (MANY) {
-      for (int j = 0; j < A.n_luts; ++j) {  // function j: row j * out_fn_stride + ct
-        const size_t row = (size_t)j * A.out_fn_stride + ct;
-        if (A.out_lv1) {  // trlwe.rs:106-120 with k=j
-          uint32_t *o = A.out_lv1 + row * (size_t)(kN + 1);
-          for (int i = tid; i < kN; i += NT) o[i] = i <= j ? q[j - i] : ~q[kN + j - i];
-          if (tid == 0) o[kN] = q[kN + j];
-        }
-        if (A.out_ext2) {  // trlwe.rs:122-136 with k=j
-          uint32_t *o = A.out_ext2 + row * (size_t)(n + 1);
-          for (int i = tid; i < n; i += NT) o[i] = i <= j ? q[j - i] : ~q[n + j - i];
-          if (tid == 0) o[n] = q[kN + j];
-        }
-      }
-    } else {
-      if (A.out_lv1) {  // trlwe.rs:106-120 with k=0
-        uint32_t *o = A.out_lv1 + ct * (size_t)(kN + 1);
-        for (int i = tid; i < kN; i += NT) o[i] = i == 0 ? q[0] : ~q[kN - i];
-        if (tid == 0) o[kN] = q[kN];
-      }
-      if (A.out_ext2) {  // trlwe.rs:122-136 with k=0
-        uint32_t *o = A.out_ext2 + ct * (size_t)(n + 1);
-        for (int i = tid; i < n; i += NT) o[i] = i == 0 ? q[0] : ~q[n - i];
-        if (tid == 0) o[n] = q[kN];
-      }
-    }
-  }
-  if (A.clk && tid == 0) {
-    atomicAdd(&A.clk[0], __builtin_amdgcn_s_memtime() - clk0);
-    atomicAdd(&A.clk[1], __builtin_amdgcn_s_memrealtime() - rtc0);
-  }
+  br_epilogue<MANY, NT>(A, cts[0], tid, acc);
+  if (b_valid) br_epilogue<MANY, NT>(A, cts[1], tid, acc + 2 * kN);
+  br_clock_stop(A, clock, tid);
 }
-
 
 }  // namespace tfhe

@@ -305,32 +305,16 @@ int ensure(tfhe_hip_ctx *ctx, DevBuf &b, size_t bytes) {
   return TFHE_HIP_OK;
 }
 
-struct GatePrep {
-  uint32_t ca, cb, cconst;
-};
-// TFHE_HIP_COPY: the plain bootstrap of the first operand, no second one (what gate_prep(TFHE_HIP_COPY, ..) gives)
-constexpr GatePrep kCopyPrep{1u, 0u, 0u};
+// TFHE_HIP_COPY: the plain bootstrap of the first operand, no second one
+static_assert(kGateCount == TFHE_HIP_COPY + 1, "kGateTable (blind_rotate.hpp) has one row per tfhe_hip_gate");
+constexpr GatePrep kCopyPrep = kGateTable[TFHE_HIP_COPY];
 // launches with per-ciphertext gate codes: placeholders, the kernel reads the codes; cb != 0 keeps in_b attached
 constexpr GatePrep kCodesPrep{1u, 1u, 0u};
 
-// src/gates.rs:54-150; constants are utils::f64_to_torus(+-0.125 / +-0.25) (utils.rs:9-12)
 bool gate_prep(int gate, GatePrep &g) {
-  const uint32_t P8 = 0x20000000u, M8 = 0xE0000000u, P4 = 0x40000000u, M4 = 0xC0000000u;
-  const uint32_t ONE = 1u, NEG = 0xFFFFFFFFu, TWO = 2u, NEG2 = 0xFFFFFFFEu;
-  switch (gate) {
-    case TFHE_HIP_NAND: g = {NEG, NEG, P8}; return true;
-    case TFHE_HIP_OR: g = {ONE, ONE, P8}; return true;
-    case TFHE_HIP_AND: g = {ONE, ONE, M8}; return true;
-    case TFHE_HIP_XOR: g = {ONE, TWO, P4}; return true;
-    case TFHE_HIP_XNOR: g = {ONE, NEG2, M4}; return true;
-    case TFHE_HIP_NOR: g = {NEG, NEG, M8}; return true;
-    case TFHE_HIP_ANDNY: g = {NEG, ONE, M8}; return true;
-    case TFHE_HIP_ANDYN: g = {ONE, NEG, M8}; return true;
-    case TFHE_HIP_ORNY: g = {NEG, ONE, P8}; return true;
-    case TFHE_HIP_ORYN: g = {ONE, NEG, P8}; return true;
-    case TFHE_HIP_COPY: g = {ONE, 0u, 0u}; return true;
-    default: return false;
-  }
+  if (gate < 0 || (uint32_t)gate >= kGateCount) return false;
+  g = kGateTable[gate];
+  return true;
 }
 
 int record_begin(tfhe_hip_ctx *ctx, hipStream_t s, std::vector<std::pair<hipEvent_t, hipEvent_t>> &v) {
@@ -368,70 +352,6 @@ int br_waves(const tfhe_hip_ctx *ctx) { return br_is_l1(ctx) ? kL1Waves : kBrWav
 constexpr bool br_is_l1(const tfhe_hip_ctx *) { return false; }
 constexpr int br_waves(const tfhe_hip_ctx *) { return kBrWaves; }
 #endif
-// many: the many-LUT instantiation (BlindRotateArgs::lut_shift / n_luts / out_fn_stride) of the same kernel
-br_kernel_t br_kernel(const tfhe_hip_ctx *ctx, bool many = false) {
-  const bool f = ctx->dispatch.fast_round;
-#if defined(TFHE_EXPERIMENT) && defined(TFHE_EXP_L1)
-  if (br_is_l1(ctx)) return many ? nullptr : f ? k_blind_rotate_l1<true> : k_blind_rotate_l1<false>;
-#endif
-  if (many) switch (ctx->P.l) {
-      case 1: return f ? k_blind_rotate_many<1, true> : k_blind_rotate_many<1, false>;
-      case 2: return f ? k_blind_rotate_many<2, true> : k_blind_rotate_many<2, false>;
-      default: return f ? k_blind_rotate_many<3, true> : k_blind_rotate_many<3, false>;
-    }
-  switch (ctx->P.l) {
-    case 1: return f ? k_blind_rotate<1, true> : k_blind_rotate<1, false>;
-    case 2: return f ? k_blind_rotate<2, true> : k_blind_rotate<2, false>;
-    default: return f ? k_blind_rotate<3, true> : k_blind_rotate<3, false>;
-  }
-}
-
-br_kernel_t br_pair_kernel(const tfhe_hip_ctx *ctx, bool many = false) {
-  const bool f = ctx->dispatch.fast_round;
-  if (many) switch (ctx->P.l) {
-      case 1: return f ? k_blind_rotate_pair<1, true, true> : k_blind_rotate_pair<1, false, true>;
-      case 2: return f ? k_blind_rotate_pair<2, true, true> : k_blind_rotate_pair<2, false, true>;
-      default: return f ? k_blind_rotate_pair<3, true, true> : k_blind_rotate_pair<3, false, true>;
-    }
-  switch (ctx->P.l) {
-    case 1: return f ? k_blind_rotate_pair<1, true> : k_blind_rotate_pair<1, false>;
-    case 2: return f ? k_blind_rotate_pair<2, true> : k_blind_rotate_pair<2, false>;
-    default: return f ? k_blind_rotate_pair<3, true> : k_blind_rotate_pair<3, false>;
-  }
-}
-
-br_kernel_t br_single_kernel(const tfhe_hip_ctx *ctx, bool many = false) {
-  const bool f = ctx->dispatch.fast_round;
-  if (many) switch (ctx->P.l) {
-      case 1: return f ? k_blind_rotate_wide2_many<1, true> : k_blind_rotate_wide2_many<1, false>;
-      case 2: return f ? k_blind_rotate_wide2_many<2, true> : k_blind_rotate_wide2_many<2, false>;
-      default: return f ? k_blind_rotate_wide2_many<3, true> : k_blind_rotate_wide2_many<3, false>;
-    }
-#if defined(TFHE_EXPERIMENT) && defined(TFHE_EXP_WIDE1)  // the superseded one-wave-per-row latency kernel (profiles/exp/superseded/blind_rotate_wide1.hpp)
-  if (ctx->dispatch.exp_wide1) switch (ctx->P.l) {
-      case 1: return f ? k_blind_rotate_wide<1, true> : k_blind_rotate_wide<1, false>;
-      case 2: return f ? k_blind_rotate_wide<2, true> : k_blind_rotate_wide<2, false>;
-      default: return f ? k_blind_rotate_wide<3, true> : k_blind_rotate_wide<3, false>;
-    }
-#endif
-  switch (ctx->P.l) {
-    case 1: return f ? k_blind_rotate_wide2<1, true> : k_blind_rotate_wide2<1, false>;
-    case 2: return f ? k_blind_rotate_wide2<2, true> : k_blind_rotate_wide2<2, false>;
-    default: return f ? k_blind_rotate_wide2<3, true> : k_blind_rotate_wide2<3, false>;
-  }
-}
-
-typedef void (*ep_kernel_t)(const uint32_t *, const int32_t *, const double2 *, uint32_t, const double2 *, int,
-                            uint32_t, uint32_t *);
-ep_kernel_t ep_kernel(const tfhe_hip_ctx *ctx) {
-  const bool f = ctx->dispatch.fast_round;
-  switch (ctx->P.l) {
-    case 1: return f ? k_external_product<1, true> : k_external_product<1, false>;
-    case 2: return f ? k_external_product<2, true> : k_external_product<2, false>;
-    default: return f ? k_external_product<3, true> : k_external_product<3, false>;
-  }
-}
-
 size_t br_lds_bytes(const tfhe_hip_ctx *ctx) {
 #if defined(TFHE_EXPERIMENT) && defined(TFHE_EXP_L1)
   if (br_is_l1(ctx)) return blind_rotate_l1_lds_bytes();
@@ -448,6 +368,55 @@ size_t br_lds_bytes(const tfhe_hip_ctx *ctx) {
 // A plan is at most two launches over contiguous parts of the batch.
 enum BrKind { BR_BATCH = 0, BR_SINGLE = 1, BR_PAIR = 2 };
 const char *const kBrKindName[3] = {"batch", "single", "pair"};
+
+// The instantiation of a kernel family for this context: pick(KernelInst<l, fast_round, many>{}).  Every family of
+// kernels templated on the decomposition level and the rounding is named once, in its `pick`.
+template <int L_, bool FAST_, bool MANY_>
+struct KernelInst {
+  static constexpr int L = L_;
+  static constexpr bool FAST = FAST_, MANY = MANY_;
+};
+template <int L, typename Pick>
+auto kernel_inst_at(bool fast, bool many, Pick pick) {
+  return fast ? (many ? pick(KernelInst<L, true, true>{}) : pick(KernelInst<L, true, false>{}))
+              : (many ? pick(KernelInst<L, false, true>{}) : pick(KernelInst<L, false, false>{}));
+}
+template <typename Pick>
+auto kernel_inst(const tfhe_hip_ctx *ctx, bool many, Pick pick) {
+  const bool f = ctx->dispatch.fast_round;
+  switch (ctx->P.l) {
+    case 1: return kernel_inst_at<1>(f, many, pick);
+    case 2: return kernel_inst_at<2>(f, many, pick);
+    default: return kernel_inst_at<3>(f, many, pick);
+  }
+}
+
+// many: the many-LUT instantiation (BlindRotateArgs::lut_shift / n_luts / out_fn_stride) of the same kernel
+br_kernel_t br_kernel(const tfhe_hip_ctx *ctx, BrKind kind, bool many = false) {
+  return kernel_inst(ctx, many, [&](auto inst) -> br_kernel_t {
+    constexpr int L = decltype(inst)::L;
+    constexpr bool F = decltype(inst)::FAST, M = decltype(inst)::MANY;
+    switch (kind) {
+      case BR_PAIR: return k_blind_rotate_pair<L, F, M>;
+      case BR_SINGLE:
+#if defined(TFHE_EXPERIMENT) && defined(TFHE_EXP_WIDE1)  // the superseded one-wave-per-row latency kernel (profiles/exp/superseded/blind_rotate_wide1.hpp)
+        if (!M && ctx->dispatch.exp_wide1) return k_blind_rotate_wide<L, F>;
+#endif
+        return M ? k_blind_rotate_wide2_many<L, F> : k_blind_rotate_wide2<L, F>;
+      default:
+#if defined(TFHE_EXPERIMENT) && defined(TFHE_EXP_L1)
+        if constexpr (L == 1) return M ? nullptr : k_blind_rotate_l1<F>;
+#endif
+        return M ? k_blind_rotate_many<L, F> : k_blind_rotate<L, F>;
+    }
+  });
+}
+
+typedef void (*ep_kernel_t)(const uint32_t *, const int32_t *, const double2 *, uint32_t, const double2 *, int,
+                            uint32_t, uint32_t *);
+ep_kernel_t ep_kernel(const tfhe_hip_ctx *ctx) {
+  return kernel_inst(ctx, false, [](auto inst) -> ep_kernel_t { return k_external_product<decltype(inst)::L, decltype(inst)::FAST>; });
+}
 struct BrPlan {
   int nparts = 0;
   BrKind kind[2] = {BR_BATCH, BR_BATCH};
@@ -603,18 +572,18 @@ int launch_blind_rotate(tfhe_hip_ctx *ctx, hipStream_t s, const BrCall &c) {
 #endif
     const size_t begin = pl.begin[q], m_all = pl.count[q];
     if (pl.kind[q] == BR_PAIR) {
-      CHK(launch(br_pair_kernel(ctx, many), (unsigned)((m_all + 1) / 2), 64u * kPairWaves, blind_rotate_pair_lds_bytes(ctx->P.n),
+      CHK(launch(br_kernel(ctx, BR_PAIR, many), (unsigned)((m_all + 1) / 2), 64u * kPairWaves, blind_rotate_pair_lds_bytes(ctx->P.n),
                  part(begin, m_all)));
     } else if (pl.kind[q] == BR_SINGLE) {
 #if defined(TFHE_EXPERIMENT) && defined(TFHE_EXP_WIDE1)
       if (ctx->dispatch.exp_wide1) {
         if (lut_shift) return fail(ctx, TFHE_HIP_EINVAL, "the one-wave-per-row experiment kernel has no many-LUT epilogue");
-        CHK(launch(br_single_kernel(ctx), (unsigned)m_all, 128u * (unsigned)ctx->P.l,
+        CHK(launch(br_kernel(ctx, BR_SINGLE), (unsigned)m_all, 128u * (unsigned)ctx->P.l,
                    blind_rotate_wide_lds_bytes(ctx->P.n, ctx->P.l), part(begin, m_all)));
         continue;
       }
 #endif
-      CHK(launch(br_single_kernel(ctx, many), (unsigned)m_all, 64u * kWide2Waves, blind_rotate_wide2_lds_bytes(ctx->P.n, ctx->P.l),
+      CHK(launch(br_kernel(ctx, BR_SINGLE, many), (unsigned)m_all, 64u * kWide2Waves, blind_rotate_wide2_lds_bytes(ctx->P.n, ctx->P.l),
                  part(begin, m_all)));
     } else {
       // Default: ONE launch of the whole part.  The four waves of a workgroup meet at a barrier every CMUX step
@@ -626,7 +595,7 @@ int launch_blind_rotate(tfhe_hip_ctx *ctx, hipStream_t s, const BrCall &c) {
       if (ctx->dispatch.br_chunk > 0) chunk = (size_t)ctx->dispatch.br_chunk;
       if (ctx->dispatch.br_chunk < 0) {
         int per_cu = 0;
-        const hipError_t e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, br_kernel(ctx), 64 * br_waves(ctx), lds);
+        const hipError_t e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, br_kernel(ctx, BR_BATCH), 64 * br_waves(ctx), lds);
         if (e == hipSuccess && per_cu > 0 && ctx->num_cus > 0) chunk = (size_t)per_cu * ctx->num_cus * br_waves(ctx);
       }
       if (ctx->dispatch.br_chunk == 0 && m_all >= 2 * kYieldChunk && comb_interactive(ctx)) chunk = kYieldChunk;
@@ -634,7 +603,7 @@ int launch_blind_rotate(tfhe_hip_ctx *ctx, hipStream_t s, const BrCall &c) {
       for (size_t done = 0; done < m_all; done += chunk) {
         const size_t m = (m_all - done < chunk) ? m_all - done : chunk;
         const unsigned bw = (unsigned)br_waves(ctx);
-        CHK(launch(br_kernel(ctx, many), (unsigned)((m + bw - 1) / bw), 64u * bw, lds, part(begin + done, m)));
+        CHK(launch(br_kernel(ctx, BR_BATCH, many), (unsigned)((m + bw - 1) / bw), 64u * bw, lds, part(begin + done, m)));
       }
     }
   }
@@ -1345,19 +1314,17 @@ int tfhe_hip_ctx_create(const tfhe_hip_params *p, int device, tfhe_hip_ctx **out
       const size_t cap = 160 * 1024;
       return hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(bytes < cap ? bytes : cap));
     };
-    if ((e = set_lds((const void *)br_kernel(ctx), br_is_l1(ctx) ? br_lds_bytes(ctx) : blind_rotate_lds_bytes(kMaxN))) != hipSuccess)
-      return bail("hipFuncSetAttribute(k_blind_rotate)", e);
-    if ((e = set_lds((const void *)br_single_kernel(ctx), blind_rotate_wide2_lds_bytes(kMaxN, p->l))) != hipSuccess)
-      return bail("hipFuncSetAttribute(k_blind_rotate_wide2)", e);
-    if (ctx->dispatch.pair_max && (e = set_lds((const void *)br_pair_kernel(ctx), blind_rotate_pair_lds_bytes(kMaxN))) != hipSuccess)
-      return bail("hipFuncSetAttribute(k_blind_rotate_pair)", e);
-    // the many-LUT instantiations of the three kernels (same LDS layouts)
-    if (!br_is_l1(ctx) && (e = set_lds((const void *)br_kernel(ctx, true), blind_rotate_lds_bytes(kMaxN))) != hipSuccess)
-      return bail("hipFuncSetAttribute(k_blind_rotate_many)", e);
-    if ((e = set_lds((const void *)br_single_kernel(ctx, true), blind_rotate_wide2_lds_bytes(kMaxN, p->l))) != hipSuccess)
-      return bail("hipFuncSetAttribute(k_blind_rotate_wide2_many)", e);
-    if (ctx->dispatch.pair_max && (e = set_lds((const void *)br_pair_kernel(ctx, true), blind_rotate_pair_lds_bytes(kMaxN))) != hipSuccess)
-      return bail("hipFuncSetAttribute(k_blind_rotate_pair_many)", e);
+    for (int many = 0; many < 2; ++many)  // the many-LUT instantiations have the same LDS layouts
+      for (BrKind kind : {BR_BATCH, BR_SINGLE, BR_PAIR}) {
+        if (kind == BR_PAIR && !ctx->dispatch.pair_max) continue;
+        if (kind == BR_BATCH && many && br_is_l1(ctx)) continue;  // (the l = 1 experiment kernel has no many-LUT form)
+        const size_t bytes = kind == BR_PAIR     ? blind_rotate_pair_lds_bytes(kMaxN)
+                             : kind == BR_SINGLE ? blind_rotate_wide2_lds_bytes(kMaxN, p->l)
+                             : br_is_l1(ctx)     ? br_lds_bytes(ctx)
+                                                 : blind_rotate_lds_bytes(kMaxN);
+        if ((e = set_lds((const void *)br_kernel(ctx, kind, many), bytes)) != hipSuccess)
+          return bail((std::string("hipFuncSetAttribute(blind rotation: ") + kBrKindName[kind] + (many ? ", many-LUT)" : ")")).c_str(), e);
+      }
     if (ks_sliced_fits(*p))
       for (int sets : {24, 28, 32, 36})
         if ((e = set_lds((const void *)sl2_kernel(p->basebit, sets), ks_sl2_lds_bytes(p->basebit, sets, ks_sl2_rp(p->basebit)))) != hipSuccess)
@@ -1371,7 +1338,7 @@ int tfhe_hip_ctx_create(const tfhe_hip_params *p, int device, tfhe_hip_ctx **out
     {
       const bool keep = ctx->dispatch.exp_wide1;
       ctx->dispatch.exp_wide1 = true;
-      (void)set_lds((const void *)br_single_kernel(ctx), blind_rotate_wide_lds_bytes(kMaxN, p->l));
+      (void)set_lds((const void *)br_kernel(ctx, BR_SINGLE), blind_rotate_wide_lds_bytes(kMaxN, p->l));
       ctx->dispatch.exp_wide1 = keep;
     }
 #endif

@@ -95,7 +95,7 @@ def test_gpu_trivial_ciphertexts_read_the_table_exactly(O, setname, m):
 
 
 def test_gpu_gate_prep_on_trivial_inputs_is_the_linear_form_of_gates_rs(O, eng128, keys128):
-    """The gate prep fused into the blind rotation's prologue (kGateCa / Cb / Cc) against the linear forms of gates.rs:54-150,
+    """The gate prep fused into the blind rotation's prologue (kGateTable) against the linear forms of gates.rs:54-150,
     with no key and no noise: trivial inputs with random phases through tfhe_hip_batch_gates_mixed_nks (per-ciphertext gate
     codes, bootstrap without key switch) -- 400 exact constraints per gate; once merged (small call) and once as a batch."""
     n = eng128.params.n

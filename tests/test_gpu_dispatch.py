@@ -100,6 +100,117 @@ def test_dispatch_crossovers_bit_exact(O, monkeypatch, setname, extra):
     fixed.close()
 
 
+FORM_COUNTS = (5, 1)  # 5: the batch kernel's second workgroup has one live wave and three spare ones, the pair kernel's
+#                       last workgroup runs its ciphertext twice and stores it once; n = 700 leaves a ragged last pass
+#                       in the 64- and the 512-strided loops
+
+
+def _forms_inputs(O, sk, count):
+    from test_gpu_many_lut import _batch
+
+    a, b, tv = _batch(sk, count, 9100 + count)
+    rng = np.random.default_rng(9200 + count)
+    tvs = rng.integers(0, 1 << 32, (count, 2, N), dtype=np.uint64).astype(np.uint32)
+    wires = np.stack([sk.encrypt_bool(rng.integers(0, 2, count).astype(bool), 9300 + 10 * count + k) for k in range(3)])
+    # device-side gate codes: 200 is far outside tfhe_hip_gate, 11 is the first code outside it
+    codes = np.array([O.GATE_NAND, 200, O.GATE_XOR, O.GATE_ANDNY, O.GATE_COPY] if count == 5 else [11], np.uint8)
+    return dict(a=a, b=b, tv=tv, tvs=tvs, wires=wires, codes=codes)
+
+
+def _forms_circuit(R, tv):
+    """One node per launch, so that every launch of a level has `count` ciphertexts, all gathered through idx_a / idx_b:
+    a gate level, a gate and a many-LUT group on its output, a programmable bootstrap on theirs."""
+    c = R.Circuit(3)
+    g1 = c.nand(0, 1)
+    g2 = c.xor(g1, 2)
+    lut = c.lut(tv)
+    m = c.pbs_many(1, g1, 1, 2, 5, lut, 2)
+    c.pbs(1, g2, 3, m[1], 0x12345678, lut)
+    return c
+
+
+FORM_CA, FORM_CB, FORM_CC = 1, 3, 0x12345678
+
+
+def _forms_oracle(O, R, ck, d):
+    from test_gpu_many_lut import _prep, many_model
+
+    a, b, tv, tvs = d["a"], d["b"], d["tv"], d["tvs"]
+    prep = _prep(a, b, FORM_CA, FORM_CB, FORM_CC)
+    want = {}
+    codes = np.where(d["codes"] > O.GATE_COPY, O.GATE_COPY, d["codes"])  # a bad code is treated as COPY
+    want["codes"] = np.concatenate([O.batch_gate(ck, int(g), a[i], b[i] if g != O.GATE_COPY else None)
+                                    for i, g in enumerate(codes)])
+    want["circuit"] = _forms_circuit(R, tv).run_reference(
+        lambda op, x, y: O.batch_gate(ck, op, x, y), d["wires"],
+        pbs_fn=lambda t, x: O.batch_bootstrap(ck, x, testvec=t), many_fn=lambda t, x, k: many_model(O, ck, x, t, k))
+    for ks in (True, False):
+        want["per_ct", ks] = O.batch_bootstrap(ck, prep, testvec=tvs, keyswitch=ks)
+    want["blind_rotate"] = O.batch_blind_rotate(ck, a, testvec=tv)
+    for k in (2, 8):
+        want["many", k, True], want["many", k, False] = many_model(O, ck, prep, tv, k, both=True)
+    return want
+
+
+def _forms_device(O, R, eng, d):
+    import torch
+
+    a, b, tv, tvs = d["a"], d["b"], d["tv"], d["tvs"]
+    got = {}
+    dev = torch.device("cuda:0")
+    ta, tb = torch.from_numpy(a.view(np.int32)).to(dev), torch.from_numpy(b.view(np.int32)).to(dev)
+    to = torch.empty_like(ta)
+    eng.synchronize()
+    eng.batch_gates_mixed_dev(torch.from_numpy(d["codes"]).to(dev), ta, tb, to)
+    with pytest.raises(R._capi.TfheHipError, match="gate code"):
+        eng.synchronize()
+    eng.synchronize()  # raised once
+    got["codes"] = to.cpu().numpy().view(np.uint32)
+    got["circuit"] = _forms_circuit(R, tv).run(eng, d["wires"])
+    for ks in (True, False):
+        got["per_ct", ks] = eng.batch_lincomb_bootstrap(FORM_CA, a, FORM_CB, b, FORM_CC, testvec=tvs, keyswitch=ks)
+    got["blind_rotate"] = eng.batch_blind_rotate(a, tv)
+    for k in (2, 8):
+        for ks in (True, False):
+            got["many", k, ks] = eng.batch_lincomb_bootstrap_many(FORM_CA, a, FORM_CB, b, FORM_CC, tv, n_luts=k, keyswitch=ks)
+    return got
+
+
+def test_every_prologue_and_epilogue_form_on_each_forced_kernel(O, keys128, monkeypatch):
+    """The fused kernels share one prologue and one epilogue (br_prologue / br_epilogue, blind_rotate.hpp), reached
+    with a lane of 64 or a thread of 512 and with accumulators at different places.  Every form of them -- device-side
+    gate codes with an out-of-range one (flag raised once, row treated as COPY), a circuit's gathered operands,
+    per-ciphertext test vectors with and without key switch, the TRLWE output, many-LUT with 2 and 8 functions with and
+    without key switch -- on each kernel forced (TFHE_HIP_BR_KERNEL), at 5 ciphertexts and at 1: the oracle's words,
+    and so the same words from all three kernels."""
+    import rs_tfhe_amd as R
+    from lockstep import BR_KERNEL_ENVS, with_br_kernel
+
+    sk, ck = keys128
+    pk = _cloud_key(ck)
+    data = {count: _forms_inputs(O, sk, count) for count in FORM_COUNTS}
+    want = {count: _forms_oracle(O, R, ck, data[count]) for count in FORM_COUNTS}
+    outs = {}
+    for name in BR_KERNEL_ENVS:
+        with_br_kernel(monkeypatch, name)
+        eng = R.Engine(pk.params, 0)
+        try:
+            eng.load_cloud_key(pk)
+            for count in FORM_COUNTS:
+                assert f"blind_rotate={name}[0,{count})" in eng.describe_dispatch(count)
+                outs[name, count] = _forms_device(O, R, eng, data[count])
+        finally:
+            eng.close()
+        for count in FORM_COUNTS:
+            assert outs[name, count].keys() == want[count].keys()
+            for form, w in want[count].items():
+                assert np.array_equal(outs[name, count][form], w), (name, count, form)
+    for other in ("pair", "batch"):
+        for count in FORM_COUNTS:
+            for form, x in outs["single", count].items():
+                assert np.array_equal(x, outs[other, count][form]), (other, count, form)
+
+
 def test_contexts_created_in_any_order_keep_their_lds_limits(O, keys128, keys80):
     """hipFuncAttributeMaxDynamicSharedMemorySize belongs to the kernel, not to the context: SECURITY_128 / 110 / 80_BIT
     share `k_blind_rotate<3, true>` and the latency kernels.  A 128-bit context, THEN an 80-bit one (smaller n, smaller
