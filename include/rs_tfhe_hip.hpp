@@ -168,6 +168,8 @@ class Engine {
     uint64_t last_use = 0;
     int users = 0;  // calls in flight (registry lock): never evicted while > 0
     std::mutex load_mu;
+    const void *pk_key = nullptr;   // the packing key loaded beside the cloud key (bootstrap_bivariate), under load_mu
+    uint64_t pk_fp = 0;
   };
 
  public:
@@ -204,6 +206,18 @@ class Engine {
     template <class F>
     void with_key(const CompressedCloudKey &, F &&call) {
       e_->check(call(v_->h));
+    }
+    // `pk` beside this view's cloud key (the tree bootstrap needs both on one handle): loaded again only when another
+    // key (address or content sample) is passed
+    void ensure_packing_key(const PackingKey &pk) {
+      if (!pk.matches(e_->params_)) throw std::runtime_error("PackingKey does not match the parameter set");
+      std::lock_guard<std::mutex> lk(v_->load_mu);
+      const uint64_t fp = fingerprint(pk);
+      if (v_->pk_key == &pk && v_->pk_fp == fp && tfhe_hip_packing_key_is_loaded(v_->h)) return;
+      v_->pk_key = nullptr;
+      e_->check(tfhe_hip_load_packing_key(v_->h, pk.mask_seed.data(), pk.bodies.data()));
+      v_->pk_key = &pk;
+      v_->pk_fp = fp;
     }
     tfhe_hip_ctx *handle() const { return v_->h; }
     tfhe_hip_ctx *context() const { return e_->ctx_; }
@@ -261,18 +275,36 @@ class Engine {
   // [G][2][N] under s1.  The packing key sits in a key view of its own on this context, loaded again only when another
   // key (address or content sample) is passed; packing needs no cloud key.
   std::vector<Torus> pack(const PackingKey &pk, const Torus *in, size_t count) {
-    if (!pk.matches(params_)) throw std::runtime_error("PackingKey does not match the parameter set");
     std::lock_guard<std::mutex> lk(pk_mu_);
-    const uint64_t fp = fingerprint(pk);
-    if (!pk_view_ && tfhe_hip_key_create(ctx_, &pk_view_) != TFHE_HIP_OK) throw std::runtime_error("tfhe_hip_key_create failed");
-    if (pk_key_ != &pk || pk_fp_ != fp || !tfhe_hip_packing_key_is_loaded(pk_view_)) {
-      pk_key_ = nullptr;
-      check(tfhe_hip_load_packing_key(pk_view_, pk.mask_seed.data(), pk.bodies.data()));
-      pk_key_ = &pk;
-      pk_fp_ = fp;
-    }
+    packing_view_locked(pk);
     std::vector<Torus> out((count + N - 1) / N * 2 * N);
     check(tfhe_hip_batch_pack_tlwe(pk_view_, in, count, out.data()));
+    return out;
+  }
+
+  // Encrypted-table key switch (tfhe_hip_batch_pack_table): in [m][count][n+1], function-major (what the many-LUT
+  // bootstrap writes) -> `count` encrypted test vectors [count][2][N] under s1, on the packing key's view (as pack).
+  std::vector<Torus> pack_table(const PackingKey &pk, const Torus *in, int m, size_t count) {
+    std::lock_guard<std::mutex> lk(pk_mu_);
+    packing_view_locked(pk);
+    std::vector<Torus> out(count * 2 * N);
+    check(tfhe_hip_batch_pack_table(pk_view_, in, m, count, out.data()));
+    return out;
+  }
+
+  // Tree bootstrap (tfhe_hip_batch_bootstrap_bivariate): out[c] encrypts f(x[c], y[c]) for digits of modulus m; tables
+  // [m / n_luts][2][N] from lut::Generator::generate_bivariate_tables.  Runs on the key view that holds `ck`, where
+  // `pk` is loaded beside it.
+  static std::vector<Torus> bootstrap_bivariate(const CloudKey &ck, const PackingKey &pk, const Torus *x, const Torus *y,
+                                                const std::vector<Torus> &tables, int m, int n_luts, bool keyswitch,
+                                                size_t count, int device = 0) {
+    if (n_luts > 0 && m > 0 && tables.size() != (size_t)(m / n_luts) * 2 * N) throw std::runtime_error("tables must be [m / n_luts][2][N]");
+    Bound b = for_key(ck, device);
+    b.ensure_packing_key(pk);
+    std::vector<Torus> out(count * (size_t)(ck.params.n + 1));
+    b.with_key(ck, [&](tfhe_hip_ctx *h) {
+      return tfhe_hip_batch_bootstrap_bivariate(h, x, y, tables.data(), m, n_luts, keyswitch ? 1 : 0, out.data(), count);
+    });
     return out;
   }
 
@@ -332,6 +364,17 @@ class Engine {
  public:
 
  private:
+  void packing_view_locked(const PackingKey &pk) {  // pk_mu_ held: the packing key's view holds `pk`
+    if (!pk.matches(params_)) throw std::runtime_error("PackingKey does not match the parameter set");
+    const uint64_t fp = fingerprint(pk);
+    if (!pk_view_ && tfhe_hip_key_create(ctx_, &pk_view_) != TFHE_HIP_OK) throw std::runtime_error("tfhe_hip_key_create failed");
+    if (pk_key_ != &pk || pk_fp_ != fp || !tfhe_hip_packing_key_is_loaded(pk_view_)) {
+      pk_key_ = nullptr;
+      check(tfhe_hip_load_packing_key(pk_view_, pk.mask_seed.data(), pk.bodies.data()));
+      pk_key_ = &pk;
+      pk_fp_ = fp;
+    }
+  }
   static Engine &for_params_locked(const SecurityParams &p, int device) {
     for (auto &e : registry())
       if (e->params_ == p && e->device_ == device) return *e;
@@ -743,6 +786,23 @@ class Generator {  // generator.rs:15-259
       for (size_t i = start; i < end; ++i) raw[i] = encoder_.encode(fs[(i - start) % k](x));
     }
     return rotate(raw);
+  }
+  // The stage-1 tables of the tree bootstrap of f(x, y) (Engine::bootstrap_bivariate): [m / k][2][N] words, table j packing
+  // f(j k + r, .) for r < k as generate_many_lookup_table does.  m a power of two in [2, 512], k in {1, 2, 4, 8}, k <= m.
+  std::vector<Torus> generate_bivariate_tables(const std::function<size_t(size_t, size_t)> &f, size_t k = 1) const {
+    const size_t m = encoder_.message_modulus;
+    if (m < 2 || m > 512 || (m & (m - 1))) throw std::invalid_argument("generate_bivariate_tables: m is a power of two in [2, 512]");
+    if ((k != 1 && k != 2 && k != 4 && k != 8) || k > m) throw std::invalid_argument("generate_bivariate_tables: n_luts is 1, 2, 4 or 8, at most m");
+    std::vector<Torus> out;
+    out.reserve(m / k * 2 * N);
+    for (size_t j = 0; j < m / k; ++j) {
+      std::vector<std::function<size_t(size_t)>> fs;
+      for (size_t r = 0; r < k; ++r) fs.push_back([&f, x = j * k + r](size_t y) { return f(x, y); });
+      const LookupTable t = generate_many_lookup_table(fs);
+      out.insert(out.end(), t.poly.a.begin(), t.poly.a.end());
+      out.insert(out.end(), t.poly.b.begin(), t.poly.b.end());
+    }
+    return out;
   }
   size_t mod_switch(Torus x) const {  // :235-238: (x / u32::MAX * size).round() % size
     const double scaled = (double)x / 4294967295.0 * (double)N;

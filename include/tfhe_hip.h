@@ -322,6 +322,54 @@ int tfhe_hip_batch_unpack_trlwe(tfhe_hip_ctx *ctx, const uint32_t *trlwe, size_t
 int tfhe_hip_batch_unpack_trlwe_dev(tfhe_hip_ctx *ctx, const uint32_t *trlwe, size_t groups, const uint32_t *slots,
                                     size_t count, uint32_t *out, void *stream);
 
+/* ---- encrypted-table key switch and the tree bootstrap: any function of two encrypted digits ------
+ *
+ * A programmable bootstrap evaluates a table of ONE input, whose message modulus the parameter set caps (16 on
+ * SECURITY_UINT4).  A function f(x, y) of two digits of modulus m is the tree-based bootstrap (Guimaraes, Borin,
+ * Aranha, TCHES 2021): bootstrap y with the m tables f(i, .), turn the m results into ONE encrypted test vector, and
+ * blind-rotate that by x -- m / k + 1 blind rotations with k-fold many-LUT tables, and no modulus above m anywhere.
+ * The middle step is the encrypted-table key switch: the packing key switch of the m results, each spread over its box.
+ *
+ * Definition (normative).  In integers mod 2^32, negacyclic mod X^N + 1.  The key, the digits d_l and the gadget are
+ * the packing key's (section above): no new key material and no new security assumption.  m is a power of two,
+ * 2 <= m <= 512; W = N / m, off = W / 2 (div_round(x N, m) = x W and div_round(N, 2m) of the LUT generator).
+ *   in   [m][count][n+1] u32, function-major: ciphertext c of function x at in[x][c] -- the layout
+ *        tfhe_hip_batch_lincomb_bootstrap_many writes.
+ *   out  [count][2][N] u32, the a row then the b row.
+ *   For ciphertext c, with c_x = (a_x, b_x) = in[x][c]:
+ *     P_x = ( - sum_{i,l} d_l(a_x[i]) a_{i,l} ,  b_x X^0 - sum_{i,l} d_l(a_x[i]) b_{i,l} )    (packing's result for one
+ *                                                                                             input at slot 0)
+ *     Q   = sum_x X^(x W) P_x
+ *     out[c] = X^(-off) (1 + X + ... + X^(W-1)) Q   on both rows, i.e.
+ *     out[c][h][y] = sum_{r < W} Q~[h][y + off - r],  Q~ the negacyclic extension (Q~[i] = -Q[i -/+ N] outside 0..N-1).
+ *   Q is what tfhe_hip_batch_pack_tlwe returns for a group that holds c_x at slot x W and zero ciphertexts elsewhere.
+ *   For trivial inputs (a = 0, b = v_x) the result is key-free: a row 0, b row the generator's table of the values v.
+ *   The phase of out[c] under s1 is that table of the inputs' phases -- each input's rounding error replicated across
+ *   its box, not summed -- plus key noise summed over W terms.  Every device and parameter set gives these words exactly.
+ * Semantics.  The call needs the packing key and no cloud key: TFHE_HIP_ENOKEY without one.  TFHE_HIP_EINVAL for m not
+ * a power of two in [2, 512], for m * count >= 2^31, or for a null pointer with count > 0; count == 0 returns
+ * TFHE_HIP_OK.  Bulk calls (the context's mutex, never the combining front end).  _dev: device pointers, only enqueued
+ * on `stream` (NULL: the context's stream). */
+int tfhe_hip_batch_pack_table(tfhe_hip_ctx *ctx, const uint32_t *in, int m, size_t count, uint32_t *out);
+int tfhe_hip_batch_pack_table_dev(tfhe_hip_ctx *ctx, const uint32_t *in, int m, size_t count, uint32_t *out,
+                                  void *stream);
+/* The tree bootstrap.  x, y, out [count][n+1]; testvecs [m / k][2][N] with k = n_luts in {1, 2, 4, 8}, k <= m: table j
+ * packs f(j k + r, .), r < k, as the many-LUT generator does (k = 1: the plain LUT of f(j, .)).
+ *   S[j k + r] = output r of tfhe_hip_batch_lincomb_bootstrap_many(1 * y, table j, n_luts = k, key switch on)
+ *   T          = tfhe_hip_batch_pack_table(S, m)
+ *   out        = tfhe_hip_batch_bootstrap(x, T, per_ct = 1, keyswitch)
+ * word for word: x selects among the m stage-1 results, y is what stage 1 rotates by.  The batch is processed in chunks
+ * so that the context-owned stage-1 scratch [m][chunk][n+1] stays at or under 256 MiB (TFHE_HIP_BIVARIATE_CHUNK in
+ * the environment lowers the chunk, in ciphertexts: for tests); neither chunking nor the kernel selectors change a bit.
+ * The scratch grows on demand and is freed with the context.  Needs the cloud key and the packing key
+ * (TFHE_HIP_ENOKEY for either); TFHE_HIP_EINVAL for bad m or n_luts, null tables, or null x / y / out with count > 0.
+ * Bulk calls, like the many-LUT bootstrap.  _dev only enqueues on `stream`. */
+int tfhe_hip_batch_bootstrap_bivariate(tfhe_hip_ctx *ctx, const uint32_t *x, const uint32_t *y, const uint32_t *testvecs,
+                                       int m, int n_luts, int keyswitch, uint32_t *out, size_t count);
+int tfhe_hip_batch_bootstrap_bivariate_dev(tfhe_hip_ctx *ctx, const uint32_t *x, const uint32_t *y,
+                                           const uint32_t *testvecs, int m, int n_luts, int keyswitch, uint32_t *out,
+                                           size_t count, void *stream);
+
 /* Pinned host buffers.  The host entry points below take ordinary (pageable) memory and stage it through the
  * device around the kernels: 3 x 184 MB for a 65,536-ciphertext gate batch, about 7 % of the call.  When EVERY
  * ciphertext operand of a call (inputs and output) is pinned host memory -- allocated here, or the caller's own
@@ -661,6 +709,12 @@ int tfhe_hip_pool_batch_unpack_trlwe(tfhe_hip_pool *pool, const uint32_t *trlwe,
                                      size_t count, uint32_t *out);
 int tfhe_hip_pool_batch_unpack_trlwe_dev(tfhe_hip_pool *pool, int home_member, const uint32_t *trlwe, size_t groups,
                                          const uint32_t *slots, size_t count, uint32_t *out, void *stream);
+/* The tree bootstrap on a pool, HOST pointers (same arguments and result as tfhe_hip_batch_bootstrap_bivariate): the
+ * batch is cut by count over the members in input order, every member gets the tables whole.  Needs the cloud key
+ * and tfhe_hip_pool_load_packing_key. */
+int tfhe_hip_pool_batch_bootstrap_bivariate(tfhe_hip_pool *pool, const uint32_t *x, const uint32_t *y,
+                                            const uint32_t *testvecs, int m, int n_luts, int keyswitch, uint32_t *out,
+                                            size_t count);
 
 /* The batched hot path over all members, HOST pointers: same arguments and semantics as the single-context host
  * entry points of the same name (gates.rs:352-547; gates.rs:157-199; bootstrap/{vanilla,lut}.rs; trgsw.rs:289-305;

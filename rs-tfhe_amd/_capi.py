@@ -101,6 +101,10 @@ SIGNATURES = {
     "tfhe_hip_batch_pack_tlwe_dev": (C.c_int, [_CTX, _P, _SZ, _P, _P]),
     "tfhe_hip_batch_unpack_trlwe": (C.c_int, [_CTX, _P, _SZ, _P, _SZ, _P]),
     "tfhe_hip_batch_unpack_trlwe_dev": (C.c_int, [_CTX, _P, _SZ, _P, _SZ, _P, _P]),
+    "tfhe_hip_batch_pack_table": (C.c_int, [_CTX, _P, C.c_int, _SZ, _P]),
+    "tfhe_hip_batch_pack_table_dev": (C.c_int, [_CTX, _P, C.c_int, _SZ, _P, _P]),
+    "tfhe_hip_batch_bootstrap_bivariate": (C.c_int, [_CTX, _P, _P, _P, C.c_int, C.c_int, C.c_int, _P, _SZ]),
+    "tfhe_hip_batch_bootstrap_bivariate_dev": (C.c_int, [_CTX, _P, _P, _P, C.c_int, C.c_int, C.c_int, _P, _SZ, _P]),
     "tfhe_hip_batch_gate": (C.c_int, [_CTX, C.c_int, _P, _P, _P, _SZ]),
     "tfhe_hip_batch_gate_dev": (C.c_int, [_CTX, C.c_int, _P, _P, _P, _SZ, _P]),
     "tfhe_hip_batch_gates_mixed": (C.c_int, [_CTX, _P, _P, _P, _P, _SZ]),
@@ -172,6 +176,7 @@ SIGNATURES = {
     "tfhe_hip_pool_batch_lincomb_bootstrap": (C.c_int, [_CTX, _U32, _P, _U32, _P, _U32, _P, C.c_int, C.c_int, _P, _SZ]),
     "tfhe_hip_pool_batch_lincomb_bootstrap_many": (
         C.c_int, [_CTX, _U32, _P, _U32, _P, _U32, _P, C.c_int, C.c_int, C.c_int, _P, _SZ]),
+    "tfhe_hip_pool_batch_bootstrap_bivariate": (C.c_int, [_CTX, _P, _P, _P, C.c_int, C.c_int, C.c_int, _P, _SZ]),
     # ... for a batch resident on one member's GPU (home_member, device pointers, stream)
     "tfhe_hip_pool_batch_gate_dev": (C.c_int, [_CTX, C.c_int, C.c_int, _P, _P, _P, _SZ, _P]),
     "tfhe_hip_pool_batch_gates_mixed_dev": (C.c_int, [_CTX, C.c_int, _P, _P, _P, _P, _SZ, _P]),

@@ -323,6 +323,24 @@ class _Handle:
             raise ValueError("out must be [ceil(count / N)][2][N]")
         self._call_dev("batch_pack_tlwe_dev", h, self._tp(h, cts), count, self._tp(h, out), self._stream_ptr(h, stream))
 
+    # -- tree bootstrap (include/tfhe_hip.h): any function of two encrypted digits -------------------------------------
+    def batch_bootstrap_bivariate(self, x, y, testvecs, m: int, n_luts: int = 1, keyswitch: bool = True) -> np.ndarray:
+        """out[c] = f(x[c], y[c]) for digits of modulus m: the m / n_luts many-LUT bootstraps of y with `testvecs`
+        [m / n_luts][2][N] (Generator.generate_bivariate_tables), the encrypted-table key switch of their results, then
+        the bootstrap of x with that per-ciphertext table (`tfhe_hip_batch_bootstrap_bivariate`).  Needs the cloud key
+        and the packing key; m, n_luts and missing tables are checked by the library."""
+        x, y = self._cts(x), self._cts(y)
+        if y.shape != x.shape:
+            raise ValueError("operand batches differ in shape")
+        tv = _u32(testvecs) if testvecs is not None else None
+        good = isinstance(m, int) and isinstance(n_luts, int) and n_luts > 0 and m % n_luts == 0
+        if tv is not None and good and tv.size != (m // n_luts) * 2 * N:
+            raise ValueError("testvecs must be [m / n_luts][2][N]")
+        out = np.empty_like(x)
+        self._call("batch_bootstrap_bivariate", _ptr(x), _ptr(y), _ptr(tv), int(m), int(n_luts), int(keyswitch),
+                   _ptr(out), len(x))
+        return out
+
     # -- unpacking key switch (include/tfhe_hip.h): slots of TRLWE lv1 ciphertexts back to lv0 ciphertexts --------------
     def unpack(self, trlwe, count=None, slots=None) -> np.ndarray:
         """[groups][2][N] TRLWE lv1 -> [count][n+1] lv0 ciphertexts under the cloud key's key-switching key
@@ -602,6 +620,42 @@ class Engine(_Handle):
         self._chk(self._lib.tfhe_hip_expand_seeded_tlwe_dev(self._ctx, C.addressof(seed), C.c_uint64(int(first_index)),
                                                             self._tp(None, bodies), count, self._tp(None, out),
                                                             self._stream_ptr(None, stream)))
+
+    # -- encrypted-table key switch and the tree bootstrap's device form (include/tfhe_hip.h) ----------------------------
+    def pack_table(self, stage1, m: int) -> np.ndarray:
+        """[m][count][n+1] lv0 ciphertexts, function-major (what batch_lincomb_bootstrap_many returns) ->
+        [count][2][N] encrypted test vectors under s1 (`tfhe_hip_batch_pack_table`; packing.table_model)."""
+        s1 = _u32(stage1)
+        width = self.params.n + 1
+        if not isinstance(m, int) or m <= 0 or s1.size % (m * width):
+            count = 0 if s1.size == 0 else -1
+        else:
+            count = s1.size // (m * width)
+        if count < 0:
+            raise ValueError("stage1 must be [m][count][n+1]")
+        out = np.empty((count, 2, N), np.uint32)
+        self._chk(self._lib.tfhe_hip_batch_pack_table(self._ctx, _ptr(s1), int(m), count, _ptr(out)))
+        return out
+
+    def pack_table_dev(self, stage1, m: int, out, stream=None) -> None:
+        """Device form: stage1 [m * count][n+1] (or [m][count][n+1]) and out [count][2][N] 32-bit CUDA tensors."""
+        width = self.params.n + 1
+        if out is None or out.numel() % (2 * N):
+            raise ValueError("out must be [count][2][N]")
+        count = out.numel() // (2 * N)
+        if stage1 is None or stage1.numel() != max(int(m), 0) * count * width:
+            raise ValueError("stage1 must be [m][count][n+1]")
+        self._chk(self._lib.tfhe_hip_batch_pack_table_dev(self._ctx, self._tp(None, stage1), int(m), count,
+                                                          self._tp(None, out), self._stream_ptr(None, stream)))
+
+    def batch_bootstrap_bivariate_dev(self, x, y, testvecs, m: int, out, n_luts: int = 1, keyswitch: bool = True,
+                                      stream=None) -> None:
+        """Device form of batch_bootstrap_bivariate: x, y, out [count][n+1] and testvecs [m / n_luts][2][N] 32-bit CUDA
+        tensors of this engine's GPU; only enqueues."""
+        count = self._dev_batch(None, x, y, out)
+        self._chk(self._lib.tfhe_hip_batch_bootstrap_bivariate_dev(
+            self._ctx, self._tp(None, x), self._tp(None, y), self._tp(None, testvecs), int(m), int(n_luts), int(keyswitch),
+            self._tp(None, out), count, self._stream_ptr(None, stream)))
 
     def cloud_key_device_tensors(self):
         """(bsk, ksk, testvec, decomposition_offset): the context's key buffers in the engine layouts as uint8 torch

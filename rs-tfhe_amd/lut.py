@@ -130,6 +130,21 @@ class Generator:
         lut.poly[1, :] = rot
         return lut
 
+    def generate_bivariate_tables(self, f, n_luts: int = 1) -> np.ndarray:
+        """The stage-1 tables of the tree bootstrap of f(x, y), x and y of this generator's modulus m
+        (Engine.batch_bootstrap_bivariate): [m / k][2][N] u32 with k = n_luts in {1, 2, 4, 8}, k <= m, table j packing
+        f(j k + r, .) for r < k as generate_many_lookup_table does (k = 1: generate_lookup_table of f(j, .)).  m is a
+        power of two in [2, 512]."""
+        m, k = self.message_modulus, n_luts
+        if m < 2 or m > 512 or m & (m - 1):
+            raise ValueError("generate_bivariate_tables: the message modulus is a power of two in [2, 512]")
+        if k not in (1, 2, 4, 8) or k > m:
+            raise ValueError("generate_bivariate_tables: n_luts is 1, 2, 4 or 8 and at most the message modulus")
+        out = np.empty((m // k, 2, N), np.uint32)
+        for j in range(m // k):
+            out[j] = self.generate_many_lookup_table([(lambda y, x=j * k + r: f(x, y)) for r in range(k)]).poly
+        return out
+
     def generate_lookup_table_assign(self, f, lut_out: LookupTable) -> None:  # generator.rs:89-137: into an existing table
         lut_out.copy_from(self.generate_lookup_table(f))
 

@@ -7,6 +7,10 @@ section's ChaCha20 keystream, bodies by exact negacyclic products with the binar
 server's result (`pack_model`), which the GPU (csrc/packing.hpp, `Engine.pack`) equals word for word.  `pack` runs it
 on the key view of a cloud key.
 
+The encrypted-table key switch ("encrypted-table key switch and the tree bootstrap" in the header) reuses the key and
+the contraction: `table_model` is its integer model (csrc/table.hpp, `Engine.pack_table`), `bootstrap_func2` runs the
+tree bootstrap of a function of two encrypted digits on the GPU.
+
 The way back ("unpacking key switch" in the header): `unpack_model` is the integer model of sample_extract_index
 followed by identity_key_switching, `unpack` runs it on the GPU (csrc/unpack.hpp, `Engine.unpack`).
 """
@@ -136,6 +140,22 @@ def make_packing_key(params: SecurityParams, key_lv0, key_lv1, rng=None, alpha=N
     return PackingKey(p, seed, bodies)
 
 
+def _key_halves(K):
+    """The 16-bit halves of the key rows as float64 matrices (the operands of contraction)."""
+    return (K & 0xFFFF).astype(np.float64), (K >> 16).astype(np.float64)
+
+
+def contraction(params: SecurityParams, halves, cts) -> np.ndarray:
+    """P[j] = sum_{i,l} d_l(a_j[i]) K[(i,l)] mod 2^32 for [M][n+1] ciphertexts: [M][2N] u32.  A float64 matmul over
+    the 16-bit halves of the key words (|sums| < 2^35: exact).  halves: _key_halves(key_rows(...))."""
+    p = params
+    k_lo, k_hi = halves
+    d = digits(p, cts[:, :p.n]).reshape(len(cts), -1).astype(np.float64)  # column i t + l
+    lo = (d @ k_lo).astype(np.int64)
+    hi = (d @ k_hi).astype(np.int64)
+    return ((lo + (hi << 16)) & 0xFFFFFFFF).astype(np.uint32)
+
+
 def pack_model(params: SecurityParams, mask_seed: bytes, bodies, cts, rows=None) -> np.ndarray:
     """The definition's result for [count][n+1] ciphertexts: [ceil(count / N)][2][N] u32.  The contraction
     P[j] = sum_{i,l} d_l(a_j[i]) K[(i,l)] is a float64 matmul over the 16-bit halves of the key words (|sums| < 2^35:
@@ -143,17 +163,14 @@ def pack_model(params: SecurityParams, mask_seed: bytes, bodies, cts, rows=None)
     p = params
     cts = np.ascontiguousarray(cts, dtype=np.uint32).reshape(-1, p.n + 1)
     K = key_rows(p, mask_seed, bodies) if rows is None else rows
-    k_lo, k_hi = (K & 0xFFFF).astype(np.float64), (K >> 16).astype(np.float64)
+    halves = _key_halves(K)
     groups = -(-len(cts) // N)
     out = np.zeros((groups, 2, N), np.uint32)
     xs = np.arange(N)
     for g in range(groups):
         c = cts[g * N:(g + 1) * N]
         m = len(c)
-        d = digits(p, c[:, :p.n]).reshape(m, -1).astype(np.float64)  # column i t + l
-        lo = (d @ k_lo).astype(np.int64)
-        hi = (d @ k_hi).astype(np.int64)
-        prod = ((lo + (hi << 16)) & 0xFFFFFFFF).astype(np.uint32)  # [m][2N]
+        prod = contraction(p, halves, c)  # [m][2N]
         y = xs[None, :] + np.arange(m)[:, None]  # X^j X^x = X^y, y < 2N - 1
         wrap = y >= N
         for h in range(2):
@@ -163,6 +180,47 @@ def pack_model(params: SecurityParams, mask_seed: bytes, bodies, cts, rows=None)
             out[g, h] = np.uint32(0) - (s.astype(np.int64) & 0xFFFFFFFF).astype(np.uint32)
         out[g, 1, :m] += c[:, p.n]
     return out
+
+
+def window(q, m: int) -> np.ndarray:
+    """X^(-off) (1 + X + ... + X^(W-1)) q on the last axis, W = N / m, off = W / 2, negacyclic mod X^N + 1 and wrapping
+    mod 2^32: out[y] = sum_{r < W} q~[y + off - r] (the second half of the encrypted-table key switch)."""
+    q = np.asarray(q, np.uint32)
+    W = N // m
+    off = W // 2
+    neg = (np.uint32(0) - q).astype(np.uint64)
+    ext = np.concatenate([neg, q.astype(np.uint64), neg], axis=-1)  # index i of q~ at position i + N
+    cs = np.concatenate([np.zeros(q.shape[:-1] + (1,), np.uint64), np.cumsum(ext, axis=-1, dtype=np.uint64)], axis=-1)
+    y = np.arange(N)
+    return ((cs[..., y + off + N + 1] - cs[..., y + off - W + N + 1]) & np.uint64(0xFFFFFFFF)).astype(np.uint32)
+
+
+def table_model(params: SecurityParams, mask_seed: bytes, bodies, stage1, m: int, rows=None) -> np.ndarray:
+    """The definition's result ("encrypted-table key switch", include/tfhe_hip.h) for stage1 [m][count][n+1],
+    function-major: [count][2][N] u32.  pack_model's contraction of every input alone (P_x at slot 0), the monomial
+    shifts X^(x W) summed per ciphertext, then `window`.  Integer arithmetic throughout: the GPU
+    (csrc/table.hpp, `Engine.pack_table`) equals it word for word.  rows: key_rows(...) when already made."""
+    p = params
+    if m < 2 or m > 512 or m & (m - 1):
+        raise ValueError("m is a power of two in [2, 512]")
+    s1 = np.ascontiguousarray(stage1, dtype=np.uint32).reshape(m, -1, p.n + 1)
+    count = s1.shape[1]
+    K = key_rows(p, mask_seed, bodies) if rows is None else rows
+    halves = _key_halves(K)
+    flat = s1.reshape(-1, p.n + 1)
+    P = np.empty((m * count, 2 * N), np.uint32)
+    for lo in range(0, len(flat), N):  # bounds the digits held at once
+        P[lo:lo + N] = np.uint32(0) - contraction(p, halves, flat[lo:lo + N])
+    P = P.reshape(m, count, 2, N)
+    P[:, :, 1, 0] += s1[:, :, p.n]
+    W = N // m
+    Q = np.zeros((count, 2, N), np.uint32)
+    for x in range(m):
+        j = x * W
+        r = np.roll(P[x], j, axis=-1)
+        r[..., :j] = np.uint32(0) - r[..., :j]  # X^(x W): what passes N changes sign
+        Q += r
+    return window(Q, m)
 
 
 def pack(cts, cloud_key, packing_key: PackingKey, device: int = 0) -> np.ndarray:
@@ -175,6 +233,21 @@ def pack(cts, cloud_key, packing_key: PackingKey, device: int = 0) -> np.ndarray
             if view._packing_key is not packing_key or not view.packing_key_is_loaded():
                 view.load_packing_key(packing_key)
             return view.pack(cts)
+
+
+def bootstrap_func2(xs, ys, f, m: int, cloud_key, packing_key: PackingKey, n_luts: int = 1, device: int = 0) -> np.ndarray:
+    """The tree bootstrap on the GPU: ciphertexts of f(x, y) for [count][n+1] ciphertexts xs, ys of digits of modulus m
+    (Generator(m).generate_bivariate_tables(f, n_luts), then Engine.batch_bootstrap_bivariate), on the key view of
+    `cloud_key` (bootstrap.keyed_engine), where `packing_key` is loaded once."""
+    from .bootstrap import keyed_engine
+    from .lut import Generator
+
+    tables = Generator(m).generate_bivariate_tables(f, n_luts)
+    with keyed_engine(cloud_key, device) as view:
+        with view.lock:  # as in pack: another thread's packing key cannot replace this one in between
+            if view._packing_key is not packing_key or not view.packing_key_is_loaded():
+                view.load_packing_key(packing_key)
+            return view.batch_bootstrap_bivariate(xs, ys, tables, m, n_luts)
 
 
 # ---- unpacking key switch: slots of TRLWE lv1 ciphertexts back to lv0 ciphertexts ------------------------------------

@@ -94,7 +94,19 @@ extern "C" {   // packing key switch (include/tfhe_hip.h): up to N lv0 results i
                                         count: usize, out: *mut u32) -> c_int;
     fn tfhe_hip_pool_batch_unpack_trlwe_dev(pool: *mut TfheHipPool, home_member: c_int, trlwe: *const u32, groups: usize,
                                             slots: *const u32, count: usize, out: *mut u32, stream: *mut c_void) -> c_int;
+    // encrypted-table key switch and the tree bootstrap: any function of two encrypted digits.  pack_table has no pool
+    // form: it runs on a member context (tfhe_hip_pool_ctx) of the packing key's view
+    fn tfhe_hip_pool_ctx(pool: *mut TfheHipPool, member: c_int) -> *mut TfheHipCtx;
+    fn tfhe_hip_last_error(ctx: *const TfheHipCtx) -> *const c_char;
+    fn tfhe_hip_batch_pack_table(ctx: *mut TfheHipCtx, input: *const u32, m: c_int, count: usize, out: *mut u32) -> c_int;
+    fn tfhe_hip_pool_batch_bootstrap_bivariate(pool: *mut TfheHipPool, x: *const u32, y: *const u32, testvecs: *const u32,
+                                               m: c_int, n_luts: c_int, keyswitch: c_int, out: *mut u32,
+                                               count: usize) -> c_int;
 }
+
+/// A member context of a pool (tfhe_hip_pool_ctx): opaque, owned by the pool.
+#[repr(C)]
+pub struct TfheHipCtx { _private: [u8; 0] }
 
 const W: usize = params::tlwe_lv0::N + 1;     // words per TLWELv0
 const N: usize = params::trgsw_lv1::N;        // 1024
@@ -121,7 +133,8 @@ thread_local! {   // one arena per calling thread: a, b, c operands and the resu
 }
 
 /// A resident key: (address, content sample) of the CloudKey it holds + its key view of the pool.
-struct KeyView { addr: usize, fp: u64, view: *mut TfheHipPool, last_use: u64, users: usize }
+/// pk_fp: content sample of the packing key loaded beside the cloud key (bootstrap_bivariate), 0 = none.
+struct KeyView { addr: usize, fp: u64, view: *mut TfheHipPool, last_use: u64, users: usize, pk_fp: u64 }
 
 /// The resident packing key: (content sample of the key it holds, its key view of the pool; null until first use).
 struct PackingView { fp: u64, view: *mut TfheHipPool }
@@ -208,7 +221,7 @@ impl HipEngine {
                     let mut v = std::ptr::null_mut();
                     assert_eq!(unsafe { tfhe_hip_pool_key_create(self.pool, &mut v) }, 0, "tfhe_hip_pool_key_create failed");
                     Self::upload(v, ck);   // under the registry lock: a second thread with the same new key waits here
-                    views.push(KeyView { addr, fp, view: v, last_use: 0, users: 0 });
+                    views.push(KeyView { addr, fp, view: v, last_use: 0, users: 0, pk_fp: 0 });
                     views.len() - 1
                 }
             };
@@ -383,8 +396,15 @@ impl HipEngine {
         assert_eq!(cts.len() % W, 0, "cts is [count][n+1]");
         let count = cts.len() / W;
         let mut out = vec![0u32; (count + N - 1) / N * 2 * N];
-        let fp = Self::packing_fingerprint(mask_seed, bodies);
         let mut g = self.packing.lock().unwrap();   // held through the pack: a concurrent call cannot swap the key
+        self.packing_view(&mut g, mask_seed, bodies);
+        Self::check(g.view, unsafe { tfhe_hip_pool_batch_pack_tlwe(g.view, cts.as_ptr(), count, out.as_mut_ptr()) });
+        out
+    }
+
+    /// The packing key's own view holds (mask_seed, bodies): created on first use, loaded again only for another key.
+    fn packing_view(&self, g: &mut PackingView, mask_seed: &[u8; 32], bodies: &[u32]) {
+        let fp = Self::packing_fingerprint(mask_seed, bodies);
         if g.view.is_null() {
             let mut view = std::ptr::null_mut();
             assert_eq!(unsafe { tfhe_hip_pool_key_create(self.pool, &mut view) }, 0, "tfhe_hip_pool_key_create failed");
@@ -396,8 +416,61 @@ impl HipEngine {
             Self::check(g.view, unsafe { tfhe_hip_pool_load_packing_key(g.view, mask_seed.as_ptr(), bodies.as_ptr()) });
             g.fp = fp;
         }
-        Self::check(g.view, unsafe { tfhe_hip_pool_batch_pack_tlwe(g.view, cts.as_ptr(), count, out.as_mut_ptr()) });
+    }
+
+    /// Encrypted-table key switch, the definition of include/tfhe_hip.h: `stage1` ([m][count][n+1] lv0 ciphertexts, flat,
+    /// function-major -- what the many-LUT bootstrap writes) becomes `count` encrypted test vectors [count][2][N] under
+    /// s1, each the generator's table of its m inputs' phases.  Runs on the first member of the packing key's view (the
+    /// call has no pool form); the packing key as in `pack_tlwe`.
+    pub fn pack_table(&self, mask_seed: &[u8; 32], bodies: &[u32], stage1: &[u32], m: usize) -> Vec<u32> {
+        let n = params::tlwe_lv0::N;
+        assert_eq!(bodies.len(), n * params::trgsw_lv1::IKS_T * N, "bodies is [n][t][N]");
+        assert!(m > 0 && stage1.len() % (m * W) == 0, "stage1 is [m][count][n+1]");
+        let count = stage1.len() / (m * W);
+        let mut out = vec![0u32; count * 2 * N];
+        let mut g = self.packing.lock().unwrap();   // held through the call: a concurrent call cannot swap the key
+        self.packing_view(&mut g, mask_seed, bodies);
+        let ctx = unsafe { tfhe_hip_pool_ctx(g.view, 0) };
+        assert!(!ctx.is_null(), "tfhe_hip_pool_ctx failed");
+        let rc = unsafe { tfhe_hip_batch_pack_table(ctx, stage1.as_ptr(), m as c_int, count, out.as_mut_ptr()) };
+        if rc != 0 {
+            let msg = unsafe { std::ffi::CStr::from_ptr(tfhe_hip_last_error(ctx)) };
+            panic!("tfhe_hip: {}", msg.to_string_lossy());
+        }
         out
+    }
+
+    /// Tree bootstrap (tfhe_hip_pool_batch_bootstrap_bivariate): ciphertexts of f(x[c], y[c]) for digits of modulus `m`.
+    /// `tables` is [m / n_luts][2][N], flat: table j packs f(j n_luts + r, .) for r < n_luts as the many-LUT generator
+    /// does.  Runs under the key view of `ck`, where the packing key (mask_seed, bodies) is loaded beside the cloud key
+    /// on first use and again only when another packing key (content sample) is passed.
+    pub fn bootstrap_bivariate(&self, x: &[Ciphertext], y: &[Ciphertext], tables: &[u32], m: usize, n_luts: usize,
+                               keyswitch: bool, mask_seed: &[u8; 32], bodies: &[u32], ck: &CloudKey) -> Vec<Ciphertext> {
+        let n = params::tlwe_lv0::N;
+        assert_eq!(bodies.len(), n * params::trgsw_lv1::IKS_T * N, "bodies is [n][t][N]");
+        assert_eq!(x.len(), y.len(), "one y per x");
+        assert!(n_luts > 0 && m % n_luts == 0 && tables.len() == m / n_luts * 2 * N, "tables is [m / n_luts][2][N]");
+        let count = x.len();
+        let (mut fx, mut fy, mut out) = (vec![0u32; count * W], vec![0u32; count * W], vec![0u32; count * W]);
+        for (i, c) in x.iter().enumerate() { fx[i * W..(i + 1) * W].copy_from_slice(&c.p); }
+        for (i, c) in y.iter().enumerate() { fy[i * W..(i + 1) * W].copy_from_slice(&c.p); }
+        let pk_fp = Self::packing_fingerprint(mask_seed, bodies) | 1;   // (0 stands for "none loaded")
+        self.with_key(ck, |v| {
+            {   // under the registry lock, as a cloud-key upload: a second thread with the same keys waits here
+                let mut g = self.views.lock().unwrap();
+                if let Some(kv) = g.0.iter_mut().find(|kv| kv.view == v) {
+                    if kv.pk_fp != pk_fp {
+                        kv.pk_fp = 0;
+                        let rc = unsafe { tfhe_hip_pool_load_packing_key(v, mask_seed.as_ptr(), bodies.as_ptr()) };
+                        if rc != 0 { return (rc, ()); }
+                        kv.pk_fp = pk_fp;
+                    }
+                }
+            }
+            (unsafe { tfhe_hip_pool_batch_bootstrap_bivariate(v, fx.as_ptr(), fy.as_ptr(), tables.as_ptr(), m as c_int,
+                                                              n_luts as c_int, keyswitch as c_int, out.as_mut_ptr(), count) }, ())
+        });
+        Self::unflatten(&out)
     }
 
     /// Unpacking key switch, the definition of include/tfhe_hip.h: slots of `trlwe` ([groups][2][N] TRLWE lv1 under s1,
