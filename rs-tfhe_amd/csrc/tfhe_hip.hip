@@ -221,7 +221,7 @@ struct tfhe_hip_ctx {
   hipEvent_t exp_ev[2] = {nullptr, nullptr};
   std::vector<std::pair<hipEvent_t, hipEvent_t>> ev_br, ev_ks;
   uint64_t bootstraps = 0;
-  hipStream_t scratch_owner = nullptr;  // stream whose queued work may still use lv1/u1/u2
+  hipStream_t scratch_owner = nullptr;  // stream whose queued work may still use the scratch (claim_scratch)
   bool scratch_owned = false;
   // device diagnostics: [0] shader cycles, [1] constant-rate ticks (both summed over blind-rotate
   // workgroups while profiling is on), [2] error flag raised by kernels (bad gate code), [4] / [5] the same two
@@ -789,8 +789,11 @@ int build_ksk_planes(tfhe_hip_ctx *ctx) {
   return TFHE_HIP_OK;
 }
 
+int claim_scratch(tfhe_hip_ctx *ctx, hipStream_t s);
+
 int launch_key_switch(tfhe_hip_ctx *ctx, hipStream_t s, const uint32_t *lv1, uint32_t *out, size_t count) {
   if (count == 0) return TFHE_HIP_OK;
+  CHK(claim_scratch(ctx, s));  // ks_out and ks_dig are taken here, where they are used: no caller can forget it
   const tfhe_hip_params &P = ctx->P;
   const int n = P.n;
   const KsPlan pl = plan_key_switch(ctx, count);
@@ -890,9 +893,10 @@ int need_reenc_key(tfhe_hip_ctx *ctx) {
 
 hipStream_t pick(tfhe_hip_ctx *ctx, void *stream) { return stream ? (hipStream_t)stream : ctx->stream; }
 
-// The intermediate buffers (lv1, u1, u2) belong to the context, not to a call.  Work queued on one
-// stream may still be using them when the next call arrives on another stream: drain the previous
-// owner first (same-stream calls are ordered by the stream itself and pay nothing).
+// The intermediate buffers (lv1, u1, u2, the key switch's ks_out and ks_dig, the tree bootstrap's biv_s1 and
+// biv_tv) belong to the context, not to a call.  Work queued on one stream may still be using them when the
+// next call arrives on another stream: drain the previous owner first (same-stream calls are ordered by the
+// stream itself and pay nothing).  launch_key_switch claims for itself; its callers' own claims cover lv1 / u1 / u2.
 int claim_scratch(tfhe_hip_ctx *ctx, hipStream_t s) {
   if (ctx->scratch_owned && ctx->scratch_owner != s) HIPCHK(ctx, hipStreamSynchronize(ctx->scratch_owner));
   ctx->scratch_owner = s;
