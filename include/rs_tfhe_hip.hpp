@@ -144,13 +144,18 @@ struct CompressedCloudKey {
 };
 
 // The packing key of include/tfhe_hip.h ("packing key switch"): the public mask seed plus the bodies [n][t][N]; the
-// device regenerates the masks on load.  Made by the client (rs-tfhe_amd/packing.py: make_packing_key).
+// device regenerates the masks on load.  Made by the client: PackingKey::generate below (tfhe_hip_gen_packing_key, on the
+// GPU), or rs-tfhe_amd/packing.py: make_packing_key on the host.
+struct SecretKey;
 struct PackingKey {
   SecurityParams params = DEFAULT_SECURITY;
   std::array<uint8_t, 32> mask_seed{};
   std::vector<Torus> bodies;  // [n][t][N]
   size_t nbytes() const { return bodies.size() * sizeof(Torus) + mask_seed.size(); }
   bool matches(const SecurityParams &p) const { return params == p && bodies.size() == (size_t)p.n * p.iks_t * N; }
+  // The packing key of `sk`, generated on the GPU (tfhe_hip_gen_packing_key) in a key view that is dropped afterwards.
+  // rng_key: the 32-byte generator key K, or nullptr to draw it from getrandom(2); alpha < 0: the set's alpha_lv1.
+  static PackingKey generate(const SecretKey &sk, int device = 0, const uint8_t *rng_key = nullptr, double alpha = -1);
 };
 
 // ---- engine handle: ONE C-ABI context per (parameter set, device); every cloud key is a key view of it ------
@@ -564,6 +569,21 @@ struct SecretKey {
     return compressed_cloud_key(rng, device);
   }
 };
+
+inline PackingKey PackingKey::generate(const SecretKey &sk, int device, const uint8_t *rng_key, double alpha) {
+  const SecurityParams &p = sk.params;
+  Engine &e = Engine::for_params(p, device);
+  PackingKey pk;
+  pk.params = p;
+  pk.bodies.resize((size_t)p.n * p.iks_t * N);
+  tfhe_hip_ctx *view = nullptr;
+  e.check(tfhe_hip_key_create(e.ctx(), &view));
+  std::unique_ptr<tfhe_hip_ctx, void (*)(tfhe_hip_ctx *)> h(view, tfhe_hip_ctx_destroy);  // dropped on every exit
+  const int rc = tfhe_hip_gen_packing_key(view, sk.key_lv0.data(), sk.key_lv1.data(), alpha < 0 ? p.alpha_lv1 : alpha, rng_key,
+                                          pk.mask_seed.data(), pk.bodies.data());
+  if (rc != TFHE_HIP_OK) throw std::runtime_error(std::string("tfhe_hip: ") + tfhe_hip_last_error(view));
+  return pk;
+}
 
 namespace tlwe {
 inline Torus inner_product(const Ciphertext &c, const std::vector<Torus> &key) {

@@ -277,11 +277,37 @@ int tfhe_hip_expand_seeded_tlwe_dev(tfhe_hip_ctx *ctx, const uint8_t mask_seed[3
  * Semantics.  The packing key lives beside the cloud key of a context or key view: loading, generating or adopting a
  * cloud key (or loading a re-encryption key) leaves it, packing needs no cloud key, destroying a view frees its key.
  * Packing without one: TFHE_HIP_ENOKEY.  Packing calls are bulk calls (the context's mutex, never the combining
- * front end).  _dev: device pointers, queued on `stream` (NULL: the context's stream). */
+ * front end).  _dev: device pointers, queued on `stream` (NULL: the context's stream).
+ *
+ * Generation (normative).  tfhe_hip_gen_packing_key makes the key above on the device from the secret key and a
+ * 32-byte generator key K (secret; generation only), so the whole key is a function of (s0, s1, K, alpha):
+ *   Mask seed   S = words 0..7 of block(K, counter 0, nonce (0, 26, 0x444553)), a PRF output that reveals nothing of K.
+ *               Stream 26 is not the compressed cloud key's stream 20 ON PURPOSE: one K gives two different public
+ *               seeds.
+ *   Noise       e_r under K, nonce (r, 25, 0x504B53), in the BSK generators' word order: block 2*lane + h (lane < 64,
+ *               h < 2) holds four pairs; pair m < 4 is Box-Muller over words 4m..4m+3 of the block (the gauss2 of the
+ *               seeded section's noise); its first sample is e[lane + 64(4h + m)], its second the same + 512;
+ *               e = f64_to_torus(sample).
+ *   Product     a_r (*) s1 is exact: the mask read as int32, s1 binary, N = 1024 terms, |coefficient| < 2^41.  The
+ *               gadget s0[i]*g_l is added to coefficient 0 after the product, wrapping mod 2^32.
+ *   Sharing K   One K may be given to this call, to tfhe_hip_gen_compressed_cloud_key and to
+ *               tfhe_hip_gen_cloud_key_with_key: every noise stream differs (1, 3, 17, 19, 25), so no two published
+ *               rows share a noise sample.
+ * Away from samples that sit within rounding of a torus step (where two correct f64 libms may truncate to neighbouring
+ * words) every implementation of this section gives the same bodies. */
 /* Word count of `bodies` for `params`.  Initialises no device. */
 int tfhe_hip_packing_key_words(const tfhe_hip_params *params, size_t *body_words);
 /* Uploads the bodies and expands the key on the device (masks from S, then the kernel's byte planes). */
 int tfhe_hip_load_packing_key(tfhe_hip_ctx *ctx, const uint8_t mask_seed[32], const uint32_t *bodies);
+/* The packing key of the secret key (key_lv0 [n], key_lv1 [N], as tfhe_hip_gen_cloud_key_with_key takes them), made on
+ * the device.  A CLIENT-side call, like tfhe_hip_gen_cloud_key*: it takes the secret key.  Writes S to mask_seed and,
+ * unless `bodies` is NULL, the bodies [n][t][N]; the handle (context or key view) is left holding the key -- bit for
+ * bit the one tfhe_hip_load_packing_key(mask_seed, bodies) builds from the outputs.  alpha: the noise's standard
+ * deviation (alpha_lv1 of the set is the usual choice).  rng_key: K from the caller's CSPRNG, or NULL to draw it from
+ * getrandom(2).  Needs no cloud key and leaves a loaded one alone.  TFHE_HIP_EINVAL (the previous packing key stays
+ * loaded) for a NULL secret key or mask_seed, basebit > 7, alpha negative or NaN. */
+int tfhe_hip_gen_packing_key(tfhe_hip_ctx *ctx, const uint32_t *key_lv0, const uint32_t *key_lv1, double alpha,
+                             const uint8_t rng_key[32], uint8_t mask_seed[32], uint32_t *bodies);
 /* 0 / 1, never an error code (no device call is made). */
 int tfhe_hip_packing_key_is_loaded(tfhe_hip_ctx *ctx);
 /* in [count][n+1] lv0 ciphertexts -> out [ceil(count / N)][2][N]. */
@@ -698,6 +724,10 @@ int tfhe_hip_pool_export_cloud_key(tfhe_hip_pool *pool, int member, double *bsk,
 /* Packing key switch on a pool: every member loads the packing key; a batch is split in whole groups of N over the
  * members, in input order (the _dev form through the grouped scatter / gather, a last partial group on home). */
 int tfhe_hip_pool_load_packing_key(tfhe_hip_pool *pool, const uint8_t mask_seed[32], const uint32_t *bodies);
+/* tfhe_hip_gen_packing_key on the first member; every other member loads the same (mask_seed, bodies) -- from a host
+ * buffer of the call's own when `bodies` is NULL.  Takes a pool or a pool key view. */
+int tfhe_hip_pool_gen_packing_key(tfhe_hip_pool *pool, const uint32_t *key_lv0, const uint32_t *key_lv1, double alpha,
+                                  const uint8_t rng_key[32], uint8_t mask_seed[32], uint32_t *bodies);
 int tfhe_hip_pool_batch_pack_tlwe(tfhe_hip_pool *pool, const uint32_t *in, size_t count, uint32_t *out);
 int tfhe_hip_pool_batch_pack_tlwe_dev(tfhe_hip_pool *pool, int home_member, const uint32_t *in, size_t count,
                                       uint32_t *out, void *stream);

@@ -96,6 +96,7 @@ SIGNATURES = {
     "tfhe_hip_expand_seeded_tlwe_dev": (C.c_int, [_CTX, _P, C.c_uint64, _P, _SZ, _P, _P]),
     "tfhe_hip_packing_key_words": (C.c_int, [C.POINTER(Params), C.POINTER(_SZ)]),
     "tfhe_hip_load_packing_key": (C.c_int, [_CTX, _P, _P]),
+    "tfhe_hip_gen_packing_key": (C.c_int, [_CTX, _P, _P, C.c_double, _P, _P, _P]),
     "tfhe_hip_packing_key_is_loaded": (C.c_int, [_CTX]),
     "tfhe_hip_batch_pack_tlwe": (C.c_int, [_CTX, _P, _SZ, _P]),
     "tfhe_hip_batch_pack_tlwe_dev": (C.c_int, [_CTX, _P, _SZ, _P, _P]),
@@ -162,6 +163,7 @@ SIGNATURES = {
     "tfhe_hip_pool_gen_cloud_key": (C.c_int, [_CTX, _P, _P, C.c_double, C.c_double, C.c_uint64]),
     "tfhe_hip_pool_export_cloud_key": (C.c_int, [_CTX, C.c_int, _P, _P, C.POINTER(C.c_uint32), _P]),
     "tfhe_hip_pool_load_packing_key": (C.c_int, [_CTX, _P, _P]),
+    "tfhe_hip_pool_gen_packing_key": (C.c_int, [_CTX, _P, _P, C.c_double, _P, _P, _P]),
     "tfhe_hip_pool_batch_pack_tlwe": (C.c_int, [_CTX, _P, _SZ, _P]),
     "tfhe_hip_pool_batch_pack_tlwe_dev": (C.c_int, [_CTX, C.c_int, _P, _SZ, _P, _P]),
     "tfhe_hip_pool_batch_unpack_trlwe": (C.c_int, [_CTX, _P, _SZ, _P, _SZ, _P]),

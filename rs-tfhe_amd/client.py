@@ -137,12 +137,25 @@ class SecretKey:
         return (torus_to_f64(self.phase(cts)) / scale + 0.5).astype(np.int64) % m
 
     # ---- packed results (packing key switch, include/tfhe_hip.h) ------------------------------------
-    def packing_key(self, rng_key=None, alpha=None):
-        """The packing key (packing.PackingKey: mask seed + bodies) under s1 for bits of s0, made on the CPU.  rng_key:
-        None draws from the OS CSPRNG; an int seed is reproducible (tests only).  alpha: alpha_lv1 by default."""
-        from .packing import make_packing_key
+    def packing_key(self, rng_key=None, alpha=None, device: int = None):
+        """The packing key (packing.PackingKey: mask seed + bodies) under s1 for bits of s0.  device=None makes it on
+        the CPU; device=d runs `tfhe_hip_gen_packing_key` there, in a key view it closes after.  rng_key: None draws from
+        the OS CSPRNG; 32 bytes are the generator key K of include/tfhe_hip.h (CPU and GPU give the same mask seed and,
+        away from borderline samples, the same bodies); an int seed is reproducible (tests only, CPU only).  alpha:
+        alpha_lv1 by default."""
+        if device is None:
+            from .packing import make_packing_key
 
-        return make_packing_key(self.params, self.key_lv0, self.key_lv1, rng=rng_key, alpha=alpha)
+            return make_packing_key(self.params, self.key_lv0, self.key_lv1, rng=rng_key, alpha=alpha)
+        if rng_key is not None and not isinstance(rng_key, (bytes, bytearray)):
+            raise ValueError("on a device rng_key is the 32-byte generator key (or None): a seed selects the CPU generator")
+        from .bootstrap import engine_for
+
+        view = engine_for(self.params, device).new_key_view()
+        try:
+            return view.gen_packing_key(self.key_lv0, self.key_lv1, rng_key=rng_key, alpha=alpha)
+        finally:
+            view.close()
 
     def packed_phase(self, packed, count: int) -> np.ndarray:
         """Phases of the first `count` results of [G][2][N] packed TRLWEs: coefficient j of B - A (*) s1 per group."""

@@ -15,7 +15,8 @@
 //  - the pool's broadcast replication splits begin (prepare_replica) and commit (finish_replica) around the
 //    broadcast, which runs outside the member's call, and synchronises the whole device before the commit;
 //  - the packing key (packing.hpp) has its own flag and planes, which are not the key switch's: it drains with a
-//    device-wide synchronisation, is left alone by a cloud-key change, and takes only upload_through_temp from here.
+//    device-wide synchronisation, is left alone by a cloud-key change, and takes only upload_through_temp from here
+//    (its generation, packing_keygen.hpp, also the staged secrets below).
 // ctx->mu is held and ctx's device is current in everything below.
 #pragma once
 

@@ -162,7 +162,8 @@ struct KeyState {
   bool pk_loaded = false;          // (a cloud-key load or change leaves it; freeing the key view frees it)
   uint32_t offset = 0;
   // The flags are written in key_change.hpp only: begin_key_change clears both, commit_cloud_key sets key_loaded (and
-  // clears reenc_loaded), commit_reenc_key sets reenc_loaded.  pk_loaded is tfhe_hip_load_packing_key's alone.
+  // clears reenc_loaded), commit_reenc_key sets reenc_loaded.  pk_loaded is tfhe_hip_load_packing_key's and
+  // tfhe_hip_gen_packing_key's alone.
   bool key_loaded = false;
   bool reenc_loaded = false;  // d_ksk (+ d_ksk8) hold a proxy re-encryption key (proxy_reenc.rs:224-233) instead of a cloud key's
 };
@@ -2275,3 +2276,4 @@ int tfhe_hip_synchronize(tfhe_hip_ctx *ctx) {
 #include "packing.hpp"
 #include "unpack.hpp"
 #include "table.hpp"
+#include "packing_keygen.hpp"

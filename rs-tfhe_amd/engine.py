@@ -305,6 +305,29 @@ class _Handle:
         self._call("load_packing_key", C.addressof(seed), _ptr(bodies))
         self._packing_key = packing_key
 
+    def gen_packing_key(self, key_lv0, key_lv1, rng_key: bytes = None, alpha=None, download: bool = True):
+        """The packing key of the secret key, generated on the GPU (`tfhe_hip_gen_packing_key`; a pool's first member,
+        whose bodies every other member loads) and left loaded on this handle.  rng_key: the 32-byte generator key K,
+        None draws it from getrandom(2); alpha: alpha_lv1 of the set by default.  Returns the packing.PackingKey, or
+        None with download=False (the bodies stay on the GPU)."""
+        from .packing import PackingKey
+
+        p = self.params
+        k0, k1 = _u32(key_lv0).reshape(-1), _u32(key_lv1).reshape(-1)
+        if len(k0) != p.n or len(k1) != N:
+            raise ValueError("secret key has the wrong size for these parameters")
+        rk = None
+        if rng_key is not None:
+            if len(rng_key) != 32:
+                raise ValueError("rng_key is 32 bytes")
+            rk = (C.c_uint8 * 32).from_buffer_copy(bytes(rng_key))
+        seed = (C.c_uint8 * 32)()
+        bodies = np.empty((p.n, p.iks_t, N), np.uint32) if download else None
+        self._call("gen_packing_key", _ptr(k0), _ptr(k1), C.c_double(p.alpha_lv1 if alpha is None else alpha),
+                   C.addressof(rk) if rk is not None else None, C.addressof(seed), _ptr(bodies))
+        self._packing_key = PackingKey(p, bytes(seed), bodies) if download else ("generated", object())
+        return self._packing_key if download else None
+
     def packing_key_is_loaded(self) -> bool:
         return self._lib.tfhe_hip_packing_key_is_loaded(self._member_ctx(0)) == 1  # 0 / 1; anything else is not "loaded"
 

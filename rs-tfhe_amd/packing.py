@@ -3,7 +3,8 @@
 The format and the result are normative in include/tfhe_hip.h ("packing key switch"): up to N = 1024 TLWE lv0 results
 become ONE TRLWE lv1 under s1, each coefficient carrying the phase of one input, so results return 350x smaller on
 SECURITY_128_BIT.  This module is the client's side -- the packing key (`make_packing_key`: masks from the seeded
-section's ChaCha20 keystream, bodies by exact negacyclic products with the binary s1) -- and the integer model of the
+section's ChaCha20 keystream, bodies by exact negacyclic products with the binary s1; given a 32-byte generator key it
+is the CPU form of `tfhe_hip_gen_packing_key`, which `Engine.gen_packing_key` runs on the GPU) -- and the integer model of the
 server's result (`pack_model`), which the GPU (csrc/packing.hpp, `Engine.pack`) equals word for word.  `pack` runs it
 on the key view of a cloud key.
 
@@ -19,10 +20,12 @@ from __future__ import annotations
 import numpy as np
 
 from .params import N, SecurityParams
-from .seeded import f64_to_torus, keystream, negacyclic_binary
+from .seeded import DOMAIN_SEED, chacha20_block, f64_to_torus, gauss2, keystream, negacyclic_binary
 
 DOMAIN_PACK = 0x504B53
-PACK_STREAM = 24
+PACK_STREAM = 24  # masks, under the mask seed
+PACK_NOISE_STREAM = 25  # noise, under the generator key
+PACK_SEED_STREAM = 26  # the mask seed from the generator key (domain "DES"; the compressed cloud key's is 20)
 
 
 def gadget(p: SecurityParams) -> np.ndarray:
@@ -60,6 +63,21 @@ def key_rows(p: SecurityParams, mask_seed: bytes, bodies) -> np.ndarray:
         out[lo:hi, :N] = key_masks(mask_seed, np.arange(lo, hi))
     out[:, N:] = np.asarray(bodies, np.uint32).reshape(rows, N)
     return out
+
+
+def mask_seed_of(rng_key: bytes) -> bytes:
+    """S = words 0..7 of block(K, 0, nonce (0, 26, "DES")): the packing key's public mask seed under generator key K."""
+    return chacha20_block(rng_key, 0, 0, PACK_SEED_STREAM, DOMAIN_SEED)[:8].astype("<u4").tobytes()
+
+
+def key_noise(rng_key: bytes, rows, alpha: float) -> np.ndarray:
+    """Noise polynomials e_r of the rows `rows` under generator key K, [len(rows), N] u32: blocks 2 lane + h of
+    (r, 25, "PKS"), pair m < 4 of a block gives e[lane + 64 (4h + m)] and the same + 512 (the BSK generators' order)."""
+    r = np.asarray(rows, np.uint64)
+    w = chacha20_block(rng_key, np.arange(128, dtype=np.uint64), r[:, None], PACK_NOISE_STREAM, DOMAIN_PACK)
+    g0, g1 = gauss2(w.reshape(len(r), 64, 2, 4, 4), alpha)  # [rows, lane, h, m]
+    return np.concatenate([f64_to_torus(g).reshape(len(r), 64, 8).transpose(0, 2, 1).reshape(len(r), N // 2)
+                           for g in (g0, g1)], axis=1)
 
 
 class PackingKey:
@@ -106,24 +124,33 @@ class PackingKey:
 
 
 def make_packing_key(params: SecurityParams, key_lv0, key_lv1, rng=None, alpha=None, chunk: int = 512) -> PackingKey:
-    """The packing key of (key_lv0, key_lv1): b_r = a_r (*) s1 + e_r + s0[i] g_l X^0.  rng: None (the OS CSPRNG), an
-    int seed or a numpy Generator (reproducible: tests only); it draws the mask seed and the noise.  alpha: the noise's
-    standard deviation, alpha_lv1 of the set by default."""
+    """The packing key of (key_lv0, key_lv1): b_r = a_r (*) s1 + e_r + s0[i] g_l X^0.  rng: 32 bytes are the generator
+    key K of include/tfhe_hip.h ("Generation"): the mask seed and every noise sample are keystream positions under K,
+    as `tfhe_hip_gen_packing_key` makes them on the GPU (the same seed and, away from borderline samples, the same
+    bodies).  Otherwise None (the OS CSPRNG), an int seed or a numpy Generator (reproducible: tests only) draws the
+    mask seed and the noise.  alpha: the noise's standard deviation, alpha_lv1 of the set by default."""
     from .client import OsRng, _rng
 
     p = params
     if p.basebit > 7:
         raise ValueError("packing needs basebit <= 7")
     alpha = p.alpha_lv1 if alpha is None else float(alpha)
-    if alpha < 0:
+    if not alpha >= 0:
         raise ValueError("alpha is non-negative")
-    g = _rng(rng)
-    if isinstance(g, OsRng):
-        import os
-
-        seed = os.urandom(32)
+    rng_key = None
+    if isinstance(rng, (bytes, bytearray)):
+        rng_key = bytes(rng)
+        if len(rng_key) != 32:
+            raise ValueError("rng_key is 32 bytes")
+        seed = mask_seed_of(rng_key)
     else:
-        seed = g.integers(0, 1 << 32, 8, dtype=np.uint64).astype("<u4").tobytes()
+        g = _rng(rng)
+        if isinstance(g, OsRng):
+            import os
+
+            seed = os.urandom(32)
+        else:
+            seed = g.integers(0, 1 << 32, 8, dtype=np.uint64).astype("<u4").tobytes()
     s0 = np.asarray(key_lv0, np.uint32).reshape(p.n)
     s1 = np.asarray(key_lv1, np.uint32).reshape(N)
     gl = gadget(p)
@@ -133,7 +160,9 @@ def make_packing_key(params: SecurityParams, key_lv0, key_lv1, rng=None, alpha=N
         for lo in range(0, rows, chunk):
             r = np.arange(lo, min(lo + chunk, rows))
             b = negacyclic_binary(key_masks(seed, r), s1)
-            if alpha > 0:
+            if rng_key is not None:
+                b += key_noise(rng_key, r, alpha)
+            elif alpha > 0:
                 b += f64_to_torus(g.normal(0.0, alpha, len(r) * N)).reshape(len(r), N)
             b[:, 0] += s0[r // p.iks_t] * gl[r % p.iks_t]
             bodies[lo:lo + len(r)] = b

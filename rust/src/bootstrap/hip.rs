@@ -88,6 +88,9 @@ pub const ORNY: c_int = 8; pub const ORYN: c_int = 9; pub const COPY: c_int = 10
 
 extern "C" {   // packing key switch (include/tfhe_hip.h): up to N lv0 results in one TRLWE lv1 under the client's s1
     fn tfhe_hip_pool_load_packing_key(pool: *mut TfheHipPool, mask_seed: *const u8, bodies: *const u32) -> c_int;
+    // the packing key generated on the first member's GPU (a client-side call: it takes the secret key); bodies may be null
+    fn tfhe_hip_pool_gen_packing_key(pool: *mut TfheHipPool, key_lv0: *const u32, key_lv1: *const u32, alpha: f64,
+                                     rng_key: *const u8, mask_seed: *mut u8, bodies: *mut u32) -> c_int;
     fn tfhe_hip_pool_batch_pack_tlwe(pool: *mut TfheHipPool, input: *const u32, count: usize, out: *mut u32) -> c_int;
     // unpacking key switch: slots of TRLWE lv1 ciphertexts back to lv0 ciphertexts under the cloud key's key-switching key
     fn tfhe_hip_pool_batch_unpack_trlwe(pool: *mut TfheHipPool, trlwe: *const u32, groups: usize, slots: *const u32,
@@ -416,6 +419,32 @@ impl HipEngine {
             Self::check(g.view, unsafe { tfhe_hip_pool_load_packing_key(g.view, mask_seed.as_ptr(), bodies.as_ptr()) });
             g.fp = fp;
         }
+    }
+
+    /// The packing key of the secret key (key_lv0 [n], key_lv1 [N]), generated on the GPU (`tfhe_hip_pool_gen_packing_key`,
+    /// the format of include/tfhe_hip.h): returns (the public mask seed, the bodies [n][t][N]).  A client-side call, as the
+    /// cloud-key generation is.  `alpha`: the noise's standard deviation (params::trgsw_lv1::ALPHA is the set's);
+    /// `rng_key`: the 32-byte generator key from the caller's CSPRNG, None draws it from getrandom(2).  The packing key's
+    /// view is left loaded with the key and its content sample set: `pack_tlwe` with the returned pair uploads nothing.
+    pub fn gen_packing_key(&self, key_lv0: &[u32], key_lv1: &[u32], alpha: f64, rng_key: Option<&[u8; 32]>) -> ([u8; 32], Vec<u32>) {
+        let n = params::tlwe_lv0::N;
+        assert_eq!(key_lv0.len(), n, "key_lv0 is [n]");
+        assert_eq!(key_lv1.len(), N, "key_lv1 is [N]");
+        let mut seed = [0u8; 32];
+        let mut bodies = vec![0u32; n * params::trgsw_lv1::IKS_T * N];
+        let mut g = self.packing.lock().unwrap();   // held through the call: a concurrent pack cannot meet half a key
+        if g.view.is_null() {
+            let mut view = std::ptr::null_mut();
+            assert_eq!(unsafe { tfhe_hip_pool_key_create(self.pool, &mut view) }, 0, "tfhe_hip_pool_key_create failed");
+            g.view = view;
+        }
+        g.fp = !g.fp;   // a failed call leaves the key it replaces unclaimed (the next pack_tlwe loads again)
+        let rk = rng_key.map_or(std::ptr::null(), |k| k.as_ptr());
+        Self::check(g.view, unsafe {
+            tfhe_hip_pool_gen_packing_key(g.view, key_lv0.as_ptr(), key_lv1.as_ptr(), alpha, rk, seed.as_mut_ptr(), bodies.as_mut_ptr())
+        });
+        g.fp = Self::packing_fingerprint(&seed, &bodies);
+        (seed, bodies)
     }
 
     /// Encrypted-table key switch, the definition of include/tfhe_hip.h: `stage1` ([m][count][n+1] lv0 ciphertexts, flat,
