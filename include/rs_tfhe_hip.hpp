@@ -1121,6 +1121,47 @@ struct PublicKeyLv0 {  // proxy_reenc.rs:95-99
     return r;
   }
   Ciphertext encrypt_bool(bool b, double alpha, ChaChaRng &rng) const { return encrypt_f64(b ? 0.125 : -0.125, alpha, rng); }  // :212-215
+
+  // ---- the keyed format of include/tfhe_hip.h ("public-key encryption ..."), on the GPU ------------------------
+  std::vector<Torus> flat() const {  // [size][n+1]
+    const size_t w = (size_t)params.n + 1;
+    std::vector<Torus> f(encryptions.size() * w);
+    for (size_t i = 0; i < encryptions.size(); ++i) std::memcpy(&f[i * w], encryptions[i].p.data(), w * sizeof(Torus));
+    return f;
+  }
+  // this key's byte planes onto `handle` (the engine's context or one of its key views): tfhe_hip_load_public_key
+  void load(const Engine &e, tfhe_hip_ctx *handle) const {
+    const std::vector<Torus> f = flat();
+    if (tfhe_hip_load_public_key(handle, f.data(), encryptions.size()) != TFHE_HIP_OK)
+      throw std::runtime_error(std::string("tfhe_hip: ") + tfhe_hip_last_error(e.ctx()));
+  }
+  // encrypt_f64 over a batch (tfhe_hip_batch_pk_encrypt): ciphertext m is row first_index + m of the generator key's
+  // streams.  rng_key: the 32-byte generator key, or nullptr to draw it from getrandom(2).  A (rng_key, row) pair must
+  // never encrypt two messages.  The key is loaded into a key view that is dropped afterwards; to keep it resident
+  // over many calls, `load` it onto a handle once and call the C entry point.
+  std::vector<Ciphertext> encrypt_batch(Engine &e, const std::vector<double> &plaintexts, double alpha,
+                                        const uint8_t *rng_key = nullptr, uint64_t first_index = 0) const {
+    std::vector<Torus> plain(plaintexts.size());
+    for (size_t m = 0; m < plain.size(); ++m) plain[m] = f64_to_torus(plaintexts[m]);
+    const size_t w = (size_t)params.n + 1;
+    std::vector<Torus> out(plain.size() * w);
+    tfhe_hip_ctx *view = nullptr;
+    e.check(tfhe_hip_key_create(e.ctx(), &view));
+    std::string msg;
+    try {
+      load(e, view);
+      if (tfhe_hip_batch_pk_encrypt(view, plain.data(), plain.size(), alpha, rng_key, first_index, out.data()) != TFHE_HIP_OK)
+        msg = tfhe_hip_last_error(e.ctx());
+    } catch (...) {
+      tfhe_hip_ctx_destroy(view);
+      throw;
+    }
+    tfhe_hip_ctx_destroy(view);
+    if (!msg.empty()) throw std::runtime_error("tfhe_hip: " + msg);
+    std::vector<Ciphertext> res(plain.size(), Ciphertext(params.n));
+    for (size_t m = 0; m < res.size(); ++m) std::memcpy(res[m].p.data(), &out[m * w], w * sizeof(Torus));
+    return res;
+  }
 };
 
 class ProxyReencryptionKey {  // proxy_reenc.rs:224-233
@@ -1146,6 +1187,25 @@ class ProxyReencryptionKey {  // proxy_reenc.rs:224-233
   static ProxyReencryptionKey new_asymmetric(const std::vector<Torus> &key_from, const PublicKeyLv0 &public_key_to, ChaChaRng &rng) {  // :271-279
     const SecurityParams &p = public_key_to.params;
     return new_asymmetric_with_params(key_from, public_key_to, p.alpha_lv0, p.basebit, p.iks_t, rng);
+  }
+
+  // new_asymmetric in the keyed format of include/tfhe_hip.h, generated on the GPU (tfhe_hip_gen_reenc_key_asymmetric) in
+  // a key view of `e` that the returned key keeps: reencrypt uploads nothing.  basebit and t are the engine's (for a
+  // custom pair take the engine of the set with that basebit / iks_t); alpha < 0: the set's alpha_lv0; rng_key: the
+  // 32-byte generator key, or nullptr to draw it from getrandom(2); download = false leaves key_encryptions empty.
+  static ProxyReencryptionKey generate_asymmetric(Engine &e, const std::vector<Torus> &key_from, const PublicKeyLv0 &public_key_to,
+                                                  const uint8_t *rng_key = nullptr, double alpha = -1, bool download = true) {
+    const SecurityParams &p = e.params();
+    if (public_key_to.params.n != p.n || key_from.size() != (size_t)p.n)
+      throw std::runtime_error("source key or public key has another dimension than the engine's parameter set");
+    ProxyReencryptionKey k;
+    k.params = p;
+    if (download) k.key_encryptions.resize((size_t)p.n * p.iks_t * p.base() * ((size_t)p.n + 1));
+    e.check(tfhe_hip_key_create(e.ctx(), &k.view_));  // (dropped by k's destructor on every path)
+    public_key_to.load(e, k.view_);
+    e.check(tfhe_hip_gen_reenc_key_asymmetric(k.view_, key_from.data(), alpha < 0 ? p.alpha_lv0 : alpha, rng_key,
+                                              download ? k.key_encryptions.data() : nullptr));
+    return k;
   }
 
   ProxyReencryptionKey() = default;

@@ -558,6 +558,70 @@ int tfhe_hip_reenc_key_is_loaded(tfhe_hip_ctx *ctx);
 int tfhe_hip_batch_reencrypt(tfhe_hip_ctx *ctx, const uint32_t *in, uint32_t *out, size_t count);
 int tfhe_hip_batch_reencrypt_dev(tfhe_hip_ctx *ctx, const uint32_t *in, uint32_t *out, size_t count, void *stream);
 
+/* ---- public-key encryption and the asymmetric re-encryption key ------------------------------------------------
+ *
+ * What happens BEFORE the proxy: a data owner who holds only a public key encrypts (PublicKeyLv0::encrypt_f64,
+ * src/proxy_reenc.rs:168-200), and a delegator makes the re-encryption key towards a delegatee's public key
+ * (ProxyReencryptionKey::new_asymmetric, :271-326, the mode the reference recommends).  Both are one exact integer
+ * contraction out[r] = sum_e c[r][e] * E[e], c in {-1, 0, +1}, over the public key E [size][n+1] (encryptions of zero
+ * under the secret key, :95-99), and run on the matrix cores the way the packing key switch does: E is split once, at
+ * load, into four balanced signed byte planes; |acc| <= 128 * size <= 2^20, so the sum is equal word for word.
+ *
+ * Format (normative).  Keystream words are block(K, counter, nonce (n0, n1, n2)) of the seeded section, under a SECRET
+ * 32-byte generator key K.  A row index g is 64 bits; its nonce is (g & 0xffffffff, g >> 32, domain):
+ *
+ *   what                                    domain               counter   use
+ *   public-key encryption selectors         0x504B45 ("PKE")     w / 16    selector word w of row g is word w % 16
+ *   public-key encryption noise             0x504B4E ("PKN")     0         g0 of gauss2(words 0..3, alpha); rest unused
+ *   re-encryption key selectors / noise     0x524B45 ("RKE") /   as above  row g = base*t*i + base*j + k, k >= 1
+ *                                           0x524B4E ("RKN")
+ *
+ *   Entry e < size of row g reads bits 2*(e % 16) (take) and 2*(e % 16) + 1 (sign, 1 = subtract) of selector word e / 16:
+ *   c_e = take ? (sign ? -1 : +1) : 0 -- the reference's two gen_bool(0.5) draws.
+ *   out[g] = sum_e c_e * E[e] on all n + 1 words, wrapping u32; the body then gets + plain + f64_to_torus(g0), gauss2
+ *   and f64_to_torus those of the seeded section.  With alpha == 0 the noise is exactly zero.
+ *   Re-encryption key: plain = f64_to_torus(((k * key_from[i]) as u32 as f64) / 2^((j+1)*basebit)); the k = 0 rows are
+ *   zero and their streams are unused.
+ *   The domains differ from every other one of this header (KSK, BSK, EWL, DES, PKS), so one K may serve all generators.
+ * Security.  (1) A (K, g) pair must never encrypt two messages: the difference of the two ciphertexts would be the
+ * difference of the plaintexts in the clear.  With a caller-held K, first_index must move past every row already used.
+ * (2) Whoever knows K can strip the mask: the selectors are a function of (K, g) and E is public.  Hence rng_key == NULL
+ * means "draw K from getrandom(2) for this call", and a caller-held K is as secret as the plaintexts.  The library
+ * zeroes the selectors on the device behind each pass; K travels to the kernels as a launch argument.
+ * Away from noise samples that sit within rounding of a torus step every implementation of this section gives the same
+ * words.
+ * Out of scope: pool forms; generating the public key itself on the device (2n ordinary encryptions); the symmetric
+ * re-encryption key (n*t*(base-1) ordinary encryptions, no contraction). */
+/* encryptions [size][n+1], 1 <= size <= 8192 (TFHE_HIP_EINVAL otherwise, and the previous public key stays).  Builds
+ * the byte planes on the device, on a context or a key view; needs no cloud key; a cloud-key or re-encryption-key
+ * change leaves it in place; freeing the view frees it. */
+int tfhe_hip_load_public_key(tfhe_hip_ctx *ctx_or_view, const uint32_t *encryptions, size_t size);
+/* 0 / 1, never an error code (no device call is made). */
+int tfhe_hip_public_key_is_loaded(tfhe_hip_ctx *ctx_or_view);
+/* plain [count] torus words (f64_to_torus of the messages) -> out [count][n+1]; row m uses g = first_index + m.
+ * alpha: the fresh noise's standard deviation.  TFHE_HIP_ENOKEY without a public key.  The host form stages through the
+ * context's buffers; _dev takes device pointers and a hipStream_t (NULL = the context's) and only enqueues. */
+int tfhe_hip_batch_pk_encrypt(tfhe_hip_ctx *ctx, const uint32_t *plain, size_t count, double alpha,
+                              const uint8_t rng_key[32], uint64_t first_index, uint32_t *out);
+int tfhe_hip_batch_pk_encrypt_dev(tfhe_hip_ctx *ctx, const uint32_t *plain, size_t count, double alpha,
+                                  const uint8_t rng_key[32], uint64_t first_index, uint32_t *out, void *stream);
+/* The asymmetric re-encryption key from key_from [n] (the delegator's secret key: a CLIENT-side call) towards the public
+ * key loaded on this handle, with basebit and t of the context's parameter set.  The handle is left holding it -- bit
+ * for bit what tfhe_hip_load_reenc_key(key_out) builds; key_out [n][t][base][n+1] may be NULL (no download).
+ * TFHE_HIP_ENOKEY without a public key; TFHE_HIP_EINVAL for n > 1024, a NULL key_from, alpha negative or NaN.  A refused
+ * call leaves the handle's keys as they were. */
+int tfhe_hip_gen_reenc_key_asymmetric(tfhe_hip_ctx *ctx_or_view, const uint32_t *key_from, double alpha,
+                                      const uint8_t rng_key[32], uint32_t *key_out);
+/* While profiling is enabled (tfhe_hip_set_profiling) the two kernels of every pass of the calls above -- the keystream
+ * pass that writes the selectors, and the contraction -- are bracketed by HIP events on the stream they run on.
+ * Synchronises the recorded events, returns the sums since the last call and resets them. */
+typedef struct tfhe_hip_pk_encrypt_times {
+  double selectors_ms;   /* sum of the keystream (selector) kernel durations */
+  double contraction_ms; /* sum of the matrix-core kernel durations          */
+  uint64_t passes;       /* launches of each (one per 65,536 rows)           */
+} tfhe_hip_pk_encrypt_times;
+int tfhe_hip_get_pk_encrypt_times(tfhe_hip_ctx *ctx, tfhe_hip_pk_encrypt_times *out);
+
 /* Replaces: FFTProcessor::{ifft, fft, poly_mul, batch_ifft, batch_fft}
  * (src/fft/mod.rs:80-107; KlemsaProcessor src/fft/klemsa.rs:88-174) and the
  * SPQLIOS C ABI Spqlios_ifft_lv1 / _fft_lv1 / _poly_mul_1024

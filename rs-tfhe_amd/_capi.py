@@ -45,6 +45,12 @@ class ClockSample(C.Structure):
                 ("rtc_ticks", C.c_uint64)]
 
 
+class PkEncryptTimes(C.Structure):
+    """struct tfhe_hip_pk_encrypt_times"""
+
+    _fields_ = [("selectors_ms", C.c_double), ("contraction_ms", C.c_double), ("passes", C.c_uint64)]
+
+
 class PoolTransferTimes(C.Structure):
     """struct tfhe_hip_pool_transfer_times"""
 
@@ -135,6 +141,12 @@ SIGNATURES = {
     "tfhe_hip_reenc_key_is_loaded": (C.c_int, [_CTX]),
     "tfhe_hip_batch_reencrypt": (C.c_int, [_CTX, _P, _P, _SZ]),
     "tfhe_hip_batch_reencrypt_dev": (C.c_int, [_CTX, _P, _P, _SZ, _P]),
+    "tfhe_hip_load_public_key": (C.c_int, [_CTX, _P, _SZ]),
+    "tfhe_hip_public_key_is_loaded": (C.c_int, [_CTX]),
+    "tfhe_hip_batch_pk_encrypt": (C.c_int, [_CTX, _P, _SZ, C.c_double, _P, C.c_uint64, _P]),
+    "tfhe_hip_batch_pk_encrypt_dev": (C.c_int, [_CTX, _P, _SZ, C.c_double, _P, C.c_uint64, _P, _P]),
+    "tfhe_hip_gen_reenc_key_asymmetric": (C.c_int, [_CTX, _P, C.c_double, _P, _P]),
+    "tfhe_hip_get_pk_encrypt_times": (C.c_int, [_CTX, C.POINTER(PkEncryptTimes)]),
     "tfhe_hip_batch_ifft": (C.c_int, [_CTX, _P, _P, _SZ]),
     "tfhe_hip_batch_fft": (C.c_int, [_CTX, _P, _P, _SZ]),
     "tfhe_hip_batch_poly_mul": (C.c_int, [_CTX, _P, _P, _P, _SZ]),

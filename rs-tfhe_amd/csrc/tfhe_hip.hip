@@ -160,6 +160,10 @@ struct KeyState {
   uint32_t *d_testvec = nullptr;
   unsigned char *d_pk8 = nullptr;  // the packing key as byte planes (packing.hpp): beside, not part of, the cloud key
   bool pk_loaded = false;          // (a cloud-key load or change leaves it; freeing the key view frees it)
+  unsigned char *d_pke8 = nullptr;  // the public key as byte planes (pk_encrypt.hpp), with the packing key's lifetime rules
+  size_t pke_cap = 0;               // bytes allocated at d_pke8
+  int pke_size = 0;                 // encryptions of zero in the loaded public key
+  bool pke_loaded = false;          // tfhe_hip_load_public_key's alone
   uint32_t offset = 0;
   // The flags are written in key_change.hpp only: begin_key_change clears both, commit_cloud_key sets key_loaded (and
   // clears reenc_loaded), commit_reenc_key sets reenc_loaded.  pk_loaded is tfhe_hip_load_packing_key's and
@@ -182,6 +186,7 @@ struct tfhe_hip_ctx {
   double2 *d_tw = nullptr;
   DevBuf lv1, u1, u2, ks_out, ks_dig;  // scratch (ks_dig: key-switch digit bytes)
   DevBuf biv_s1, biv_tv;               // tree bootstrap (table.hpp): stage-1 results [m][chunk][n+1], their tables [chunk][2][N]
+  DevBuf pke_sel;                      // public-key encryption (pk_encrypt.hpp): selector words and addends of one pass
   // host-API staging: a / b / c / out also stage through their arenas on pool members (to_dev / to_host);
   // the arenas of tv / idx serve the combiner lanes only
   Staging a{{}, {}, true}, b{{}, {}, true}, c{{}, {}, true}, out{{}, {}, true}, tv, idx;
@@ -221,6 +226,7 @@ struct tfhe_hip_ctx {
   hipStream_t exp_stream2 = nullptr;
   hipEvent_t exp_ev[2] = {nullptr, nullptr};
   std::vector<std::pair<hipEvent_t, hipEvent_t>> ev_br, ev_ks;
+  std::vector<std::pair<hipEvent_t, hipEvent_t>> ev_pke_sel, ev_pke_mm;  // pk_encrypt.hpp: the keystream pass, the contraction
   uint64_t bootstraps = 0;
   hipStream_t scratch_owner = nullptr;  // stream whose queued work may still use the scratch (claim_scratch)
   bool scratch_owned = false;
@@ -1382,6 +1388,7 @@ void free_key(KeyState &k) {
   if (k.d_ksk) (void)hipFree(k.d_ksk);
   if (k.d_ksk8) (void)hipFree(k.d_ksk8);
   if (k.d_pk8) (void)hipFree(k.d_pk8);
+  if (k.d_pke8) (void)hipFree(k.d_pke8);
   if (k.d_testvec) (void)hipFree(k.d_testvec);
   k = KeyState();
 }
@@ -1428,8 +1435,13 @@ void tfhe_hip_ctx_destroy(tfhe_hip_ctx *ctx) {
     (void)hipEventDestroy(p.first);
     (void)hipEventDestroy(p.second);
   }
+  for (auto *v : {&ctx->ev_pke_sel, &ctx->ev_pke_mm})
+    for (auto &p : *v) {
+      (void)hipEventDestroy(p.first);
+      (void)hipEventDestroy(p.second);
+    }
   Staging *stage[] = {&ctx->a, &ctx->b, &ctx->c, &ctx->out, &ctx->tv, &ctx->idx};
-  for (DevBuf *b : {&ctx->lv1, &ctx->u1, &ctx->u2, &ctx->ks_out, &ctx->ks_dig, &ctx->biv_s1, &ctx->biv_tv})
+  for (DevBuf *b : {&ctx->lv1, &ctx->u1, &ctx->u2, &ctx->ks_out, &ctx->ks_dig, &ctx->biv_s1, &ctx->biv_tv, &ctx->pke_sel})
     if (b->p) (void)hipFree(b->p);
   for (Staging *s : stage)
     if (s->dev.p) (void)hipFree(s->dev.p);
@@ -2277,3 +2289,4 @@ int tfhe_hip_synchronize(tfhe_hip_ctx *ctx) {
 #include "unpack.hpp"
 #include "table.hpp"
 #include "packing_keygen.hpp"
+#include "pk_encrypt.hpp"

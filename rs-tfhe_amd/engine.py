@@ -756,6 +756,69 @@ class Engine(_Handle):
         self._chk(self._lib.tfhe_hip_batch_reencrypt_dev(self._ctx, self._tp(None, a), self._tp(None, out), count,
                                                          self._stream_ptr(None, stream)))
 
+    # -- public-key encryption and the asymmetric re-encryption key (include/tfhe_hip.h; proxy_reenc.py is the client) --
+    def load_public_key(self, encryptions) -> None:
+        """PublicKeyLv0::encryptions [size][n+1] (proxy_reenc.rs:95-99), 1 <= size <= 8192, -> this handle, beside
+        whatever key it holds (`tfhe_hip_load_public_key`); accepts a proxy_reenc.PublicKeyLv0."""
+        enc = _u32(getattr(encryptions, "encryptions", encryptions)).reshape(-1, self.params.n + 1)
+        self._chk(self._lib.tfhe_hip_load_public_key(self._ctx, _ptr(enc), len(enc)))
+
+    def public_key_is_loaded(self) -> bool:
+        return self._lib.tfhe_hip_public_key_is_loaded(self._ctx) == 1  # 0 / 1; anything else is not "loaded"
+
+    @staticmethod
+    def _rng_key_arg(rng_key):
+        """(keep-alive, pointer) of a 32-byte generator key; None: the library draws it from getrandom(2)"""
+        if rng_key is None:
+            return None, None
+        if len(rng_key) != 32:
+            raise ValueError("rng_key is 32 bytes")
+        rk = (C.c_uint8 * 32).from_buffer_copy(bytes(rng_key))
+        return rk, C.addressof(rk)
+
+    def batch_pk_encrypt(self, plain, alpha: float, rng_key: bytes = None, first_index: int = 0) -> np.ndarray:
+        """plain [count] torus words -> [count][n+1] public-key encryptions, row m at index first_index + m of the
+        generator key's streams (`tfhe_hip_batch_pk_encrypt`).  A (rng_key, index) pair must encrypt one message only."""
+        plain = _u32(plain).reshape(-1)
+        out = np.empty((len(plain), self.params.n + 1), np.uint32)
+        rk, rkp = self._rng_key_arg(rng_key)
+        self._chk(self._lib.tfhe_hip_batch_pk_encrypt(self._ctx, _ptr(plain), len(plain), C.c_double(alpha), rkp,
+                                                      C.c_uint64(int(first_index)), _ptr(out)))
+        return out
+
+    def batch_pk_encrypt_dev(self, plain, out, alpha: float, rng_key: bytes = None, first_index: int = 0, stream=None) -> None:
+        """Device form: plain [count] and out [count][n+1] torch tensors (32-bit words) on this engine's GPU; only enqueues."""
+        if plain.dim() != 1:
+            raise ValueError("plain must be [count]")
+        count = plain.shape[0]
+        if out.dim() != 2 or out.shape[0] != count or out.shape[1] != self.params.n + 1:
+            raise ValueError(f"out must be [{count}][{self.params.n + 1}]")
+        rk, rkp = self._rng_key_arg(rng_key)
+        self._chk(self._lib.tfhe_hip_batch_pk_encrypt_dev(self._ctx, self._tp(None, plain), count, C.c_double(alpha), rkp,
+                                                          C.c_uint64(int(first_index)), self._tp(None, out),
+                                                          self._stream_ptr(None, stream)))
+
+    def gen_reenc_key_asymmetric(self, key_from, alpha=None, rng_key: bytes = None, download: bool = True):
+        """ProxyReencryptionKey::new_asymmetric (proxy_reenc.rs:271-326) towards the public key loaded on this handle,
+        generated on the GPU and left loaded here (`tfhe_hip_gen_reenc_key_asymmetric`).  key_from: the delegator's
+        key_lv0 [n]; alpha: alpha_lv0 of the set by default.  Returns key_encryptions [n t base][n+1], or None with
+        download=False (the key stays on the GPU)."""
+        p = self.params
+        k0 = _u32(key_from).reshape(-1)
+        if len(k0) != p.n:
+            raise ValueError("secret key has the wrong size for these parameters")
+        key = np.empty((p.n * p.iks_t * p.base, p.n + 1), np.uint32) if download else None
+        rk, rkp = self._rng_key_arg(rng_key)
+        self._chk(self._lib.tfhe_hip_gen_reenc_key_asymmetric(self._ctx, _ptr(k0), C.c_double(p.alpha_lv0 if alpha is None else alpha),
+                                                              rkp, _ptr(key)))
+        return key
+
+    def pk_encrypt_times(self) -> dict:
+        """Kernel times of the public-key encryption / asymmetric key passes since the last call (profiling on)."""
+        t = _capi.PkEncryptTimes()
+        self._chk(self._lib.tfhe_hip_get_pk_encrypt_times(self._ctx, C.byref(t)))
+        return {"selectors_ms": t.selectors_ms, "contraction_ms": t.contraction_ms, "passes": int(t.passes)}
+
     def batch_ifft(self, polys) -> np.ndarray:
         polys = _u32(polys).reshape(-1, N)
         out = np.empty((len(polys), N), np.float64)

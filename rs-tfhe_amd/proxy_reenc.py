@@ -12,17 +12,62 @@ switch with a source of n coefficients -- runs on the GPU through the key-switch
 
 Randomness follows client.py: `seed=None` draws from the operating system; an integer seed is reproducible and for
 tests only.
+
+Public-key encryption and the asymmetric key also exist in the keyed format of include/tfhe_hip.h ("public-key
+encryption and the asymmetric re-encryption key"): every selector bit and noise sample is a position of a ChaCha20
+keystream under a secret 32-byte generator key.  `rng_key=` alone is the CPU form of that format (`encrypt_rows`
+below); `device=` runs it on the GPU (`tfhe_hip_batch_pk_encrypt`, `tfhe_hip_gen_reenc_key_asymmetric`), where
+rng_key=None draws the key from getrandom(2).  A (rng_key, row index) pair must never encrypt two messages.
 """
 from __future__ import annotations
 
 import numpy as np
 
+from . import seeded
 from .client import SecretKey, _rng, f64_to_torus
 from .params import SecurityParams
+
+DOMAIN_PKE_SEL, DOMAIN_PKE_NOISE = 0x504B45, 0x504B4E  # "PKE", "PKN": public-key encryptions
+DOMAIN_RKE_SEL, DOMAIN_RKE_NOISE = 0x524B45, 0x524B4E  # "RKE", "RKN": rows of the asymmetric re-encryption key
+MAX_PUBLIC_KEY_SIZE = 8192
 
 
 def _key_lv0(key) -> np.ndarray:
     return np.ascontiguousarray(key.key_lv0 if isinstance(key, SecretKey) else key, dtype=np.uint32)
+
+
+def _rng_key(rng_key) -> bytes:
+    if not isinstance(rng_key, (bytes, bytearray)) or len(rng_key) != 32:
+        raise ValueError("rng_key is 32 bytes")
+    return bytes(rng_key)
+
+
+def selectors(rng_key: bytes, rows, size: int, domain: int) -> np.ndarray:
+    """The coefficients c in {-1, 0, +1} of rows `rows` (u64 indices) as [rows][size] f64: entry e reads bits
+    2 (e % 16) (take) and 2 (e % 16) + 1 (sign, 1 = subtract) of word e / 16 of the stream (g lo, g hi, domain)."""
+    g = np.asarray(rows, np.uint64)
+    w = seeded.keystream(rng_key, (size + 15) // 16, g & np.uint64(0xFFFFFFFF), g >> np.uint64(32), domain)
+    e = np.arange(size)
+    fields = (w[:, e // 16] >> (2 * (e % 16)).astype(np.uint32)) & np.uint32(3)
+    return np.where(fields & 1, np.where(fields & 2, -1.0, 1.0), 0.0)
+
+
+def encrypt_rows(encryptions: np.ndarray, rng_key: bytes, rows, plain, alpha: float, domains, chunk: int = 2048) -> np.ndarray:
+    """The CPU form of the keyed format: row g of `rows` is sum_e c_e E[e] (the exact f64 product: |sum| <= size 2^32
+    < 2^53) with plain (torus words) + f64_to_torus(g0 of gauss2(block 0 of the noise stream)) on the body."""
+    rng_key = _rng_key(rng_key)
+    rows = np.asarray(rows, np.uint64).reshape(-1)
+    plain = np.asarray(plain, np.uint32).reshape(-1)
+    size, w = encryptions.shape
+    enc = encryptions.astype(np.float64)
+    out = np.empty((len(rows), w), np.uint32)
+    for lo in range(0, len(rows), chunk):
+        acc = selectors(rng_key, rows[lo:lo + chunk], size, domains[0]) @ enc
+        out[lo:lo + chunk] = np.mod(acc, 4294967296.0).astype(np.uint64).astype(np.uint32)
+    nw = seeded.chacha20_block(rng_key, 0, rows & np.uint64(0xFFFFFFFF), rows >> np.uint64(32), domains[1])[:, :4]
+    g0, _ = seeded.gauss2(nw, float(alpha))
+    out[:, -1] += plain + f64_to_torus(g0)
+    return out
 
 
 class PublicKeyLv0:
@@ -31,6 +76,7 @@ class PublicKeyLv0:
     def __init__(self, params: SecurityParams, encryptions):
         self.params = params
         self.encryptions = np.ascontiguousarray(encryptions, dtype=np.uint32).reshape(-1, params.n + 1)
+        self._view = None
 
     @classmethod
     def new(cls, secret_key: SecretKey, seed=None) -> "PublicKeyLv0":
@@ -43,11 +89,22 @@ class PublicKeyLv0:
         """proxy_reenc.rs:144-153."""
         return cls(secret_key.params, secret_key.encrypt_f64(np.zeros(int(size)), seed, alpha))
 
-    def encrypt_f64(self, plaintext, alpha: float, seed=None) -> np.ndarray:
+    def encrypt_f64(self, plaintext, alpha: float, seed=None, rng_key=None, first_index: int = 0, device=None) -> np.ndarray:
         """proxy_reenc.rs:168-200, batched over `plaintext`: every encryption of zero joins with probability 1/2, added
-        or subtracted with probability 1/2 each; then f64_to_torus(plaintext) and fresh noise N(0, alpha) on b."""
-        g = _rng(seed)
+        or subtracted with probability 1/2 each; then f64_to_torus(plaintext) and fresh noise N(0, alpha) on b.
+        rng_key / first_index / device: the keyed format of include/tfhe_hip.h, ciphertext m at row first_index + m --
+        on the CPU with rng_key alone, on GPU `device` otherwise (rng_key=None there: a key from getrandom(2))."""
         pt = np.atleast_1d(np.asarray(plaintext, dtype=np.float64))
+        if rng_key is not None or device is not None:
+            if seed is not None:
+                raise ValueError("seed selects numpy's generator; rng_key / device select the keyed format")
+            if not (0 <= int(first_index) and int(first_index) + len(pt) <= 1 << 64):
+                raise ValueError("first_index is a u64")
+            if device is not None:
+                return self.view(device).batch_pk_encrypt(f64_to_torus(pt), alpha, rng_key, first_index)
+            rows = np.uint64(int(first_index)) + np.arange(len(pt), dtype=np.uint64)
+            return encrypt_rows(self.encryptions, rng_key, rows, f64_to_torus(pt), alpha, (DOMAIN_PKE_SEL, DOMAIN_PKE_NOISE))
+        g = _rng(seed)
         size, w = self.encryptions.shape
         enc = self.encryptions.astype(np.float64)  # |sum| <= size * 2^32 < 2^53: the f64 product below is exact
         out = np.empty((len(pt), w), np.uint32)
@@ -61,10 +118,42 @@ class PublicKeyLv0:
         out[:, -1] += f64_to_torus(pt) + noise
         return out
 
-    def encrypt_bool(self, bits, alpha: float, seed=None) -> np.ndarray:
+    def encrypt_bool(self, bits, alpha: float, seed=None, rng_key=None, first_index: int = 0, device=None) -> np.ndarray:
         """proxy_reenc.rs:212-215."""
         bits = np.atleast_1d(np.asarray(bits)).astype(bool)
-        return self.encrypt_f64(np.where(bits, 0.125, -0.125), alpha, seed)
+        return self.encrypt_f64(np.where(bits, 0.125, -0.125), alpha, seed, rng_key, first_index, device)
+
+    def view(self, device: int = 0):
+        """The key view of the shared context that holds this public key's byte planes (loaded on first use)."""
+        if self._view is None or self._view[0] != device:
+            from .bootstrap import engine_for
+
+            self.close()
+            v = engine_for(self.params, device).new_key_view()
+            v.load_public_key(self.encryptions)
+            self._view = (device, v)
+        return self._view[1]
+
+    def close(self) -> None:
+        """Free the device copy (also on garbage collection)."""
+        if getattr(self, "_view", None) is not None:
+            self._view[1].close()
+            self._view = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def _engine_params(p: SecurityParams, basebit: int, t: int) -> SecurityParams:
+    """The context's parameter set: the ciphertexts' set with the key's (basebit, t) (custom `_with_params` keys)."""
+    if (p.basebit, p.iks_t) == (basebit, t):
+        return p
+    import dataclasses
+
+    return dataclasses.replace(p, name=f"{p.name}+reenc(basebit={basebit},t={t})", basebit=basebit, iks_t=t)
 
 
 class ProxyReencryptionKey:
@@ -76,9 +165,9 @@ class ProxyReencryptionKey:
             raise ValueError(f"proxy re-encryption on the GPU needs n <= 1024 ({params.name}: n = {params.n})")
         self.params = params
         self.basebit, self.t, self.base = int(basebit), int(t), 1 << int(basebit)
+        self._view = None
         self.key_encryptions = np.ascontiguousarray(key_encryptions, dtype=np.uint32).reshape(
             params.n * self.t * self.base, params.n + 1)
-        self._view = None
 
     # the plaintexts both constructors encrypt: k * key_from[i] / 2^((j+1) basebit), k = 1 .. base-1 (:316, :414)
     @staticmethod
@@ -106,30 +195,51 @@ class ProxyReencryptionKey:
         return cls(p, enc, basebit, t)
 
     @classmethod
-    def new_asymmetric(cls, key_from, public_key_to: PublicKeyLv0, seed=None) -> "ProxyReencryptionKey":
+    def new_asymmetric(cls, key_from, public_key_to: PublicKeyLv0, seed=None, rng_key=None,
+                       device=None) -> "ProxyReencryptionKey":
         """proxy_reenc.rs:271-279."""
         p = public_key_to.params
-        return cls.new_asymmetric_with_params(key_from, public_key_to, p.alpha_lv0, p.basebit, p.iks_t, seed)
+        return cls.new_asymmetric_with_params(key_from, public_key_to, p.alpha_lv0, p.basebit, p.iks_t, seed, rng_key, device)
 
     @classmethod
     def new_asymmetric_with_params(cls, key_from, public_key_to: PublicKeyLv0, alpha: float, basebit: int, t: int,
-                                   seed=None) -> "ProxyReencryptionKey":
-        """proxy_reenc.rs:294-330: public_key_to.encrypt_f64(p, alpha) per (i, j, k != 0)."""
+                                   seed=None, rng_key=None, device=None) -> "ProxyReencryptionKey":
+        """proxy_reenc.rs:294-330: public_key_to.encrypt_f64(p, alpha) per (i, j, k != 0).
+        rng_key / device: the keyed format of include/tfhe_hip.h (row base t i + base j + k) -- on the CPU with rng_key
+        alone; with `device` the key is generated in a key view of that GPU (`tfhe_hip_gen_reenc_key_asymmetric`;
+        rng_key=None: a key from getrandom(2)) which the returned object keeps, so `reencrypt` uploads nothing."""
         p = public_key_to.params
         pts = cls._plaintexts(_key_lv0(key_from), basebit, t)
+        if rng_key is not None or device is not None:
+            if seed is not None:
+                raise ValueError("seed selects numpy's generator; rng_key / device select the keyed format")
+            if device is not None:
+                from .bootstrap import engine_for
+
+                if p.n > 1024:
+                    raise ValueError(f"proxy re-encryption on the GPU needs n <= 1024 ({p.name}: n = {p.n})")
+                v = engine_for(_engine_params(p, int(basebit), int(t)), device).new_key_view()
+                try:
+                    v.load_public_key(public_key_to.encryptions)
+                    key = cls(p, v.gen_reenc_key_asymmetric(_key_lv0(key_from), alpha, rng_key), basebit, t)
+                except Exception:
+                    v.close()
+                    raise
+                key._view = (device, v)
+                return key
+            rows = np.arange(pts.size, dtype=np.uint64)
+            live = rows % np.uint64(1 << basebit) != 0
+            enc = np.zeros((pts.size, p.n + 1), np.uint32)
+            enc[live] = encrypt_rows(public_key_to.encryptions, rng_key, rows[live], f64_to_torus(pts.reshape(-1)[live]),
+                                     alpha, (DOMAIN_RKE_SEL, DOMAIN_RKE_NOISE))
+            return cls(p, enc, basebit, t)
         enc = public_key_to.encrypt_f64(pts.reshape(-1), alpha, seed).reshape(p.n, t, 1 << basebit, p.n + 1)
         enc[:, :, 0, :] = 0
         return cls(p, enc, basebit, t)
 
     # ---- the proxy's side: on the GPU -------------------------------------------------------------------------
     def _engine_params(self) -> SecurityParams:
-        """The context's parameter set: the ciphertexts' set with this key's (basebit, t) (custom `_with_params` keys)."""
-        p = self.params
-        if (p.basebit, p.iks_t) == (self.basebit, self.t):
-            return p
-        import dataclasses
-
-        return dataclasses.replace(p, name=f"{p.name}+reenc(basebit={self.basebit},t={self.t})", basebit=self.basebit, iks_t=self.t)
+        return _engine_params(self.params, self.basebit, self.t)
 
     def view(self, device: int = 0):
         """The key view that holds this key (created and loaded on first use; `close()` frees its 0.1 GB)."""

@@ -105,6 +105,14 @@ extern "C" {   // packing key switch (include/tfhe_hip.h): up to N lv0 results i
     fn tfhe_hip_pool_batch_bootstrap_bivariate(pool: *mut TfheHipPool, x: *const u32, y: *const u32, testvecs: *const u32,
                                                m: c_int, n_luts: c_int, keyswitch: c_int, out: *mut u32,
                                                count: usize) -> c_int;
+    // public-key encryption and the asymmetric re-encryption key (include/tfhe_hip.h): no pool forms, they run on a
+    // member context (tfhe_hip_pool_ctx) of the public key's view
+    fn tfhe_hip_load_public_key(ctx_or_view: *mut TfheHipCtx, encryptions: *const u32, size: usize) -> c_int;
+    fn tfhe_hip_batch_pk_encrypt(ctx: *mut TfheHipCtx, plain: *const u32, count: usize, alpha: f64, rng_key: *const u8,
+                                 first_index: u64, out: *mut u32) -> c_int;
+    fn tfhe_hip_gen_reenc_key_asymmetric(ctx_or_view: *mut TfheHipCtx, key_from: *const u32, alpha: f64,
+                                         rng_key: *const u8, key_out: *mut u32) -> c_int;
+    fn tfhe_hip_batch_reencrypt(ctx: *mut TfheHipCtx, input: *const u32, out: *mut u32, count: usize) -> c_int;
 }
 
 /// A member context of a pool (tfhe_hip_pool_ctx): opaque, owned by the pool.
@@ -143,7 +151,8 @@ struct KeyView { addr: usize, fp: u64, view: *mut TfheHipPool, last_use: u64, us
 struct PackingView { fp: u64, view: *mut TfheHipPool }
 
 /// Owns the C pool (one context per device) and the key views on it.
-pub struct HipEngine { pool: *mut TfheHipPool, views: Mutex<(Vec<KeyView>, u64)>, packing: Mutex<PackingView> }
+pub struct HipEngine { pool: *mut TfheHipPool, views: Mutex<(Vec<KeyView>, u64)>, packing: Mutex<PackingView>,
+                       public_key: Mutex<PackingView> }   // (the public key's own view; `fp` is its size, 0 = none)
 unsafe impl Send for HipEngine {}   // the library merges concurrent small calls into shared launches and serialises the rest per context; `views` is behind its Mutex
 unsafe impl Sync for HipEngine {}
 
@@ -161,7 +170,8 @@ impl HipEngine {
         let rc = unsafe { tfhe_hip_pool_create(&p, devices.as_ptr(), devices.len() as c_int, &mut pool) };
         assert_eq!(rc, 0, "tfhe_hip_pool_create failed");   // the reference has no Result on this path
         HipEngine { pool, views: Mutex::new((Vec::new(), 0)),
-                    packing: Mutex::new(PackingView { fp: 0, view: std::ptr::null_mut() }) }
+                    packing: Mutex::new(PackingView { fp: 0, view: std::ptr::null_mut() }),
+                    public_key: Mutex::new(PackingView { fp: 0, view: std::ptr::null_mut() }) }
     }
 
     fn check(h: *mut TfheHipPool, rc: c_int) {
@@ -447,6 +457,78 @@ impl HipEngine {
         (seed, bodies)
     }
 
+    fn check_ctx(ctx: *mut TfheHipCtx, rc: c_int) {
+        if rc != 0 {
+            let msg = unsafe { std::ffi::CStr::from_ptr(tfhe_hip_last_error(ctx)) };
+            panic!("tfhe_hip: {}", msg.to_string_lossy());
+        }
+    }
+
+    /// The first member's context of the public key's view (created on first use).
+    fn public_key_ctx(&self, g: &mut PackingView) -> *mut TfheHipCtx {
+        if g.view.is_null() {
+            let mut view = std::ptr::null_mut();
+            assert_eq!(unsafe { tfhe_hip_pool_key_create(self.pool, &mut view) }, 0, "tfhe_hip_pool_key_create failed");
+            g.view = view;
+        }
+        let ctx = unsafe { tfhe_hip_pool_ctx(g.view, 0) };
+        assert!(!ctx.is_null(), "tfhe_hip_pool_ctx failed");
+        ctx
+    }
+
+    /// PublicKeyLv0::encryptions, flat [size][n+1] with 1 <= size <= 8192, onto the public key's view
+    /// (`tfhe_hip_load_public_key`): what `pk_encrypt` and `gen_reenc_key_asymmetric` below encrypt under.
+    pub fn load_public_key(&self, encryptions: &[u32]) {
+        assert!(!encryptions.is_empty() && encryptions.len() % W == 0, "encryptions is [size][n+1]");
+        let mut g = self.public_key.lock().unwrap();   // held through the call: a concurrent encryption cannot meet half a key
+        let ctx = self.public_key_ctx(&mut g);
+        g.fp = 0;
+        Self::check_ctx(ctx, unsafe { tfhe_hip_load_public_key(ctx, encryptions.as_ptr(), encryptions.len() / W) });
+        g.fp = (encryptions.len() / W) as u64;
+    }
+
+    /// PublicKeyLv0::encrypt_f64 over a batch on the GPU, in the keyed format of include/tfhe_hip.h: `plain` are torus
+    /// words (f64_to_torus of the messages), ciphertext m is row `first_index + m` of the generator key's streams.
+    /// `rng_key`: the 32-byte generator key from the caller's CSPRNG, None draws it from getrandom(2).  A (rng_key, row)
+    /// pair must never encrypt two messages.  Returns [count][n+1], flat.
+    pub fn pk_encrypt(&self, plain: &[u32], alpha: f64, rng_key: Option<&[u8; 32]>, first_index: u64) -> Vec<u32> {
+        let mut out = vec![0u32; plain.len() * W];
+        let mut g = self.public_key.lock().unwrap();
+        assert!(g.fp != 0, "no public key loaded: call load_public_key first");
+        let ctx = self.public_key_ctx(&mut g);
+        let rk = rng_key.map_or(std::ptr::null(), |k| k.as_ptr());
+        Self::check_ctx(ctx, unsafe {
+            tfhe_hip_batch_pk_encrypt(ctx, plain.as_ptr(), plain.len(), alpha, rk, first_index, out.as_mut_ptr())
+        });
+        out
+    }
+
+    /// ProxyReencryptionKey::new_asymmetric (src/proxy_reenc.rs:271-326) from `key_from` (the delegator's key_lv0 [n])
+    /// towards the loaded public key, generated on the GPU (`tfhe_hip_gen_reenc_key_asymmetric`): returns
+    /// key_encryptions [n][t][base][n+1], flat, and leaves the public key's view holding the key, so that
+    /// `reencrypt_generated` uploads nothing.  A client-side call: it takes a secret key.
+    pub fn gen_reenc_key_asymmetric(&self, key_from: &[u32], alpha: f64, rng_key: Option<&[u8; 32]>) -> Vec<u32> {
+        let n = params::tlwe_lv0::N;
+        assert_eq!(key_from.len(), n, "key_from is [n]");
+        let mut key = vec![0u32; n * params::trgsw_lv1::IKS_T * (1usize << params::trgsw_lv1::BASEBIT) * W];
+        let mut g = self.public_key.lock().unwrap();
+        assert!(g.fp != 0, "no public key loaded: call load_public_key first");
+        let ctx = self.public_key_ctx(&mut g);
+        let rk = rng_key.map_or(std::ptr::null(), |k| k.as_ptr());
+        Self::check_ctx(ctx, unsafe { tfhe_hip_gen_reenc_key_asymmetric(ctx, key_from.as_ptr(), alpha, rk, key.as_mut_ptr()) });
+        key
+    }
+
+    /// reencrypt_tlwe_lv0 over `cts` ([count][n+1], flat) under the key `gen_reenc_key_asymmetric` left on the view.
+    pub fn reencrypt_generated(&self, cts: &[u32]) -> Vec<u32> {
+        assert_eq!(cts.len() % W, 0, "cts is [count][n+1]");
+        let mut out = vec![0u32; cts.len()];
+        let mut g = self.public_key.lock().unwrap();
+        let ctx = self.public_key_ctx(&mut g);
+        Self::check_ctx(ctx, unsafe { tfhe_hip_batch_reencrypt(ctx, cts.as_ptr(), out.as_mut_ptr(), cts.len() / W) });
+        out
+    }
+
     /// Encrypted-table key switch, the definition of include/tfhe_hip.h: `stage1` ([m][count][n+1] lv0 ciphertexts, flat,
     /// function-major -- what the many-LUT bootstrap writes) becomes `count` encrypted test vectors [count][2][N] under
     /// s1, each the generator's table of its m inputs' phases.  Runs on the first member of the packing key's view (the
@@ -554,6 +636,8 @@ impl Drop for HipEngine {
         for v in self.views.lock().unwrap().0.drain(..) { unsafe { tfhe_hip_pool_destroy(v.view) } }   // views before their pool
         let pv = self.packing.lock().unwrap().view;
         if !pv.is_null() { unsafe { tfhe_hip_pool_destroy(pv) } }
+        let kv = self.public_key.lock().unwrap().view;
+        if !kv.is_null() { unsafe { tfhe_hip_pool_destroy(kv) } }
         unsafe { tfhe_hip_pool_destroy(self.pool) }
     }
 }
