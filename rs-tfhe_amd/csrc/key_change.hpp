@@ -14,9 +14,10 @@
 //    quiesces the lanes and synchronises the whole device first, and the old flag stands until the commit;
 //  - the pool's broadcast replication splits begin (prepare_replica) and commit (finish_replica) around the
 //    broadcast, which runs outside the member's call, and synchronises the whole device before the commit;
-//  - the packing key (packing.hpp) has its own flag and planes, which are not the key switch's: it drains with a
-//    device-wide synchronisation, is left alone by a cloud-key change, and takes only upload_through_temp from here
-//    (its generation, packing_keygen.hpp, also the staged secrets below).
+// The side keys -- the packing key (packing.hpp, packing_keygen.hpp) and the public key (pk_encrypt.hpp) -- have their
+// own flags and byte planes, which are not the key switch's, and their own, smaller pair: begin_side_key drains the
+// whole device, clears the side key's flag and grows its planes; the route fills them; commit_side_key sets the flag
+// LAST.  A cloud-key change leaves them alone, and validation comes before the begin here too.
 // ctx->mu is held and ctx's device is current in everything below.
 #pragma once
 
@@ -77,6 +78,32 @@ int commit_reenc_key(tfhe_hip_ctx *ctx) {
   return TFHE_HIP_OK;
 }
 
+// ---- side keys ------------------------------------------------------------------------------------------------------
+// `flag` / `planes` / `cap` are the side key's members of *ctx->K.  Calls queued on the caller's streams may still read
+// the planes that are about to be overwritten: hence the device-wide drain.
+int begin_side_key(tfhe_hip_ctx *ctx, bool &flag, unsigned char *&planes, size_t &cap, size_t bytes) {
+  HIPCHK(ctx, hipDeviceSynchronize());
+  flag = false;
+  if (bytes <= cap) return TFHE_HIP_OK;
+  if (planes) HIPCHK(ctx, hipFree(planes));
+  planes = nullptr;
+  cap = 0;
+  HIPCHK(ctx, hipMalloc((void **)&planes, bytes));
+  cap = bytes;
+  return TFHE_HIP_OK;
+}
+void commit_side_key(bool &flag) { flag = true; }
+
+// The *_is_loaded calls: 0 / 1, never an error code, no device call.  No lock: the host mirrors ask this before EVERY
+// call (is the view's key resident yet?), and the context's mutex may be held for the length of a 65,536-ciphertext
+// host call -- a one-gate call on another thread would wait 330 ms just to learn what it already knows.  A flag is set
+// last by the calls that load a key and cleared first by those that change one; a caller that races its own key load is
+// the caller's to order (as for any call under that key).
+int flag_is_loaded(tfhe_hip_ctx *ctx, bool KeyState::*flag) {
+  if (!ctx) return 0;
+  return __atomic_load_n(&(ctx->own.*flag), __ATOMIC_ACQUIRE) ? 1 : 0;
+}
+
 // ---- host key -> device, converted ----------------------------------------------------------------------------------
 // A device temporary of the sources' bytes plus `extra_bytes`; the sources copied into it back to back on ctx->stream;
 // launch(temporary) -> hipError_t queues the conversion; the stream drained and the temporary freed on every path.
@@ -104,6 +131,42 @@ int upload_through_temp(tfhe_hip_ctx *ctx, const char *label, std::initializer_l
   if (e != hipSuccess) return fail(ctx, TFHE_HIP_EHIP, std::string(label) + " upload: " + hipGetErrorString(e));
   return TFHE_HIP_OK;
 }
+
+// the kernel's CSPRNG, as the reference's thread_rng is seeded (OsRng)
+int os_random(uint8_t *buf, size_t bytes) {  // 0, or errno
+  size_t got = 0;
+  while (got < bytes) {
+    const ssize_t r = getrandom(buf + got, bytes - got, 0);
+    if (r < 0) {
+      if (errno == EINTR) continue;
+      return errno;
+    }
+    got += (size_t)r;
+  }
+  return 0;
+}
+std::string os_random_text(int err) { return std::string("getrandom: ") + strerror(err); }
+
+// The 256-bit generator key K of one call: the caller's rng_key, or (NULL) 32 bytes of getrandom(2).  Wiped when the call
+// leaves, whichever way.
+struct GeneratorKey {
+  ChaChaKey k{};
+  GeneratorKey() = default;
+  GeneratorKey(const GeneratorKey &) = delete;
+  GeneratorKey &operator=(const GeneratorKey &) = delete;
+  int fill(tfhe_hip_ctx *ctx, const uint8_t *rng_key) {
+    if (rng_key) {
+      memcpy(k.k, rng_key, 32);  // 8 little-endian words
+    } else if (const int err = os_random((uint8_t *)k.k, sizeof(k.k))) {
+      return fail(ctx, TFHE_HIP_EHIP, os_random_text(err));
+    }
+    return TFHE_HIP_OK;
+  }
+  ~GeneratorKey() {
+    volatile uint32_t *wipe = k.k;
+    for (int i = 0; i < 8; ++i) wipe[i] = 0;
+  }
+};
 
 // ---- key generation: the secrets on the device -----------------------------------------------------------------------
 // The secret keys, the spectrum of the ring key and the generator key do not outlive the call on the device,
@@ -142,6 +205,17 @@ int stage_secrets(tfhe_hip_ctx *ctx, const uint32_t *key_lv0, const uint32_t *ke
   return TFHE_HIP_OK;
 }
 
+// The public mask seed S of stream STREAM of the staged generator key (k_derive_stream_seed), derived into the slot
+// behind it (idx[32, 64): stage_secrets was given 2 * sizeof(ChaChaKey)) and copied back.
+template <uint32_t STREAM>
+int derive_public_seed(tfhe_hip_ctx *ctx, const StagedSecrets &s, ChaChaKey &seed) {
+  hipLaunchKernelGGL((k_derive_stream_seed<64, STREAM>), dim3(1), dim3(64), 0, ctx->stream, s.d_rk, s.d_rk + 1);
+  HIPCHK(ctx, hipGetLastError());
+  HIPCHK(ctx, hipMemcpyAsync(&seed, s.d_rk + 1, sizeof(seed), hipMemcpyDeviceToHost, ctx->stream));
+  HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+  return TFHE_HIP_OK;
+}
+
 // what a generated key gets: the decomposition offset (key.rs:78-89) and the test vector (key.rs:91-100), uploaded
 int default_offset_and_testvec(tfhe_hip_ctx *ctx, uint32_t *offset) {
   const tfhe_hip_params &P = ctx->P;
@@ -154,20 +228,5 @@ int default_offset_and_testvec(tfhe_hip_ctx *ctx, uint32_t *offset) {
   *offset = off;
   return TFHE_HIP_OK;
 }
-
-// the kernel's CSPRNG, as the reference's thread_rng is seeded (OsRng)
-int os_random(uint8_t *buf, size_t bytes) {  // 0, or errno
-  size_t got = 0;
-  while (got < bytes) {
-    const ssize_t r = getrandom(buf + got, bytes - got, 0);
-    if (r < 0) {
-      if (errno == EINTR) continue;
-      return errno;
-    }
-    got += (size_t)r;
-  }
-  return 0;
-}
-std::string os_random_text(int err) { return std::string("getrandom: ") + strerror(err); }
 
 }  // namespace

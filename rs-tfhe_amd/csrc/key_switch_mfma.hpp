@@ -95,6 +95,21 @@ __host__ __device__ __forceinline__ uint32_t ks_plane_byte(uint32_t w, int p) {
   return s;
 }
 
+// The 16 bytes of a lane's key fragment: byte e of dword q = plane byte p of word(q, e).  The three plane builders
+// (k_ksk_planes, k_pack_planes, k_pke_planes) differ only in `word`, the mapping (step, lane, q, e) -> key word.
+template <class Word>
+__device__ __forceinline__ uint4 ks_plane_fragment(int p, Word word) {
+  uint32_t o[4];
+#pragma unroll
+  for (int q = 0; q < 4; ++q) {
+    uint32_t d = 0;
+#pragma unroll
+    for (int e = 0; e < 4; ++e) d |= ks_plane_byte(word(q, e), p) << (8 * e);
+    o[q] = d;
+  }
+  return make_uint4(o[0], o[1], o[2], o[3]);
+}
+
 // u32 engine layout [N*t*4][RW] -> byte planes in MFMA fragment order:
 //   [plane p][column block cb][K-step s][tile c < block tiles][lane][16 B],  s = blk*2t + 2j + hh  (blk: 16-coefficient
 //   block, j: digit position, hh: which 8 coefficients), lane = (column in tile = lane & 31, kb = lane >> 5),
@@ -117,20 +132,11 @@ __global__ void k_ksk_planes(const uint32_t *__restrict__ eng, unsigned char *__
   const int col = (ks_mfma_block_first(n, cb) + c) * 32 + (lane & 31), kb = lane >> 5;
   const int blk = s / (2 * t), u = s % (2 * t), j = u >> 1, hh = u & 1;
   const int rw = (n + 1 + 3) & ~3;
-  uint32_t o[4];
-#pragma unroll
-  for (int cc = 0; cc < 4; ++cc) {
+  reinterpret_cast<uint4 *>(out)[idx] = ks_plane_fragment(p, [=](int cc, int k) {
     const int i = 16 * blk + 8 * hh + 4 * kb + cc;
-    uint32_t d = 0;
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-      const size_t row = ((size_t)i * t + j) * 4 + k;
-      const uint32_t w = (col <= n && k != 0) ? eng[row * (size_t)rw + col] : 0u;
-      d |= ks_plane_byte(w, p) << (8 * k);
-    }
-    o[cc] = d;
-  }
-  reinterpret_cast<uint4 *>(out)[idx] = make_uint4(o[0], o[1], o[2], o[3]);
+    const size_t row = ((size_t)i * t + j) * 4 + k;
+    return (col <= n && k != 0) ? eng[row * (size_t)rw + col] : 0u;
+  });
 }
 
 using km_i32x4 = __attribute__((ext_vector_type(4))) int;

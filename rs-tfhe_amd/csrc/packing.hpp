@@ -29,7 +29,6 @@
 
 namespace tfhe {
 
-constexpr uint32_t kSeedDomainPack = 0x504B53u;  // "PKS": masks of the packing key, nonce (row, 24, "PKS")
 constexpr int kPkTiles = 2 * kN / 32;            // 32-column tiles of a key row: a = 0..31, b = 32..63
 constexpr int kPkNT = 8;                         // tiles per wave (divides 32: a column group never straddles a and b)
 constexpr int kPkMaxBasebit = 7;                 // digits in [-64, 64): one signed byte
@@ -49,7 +48,7 @@ __global__ __launch_bounds__(WG) void k_pack_expand_key(const uint32_t *__restri
   const uint32_t r = blockIdx.x;
   const int lane = threadIdx.x;
   uint32_t w[16];
-  chacha20_block(seed, (uint32_t)lane, r, 24u, kSeedDomainPack, w);
+  chacha20_block(seed, (uint32_t)lane, r, kStreamPackMask, kSeedDomainPack, w);
   uint4 *dst = reinterpret_cast<uint4 *>(rows + (size_t)r * 2 * kN + 16 * lane);
 #pragma unroll
   for (int q = 0; q < 4; ++q) dst[q] = make_uint4(w[4 * q], w[4 * q + 1], w[4 * q + 2], w[4 * q + 3]);
@@ -74,19 +73,10 @@ __global__ __launch_bounds__(WG) void k_pack_planes(const uint32_t *__restrict__
   const int ct = (int)(r % kPkTiles), p = (int)(r / kPkTiles);
   const int col = ct * 32 + (lane & 31), kb = lane >> 5;
   const int ib = s / t, l = s % t;
-  uint32_t o[4];
-#pragma unroll
-  for (int q = 0; q < 4; ++q) {
-    uint32_t d = 0;
-#pragma unroll
-    for (int e = 0; e < 4; ++e) {
-      const int i = 32 * ib + 16 * kb + 4 * q + e;
-      const uint32_t w = i < n ? rows[((size_t)i * t + l) * 2 * kN + col] : 0u;
-      d |= ks_plane_byte(w, p) << (8 * e);
-    }
-    o[q] = d;
-  }
-  reinterpret_cast<uint4 *>(out)[idx] = make_uint4(o[0], o[1], o[2], o[3]);
+  reinterpret_cast<uint4 *>(out)[idx] = ks_plane_fragment(p, [=](int q, int e) {
+    const int i = 32 * ib + 16 * kb + 4 * q + e;
+    return i < n ? rows[((size_t)i * t + l) * 2 * kN + col] : 0u;
+  });
 }
 
 // out [groups][2][N]: a rows 0, b rows b_j on the slots that hold an input (k_pack_mfma's atomics add the rest)
@@ -210,6 +200,7 @@ __global__ __launch_bounds__(256, 2) void k_pack_mfma(const uint32_t *__restrict
 // ---- packing key switch (packing.hpp) -------------------------------------------------------------------------
 namespace {
 bool packing_supported(const tfhe_hip_params *p) { return params_supported(p) && p->basebit <= kPkMaxBasebit; }
+const char *const kPackingRefusal = "packing needs basebit <= 7 (digits in one byte)";
 }  // namespace
 
 int tfhe_hip_packing_key_words(const tfhe_hip_params *params, size_t *body_words) {
@@ -250,13 +241,11 @@ int tfhe_hip_load_packing_key(tfhe_hip_ctx *ctx, const uint8_t mask_seed[32], co
   ENTER(ctx);
   if (!mask_seed || !bodies) return fail(ctx, TFHE_HIP_EINVAL, "null key pointer");
   const tfhe_hip_params &P = ctx->P;
-  if (P.basebit > kPkMaxBasebit) return fail(ctx, TFHE_HIP_EINVAL, "packing needs basebit <= 7 (digits in one byte)");
-  // packing calls queued on the caller's streams may still read the planes this call overwrites
-  HIPCHK(ctx, hipDeviceSynchronize());
+  if (!packing_supported(&P)) return fail(ctx, TFHE_HIP_EINVAL, kPackingRefusal);
+  KeyState &k = *ctx->K;
+  CHK(begin_side_key(ctx, k.pk_loaded, k.d_pk8, k.pk_cap, pk_plane_bytes(P.n, P.t)));
   const size_t rows = (size_t)P.n * P.t, body_words = rows * kN;
   const size_t chunks = pk_plane_bytes(P.n, P.t) / 16;
-  ctx->K->pk_loaded = false;
-  if (!ctx->K->d_pk8) HIPCHK(ctx, hipMalloc((void **)&ctx->K->d_pk8, pk_plane_bytes(P.n, P.t)));
   // the temporary: bodies [n t][N], then the rows [n t][2][N]
   CHK(upload_through_temp(ctx, "packing key", {{bodies, body_words * 4}}, rows * 2 * kN * 4, [&](void *tmp) {
     uint32_t *d_tmp = (uint32_t *)tmp;
@@ -264,17 +253,14 @@ int tfhe_hip_load_packing_key(tfhe_hip_ctx *ctx, const uint8_t mask_seed[32], co
                        seed_key(mask_seed));
     if (const hipError_t e = hipGetLastError()) return e;
     hipLaunchKernelGGL(k_pack_planes<256>, dim3((unsigned)((chunks + 255) / 256)), dim3(256), 0, ctx->stream,
-                       d_tmp + body_words, ctx->K->d_pk8, P.n, P.t, chunks);
+                       d_tmp + body_words, k.d_pk8, P.n, P.t, chunks);
     return hipGetLastError();
   }));
-  ctx->K->pk_loaded = true;
+  commit_side_key(k.pk_loaded);
   return TFHE_HIP_OK;
 }
 
-int tfhe_hip_packing_key_is_loaded(tfhe_hip_ctx *ctx) {  // 0 / 1, never an error code (no device call is made)
-  if (!ctx) return 0;
-  return __atomic_load_n(&ctx->own.pk_loaded, __ATOMIC_ACQUIRE) ? 1 : 0;  // (no lock: see tfhe_hip_key_is_loaded)
-}
+int tfhe_hip_packing_key_is_loaded(tfhe_hip_ctx *ctx) { return flag_is_loaded(ctx, &KeyState::pk_loaded); }
 
 int tfhe_hip_batch_pack_tlwe(tfhe_hip_ctx *ctx, const uint32_t *in, size_t count, uint32_t *out) {
   if (!ctx) return TFHE_HIP_EINVAL;

@@ -29,10 +29,6 @@
 
 namespace tfhe {
 
-constexpr uint32_t kSeedDomainPkeSel = 0x504B45u;    // "PKE": selectors of public-key encryptions
-constexpr uint32_t kSeedDomainPkeNoise = 0x504B4Eu;  // "PKN": their noise
-constexpr uint32_t kSeedDomainRkeSel = 0x524B45u;    // "RKE": selectors of asymmetric re-encryption key rows
-constexpr uint32_t kSeedDomainRkeNoise = 0x524B4Eu;  // "RKN": their noise
 constexpr int kPkeNT = 8;                            // column tiles per wave: the LDS tile is 32 x 256 words
 constexpr int kPkeMaxSize = 8192;                    // |acc| <= 128 size <= 2^20; steps <= 256
 constexpr size_t kPkeChunkRows = (size_t)1 << 16;    // rows per pass: bounds the selector scratch (23 MiB at size 1400)
@@ -62,19 +58,10 @@ __global__ __launch_bounds__(WG) void k_pke_planes(const uint32_t *__restrict__ 
   r /= (size_t)S;
   const int ct = (int)(r % (size_t)T), p = (int)(r / (size_t)T);
   const int col = ct * 32 + (lane & 31), kb = lane >> 5;
-  uint32_t o[4];
-#pragma unroll
-  for (int q = 0; q < 4; ++q) {
-    uint32_t d = 0;
-#pragma unroll
-    for (int b = 0; b < 4; ++b) {
-      const int e = 32 * s + 16 * kb + 4 * q + b;
-      const uint32_t w = (e < size && col <= n) ? enc[(size_t)e * (size_t)(n + 1) + col] : 0u;
-      d |= ks_plane_byte(w, p) << (8 * b);
-    }
-    o[q] = d;
-  }
-  reinterpret_cast<uint4 *>(out)[idx] = make_uint4(o[0], o[1], o[2], o[3]);
+  reinterpret_cast<uint4 *>(out)[idx] = ks_plane_fragment(p, [=](int q, int b) {
+    const int e = 32 * s + 16 * kb + 4 * q + b;
+    return (e < size && col <= n) ? enc[(size_t)e * (size_t)(n + 1) + col] : 0u;
+  });
 }
 
 // One lane per (row, keystream block): blocks 0 .. nblk-1 of the selector stream give selector words 16 blk .. 16 blk + 15
@@ -112,14 +99,11 @@ __global__ __launch_bounds__(WG) void k_pke_selectors(ChaChaKey key, uint64_t fi
   } else {
     pl = plain[row];
   }
-  uint32_t w[16];
   if (blk == nblk) {
-    chacha20_block(key, 0u, (uint32_t)g, (uint32_t)(g >> 32), dom_noise, w);
-    double g0, g1;
-    gauss2(w, alpha, g0, g1);
-    addend[row] = pl + dev_f64_to_torus(g0);
+    addend[row] = pl + noise_sample(key, (uint32_t)g, (uint32_t)(g >> 32), dom_noise, alpha);
     return;
   }
+  uint32_t w[16];
   chacha20_block(key, (uint32_t)blk, (uint32_t)g, (uint32_t)(g >> 32), dom_sel, w);
 #pragma unroll
   for (int q = 0; q < 16; ++q) {
@@ -216,20 +200,6 @@ int need_public_key(tfhe_hip_ctx *ctx) {
   return TFHE_HIP_OK;
 }
 
-// rng_key, or 32 bytes of getrandom(2)
-int pke_generator_key(tfhe_hip_ctx *ctx, const uint8_t rng_key[32], ChaChaKey &k) {
-  if (rng_key) {
-    memcpy(k.k, rng_key, 32);
-    return TFHE_HIP_OK;
-  }
-  if (const int err = os_random((uint8_t *)k.k, sizeof(k.k))) return fail(ctx, TFHE_HIP_EHIP, os_random_text(err));
-  return TFHE_HIP_OK;
-}
-void pke_wipe(ChaChaKey &k) {
-  volatile uint32_t *wipe = k.k;
-  for (int i = 0; i < 8; ++i) wipe[i] = 0;
-}
-
 // Selectors and addends of `rows` rows into `sel`, then the contraction into out [rows][n+1], on stream s; the
 // selectors (whoever reads them can strip the masks) are zeroed behind the contraction.
 int pke_rows_launch(tfhe_hip_ctx *ctx, const ChaChaKey &k, uint64_t first_index, size_t rows, double alpha,
@@ -285,33 +255,20 @@ int tfhe_hip_load_public_key(tfhe_hip_ctx *ctx, const uint32_t *encryptions, siz
   if (size < 1 || size > (size_t)kPkeMaxSize)
     return fail(ctx, TFHE_HIP_EINVAL, "public key size must be in [1, 8192] (exact i32 accumulation)");
   const tfhe_hip_params &P = ctx->P;
-  // encryptions queued on the caller's streams may still read the planes this call overwrites
-  HIPCHK(ctx, hipDeviceSynchronize());
   KeyState &k = *ctx->K;
-  k.pke_loaded = false;
-  const size_t bytes = pke_plane_bytes(P.n, (int)size);
-  if (bytes > k.pke_cap) {
-    if (k.d_pke8) HIPCHK(ctx, hipFree(k.d_pke8));
-    k.d_pke8 = nullptr;
-    k.pke_cap = 0;
-    HIPCHK(ctx, hipMalloc((void **)&k.d_pke8, bytes));
-    k.pke_cap = bytes;
-  }
-  const size_t chunks = bytes / 16;
+  const size_t bytes = pke_plane_bytes(P.n, (int)size), chunks = bytes / 16;
+  CHK(begin_side_key(ctx, k.pke_loaded, k.d_pke8, k.pke_cap, bytes));
   CHK(upload_through_temp(ctx, "public key", {{encryptions, size * (size_t)(P.n + 1) * 4}}, 0, [&](void *d_enc) {
     hipLaunchKernelGGL(k_pke_planes<256>, dim3((unsigned)((chunks + 255) / 256)), dim3(256), 0, ctx->stream,
                        (const uint32_t *)d_enc, k.d_pke8, P.n, (int)size, chunks);
     return hipGetLastError();
   }));
   k.pke_size = (int)size;
-  k.pke_loaded = true;
+  commit_side_key(k.pke_loaded);
   return TFHE_HIP_OK;
 }
 
-int tfhe_hip_public_key_is_loaded(tfhe_hip_ctx *ctx) {  // 0 / 1, never an error code (no device call is made)
-  if (!ctx) return 0;
-  return __atomic_load_n(&ctx->own.pke_loaded, __ATOMIC_ACQUIRE) ? 1 : 0;  // (no lock: see tfhe_hip_key_is_loaded)
-}
+int tfhe_hip_public_key_is_loaded(tfhe_hip_ctx *ctx) { return flag_is_loaded(ctx, &KeyState::pke_loaded); }
 
 int tfhe_hip_batch_pk_encrypt(tfhe_hip_ctx *ctx, const uint32_t *plain, size_t count, double alpha,
                               const uint8_t rng_key[32], uint64_t first_index, uint32_t *out) {
@@ -320,12 +277,11 @@ int tfhe_hip_batch_pk_encrypt(tfhe_hip_ctx *ctx, const uint32_t *plain, size_t c
   CHK(need_public_key(ctx));
   if (const char *why = pke_refusal(plain, count, alpha, out)) return fail(ctx, TFHE_HIP_EINVAL, why);
   if (count == 0) return TFHE_HIP_OK;
-  ChaChaKey k;
-  CHK(pke_generator_key(ctx, rng_key, k));
+  GeneratorKey gk;
+  CHK(gk.fill(ctx, rng_key));
   const int rc = host_call(ctx, false, {{plain, count * 4, &ctx->a}}, out, tlwe_bytes(ctx, count), [&](const void *const *d, void *o) {
-    return pke_launch(ctx, k, first_index, u32(d[0]), count, alpha, (uint32_t *)o, ctx->stream);
+    return pke_launch(ctx, gk.k, first_index, u32(d[0]), count, alpha, (uint32_t *)o, ctx->stream);
   });
-  pke_wipe(k);
   // the plaintexts do not stay behind in the staging buffer (best effort: the call's status is rc)
   if (ctx->a.dev.p && ctx->a.dev.cap >= count * 4 && hipMemsetAsync(ctx->a.dev.p, 0, count * 4, ctx->stream) == hipSuccess)
     (void)hipStreamSynchronize(ctx->stream);
@@ -339,11 +295,9 @@ int tfhe_hip_batch_pk_encrypt_dev(tfhe_hip_ctx *ctx, const uint32_t *plain, size
   CHK(need_public_key(ctx));
   if (const char *why = pke_refusal(plain, count, alpha, out)) return fail(ctx, TFHE_HIP_EINVAL, why);
   if (count == 0) return TFHE_HIP_OK;
-  ChaChaKey k;
-  CHK(pke_generator_key(ctx, rng_key, k));
-  const int rc = pke_launch(ctx, k, first_index, plain, count, alpha, out, pick(ctx, stream));
-  pke_wipe(k);
-  return rc;
+  GeneratorKey gk;
+  CHK(gk.fill(ctx, rng_key));
+  return pke_launch(ctx, gk.k, first_index, plain, count, alpha, out, pick(ctx, stream));
 }
 
 int tfhe_hip_get_pk_encrypt_times(tfhe_hip_ctx *ctx, tfhe_hip_pk_encrypt_times *out) {
@@ -380,12 +334,8 @@ int tfhe_hip_gen_reenc_key_asymmetric(tfhe_hip_ctx *ctx, const uint32_t *key_fro
   if (P.n > kN) return fail(ctx, TFHE_HIP_EINVAL, "proxy re-encryption needs n <= N = 1024 (this parameter set's n is larger)");
   if (!(alpha >= 0.0)) return fail(ctx, TFHE_HIP_EINVAL, "negative noise parameter");
   CHK(need_public_key(ctx));
-  ChaChaKey k;
-  CHK(pke_generator_key(ctx, rng_key, k));
-  struct WipeKey {
-    ChaChaKey &k;
-    ~WipeKey() { pke_wipe(k); }
-  } wipe_key{k};
+  GeneratorKey gk;
+  CHK(gk.fill(ctx, rng_key));
   Wipe wipe{ctx};  // key_from rides in the staging buffer `a` and does not outlive the call on the device
   CHK(to_dev(ctx, ctx->a, key_from, (size_t)P.n * 4));
   const uint32_t *d_from = (const uint32_t *)ctx->a.dev.p;
@@ -398,7 +348,7 @@ int tfhe_hip_gen_reenc_key_asymmetric(tfhe_hip_ctx *ctx, const uint32_t *key_fro
   const size_t tmp_bytes = (key_words + pke_sel_words(rows, ctx->K->pke_size)) * 4;
   CHK(upload_through_temp(ctx, "re-encryption key generation", {}, tmp_bytes, [&](void *tmp) -> hipError_t {
     uint32_t *d_rows = (uint32_t *)tmp, *d_sel = d_rows + key_words;
-    if (pke_rows_launch(ctx, k, 0, rows, alpha, nullptr, d_from, d_sel, d_rows, ctx->stream) != TFHE_HIP_OK)
+    if (pke_rows_launch(ctx, gk.k, 0, rows, alpha, nullptr, d_from, d_sel, d_rows, ctx->stream) != TFHE_HIP_OK)
       return hipErrorLaunchFailure;
     hipLaunchKernelGGL(k_ksk_convert, dim3((unsigned)rows), dim3(256), 0, ctx->stream, (const uint32_t *)d_rows, ctx->K->d_ksk,
                        P.n, base, rows);

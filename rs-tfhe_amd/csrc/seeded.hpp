@@ -4,49 +4,15 @@
 // (uniform mask, body).  When the mask is a fixed position of a ChaCha20 keystream under a PUBLIC 32-byte seed S,
 // only the bodies travel; the expand kernels below regenerate the masks and write the engine layouts the existing
 // kernels read.  The format (nonces, word order, the q < l body rule of the BSK) is normative and documented in
-// include/tfhe_hip.h; keygen.hpp holds the ChaCha20 block function and the Gaussian sampler used here.
+// include/tfhe_hip.h; keygen.hpp holds the ChaCha20 block function, the stream table every nonce here is named in
+// (kStream*, kSeedDomain*), the seed derivation and the row helpers shared with the plain generator.
 //
 // Every kernel here is a template (on its workgroup size, or on l): template instantiations are emitted after the
-// library's other kernels, so these leave the code of every existing kernel byte-identical (labels included, which
-// kernel_isa.json records).
+// library's other kernels, so these leave the labels of the bootstrap kernels, which kernel_isa.json records, alone.
 #pragma once
 #include "keygen.hpp"
 
 namespace tfhe {
-
-constexpr uint32_t kSeedDomainKsk = 0x4B534Bu;   // "KSK"
-constexpr uint32_t kSeedDomainBsk = 0x42534Bu;   // "BSK"
-constexpr uint32_t kSeedDomainTlwe = 0x45574Cu;  // "EWL"
-constexpr uint32_t kSeedDomainSeed = 0x444553u;  // "DES"
-
-// S = words 0..7 of block 0 of the generator key's stream (0, 20, "DES"): a PRF output, so S reveals nothing of K.
-template <int WG>
-__global__ __launch_bounds__(WG) void k_derive_mask_seed(const ChaChaKey *__restrict__ key_p, ChaChaKey *__restrict__ seed) {
-  if (threadIdx.x != 0) return;
-  uint32_t w[16];
-  chacha20_block(*key_p, 0u, 0u, 20u, kSeedDomainSeed, w);
-#pragma unroll
-  for (int c = 0; c < 8; ++c) seed->k[c] = w[c];
-}
-
-// Mask polynomial of BSK row `row`: coefficient c is word c % 16 of block c / 16 under (row, 18, "BSK").  Lane l makes
-// block l (coefficients 16l..16l+15); the FFT wants lane l to hold l+64m and l+64m+512, so the blocks go through the
-// LDS (4 KB of the tile, which the caller's transforms reuse afterwards).  One wave per workgroup.
-__device__ __forceinline__ void seeded_bsk_mask(const ChaChaKey &seed, uint32_t row, uint32_t *s, int lane,
-                                                uint32_t (&a_lo)[8], uint32_t (&a_hi)[8]) {
-  uint32_t w[16];
-  chacha20_block(seed, (uint32_t)lane, row, 18u, kSeedDomainBsk, w);
-  uint4 *s4 = reinterpret_cast<uint4 *>(s) + lane * 4;
-#pragma unroll
-  for (int q = 0; q < 4; ++q) s4[q] = make_uint4(w[4 * q], w[4 * q + 1], w[4 * q + 2], w[4 * q + 3]);
-  __syncthreads();
-#pragma unroll
-  for (int m = 0; m < 8; ++m) {
-    a_lo[m] = s[lane + 64 * m];
-    a_hi[m] = s[lane + 64 * m + kN2];
-  }
-  __syncthreads();  // the tile is the transforms' next
-}
 
 // ---- key-switching key ------------------------------------------------------------------------------------------
 // Row r = base*t*i + base*j + k (k >= 1): mask word x < n is keystream word x of (r, 16, "KSK") under S; the body is
@@ -60,35 +26,15 @@ __global__ __launch_bounds__(WG) void k_gen_compressed_ksk(const uint32_t *__res
   static_assert(WG == 256, "the body's reduction is over four waves");
   __shared__ uint32_t s_part[4];
   const uint32_t row = blockIdx.x;
-  const int base = 1 << basebit;
-  const int k = row % base, j = (row / base) % t, i = row / (base * t);
   const int tid = threadIdx.x;
-  if (k == 0) {
+  if ((row & ((1u << basebit) - 1u)) == 0) {
     if (tid == 0) bodies[row] = 0u;
     return;
   }
-  uint32_t inner = 0;
-  for (int x16 = tid; x16 * 16 < n; x16 += WG) {
-    uint32_t w[16];
-    chacha20_block(seed, (uint32_t)x16, row, 16u, kSeedDomainKsk, w);
-#pragma unroll
-    for (int c = 0; c < 16; ++c) {
-      const int x = x16 * 16 + c;
-      if (x < n) inner += key_lv0[x] * w[c];
-    }
-  }
-  for (int off = 32; off > 0; off >>= 1) inner += __shfl_down(inner, off);
-  if ((tid & 63) == 0) s_part[tid >> 6] = inner;
-  __syncthreads();
-  if (tid == 0) {
-    const uint32_t total = s_part[0] + s_part[1] + s_part[2] + s_part[3];
-    uint32_t w[16];
-    chacha20_block(*key_p, 0u, row, 17u, kSeedDomainKsk, w);
-    double g0, g1;
-    gauss2(w, alpha, g0, g1);
-    const double p = (double)((uint32_t)k * key_lv1[i]) / (double)(1u << ((j + 1) * basebit));
-    bodies[row] = total + gaussian_torus(p, g0);
-  }
+  const uint32_t inner =
+      lwe_mask_walk<false, true>(seed, row, kStreamSeededKskMask, kSeedDomainKsk, n, tid, WG, nullptr, key_lv0);
+  const uint32_t body = ksk_body(inner, s_part, *key_p, row, kStreamSeededKskNoise, key_lv1, basebit, t, alpha);
+  if (tid == 0) bodies[row] = body;
 }
 
 // Engine layout of k_gen_ksk / k_ksk_convert: rows of ksk_row_words(n), zero padding, k = 0 rows all zero.
@@ -104,22 +50,14 @@ __global__ __launch_bounds__(WG) void k_expand_ksk(const uint32_t *__restrict__ 
     for (int x = tid; x < rw; x += WG) dst[x] = 0u;
     return;
   }
-  for (int x16 = tid; x16 * 16 < n; x16 += WG) {
-    uint32_t w[16];
-    chacha20_block(seed, (uint32_t)x16, row, 16u, kSeedDomainKsk, w);
-#pragma unroll
-    for (int c = 0; c < 16; ++c) {
-      const int x = x16 * 16 + c;
-      if (x < n) dst[x] = w[c];
-    }
-  }
+  lwe_mask_walk<true, false>(seed, row, kStreamSeededKskMask, kSeedDomainKsk, n, tid, WG, dst, nullptr);
   if (tid == 0) dst[n] = bodies[row];
   if (tid > 0 && n + tid < rw) dst[n + tid] = 0u;
 }
 
 // ---- bootstrapping key --------------------------------------------------------------------------------------------
-// Row r = i*2l + q of TRGSW(s0[i]), p = s0[i], g_d = f64_to_torus(Bg^-(d+1)), a from S (seeded_bsk_mask), e from
-// (r, 19, "BSK") under K in k_gen_bsk's word order:
+// Row r = i*2l + q of TRGSW(s0[i]), p = s0[i], g_d = f64_to_torus(Bg^-(d+1)), a from S (natural_mask over
+// (r, 18, "BSK")), e from (r, 19, "BSK") under K in k_gen_bsk's word order:
 //   q <  l: b = a (*) s1 + e - p*g_q*s1      (the reference's a[0] += p*g_q folded into the body: a stays the seed's)
 //   q >= l: b = a (*) s1 + e + p*g_{q-l}     (on coefficient 0, as k_gen_bsk)
 // computed as (a - p*g*[q < l]) (*) s1 through the FFT of k_gen_bsk (|coefficients| < 2^41: the rounding is exact).
@@ -138,51 +76,15 @@ __global__ __launch_bounds__(64) void k_gen_compressed_bsk(const uint32_t *__res
   Twiddles tw;
   tw.load(twt, reinterpret_cast<double2 *>(smem + kTileBytes), lane);
   uint32_t a_lo[8], a_hi[8], b_lo[8], b_hi[8];
-  seeded_bsk_mask(seed, row, reinterpret_cast<uint32_t *>(smem), lane, a_lo, a_hi);
-  const ChaChaKey key = *key_p;
-#pragma unroll
-  for (int h = 0; h < 2; ++h) {
-    uint32_t w[16];
-    chacha20_block(key, (uint32_t)(lane * 2 + h), row, 19u, kSeedDomainBsk, w);
-#pragma unroll
-    for (int m = 0; m < 4; ++m) {
-      double g0, g1;
-      gauss2(w + 4 * m, alpha, g0, g1);
-      b_lo[4 * h + m] = gaussian_torus(0.0, g0);
-      b_hi[4 * h + m] = gaussian_torus(0.0, g1);
-    }
-  }
-  const uint32_t p = key_lv0[i];
-  const uint32_t gadget = p * dev_f64_to_torus(exp2(-(double)(bgbit * (q % L + 1))));
+  natural_mask<false>(seed, row, kStreamSeededBskMask, kSeedDomainBsk, reinterpret_cast<uint32_t *>(smem), lane, nullptr, a_lo,
+                      a_hi);
+  row_noise(*key_p, row, kStreamSeededBskNoise, kSeedDomainBsk, alpha, lane, b_lo, b_hi);
+  const uint32_t gadget = key_lv0[i] * dev_f64_to_torus(exp2(-(double)(bgbit * (q % L + 1))));
   if (q < L && lane == 0) a_lo[0] -= gadget;
-  double re[8], im[8];
-#pragma unroll
-  for (int m = 0; m < 8; ++m) {
-    re[m] = (double)(int32_t)a_lo[m];
-    im[m] = (double)(int32_t)a_hi[m];
-  }
-  fft_forward(re, im, tw, tile, lane);
-#pragma unroll
-  for (int s = 0; s < 8; ++s) {
-    const double2 sp = s1_spec[s * 64 + lane];
-    const double pr = (re[s] * sp.x - im[s] * sp.y) * 0x1p-9;
-    const double pi = (re[s] * sp.y + im[s] * sp.x) * 0x1p-9;
-    re[s] = pr;
-    im[s] = pi;
-  }
-  fft_inverse(re, im, tw, tile, lane);
-#pragma unroll
-  for (int m = 0; m < 8; ++m) {
-    b_lo[m] += round_to_torus<false>(re[m]);
-    b_hi[m] += round_to_torus<false>(im[m]);
-  }
+  double are[8], aim[8];
+  add_ring_product(a_lo, a_hi, s1_spec, tw, tile, lane, are, aim, b_lo, b_hi);
   if (q >= L && lane == 0) b_lo[0] += gadget;
-  uint32_t *dst = bodies + (size_t)row * kN;
-#pragma unroll
-  for (int m = 0; m < 8; ++m) {
-    dst[lane + 64 * m] = b_lo[m];
-    dst[lane + 64 * m + kN2] = b_hi[m];
-  }
+  store_row(bodies + (size_t)row * kN, lane, b_lo, b_hi);
 }
 
 // Spectra of (a from S, b from `bodies`) in the engine layout of k_gen_bsk, scaled by 2 * key_scale(fast).
@@ -196,26 +98,16 @@ __global__ __launch_bounds__(WG) void k_expand_bsk(const uint32_t *__restrict__ 
   const uint32_t row = blockIdx.x;
   Twiddles tw;
   tw.load(twt, reinterpret_cast<double2 *>(smem + kTileBytes), lane);
-  uint32_t a_lo[8], a_hi[8];
-  seeded_bsk_mask(seed, row, reinterpret_cast<uint32_t *>(smem), lane, a_lo, a_hi);
+  uint32_t lo[8], hi[8];
+  natural_mask<false>(seed, row, kStreamSeededBskMask, kSeedDomainBsk, reinterpret_cast<uint32_t *>(smem), lane, nullptr, lo, hi);
   const double k2 = 2.0 * scale;
   double2 *dst = bsk_eng + (size_t)row * 2 * kN2;
   double re[8], im[8];
-#pragma unroll
-  for (int m = 0; m < 8; ++m) {
-    re[m] = (double)(int32_t)a_lo[m];
-    im[m] = (double)(int32_t)a_hi[m];
-  }
-  fft_forward(re, im, tw, tile, lane);
+  torus_spectrum(lo, hi, re, im, tw, tile, lane);
 #pragma unroll
   for (int s = 0; s < 8; ++s) dst[s * 64 + lane] = make_double2(re[s] * k2, im[s] * k2);
-  const uint32_t *src = bodies + (size_t)row * kN;
-#pragma unroll
-  for (int m = 0; m < 8; ++m) {
-    re[m] = (double)(int32_t)src[lane + 64 * m];
-    im[m] = (double)(int32_t)src[lane + 64 * m + kN2];
-  }
-  fft_forward(re, im, tw, tile, lane);
+  load_row(bodies + (size_t)row * kN, lane, lo, hi);
+  torus_spectrum(lo, hi, re, im, tw, tile, lane);
 #pragma unroll
   for (int s = 0; s < 8; ++s) dst[kN2 + s * 64 + lane] = make_double2(re[s] * k2, im[s] * k2);
 }
@@ -287,20 +179,14 @@ int gen_compressed_locked(tfhe_hip_ctx *ctx, const uint32_t *key_lv0, const uint
   const uint32_t *d_k0 = s.d_k0, *d_k1 = s.d_k1;
   const double2 *d_spec = s.d_spec;
   const ChaChaKey *d_rk = s.d_rk;
-  hipLaunchKernelGGL(k_derive_mask_seed<64>, dim3(1), dim3(64), 0, ctx->stream, d_rk, s.d_rk + 1);
-  HIPCHK(ctx, hipGetLastError());
   ChaChaKey seed;
-  HIPCHK(ctx, hipMemcpyAsync(&seed, s.d_rk + 1, sizeof(seed), hipMemcpyDeviceToHost, ctx->stream));
-  HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+  CHK(derive_public_seed<kStreamSeededSeed>(ctx, s, seed));
   // bodies: public, in ctx->out
   CHK(ensure(ctx, ctx->out.dev, (bsk_words + ksk_words) * 4));
   uint32_t *d_bb = (uint32_t *)ctx->out.dev.p, *d_kb = d_bb + bsk_words;
-  const dim3 bgrid((unsigned)(P.n * 2 * P.l));
-  switch (P.l) {
-    case 1: hipLaunchKernelGGL(k_gen_compressed_bsk<1>, bgrid, dim3(64), kStageLdsBytes, ctx->stream, d_k0, d_spec, ctx->d_tw, d_bb, P.bgbit, alpha_bsk, d_rk, seed); break;
-    case 2: hipLaunchKernelGGL(k_gen_compressed_bsk<2>, bgrid, dim3(64), kStageLdsBytes, ctx->stream, d_k0, d_spec, ctx->d_tw, d_bb, P.bgbit, alpha_bsk, d_rk, seed); break;
-    default: hipLaunchKernelGGL(k_gen_compressed_bsk<3>, bgrid, dim3(64), kStageLdsBytes, ctx->stream, d_k0, d_spec, ctx->d_tw, d_bb, P.bgbit, alpha_bsk, d_rk, seed); break;
-  }
+  const auto gen_bsk = kernel_inst(ctx, false, [](auto inst) { return k_gen_compressed_bsk<decltype(inst)::L>; });
+  hipLaunchKernelGGL(gen_bsk, dim3((unsigned)(P.n * 2 * P.l)), dim3(64), kStageLdsBytes, ctx->stream, d_k0, d_spec, ctx->d_tw,
+                     d_bb, P.bgbit, alpha_bsk, d_rk, seed);
   HIPCHK(ctx, hipGetLastError());
   hipLaunchKernelGGL(k_gen_compressed_ksk<256>, dim3((unsigned)ksk_words), dim3(256), 0, ctx->stream, d_k0, d_k1, d_kb, P.n,
                      P.basebit, P.t, alpha_ksk, d_rk, seed);
@@ -325,17 +211,10 @@ int tfhe_hip_gen_compressed_cloud_key(tfhe_hip_ctx *ctx, const uint32_t *key_lv0
   if (!key_lv0 || !key_lv1 || !mask_seed || !bsk_bodies || !ksk_bodies || !decomp_offset)
     return fail(ctx, TFHE_HIP_EINVAL, "null pointer");
   if (!(alpha_ksk >= 0.0) || !(alpha_bsk >= 0.0)) return fail(ctx, TFHE_HIP_EINVAL, "negative noise parameter");
-  ChaChaKey k;
-  if (rng_key) {
-    memcpy(k.k, rng_key, 32);
-  } else if (const int err = os_random((uint8_t *)k.k, sizeof(k.k))) {
-    return fail(ctx, TFHE_HIP_EHIP, os_random_text(err));
-  }
-  const int rc = gen_compressed_locked(ctx, key_lv0, key_lv1, alpha_ksk, alpha_bsk, k, mask_seed, bsk_bodies, ksk_bodies,
-                                       decomp_offset);
-  volatile uint32_t *wipe = k.k;
-  for (int i = 0; i < 8; ++i) wipe[i] = 0;
-  return rc;
+  GeneratorKey gk;
+  CHK(gk.fill(ctx, rng_key));
+  return gen_compressed_locked(ctx, key_lv0, key_lv1, alpha_ksk, alpha_bsk, gk.k, mask_seed, bsk_bodies, ksk_bodies,
+                               decomp_offset);
 }
 
 int tfhe_hip_load_compressed_cloud_key(tfhe_hip_ctx *ctx, const uint8_t mask_seed[32], const uint32_t *bsk_bodies,

@@ -158,16 +158,19 @@ struct KeyState {
   uint32_t *d_ksk = nullptr;
   unsigned char *d_ksk8 = nullptr;  // base-4 sets: the key as signed byte planes in MFMA fragment order (k_ksk_planes)
   uint32_t *d_testvec = nullptr;
-  unsigned char *d_pk8 = nullptr;  // the packing key as byte planes (packing.hpp): beside, not part of, the cloud key
-  bool pk_loaded = false;          // (a cloud-key load or change leaves it; freeing the key view frees it)
-  unsigned char *d_pke8 = nullptr;  // the public key as byte planes (pk_encrypt.hpp), with the packing key's lifetime rules
+  // the side keys, as byte planes: beside, not part of, the cloud key (a cloud-key load or change leaves them; freeing
+  // the key view frees them)
+  unsigned char *d_pk8 = nullptr;   // the packing key (packing.hpp)
+  size_t pk_cap = 0;                // bytes allocated at d_pk8
+  bool pk_loaded = false;
+  unsigned char *d_pke8 = nullptr;  // the public key (pk_encrypt.hpp)
   size_t pke_cap = 0;               // bytes allocated at d_pke8
   int pke_size = 0;                 // encryptions of zero in the loaded public key
-  bool pke_loaded = false;          // tfhe_hip_load_public_key's alone
+  bool pke_loaded = false;
   uint32_t offset = 0;
   // The flags are written in key_change.hpp only: begin_key_change clears both, commit_cloud_key sets key_loaded (and
-  // clears reenc_loaded), commit_reenc_key sets reenc_loaded.  pk_loaded is tfhe_hip_load_packing_key's and
-  // tfhe_hip_gen_packing_key's alone.
+  // clears reenc_loaded), commit_reenc_key sets reenc_loaded; begin_side_key clears pk_loaded or pke_loaded and
+  // commit_side_key sets it.
   bool key_loaded = false;
   bool reenc_loaded = false;  // d_ksk (+ d_ksk8) hold a proxy re-encryption key (proxy_reenc.rs:224-233) instead of a cloud key's
 };
@@ -1471,14 +1474,7 @@ int tfhe_hip_key_create(tfhe_hip_ctx *ctx, tfhe_hip_ctx **out) {
 
 tfhe_hip_ctx *tfhe_hip_key_parent(tfhe_hip_ctx *key) { return key ? (key->parent ? key->parent : key) : nullptr; }
 
-int tfhe_hip_key_is_loaded(tfhe_hip_ctx *ctx) {
-  if (!ctx) return 0;
-  // No lock: the host mirrors ask this before EVERY call (is the view's key resident yet?), and the context's mutex may
-  // be held for the length of a 65,536-ciphertext host call -- a one-gate call on another thread would wait 330 ms just to
-  // learn what it already knows.  The flag is set last by the calls that load a key and cleared first by those that
-  // change one; a caller that races its own key load is the caller's to order (as for any call under that key).
-  return __atomic_load_n(&ctx->own.key_loaded, __ATOMIC_ACQUIRE) ? 1 : 0;
-}
+int tfhe_hip_key_is_loaded(tfhe_hip_ctx *ctx) { return flag_is_loaded(ctx, &KeyState::key_loaded); }
 
 int tfhe_hip_load_cloud_key(tfhe_hip_ctx *ctx, const double *bsk, const uint32_t *ksk,
                             uint32_t decomp_offset, const uint32_t *testvec) {
@@ -1514,12 +1510,9 @@ int gen_cloud_key_locked(tfhe_hip_ctx *ctx, const uint32_t *key_lv0, const uint3
   const tfhe_hip_params &P = ctx->P;
   StagedSecrets s{{ctx}};  // (wiped on every exit path)
   CHK(stage_secrets(ctx, key_lv0, key_lv1, rk, sizeof(ChaChaKey), s));
-  const dim3 bgrid((unsigned)(P.n * 2 * P.l));
-  switch (P.l) {
-    case 1: hipLaunchKernelGGL(k_gen_bsk<1>, bgrid, dim3(64), kStageLdsBytes, ctx->stream, s.d_k0, s.d_spec, ctx->d_tw, ctx->K->d_bsk, P.bgbit, alpha_bsk, s.d_rk, key_scale(ctx->dispatch.fast_round)); break;
-    case 2: hipLaunchKernelGGL(k_gen_bsk<2>, bgrid, dim3(64), kStageLdsBytes, ctx->stream, s.d_k0, s.d_spec, ctx->d_tw, ctx->K->d_bsk, P.bgbit, alpha_bsk, s.d_rk, key_scale(ctx->dispatch.fast_round)); break;
-    default: hipLaunchKernelGGL(k_gen_bsk<3>, bgrid, dim3(64), kStageLdsBytes, ctx->stream, s.d_k0, s.d_spec, ctx->d_tw, ctx->K->d_bsk, P.bgbit, alpha_bsk, s.d_rk, key_scale(ctx->dispatch.fast_round)); break;
-  }
+  const auto gen_bsk = kernel_inst(ctx, false, [](auto inst) { return k_gen_bsk<decltype(inst)::L>; });
+  hipLaunchKernelGGL(gen_bsk, dim3((unsigned)(P.n * 2 * P.l)), dim3(64), kStageLdsBytes, ctx->stream, s.d_k0, s.d_spec,
+                     ctx->d_tw, ctx->K->d_bsk, P.bgbit, alpha_bsk, s.d_rk, key_scale(ctx->dispatch.fast_round));
   HIPCHK(ctx, hipGetLastError());
   hipLaunchKernelGGL(k_gen_ksk, dim3((unsigned)ksk_rows(P)), dim3(256), 0, ctx->stream, s.d_k0, s.d_k1,
                      ctx->K->d_ksk, P.n, P.basebit, P.t, alpha_ksk, s.d_rk);
@@ -1558,27 +1551,18 @@ int tfhe_hip_gen_cloud_key_with_key(tfhe_hip_ctx *ctx, const uint32_t *key_lv0, 
   if (!ctx) return TFHE_HIP_EINVAL;
   ENTER(ctx);
   if (!rng_key) return fail(ctx, TFHE_HIP_EINVAL, "null generator key");
-  ChaChaKey k;
-  memcpy(k.k, rng_key, 32);
-  const int rc = gen_cloud_key_locked(ctx, key_lv0, key_lv1, alpha_ksk, alpha_bsk, k);
-  volatile uint32_t *wipe = k.k;
-  for (int i = 0; i < 8; ++i) wipe[i] = 0;
-  return rc;
+  GeneratorKey gk;
+  CHK(gk.fill(ctx, rng_key));
+  return gen_cloud_key_locked(ctx, key_lv0, key_lv1, alpha_ksk, alpha_bsk, gk.k);
 }
 
 int tfhe_hip_gen_cloud_key_secure(tfhe_hip_ctx *ctx, const uint32_t *key_lv0, const uint32_t *key_lv1,
                                   double alpha_ksk, double alpha_bsk) {
   if (!ctx) return TFHE_HIP_EINVAL;
-  uint8_t buf[32];
-  if (const int err = os_random(buf, sizeof(buf))) {
-    tfhe_hip_ctx *base = ctx->parent ? ctx->parent : ctx;
-    std::lock_guard<FairMutex> lk(base->mu);
-    return fail(base, TFHE_HIP_EHIP, os_random_text(err));
-  }
-  const int rc = tfhe_hip_gen_cloud_key_with_key(ctx, key_lv0, key_lv1, alpha_ksk, alpha_bsk, buf);
-  volatile uint8_t *wipe = buf;
-  for (size_t i = 0; i < sizeof(buf); ++i) wipe[i] = 0;
-  return rc;
+  ENTER(ctx);
+  GeneratorKey gk;
+  CHK(gk.fill(ctx, nullptr));  // (a failure is reported on the base context)
+  return gen_cloud_key_locked(ctx, key_lv0, key_lv1, alpha_ksk, alpha_bsk, gk.k);
 }
 
 
@@ -2034,10 +2018,7 @@ int tfhe_hip_load_reenc_key(tfhe_hip_ctx *ctx, const uint32_t *key) {
   return commit_reenc_key(ctx);
 }
 
-int tfhe_hip_reenc_key_is_loaded(tfhe_hip_ctx *ctx) {  // 0 / 1, never an error code (no device call is made)
-  if (!ctx) return 0;
-  return __atomic_load_n(&ctx->own.reenc_loaded, __ATOMIC_ACQUIRE) ? 1 : 0;  // (no lock: see tfhe_hip_key_is_loaded)
-}
+int tfhe_hip_reenc_key_is_loaded(tfhe_hip_ctx *ctx) { return flag_is_loaded(ctx, &KeyState::reenc_loaded); }
 
 int tfhe_hip_batch_reencrypt_dev(tfhe_hip_ctx *ctx, const uint32_t *in, uint32_t *out, size_t count, void *stream) {
   if (!ctx) return TFHE_HIP_EINVAL;
