@@ -718,8 +718,8 @@ int tfhe_hip_get_key_switch_clock_sample(tfhe_hip_ctx *ctx, tfhe_hip_clock_sampl
  *                                      devices are distinct, 2 also for a pool of one (plumbing test)
  *   TFHE_HIP_POOL_PINNED_STAGING = 0 | 1   pools: stage pageable operands through per-member pinned arenas
  *                                      (default: 1 for pools of several members)
- * Anything else (crossover counts, chunk counts, ring depths) is compiled in; overrides for those exist only in
- * experiment builds (-DTFHE_EXPERIMENT, profiles/exp/build_variants.sh) and are not part of this interface. */
+ * Anything else (crossover counts, chunk counts, ring depths) is compiled in: constants of the kernels and of the
+ * dispatch, with no override. */
 int tfhe_hip_describe_dispatch(tfhe_hip_ctx *ctx, size_t count, char *buf, size_t buflen);
 
 /* How this context's blind-rotation kernels round the external product (KlemsaProcessor::fft's `round() as i64 as u32`,

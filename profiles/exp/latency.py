@@ -67,37 +67,5 @@ def main():
         print(json.dumps(rows[-1]), flush=True)
 
 
-def stamps(params="SECURITY_128_BIT"):
-    """With a -DTFHE_EXPERIMENT -DTFHE_LAT_STAMPS build (TFHE_HIP_LIB): cycles between the phase stamps of step n/2."""
-    import ctypes as C
-
-    import numpy as np
-    import torch
-
-    import rs_tfhe_amd as R
-
-    P = R.params.PARAM_SETS[params]
-    sk = R.SecretKey.new(P, seed=2024)
-    eng = R.Engine(P, 0)
-    eng.gen_cloud_key(sk.key_lv0, sk.key_lv1, seed=2025)
-    ca, cb = sk.encrypt_bool([True], seed=1), sk.encrypt_bool([False], seed=2)
-    eng.batch_gate(R.engine.NAND, ca, cb)
-    eng.set_profiling(True)
-    eng.batch_gate(R.engine.NAND, ca, cb)
-    buf = (C.c_uint64 * 128)()
-    fn = eng._lib.tfhe_hip_experiment_diag
-    fn.argtypes, fn.restype = [C.c_void_p, C.c_void_p, C.c_size_t], C.c_int
-    assert fn(eng._ctx, buf, 128) == 0
-    w = np.array(buf[:], dtype=np.uint64)
-    names = ["start", "digits", "fwd_fft", "products+keyloads", "barrier1", "partial_sum", "inv_fft", "acc_update", "barrier2"]
-    for wave in range(2 * P.l):
-        st = w[8 + wave * 16: 8 + wave * 16 + 9].astype(np.int64)
-        d = {names[i]: int(st[i] - st[i - 1]) for i in range(1, 9) if st[i] and st[i - 1]}
-        print(json.dumps({"wave": wave, "step_total": int(st[8] - st[0]) if st[8] and st[0] else None, **d}), flush=True)
-
-
 if __name__ == "__main__":
-    if "--stamps" in sys.argv:
-        stamps()
-        sys.exit(0)
     main()

@@ -53,8 +53,8 @@ if __name__ == "__main__":
         child(sys.argv[2])
     else:
         mode = "time" if "--time" in sys.argv else "bits"
-        for name, env in (("pair kernel everywhere", {"TFHE_HIP_PAIR_LO": "0", "TFHE_HIP_PAIR_MAX": "1000000", "TFHE_HIP_WIDE_MAX": "0"}),
+        for name, env in (("pair kernel everywhere", {"TFHE_HIP_BR_KERNEL": "pair"}),
                           ("shipped dispatch", {}),
-                          ("no pair kernel", {"TFHE_HIP_PAIR_MAX": "0"})):
+                          ("batch kernel everywhere", {"TFHE_HIP_BR_KERNEL": "batch"})):
             print("#", name, flush=True)
             subprocess.run([sys.executable, os.path.abspath(__file__), "--child", mode], env=dict(os.environ, **env))

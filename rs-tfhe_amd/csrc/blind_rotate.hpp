@@ -38,14 +38,7 @@ __device__ __forceinline__ uint32_t rot_read(const P *p, int j, int k) {
 using f64x2 = __attribute__((ext_vector_type(2))) double;
 using u32x4 = __attribute__((ext_vector_type(4))) unsigned int;
 
-// (TFHE_ABL_NOKEY: timing-only experiment switch, see experiment.hpp -- 0 in every product build)
 __device__ __forceinline__ f64x2 ldkey(__amdgpu_buffer_rsrc_t rsrc, uint32_t lane_off, uint32_t soff) {
-  if (TFHE_ABL_NOKEY) {
-    f64x2 r;
-    r.x = (double)(lane_off + soff);
-    r.y = (double)(lane_off ^ soff);
-    return r;
-  }
   u32x4 v = __builtin_amdgcn_raw_buffer_load_b128(rsrc, (int)lane_off, (int)soff, 0);
   return __builtin_bit_cast(f64x2, v);
 }
@@ -60,26 +53,6 @@ __device__ __forceinline__ f64x2 ldkey(__amdgpu_buffer_rsrc_t rsrc, uint32_t lan
 //      in the forward-FFT bin order, ready for fft_inverse.  INIT0: the first row
 //      WRITES the accumulators (no zero fill, no add).
 //      (decomposition trgsw.rs:144-171, batch_ifft + fma_in_fd_1024 trgsw.rs:99-106)
-// How many of the 8 a-half / b-half key loads of a row are issued before the forward FFT.
-#ifndef TFHE_PREFETCH_A
-#define TFHE_PREFETCH_A 8
-#endif
-#ifndef TFHE_PREFETCH_B
-#define TFHE_PREFETCH_B 4
-#endif
-#ifndef TFHE_L1_PA  // cap on TFHE_PREFETCH_A at L == 1 (a whole a-half in flight spilled there in round 2)
-#define TFHE_L1_PA 7
-#endif
-// 1 = the inverse-pass-3 twiddles (20 VGPRs) are re-read from the cache-resident table before the inverse
-// transforms of each CMUX step instead of living in registers across the forward phase (measured: 432 vs 469 ms
-// on the round-2 kernel before the workgroup change, profiles/exp/logs/r2a_ab_fft_v2_and_ablations.log)
-#ifndef TFHE_RELOAD_I3
-#define TFHE_RELOAD_I3 1
-#endif
-// 1 = the two inverse transforms of a CMUX step are interleaved through the one tile (fft_inverse2)
-#ifndef TFHE_INV_PAIR
-#define TFHE_INV_PAIR 1
-#endif
 
 // Signed bit-field extract (v_bfe_i32).  Written as inline asm on purpose: with
 // __builtin_amdgcn_sbfe and a run-time width, hipcc (ROCm 7.2 / clang 22) turns the following
@@ -91,34 +64,17 @@ __device__ __forceinline__ int32_t sbfe(uint32_t src, int shift, int width) {
   return d;
 }
 
-// Waves per workgroup of the batch kernel (each wave still owns one ciphertext and its own LDS regions) and
-// how tightly a workgroup's waves are held together: 0 = free-running, 1 = one barrier per CMUX step,
-// 2 = per polynomial half, 3 = per digit row.  Waves that walk the key together fetch each 1-KiB key slice
-// within a few hundred cycles of each other, so all but the first are served by the CU's vector L1 instead
-// of the L2 -- the L2 -> L1 key stream (68.8 MB per ciphertext) is what holds the shader clock down.
-#ifndef TFHE_WG_WAVES
-#define TFHE_WG_WAVES 4
-#endif
-#ifndef TFHE_WG_SYNC
-#define TFHE_WG_SYNC 1
-#endif
-template <int LEVEL>
-__device__ __forceinline__ void wg_sync() {
-  if (TFHE_WG_WAVES > 1 && TFHE_WG_SYNC >= LEVEL) __builtin_amdgcn_s_barrier();
-}
+// Waves per workgroup of the batch kernel (each wave still owns one ciphertext and its own LDS regions).  A
+// workgroup's waves are held together by one barrier per CMUX step: waves that walk the key together fetch each
+// 1-KiB key slice within a few hundred cycles of each other, so all but the first are served by the CU's vector L1
+// instead of the L2 -- the L2 -> L1 key stream (68.8 MB per ciphertext) is what holds the shader clock down.
+constexpr int kBrWaves = 4;
 
-// acc[j] += v in LDS.  1 (default): one ds_add_u32 without return -- the add happens in the LDS, nothing travels
-// to the registers and back (it was ds_read_b32 + v_add_u32 + ds_write_b32); a wave's LDS operations execute in
-// order, so the next step's reads see it.  0: the read-modify-write through registers.
-#ifndef TFHE_ACC_LDS_ADD
-#define TFHE_ACC_LDS_ADD 1
-#endif
+// acc[j] += v in LDS: one ds_add_u32 without return -- the add happens in the LDS, nothing travels to the registers
+// and back (it was ds_read_b32 + v_add_u32 + ds_write_b32); a wave's LDS operations execute in order, so the next
+// step's reads see it.
 __device__ __forceinline__ void acc_add(uint32_t *p, uint32_t v) {
-#if TFHE_ACC_LDS_ADD
   __hip_atomic_fetch_add(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-#else
-  *p += v;
-#endif
 }
 
 // f (+)= x * v, complex, as four fused multiply-adds (fma_in_fd_1024, trgsw.rs:118-142; the 0.5 of the
@@ -145,15 +101,15 @@ __device__ __forceinline__ void external_product_row(int r, int shift, const uin
                                                      int lane, int bgbit, double (&fa_re)[8], double (&fa_im)[8],
                                                      double (&fb_re)[8], double (&fb_im)[8]) {
   const uint32_t lane_off = (uint32_t)lane * 16u;
-  wg_sync<3>();
   // key row r: 2 x 8 coalesced 16-byte loads per lane off one buffer descriptor (lane
   // offset in a VGPR, row offset in an SGPR: no per-lane address arithmetic), issued
   // ahead of the FFT they are consumed after, so their latency hides under it.
   const uint32_t row_off = bsk_i_off + (uint32_t)r * (2u * kN2 * 16u);
   f64x2 va[8], vb[8];
-  // with a single digit row per half the schedule gets tighter: a whole a-half in flight spills there
-  constexpr int PA = (L == 1 && TFHE_PREFETCH_A > TFHE_L1_PA) ? TFHE_L1_PA : TFHE_PREFETCH_A;
-  constexpr int PB = TFHE_PREFETCH_B;
+  // How many of the 8 a-half / b-half key loads of the row are issued before the forward FFT.  With a single digit
+  // row per half the schedule gets tighter: a whole a-half in flight spilled there in round 2
+  constexpr int PA = L == 1 ? 7 : 8;
+  constexpr int PB = 4;
 #pragma unroll
   for (int s = 0; s < PA; ++s) va[s] = ldkey(bsk_rsrc, lane_off, row_off + (uint32_t)s * 1024u);
 #pragma unroll
@@ -194,7 +150,6 @@ __device__ __forceinline__ void external_product_half(int half_sel, const uint32
     w_lo[m] = t_lo[m] ^ signmask;
     w_hi[m] = t_hi[m] ^ signmask;
   }
-  if (TFHE_WG_SYNC == 2) wg_sync<2>();
   external_product_row<L, INIT0>(half_sel * L, 32 - bgbit, w_lo, w_hi, bsk_rsrc, bsk_i_off, tw, tile, lane, bgbit,
                                  fa_re, fa_im, fb_re, fb_im);
   // The remaining rows stay a LOOP: with the body duplicated (or, at L = 2, the one-trip loop flattened)
@@ -266,7 +221,6 @@ constexpr uint32_t kGateCopy = kGateCount - 1;  // the last row; what a code out
 // pass-2 twiddle table for the whole workgroup (every wave stores the same 64 entries).  Two workgroups share a
 // CU's 160 KiB up to n = 1183, i.e. for every parameter set (n <= 1160).
 constexpr int kAccBytes = 2 * kN * 4;
-constexpr int kBrWaves = TFHE_WG_WAVES;  // waves (= ciphertexts) per workgroup of k_blind_rotate
 __host__ __device__ __forceinline__ size_t blind_rotate_wave_lds_bytes(int n) {
   return ((size_t)kTileBytes + kAccBytes + (size_t)n * 2 + 15) & ~(size_t)15;
 }
@@ -427,7 +381,7 @@ __device__ __forceinline__ void blind_rotate_batch(BlindRotateArgs A) {
   for (int i = 0; i < L; ++i) signmask |= 1u << (32 - i * A.bgbit - 1);
 #pragma unroll 1
   for (int i = 0; i < n; ++i) {
-    wg_sync<1>();  // (a barrier only every 2nd / 4th / 16th step: 722 / 713 / 698 M cycles and 331.9 / 332.1 / 333.4 ms vs 331.7)
+    __builtin_amdgcn_s_barrier();  // holds the workgroup's waves together (a barrier only every 2nd / 4th / 16th step: 722 / 713 / 698 M cycles and 331.9 / 332.1 / 333.4 ms vs 331.7)
     const int k = s_abar[i];
     double fa_re[8], fa_im[8], fb_re[8], fb_im[8];  // written by the first row of the a half
     // cmux: tmp = in2 - in1 = X^k*acc - acc (trgsw.rs:183-186), + decomposition offset; the a
@@ -455,14 +409,14 @@ __device__ __forceinline__ void blind_rotate_batch(BlindRotateArgs A) {
       external_product_half<L, false>(1, t_lo, t_hi, bsk_rsrc, (uint32_t)i * per_i_bytes, tw, tile, lane, A.bgbit,
                                       signmask, fa_re, fa_im, fb_re, fb_im);
     }
-#if TFHE_RELOAD_I3
+    // The inverse-pass-3 twiddles (20 VGPRs) are re-read from the cache-resident table before the inverse transforms
+    // of each step instead of living in registers across the forward phase (measured: 432 vs 469 ms on the round-2
+    // kernel before the workgroup change, profiles/exp/logs/r2a_ab_fft_v2_and_ablations.log)
     {
       int z = 0;
       asm volatile("" : "+v"(z));  // opaque 0: keeps the reload inside the loop (see Twiddles::reload_i3)
       tw.reload_i3(A.tw, lane, z);
     }
-#endif
-#if TFHE_INV_PAIR
     fft_inverse2(fa_re, fa_im, fb_re, fb_im, tw, tile, lane);
 #pragma unroll
     for (int m = 0; m < 8; ++m) {  // res = ext + in1 (trgsw.rs:189-193)
@@ -472,22 +426,6 @@ __device__ __forceinline__ void blind_rotate_batch(BlindRotateArgs A) {
       acc_add(&acc[kN + j], round_product<FAST>(fb_re[m]));
       acc_add(&acc[kN + j + kN2], round_product<FAST>(fb_im[m]));
     }
-#else
-    fft_inverse(fa_re, fa_im, tw, tile, lane);
-#pragma unroll
-    for (int m = 0; m < 8; ++m) {  // res = ext + in1 (trgsw.rs:189-193)
-      const int j = lane + 64 * m;
-      acc[j] += round_product<FAST>(fa_re[m]);
-      acc[j + kN2] += round_product<FAST>(fa_im[m]);
-    }
-    fft_inverse(fb_re, fb_im, tw, tile, lane);
-#pragma unroll
-    for (int m = 0; m < 8; ++m) {
-      const int j = lane + 64 * m;
-      acc[kN + j] += round_product<FAST>(fb_re[m]);
-      acc[kN + j + kN2] += round_product<FAST>(fb_im[m]);
-    }
-#endif
     wave_lds_sync();  // the next step re-reads acc at rotated (other lanes') positions
   }
 

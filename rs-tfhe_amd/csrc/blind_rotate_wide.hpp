@@ -1,9 +1,10 @@
 // blind_rotate_wide.hpp -- the latency kernel, second form: one WORKGROUP OF EIGHT WAVES per ciphertext.
 //
-// k_blind_rotate_wide (blind_rotate.hpp) gives decomposition row r to wave r: digits, forward FFT, both products
-// with its key row, 16 KiB of partial products through LDS, then waves 0 / 1 sum the 2l partials and run the inverse
-// transforms.  Measured (profiles/exp/latency_ablation.py): 10,300 cycles per CMUX step, of which
-// 2,220 are that exchange (the CU's two 39-B/cycle LDS store paths) and 1,950 the rotated reads + digit extraction that the l
+// The first form (k_blind_rotate_wide, no longer in the tree: profiles/exp/CLOSED.md) gave decomposition row r to wave
+// r: digits, forward FFT, both products with its key row, 16 KiB of partial products through LDS, then waves 0 / 1
+// summed the 2l partials and ran the inverse transforms.  Measured (profiles/exp/logs/r3f_latency_before.log,
+// DESIGN.md 4.3): 10,300 cycles per CMUX step, of which
+// 2,220 were that exchange (the CU's two 39-B/cycle LDS store paths) and 1,950 the rotated reads + digit extraction that the l
 // waves of a half all repeat.  This form removes both repetitions:
 //   P0  the digit preparation is SHARED: four waves per half (its l forward waves + 4 - l of the waves without a row)
 //       each compute w = ((X^k acc - acc) + offset) ^ signmask (trgsw.rs:183-186, 144-171) for a quarter of the
@@ -98,9 +99,9 @@ __device__ __forceinline__ void blind_rotate_wide2(BlindRotateArgs A) {
     // 900-1,150 cycles per step (measured, also with the loads hitting L1).  So the six waves that idle through P3
     // issue theirs after that barrier, and waves 0 / 1 after their inverse transform, when the path is empty again.
     auto load_next_keys = [&]() {
-      const uint32_t nxt = ((TFHE_ABL_LAT & 256) ? (uint32_t)(i & 1) : (uint32_t)(i + 1 < n ? i + 1 : i)) * per_i_bytes + my_slot;
+      const uint32_t nxt = (uint32_t)(i + 1 < n ? i + 1 : i) * per_i_bytes + my_slot;
 #pragma unroll
-      for (int r = 0; r < ((TFHE_ABL_LAT & 64) ? 0 : W); ++r) {
+      for (int r = 0; r < W; ++r) {
         va[r] = ldkey(bsk_rsrc, lane_off, nxt + (uint32_t)r * (2u * kN2 * 16u));
         vb[r] = ldkey(bsk_rsrc, lane_off, nxt + (uint32_t)r * (2u * kN2 * 16u) + (uint32_t)(kN2 * 16));
       }
@@ -110,12 +111,10 @@ __device__ __forceinline__ void blind_rotate_wide2(BlindRotateArgs A) {
       // P0: my quarter of w = (X^k acc - acc + offset) ^ signmask for my half (trgsw.rs:183-186 + the digit offset)
       const uint32_t *p = acc + prep_half * kN;
       uint32_t *wb = wbuf + prep_half * kN;
-      if (!(TFHE_ABL_LAT & 128)) {
 #pragma unroll
-        for (int mm = 0; mm < 4; ++mm) {
-          const int j = lane + 64 * (4 * prep_idx + mm);
-          wb[j] = (rot_read(p, j, k) - p[j] + offset) ^ signmask;
-        }
+      for (int mm = 0; mm < 4; ++mm) {
+        const int j = lane + 64 * (4 * prep_idx + mm);
+        wb[j] = (rot_read(p, j, k) - p[j] + offset) ^ signmask;
       }
     }
     lds_barrier();
@@ -127,13 +126,13 @@ __device__ __forceinline__ void blind_rotate_wide2(BlindRotateArgs A) {
         im[m] = (double)sbfe(wb[lane + 64 * m + kN2], shift, bgbit);
       }
       // P1: forward transform; the spectrum stays in this wave's tile, slot-major: [s][lane]
-      if (!(TFHE_ABL_LAT & 8)) fft_forward(re, im, tw, mytile, lane);
+      fft_forward(re, im, tw, mytile, lane);
       wave_lds_sync();  // the transform's last tile reads are done
 #pragma unroll
       for (int s = 0; s < 8; ++s) mytile[s * 64 + lane] = make_double2(re[s], im[s]);
     }
     lds_barrier();
-    if (!(TFHE_ABL_LAT & 32)) {
+    {
       // P2: slot `wave` of fa = sum_r spectrum_r * Ka_r, fb = sum_r spectrum_r * Kb_r, rows in the batch kernel's order
       double far, fai, fbr, fbi;
 #pragma unroll
@@ -159,7 +158,7 @@ __device__ __forceinline__ void blind_rotate_wide2(BlindRotateArgs A) {
         f_re[s] = v.x;
         f_im[s] = v.y;
       }
-      if (!(TFHE_ABL_LAT & 16)) fft_inverse(f_re, f_im, tw, tiles + (size_t)wave * kTileCplx, lane);
+      fft_inverse(f_re, f_im, tw, tiles + (size_t)wave * kTileCplx, lane);
       __builtin_amdgcn_sched_barrier(0);
       load_next_keys();
       uint32_t *q = acc + wave * kN;
@@ -288,7 +287,7 @@ __global__ __launch_bounds__(64 * kPairWaves, 1) void k_blind_rotate_pair(BlindR
       re[m] = (double)sbfe(wb[lane + 64 * m], shift, bgbit);
       im[m] = (double)sbfe(wb[lane + 64 * m + kN2], shift, bgbit);
     }
-    if (!(TFHE_ABL_LAT & 8)) fft_forward(re, im, tw, mytile, lane);
+    fft_forward(re, im, tw, mytile, lane);
     wave_lds_sync();
 #pragma unroll
     for (int s = 0; s < 8; ++s) mytile[s * 64 + lane] = make_double2(re[s], im[s]);
@@ -321,7 +320,7 @@ __global__ __launch_bounds__(64 * kPairWaves, 1) void k_blind_rotate_pair(BlindR
       f_re[s] = v.x;
       f_im[s] = v.y;
     }
-    if (!(TFHE_ABL_LAT & 16)) fft_inverse(f_re, f_im, tw, mytile, lane);
+    fft_inverse(f_re, f_im, tw, mytile, lane);
     uint32_t *q = acc + (c * 2 + wave) * kN;
 #pragma unroll
     for (int m = 0; m < 8; ++m) {
@@ -338,7 +337,7 @@ __global__ __launch_bounds__(64 * kPairWaves, 1) void k_blind_rotate_pair(BlindR
     // This step's key slots: 96 KiB through the CU's one vector-memory path.  Issued AFTER the barrier that follows
     // their registers' last use (nobody waits at a barrier for the issue, see k_blind_rotate_wide2), a transform ahead
     // of their first use in beta.
-    if (i > 0 && !(TFHE_ABL_LAT & 64)) load_keys(i);
+    if (i > 0) load_keys(i);
     // alpha: forward transforms of A beside the inverse transforms of B's previous step
     if (fwd) forward(0);
     else if (wave < 2 && i > 0) inverse(1);

@@ -26,7 +26,7 @@
 // same on two lanes when the launches overlap -- but when the runtime maps the two streams to one hardware queue (it
 // hands out four per process and shares beyond that; seen whenever the second lane was created later than the first)
 // the launches run one after the other and every call takes two launch times: 14-15 k gates/s.  One lane cannot lose
-// that lottery.  (-DTFHE_EXPERIMENT builds read TFHE_HIP_COMBINE_LANES.)
+// that lottery.
 //
 // Same kernels, same per-element operations in the same order as the unmerged call: the results are the same bits
 // (tests/test_gpu_combine.py holds every word to the CPU checker).  Errors stay per calling thread: argument errors
@@ -60,13 +60,9 @@ struct Combiner : combq::Queue {
   tfhe_hip_ctx *lane_ctx[kLanes] = {};  // created by the lane's first leader
   std::atomic<size_t> max_count{0};     // calls of up to this many ciphertexts are merged; 0 = front end off
   std::atomic<bool> profiling{false};   // what lanes created later start with
-  bool zero_copy_in = false;            // gate groups: the kernels read the pinned arena in place instead of a copy of it
-  bool lane_high_priority = false;      // the lanes' streams are created at the device's highest stream priority
 };
 
 namespace {
-
-bool g_comb_force_heap = false;  // (experiment builds, TFHE_HIP_COMBINE_HEAP: take the no-pinned-memory path of the lanes' arenas)
 
 enum CombClass { CB_GATES = 0, CB_MUX = 1, CB_MUX_NAIVE = 2, CB_ROTATE = 3 };  // CB_ROTATE: trgsw::blind_rotate, the output is the TRLWE
 
@@ -76,7 +72,7 @@ int comb_arena(tfhe_hip_ctx *x, Staging &st, size_t bytes) {
   PinBuf &pin = st.pin;
   CHK(ensure(x, st.dev, bytes));
   if (bytes <= pin.cap) return TFHE_HIP_OK;
-  if (!pin.heap && !g_comb_force_heap && ensure_pinned(x, pin, bytes) == TFHE_HIP_OK) return TFHE_HIP_OK;
+  if (!pin.heap && ensure_pinned(x, pin, bytes) == TFHE_HIP_OK) return TFHE_HIP_OK;
   if (pin.p && pin.heap) free(pin.p);
   pin.p = nullptr;
   pin.cap = 0;
@@ -89,7 +85,7 @@ int comb_arena(tfhe_hip_ctx *x, Staging &st, size_t bytes) {
 }
 
 // One merged launch: requests of one key view and one operation class, in queue order.  x's device is current.
-int comb_run_group(tfhe_hip_ctx *x, KeyState *key, const std::vector<CombReq *> &g, double (&phase_us)[3], bool zero_copy_in) {
+int comb_run_group(tfhe_hip_ctx *x, KeyState *key, const std::vector<CombReq *> &g, double (&phase_us)[3]) {
   KeyBind kb(x, key);
   const auto t_begin = std::chrono::steady_clock::now();
   const CombReq &r0 = *g[0];
@@ -143,22 +139,12 @@ int comb_run_group(tfhe_hip_ctx *x, KeyState *key, const std::vector<CombReq *> 
     }
   }
   const auto t_packed = std::chrono::steady_clock::now();
-  // gate groups read each operand row once, in the blind rotation's prologue: with zero_copy_in the kernel takes the
-  // pinned arena as it is (no copy to wait for ahead of the launch); mux reads its operands in three launches: copied
-  const bool zc = zero_copy_in && !mux && !any_lin && !x->a.pin.heap && !x->b.pin.heap && !x->tv.pin.heap;
   const uint32_t *da = (const uint32_t *)x->a.dev.p, *db = need_b ? (const uint32_t *)x->b.dev.p : nullptr;
   const uint32_t *dtv0 = has_tv ? (const uint32_t *)x->tv.dev.p : nullptr;
-  if (zc) {
-    da = pinned_view((const uint32_t *)x->a.pin.p, m * wb);
-    if (need_b) db = pinned_view((const uint32_t *)x->b.pin.p, m * wb);
-    if (has_tv) dtv0 = pinned_view((const uint32_t *)x->tv.pin.p, m * (size_t)2 * kN * 4);
-    if (!da || (need_b && !db) || (has_tv && !dtv0)) return fail(x, TFHE_HIP_EHIP, "merged-call arena is not device-addressable");
-  } else {
-    HIPCHK(x, hipMemcpyAsync(x->a.dev.p, x->a.pin.p, m * wb, hipMemcpyHostToDevice, s));
-    if (need_b) HIPCHK(x, hipMemcpyAsync(x->b.dev.p, x->b.pin.p, m * wb, hipMemcpyHostToDevice, s));
-    if (need_c) HIPCHK(x, hipMemcpyAsync(x->c.dev.p, x->c.pin.p, m * wb, hipMemcpyHostToDevice, s));
-    if (has_tv) HIPCHK(x, hipMemcpyAsync(x->tv.dev.p, x->tv.pin.p, m * (size_t)2 * kN * 4, hipMemcpyHostToDevice, s));
-  }
+  HIPCHK(x, hipMemcpyAsync(x->a.dev.p, x->a.pin.p, m * wb, hipMemcpyHostToDevice, s));
+  if (need_b) HIPCHK(x, hipMemcpyAsync(x->b.dev.p, x->b.pin.p, m * wb, hipMemcpyHostToDevice, s));
+  if (need_c) HIPCHK(x, hipMemcpyAsync(x->c.dev.p, x->c.pin.p, m * wb, hipMemcpyHostToDevice, s));
+  if (has_tv) HIPCHK(x, hipMemcpyAsync(x->tv.dev.p, x->tv.pin.p, m * (size_t)2 * kN * 4, hipMemcpyHostToDevice, s));
   if (!mux && !uniform) HIPCHK(x, hipMemcpyAsync(x->idx.dev.p, x->idx.pin.p, m, hipMemcpyHostToDevice, s));
   if (any_lin) {  // one streaming launch per run of requests with the same coefficients, in place in the packed rows
     size_t at = 0;
@@ -219,20 +205,6 @@ int comb_make_lane(tfhe_hip_ctx *base, Combiner &C, int li, std::string &why) {
   x->is_lane = true;
   delete x->comb;  // (a lane has no front end of its own)
   x->comb = nullptr;
-  if (C.lane_high_priority) {
-    // Small calls are the latency-sensitive ones: their launches go to a stream of the highest priority the device has,
-    // so that the command processor dispatches their few workgroups ahead of a bulk launch's thousands when both are
-    // pending (a 65,536-ciphertext batch on the context's own stream holds every CU for 330 ms).
-    int least = 0, greatest = 0;
-    hipStream_t hs = nullptr;
-    if (hipDeviceGetStreamPriorityRange(&least, &greatest) == hipSuccess && greatest != least &&
-        hipStreamCreateWithPriority(&hs, hipStreamNonBlocking, greatest) == hipSuccess) {
-      (void)hipStreamDestroy(x->stream);
-      x->stream = hs;
-    } else {
-      (void)hipGetLastError();
-    }
-  }
   x->dispatch = base->dispatch;
   x->profiling = C.profiling.load(std::memory_order_relaxed);
   // arenas for a full round of the default bound up front (a, b, out: < 1 MB each): the first calls of a team do not
@@ -284,7 +256,7 @@ combq::Round comb_run_round(tfhe_hip_ctx *base, Combiner &C, int li, std::vector
       g.push_back(all[j]);
       m += r.count;
     }
-    const int grc = comb_run_group(x, h.key, g, phase_us, C.zero_copy_in);
+    const int grc = comb_run_group(x, h.key, g, phase_us);
     ++rd.launches;
     if (grc != TFHE_HIP_OK) {
       const std::string text = err_text(x->id);

@@ -68,11 +68,11 @@ struct Queue {
   // per round) -- and when (steady_clock ns).
   std::atomic<size_t> last_reqs{0};
   std::atomic<int64_t> last_done_ns{0};
-  // Lingering: only within linger_window of a round that knew of several callers; ends when as many requests are waiting
-  // as that (`want`), when nobody has arrived for linger_quiet + want / 4 microseconds, or after linger_max + want
+  // Lingering: only within kLingerWindowUs of a round that knew of several callers; ends when as many requests are waiting
+  // as that (`want`), when nobody has arrived for kLingerQuietUs + want / 4 microseconds, or after kLingerMaxUs + want
   // microseconds (a team of hundreds of threads takes that long to come back through the scheduler; a launch that leaves
   // without most of them makes them wait a whole launch).
-  long linger_window_us = 1000, linger_quiet_us = 50, linger_max_us = 250;
+  static constexpr long kLingerWindowUs = 1000, kLingerQuietUs = 50, kLingerMaxUs = 250;
   // statistics; leaders only
   std::mutex st_mu;
   uint64_t st_launches = 0, st_requests = 0, st_units = 0, st_max_requests = 0, st_lingers = 0;
@@ -117,7 +117,7 @@ struct Queue {
       const uint64_t taken0 = taken.load(std::memory_order_relaxed);
       auto waiting = [&] { return (size_t)(arrivals.load(std::memory_order_relaxed) - taken0); };
       const int64_t t0 = now_ns();
-      if (want > 1 && waiting() < want && t0 - last_done_ns.load(std::memory_order_relaxed) < linger_window_us * 1000) {
+      if (want > 1 && waiting() < want && t0 - last_done_ns.load(std::memory_order_relaxed) < kLingerWindowUs * 1000) {
         int64_t last_growth = t0, now = t0;
         size_t seen = waiting();
         for (;;) {
@@ -128,7 +128,7 @@ struct Queue {
             seen = cur;
             last_growth = now;
           }
-          if (cur >= want || now - last_growth > (linger_quiet_us * 4 + (long)want) * 250 || now - t0 > (linger_max_us + (long)want) * 1000) break;
+          if (cur >= want || now - last_growth > (kLingerQuietUs * 4 + (long)want) * 250 || now - t0 > (kLingerMaxUs + (long)want) * 1000) break;
         }
         std::lock_guard<std::mutex> lk(st_mu);
         ++st_lingers;

@@ -20,8 +20,6 @@
 
 #include <type_traits>
 
-#include "experiment.hpp"
-
 namespace tfhe {
 
 __host__ __device__ __forceinline__ int ksk_row_words(int n) { return (n + 1 + 3) & ~3; }
@@ -332,13 +330,7 @@ __global__ __launch_bounds__(320) void k_key_switch_split(const uint32_t *__rest
 // Waves per workgroup: four, two workgroups per CU, while two rings fit a CU's LDS (base 16 / 32); EIGHT in ONE workgroup
 // per CU at base 64 / 128, whose rings (16 / 32 KiB per group) leave room for one workgroup only -- the same two waves
 // per SIMD, one ring and one digit stage for twice the ciphertexts (half the L2 -> LDS traffic per ciphertext).
-#ifndef TFHE_KS_SL2_WAVES_WIDE  // (experiment knob: 4 = the four-wave workgroup at base 64 / 128 too)
-#define TFHE_KS_SL2_WAVES_WIDE 8
-#endif
-#ifndef TFHE_KS_SL2_WAVES_B32  // (experiment knob: 8 = one eight-wave workgroup per CU at base 32 as well; base 16's 4 KiB groups are 4 DMAs)
-#define TFHE_KS_SL2_WAVES_B32 4
-#endif
-__host__ __device__ constexpr int ks_sl2_waves(int basebit) { return basebit <= 4 ? 4 : basebit == 5 ? TFHE_KS_SL2_WAVES_B32 : TFHE_KS_SL2_WAVES_WIDE; }
+__host__ __device__ constexpr int ks_sl2_waves(int basebit) { return basebit <= 5 ? 4 : 8; }
 __host__ __device__ constexpr int ks_sl2_cts(int basebit, int sets) { return 4 * sets * ks_sl2_waves(basebit); }  // ciphertexts per workgroup (512 at S = 32, four waves)
 
 // The kernel's first form (rounds 1-3: digits extracted per read with v_bfe + v_lshl_add, four v_sub per row read, a_bar
@@ -371,14 +363,9 @@ __host__ __device__ constexpr int ks_sl2_stage_words(int basebit, int sets) {
 __host__ __device__ constexpr size_t ks_sl2_lds_bytes(int basebit, int sets, int rp) {
   return (size_t)2 * rp * ((size_t)(1 << basebit) * 256) + (size_t)2 * ks_sl2_stage_words(basebit, sets) * 4;
 }
-// pairs of groups in the ring: 4 (lookahead 6 groups) at base 16 / 32, 2 at base 64 / 128
-#ifndef TFHE_KS_SL2_RP_SMALL  // (experiment knob)
-#define TFHE_KS_SL2_RP_SMALL 4
-#endif
-#ifndef TFHE_KS_SL2_RP_B64  // (experiment knob) base 64: 2 pairs (64 KiB); 4 pairs measured no better (11.1 vs 10.9 ms at SECURITY_UINT6)
-#define TFHE_KS_SL2_RP_B64 2
-#endif
-__host__ __device__ constexpr int ks_sl2_rp(int basebit) { return basebit <= 5 ? TFHE_KS_SL2_RP_SMALL : basebit == 6 ? TFHE_KS_SL2_RP_B64 : 2; }
+// pairs of groups in the ring: 4 (lookahead 6 groups) at base 16 / 32, 2 at base 64 / 128 (base 64: 2 pairs are 64 KiB;
+// 4 pairs measured no better, 11.1 vs 10.9 ms at SECURITY_UINT6)
+__host__ __device__ constexpr int ks_sl2_rp(int basebit) { return basebit <= 5 ? 4 : 2; }
 // rows of the digit buffer: the ciphertexts of whole workgroups plus one DMA round of slack
 __host__ __device__ inline size_t ks_sl2_ct_stride(size_t count, int basebit, int sets) {
   const size_t cts = (size_t)ks_sl2_cts(basebit, sets);
@@ -531,14 +518,12 @@ __global__ __launch_bounds__(64 * ks_sl2_waves(BASEBIT), 2) void k_key_switch_sl
       if (RP == 2) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
       else if (p % 2 == 0) asm volatile("s_waitcnt vmcnt(%0)" ::"n"((RP - 2) * PW) : "memory");
       else asm volatile("s_waitcnt vmcnt(%0)" ::"n"((RP - 2) * PW + ST) : "memory");
-      if (!(TFHE_ABL_SL & 2)) __builtin_amdgcn_s_barrier();  // every wave's pieces are visible; the pair consumed last step is retired
+      __builtin_amdgcn_s_barrier();  // every wave's pieces are visible; the pair consumed last step is retired
       asm volatile("" ::: "memory");
       const uint32_t quad = (g + 2u * p) / 4u;
       if (p % 2 == 0) dma_stage(quad + 1u);
-      if (!(TFHE_ABL_SL & 1)) {
-        dma_group(g + 2u * (p + RP - 1));
-        dma_group(g + 2u * (p + RP - 1) + 1u);
-      }
+      dma_group(g + 2u * (p + RP - 1));
+      dma_group(g + 2u * (p + RP - 1) + 1u);
       if (p % 2 == 0) {  // the quad's digit words of this lane quarter's ciphertexts
         const uint32_t *st = reinterpret_cast<const uint32_t *>(sl_smem + off_stage + (quad & 1u) * (STW * 4u));
 #pragma unroll
@@ -555,10 +540,7 @@ __global__ __launch_bounds__(64 * ks_sl2_waves(BASEBIT), 2) void k_key_switch_sl
       // additions of batch b, so the LDS always has this wave's next reads queued while its VALU adds (with the reads
       // drained per batch the two pipes took turns: 8.4 ms = VALU 3.8 + LDS 4.6 at SECURITY_UINT4).  The batches are
       // fenced for the scheduler: hoisting still more reads over additions only costs registers.
-#ifndef TFHE_KS_SL2_GB
-#define TFHE_KS_SL2_GB 2
-#endif
-      constexpr int GB = TFHE_KS_SL2_GB, NB = S / GB;
+      constexpr int GB = 2, NB = S / GB;
       static_assert(S % GB == 0, "the read batch must divide S");
       u32x4 r0[2][GB], r1[2][GB];
       auto issue = [&](int bt, int buf) {
@@ -568,11 +550,6 @@ __global__ __launch_bounds__(64 * ks_sl2_waves(BASEBIT), 2) void k_key_switch_sl
           const uint32_t a1 = __builtin_amdgcn_perm(abw[bt * GB + x], lane_col, sel1);
           // LDS addresses as integers: the dynamic LDS of a kernel without static LDS starts at 0 (checked on entry), so
           // the picked address goes to the ds_read as it is and the slot rides in the instruction's offset field
-          if (TFHE_ABL_SL & 8) {  // timing-only: no LDS row reads
-            r0[buf][x] = u32x4{a0, a1, a0 ^ a1, a0 + 1u};
-            r1[buf][x] = u32x4{a1, a0, a1 + 1u, a0 & a1};
-            continue;
-          }
           r0[buf][x] = *(const __attribute__((address_space(3))) u32x4 *)(uintptr_t)(a0 + slot0);
           r1[buf][x] = *(const __attribute__((address_space(3))) u32x4 *)(uintptr_t)(a1 + slot1);
         }
@@ -585,10 +562,6 @@ __global__ __launch_bounds__(64 * ks_sl2_waves(BASEBIT), 2) void k_key_switch_sl
         __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
         for (int x = 0; x < GB; ++x) {
-          if (TFHE_ABL_SL & 16) {  // timing-only: the rows are read and dropped
-            asm volatile("" ::"v"(r0[bt & 1][x]), "v"(r1[bt & 1][x]));
-            continue;
-          }
           // v_add3_u32 x 4, IN PLACE (inline asm: left to itself the allocator rotates the accumulators through the
           // row buffers' registers across the unrolled steps and needs ~60 more of them; S = 32 / 36 then spill)
           add3_inplace(acc[bt * GB + x][0], r0[bt & 1][x].x, r1[bt & 1][x].x);

@@ -38,27 +38,16 @@
 
 #include <type_traits>
 
-#include "experiment.hpp"
-
 namespace tfhe {
 
-#ifndef TFHE_KM_FRAGS  // experiment knobs (profiles/exp/build_variants.sh); the defaults are the product
-#define TFHE_KM_FRAGS 1
-#endif
-#ifndef TFHE_KM_COLBLOCKS
-#define TFHE_KM_COLBLOCKS 2
-#endif
 constexpr int kKmWaves = 4;              // waves per workgroup (two workgroups per CU: 2 waves per SIMD)
-constexpr int kKmFrags = TFHE_KM_FRAGS;  // 32-row A fragments per wave: a key tile read from LDS feeds this many matrix instructions
+constexpr int kKmFrags = 1;  // 32-row A fragments per wave: a key tile read from LDS feeds this many matrix instructions
 constexpr int kKmRows = 32 * kKmFrags * kKmWaves;  // ciphertexts per workgroup; level-1 buffers are padded to a multiple
-#ifndef TFHE_KM_SLOTS
-#define TFHE_KM_SLOTS 4
-#endif
-constexpr int kKmSlots = TFHE_KM_SLOTS;  // ring depth in K-steps
+constexpr int kKmSlots = 4;              // ring depth in K-steps
 constexpr int kKmAhead = kKmSlots - 1;   // DMA lead in K-steps
 constexpr int kKmAbBytes = 32 * kKmFrags * 16 * 4;  // one wave's a_bar stage: its rows x 16 coefficients
 constexpr int kKmAbQ = kKmAbBytes / 256; // dword DMA instructions per stage (256 B each)
-constexpr int kKmColBlocks = TFHE_KM_COLBLOCKS;
+constexpr int kKmColBlocks = 2;
 constexpr int kKmMaxTiles = 12 / kKmFrags;  // accumulator budget: kKmFrags x NT x 16 registers <= 192 (two waves per SIMD)
 
 // key tiles a wave copies per K-step, tile positions per ring slot
@@ -180,9 +169,6 @@ struct KmPos {
 // zero on entry: the four byte planes and the `ksplit` K chunks (both decoded from the linear workgroup index below)
 // are merged with integer atomics (u32 addition commutes: same bits in any arrival order).
 // NT = tiles of the widest column block; a block with NT-1 tiles skips the last tile (wave-uniform branch).
-#ifndef TFHE_KM_XCD
-#define TFHE_KM_XCD 1
-#endif
 template <int NT>
 __global__ __launch_bounds__(64 * kKmWaves, 2) void k_key_switch_mfma(const uint32_t *__restrict__ lv1,        // [count][N+1]
                                                                        const unsigned char *__restrict__ ksk8,  // k_ksk_planes layout
@@ -200,17 +186,12 @@ __global__ __launch_bounds__(64 * kKmWaves, 2) void k_key_switch_mfma(const uint
   const uint32_t lds_base = (uint32_t)(size_t)(__attribute__((address_space(3))) unsigned char *)km_smem;
   const uint32_t off_ab = (uint32_t)(kKmSlots * SLOT) + (uint32_t)wave * 2u * kKmAbBytes;
   const uint32_t off_dump = (uint32_t)(kKmSlots * SLOT) + (uint32_t)(WAVES * 2 * kKmAbBytes) + (uint32_t)wave * 256u;
-#if TFHE_KM_XCD
   // Workgroups are handed to the 8 XCDs round-robin in dispatch order (x fastest).  With 2 column blocks x 4 planes =
   // 8 (plane, column block) streams, giving workgroup `lin` stream lin % 8 puts each stream on ONE XCD: that XCD's L2
   // then holds one stream's window (all its row blocks walk K together) instead of a window of all eight.
   const unsigned lin = blockIdx.x + gridDim.x * (blockIdx.y + gridDim.y * blockIdx.z);
   const unsigned combos = gridDim.y * gridDim.z, combo = lin % combos, rest = lin / combos;
   const int cb = (int)(combo % gridDim.y), plane = (int)(combo / gridDim.y);  // one byte plane per workgroup
-#else
-  const unsigned rest = blockIdx.x;
-  const int cb = blockIdx.y, plane = blockIdx.z;  // one byte plane per workgroup: no epilogue inside the K loop
-#endif
   // grid.x = row blocks x K chunks: small batches cut the walk over K so that the whole chip works on them (the
   // chunks, like the planes, meet in the output through integer atomics)
   const unsigned n_rb = gridDim.x / (unsigned)ksplit;
@@ -278,10 +259,7 @@ __global__ __launch_bounds__(64 * kKmWaves, 2) void k_key_switch_mfma(const uint
   km_i32x4 A[R];
 #pragma unroll
   for (int f = 0; f < R; ++f) A[f] = make_a(cur, f);
-#ifndef TFHE_KM_PRE
-#define TFHE_KM_PRE 3
-#endif
-  constexpr int PRE = NT < TFHE_KM_PRE ? NT : TFHE_KM_PRE;  // key tiles in flight ahead of the matrix instruction that consumes them
+  constexpr int PRE = NT < 3 ? NT : 3;  // key tiles in flight ahead of the matrix instruction that consumes them
   constexpr int H = NT / 2;             // tiles consumed before the mid-step barrier
   km_i32x4 Bpre[PRE];
 #pragma unroll
@@ -315,7 +293,7 @@ __global__ __launch_bounds__(64 * kKmWaves, 2) void k_key_switch_mfma(const uint
       }
       __builtin_amdgcn_sched_barrier(0);  // the first half's matrix instructions stay ahead of the barrier
       asm volatile("s_waitcnt vmcnt(%0)" ::"n"((D - 2) * OPS) : "memory");
-      if (!TFHE_ABL_KM_NOBARRIER) __builtin_amdgcn_s_barrier();
+      __builtin_amdgcn_s_barrier();
       asm volatile("" ::: "memory");
       const uint32_t dslot = lds_base + (uint32_t)((g + D) % kKmSlots) * SLOT;
       const int nblk = (cur.blk + 1) & 63;

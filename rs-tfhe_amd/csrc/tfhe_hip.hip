@@ -31,12 +31,6 @@
 
 #include "blind_rotate.hpp"
 #include "blind_rotate_wide.hpp"
-#if defined(TFHE_EXPERIMENT) && defined(TFHE_EXP_L1)
-#include "../../profiles/exp/superseded/blind_rotate_l1.hpp"
-#endif
-#if defined(TFHE_EXPERIMENT) && defined(TFHE_EXP_WIDE1)
-#include "../../profiles/exp/superseded/blind_rotate_wide1.hpp"
-#endif
 #include "key_switch.hpp"
 #include "key_switch_mfma.hpp"
 #include "keygen.hpp"
@@ -208,26 +202,14 @@ struct tfhe_hip_ctx {
     // AUTO picks per batch size, anything else runs that kernel at every batch size.
     int br_force = 0;  // BrKind + 1, 0 = auto
     int ks_force = 0;  // KsKind + 1, 0 = auto
-    // crossovers of the automatic choice, in ciphertexts; set from the CU count at creation.  Numeric overrides exist
-    // only in -DTFHE_EXPERIMENT builds (profiles/exp/).
+    // crossovers of the automatic choice, in ciphertexts; set from the CU count at creation
     size_t wide_max = 256;      // blind rotate: one eight-wave workgroup per ciphertext up to this batch size
     size_t pair_lo = 0, pair_max = 0;  // ... two ciphertexts per workgroup (k_blind_rotate_pair) for pair_lo < count <= pair_max
     size_t ks_split_max = 256;  // key switch: coefficient walk split over 32 workgroups up to this batch size
     size_t ks_mfma_min = 64;    // smallest batch the matrix-core kernel takes (below: the split kernel)
     size_t ks_sl_chunk_min = 384;  // wider bases: smallest batch the column-sliced kernel takes (with K chunks; below: the split kernel)
-    int ks_sliced_sets = 0;     // 0: accumulator sets per lane picked per launch (ks_sl2_pick_sets); else forced (24..36; experiment builds)
-    int ks_mfma_ksplit = 0;     // 0: K chunks per row block picked per launch; else forced (1, 2, 4, 8, 16)
-    int ks_sl_kchunks = 0;      // 0: K chunks of the column-sliced kernel picked per launch; else forced (1 ... 64, a power of two)
-    long br_chunk = 0;  // blind-rotate workgroups per launch: 0 = whole batch (default), -1 = resident set, N = N
-    bool exp_wide1 = false;  // (experiment builds with -DTFHE_EXP_WIDE1: SINGLE runs the superseded one-wave-per-row kernel)
     bool fast_round = false;  // |pre-rounding value| < 2^51 guaranteed (see round_to_torus<FAST>)
   } dispatch;
-  // experiment builds (profiles/exp/midsize.py): the two parts of a blind-rotation plan on TWO streams, and a forced cut
-  bool exp_overlap = false;
-  size_t exp_split_at = 0;
-  int exp_split_kind[2] = {0, 0};
-  hipStream_t exp_stream2 = nullptr;
-  hipEvent_t exp_ev[2] = {nullptr, nullptr};
   std::vector<std::pair<hipEvent_t, hipEvent_t>> ev_br, ev_ks;
   std::vector<std::pair<hipEvent_t, hipEvent_t>> ev_pke_sel, ev_pke_mm;  // pk_encrypt.hpp: the keystream pass, the contraction
   uint64_t bootstraps = 0;
@@ -356,19 +338,6 @@ constexpr size_t kYieldChunk = 8192;
 constexpr int64_t kYieldWindowNs = 250 * 1000 * 1000;
 
 typedef void (*br_kernel_t)(BlindRotateArgs);
-#if defined(TFHE_EXPERIMENT) && defined(TFHE_EXP_L1)  // the three-waves-per-SIMD l = 1 experiment (profiles/exp/superseded/blind_rotate_l1.hpp)
-bool br_is_l1(const tfhe_hip_ctx *ctx) { return ctx->P.l == 1; }
-int br_waves(const tfhe_hip_ctx *ctx) { return br_is_l1(ctx) ? kL1Waves : kBrWaves; }
-#else
-constexpr bool br_is_l1(const tfhe_hip_ctx *) { return false; }
-constexpr int br_waves(const tfhe_hip_ctx *) { return kBrWaves; }
-#endif
-size_t br_lds_bytes(const tfhe_hip_ctx *ctx) {
-#if defined(TFHE_EXPERIMENT) && defined(TFHE_EXP_L1)
-  if (br_is_l1(ctx)) return blind_rotate_l1_lds_bytes();
-#endif
-  return blind_rotate_lds_bytes(ctx->P.n);
-}
 
 // ---- which blind-rotation kernels a batch of `count` runs on ----------------------------------------
 // Three kernels, one arithmetic (the same per-element operations in the same order: results are the same bits
@@ -409,16 +378,8 @@ br_kernel_t br_kernel(const tfhe_hip_ctx *ctx, BrKind kind, bool many = false) {
     constexpr bool F = decltype(inst)::FAST, M = decltype(inst)::MANY;
     switch (kind) {
       case BR_PAIR: return k_blind_rotate_pair<L, F, M>;
-      case BR_SINGLE:
-#if defined(TFHE_EXPERIMENT) && defined(TFHE_EXP_WIDE1)  // the superseded one-wave-per-row latency kernel (profiles/exp/superseded/blind_rotate_wide1.hpp)
-        if (!M && ctx->dispatch.exp_wide1) return k_blind_rotate_wide<L, F>;
-#endif
-        return M ? k_blind_rotate_wide2_many<L, F> : k_blind_rotate_wide2<L, F>;
-      default:
-#if defined(TFHE_EXPERIMENT) && defined(TFHE_EXP_L1)
-        if constexpr (L == 1) return M ? nullptr : k_blind_rotate_l1<F>;
-#endif
-        return M ? k_blind_rotate_many<L, F> : k_blind_rotate<L, F>;
+      case BR_SINGLE: return M ? k_blind_rotate_wide2_many<L, F> : k_blind_rotate_wide2<L, F>;
+      default: return M ? k_blind_rotate_many<L, F> : k_blind_rotate<L, F>;
     }
   });
 }
@@ -474,7 +435,7 @@ BrPlan plan_blind_rotate(const tfhe_hip_ctx *ctx, size_t count) {
   // ms, 2,200: 14.4 vs 17.9, 3,300: 19.7 vs 22.9); done up to 32N, beyond which the step is a few per cent of the launch.
   // (at l = 1 a pair launch costs as much as the step it would save: tails of up to N only)
   size_t tail = 0;
-  if (pairs_on && ctx->dispatch.br_chunk == 0 && count <= 32 * N1) {
+  if (pairs_on && count <= 32 * N1) {
     const size_t r = count % (4 * N1);
     if (r > 0 && r <= (ctx->P.l == 1 ? N1 : N2) && count > r) tail = r;
   }
@@ -530,9 +491,6 @@ int launch_blind_rotate(tfhe_hip_ctx *ctx, hipStream_t s, const BrCall &c) {
   A.n_luts = 1 << lut_shift;
   A.out_fn_stride = count;  // the whole call's: part() moves the output bases, not the stride
   const bool many = lut_shift > 0;
-#if defined(TFHE_EXPERIMENT) && defined(TFHE_EXP_L1)
-  if (many && br_is_l1(ctx)) return fail(ctx, TFHE_HIP_EINVAL, "the l = 1 experiment kernel has no many-LUT epilogue");
-#endif
   A.clk = ctx->profiling ? ctx->d_diag : nullptr;
   A.err_flag = reinterpret_cast<uint32_t *>(ctx->d_diag + 2);
   // sample_extract_index_2 reads a[n - i] of an N-coefficient polynomial (trlwe.rs:122-136): the reference
@@ -562,68 +520,26 @@ int launch_blind_rotate(tfhe_hip_ctx *ctx, hipStream_t s, const BrCall &c) {
     return record_end(ctx, s, ctx->ev_br);
   };
   BrPlan pl = plan_blind_rotate(ctx, count);
-#ifdef TFHE_EXPERIMENT
-  if (ctx->exp_split_at && count > ctx->exp_split_at) {  // a forced cut: kind[0] over [0, at), kind[1] over the rest
-    pl = BrPlan();
-    pl.add((BrKind)ctx->exp_split_kind[0], 0, ctx->exp_split_at);
-    pl.add((BrKind)ctx->exp_split_kind[1], ctx->exp_split_at, count - ctx->exp_split_at);
-  }
-  const bool overlap = ctx->exp_overlap && pl.nparts == 2 && ctx->exp_stream2;
-  hipStream_t s_home = s;
-  // (event and wait calls take the runtime's own name for the default stream, NULL: they fault on the hipStreamLegacy handle)
-  hipStream_t s_rt = s == hipStreamLegacy ? (hipStream_t) nullptr : s;
-  if (overlap) {  // the second part may start as soon as what precedes this call on `s` is done
-    HIPCHK(ctx, hipEventRecord(ctx->exp_ev[0], s_rt));
-    HIPCHK(ctx, hipStreamWaitEvent(ctx->exp_stream2, ctx->exp_ev[0], 0));
-  }
-#endif
   for (int q = 0; q < pl.nparts; ++q) {
-#ifdef TFHE_EXPERIMENT
-    if (overlap) s = q == 1 ? ctx->exp_stream2 : s_home;
-#endif
     const size_t begin = pl.begin[q], m_all = pl.count[q];
     if (pl.kind[q] == BR_PAIR) {
       CHK(launch(br_kernel(ctx, BR_PAIR, many), (unsigned)((m_all + 1) / 2), 64u * kPairWaves, blind_rotate_pair_lds_bytes(ctx->P.n),
                  part(begin, m_all)));
     } else if (pl.kind[q] == BR_SINGLE) {
-#if defined(TFHE_EXPERIMENT) && defined(TFHE_EXP_WIDE1)
-      if (ctx->dispatch.exp_wide1) {
-        if (lut_shift) return fail(ctx, TFHE_HIP_EINVAL, "the one-wave-per-row experiment kernel has no many-LUT epilogue");
-        CHK(launch(br_kernel(ctx, BR_SINGLE), (unsigned)m_all, 128u * (unsigned)ctx->P.l,
-                   blind_rotate_wide_lds_bytes(ctx->P.n, ctx->P.l), part(begin, m_all)));
-        continue;
-      }
-#endif
       CHK(launch(br_kernel(ctx, BR_SINGLE, many), (unsigned)m_all, 64u * kWide2Waves, blind_rotate_wide2_lds_bytes(ctx->P.n, ctx->P.l),
                  part(begin, m_all)));
     } else {
-      // Default: ONE launch of the whole part.  The four waves of a workgroup meet at a barrier every CMUX step
-      // (blind_rotate.hpp), which keeps the resident workgroups streaming the key in near lock-step on its own:
-      // L1 86 % / L2 97 % hits.  (Experiment builds: TFHE_HIP_BR_CHUNK splits the batch into launches of N ciphertexts,
-      // -1: the resident set -- the round-1 remedy for free-running one-wave workgroups.)
-      const size_t lds = br_lds_bytes(ctx);
-      size_t chunk = m_all;
-      if (ctx->dispatch.br_chunk > 0) chunk = (size_t)ctx->dispatch.br_chunk;
-      if (ctx->dispatch.br_chunk < 0) {
-        int per_cu = 0;
-        const hipError_t e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, br_kernel(ctx, BR_BATCH), 64 * br_waves(ctx), lds);
-        if (e == hipSuccess && per_cu > 0 && ctx->num_cus > 0) chunk = (size_t)per_cu * ctx->num_cus * br_waves(ctx);
-      }
-      if (ctx->dispatch.br_chunk == 0 && m_all >= 2 * kYieldChunk && comb_interactive(ctx)) chunk = kYieldChunk;
-      if (chunk == 0 || chunk > m_all) chunk = m_all;
+      // ONE launch of the whole part (unless small calls are arriving: kYieldChunk).  The four waves of a workgroup meet
+      // at a barrier every CMUX step (blind_rotate.hpp), which keeps the resident workgroups streaming the key in near
+      // lock-step on its own: L1 86 % / L2 97 % hits.
+      const size_t chunk = (m_all >= 2 * kYieldChunk && comb_interactive(ctx)) ? kYieldChunk : m_all;
       for (size_t done = 0; done < m_all; done += chunk) {
         const size_t m = (m_all - done < chunk) ? m_all - done : chunk;
-        const unsigned bw = (unsigned)br_waves(ctx);
-        CHK(launch(br_kernel(ctx, BR_BATCH, many), (unsigned)((m + bw - 1) / bw), 64u * bw, lds, part(begin + done, m)));
+        CHK(launch(br_kernel(ctx, BR_BATCH, many), (unsigned)((m + kBrWaves - 1) / kBrWaves), 64u * kBrWaves,
+                   blind_rotate_lds_bytes(ctx->P.n), part(begin + done, m)));
       }
     }
   }
-#ifdef TFHE_EXPERIMENT
-  if (overlap) {  // whatever follows on the caller's stream waits for the second part
-    HIPCHK(ctx, hipEventRecord(ctx->exp_ev[1], ctx->exp_stream2));
-    HIPCHK(ctx, hipStreamWaitEvent(s_rt, ctx->exp_ev[1], 0));
-  }
-#endif
   ctx->bootstraps += count;
   return TFHE_HIP_OK;
 }
@@ -693,15 +609,10 @@ sl2_kernel_t sl2_kernel(int basebit, int sets) {
 // costs ceil(grid / slots) x S (SECURITY_UINT4, 65,536 ciphertexts, 13 slices, 512 slots: S = 32 is 3.25 rounds = 4 x 32,
 // S = 36 is 2.9 rounds = 3 x 36; base 64 / 128 run ONE eight-wave workgroup per CU, 256 slots: SECURITY_UINT7, 19
 // slices: S = 32 is 4.75 rounds = 5 x 32 -- 15.8 ms measured, 16.8 / 17.8 at 36 / 28) -- profiles/exp/logs/r4_ks_sl_ablation.log.
-bool ks_sl2_sets_allowed(int basebit, int sets) {
-  (void)basebit;
-  return sets == 24 || sets == 28 || sets == 32 || sets == 36;
-}
 int ks_sl2_pick_sets(int basebit, size_t count, int slices, int slots) {
   int best = basebit == 7 ? 36 : basebit == 6 ? 28 : 32;
   size_t best_cost = ~(size_t)0;
   for (int sets : {24, 28, 32, 36}) {
-    if (!ks_sl2_sets_allowed(basebit, sets)) continue;
     const size_t grid = ((count + (size_t)ks_sl2_cts(basebit, sets) - 1) / (size_t)ks_sl2_cts(basebit, sets)) * (size_t)slices;
     const size_t cost = ((grid + (size_t)slots - 1) / (size_t)slots) * (size_t)sets;
     if (cost < best_cost || (cost == best_cost && sets == 32)) {
@@ -754,7 +665,6 @@ KsPlan plan_key_switch(const tfhe_hip_ctx *ctx, size_t count) {
     const size_t ncb = (size_t)(tiles < kKmColBlocks ? tiles : kKmColBlocks);
     int ksplit = 1;
     while (ksplit < 16 && rb * ncb * 4 * (size_t)ksplit < 2 * (size_t)ctx->num_cus) ksplit *= 2;
-    if (ctx->dispatch.ks_mfma_ksplit) ksplit = ctx->dispatch.ks_mfma_ksplit;
     pl.kparts = ksplit;
     pl.atomics = true;
   } else if (pl.kind == KS_SLICED) {
@@ -765,15 +675,13 @@ KsPlan plan_key_switch(const tfhe_hip_ctx *ctx, size_t count) {
     // workgroups resident per CU: two waves per SIMD by registers (8 wave slots), and the rings must fit the LDS
     const int by_waves = 8 / ks_sl2_waves(P.basebit), by_lds = 2 * ks_sl2_lds_bytes(P.basebit, 36, rp) <= 160 * 1024 ? 2 : 1;
     const int per_cu = by_waves < by_lds ? by_waves : by_lds;
-    int sets = ks_sl2_pick_sets(P.basebit, in_launch, slices, per_cu * ctx->num_cus);
-    if (ctx->dispatch.ks_sliced_sets) sets = ctx->dispatch.ks_sliced_sets;
+    const int sets = ks_sl2_pick_sets(P.basebit, in_launch, slices, per_cu * ctx->num_cus);
     // small batches have few ciphertext groups: the walk over the N * t groups is cut into up to 64 chunks (grid.z)
     // so that about two workgroups per CU exist; the chunks meet in the zeroed output through integer atomics.
     // A chunk is whole rings (2 * rp groups).
     const size_t groups = (in_launch + (size_t)ks_sl2_cts(P.basebit, sets) - 1) / (size_t)ks_sl2_cts(P.basebit, sets);
     int kchunks = 1;
     while (kchunks < 64 && groups * (size_t)slices * (size_t)kchunks < 2 * (size_t)ctx->num_cus) kchunks *= 2;
-    if (ctx->dispatch.ks_sl_kchunks) kchunks = ctx->dispatch.ks_sl_kchunks;
     while (kchunks > 1 && (kN * P.t / kchunks) % (2 * rp) != 0) kchunks /= 2;
     pl.sets = sets;
     pl.kparts = kchunks;
@@ -1278,47 +1186,6 @@ int tfhe_hip_ctx_create(const tfhe_hip_params *p, int device, tfhe_hip_ctx **out
   if (blind_rotate_pair_lds_bytes(p->n) > 160 * 1024) ctx->dispatch.pair_max = 0;  // (n > 1,900: no parameter set)
   ctx->dispatch.br_force = br_force;
   ctx->dispatch.ks_force = ks_force;
-#ifdef TFHE_EXPERIMENT
-  // Numeric overrides of the crossovers and of the per-launch choices: experiment builds only (profiles/exp/).
-  if (const char *env = getenv("TFHE_HIP_FAST_ROUND")) ctx->dispatch.fast_round = ctx->dispatch.fast_round && atoi(env) != 0;
-  if (const char *env = getenv("TFHE_HIP_KS_SLICED_SETS")) {
-    const int v = atoi(env);
-    ctx->dispatch.ks_sliced_sets = (v == 24 || v == 28 || v == 32 || v == 36) ? v : 0;
-  }
-  if (const char *env = getenv("TFHE_HIP_KS_MFMA_MIN")) ctx->dispatch.ks_mfma_min = (size_t)atol(env);
-  if (const char *env = getenv("TFHE_HIP_KS_SL_CHUNK_MIN")) ctx->dispatch.ks_sl_chunk_min = (size_t)atol(env);
-  if (const char *env = getenv("TFHE_HIP_KS_SL_KCHUNKS")) {
-    const int v = atoi(env);
-    ctx->dispatch.ks_sl_kchunks = (v >= 1 && v <= 64 && (v & (v - 1)) == 0) ? v : 0;
-  }
-  if (const char *env = getenv("TFHE_HIP_KS_MFMA_KSPLIT")) {
-    const int v = atoi(env);
-    ctx->dispatch.ks_mfma_ksplit = (v == 1 || v == 2 || v == 4 || v == 8 || v == 16) ? v : 0;
-  }
-  if (const char *env = getenv("TFHE_HIP_WIDE_MAX")) ctx->dispatch.wide_max = (size_t)atol(env);
-  if (const char *env = getenv("TFHE_HIP_PAIR_LO")) ctx->dispatch.pair_lo = (size_t)atol(env);
-  if (const char *env = getenv("TFHE_HIP_PAIR_MAX")) ctx->dispatch.pair_max = (size_t)atol(env);
-  if (const char *env = getenv("TFHE_HIP_KS_SPLIT_MAX")) ctx->dispatch.ks_split_max = (size_t)atol(env);
-  if (const char *env = getenv("TFHE_HIP_BR_CHUNK")) ctx->dispatch.br_chunk = atol(env);
-  if (const char *env = getenv("TFHE_HIP_BR_OVERLAP")) ctx->exp_overlap = atoi(env) != 0;
-  if (const char *env = getenv("TFHE_HIP_BR_SPLIT")) {  // "<at>:<kind0>:<kind1>", kinds 0 batch / 1 single / 2 pair
-    unsigned long at = 0;
-    int k0 = 0, k1 = 0;
-    if (sscanf(env, "%lu:%d:%d", &at, &k0, &k1) == 3 && k0 >= 0 && k0 <= 2 && k1 >= 0 && k1 <= 2) {
-      ctx->exp_split_at = at;
-      ctx->exp_split_kind[0] = k0;
-      ctx->exp_split_kind[1] = k1;
-    }
-  }
-  if (ctx->exp_overlap) {
-    (void)hipStreamCreateWithFlags(&ctx->exp_stream2, hipStreamNonBlocking);
-    (void)hipEventCreateWithFlags(&ctx->exp_ev[0], hipEventDisableTiming);
-    (void)hipEventCreateWithFlags(&ctx->exp_ev[1], hipEventDisableTiming);
-  }
-#ifdef TFHE_EXP_WIDE1
-  if (const char *env = getenv("TFHE_HIP_BR_WIDE2")) ctx->dispatch.exp_wide1 = atoi(env) == 0;
-#endif
-#endif
   // Dynamic LDS above the 64 KiB default.  The attribute belongs to the (kernel, device), not to the context, and
   // contexts of different n share an instantiation (SECURITY_80/110/128_BIT all run k_blind_rotate<3, true>): it is
   // set to the size for the LARGEST supported n, so the order in which contexts are created cannot lower it below
@@ -1332,10 +1199,8 @@ int tfhe_hip_ctx_create(const tfhe_hip_params *p, int device, tfhe_hip_ctx **out
     for (int many = 0; many < 2; ++many)  // the many-LUT instantiations have the same LDS layouts
       for (BrKind kind : {BR_BATCH, BR_SINGLE, BR_PAIR}) {
         if (kind == BR_PAIR && !ctx->dispatch.pair_max) continue;
-        if (kind == BR_BATCH && many && br_is_l1(ctx)) continue;  // (the l = 1 experiment kernel has no many-LUT form)
         const size_t bytes = kind == BR_PAIR     ? blind_rotate_pair_lds_bytes(kMaxN)
                              : kind == BR_SINGLE ? blind_rotate_wide2_lds_bytes(kMaxN, p->l)
-                             : br_is_l1(ctx)     ? br_lds_bytes(ctx)
                                                  : blind_rotate_lds_bytes(kMaxN);
         if ((e = set_lds((const void *)br_kernel(ctx, kind, many), bytes)) != hipSuccess)
           return bail((std::string("hipFuncSetAttribute(blind rotation: ") + kBrKindName[kind] + (many ? ", many-LUT)" : ")")).c_str(), e);
@@ -1349,14 +1214,6 @@ int tfhe_hip_ctx_create(const tfhe_hip_params *p, int device, tfhe_hip_ctx **out
       if ((e = set_lds((const void *)km_kernel(nt), ks_mfma_lds_bytes(nt))) != hipSuccess)
         return bail("hipFuncSetAttribute(k_key_switch_mfma)", e);
     }
-#if defined(TFHE_EXPERIMENT) && defined(TFHE_EXP_WIDE1)
-    {
-      const bool keep = ctx->dispatch.exp_wide1;
-      ctx->dispatch.exp_wide1 = true;
-      (void)set_lds((const void *)br_kernel(ctx, BR_SINGLE), blind_rotate_wide_lds_bytes(kMaxN, p->l));
-      ctx->dispatch.exp_wide1 = keep;
-    }
-#endif
   }
   std::vector<double2> tw;
   make_twiddles(tw);
@@ -1372,15 +1229,6 @@ int tfhe_hip_ctx_create(const tfhe_hip_params *p, int device, tfhe_hip_ctx **out
   // (tfhe_hip_set_combining changes it at run time).
   ctx->comb = new Combiner();
   ctx->comb->max_count = combine_max;
-#ifdef TFHE_EXPERIMENT
-  if (const char *env = getenv("TFHE_HIP_COMBINE_LANES")) ctx->comb->nlanes = std::max(1, std::min((int)Combiner::kLanes, atoi(env)));
-  if (const char *env = getenv("TFHE_HIP_COMBINE_ZEROCOPY")) ctx->comb->zero_copy_in = atoi(env) != 0;
-  if (const char *env = getenv("TFHE_HIP_COMBINE_HEAP")) g_comb_force_heap = atoi(env) != 0;
-  if (const char *env = getenv("TFHE_HIP_LANE_PRIORITY")) ctx->comb->lane_high_priority = atoi(env) != 0;
-  if (const char *env = getenv("TFHE_HIP_LINGER_WINDOW_US")) ctx->comb->linger_window_us = atol(env);
-  if (const char *env = getenv("TFHE_HIP_LINGER_QUIET_US")) ctx->comb->linger_quiet_us = atol(env);
-  if (const char *env = getenv("TFHE_HIP_LINGER_MAX_US")) ctx->comb->linger_max_us = atol(env);
-#endif
   *out = ctx;
   return TFHE_HIP_OK;
 }
@@ -2185,17 +2033,6 @@ const char *tfhe_hip_rounding_mode(const tfhe_hip_ctx *ctx) {
   const tfhe_hip_ctx *base = ctx->parent ? ctx->parent : ctx;
   return base->dispatch.fast_round ? "fast" : "general";
 }
-
-#ifdef TFHE_EXPERIMENT
-// experiment builds only (profiles/exp/): the raw diagnostics words, e.g. the per-phase stamps of TFHE_LAT_STAMPS
-extern "C" int tfhe_hip_experiment_diag(tfhe_hip_ctx *ctx, unsigned long long *out, size_t words) {
-  if (!ctx || !out || words > 128) return TFHE_HIP_EINVAL;
-  ENTER(ctx);
-  HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-  HIPCHK(ctx, hipMemcpy(out, ctx->d_diag, words * 8, hipMemcpyDeviceToHost));
-  return TFHE_HIP_OK;
-}
-#endif
 
 int tfhe_hip_set_combining(tfhe_hip_ctx *ctx, size_t max_count) {
   if (!ctx) return TFHE_HIP_EINVAL;

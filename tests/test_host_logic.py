@@ -88,14 +88,34 @@ def test_kernel_selectors_are_validated_without_gpu(monkeypatch):
         monkeypatch.delenv(var)
     # the product library reads exactly the variables the header lists
     src = "".join(open(os.path.join(ROOT, "rs-tfhe_amd", "csrc", f)).read() for f in ("tfhe_hip.hip", "pool.hpp", "combine.hpp"))
-    product = re.sub(r"#ifdef TFHE_EXPERIMENT\n(?:(?!#if|#endif).)*#endif\n", "", src, flags=re.S)  # experiment-only overrides (a flat block)
-    product = re.sub(r"#ifdef TFHE_EXPERIMENT.*?\n#endif\n#endif\n", "", product, flags=re.S)  # ... (a block with one nested #ifdef)
-    read = set(re.findall(r'getenv\("(TFHE_HIP_[A-Z0-9_]+)"\)', product))
+    read = set(re.findall(r'getenv\("(TFHE_HIP_[A-Z0-9_]+)"\)', src))
     hdr = open(os.path.join(ROOT, "include", "tfhe_hip.h")).read()
     assert read == {"TFHE_HIP_BR_KERNEL", "TFHE_HIP_KS_KERNEL", "TFHE_HIP_POOL_RCCL", "TFHE_HIP_POOL_PINNED_STAGING",
                     "TFHE_HIP_COMBINE"}, read
     for v in read:
         assert v in hdr
+
+
+def test_no_experiment_switches_in_product_sources():
+    """The kernels and the host code carry no build-time knobs: the only TFHE_ABL_* names, and the only `#ifndef TFHE_... /
+    #define` override points, are the two mutation switches of `make mutation`, and only experiment.hpp knows of
+    -DTFHE_EXPERIMENT."""
+    import glob
+
+    csrc = os.path.join(ROOT, "rs-tfhe_amd", "csrc")
+    files = sorted(glob.glob(os.path.join(csrc, "*.hpp"))) + [os.path.join(csrc, "tfhe_hip.hip")]
+    assert len(files) >= 10
+    mutations = {"TFHE_ABL_ROUND_LSB", "TFHE_ABL_TW_REL"}
+    abl, overrides, experiment = set(), set(), set()
+    for f in files:
+        src = open(f).read()
+        abl |= set(re.findall(r"\bTFHE_ABL_[A-Z0-9_]+", src))
+        overrides |= set(re.findall(r"#\s*ifndef\s+(TFHE_[A-Z0-9_]+)[^\n]*\n(?:[ \t]*//[^\n]*\n)*\s*#\s*define\s+\1\b", src))
+        if re.search(r"\bTFHE_EXPERIMENT\b", src):
+            experiment.add(os.path.basename(f))
+    assert abl == mutations, abl
+    assert overrides == mutations, overrides
+    assert experiment == {"experiment.hpp"}, experiment
 
 
 def test_pool_create_and_shard_without_gpu():
