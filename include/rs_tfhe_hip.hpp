@@ -568,6 +568,26 @@ struct SecretKey {
     ChaChaRng rng;
     return compressed_cloud_key(rng, device);
   }
+  // tlwe::encrypt_f64 over a batch on the GPU, in the keyed format of include/tfhe_hip.h ("symmetric encryption",
+  // tfhe_hip_batch_encrypt): ciphertext m is row first_index + m, its mask under the PUBLIC 32-byte mask_seed, its noise
+  // under rng_key -- the secret 32-byte generator key, or nullptr to draw it from getrandom(2).  alpha < 0: the set's
+  // alpha_lv0.  Neither a (rng_key, row) nor a (mask_seed, row) pair may encrypt twice.  bodies != nullptr also receives
+  // the seeded form's bodies [count].
+  std::vector<Ciphertext> encrypt_batch(Engine &e, const std::vector<double> &plaintexts, const uint8_t mask_seed[32],
+                                        const uint8_t *rng_key = nullptr, uint64_t first_index = 0, double alpha = -1,
+                                        std::vector<Torus> *bodies = nullptr) const {
+    if (e.params().n != params.n) throw std::runtime_error("secret key has another dimension than the engine's parameter set");
+    std::vector<Torus> plain(plaintexts.size());
+    for (size_t m = 0; m < plain.size(); ++m) plain[m] = f64_to_torus(plaintexts[m]);
+    const size_t w = (size_t)params.n + 1;
+    std::vector<Torus> out(plain.size() * w);
+    if (bodies) bodies->resize(plain.size());
+    e.check(tfhe_hip_batch_encrypt(e.ctx(), key_lv0.data(), plain.data(), plain.size(), alpha < 0 ? params.alpha_lv0 : alpha,
+                                   rng_key, mask_seed, first_index, bodies ? bodies->data() : nullptr, out.data()));
+    std::vector<Ciphertext> res(plain.size(), Ciphertext(params.n));
+    for (size_t m = 0; m < res.size(); ++m) std::memcpy(res[m].p.data(), &out[m * w], w * sizeof(Torus));
+    return res;
+  }
 };
 
 inline PackingKey PackingKey::generate(const SecretKey &sk, int device, const uint8_t *rng_key, double alpha) {
@@ -1107,6 +1127,27 @@ struct PublicKeyLv0 {  // proxy_reenc.rs:95-99
   static PublicKeyLv0 generate(const SecretKey &sk, ChaChaRng &rng) {  // :125-131
     return generate_with_params(sk, (size_t)sk.params.n * 2, sk.params.alpha_lv0, rng);
   }
+  // generate[_with_params] in the keyed format of include/tfhe_hip.h ("symmetric encryption"), made on the GPU
+  // (tfhe_hip_gen_public_key) in a key view that is dropped afterwards.  size 0: 2n; alpha < 0: the set's alpha_lv0;
+  // rng_key: the 32-byte generator key (one key, one public key), or nullptr to draw it from getrandom(2).
+  static PublicKeyLv0 generate(Engine &e, const SecretKey &sk, const uint8_t *rng_key = nullptr, size_t size = 0,
+                               double alpha = -1) {
+    const SecurityParams &p = sk.params;
+    if (e.params().n != p.n) throw std::runtime_error("secret key has another dimension than the engine's parameter set");
+    if (size == 0) size = (size_t)p.n * 2;
+    const size_t w = (size_t)p.n + 1;
+    std::vector<Torus> f(size * w);
+    tfhe_hip_ctx *view = nullptr;
+    e.check(tfhe_hip_key_create(e.ctx(), &view));
+    std::unique_ptr<tfhe_hip_ctx, void (*)(tfhe_hip_ctx *)> h(view, tfhe_hip_ctx_destroy);  // dropped on every exit
+    if (tfhe_hip_gen_public_key(view, sk.key_lv0.data(), size, alpha < 0 ? p.alpha_lv0 : alpha, rng_key, f.data()) != TFHE_HIP_OK)
+      throw std::runtime_error(std::string("tfhe_hip: ") + tfhe_hip_last_error(e.ctx()));
+    PublicKeyLv0 pk;
+    pk.params = p;
+    pk.encryptions.assign(size, Ciphertext(p.n));
+    for (size_t i = 0; i < size; ++i) std::memcpy(pk.encryptions[i].p.data(), &f[i * w], w * sizeof(Torus));
+    return pk;
+  }
   Ciphertext encrypt_f64(double plaintext, double alpha, ChaChaRng &rng) const {  // :168-200
     Ciphertext r(params.n);
     r.b_mut() = f64_to_torus(plaintext);
@@ -1205,6 +1246,23 @@ class ProxyReencryptionKey {  // proxy_reenc.rs:224-233
     public_key_to.load(e, k.view_);
     e.check(tfhe_hip_gen_reenc_key_asymmetric(k.view_, key_from.data(), alpha < 0 ? p.alpha_lv0 : alpha, rng_key,
                                               download ? k.key_encryptions.data() : nullptr));
+    return k;
+  }
+
+  // new_symmetric in the keyed format of include/tfhe_hip.h ("symmetric encryption"), generated on the GPU
+  // (tfhe_hip_gen_reenc_key_symmetric) in a key view of `e` that the returned key keeps: reencrypt uploads nothing.
+  // basebit, t, alpha, rng_key and download as in generate_asymmetric; one rng_key, one key.
+  static ProxyReencryptionKey generate_symmetric(Engine &e, const std::vector<Torus> &key_from, const SecretKey &key_to,
+                                                 const uint8_t *rng_key = nullptr, double alpha = -1, bool download = true) {
+    const SecurityParams &p = e.params();
+    if (key_to.params.n != p.n || key_from.size() != (size_t)p.n)
+      throw std::runtime_error("source or target key has another dimension than the engine's parameter set");
+    ProxyReencryptionKey k;
+    k.params = p;
+    if (download) k.key_encryptions.resize((size_t)p.n * p.iks_t * p.base() * ((size_t)p.n + 1));
+    e.check(tfhe_hip_key_create(e.ctx(), &k.view_));  // (dropped by k's destructor on every path)
+    e.check(tfhe_hip_gen_reenc_key_symmetric(k.view_, key_from.data(), key_to.key_lv0.data(), alpha < 0 ? p.alpha_lv0 : alpha,
+                                             rng_key, download ? k.key_encryptions.data() : nullptr));
     return k;
   }
 

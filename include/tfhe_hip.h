@@ -590,8 +590,8 @@ int tfhe_hip_batch_reencrypt_dev(tfhe_hip_ctx *ctx, const uint32_t *in, uint32_t
  * zeroes the selectors on the device behind each pass; K travels to the kernels as a launch argument.
  * Away from noise samples that sit within rounding of a torus step every implementation of this section gives the same
  * words.
- * Out of scope: pool forms; generating the public key itself on the device (2n ordinary encryptions); the symmetric
- * re-encryption key (n*t*(base-1) ordinary encryptions, no contraction). */
+ * Out of scope: pool forms.  (The public key itself and the symmetric re-encryption key are made on the device by the
+ * next section.) */
 /* encryptions [size][n+1], 1 <= size <= 8192 (TFHE_HIP_EINVAL otherwise, and the previous public key stays).  Builds
  * the byte planes on the device, on a context or a key view; needs no cloud key; a cloud-key or re-encryption-key
  * change leaves it in place; freeing the view frees it. */
@@ -621,6 +621,64 @@ typedef struct tfhe_hip_pk_encrypt_times {
   uint64_t passes;       /* launches of each (one per 65,536 rows)           */
 } tfhe_hip_pk_encrypt_times;
 int tfhe_hip_get_pk_encrypt_times(tfhe_hip_ctx *ctx, tfhe_hip_pk_encrypt_times *out);
+
+/* ---- symmetric encryption: ciphertexts, the public key and the symmetric re-encryption key ------------------------
+ *
+ * Everything made with the SECRET key: ordinary TLWE lv0 encryptions in bulk (TLWELv0::encrypt_f64, src/tlwe.rs:37-53),
+ * the public key's encryptions of zero (PublicKeyLv0::new, src/proxy_reenc.rs:125-153) and the symmetric re-encryption
+ * key (ProxyReencryptionKey::new_symmetric, :362-425).  All three are the same row, made by one wave of one kernel
+ * (csrc/sym_encrypt.hpp); with these every key and ciphertext type of the reference has a device constructor.
+ *
+ * Format (normative).  Keystream words, gauss2 and f64_to_torus are those of the seeded section.  A row index g is
+ * 64 bits; its nonce is (g & 0xffffffff, g >> 32, domain).  Mask word x < n of row g is word x % 16 of the block with
+ * counter x / 16 of the mask stream; the noise is g0 of gauss2(words 0..3 of block 0 of the noise stream, alpha), the
+ * rest of that block unused.
+ *
+ *   use                              row index g                  mask: key, domain              noise: under K, domain
+ *   bulk TLWE lv0                    first_index + m              public seed S, 0x45574C "EWL"  0x45574E "EWN"
+ *                                                                 (the seeded-TLWE masks)
+ *   public key row                   e < size                     K, 0x504B4D "PKM"              0x504B5A "PKZ"
+ *   symmetric re-encryption key row  base*t*i + base*j + k, k>=1  K, 0x524B4D "RKM"              0x524B53 "RKS"
+ *
+ *   row = (a, <a, s0> + plain + f64_to_torus(g0)), wrapping u32.  With alpha == 0 the noise is exactly zero.
+ *   plain: bulk TLWE: the caller's torus word; public key: 0; re-encryption key:
+ *   f64_to_torus(((k * key_from[i]) as u32 as f64) / 2^((j+1)*basebit)) -- the k = 0 rows are zero and their streams are
+ *   unused, as in the asymmetric key.
+ *   A bulk result (S, first_index, bodies) is by construction a seeded TLWE batch: tfhe_hip_expand_seeded_tlwe expands
+ *   it to the words the full form writes.
+ *   The five new domains differ from every other one of this header, so one K may serve all generators.
+ * Security.  (1) A (K, g) pair is used once, whatever S is: two rows with equal noise and different masks give a
+ * noise-free LWE sample of the secret key.  With a caller-held K, first_index must move past every row already used, and
+ * one K makes one public key and one re-encryption key.  (2) An (S, g) pair is used once (the seeded section's rule).
+ * (3) rng_key == NULL draws K from getrandom(2) per call; a caller-held K is as secret as the secret key: whoever can
+ * regenerate the noise reads the key off the rows.  (4) The staged secret keys and K's device copy are zeroed before a
+ * host-form call returns, as tfhe_hip_gen_cloud_key* does; the _dev form, which only enqueues, queues the zeroing on
+ * `stream` behind its kernel.
+ * Away from noise samples that sit within rounding of a torus step every implementation of this section gives the same
+ * words.
+ * Out of scope: pool forms. */
+/* key_lv0 [n] (host memory in both forms), plain [count] torus words -> bodies [count] and / or out [count][n+1]; either
+ * may be NULL, and with out == NULL no mask is written (the seeded form).  Needs no key on the handle; every parameter
+ * set (n <= 1279).  TFHE_HIP_EINVAL for a NULL key_lv0, mask_seed or plain, for bodies and out both NULL with count > 0,
+ * alpha negative or NaN, first_index + count beyond 2^64.  count == 0 returns TFHE_HIP_OK.  _dev: plain / bodies / out
+ * are device pointers, queued on `stream` (NULL: the context's stream). */
+int tfhe_hip_batch_encrypt(tfhe_hip_ctx *ctx, const uint32_t *key_lv0, const uint32_t *plain, size_t count, double alpha,
+                           const uint8_t rng_key[32], const uint8_t mask_seed[32], uint64_t first_index,
+                           uint32_t *bodies, uint32_t *out);
+int tfhe_hip_batch_encrypt_dev(tfhe_hip_ctx *ctx, const uint32_t *key_lv0, const uint32_t *plain, size_t count, double alpha,
+                               const uint8_t rng_key[32], const uint8_t mask_seed[32], uint64_t first_index,
+                               uint32_t *bodies, uint32_t *out, void *stream);
+/* `size` encryptions of zero under key_lv0 [n], 1 <= size <= 8192 (TFHE_HIP_EINVAL otherwise, and the previous public
+ * key stays).  The handle is left holding the public key -- bit for bit what tfhe_hip_load_public_key(encryptions_out)
+ * builds; encryptions_out [size][n+1] may be NULL (no download). */
+int tfhe_hip_gen_public_key(tfhe_hip_ctx *ctx_or_view, const uint32_t *key_lv0, size_t size, double alpha,
+                            const uint8_t rng_key[32], uint32_t *encryptions_out);
+/* The symmetric re-encryption key from key_from [n] to key_to [n] (both secret: a call for whoever holds both), with
+ * basebit and t of the context's parameter set.  The handle is left holding it -- bit for bit what
+ * tfhe_hip_load_reenc_key(key_out) builds; key_out [n][t][base][n+1] may be NULL (no download).  TFHE_HIP_EINVAL for
+ * n > 1024, a NULL key, alpha negative or NaN.  A refused call leaves the handle's keys as they were. */
+int tfhe_hip_gen_reenc_key_symmetric(tfhe_hip_ctx *ctx_or_view, const uint32_t *key_from, const uint32_t *key_to,
+                                     double alpha, const uint8_t rng_key[32], uint32_t *key_out);
 
 /* Replaces: FFTProcessor::{ifft, fft, poly_mul, batch_ifft, batch_fft}
  * (src/fft/mod.rs:80-107; KlemsaProcessor src/fft/klemsa.rs:88-174) and the

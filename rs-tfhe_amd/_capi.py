@@ -147,6 +147,10 @@ SIGNATURES = {
     "tfhe_hip_batch_pk_encrypt_dev": (C.c_int, [_CTX, _P, _SZ, C.c_double, _P, C.c_uint64, _P, _P]),
     "tfhe_hip_gen_reenc_key_asymmetric": (C.c_int, [_CTX, _P, C.c_double, _P, _P]),
     "tfhe_hip_get_pk_encrypt_times": (C.c_int, [_CTX, C.POINTER(PkEncryptTimes)]),
+    "tfhe_hip_batch_encrypt": (C.c_int, [_CTX, _P, _P, _SZ, C.c_double, _P, _P, C.c_uint64, _P, _P]),
+    "tfhe_hip_batch_encrypt_dev": (C.c_int, [_CTX, _P, _P, _SZ, C.c_double, _P, _P, C.c_uint64, _P, _P, _P]),
+    "tfhe_hip_gen_public_key": (C.c_int, [_CTX, _P, _SZ, C.c_double, _P, _P]),
+    "tfhe_hip_gen_reenc_key_symmetric": (C.c_int, [_CTX, _P, _P, C.c_double, _P, _P]),
     "tfhe_hip_batch_ifft": (C.c_int, [_CTX, _P, _P, _SZ]),
     "tfhe_hip_batch_fft": (C.c_int, [_CTX, _P, _P, _SZ]),
     "tfhe_hip_batch_poly_mul": (C.c_int, [_CTX, _P, _P, _P, _SZ]),

@@ -19,6 +19,11 @@ default everywhere -- draws from the operating system's CSPRNG (`os.urandom`); p
 seed or a numpy Generator selects numpy's PCG64 instead, which is reproducible and NOT
 cryptographic: tests and benchmarks only.  A guessable generator behind `SecretKey.new`,
 `encrypt_*` or `cloud_key` gives the secret key away.
+
+`encrypt_*` and `encrypt_*_seeded` also exist in the keyed format of include/tfhe_hip.h ("symmetric encryption"):
+`rng_key=` (a secret 32-byte generator key) alone is its CPU form, `device=` runs it on the GPU
+(`tfhe_hip_batch_encrypt`; rng_key=None there draws the key from getrandom(2)), `first_index=` places the batch in the
+streams.  A (rng_key, row) pair must never encrypt twice.
 """
 from __future__ import annotations
 
@@ -98,22 +103,60 @@ class SecretKey:
     def _cts(self, cts) -> np.ndarray:
         return np.ascontiguousarray(cts, dtype=np.uint32).reshape(-1, self.params.n + 1)
 
-    def encrypt_f64(self, p, seed=None, alpha: float | None = None) -> np.ndarray:
+    def _keyed(self, seed, rng_key, first_index, device, count: int) -> bool:
+        """Whether a call asks for the keyed format of include/tfhe_hip.h ("symmetric encryption"), with its checks"""
+        if rng_key is None and device is None:
+            if int(first_index) != 0:
+                raise ValueError("first_index belongs to the keyed format: give rng_key or device")
+            return False
+        if seed is not None:
+            raise ValueError("seed selects numpy's generator; rng_key / device select the keyed format")
+        if rng_key is not None and (not isinstance(rng_key, (bytes, bytearray)) or len(rng_key) != 32):
+            raise ValueError("rng_key is 32 bytes")
+        if not (0 <= int(first_index) and int(first_index) + count <= 1 << 64):
+            raise ValueError("the ciphertext indices run past 2^64")
+        return True
+
+    def _encrypt_keyed(self, p, alpha, rng_key, mask_seed, first_index, device, full: bool):
+        """encrypt_f64 in the keyed format: [count][n+1] (full) or seeded.SeededCiphertexts"""
+        from .seeded import DOMAINS_SYM_TLWE, SeededCiphertexts, symmetric_rows
+
+        mask_seed = os.urandom(32) if mask_seed is None else bytes(mask_seed)
+        if len(mask_seed) != 32:
+            raise ValueError("mask_seed is 32 bytes")
+        if device is not None:
+            from .bootstrap import engine_for
+
+            return engine_for(self.params, device).batch_encrypt(self.key_lv0, f64_to_torus(p), alpha, rng_key, mask_seed,
+                                                                 first_index, full=full, bodies=not full)
+        rows = np.uint64(int(first_index)) + np.arange(len(p), dtype=np.uint64)
+        got = symmetric_rows(mask_seed, bytes(rng_key), rows, self.key_lv0, f64_to_torus(p), alpha, DOMAINS_SYM_TLWE, full)
+        return got if full else SeededCiphertexts(self.params, mask_seed, first_index, got)
+
+    def encrypt_f64(self, p, seed=None, alpha: float | None = None, rng_key=None, first_index: int = 0, device=None,
+                    mask_seed: bytes = None) -> np.ndarray:
         """tlwe.rs:37-53: a uniform, b = <a, s> + f64_to_torus(p) + f64_to_torus(N(0, alpha)).
-        p: scalar or [count]; returns [count][n+1] u32."""
-        g = _rng(seed)
+        p: scalar or [count]; returns [count][n+1] u32.
+        rng_key / first_index / device: the keyed format of include/tfhe_hip.h ("symmetric encryption"), ciphertext m at
+        row first_index + m: masks under the public mask_seed (None: fresh from the OS), noise under the secret 32-byte
+        rng_key -- on the CPU with rng_key alone, on GPU `device` otherwise (rng_key=None there: a key from
+        getrandom(2)).  A (rng_key, row) pair must never encrypt twice."""
         p = np.atleast_1d(np.asarray(p, dtype=np.float64))
         alpha = self.params.alpha_lv0 if alpha is None else alpha
+        if self._keyed(seed, rng_key, first_index, device, len(p)):
+            return self._encrypt_keyed(p, alpha, rng_key, mask_seed, first_index, device, True)
+        g = _rng(seed)
         out = np.empty((len(p), self.params.n + 1), np.uint32)
         out[:, :-1] = g.integers(0, 1 << 32, (len(p), self.params.n), dtype=np.uint64).astype(np.uint32)
         noise = f64_to_torus(g.normal(0.0, alpha, len(p))) if alpha > 0 else np.zeros(len(p), np.uint32)
         out[:, -1] = self._inner(out) + f64_to_torus(p) + noise
         return out
 
-    def encrypt_bool(self, bits, seed=None, alpha: float | None = None) -> np.ndarray:
+    def encrypt_bool(self, bits, seed=None, alpha: float | None = None, rng_key=None, first_index: int = 0, device=None,
+                     mask_seed: bytes = None) -> np.ndarray:
         """tlwe.rs:55-58: true -> +1/8, false -> -1/8."""
         bits = np.atleast_1d(np.asarray(bits)).astype(bool)
-        return self.encrypt_f64(np.where(bits, 0.125, -0.125), seed, alpha)
+        return self.encrypt_f64(np.where(bits, 0.125, -0.125), seed, alpha, rng_key, first_index, device, mask_seed)
 
     def phase(self, cts) -> np.ndarray:
         """b - <a, s> (u32)."""
@@ -124,11 +167,13 @@ class SecretKey:
         """tlwe.rs:60-68: the phase read as i32 is non-negative."""
         return self.phase(cts).view(np.int32) >= 0
 
-    def encrypt_lwe_message(self, msgs, message_modulus: int, seed=None, alpha: float | None = None) -> np.ndarray:
+    def encrypt_lwe_message(self, msgs, message_modulus: int, seed=None, alpha: float | None = None, rng_key=None,
+                            first_index: int = 0, device=None, mask_seed: bytes = None) -> np.ndarray:
         """tlwe.rs:84-98: (msg mod m) / (2m)."""
         m = int(message_modulus)
         msgs = np.atleast_1d(np.asarray(msgs)).astype(np.int64) % m
-        return self.encrypt_f64(msgs.astype(np.float64) * (1.0 / (2.0 * m)), seed, alpha)
+        return self.encrypt_f64(msgs.astype(np.float64) * (1.0 / (2.0 * m)), seed, alpha, rng_key, first_index, device,
+                                mask_seed)
 
     def decrypt_lwe_message(self, cts, message_modulus: int) -> np.ndarray:
         """tlwe.rs:111-126: ((phase / 2^32) / scale + 0.5) as usize % m, scale = 1/(2m)."""
@@ -242,17 +287,21 @@ class SecretKey:
         finally:
             view.close()
 
-    def encrypt_f64_seeded(self, p, mask_seed: bytes = None, first_index: int = 0, seed=None, alpha: float | None = None):
+    def encrypt_f64_seeded(self, p, mask_seed: bytes = None, first_index: int = 0, seed=None, alpha: float | None = None,
+                           rng_key=None, device=None):
         """encrypt_f64 with the masks of the seeded TLWE format: returns seeded.SeededCiphertexts (bodies only).
         mask_seed=None draws a fresh one from the OS.  Never encrypt twice under one (mask_seed, index): the
         difference of the two bodies is the difference of the messages plus noise.  `seed` / `alpha` pick the noise
-        as in encrypt_f64."""
+        as in encrypt_f64.  rng_key / device: the noise in the keyed format of include/tfhe_hip.h ("symmetric
+        encryption") -- on the CPU with rng_key alone, on GPU `device` otherwise, where no mask is made at all."""
         from .seeded import SeededCiphertexts, tlwe_masks
 
-        mask_seed = os.urandom(32) if mask_seed is None else bytes(mask_seed)
-        g = _rng(seed)
         p = np.atleast_1d(np.asarray(p, dtype=np.float64))
         alpha = self.params.alpha_lv0 if alpha is None else alpha
+        if (rng_key is not None or device is not None) and self._keyed(seed, rng_key, first_index, device, len(p)):
+            return self._encrypt_keyed(p, alpha, rng_key, mask_seed, first_index, device, False)
+        mask_seed = os.urandom(32) if mask_seed is None else bytes(mask_seed)
+        g = _rng(seed)
         sc = SeededCiphertexts(self.params, mask_seed, first_index, np.zeros(len(p), np.uint32))
         if int(first_index) + len(p) > 1 << 64:
             raise ValueError("the ciphertext indices run past 2^64")
@@ -266,14 +315,15 @@ class SecretKey:
         return sc
 
     def encrypt_bool_seeded(self, bits, mask_seed: bytes = None, first_index: int = 0, seed=None,
-                            alpha: float | None = None):
+                            alpha: float | None = None, rng_key=None, device=None):
         """encrypt_bool in the seeded form (see encrypt_f64_seeded)."""
         bits = np.atleast_1d(np.asarray(bits)).astype(bool)
-        return self.encrypt_f64_seeded(np.where(bits, 0.125, -0.125), mask_seed, first_index, seed, alpha)
+        return self.encrypt_f64_seeded(np.where(bits, 0.125, -0.125), mask_seed, first_index, seed, alpha, rng_key, device)
 
     def encrypt_lwe_message_seeded(self, msgs, message_modulus: int, mask_seed: bytes = None, first_index: int = 0,
-                                   seed=None, alpha: float | None = None):
+                                   seed=None, alpha: float | None = None, rng_key=None, device=None):
         """encrypt_lwe_message in the seeded form (see encrypt_f64_seeded)."""
         m = int(message_modulus)
         msgs = np.atleast_1d(np.asarray(msgs)).astype(np.int64) % m
-        return self.encrypt_f64_seeded(msgs.astype(np.float64) * (1.0 / (2.0 * m)), mask_seed, first_index, seed, alpha)
+        return self.encrypt_f64_seeded(msgs.astype(np.float64) * (1.0 / (2.0 * m)), mask_seed, first_index, seed, alpha,
+                                       rng_key, device)

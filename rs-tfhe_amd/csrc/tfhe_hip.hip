@@ -184,6 +184,7 @@ struct tfhe_hip_ctx {
   DevBuf lv1, u1, u2, ks_out, ks_dig;  // scratch (ks_dig: key-switch digit bytes)
   DevBuf biv_s1, biv_tv;               // tree bootstrap (table.hpp): stage-1 results [m][chunk][n+1], their tables [chunk][2][N]
   DevBuf pke_sel;                      // public-key encryption (pk_encrypt.hpp): selector words and addends of one pass
+  DevBuf sym_sec;                      // symmetric encryption (sym_encrypt.hpp): the staged keys of one call, wiped behind it
   // host-API staging: a / b / c / out also stage through their arenas on pool members (to_dev / to_host);
   // the arenas of tv / idx serve the combiner lanes only
   Staging a{{}, {}, true}, b{{}, {}, true}, c{{}, {}, true}, out{{}, {}, true}, tv, idx;
@@ -1292,7 +1293,7 @@ void tfhe_hip_ctx_destroy(tfhe_hip_ctx *ctx) {
       (void)hipEventDestroy(p.second);
     }
   Staging *stage[] = {&ctx->a, &ctx->b, &ctx->c, &ctx->out, &ctx->tv, &ctx->idx};
-  for (DevBuf *b : {&ctx->lv1, &ctx->u1, &ctx->u2, &ctx->ks_out, &ctx->ks_dig, &ctx->biv_s1, &ctx->biv_tv, &ctx->pke_sel})
+  for (DevBuf *b : {&ctx->lv1, &ctx->u1, &ctx->u2, &ctx->ks_out, &ctx->ks_dig, &ctx->biv_s1, &ctx->biv_tv, &ctx->pke_sel, &ctx->sym_sec})
     if (b->p) (void)hipFree(b->p);
   for (Staging *s : stage)
     if (s->dev.p) (void)hipFree(s->dev.p);
@@ -2108,3 +2109,4 @@ int tfhe_hip_synchronize(tfhe_hip_ctx *ctx) {
 #include "table.hpp"
 #include "packing_keygen.hpp"
 #include "pk_encrypt.hpp"
+#include "sym_encrypt.hpp"

@@ -2,6 +2,7 @@
 from __future__ import annotations
 
 import ctypes as C
+import os
 import threading
 import weakref
 from typing import Optional
@@ -811,6 +812,81 @@ class Engine(_Handle):
         rk, rkp = self._rng_key_arg(rng_key)
         self._chk(self._lib.tfhe_hip_gen_reenc_key_asymmetric(self._ctx, _ptr(k0), C.c_double(p.alpha_lv0 if alpha is None else alpha),
                                                               rkp, _ptr(key)))
+        return key
+
+    # -- symmetric encryption: ciphertexts, the public key, the symmetric re-encryption key (include/tfhe_hip.h) --------
+    def _key_lv0_arg(self, key_lv0) -> np.ndarray:
+        k0 = _u32(getattr(key_lv0, "key_lv0", key_lv0)).reshape(-1)
+        if len(k0) != self.params.n:
+            raise ValueError("secret key has the wrong size for these parameters")
+        return k0
+
+    def batch_encrypt(self, key_lv0, plain, alpha: float = None, rng_key: bytes = None, mask_seed: bytes = None,
+                      first_index: int = 0, full: bool = True, bodies: bool = False):
+        """plain [count] torus words -> TLWE lv0 encryptions under key_lv0 [n], row m at index first_index + m of the
+        streams (`tfhe_hip_batch_encrypt`): masks under the public mask_seed (None: 32 fresh bytes from the OS), noise
+        under rng_key (None: the library draws it from getrandom(2)).  full: return [count][n+1]; bodies: return
+        seeded.SeededCiphertexts; both: (full, seeded).  Neither a (rng_key, index) nor a (mask_seed, index) pair may
+        encrypt twice."""
+        from .seeded import SeededCiphertexts
+
+        if not (full or bodies):
+            raise ValueError("nothing to return: full and bodies are both off")
+        k0 = self._key_lv0_arg(key_lv0)
+        plain = _u32(plain).reshape(-1)
+        mask_seed = os.urandom(32) if mask_seed is None else _seed_bytes(mask_seed)
+        seed = (C.c_uint8 * 32).from_buffer_copy(mask_seed)
+        out = np.empty((len(plain), self.params.n + 1), np.uint32) if full else None
+        bod = np.empty(len(plain), np.uint32) if bodies else None
+        rk, rkp = self._rng_key_arg(rng_key)
+        alpha = self.params.alpha_lv0 if alpha is None else alpha
+        self._chk(self._lib.tfhe_hip_batch_encrypt(self._ctx, _ptr(k0), _ptr(plain), len(plain), C.c_double(alpha), rkp,
+                                                   C.addressof(seed), C.c_uint64(int(first_index)), _ptr(bod), _ptr(out)))
+        sc = SeededCiphertexts(self.params, mask_seed, first_index, bod) if bodies else None
+        return (out, sc) if full and bodies else (out if full else sc)
+
+    def batch_encrypt_dev(self, key_lv0, plain, alpha: float, mask_seed: bytes, rng_key: bytes = None, first_index: int = 0,
+                          bodies=None, out=None, stream=None) -> None:
+        """Device form: plain [count], bodies [count] and out [count][n+1] torch tensors (32-bit words) on this engine's
+        GPU, bodies or out may be None; key_lv0 stays a host array.  Enqueues on `stream`."""
+        k0 = self._key_lv0_arg(key_lv0)
+        if plain.dim() != 1:
+            raise ValueError("plain must be [count]")
+        count = plain.shape[0]
+        if bodies is not None and (bodies.dim() != 1 or bodies.shape[0] != count):
+            raise ValueError(f"bodies must be [{count}]")
+        if out is not None and (out.dim() != 2 or out.shape[0] != count or out.shape[1] != self.params.n + 1):
+            raise ValueError(f"out must be [{count}][{self.params.n + 1}]")
+        seed = (C.c_uint8 * 32).from_buffer_copy(_seed_bytes(mask_seed))
+        rk, rkp = self._rng_key_arg(rng_key)
+        self._chk(self._lib.tfhe_hip_batch_encrypt_dev(
+            self._ctx, _ptr(k0), self._tp(None, plain), count, C.c_double(alpha), rkp, C.addressof(seed),
+            C.c_uint64(int(first_index)), self._tp(None, bodies) if bodies is not None else None,
+            self._tp(None, out) if out is not None else None, self._stream_ptr(None, stream)))
+
+    def gen_public_key(self, key_lv0, size: int = None, alpha: float = None, rng_key: bytes = None, download: bool = True):
+        """PublicKeyLv0::new (proxy_reenc.rs:125-153) on the GPU, left loaded on this handle (`tfhe_hip_gen_public_key`):
+        `size` (2n by default) encryptions of zero under key_lv0 at alpha (alpha_lv0 by default).  Returns the
+        encryptions [size][n+1], or None with download=False."""
+        p = self.params
+        k0 = self._key_lv0_arg(key_lv0)
+        size = 2 * p.n if size is None else int(size)
+        enc = np.empty((max(size, 0), p.n + 1), np.uint32) if download else None
+        rk, rkp = self._rng_key_arg(rng_key)
+        self._chk(self._lib.tfhe_hip_gen_public_key(self._ctx, _ptr(k0), size, C.c_double(p.alpha_lv0 if alpha is None else alpha),
+                                                    rkp, _ptr(enc)))
+        return enc
+
+    def gen_reenc_key_symmetric(self, key_from, key_to, alpha=None, rng_key: bytes = None, download: bool = True):
+        """ProxyReencryptionKey::new_symmetric (proxy_reenc.rs:362-425) on the GPU, left loaded on this handle
+        (`tfhe_hip_gen_reenc_key_symmetric`), with basebit and t of this engine's set.  Returns key_encryptions
+        [n t base][n+1], or None with download=False (the key stays on the GPU)."""
+        p = self.params
+        kf, kt = self._key_lv0_arg(key_from), self._key_lv0_arg(key_to)
+        key = np.empty((p.n * p.iks_t * p.base, p.n + 1), np.uint32) if download else None
+        rk, rkp = self._rng_key_arg(rng_key)
+        self._chk(self._lib.tfhe_hip_gen_reenc_key_symmetric(self._ctx, _ptr(kf), _ptr(kt),
+                                                             C.c_double(p.alpha_lv0 if alpha is None else alpha), rkp, _ptr(key)))
         return key
 
     def pk_encrypt_times(self) -> dict:

@@ -18,6 +18,11 @@ encryption and the asymmetric re-encryption key"): every selector bit and noise 
 keystream under a secret 32-byte generator key.  `rng_key=` alone is the CPU form of that format (`encrypt_rows`
 below); `device=` runs it on the GPU (`tfhe_hip_batch_pk_encrypt`, `tfhe_hip_gen_reenc_key_asymmetric`), where
 rng_key=None draws the key from getrandom(2).  A (rng_key, row index) pair must never encrypt two messages.
+
+What is made with the SECRET key -- `PublicKeyLv0.new` and `ProxyReencryptionKey.new_symmetric` -- takes the same two
+arguments, in the format of the header's "symmetric encryption" section (`seeded.symmetric_rows` is its CPU form;
+`tfhe_hip_gen_public_key` and `tfhe_hip_gen_reenc_key_symmetric` run it on the GPU and leave the key on its view).  There
+a caller-held rng_key is as secret as the secret key, and one rng_key makes one key.
 """
 from __future__ import annotations
 
@@ -79,15 +84,40 @@ class PublicKeyLv0:
         self._view = None
 
     @classmethod
-    def new(cls, secret_key: SecretKey, seed=None) -> "PublicKeyLv0":
+    def new(cls, secret_key: SecretKey, seed=None, rng_key=None, device=None) -> "PublicKeyLv0":
         """proxy_reenc.rs:125-131: 2n encryptions of zero at the level-0 noise."""
         p = secret_key.params
-        return cls.new_with_params(secret_key, 2 * p.n, p.alpha_lv0, seed)
+        return cls.new_with_params(secret_key, 2 * p.n, p.alpha_lv0, seed, rng_key, device)
 
     @classmethod
-    def new_with_params(cls, secret_key: SecretKey, size: int, alpha: float, seed=None) -> "PublicKeyLv0":
-        """proxy_reenc.rs:144-153."""
-        return cls(secret_key.params, secret_key.encrypt_f64(np.zeros(int(size)), seed, alpha))
+    def new_with_params(cls, secret_key: SecretKey, size: int, alpha: float, seed=None, rng_key=None,
+                        device=None) -> "PublicKeyLv0":
+        """proxy_reenc.rs:144-153.
+        rng_key / device: the keyed format of include/tfhe_hip.h ("symmetric encryption", row e of the "PKM" / "PKZ"
+        streams) -- on the CPU with rng_key alone; with `device` the key is generated in a key view of that GPU
+        (`tfhe_hip_gen_public_key`; rng_key=None: a key from getrandom(2)) which the returned object keeps, so
+        `encrypt_f64(device=)` uploads nothing.  One rng_key makes one public key."""
+        p = secret_key.params
+        if rng_key is None and device is None:
+            return cls(p, secret_key.encrypt_f64(np.zeros(int(size)), seed, alpha))
+        if seed is not None:
+            raise ValueError("seed selects numpy's generator; rng_key / device select the keyed format")
+        if not 1 <= int(size) <= MAX_PUBLIC_KEY_SIZE:
+            raise ValueError(f"public key size must be in [1, {MAX_PUBLIC_KEY_SIZE}]")
+        if device is None:
+            rows = np.arange(int(size), dtype=np.uint64)
+            k = _rng_key(rng_key)
+            return cls(p, seeded.symmetric_rows(k, k, rows, secret_key.key_lv0, 0, alpha, seeded.DOMAINS_SYM_PK))
+        from .bootstrap import engine_for
+
+        v = engine_for(p, device).new_key_view()
+        try:
+            pk = cls(p, v.gen_public_key(secret_key.key_lv0, int(size), alpha, rng_key))
+        except Exception:
+            v.close()
+            raise
+        pk._view = (device, v)
+        return pk
 
     def encrypt_f64(self, plaintext, alpha: float, seed=None, rng_key=None, first_index: int = 0, device=None) -> np.ndarray:
         """proxy_reenc.rs:168-200, batched over `plaintext`: every encryption of zero joins with probability 1/2, added
@@ -179,17 +209,44 @@ class ProxyReencryptionKey:
         return val / (1 << ((j + 1) * basebit)).astype(np.float64)  # [n][t][base]
 
     @classmethod
-    def new_symmetric(cls, key_from, key_to: SecretKey, seed=None) -> "ProxyReencryptionKey":
+    def new_symmetric(cls, key_from, key_to: SecretKey, seed=None, rng_key=None, device=None) -> "ProxyReencryptionKey":
         """proxy_reenc.rs:362-370: the set's key-switch noise, basebit and t."""
         p = key_to.params
-        return cls.new_symmetric_with_params(key_from, key_to, p.alpha_lv0, p.basebit, p.iks_t, seed)
+        return cls.new_symmetric_with_params(key_from, key_to, p.alpha_lv0, p.basebit, p.iks_t, seed, rng_key, device)
 
     @classmethod
     def new_symmetric_with_params(cls, key_from, key_to: SecretKey, alpha: float, basebit: int, t: int,
-                                  seed=None) -> "ProxyReencryptionKey":
-        """proxy_reenc.rs:389-425: TLWELv0::encrypt_f64(p, alpha, key_to) per (i, j, k != 0)."""
+                                  seed=None, rng_key=None, device=None) -> "ProxyReencryptionKey":
+        """proxy_reenc.rs:389-425: TLWELv0::encrypt_f64(p, alpha, key_to) per (i, j, k != 0).
+        rng_key / device: the keyed format of include/tfhe_hip.h ("symmetric encryption", row base t i + base j + k of
+        the "RKM" / "RKS" streams) -- on the CPU with rng_key alone; with `device` the key is generated in a key view of
+        that GPU (`tfhe_hip_gen_reenc_key_symmetric`; rng_key=None: a key from getrandom(2)) which the returned object
+        keeps, so `reencrypt` uploads nothing.  One rng_key makes one re-encryption key."""
         p = key_to.params
         pts = cls._plaintexts(_key_lv0(key_from), basebit, t)
+        if rng_key is not None or device is not None:
+            if seed is not None:
+                raise ValueError("seed selects numpy's generator; rng_key / device select the keyed format")
+            if device is not None:
+                from .bootstrap import engine_for
+
+                if p.n > 1024:
+                    raise ValueError(f"proxy re-encryption on the GPU needs n <= 1024 ({p.name}: n = {p.n})")
+                v = engine_for(_engine_params(p, int(basebit), int(t)), device).new_key_view()
+                try:
+                    key = cls(p, v.gen_reenc_key_symmetric(_key_lv0(key_from), key_to.key_lv0, alpha, rng_key), basebit, t)
+                except Exception:
+                    v.close()
+                    raise
+                key._view = (device, v)
+                return key
+            rows = np.arange(pts.size, dtype=np.uint64)
+            live = rows % np.uint64(1 << basebit) != 0
+            enc = np.zeros((pts.size, p.n + 1), np.uint32)
+            k = _rng_key(rng_key)
+            enc[live] = seeded.symmetric_rows(k, k, rows[live], key_to.key_lv0, f64_to_torus(pts.reshape(-1)[live]), alpha,
+                                              seeded.DOMAINS_SYM_RK)
+            return cls(p, enc, basebit, t)
         enc = key_to.encrypt_f64(pts.reshape(-1), seed, alpha).reshape(p.n, t, 1 << basebit, p.n + 1)
         enc[:, :, 0, :] = 0
         return cls(p, enc, basebit, t)

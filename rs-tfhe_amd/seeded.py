@@ -16,6 +16,11 @@ DOMAIN_KSK = 0x4B534B
 DOMAIN_BSK = 0x42534B
 DOMAIN_TLWE = 0x45574C
 DOMAIN_SEED = 0x444553
+# symmetric encryption (include/tfhe_hip.h): (mask domain, noise domain) of the three uses; the index g of a row is 64
+# bits and rides in the nonce (g & 0xffffffff, g >> 32, domain)
+DOMAINS_SYM_TLWE = (DOMAIN_TLWE, 0x45574E)  # "EWL" masks under the public seed S, "EWN" noise under K
+DOMAINS_SYM_PK = (0x504B4D, 0x504B5A)       # "PKM", "PKZ": rows of the public key, both under K
+DOMAINS_SYM_RK = (0x524B4D, 0x524B53)       # "RKM", "RKS": rows of the symmetric re-encryption key, both under K
 _SIGMA = (0x61707865, 0x3320646E, 0x79622D32, 0x6B206574)
 _QR = ((0, 4, 8, 12), (1, 5, 9, 13), (2, 6, 10, 14), (3, 7, 11, 15),
        (0, 5, 10, 15), (1, 6, 11, 12), (2, 7, 8, 13), (3, 4, 9, 14))
@@ -197,6 +202,29 @@ def tlwe_masks(seed: bytes, first_index: int, count: int, n: int) -> np.ndarray:
     """Masks of seeded TLWE ciphertexts first_index .. first_index + count - 1: [count, n] u32."""
     g = np.uint64(int(first_index)) + np.arange(count, dtype=np.uint64)
     return keystream(seed, n, g & np.uint64(0xFFFFFFFF), g >> np.uint64(32), DOMAIN_TLWE)
+
+
+def symmetric_rows(mask_key: bytes, rng_key: bytes, rows, key_lv0, plain, alpha: float, domains, full: bool = True,
+                   chunk: int = 8192) -> np.ndarray:
+    """The CPU form of the symmetric-encryption format: row g of `rows` (u64 indices) is
+    (a, <a, s0> + plain + f64_to_torus(g0)) with the mask a under (mask_key, g, domains[0]) and g0 of
+    gauss2(words 0..3 of block 0 of (rng_key, g, domains[1]), alpha).  Returns [rows][n+1], or the bodies with full=False."""
+    g = np.asarray(rows, np.uint64).reshape(-1)
+    s0 = np.asarray(key_lv0, np.uint32).reshape(-1)
+    n = len(s0)
+    plain = np.broadcast_to(np.asarray(plain, np.uint32).reshape(-1), g.shape)
+    out = np.empty((len(g), n + 1 if full else 1), np.uint32)
+    lo32, hi32 = g & np.uint64(0xFFFFFFFF), g >> np.uint64(32)
+    with np.errstate(over="ignore"):
+        for lo in range(0, len(g), chunk):
+            sl = slice(lo, lo + chunk)
+            masks = keystream(mask_key, n, lo32[sl], hi32[sl], domains[0])
+            g0, _ = gauss2(chacha20_block(rng_key, 0, lo32[sl], hi32[sl], domains[1])[:, :4], float(alpha))
+            inner = (masks * s0[None, :]).sum(axis=1, dtype=np.uint32)
+            if full:
+                out[sl, :-1] = masks
+            out[sl, -1] = inner + plain[sl] + f64_to_torus(g0)
+    return out if full else out[:, 0].copy()
 
 
 class SeededCiphertexts:

@@ -113,6 +113,15 @@ extern "C" {   // packing key switch (include/tfhe_hip.h): up to N lv0 results i
     fn tfhe_hip_gen_reenc_key_asymmetric(ctx_or_view: *mut TfheHipCtx, key_from: *const u32, alpha: f64,
                                          rng_key: *const u8, key_out: *mut u32) -> c_int;
     fn tfhe_hip_batch_reencrypt(ctx: *mut TfheHipCtx, input: *const u32, out: *mut u32, count: usize) -> c_int;
+    // symmetric encryption (include/tfhe_hip.h): bulk ciphertexts, the public key and the symmetric re-encryption key
+    // made on the device; no pool forms either
+    fn tfhe_hip_batch_encrypt(ctx: *mut TfheHipCtx, key_lv0: *const u32, plain: *const u32, count: usize, alpha: f64,
+                              rng_key: *const u8, mask_seed: *const u8, first_index: u64, bodies: *mut u32,
+                              out: *mut u32) -> c_int;
+    fn tfhe_hip_gen_public_key(ctx_or_view: *mut TfheHipCtx, key_lv0: *const u32, size: usize, alpha: f64,
+                               rng_key: *const u8, encryptions_out: *mut u32) -> c_int;
+    fn tfhe_hip_gen_reenc_key_symmetric(ctx_or_view: *mut TfheHipCtx, key_from: *const u32, key_to: *const u32,
+                                        alpha: f64, rng_key: *const u8, key_out: *mut u32) -> c_int;
 }
 
 /// A member context of a pool (tfhe_hip_pool_ctx): opaque, owned by the pool.
@@ -519,7 +528,63 @@ impl HipEngine {
         key
     }
 
-    /// reencrypt_tlwe_lv0 over `cts` ([count][n+1], flat) under the key `gen_reenc_key_asymmetric` left on the view.
+    /// TLWELv0::encrypt_f64 over a batch on the GPU, in the keyed format of include/tfhe_hip.h ("symmetric encryption",
+    /// `tfhe_hip_batch_encrypt`): `plain` are torus words, ciphertext m is row `first_index + m`, its mask under the
+    /// PUBLIC `mask_seed`, its noise under `rng_key` (the secret 32-byte generator key; None draws it from
+    /// getrandom(2)).  Neither a (rng_key, row) nor a (mask_seed, row) pair may encrypt twice.  Returns [count][n+1],
+    /// flat; with `bodies` the seeded form's bodies [count] are written there too.  Runs on the pool's first member.
+    pub fn encrypt_batch(&self, key_lv0: &[u32], plain: &[u32], alpha: f64, rng_key: Option<&[u8; 32]>,
+                         mask_seed: &[u8; 32], first_index: u64, bodies: Option<&mut [u32]>) -> Vec<u32> {
+        assert_eq!(key_lv0.len(), params::tlwe_lv0::N, "key_lv0 is [n]");
+        let mut out = vec![0u32; plain.len() * W];
+        let bp = match bodies {
+            Some(b) => { assert_eq!(b.len(), plain.len(), "bodies is [count]"); b.as_mut_ptr() }
+            None => std::ptr::null_mut(),
+        };
+        let ctx = unsafe { tfhe_hip_pool_ctx(self.pool, 0) };
+        assert!(!ctx.is_null(), "tfhe_hip_pool_ctx failed");
+        let rk = rng_key.map_or(std::ptr::null(), |k| k.as_ptr());
+        Self::check_ctx(ctx, unsafe {
+            tfhe_hip_batch_encrypt(ctx, key_lv0.as_ptr(), plain.as_ptr(), plain.len(), alpha, rk, mask_seed.as_ptr(),
+                                   first_index, bp, out.as_mut_ptr())
+        });
+        out
+    }
+
+    /// PublicKeyLv0::new_with_params (src/proxy_reenc.rs:144-153) on the GPU (`tfhe_hip_gen_public_key`): `size`
+    /// encryptions of zero under `key_lv0`, returned flat [size][n+1] and left loaded on the public key's view, so that
+    /// `pk_encrypt` and `gen_reenc_key_asymmetric` upload nothing.  One rng_key makes one public key.
+    pub fn gen_public_key(&self, key_lv0: &[u32], size: usize, alpha: f64, rng_key: Option<&[u8; 32]>) -> Vec<u32> {
+        assert_eq!(key_lv0.len(), params::tlwe_lv0::N, "key_lv0 is [n]");
+        assert!(size >= 1 && size <= 8192, "1 <= size <= 8192");
+        let mut enc = vec![0u32; size * W];
+        let mut g = self.public_key.lock().unwrap();
+        let ctx = self.public_key_ctx(&mut g);
+        g.fp = 0;
+        let rk = rng_key.map_or(std::ptr::null(), |k| k.as_ptr());
+        Self::check_ctx(ctx, unsafe { tfhe_hip_gen_public_key(ctx, key_lv0.as_ptr(), size, alpha, rk, enc.as_mut_ptr()) });
+        g.fp = size as u64;
+        enc
+    }
+
+    /// ProxyReencryptionKey::new_symmetric (src/proxy_reenc.rs:362-425) from `key_from` to `key_to` (both key_lv0 [n]),
+    /// generated on the GPU (`tfhe_hip_gen_reenc_key_symmetric`): returns key_encryptions [n][t][base][n+1], flat, and
+    /// leaves the public key's view holding the key, so that `reencrypt_generated` uploads nothing.
+    pub fn gen_reenc_key_symmetric(&self, key_from: &[u32], key_to: &[u32], alpha: f64, rng_key: Option<&[u8; 32]>) -> Vec<u32> {
+        let n = params::tlwe_lv0::N;
+        assert!(key_from.len() == n && key_to.len() == n, "key_from and key_to are [n]");
+        let mut key = vec![0u32; n * params::trgsw_lv1::IKS_T * (1usize << params::trgsw_lv1::BASEBIT) * W];
+        let mut g = self.public_key.lock().unwrap();
+        let ctx = self.public_key_ctx(&mut g);
+        let rk = rng_key.map_or(std::ptr::null(), |k| k.as_ptr());
+        Self::check_ctx(ctx, unsafe {
+            tfhe_hip_gen_reenc_key_symmetric(ctx, key_from.as_ptr(), key_to.as_ptr(), alpha, rk, key.as_mut_ptr())
+        });
+        key
+    }
+
+    /// reencrypt_tlwe_lv0 over `cts` ([count][n+1], flat) under the key `gen_reenc_key_asymmetric` or
+    /// `gen_reenc_key_symmetric` left on the view.
     pub fn reencrypt_generated(&self, cts: &[u32]) -> Vec<u32> {
         assert_eq!(cts.len() % W, 0, "cts is [count][n+1]");
         let mut out = vec![0u32; cts.len()];
