@@ -1,6 +1,6 @@
 """Seeded (compressed) cloud keys on one GPU: wall time of loading a full key (tfhe_hip_load_cloud_key) against loading
 its compressed form (tfhe_hip_load_compressed_cloud_key), both from pageable host arrays, on SECURITY_128_BIT, UINT4
-and UINT8; the time of tfhe_hip_gen_compressed_cloud_key; and expanding 65,536 seeded SECURITY_128_BIT ciphertexts on
+and UINT8; the times of tfhe_hip_gen_cloud_key_with_key and tfhe_hip_gen_compressed_cloud_key; and expanding 65,536 seeded SECURITY_128_BIT ciphertexts on
 the device (tfhe_hip_expand_seeded_tlwe_dev) against staging the full batch from the host.
 
     python3 profiles/compressed_key_bench.py [--reps 5] [--out profiles/compressed_key_bench.json]
@@ -75,6 +75,7 @@ def main():
         sk = R.SecretKey.new(p, 1)
         e = R.Engine(p, 0)
         try:
+            gen_plain = timed(lambda: e.gen_cloud_key(sk.key_lv0, sk.key_lv1, rng_key=bytes(32)), args.reps)
             gen = timed(lambda: e.gen_compressed_cloud_key(sk.key_lv0, sk.key_lv1, rng_key=bytes(32)), args.reps)
             ck = e.gen_compressed_cloud_key(sk.key_lv0, sk.key_lv1, rng_key=bytes(32))
             full = e.export_cloud_key()
@@ -84,7 +85,7 @@ def main():
         finally:
             e.close()
         res["sets"][name] = {"full_mb": round(full_bytes / 1e6, 2), "compressed_mb": round(ck.nbytes / 1e6, 2),
-                             "gen_compressed": gen, "load_cloud_key": load_full, "load_compressed_cloud_key": load_comp,
+                             "gen_cloud_key": gen_plain, "gen_compressed": gen, "load_cloud_key": load_full, "load_compressed_cloud_key": load_comp,
                              "load_speedup": round(load_full["median_ms"] / load_comp["median_ms"], 2)}
         del full
         print(name, json.dumps(res["sets"][name]), flush=True)

@@ -216,6 +216,40 @@ int derive_public_seed(tfhe_hip_ctx *ctx, const StagedSecrets &s, ChaChaKey &see
   return TFHE_HIP_OK;
 }
 
+// The one launch of k_lwe_rows (keygen.hpp), on stream s: the encrypting variant, or with no generator key (j.k NULL)
+// the expansion of given bodies.  j.rows >= 1.
+int lwe_rows_launch(tfhe_hip_ctx *ctx, const LweRowJob &j, hipStream_t s) {
+  const tfhe_hip_params &P = ctx->P;
+  if (P.n > kLweMaxN) return fail(ctx, TFHE_HIP_EINVAL, "n too large");  // (params_supported admits no such context)
+  const size_t per = (size_t)kLweWaves * kLweRowsPerWave;
+  const dim3 grid((unsigned)((j.rows + per - 1) / per)), wg(64 * kLweWaves);
+  if (j.k) hipLaunchKernelGGL((k_lwe_rows<kLweWaves, false>), grid, wg, 0, s, j, P.n, P.basebit, P.t);
+  else hipLaunchKernelGGL((k_lwe_rows<kLweWaves, true>), grid, wg, 0, s, j, P.n, P.basebit, P.t);
+  return launched(ctx);
+}
+
+// The key-switching key's rows (key.rs:102-122) over the staged secrets: plain (masks under K, streams 0 / 1) into the
+// engine layout at `out`, or compressed (seed != NULL: masks under S, streams 16 / 17) as bodies only.
+int ksk_rows_launch(tfhe_hip_ctx *ctx, const StagedSecrets &s, const ChaChaKey *seed, double alpha, uint32_t *bodies,
+                    uint32_t *out) {
+  LweRowJob j{};
+  if (seed) j.seed = *seed;
+  j.k = s.d_rk;
+  j.mask_under_k = !seed;
+  j.stream_mask = seed ? kStreamSeededKskMask : kStreamKskMask;
+  j.stream_noise = seed ? kStreamSeededKskNoise : kStreamKskNoise;
+  j.dom_mask = j.dom_noise = kSeedDomainKsk;
+  j.rows = ksk_rows(ctx->P);
+  j.alpha = alpha;
+  j.s0 = s.d_k0;
+  j.key_rows = true;
+  j.key_from = s.d_k1;
+  j.bodies = bodies;
+  j.out = out;
+  j.stride = ksk_row_words(ctx->P.n);
+  return lwe_rows_launch(ctx, j, ctx->stream);
+}
+
 // what a generated key gets: the decomposition offset (key.rs:78-89) and the test vector (key.rs:91-100), uploaded
 int default_offset_and_testvec(tfhe_hip_ctx *ctx, uint32_t *offset) {
   const tfhe_hip_params &P = ctx->P;

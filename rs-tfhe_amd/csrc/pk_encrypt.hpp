@@ -85,17 +85,12 @@ __global__ __launch_bounds__(WG) void k_pke_selectors(ChaChaKey key, uint64_t fi
   uint32_t *srow = sel + row * (size_t)words;
   uint32_t pl = 0;
   if (key_from) {
-    const uint64_t base = (uint64_t)1 << basebit;
-    const uint32_t k = (uint32_t)(g % base);
-    const int j = (int)((g / base) % (uint64_t)t);
-    const size_t i = (size_t)(g / (base * (uint64_t)t));
-    if (k == 0) {  // never read by the re-encryption (proxy_reenc.rs:311-313): zero
+    if (!key_row_plain(g, basebit, t, key_from, pl)) {  // never read by the re-encryption (proxy_reenc.rs:311-313): zero
       if (blk == nblk) addend[row] = 0u;
       else
         for (int q = 0; q < 16 && 16 * blk + q < words; ++q) srow[16 * blk + q] = 0u;
       return;
     }
-    pl = dev_f64_to_torus((double)(uint32_t)(k * key_from[i]) * exp2(-(double)((j + 1) * basebit)));
   } else {
     pl = plain[row];
   }

@@ -2,10 +2,12 @@
 //
 // Every row of the key-switching key, every TRLWE row of the bootstrapping key and every fresh TLWE ciphertext is
 // (uniform mask, body).  When the mask is a fixed position of a ChaCha20 keystream under a PUBLIC 32-byte seed S,
-// only the bodies travel; the expand kernels below regenerate the masks and write the engine layouts the existing
-// kernels read.  The format (nonces, word order, the q < l body rule of the BSK) is normative and documented in
+// only the bodies travel; the expansion regenerates the masks and writes the engine layouts the existing kernels
+// read.  The format (nonces, word order, the q < l body rule of the BSK) is normative and documented in
 // include/tfhe_hip.h; keygen.hpp holds the ChaCha20 block function, the stream table every nonce here is named in
-// (kStream*, kSeedDomain*), the seed derivation and the row helpers shared with the plain generator.
+// (kStream*, kSeedDomain*), the seed derivation, the ring-row helpers shared with the plain generator, and the LWE
+// row kernel k_lwe_rows: the key-switching key's rows (bodies only under S, streams 16 / 17 of "KSK") and the
+// expansion of them and of seeded TLWE ciphertexts ("EWL") are launches of it, so only the ring rows have kernels here.
 //
 // Every kernel here is a template (on its workgroup size, or on l): template instantiations are emitted after the
 // library's other kernels, so these leave the labels of the bootstrap kernels, which kernel_isa.json records, alone.
@@ -13,47 +15,6 @@
 #include "keygen.hpp"
 
 namespace tfhe {
-
-// ---- key-switching key ------------------------------------------------------------------------------------------
-// Row r = base*t*i + base*j + k (k >= 1): mask word x < n is keystream word x of (r, 16, "KSK") under S; the body is
-// <a, s0> + gaussian_f64(k * s1[i] / 2^((j+1) basebit)) with the noise from (r, 17, "KSK") under K.  k = 0: body 0.
-template <int WG>
-__global__ __launch_bounds__(WG) void k_gen_compressed_ksk(const uint32_t *__restrict__ key_lv0,
-                                                             const uint32_t *__restrict__ key_lv1,
-                                                             uint32_t *__restrict__ bodies, int n, int basebit, int t,
-                                                             double alpha, const ChaChaKey *__restrict__ key_p,
-                                                             ChaChaKey seed) {
-  static_assert(WG == 256, "the body's reduction is over four waves");
-  __shared__ uint32_t s_part[4];
-  const uint32_t row = blockIdx.x;
-  const int tid = threadIdx.x;
-  if ((row & ((1u << basebit) - 1u)) == 0) {
-    if (tid == 0) bodies[row] = 0u;
-    return;
-  }
-  const uint32_t inner =
-      lwe_mask_walk<false, true>(seed, row, kStreamSeededKskMask, kSeedDomainKsk, n, tid, WG, nullptr, key_lv0);
-  const uint32_t body = ksk_body(inner, s_part, *key_p, row, kStreamSeededKskNoise, key_lv1, basebit, t, alpha);
-  if (tid == 0) bodies[row] = body;
-}
-
-// Engine layout of k_gen_ksk / k_ksk_convert: rows of ksk_row_words(n), zero padding, k = 0 rows all zero.
-template <int WG>
-__global__ __launch_bounds__(WG) void k_expand_ksk(const uint32_t *__restrict__ bodies, uint32_t *__restrict__ ksk_eng,
-                                                     int n, int basebit, ChaChaKey seed) {
-  const uint32_t row = blockIdx.x;
-  const int k = row & ((1 << basebit) - 1);
-  const int rw = ksk_row_words(n);
-  uint32_t *dst = ksk_eng + (size_t)row * rw;
-  const int tid = threadIdx.x;
-  if (k == 0) {
-    for (int x = tid; x < rw; x += WG) dst[x] = 0u;
-    return;
-  }
-  lwe_mask_walk<true, false>(seed, row, kStreamSeededKskMask, kSeedDomainKsk, n, tid, WG, dst, nullptr);
-  if (tid == 0) dst[n] = bodies[row];
-  if (tid > 0 && n + tid < rw) dst[n + tid] = 0u;
-}
 
 // ---- bootstrapping key --------------------------------------------------------------------------------------------
 // Row r = i*2l + q of TRGSW(s0[i]), p = s0[i], g_d = f64_to_torus(Bg^-(d+1)), a from S (natural_mask over
@@ -112,29 +73,6 @@ __global__ __launch_bounds__(WG) void k_expand_bsk(const uint32_t *__restrict__ 
   for (int s = 0; s < 8; ++s) dst[kN2 + s * 64 + lane] = make_double2(re[s] * k2, im[s] * k2);
 }
 
-// ---- seeded TLWE lv0 ----------------------------------------------------------------------------------------------
-// Ciphertext g = first + m: mask word x < n is keystream word x of (g & 0xffffffff, g >> 32, "EWL") under S, the body
-// is bodies[m].  One thread per (ciphertext, keystream block); out [count][n+1].
-template <int WG>
-__global__ __launch_bounds__(WG) void k_expand_seeded_tlwe(ChaChaKey seed, uint64_t first, const uint32_t *__restrict__ bodies,
-                                                             uint32_t *__restrict__ out, size_t count, int n) {
-  const int nb = (n + 15) >> 4;
-  const size_t tid = (size_t)blockIdx.x * WG + threadIdx.x;
-  if (tid >= count * (size_t)nb) return;
-  const size_t m = tid / nb;
-  const int blk = (int)(tid - m * nb);
-  const uint64_t g = first + m;
-  uint32_t w[16];
-  chacha20_block(seed, (uint32_t)blk, (uint32_t)g, (uint32_t)(g >> 32), kSeedDomainTlwe, w);
-  uint32_t *dst = out + m * (size_t)(n + 1);
-#pragma unroll
-  for (int c = 0; c < 16; ++c) {
-    const int x = blk * 16 + c;
-    if (x < n) dst[x] = w[c];
-  }
-  if (blk == 0) dst[n] = bodies[m];
-}
-
 }  // namespace tfhe
 
 using namespace tfhe;
@@ -161,9 +99,17 @@ hipError_t expand_key_locked(tfhe_hip_ctx *ctx, const ChaChaKey &seed, const uin
   hipLaunchKernelGGL(k_expand_bsk<64>, dim3((unsigned)(P.n * 2 * P.l)), dim3(64), kStageLdsBytes, ctx->stream, d_bsk_bodies,
                      ctx->d_tw, ctx->K->d_bsk, seed, key_scale(ctx->dispatch.fast_round));
   if (const hipError_t e = hipGetLastError()) return e;
-  hipLaunchKernelGGL(k_expand_ksk<256>, dim3((unsigned)ksk_rows(P)), dim3(256), 0, ctx->stream, d_ksk_bodies, ctx->K->d_ksk, P.n,
-                     P.basebit, seed);
-  return hipGetLastError();
+  // key-switching key: the engine layout of k_ksk_convert (rows of ksk_row_words(n), zero padding, k = 0 rows all zero)
+  LweRowJob j{};
+  j.seed = seed;
+  j.stream_mask = kStreamSeededKskMask;
+  j.dom_mask = kSeedDomainKsk;
+  j.rows = ksk_rows(P);
+  j.plain = d_ksk_bodies;
+  j.key_rows = true;
+  j.out = ctx->K->d_ksk;
+  j.stride = ksk_row_words(P.n);
+  return lwe_rows_launch(ctx, j, ctx->stream) == TFHE_HIP_OK ? hipSuccess : hipErrorLaunchFailure;
 }
 
 // ctx->mu held, ctx's device current
@@ -176,7 +122,7 @@ int gen_compressed_locked(tfhe_hip_ctx *ctx, const uint32_t *key_lv0, const uint
   // generator key at idx[0, 32), the mask seed derived from it at idx[32, 64)
   StagedSecrets s{{ctx}};  // (wiped on every exit path)
   CHK(stage_secrets(ctx, key_lv0, key_lv1, rk, 2 * sizeof(ChaChaKey), s));
-  const uint32_t *d_k0 = s.d_k0, *d_k1 = s.d_k1;
+  const uint32_t *d_k0 = s.d_k0;
   const double2 *d_spec = s.d_spec;
   const ChaChaKey *d_rk = s.d_rk;
   ChaChaKey seed;
@@ -188,9 +134,7 @@ int gen_compressed_locked(tfhe_hip_ctx *ctx, const uint32_t *key_lv0, const uint
   hipLaunchKernelGGL(gen_bsk, dim3((unsigned)(P.n * 2 * P.l)), dim3(64), kStageLdsBytes, ctx->stream, d_k0, d_spec, ctx->d_tw,
                      d_bb, P.bgbit, alpha_bsk, d_rk, seed);
   HIPCHK(ctx, hipGetLastError());
-  hipLaunchKernelGGL(k_gen_compressed_ksk<256>, dim3((unsigned)ksk_words), dim3(256), 0, ctx->stream, d_k0, d_k1, d_kb, P.n,
-                     P.basebit, P.t, alpha_ksk, d_rk, seed);
-  HIPCHK(ctx, hipGetLastError());
+  CHK(ksk_rows_launch(ctx, s, &seed, alpha_ksk, d_kb, nullptr));
   HIPCHK(ctx, hipMemcpyAsync(bsk_bodies, d_bb, bsk_words * 4, hipMemcpyDeviceToHost, ctx->stream));
   HIPCHK(ctx, hipMemcpyAsync(ksk_bodies, d_kb, ksk_words * 4, hipMemcpyDeviceToHost, ctx->stream));
   // the context's key is what tfhe_hip_load_compressed_cloud_key rebuilds from these bodies, bit for bit
@@ -237,10 +181,15 @@ int tfhe_hip_load_compressed_cloud_key(tfhe_hip_ctx *ctx, const uint8_t mask_see
 namespace {
 int expand_seeded_launch(tfhe_hip_ctx *ctx, const ChaChaKey &seed, uint64_t first_index, const uint32_t *bodies, size_t count,
                          uint32_t *out, hipStream_t s) {
-  const size_t threads = count * (size_t)((ctx->P.n + 15) >> 4);
-  hipLaunchKernelGGL(k_expand_seeded_tlwe<256>, dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, s, seed, first_index,
-                     bodies, out, count, ctx->P.n);
-  return launched(ctx);
+  LweRowJob j{};
+  j.seed = seed;
+  j.dom_mask = kSeedDomainTlwe;
+  j.first_index = first_index;
+  j.rows = count;
+  j.plain = bodies;
+  j.out = out;
+  j.stride = ctx->P.n + 1;
+  return lwe_rows_launch(ctx, j, s);
 }
 }  // namespace
 

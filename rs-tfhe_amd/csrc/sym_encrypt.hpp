@@ -1,24 +1,9 @@
 // sym_encrypt.hpp -- symmetric (secret-key) TLWE lv0 encryption on the GPU, behind the C ABI: bulk ciphertexts, the
 // public key's encryptions of zero and the symmetric proxy re-encryption key.
 //
-// The format is normative in include/tfhe_hip.h ("symmetric encryption").  All three are the row of
-// TLWELv0::encrypt_f64 (tlwe.rs:37-53):
-//
-//   row g = (a, <a, s0> + plain + f64_to_torus(noise))      a: n keystream words, wrapping u32
-//
-// with the mask a under (mask key, g, mask domain) and the one noise sample under (K, g, noise domain).  A row has at
-// most 80 keystream blocks, so ONE WAVE makes a row (k_gen_ksk spends a 256-thread workgroup and an LDS reduction on
-// it): lane l makes block l (and l + 64 where n > 1024), multiplies its 16 words into s0 held in LDS, and the wave
-// reduces with shuffles.  The lane just past the last mask block makes the row's noise block in the same pass -- under
-// the other key and nonce, the same instructions -- and feeds f64_to_torus(g0) into the same reduction, so the noise
-// costs no pass of its own.  Lane 0 adds the plaintext.
-//
-// Stores decide the speed (184 MB for 65,536 SECURITY_128_BIT rows).  A lane holds 16 consecutive words; stored from
-// the registers, one store instruction of the wave would scatter 64 pieces of 64 bytes.  The row is staged in LDS
-// instead (one word of padding per block: lane l's words start at 17 l, so the 64 writes of one instruction fall on
-// distinct banks) and leaves in whole 16-byte chunks of the DESTINATION's alignment: rows are n + 1 words, so a row
-// starts at any word of a chunk; the staged row is shifted by that and lane l stores chunk l, l + 64, ... -- one
-// store instruction covers 1 KiB of contiguous bytes.  Only a row's first and last chunk are partial: word stores.
+// The format is normative in include/tfhe_hip.h ("symmetric encryption").  All three are launches of the library's LWE
+// row kernel, k_lwe_rows (keygen.hpp): the row (a, <a, s0> + plain + f64_to_torus(noise)) with the mask a under
+// (mask key, g, mask domain) and the one noise sample under (K, g, noise domain), no stream number.
 //
 //   bulk TLWE        g = first_index + m, masks under the public seed S ("EWL": the seeded-TLWE masks), out [count][n+1]
 //                    and / or bodies [count]; bodies-only mode stages and stores no mask.
@@ -26,151 +11,19 @@
 //   re-encryption    g = base t i + base j + k, plain from (i, j, k) and key_from in the kernel, k = 0 rows zero, out
 //                    in the engine layout of the key-switching key (rows of ksk_row_words(n), zero padding): what
 //                    k_ksk_convert would have made, so no conversion pass follows.
-//
-// The kernel is a template: instantiations are emitted after the library's other kernels, whose code stays
-// byte-identical.
 #pragma once
 #include "pk_encrypt.hpp"
 
-namespace tfhe {
-
-constexpr int kSymMaxN = 1279;                      // 80 keystream blocks: two passes of a wave
-constexpr int kSymWaves = 4;                        // rows in flight per workgroup
-constexpr int kSymRowsPerWave = 4;                  // rows a wave makes one after the other (s0 is loaded once)
-constexpr int kSymKeyWords = 80 * 17;               // s0 in LDS: 17 words a block of 16
-constexpr int kSymStageWords = 81 * 17;             // a row image: up to 3 words of shift + 1280 words, read in whole chunks
-
-// word x of a row sits at x + x / 16 of its LDS image: 16 words, one of padding
-__device__ __forceinline__ int sym_slot(int x) { return x + (x >> 4); }
-
-// sec: [0] the mask key, [1] the noise key K (a device buffer the host wipes behind the launch), then s0 [n], then
-// (re-encryption key) key_from [n].  Rows `rows`, row r of the launch is index g = first_index + r.
-//   plain     != NULL: the plaintext torus words [rows]                                     (bulk)
-//   from_key:          plain = f64_to_torus(((k key_from[i]) as u32 as f64) / 2^((j+1) basebit)), k = 0 rows zero
-//   neither:           plain 0                                                               (public key)
-//   out       != NULL: the rows, `stride` >= n + 1 words apart, words n + 1 .. stride - 1 zero
-//   bodies    != NULL: the bodies [rows]
-template <int WAVES>
-__global__ __launch_bounds__(64 * WAVES) void k_sym_encrypt(const uint32_t *__restrict__ sec, uint32_t dom_mask,
-                                                             uint32_t dom_noise, uint64_t first_index, size_t rows, int n,
-                                                             double alpha, const uint32_t *__restrict__ plain,
-                                                             int from_key, int basebit, int t,
-                                                             uint32_t *__restrict__ bodies, uint32_t *__restrict__ out,
-                                                             int stride) {
-  __shared__ uint32_t s_key[kSymKeyWords];
-  __shared__ __attribute__((aligned(16))) uint32_t s_stage[WAVES][kSymStageWords];
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int nb = (n + 15) >> 4;  // mask blocks; block nb of the walk is the noise block
-  ChaChaKey kmask, knoise;
-#pragma unroll
-  for (int c = 0; c < 8; ++c) {
-    kmask.k[c] = sec[c];
-    knoise.k[c] = sec[8 + c];
-  }
-  const uint32_t *s0 = sec + 16, *key_from = sec + 16 + n;
-  for (int x = tid; x < n; x += 64 * WAVES) s_key[sym_slot(x)] = s0[x];
-  __syncthreads();
-  uint32_t *stage = s_stage[wave];
-  const size_t row0 = ((size_t)blockIdx.x * WAVES + (size_t)wave) * kSymRowsPerWave;
-#pragma unroll 1
-  for (int it = 0; it < kSymRowsPerWave; ++it) {
-    const size_t row = row0 + (size_t)it;
-    if (row >= rows) break;  // (wave-uniform; nothing below synchronises across waves)
-    const uint64_t g = first_index + (uint64_t)row;
-    uint32_t *dst = out ? out + row * (size_t)stride : nullptr;
-    // a row's image is shifted by the word its destination starts at within a 16-byte chunk
-    const int shift = dst ? (int)(((uintptr_t)dst >> 2) & 3u) : 0;
-    uint32_t pl = 0;
-    bool zero_row = false;
-    if (from_key) {
-      const uint64_t base = (uint64_t)1 << basebit;
-      const uint32_t k = (uint32_t)(g % base);
-      const int j = (int)((g / base) % (uint64_t)t);
-      const size_t i = (size_t)(g / (base * (uint64_t)t));
-      zero_row = k == 0;  // never read by the re-encryption (proxy_reenc.rs:405-407): zero, its streams unused
-      if (!zero_row) pl = dev_f64_to_torus((double)(uint32_t)(k * key_from[i]) * exp2(-(double)((j + 1) * basebit)));
-    } else if (plain) {
-      pl = plain[row];
-    }
-    uint32_t inner = 0;
-    if (!zero_row) {
-#pragma unroll 1
-      for (int blk = lane; blk <= nb; blk += 64) {
-        const bool noise = blk == nb;
-        ChaChaKey key;
-#pragma unroll
-        for (int c = 0; c < 8; ++c) key.k[c] = noise ? knoise.k[c] : kmask.k[c];
-        uint32_t w[16];
-        chacha20_block(key, noise ? 0u : (uint32_t)blk, (uint32_t)g, (uint32_t)(g >> 32), noise ? dom_noise : dom_mask, w);
-        if (noise) {
-          double g0, g1;
-          gauss2(w, alpha, g0, g1);
-          inner += dev_f64_to_torus(g0);
-        } else {
-          const int at = 17 * blk;
-#pragma unroll
-          for (int c = 0; c < 16; ++c) {
-            if (16 * blk + c < n) {
-              inner += s_key[at + c] * w[c];
-              if (dst) stage[sym_slot(16 * blk + c + shift)] = w[c];
-            }
-          }
-        }
-      }
-    }
-    for (int off = 32; off > 0; off >>= 1) inner += __shfl_down(inner, off);
-    const uint32_t body = zero_row ? 0u : inner + pl;
-    if (lane == 0 && bodies) bodies[row] = body;
-    if (!dst) continue;
-    if (zero_row) {
-      for (int x = lane; x < stride; x += 64) dst[x] = 0u;
-      continue;
-    }
-    if (lane == 0) stage[sym_slot(n + shift)] = body;
-    if (lane > 0 && n + lane < stride) stage[sym_slot(n + lane + shift)] = 0u;  // (stride - n - 1 <= 3)
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
-    // image words [shift, shift + stride) are the row; chunk q holds image words 4q .. 4q + 3
-    const int end = shift + stride;
-    uint32_t *dst0 = dst - shift;  // 16-byte aligned
-    for (int q = lane; 4 * q < end; q += 64) {
-      const int x0 = 4 * q;
-      const uint4 v = make_uint4(stage[sym_slot(x0)], stage[sym_slot(x0 + 1)], stage[sym_slot(x0 + 2)], stage[sym_slot(x0 + 3)]);
-      if (x0 >= shift && x0 + 4 <= end) {
-        *reinterpret_cast<uint4 *>(dst0 + x0) = v;
-      } else {
-        const uint32_t e[4] = {v.x, v.y, v.z, v.w};
-#pragma unroll
-        for (int c = 0; c < 4; ++c)
-          if (x0 + c >= shift && x0 + c < end) dst0[x0 + c] = e[c];
-      }
-    }
-    // the next row's image is written by the same wave behind these reads (LDS operations of a wave stay in order)
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
-    __builtin_amdgcn_wave_barrier();
-  }
-}
-
-}  // namespace tfhe
-
 // ---- symmetric encryption (sym_encrypt.hpp) -----------------------------------------------------------------------
 namespace {
-inline size_t sym_blocks(size_t rows) {
-  const size_t per = (size_t)kSymWaves * kSymRowsPerWave;
-  return (rows + per - 1) / per;
-}
-
-// The secrets of one launch in the context's `sym_sec` buffer: mask key, K, s0 [n], key_from [n] (or nothing).  The
-// copy has landed when this returns (the sources are the caller's and this frame's).
-int sym_stage(tfhe_hip_ctx *ctx, const ChaChaKey &kmask, const ChaChaKey &knoise, const uint32_t *key_lv0,
-              const uint32_t *key_from, hipStream_t s) {
+// The secrets of one launch in the context's `sym_sec` buffer: K, s0 [n], key_from [n] (or nothing).  The copy has
+// landed when this returns (the sources are the caller's and this frame's).
+int sym_stage(tfhe_hip_ctx *ctx, const ChaChaKey &k, const uint32_t *key_lv0, const uint32_t *key_from, hipStream_t s) {
   const int n = ctx->P.n;
-  std::vector<uint32_t> h(16 + (size_t)n * (key_from ? 2 : 1));
-  memcpy(h.data(), kmask.k, 32);
-  memcpy(h.data() + 8, knoise.k, 32);
-  memcpy(h.data() + 16, key_lv0, (size_t)n * 4);
-  if (key_from) memcpy(h.data() + 16 + n, key_from, (size_t)n * 4);
+  std::vector<uint32_t> h(8 + (size_t)n * (key_from ? 2 : 1));
+  memcpy(h.data(), k.k, 32);
+  memcpy(h.data() + 8, key_lv0, (size_t)n * 4);
+  if (key_from) memcpy(h.data() + 8 + n, key_from, (size_t)n * 4);
   int rc = ensure(ctx, ctx->sym_sec, h.size() * 4);
   if (rc == TFHE_HIP_OK) {
     hipError_t e = hipMemcpyAsync(ctx->sym_sec.p, h.data(), h.size() * 4, hipMemcpyHostToDevice, s);
@@ -188,23 +41,29 @@ int sym_wipe(tfhe_hip_ctx *ctx, hipStream_t s) {
   return TFHE_HIP_OK;
 }
 
-struct SymJob {
-  uint32_t dom_mask, dom_noise;
-  uint64_t first_index;
-  size_t rows;
-  double alpha;
-  const uint32_t *plain;  // device, or NULL
-  bool from_key;
-  uint32_t *bodies, *out;  // device, either may be NULL
-  int stride;
-};
-
-int sym_launch(tfhe_hip_ctx *ctx, const SymJob &j, hipStream_t s) {
-  const tfhe_hip_params &P = ctx->P;
-  hipLaunchKernelGGL(k_sym_encrypt<kSymWaves>, dim3((unsigned)sym_blocks(j.rows)), dim3(64 * kSymWaves), 0, s,
-                     (const uint32_t *)ctx->sym_sec.p, j.dom_mask, j.dom_noise, j.first_index, j.rows, P.n, j.alpha, j.plain,
-                     j.from_key ? 1 : 0, P.basebit, P.t, j.bodies, j.out, j.stride);
-  return launched(ctx);
+// `rows` rows from index `first_index` over the staged secrets (sym_stage), under the indexed domains dom_mask /
+// dom_noise; masks under `seed`, or (NULL) under K.  plain / bodies / out are device pointers, any may be NULL.
+int sym_launch(tfhe_hip_ctx *ctx, const ChaChaKey *seed, uint32_t dom_mask, uint32_t dom_noise, uint64_t first_index,
+               size_t rows, double alpha, const uint32_t *plain, bool key_rows, uint32_t *bodies, uint32_t *out, int stride,
+               hipStream_t s) {
+  const uint32_t *sec = (const uint32_t *)ctx->sym_sec.p;
+  LweRowJob j{};
+  if (seed) j.seed = *seed;
+  j.k = (const ChaChaKey *)sec;
+  j.mask_under_k = !seed;
+  j.dom_mask = dom_mask;
+  j.dom_noise = dom_noise;
+  j.first_index = first_index;
+  j.rows = rows;
+  j.alpha = alpha;
+  j.s0 = sec + 8;
+  j.plain = plain;
+  j.key_rows = key_rows;
+  j.key_from = key_rows ? sec + 8 + ctx->P.n : nullptr;
+  j.bodies = bodies;
+  j.out = out;
+  j.stride = stride;
+  return lwe_rows_launch(ctx, j, s);
 }
 
 const char *sym_refusal(const tfhe_hip_ctx *ctx, const uint32_t *key_lv0, const uint32_t *plain, size_t count, double alpha,
@@ -214,7 +73,6 @@ const char *sym_refusal(const tfhe_hip_ctx *ctx, const uint32_t *key_lv0, const 
   if (!(alpha >= 0.0)) return "negative noise parameter";
   if (count && first_index + (uint64_t)(count - 1) < first_index) return "the row indices run past 2^64";
   if (count > 0x7FFFFFFFull) return "count too large";
-  if (ctx->P.n > kSymMaxN) return "n too large";
   return nullptr;
 }
 
@@ -222,9 +80,9 @@ const char *sym_refusal(const tfhe_hip_ctx *ctx, const uint32_t *key_lv0, const 
 int sym_bulk(tfhe_hip_ctx *ctx, const ChaChaKey &seed, const ChaChaKey &k, const uint32_t *key_lv0, const uint32_t *plain,
              size_t count, double alpha, uint64_t first_index, uint32_t *bodies, uint32_t *out, hipStream_t s) {
   CHK(claim_scratch(ctx, s));  // sym_sec belongs to the context
-  CHK(sym_stage(ctx, seed, k, key_lv0, nullptr, s));
-  const int rc = sym_launch(ctx, {kSeedDomainTlwe, kSeedDomainSymNoise, first_index, count, alpha, plain, false, bodies, out,
-                                  ctx->P.n + 1}, s);
+  CHK(sym_stage(ctx, k, key_lv0, nullptr, s));
+  const int rc = sym_launch(ctx, &seed, kSeedDomainTlwe, kSeedDomainSymNoise, first_index, count, alpha, plain, false, bodies,
+                            out, ctx->P.n + 1, s);
   const int rc_wipe = sym_wipe(ctx, s);
   return rc != TFHE_HIP_OK ? rc : rc_wipe;
 }
@@ -283,18 +141,17 @@ int tfhe_hip_gen_public_key(tfhe_hip_ctx *ctx, const uint32_t *key_lv0, size_t s
     return fail(ctx, TFHE_HIP_EINVAL, "public key size must be in [1, 8192] (exact i32 accumulation)");
   if (!(alpha >= 0.0)) return fail(ctx, TFHE_HIP_EINVAL, "negative noise parameter");
   const tfhe_hip_params &P = ctx->P;
-  if (P.n > kSymMaxN) return fail(ctx, TFHE_HIP_EINVAL, "n too large");
   GeneratorKey gk;
   CHK(gk.fill(ctx, rng_key));
   KeyState &k = *ctx->K;
   const size_t bytes = pke_plane_bytes(P.n, (int)size), chunks = bytes / 16, enc_bytes = size * (size_t)(P.n + 1) * 4;
   CHK(begin_side_key(ctx, k.pke_loaded, k.d_pke8, k.pke_cap, bytes));
   CHK(claim_scratch(ctx, ctx->stream));
-  int rc = sym_stage(ctx, gk.k, gk.k, key_lv0, nullptr, ctx->stream);
+  int rc = sym_stage(ctx, gk.k, key_lv0, nullptr, ctx->stream);
   if (rc == TFHE_HIP_OK)
     rc = upload_through_temp(ctx, "public key generation", {}, enc_bytes, [&](void *d_enc) -> hipError_t {
-      if (sym_launch(ctx, {kSeedDomainPkMask, kSeedDomainPkNoise, 0, size, alpha, nullptr, false, nullptr, (uint32_t *)d_enc,
-                           P.n + 1}, ctx->stream) != TFHE_HIP_OK)
+      if (sym_launch(ctx, nullptr, kSeedDomainPkMask, kSeedDomainPkNoise, 0, size, alpha, nullptr, false, nullptr,
+                     (uint32_t *)d_enc, P.n + 1, ctx->stream) != TFHE_HIP_OK)
         return hipErrorLaunchFailure;
       hipLaunchKernelGGL(k_pke_planes<256>, dim3((unsigned)((chunks + 255) / 256)), dim3(256), 0, ctx->stream,
                          (const uint32_t *)d_enc, k.d_pke8, P.n, (int)size, chunks);
@@ -327,14 +184,14 @@ int tfhe_hip_gen_reenc_key_symmetric(tfhe_hip_ctx *ctx, const uint32_t *key_from
   const int base = 1 << P.basebit;
   const size_t rows = (size_t)P.n * P.t * base, key_words = rows * (size_t)(P.n + 1);
   CHK(claim_scratch(ctx, ctx->stream));
-  int rc = sym_stage(ctx, gk.k, gk.k, key_to, key_from, ctx->stream);
+  int rc = sym_stage(ctx, gk.k, key_to, key_from, ctx->stream);
   if (rc == TFHE_HIP_OK) {
     hipError_t e = hipMemsetAsync(ctx->K->d_ksk, 0, ksk_bytes(P), ctx->stream);
     if (e != hipSuccess) rc = fail(ctx, TFHE_HIP_EHIP, std::string("re-encryption key generation: ") + hipGetErrorString(e));
   }
   if (rc == TFHE_HIP_OK)
-    rc = sym_launch(ctx, {kSeedDomainRkMask, kSeedDomainRkNoise, 0, rows, alpha, nullptr, true, nullptr, ctx->K->d_ksk,
-                          ksk_row_words(P.n)}, ctx->stream);
+    rc = sym_launch(ctx, nullptr, kSeedDomainRkMask, kSeedDomainRkNoise, 0, rows, alpha, nullptr, true, nullptr,
+                    ctx->K->d_ksk, ksk_row_words(P.n), ctx->stream);
   if (rc == TFHE_HIP_OK && key_out)
     rc = upload_through_temp(ctx, "re-encryption key export", {}, key_words * 4, [&](void *d_ref) -> hipError_t {
       hipLaunchKernelGGL(k_ksk_export, dim3((unsigned)rows), dim3(256), 0, ctx->stream, (const uint32_t *)ctx->K->d_ksk,

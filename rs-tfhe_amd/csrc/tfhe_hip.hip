@@ -1363,9 +1363,7 @@ int gen_cloud_key_locked(tfhe_hip_ctx *ctx, const uint32_t *key_lv0, const uint3
   hipLaunchKernelGGL(gen_bsk, dim3((unsigned)(P.n * 2 * P.l)), dim3(64), kStageLdsBytes, ctx->stream, s.d_k0, s.d_spec,
                      ctx->d_tw, ctx->K->d_bsk, P.bgbit, alpha_bsk, s.d_rk, key_scale(ctx->dispatch.fast_round));
   HIPCHK(ctx, hipGetLastError());
-  hipLaunchKernelGGL(k_gen_ksk, dim3((unsigned)ksk_rows(P)), dim3(256), 0, ctx->stream, s.d_k0, s.d_k1,
-                     ctx->K->d_ksk, P.n, P.basebit, P.t, alpha_ksk, s.d_rk);
-  HIPCHK(ctx, hipGetLastError());
+  CHK(ksk_rows_launch(ctx, s, nullptr, alpha_ksk, nullptr, ctx->K->d_ksk));
   uint32_t off = 0;
   CHK(default_offset_and_testvec(ctx, &off));
   return commit_cloud_key(ctx, off);

@@ -5,7 +5,7 @@ key is a function of (secret key, generator key K, alphas) and numpy can compute
 keystream (pinned to RFC 8439 in test_compressed_key_host.py), gauss2, f64_to_torus and the exact negacyclic product.
 
 Three pieces sit on top of that:
-  * the plain generator in the word order of k_gen_ksk / k_gen_bsk (streams 0/1 "KSK", 2/3 "BSK" under K; the
+  * the plain generator in the word order of k_lwe_rows / k_gen_bsk (streams 0/1 "KSK", 2/3 "BSK" under K; the
     compressed generator uses 16/17 and 18/19 with the masks under the mask seed) and key_from_seed, the SplitMix64
     expansion behind the 64-bit-seed entry point;
   * gauss2 in long double, which says where an f64 libm may legitimately land on the neighbouring torus word

@@ -213,6 +213,33 @@ def test_seeded_inputs_expand_on_the_gpu():
         e.close()
 
 
+@pytest.mark.parametrize("n", [1, 16, 33, 1279])
+def test_seeded_expansion_at_the_edges_of_the_row_walk(n):
+    """expand_seeded_dev == SeededCiphertexts.expand(), word for word (no noise is drawn), where the wave-per-row walk
+    changes path: n = 1 (one word), 16 (exactly one keystream block), 33 (a ragged tail), 1279 (80 blocks: a wave's
+    second pass); 1, 17 and 257 rows (below, across and well past the 16 rows of a workgroup, none a multiple of it);
+    first_index 0 and 2^32 - 3, where the nonce's high word changes inside the batch."""
+    import torch
+
+    import keygen_model as KM
+    import rs_tfhe_amd as R
+
+    p = KM.shape_params((n, 1, 10, 2, 2))
+    rng = np.random.default_rng(n)
+    e = R.Engine(p, 0)
+    try:
+        for count in (1, 17, 257):
+            for first in (0, (1 << 32) - 3):
+                sc = R.seeded.SeededCiphertexts(p, K, first, rng.integers(0, 1 << 32, count, dtype=np.uint32))
+                bodies = torch.from_numpy(sc.bodies.view(np.int32)).to("cuda:0")
+                out = torch.zeros((count, n + 1), dtype=torch.int32, device="cuda:0")
+                e.expand_seeded_dev(sc.mask_seed, sc.first_index, bodies, out)
+                torch.cuda.synchronize()
+                assert np.array_equal(out.cpu().numpy().view(np.uint32), sc.expand()), (n, count, first)
+    finally:
+        e.close()
+
+
 def test_invalid_arguments_on_a_live_context():
     import rs_tfhe_amd as R
     from rs_tfhe_amd import _capi

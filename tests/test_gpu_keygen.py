@@ -1,8 +1,8 @@
 """Cloud-key generation on the GPU held to the CPU model of tests/keygen_model.py, sample for sample.
 
-k_gen_ksk / k_gen_bsk<L> (keygen.hpp) and k_gen_compressed_ksk / k_gen_compressed_bsk<L> (seeded.hpp) are the only
-kernels whose output nobody can recompute from what they are sent -- unless the generator key is fixed, and then every
-mask word and every Gaussian sample is a keystream position the model knows.  So: generate on the device, export, take
+k_lwe_rows (the key-switching key's rows, plain and compressed) / k_gen_bsk<L> (keygen.hpp) and
+k_gen_compressed_bsk<L> (seeded.hpp) are the only kernels of the cloud key whose output nobody can recompute from what
+they are sent -- unless the generator key is fixed, and then every mask word and every Gaussian sample is a keystream position the model knows.  So: generate on the device, export, take
 the BSK spectra back to torus polynomials (O.klemsa_fft, exact), and compare EVERY word.  A body may differ by exactly
 +-1 LSB only where the long-double sampler marks its noise sample borderline, at most 16 words a key.
 
@@ -101,8 +101,8 @@ _ids = lambda v: str(v).replace(" ", "")  # noqa: E731
 # ---- 1. plain generator, rng_key route ---------------------------------------------------------------------------
 @pytest.mark.parametrize("shape,alpha_bsk", PLAIN_CASES, ids=_ids)
 def test_plain_generator_equals_the_model(O, shape, alpha_bsk):
-    """Every KSK word and every BSK word (masks, bodies, gadget, the all-zero k = 0 rows) of k_gen_ksk and
-    k_gen_bsk<l>.  At alpha_bsk = 2.2e-16 the reference truncates the noise to zero and so must the device: no sample is
+    """Every KSK word and every BSK word (masks, bodies, gadget, the all-zero k = 0 rows) of k_lwe_rows' key rows
+    and k_gen_bsk<l>.  At alpha_bsk = 2.2e-16 the reference truncates the noise to zero and so must the device: no sample is
     borderline there, so the comparison is plain equality."""
     p = KM.shape_params(shape, alpha_bsk=alpha_bsk)
     ksk, bsk = _plain(O, p, rng_key=K)
@@ -141,7 +141,7 @@ def test_seed_route_is_the_model_under_the_splitmix64_key(O):
 
 
 # ---- 3. compressed generator at real noise -----------------------------------------------------------------------
-COMPRESSED_CASES = [(s, KM.ALPHA_BSK) for s in KM.SHAPES[:4]] + [(KM.SHAPES[2], KM.ALPHA_BSK_UINT)]
+COMPRESSED_CASES = [(s, KM.ALPHA_BSK) for s in KM.SHAPES] + [(KM.SHAPES[2], KM.ALPHA_BSK_UINT)]
 
 
 @pytest.mark.parametrize("shape,alpha_bsk", COMPRESSED_CASES, ids=_ids)

@@ -1,4 +1,4 @@
-"""Symmetric encryption on the GPU (csrc/sym_encrypt.hpp: k_sym_encrypt behind tfhe_hip_batch_encrypt[_dev] /
+"""Symmetric encryption on the GPU (csrc/sym_encrypt.hpp: k_lwe_rows of csrc/keygen.hpp behind tfhe_hip_batch_encrypt[_dev] /
 tfhe_hip_gen_public_key / tfhe_hip_gen_reenc_key_symmetric) held to the term-by-term CPU model of
 tests/sym_encrypt_model.py.
 
@@ -108,6 +108,51 @@ def test_bulk_second_block_pass(count, first_index):
 
     p = R.params.SECURITY_UINT5
     _bulk_case(p, SecretKey.new(p, 4000 + p.n), count, first_index, SM.ALPHA)
+
+
+@pytest.mark.parametrize("offset", [0, 1, 2, 3])
+@pytest.mark.parametrize("shape", [SM.SHAPES[1], SM.SHAPES[0]], ids=lambda s: f"n{s[0]}")
+def test_rows_land_at_any_word_of_a_chunk(shape, offset):
+    """The row kernel stores a staged row in 16-byte chunks of its destination's alignment.  Rows written through a view
+    that starts `offset` words into a larger tensor, by expand_seeded_dev and by batch_encrypt_dev (full rows, alpha 0:
+    no noise, so equality), are the CPU form, and no word before the first row or after the last is touched."""
+    import torch
+
+    import rs_tfhe_amd as R
+    from rs_tfhe_amd.seeded import SeededCiphertexts
+
+    p = KM.shape_params(shape)
+    sk = KM.secret_key(p)
+    count, pad, width, sentinel = 17, 8, p.n + 1, 0x5A5AA5A5
+    plain = SM.plaintexts(count, p.n + offset)
+    want, border = SM.bulk(sk.key_lv0, plain, SM.HIGH, 0.0)
+    assert not border.any()
+    sc = SeededCiphertexts(p, SEED, SM.HIGH, want[:, -1].copy())
+    assert np.array_equal(sc.expand(), want)
+    eng = R.Engine(p, 0)
+    try:
+        def through_view(call):
+            big = torch.full((pad + count * width + pad,), sentinel, dtype=torch.int32, device="cuda")
+            assert big.data_ptr() % 16 == 0
+            view = big[offset:offset + count * width].view(count, width)
+            call(view)
+            torch.cuda.synchronize()
+            return big.cpu().numpy().view(np.uint32)
+
+        tb = torch.from_numpy(sc.bodies.view(np.int32)).cuda()
+        tp = torch.from_numpy(np.ascontiguousarray(plain, np.uint32).view(np.int32)).cuda()
+        got = {
+            "expand_seeded_dev": through_view(lambda v: eng.expand_seeded_dev(SEED, SM.HIGH, tb, v)),
+            "batch_encrypt_dev": through_view(lambda v: eng.batch_encrypt_dev(sk.key_lv0, tp, 0.0, SEED, K, SM.HIGH, out=v)),
+        }
+    finally:
+        eng.close()
+    for name, g in got.items():
+        rows = g[offset:offset + count * width].reshape(count, width)
+        _say(case="alignment", call=name, n=p.n, offset=offset, differing=int((rows != want).sum()))
+        assert np.array_equal(rows, want), name
+        outside = np.concatenate([g[:offset], g[offset + count * width:]])
+        assert len(outside) == 2 * pad and (outside == sentinel).all(), f"{name} wrote outside its rows"
 
 
 def test_bulk_refusals():
