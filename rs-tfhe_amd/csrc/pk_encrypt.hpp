@@ -18,9 +18,10 @@
 //                    one word: 16 two-bit fields) and the body's addend plain + noise [rows].  The row's place in its
 //                    batch, its plaintext and whether it is a zero row (k = 0) are decided HERE, so the contraction
 //                    below is the same instantiation for ciphertexts and for key rows: output row = input row.
-//   k_pke_mfma       grid (ceil(rows / 32), column groups), 4 waves = the 4 byte planes, key tiles read one step ahead,
-//                    no K split (steps <= 256).  The planes are summed, shifted by 8p, in a 32 x 32 kPkeNT LDS tile
-//                    that goes out in coalesced row stores; column n receives the addend; columns past n are dropped.
+//   k_pke_mfma       grid (ceil(rows / 32), column groups), 4 waves = the 4 byte planes: the byte-plane K-walk of
+//                    packing.hpp (plane_walk) with the selector words as the A side, no K split (steps <= 256).  The
+//                    planes are summed (plane_merge) in a 32 x 32 kPkeNT LDS tile that goes out in coalesced row
+//                    stores; column n receives the addend; columns past n are dropped.
 //
 // Every kernel here is a template: instantiations are emitted after the library's other kernels, so the code of every
 // existing kernel stays byte-identical.
@@ -134,43 +135,20 @@ __global__ __launch_bounds__(256, 2) void k_pke_mfma(const uint32_t *__restrict_
   // selector word 2 s + kb of the row is the lane's A fragment of step s (entries 32 s + 16 kb .. + 15)
   const uint32_t *srow = sel + (live ? row : 0) * (size_t)(2 * steps) + kb;
   const int ct0 = (int)blockIdx.y * NT, tiles = (int)gridDim.y * NT;
-  const unsigned char *kp = pke8 + ((size_t)(plane * tiles + ct0) * steps) * 1024 + (size_t)lane * 16;
-  const size_t tstride = (size_t)steps * 1024;
-  auto load_b = [&](int s, km_i32x4(&B)[NT]) {
-#pragma unroll
-    for (int c = 0; c < NT; ++c) B[c] = *reinterpret_cast<const km_i32x4 *>(kp + c * tstride + (size_t)s * 1024);
-  };
   km_i32x16 acc[NT];
-#pragma unroll
-  for (int c = 0; c < NT; ++c) acc[c] = km_i32x16{0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
-  km_i32x4 Bc[NT];
-  load_b(0, Bc);
   uint32_t wc = live ? srow[0] : 0u;  // a 0 word takes no entry
-#pragma unroll 1
-  for (int s = 0; s < steps; ++s) {
-    const int sn = s + 1 < steps ? s + 1 : s;  // one step ahead (the last step reloads its own)
-    km_i32x4 Bn[NT];
-    load_b(sn, Bn);
-    const uint32_t wn = live ? srow[2 * sn] : 0u;
-    km_u32x4 a;
+  plane_walk<NT>(pke8 + ((size_t)(plane * tiles + ct0) * steps) * 1024 + (size_t)lane * 16, (size_t)steps * 1024, 0, steps,
+                 [&](int s) {
+                   const uint32_t wn = live ? srow[2 * (s + 1 < steps ? s + 1 : s)] : 0u;  // one step ahead, as the tiles
+                   km_u32x4 a;
 #pragma unroll
-    for (int q = 0; q < 4; ++q) a[q] = pke_expand4((wc >> (8 * q)) & 0xFFu);
-    const km_i32x4 A = __builtin_bit_cast(km_i32x4, a);
-#pragma unroll
-    for (int c = 0; c < NT; ++c) acc[c] = __builtin_amdgcn_mfma_i32_32x32x32_i8(A, Bc[c], acc[c], 0, 0, 0);
-#pragma unroll
-    for (int c = 0; c < NT; ++c) Bc[c] = Bn[c];
-    wc = wn;
-  }
+                   for (int q = 0; q < 4; ++q) a[q] = pke_expand4((wc >> (8 * q)) & 0xFFu);
+                   wc = wn;
+                   return __builtin_bit_cast(km_i32x4, a);
+                 },
+                 acc);
   __syncthreads();  // (the tile is zeroed)
-  // C element e of the lane: row (e & 3) + 8 (e >> 2) + 4 kb of the block, column lane & 31 of its tile
-  const uint32_t sh8 = 8u * (uint32_t)plane;
-#pragma unroll
-  for (int e = 0; e < 16; ++e) {
-    uint32_t *ln = tile + ((e & 3) + 8 * (e >> 2) + 4 * kb) * CG + (lane & 31);
-#pragma unroll
-    for (int c = 0; c < NT; ++c) atomicAdd(&ln[32 * c], (uint32_t)acc[c][e] << sh8);
-  }
+  plane_merge<NT>(acc, plane, lane, [&](int r) { return tile + r * CG; });
   __syncthreads();
   for (int r = 0; r < 32; ++r) {
     const size_t orow = row0 + (size_t)r;

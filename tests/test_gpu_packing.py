@@ -34,6 +34,21 @@ def _words(p, count, seed):
     return np.random.default_rng(seed).integers(0, 1 << 32, (count, p.n + 1), dtype=np.uint64).astype(np.uint32)
 
 
+def _unsplit_count():
+    """A count whose launch does not cut K.  A launch has ceil(count / 32) row blocks times 64 / 8 = 8 column groups
+    (the 64 tiles of a key row, 8 a workgroup) and cuts K over workgroups while that is below 4 per CU, as for every
+    count of COUNTS on 256 CUs.  The fewest row blocks on the other side are ceil(4 CUs / 8); that many full blocks plus 4
+    rows: on 256 CUs 128 * 32 + 4 = 4100 inputs, 129 row blocks, the last with four live rows, and five groups, the
+    last partial."""
+    import torch
+
+    cus = torch.cuda.get_device_properties(0).multi_processor_count
+    tile_groups = (2 * N // 32) // 8
+    count = 32 * -(-4 * cus // tile_groups) + 4
+    assert -(-count // 32) * tile_groups >= 4 * cus  # the unsplit side
+    return count
+
+
 @pytest.mark.parametrize("name", ["SECURITY_128_BIT", "SECURITY_80_BIT", "SECURITY_UINT4", "SECURITY_UINT8"])
 def test_gpu_pack_equals_the_model(name):
     import rs_tfhe_amd as R
@@ -45,7 +60,10 @@ def test_gpu_pack_equals_the_model(name):
     try:
         e.load_packing_key(pk)
         assert e.packing_key_is_loaded()
-        for count in COUNTS:
+        counts = COUNTS
+        if name == "SECURITY_UINT4":  # n = 820: the last 32-coefficient block is partial; base 32, t = 3
+            counts += (_unsplit_count(),)
+        for count in counts:
             cts = _words(p, count, count)
             got = e.pack(cts)
             assert got.shape == (-(-count // N), 2, N)
