@@ -1111,6 +1111,31 @@ inline std::vector<TRLWELv1> batch_blind_rotate(const std::vector<Ciphertext> &s
 }
 }  // namespace trgsw
 
+// ---- encrypted linear layers (tfhe_hip_batch_tlwe_matmul / tfhe_hip_batch_trlwe_matmul, include/tfhe_hip.h) ---------
+// out[g][r] = sum_j w[r][j] * input j of group g + bias[r] on the body, exact mod 2^32: w [rows][cols] int8 row-major,
+// bias [rows] torus words or nullptr.  On the key view that holds `ck` (only the key-switched packed form uses the key).
+namespace linear {
+// dense form: in [groups][cols][n+1] lv0 ciphertexts -> [groups][rows][n+1]
+inline std::vector<Torus> matmul(const CloudKey &ck, const int8_t *w, const Torus *bias, size_t rows, size_t cols,
+                                 const Torus *in, size_t groups, int device = 0) {
+  std::vector<Torus> out(groups * rows * (size_t)(ck.params.n + 1));
+  Engine::for_key(ck, device).with_key(ck, [&](tfhe_hip_ctx *c) {
+    return tfhe_hip_batch_tlwe_matmul(c, w, bias, rows, cols, in, groups, out.data());
+  });
+  return out;
+}
+// packed form: slots 0 .. cols-1 of trlwe [groups][2][N] -> [groups][rows][n+1] lv0 ciphertexts under the key-switching
+// key of `ck`, or with keyswitch == false the lv1 rows [groups][rows][N+1] before the key switch
+inline std::vector<Torus> matmul_packed(const CloudKey &ck, const int8_t *w, const Torus *bias, size_t rows, size_t cols,
+                                        const Torus *trlwe, size_t groups, bool keyswitch = true, int device = 0) {
+  std::vector<Torus> out(groups * rows * (size_t)((keyswitch ? ck.params.n : (int)N) + 1));
+  Engine::for_key(ck, device).with_key(ck, [&](tfhe_hip_ctx *c) {
+    return tfhe_hip_batch_trlwe_matmul(c, w, bias, rows, cols, trlwe, groups, keyswitch ? 1 : 0, out.data());
+  });
+  return out;
+}
+}  // namespace linear
+
 // ---- src/proxy_reenc.rs (feature `proxy-reenc`): LWE proxy re-encryption -----------------------------------------
 // Key generation is the client's (host side, as in the reference); reencrypt_tlwe_lv0 -- the proxy's walk over n * t
 // key rows per ciphertext -- runs on the GPU through tfhe_hip_load_reenc_key / tfhe_hip_batch_reencrypt.

@@ -348,6 +348,53 @@ int tfhe_hip_batch_unpack_trlwe(tfhe_hip_ctx *ctx, const uint32_t *trlwe, size_t
 int tfhe_hip_batch_unpack_trlwe_dev(tfhe_hip_ctx *ctx, const uint32_t *trlwe, size_t groups, const uint32_t *slots,
                                     size_t count, uint32_t *out, void *stream);
 
+/* ---- encrypted linear layers: a plaintext int8 matrix times LWE ciphertexts or the slots of a TRLWE ------
+ *
+ * The linear step between bootstraps: y = W x + bias with a plaintext matrix W and encrypted x, for every one of
+ * `groups` independent inputs (the samples of a batch).  On a binary-key torus scheme this is exact integer arithmetic
+ * mod 2^32; it runs on the matrix cores (csrc/matmul.hpp) and needs no key unless the packed form is asked for the
+ * final lv1 -> lv0 key switch.
+ *
+ * Definition (normative).  N = 1024, n of the context's set; all sums in wrapping u32 arithmetic.
+ *   w     [rows][cols] int8, row-major.      bias  [rows] u32 torus words, or NULL for zero.
+ * Dense form (tfhe_hip_batch_tlwe_matmul).  in [groups][cols][n+1], out [groups][rows][n+1]; for every word x <= n
+ *     out[g][r][x] = sum_{j < cols} (int32)w[r][j] * in[g][j][x]  +  (x == n ? bias[r] : 0).
+ *   1 <= cols <= 65,536 (each byte-plane accumulator of the kernel then stays at or below cols * 2^14 <= 2^30).
+ * Packed form (tfhe_hip_batch_trlwe_matmul).  trlwe [groups][2][N], the a row then the b row (the layout
+ *   tfhe_hip_batch_pack_tlwe writes); w acts on slots 0 .. cols-1 of every group, 1 <= cols <= N.  E_g[j], the lv1
+ *   extraction of slot j of group g with the EXACT wrapping negation:
+ *     E[j][i] = a[j - i]            for i <= j,
+ *     E[j][i] = 0 - a[N + j - i]    for j < i < N,
+ *     E[j][N] = b[j].
+ *   This is deliberately not the Torus::MAX - a of the unpacking key switch and tfhe_hip_batch_sample_extract (the
+ *   reference's negation), which is one LSB low per negated word: multiplied by the weights that would add the
+ *   deterministic phase offset sum_i s1[i] * sum_{j < i} w[r][j], up to 2^26 LSB -- 1/64 of the torus -- at cols = 1024
+ *   and weights of 127.
+ *     lv1[g][r][x] = sum_{j < cols} (int32)w[r][j] * E_g[j][x]  +  (x == N ? bias[r] : 0).
+ *   keyswitch == 0: out is [groups][rows][N+1] and holds these rows (ciphertexts under s1); no key is needed.
+ *   keyswitch != 0: out is [groups][rows][n+1] and holds trgsw::identity_key_switching (trgsw.rs:332-360) of them
+ *   under the handle's cloud key -- the words tfhe_hip_batch_identity_key_switch returns for the rows.  The rows pass
+ *   through the context's lv1 scratch like a bootstrap's, and TFHE_HIP_KS_KERNEL and the automatic choice of the
+ *   key-switch kernel apply as they do there.  TFHE_HIP_ENOKEY on a handle without a cloud key.
+ * Consequences.  Before any key switch the phase of an output row is sum_j w[r][j] * phase(input j) + bias[r], exactly,
+ *   mod 2^32 (input j: in[g][j], or slot j of trlwe[g]); the noise variance scales by sum_j w[r][j]^2.  Under the
+ *   (msg mod m) / (2m) encoding the sum of the messages is therefore taken mod 2m on the torus.  Weights wider than int8
+ *   are the caller's affair: split them into int8 limbs and combine the products with tfhe_hip_batch_tlwe_lincomb.
+ * Semantics.  rows >= 1 and rows * groups <= 2^31 - 1.  TFHE_HIP_EINVAL for rows == 0, cols out of range, a NULL w,
+ *   in / trlwe or out (with groups > 0) and rows * groups too large; groups == 0 with valid rows and cols returns
+ *   TFHE_HIP_OK and writes nothing.  out must not overlap the input.  The calls are bulk calls (the context's mutex and
+ *   the one staging path of the host-pointer forms, never the combining front end).  _dev: every pointer, w and bias
+ *   included, is device memory; the call is queued on `stream` (NULL: the context's stream).  w needs no alignment
+ *   (rows that start on 16-byte boundaries -- cols a multiple of 16 -- load fastest). */
+int tfhe_hip_batch_tlwe_matmul(tfhe_hip_ctx *ctx, const int8_t *w, const uint32_t *bias, size_t rows, size_t cols,
+                               const uint32_t *in, size_t groups, uint32_t *out);
+int tfhe_hip_batch_tlwe_matmul_dev(tfhe_hip_ctx *ctx, const int8_t *w, const uint32_t *bias, size_t rows, size_t cols,
+                                   const uint32_t *in, size_t groups, uint32_t *out, void *stream);
+int tfhe_hip_batch_trlwe_matmul(tfhe_hip_ctx *ctx, const int8_t *w, const uint32_t *bias, size_t rows, size_t cols,
+                                const uint32_t *trlwe, size_t groups, int keyswitch, uint32_t *out);
+int tfhe_hip_batch_trlwe_matmul_dev(tfhe_hip_ctx *ctx, const int8_t *w, const uint32_t *bias, size_t rows, size_t cols,
+                                    const uint32_t *trlwe, size_t groups, int keyswitch, uint32_t *out, void *stream);
+
 /* ---- encrypted-table key switch and the tree bootstrap: any function of two encrypted digits ------
  *
  * A programmable bootstrap evaluates a table of ONE input, whose message modulus the parameter set caps (16 on

@@ -108,6 +108,10 @@ SIGNATURES = {
     "tfhe_hip_batch_pack_tlwe_dev": (C.c_int, [_CTX, _P, _SZ, _P, _P]),
     "tfhe_hip_batch_unpack_trlwe": (C.c_int, [_CTX, _P, _SZ, _P, _SZ, _P]),
     "tfhe_hip_batch_unpack_trlwe_dev": (C.c_int, [_CTX, _P, _SZ, _P, _SZ, _P, _P]),
+    "tfhe_hip_batch_tlwe_matmul": (C.c_int, [_CTX, _P, _P, _SZ, _SZ, _P, _SZ, _P]),
+    "tfhe_hip_batch_tlwe_matmul_dev": (C.c_int, [_CTX, _P, _P, _SZ, _SZ, _P, _SZ, _P, _P]),
+    "tfhe_hip_batch_trlwe_matmul": (C.c_int, [_CTX, _P, _P, _SZ, _SZ, _P, _SZ, C.c_int, _P]),
+    "tfhe_hip_batch_trlwe_matmul_dev": (C.c_int, [_CTX, _P, _P, _SZ, _SZ, _P, _SZ, C.c_int, _P, _P]),
     "tfhe_hip_batch_pack_table": (C.c_int, [_CTX, _P, C.c_int, _SZ, _P]),
     "tfhe_hip_batch_pack_table_dev": (C.c_int, [_CTX, _P, C.c_int, _SZ, _P, _P]),
     "tfhe_hip_batch_bootstrap_bivariate": (C.c_int, [_CTX, _P, _P, _P, C.c_int, C.c_int, C.c_int, _P, _SZ]),

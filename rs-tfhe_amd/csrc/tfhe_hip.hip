@@ -2104,6 +2104,7 @@ int tfhe_hip_synchronize(tfhe_hip_ctx *ctx) {
 #include "seeded.hpp"
 #include "packing.hpp"
 #include "unpack.hpp"
+#include "matmul.hpp"
 #include "table.hpp"
 #include "packing_keygen.hpp"
 #include "pk_encrypt.hpp"

@@ -645,6 +645,91 @@ class Engine(_Handle):
                                                             self._tp(None, bodies), count, self._tp(None, out),
                                                             self._stream_ptr(None, stream)))
 
+    # -- encrypted linear layers (include/tfhe_hip.h): a plaintext int8 matrix times ciphertexts ------------------------
+    @staticmethod
+    def _weights(w, bias):
+        """(w as C-contiguous [rows][cols] int8, bias as [rows] u32 or None) after the shape checks."""
+        w = np.asarray(w)
+        if w.ndim != 2 or w.shape[0] < 1 or w.shape[1] < 1:
+            raise ValueError("w must be [rows][cols] with rows, cols >= 1")
+        if w.dtype != np.int8:
+            if not np.issubdtype(w.dtype, np.integer) or w.min() < -128 or w.max() > 127:
+                raise ValueError("weights must be integers in [-128, 127]")
+        w = np.ascontiguousarray(w, dtype=np.int8)
+        if bias is not None:
+            bias = _u32(bias).reshape(-1)
+            if len(bias) != w.shape[0]:
+                raise ValueError("bias must be [rows]")
+        return w, bias
+
+    def batch_tlwe_matmul(self, w, cts, bias=None) -> np.ndarray:
+        """out[g][r] = sum_j w[r][j] * cts[g][j] + bias[r] on the body (`tfhe_hip_batch_tlwe_matmul`): w [rows][cols]
+        int8, cts [groups][cols][n+1] (or [cols][n+1]: one group), bias [rows] torus words or None.  Returns
+        [groups][rows][n+1].  Needs no key."""
+        from .linear import MAX_COLS
+
+        w, bias = self._weights(w, bias)
+        rows, cols = w.shape
+        width = self.params.n + 1
+        cts = _u32(cts)
+        if cols > MAX_COLS or cts.ndim not in (2, 3) or cts.shape[-2:] != (cols, width):
+            raise ValueError(f"cts must be [groups][{cols}][{width}] with cols <= {MAX_COLS}")
+        groups = cts.shape[0] if cts.ndim == 3 else 1
+        out = np.empty((groups, rows, width), np.uint32)
+        self._call("batch_tlwe_matmul", _ptr(w), _ptr(bias), rows, cols, _ptr(cts), groups, _ptr(out))
+        return out
+
+    def batch_trlwe_matmul(self, w, trlwe, bias=None, keyswitch: bool = True) -> np.ndarray:
+        """The same product on slots 0 .. cols-1 of every TRLWE lv1 of trlwe [groups][2][N]
+        (`tfhe_hip_batch_trlwe_matmul`).  keyswitch=True: [groups][rows][n+1] lv0 ciphertexts under the cloud key's
+        key-switching key; keyswitch=False: [groups][rows][N+1] lv1 ciphertexts, no key needed."""
+        w, bias = self._weights(w, bias)
+        rows, cols = w.shape
+        trlwe = _u32(trlwe)
+        if cols > N or trlwe.ndim not in (2, 3) or trlwe.shape[-2:] != (2, N):
+            raise ValueError(f"trlwe must be [groups][2][{N}] and cols <= {N}")
+        trlwe = trlwe.reshape(-1, 2, N)
+        out = np.empty((len(trlwe), rows, (self.params.n if keyswitch else N) + 1), np.uint32)
+        self._call("batch_trlwe_matmul", _ptr(w), _ptr(bias), rows, cols, _ptr(trlwe), len(trlwe), int(bool(keyswitch)),
+                   _ptr(out))
+        return out
+
+    def _dev_weights(self, w, bias):
+        """(rows, cols) of a contiguous int8 CUDA tensor w [rows][cols] on this engine's GPU; bias [rows] or None."""
+        if w is None or not w.is_cuda or w.dim() != 2 or w.element_size() != 1 or not w.is_contiguous() or \
+                w.device.index != self.device or w.shape[0] < 1 or w.shape[1] < 1:
+            raise ValueError(f"w must be a contiguous int8 CUDA tensor [rows][cols] on cuda:{self.device}")
+        if bias is not None and bias.numel() != w.shape[0]:
+            raise ValueError("bias must be [rows]")
+        return int(w.shape[0]), int(w.shape[1])
+
+    def batch_tlwe_matmul_dev(self, w, cts, out, bias=None, stream=None) -> None:
+        """Device form: w int8 [rows][cols], cts [groups][cols][n+1], out [groups][rows][n+1] and bias [rows] (or None)
+        CUDA tensors on this engine's GPU (32-bit words but for w); out must not overlap cts."""
+        from .linear import MAX_COLS
+
+        rows, cols = self._dev_weights(w, bias)
+        width = self.params.n + 1
+        if cols > MAX_COLS or cts is None or cts.dim() != 3 or tuple(cts.shape[1:]) != (cols, width):
+            raise ValueError(f"cts must be [groups][{cols}][{width}] with cols <= {MAX_COLS}")
+        groups = int(cts.shape[0])
+        if out is None or tuple(out.shape) != (groups, rows, width):
+            raise ValueError(f"out must be [{groups}][{rows}][{width}]")
+        self._call("batch_tlwe_matmul_dev", C.c_void_p(w.data_ptr()), self._tp(None, bias), rows, cols, self._tp(None, cts),
+                   groups, self._tp(None, out), self._stream_ptr(None, stream))
+
+    def batch_trlwe_matmul_dev(self, w, trlwe, out, bias=None, keyswitch: bool = True, stream=None) -> None:
+        """Device form: trlwe [groups][2][N], out [groups][rows][n+1] (keyswitch) or [groups][rows][N+1]."""
+        rows, cols = self._dev_weights(w, bias)
+        if cols > N or trlwe is None or trlwe.dim() != 3 or tuple(trlwe.shape[1:]) != (2, N):
+            raise ValueError(f"trlwe must be [groups][2][{N}] and cols <= {N}")
+        groups = int(trlwe.shape[0])
+        width = (self.params.n if keyswitch else N) + 1
+        if out is None or tuple(out.shape) != (groups, rows, width):
+            raise ValueError(f"out must be [{groups}][{rows}][{width}]")
+        self._call("batch_trlwe_matmul_dev", C.c_void_p(w.data_ptr()), self._tp(None, bias), rows, cols,
+                   self._tp(None, trlwe), groups, int(bool(keyswitch)), self._tp(None, out), self._stream_ptr(None, stream))
+
     # -- encrypted-table key switch and the tree bootstrap's device form (include/tfhe_hip.h) ----------------------------
     def pack_table(self, stage1, m: int) -> np.ndarray:
         """[m][count][n+1] lv0 ciphertexts, function-major (what batch_lincomb_bootstrap_many returns) ->

@@ -1,0 +1,117 @@
+"""Encrypted linear layers: y = W x + bias with a plaintext int8 matrix W and encrypted x ("encrypted linear layers",
+include/tfhe_hip.h; csrc/matmul.hpp).
+
+The inputs are LWE ciphertexts [groups][cols][n+1] (dense form) or the first `cols` slots of TRLWE lv1 ciphertexts
+[groups][2][N] (packed form: what packing.pack wrote, or what a client encrypted with SecretKey.encrypt_packed_*).
+Everything is integer arithmetic mod 2^32, so the numpy models here ARE the definition and the GPU equals them word for
+word: the phase of output row r is sum_j w[r][j] * phase(input j) + bias[r] exactly, and the noise variance scales by
+sum_j w[r][j]^2.  Under the (msg mod m) / (2m) encoding the messages add mod 2m on the torus: keep every row sum below m
+when a programmable bootstrap follows, so that it stays in the table's non-negacyclic half.
+"""
+from __future__ import annotations
+
+import numpy as np
+
+from .params import N, SecurityParams
+
+MAX_COLS = 65536  # dense form: each byte-plane accumulator of the kernel stays at or below cols * 2^14 <= 2^30
+
+
+def _weights(w, bias, max_cols: int):
+    """(w as [rows][cols] int64, bias as [rows] u32 or None) after the header's shape checks."""
+    w = np.asarray(w)
+    if w.ndim != 2 or w.shape[0] < 1 or not 1 <= w.shape[1] <= max_cols:
+        raise ValueError(f"w must be [rows][cols] with rows >= 1 and 1 <= cols <= {max_cols}")
+    if not np.issubdtype(w.dtype, np.integer) or w.min() < -128 or w.max() > 127:
+        raise ValueError("weights must be integers in [-128, 127]")
+    if bias is not None:
+        bias = np.ascontiguousarray(bias, dtype=np.uint32).reshape(-1)
+        if len(bias) != w.shape[0]:
+            raise ValueError("bias must be [rows]")
+    return w.astype(np.int64), bias
+
+
+def _product(w, rows_in, bias) -> np.ndarray:
+    """[groups][cols][width] u32 -> [groups][rows][width]: sum_j w[r][j] * in[g][j] mod 2^32, + bias on the last word.
+    The words are split in 16-bit halves so that the int64 sums stay below 2^40."""
+    x = rows_in.astype(np.int64)
+    lo = np.matmul(w, x & 0xFFFF)
+    hi = np.matmul(w, x >> 16)
+    out = ((lo + (hi << 16)) & 0xFFFFFFFF).astype(np.uint32)
+    if bias is not None:
+        out[..., -1] += bias
+    return out
+
+
+def matmul_model(params: SecurityParams, w, cts, bias=None) -> np.ndarray:
+    """The dense form's definition: w [rows][cols] int8, cts [groups][cols][width] (or [cols][width]: one group), bias
+    [rows] torus words or None -> [groups][rows][width] u32.  width is n + 1 for lv0 ciphertexts; N + 1 (lv1 rows) is
+    accepted too, which is how matmul_packed_model uses it."""
+    w, bias = _weights(w, bias, MAX_COLS)
+    cts = np.asarray(cts, np.uint32)
+    if cts.ndim == 2:
+        cts = cts[None]
+    if cts.ndim != 3 or cts.shape[1] != w.shape[1] or cts.shape[2] not in (params.n + 1, N + 1):
+        raise ValueError(f"cts must be [groups][{w.shape[1]}][{params.n + 1}]")
+    return _product(w, cts, bias)
+
+
+def extract_rows_exact(trlwe, slots) -> np.ndarray:
+    """The lv1 extraction of slot s = G N + j for every s in `slots`, with the exact wrapping negation:
+    r[i] = a_G[j - i] for i <= j, 0 - a_G[N + j - i] for i > j, r[N] = b_G[j]: [len(slots)][N+1] u32.
+    (packing.extract_rows has the reference's Torus::MAX - a instead: one LSB lower in every negated word.)"""
+    trlwe = np.asarray(trlwe, np.uint32).reshape(-1, 2, N)
+    s = np.asarray(slots, np.int64).reshape(-1)
+    if len(s) and (s.min() < 0 or s.max() >= len(trlwe) * N):
+        raise ValueError("slot out of range")
+    G, j = s // N, s % N
+    i = np.arange(N)
+    out = np.empty((len(s), N + 1), np.uint32)
+    r = np.take_along_axis(trlwe[G, 0], (j[:, None] - i[None, :]) % N, axis=1)
+    out[:, :N] = np.where(i[None, :] > j[:, None], np.uint32(0) - r, r)
+    out[:, N] = trlwe[G, 1, j]
+    return out
+
+
+def matmul_packed_model(params: SecurityParams, w, trlwe, bias=None) -> np.ndarray:
+    """The packed form's definition without the key switch: matmul_model on extract_rows_exact of slots 0 .. cols-1 of
+    every group of trlwe [groups][2][N] -> [groups][rows][N+1] lv1 rows.  The key-switched result is
+    packing.key_switch_model(params, ksk, rows) of these rows."""
+    wi, bias = _weights(w, bias, N)
+    trlwe = np.asarray(trlwe, np.uint32).reshape(-1, 2, N)
+    cols = wi.shape[1]
+    slots = (np.arange(len(trlwe))[:, None] * N + np.arange(cols)[None, :]).reshape(-1)
+    return matmul_model(params, wi, extract_rows_exact(trlwe, slots).reshape(len(trlwe), cols, N + 1), bias)
+
+
+def _checked(w, bias, max_cols: int):
+    """(w as int8, bias as u32 or None): what the user-level calls check before they touch the library."""
+    w, bias = _weights(w, bias, max_cols)
+    return w.astype(np.int8), bias
+
+
+def matmul(w, cts, cloud_key, bias=None, device: int = 0) -> np.ndarray:
+    """The server side, dense form: [groups][cols][n+1] ciphertexts -> [groups][rows][n+1] on the GPU
+    (Engine.batch_tlwe_matmul on the shared context of `cloud_key`'s parameter set; the product itself uses no key)."""
+    from .bootstrap import keyed_engine
+
+    p = cloud_key.params
+    w8, bias = _checked(w, bias, MAX_COLS)
+    cts = np.ascontiguousarray(cts, dtype=np.uint32)
+    if cts.ndim not in (2, 3) or cts.shape[-2:] != (w8.shape[1], p.n + 1):
+        raise ValueError(f"cts must be [groups][{w8.shape[1]}][{p.n + 1}]")
+    with keyed_engine(cloud_key, device) as view:
+        return view.batch_tlwe_matmul(w8, cts, bias)
+
+
+def matmul_packed(w, packed, cloud_key, bias=None, keyswitch: bool = True, device: int = 0) -> np.ndarray:
+    """The server side, packed form: slots 0 .. cols-1 of [groups][2][N] TRLWE lv1 ciphertexts -> [groups][rows][n+1]
+    lv0 ciphertexts under `cloud_key`'s key-switching key (keyswitch=False: [groups][rows][N+1] lv1 rows)."""
+    from .bootstrap import keyed_engine
+
+    w8, bias = _checked(w, bias, N)
+    packed = np.ascontiguousarray(packed, dtype=np.uint32)
+    if packed.ndim not in (2, 3) or packed.shape[-2:] != (2, N):
+        raise ValueError(f"packed must be [groups][2][{N}]")
+    with keyed_engine(cloud_key, device) as view:
+        return view.batch_trlwe_matmul(w8, packed, bias, keyswitch)

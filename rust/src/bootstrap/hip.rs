@@ -124,6 +124,22 @@ extern "C" {   // packing key switch (include/tfhe_hip.h): up to N lv0 results i
                                         alpha: f64, rng_key: *const u8, key_out: *mut u32) -> c_int;
 }
 
+#[allow(non_camel_case_types)]
+type int8_t = i8;   // the header's spelling of the weights' type
+
+extern "C" {   // encrypted linear layers (include/tfhe_hip.h): a plaintext int8 matrix times LWE ciphertexts or TRLWE slots;
+    // no pool forms, they run on a member context (tfhe_hip_pool_ctx) of the cloud key's view
+    fn tfhe_hip_batch_tlwe_matmul(ctx: *mut TfheHipCtx, w: *const int8_t, bias: *const u32, rows: usize, cols: usize,
+                                  input: *const u32, groups: usize, out: *mut u32) -> c_int;
+    fn tfhe_hip_batch_tlwe_matmul_dev(ctx: *mut TfheHipCtx, w: *const int8_t, bias: *const u32, rows: usize, cols: usize,
+                                      input: *const u32, groups: usize, out: *mut u32, stream: *mut c_void) -> c_int;
+    fn tfhe_hip_batch_trlwe_matmul(ctx: *mut TfheHipCtx, w: *const int8_t, bias: *const u32, rows: usize, cols: usize,
+                                   trlwe: *const u32, groups: usize, keyswitch: c_int, out: *mut u32) -> c_int;
+    fn tfhe_hip_batch_trlwe_matmul_dev(ctx: *mut TfheHipCtx, w: *const int8_t, bias: *const u32, rows: usize, cols: usize,
+                                       trlwe: *const u32, groups: usize, keyswitch: c_int, out: *mut u32,
+                                       stream: *mut c_void) -> c_int;
+}
+
 /// A member context of a pool (tfhe_hip_pool_ctx): opaque, owned by the pool.
 #[repr(C)]
 pub struct TfheHipCtx { _private: [u8; 0] }
@@ -667,6 +683,66 @@ impl HipEngine {
     pub unsafe fn unpack_trlwe_dev(&self, home: usize, trlwe: *const u32, groups: usize, slots: *const u32, count: usize,
                                    out: *mut u32, stream: *mut c_void, ck: &CloudKey) {
         self.with_key(ck, |v| (tfhe_hip_pool_batch_unpack_trlwe_dev(v, home as c_int, trlwe, groups, slots, count, out, stream), ()));
+    }
+
+    /// Encrypted linear layer, dense form (`tfhe_hip_batch_tlwe_matmul`): `w` is [rows][cols] int8 row-major, `input`
+    /// [groups][cols][n+1] flat, `bias` [rows] torus words; returns [groups][rows][n+1] flat with
+    /// out[g][r] = sum_j w[r][j] * input[g][j] + bias[r] on the body, exact mod 2^32.  Runs on the first member of `ck`'s
+    /// key view (the call has no pool form; the product itself uses no key).
+    pub fn tlwe_matmul(&self, w: &[i8], bias: Option<&[u32]>, rows: usize, cols: usize, input: &[u32], ck: &CloudKey) -> Vec<u32> {
+        assert!(rows > 0 && cols > 0 && w.len() == rows * cols, "w is [rows][cols]");
+        assert!(input.len() % (cols * W) == 0, "input is [groups][cols][n+1]");
+        assert!(bias.map_or(true, |b| b.len() == rows), "bias is [rows]");
+        let groups = input.len() / (cols * W);
+        let bp = bias.map_or(std::ptr::null(), |b| b.as_ptr());
+        let mut out = vec![0u32; groups * rows * W];
+        self.with_key(ck, |v| {
+            let ctx = unsafe { tfhe_hip_pool_ctx(v, 0) };
+            assert!(!ctx.is_null(), "tfhe_hip_pool_ctx failed");
+            Self::check_ctx(ctx, unsafe {
+                tfhe_hip_batch_tlwe_matmul(ctx, w.as_ptr(), bp, rows, cols, input.as_ptr(), groups, out.as_mut_ptr())
+            });
+            (0, ())
+        });
+        out
+    }
+    /// The packed form (`tfhe_hip_batch_trlwe_matmul`): the same product on slots 0 .. cols-1 of every group of `trlwe`
+    /// ([groups][2][N] flat), extracted with the exact wrapping negation.  `keyswitch`: [groups][rows][n+1] lv0
+    /// ciphertexts under `ck`'s key-switching key; without, the lv1 rows [groups][rows][N+1].
+    pub fn trlwe_matmul(&self, w: &[i8], bias: Option<&[u32]>, rows: usize, cols: usize, trlwe: &[u32], keyswitch: bool,
+                        ck: &CloudKey) -> Vec<u32> {
+        assert!(rows > 0 && cols > 0 && cols <= N && w.len() == rows * cols, "w is [rows][cols], cols <= N");
+        assert_eq!(trlwe.len() % (2 * N), 0, "trlwe is [groups][2][N]");
+        assert!(bias.map_or(true, |b| b.len() == rows), "bias is [rows]");
+        let groups = trlwe.len() / (2 * N);
+        let bp = bias.map_or(std::ptr::null(), |b| b.as_ptr());
+        let mut out = vec![0u32; groups * rows * if keyswitch { W } else { N + 1 }];
+        self.with_key(ck, |v| {
+            let ctx = unsafe { tfhe_hip_pool_ctx(v, 0) };
+            assert!(!ctx.is_null(), "tfhe_hip_pool_ctx failed");
+            Self::check_ctx(ctx, unsafe {
+                tfhe_hip_batch_trlwe_matmul(ctx, w.as_ptr(), bp, rows, cols, trlwe.as_ptr(), groups, keyswitch as c_int,
+                                            out.as_mut_ptr())
+            });
+            (0, ())
+        });
+        out
+    }
+    /// Both forms on device pointers of the first member's GPU (`w` and `bias` too; `bias` may be null), queued on
+    /// `stream`; `trlwe_input` selects the packed form.  Safety: the pointers must stay valid until the work has run.
+    pub unsafe fn matmul_dev(&self, trlwe_input: bool, w: *const i8, bias: *const u32, rows: usize, cols: usize,
+                             input: *const u32, groups: usize, keyswitch: bool, out: *mut u32, stream: *mut c_void,
+                             ck: &CloudKey) {
+        self.with_key(ck, |v| {
+            let ctx = tfhe_hip_pool_ctx(v, 0);
+            assert!(!ctx.is_null(), "tfhe_hip_pool_ctx failed");
+            Self::check_ctx(ctx, if trlwe_input {
+                tfhe_hip_batch_trlwe_matmul_dev(ctx, w, bias, rows, cols, input, groups, keyswitch as c_int, out, stream)
+            } else {
+                tfhe_hip_batch_tlwe_matmul_dev(ctx, w, bias, rows, cols, input, groups, out, stream)
+            });
+            (0, ())
+        });
     }
 
     /// the seed, 64 evenly spaced body words and the size (FNV-style mix), as the C++ mirror samples a packing key
