@@ -1134,6 +1134,27 @@ inline std::vector<Torus> matmul_packed(const CloudKey &ck, const int8_t *w, con
   });
   return out;
 }
+// 2-D convolution (tfhe_hip_batch_tlwe_conv2d): w [out_c][k_h][k_w][in_c] int8 over in [groups][in_h][in_w][in_c][n+1],
+// channels-last, zero outside the map -> [groups][out_h][out_w][out_c][n+1] with out_h = (in_h + 2 pad_h - k_h) /
+// stride_h + 1 and out_w likewise; bias [out_c] torus words or nullptr.  A shape the header refuses throws, as every
+// call here does.
+inline std::vector<Torus> conv2d(const CloudKey &ck, const tfhe_hip_conv2d_shape &shape, const int8_t *w, const Torus *bias,
+                                 const Torus *in, size_t groups, int device = 0) {
+  size_t cts = 0;  // a refused shape leaves `out` empty: the library reports it before it writes
+  if (shape.stride_h && shape.stride_w && shape.k_h <= (uint64_t)shape.in_h + 2 * (uint64_t)shape.pad_h &&
+      shape.k_w <= (uint64_t)shape.in_w + 2 * (uint64_t)shape.pad_w) {
+    const uint64_t out_h = ((uint64_t)shape.in_h + 2 * (uint64_t)shape.pad_h - shape.k_h) / shape.stride_h + 1;
+    const uint64_t out_w = ((uint64_t)shape.in_w + 2 * (uint64_t)shape.pad_w - shape.k_w) / shape.stride_w + 1;
+    const uint64_t per = out_h * out_w;  // < 2^62
+    if (per <= 0x7FFFFFFFull && per * shape.out_c <= 0x7FFFFFFFull && groups <= 0x7FFFFFFFull / (per * shape.out_c ? per * shape.out_c : 1))
+      cts = groups * (size_t)(per * shape.out_c);
+  }
+  std::vector<Torus> out(cts * (size_t)(ck.params.n + 1));
+  Engine::for_key(ck, device).with_key(ck, [&](tfhe_hip_ctx *c) {
+    return tfhe_hip_batch_tlwe_conv2d(c, &shape, w, bias, in, groups, out.data());
+  });
+  return out;
+}
 }  // namespace linear
 
 // ---- src/proxy_reenc.rs (feature `proxy-reenc`): LWE proxy re-encryption -----------------------------------------

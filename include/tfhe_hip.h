@@ -395,6 +395,48 @@ int tfhe_hip_batch_trlwe_matmul(tfhe_hip_ctx *ctx, const int8_t *w, const uint32
 int tfhe_hip_batch_trlwe_matmul_dev(tfhe_hip_ctx *ctx, const int8_t *w, const uint32_t *bias, size_t rows, size_t cols,
                                     const uint32_t *trlwe, size_t groups, int keyswitch, uint32_t *out, void *stream);
 
+/* ---- encrypted 2-D convolution: int8 filters over a feature map of LWE ciphertexts ------
+ *
+ * The convolutional layer beside the linear one: `out_c` plaintext int8 filters of k_h x k_w x in_c slide over an
+ * in_h x in_w map whose every pixel holds in_c LWE ciphertexts, for each of `groups` independent maps.  It is the dense
+ * form's product evaluated as an implicit GEMM (csrc/matmul.hpp, MmConv): the kernel reads each tap's ciphertexts
+ * where they lie, so no im2col copy of the input is ever made; exact mod 2^32, no key, no atomics.
+ *
+ * Definition (normative).  Channels-last on both sides, so one layer's output is the next layer's input without a
+ * transpose; n of the context's set; all sums in wrapping u32 arithmetic.
+ *   out_h = (in_h + 2 pad_h - k_h) / stride_h + 1,  out_w likewise   (k_h <= in_h + 2 pad_h, k_w <= in_w + 2 pad_w)
+ *   in   [groups][in_h][in_w][in_c][n+1]     u32
+ *   w    [out_c][k_h][k_w][in_c]             int8  (the im2col order: K = k_h * k_w * in_c contiguous per filter)
+ *   bias [out_c] u32 torus words, or NULL for zero
+ *   out  [groups][out_h][out_w][out_c][n+1]  u32
+ *     out[g][oy][ox][oc][x] = sum_{ky,kx,ic} (int32)w[oc][ky][kx][ic]
+ *                                            * in[g][oy*stride_h + ky - pad_h][ox*stride_w + kx - pad_w][ic][x]
+ *                             + (x == n ? bias[oc] : 0)
+ *   where a term whose input coordinate falls outside the map is zero (the trivial encryption of 0: exact).
+ *   1 <= K <= 65,536 (the dense form's accumulator bound).  A 1-D convolution is in_h = k_h = 1.
+ * Consequences.  The phase of an output is sum w * phase(input) + bias[oc], exactly, mod 2^32; the noise variance scales
+ *   by the sum of w^2 over the taps that fall inside the map (a border output has fewer terms than an interior one).
+ *   What the dense form says about the message encoding and about weights wider than int8 holds here too.
+ * Semantics.  Every field but pad_h and pad_w is at least 1; in_h + 2 pad_h and in_w + 2 pad_w are at most 2^31 - 1;
+ *   groups * out_h * out_w * out_c <= 2^31 - 1 and groups * in_h * in_w * in_c <= 2^31 - 1 (ciphertexts written and
+ *   read).  TFHE_HIP_EINVAL for a NULL shape, a field that is zero or out of range, a filter larger than the padded map,
+ *   K out of range, a NULL w, in or out (with groups > 0) and a product too large -- checked in this order, shape first,
+ *   then as the dense form checks rows = out_c, cols = K and one group per output position; groups == 0 with a valid
+ *   shape returns TFHE_HIP_OK and writes nothing.  out must not overlap in.  Bulk calls (the context's mutex and the one
+ *   staging path of the host-pointer form, never the combining front end); no key is needed.  _dev: every pointer but
+ *   `shape`, w and bias included, is device memory; the call is queued on `stream` (NULL: the context's stream).  w
+ *   needs no alignment; in_c a multiple of 16 takes the kernel's fast path (one tap per 16 K-rows). */
+typedef struct tfhe_hip_conv2d_shape {
+  uint32_t in_h, in_w, in_c;   /* input feature map */
+  uint32_t out_c, k_h, k_w;    /* filters */
+  uint32_t stride_h, stride_w; /* >= 1 */
+  uint32_t pad_h, pad_w;       /* zero padding on both sides of each axis */
+} tfhe_hip_conv2d_shape;
+int tfhe_hip_batch_tlwe_conv2d(tfhe_hip_ctx *ctx, const tfhe_hip_conv2d_shape *shape, const int8_t *w,
+                               const uint32_t *bias, const uint32_t *in, size_t groups, uint32_t *out);
+int tfhe_hip_batch_tlwe_conv2d_dev(tfhe_hip_ctx *ctx, const tfhe_hip_conv2d_shape *shape, const int8_t *w,
+                                   const uint32_t *bias, const uint32_t *in, size_t groups, uint32_t *out, void *stream);
+
 /* ---- encrypted-table key switch and the tree bootstrap: any function of two encrypted digits ------
  *
  * A programmable bootstrap evaluates a table of ONE input, whose message modulus the parameter set caps (16 on

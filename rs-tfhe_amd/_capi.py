@@ -68,6 +68,13 @@ class CombineStats(C.Structure):
                 ("linger_us", C.c_double), ("pack_us", C.c_double), ("gpu_us", C.c_double), ("unpack_us", C.c_double)]
 
 
+class Conv2dShape(C.Structure):
+    """struct tfhe_hip_conv2d_shape"""
+
+    _fields_ = [(f, C.c_uint32) for f in ("in_h", "in_w", "in_c", "out_c", "k_h", "k_w", "stride_h", "stride_w",
+                                          "pad_h", "pad_w")]
+
+
 _P = C.c_void_p
 _SZ = C.c_size_t
 _CTX = C.c_void_p
@@ -112,6 +119,8 @@ SIGNATURES = {
     "tfhe_hip_batch_tlwe_matmul_dev": (C.c_int, [_CTX, _P, _P, _SZ, _SZ, _P, _SZ, _P, _P]),
     "tfhe_hip_batch_trlwe_matmul": (C.c_int, [_CTX, _P, _P, _SZ, _SZ, _P, _SZ, C.c_int, _P]),
     "tfhe_hip_batch_trlwe_matmul_dev": (C.c_int, [_CTX, _P, _P, _SZ, _SZ, _P, _SZ, C.c_int, _P, _P]),
+    "tfhe_hip_batch_tlwe_conv2d": (C.c_int, [_CTX, C.POINTER(Conv2dShape), _P, _P, _P, _SZ, _P]),
+    "tfhe_hip_batch_tlwe_conv2d_dev": (C.c_int, [_CTX, C.POINTER(Conv2dShape), _P, _P, _P, _SZ, _P, _P]),
     "tfhe_hip_batch_pack_table": (C.c_int, [_CTX, _P, C.c_int, _SZ, _P]),
     "tfhe_hip_batch_pack_table_dev": (C.c_int, [_CTX, _P, C.c_int, _SZ, _P, _P]),
     "tfhe_hip_batch_bootstrap_bivariate": (C.c_int, [_CTX, _P, _P, _P, C.c_int, C.c_int, C.c_int, _P, _SZ]),

@@ -33,7 +33,8 @@
 //   * The B loader is a template parameter: MmDense reads rows of `in`; MmToeplitz generates B[j][i] = ext[j - i]
 //     from the one TRLWE of the group, held in LDS already split (ext[t] = a[t], t >= 0; 0 - a[N + t], t < 0: 2N
 //     packed words = 8 KiB, + 4 KiB for b, the last column).  The packed form's ninth column block holds the b column
-//     alone (N + 1 = 8 * 128 + 1).
+//     alone (N + 1 = 8 * 128 + 1).  MmConv is the 2-D convolution as an implicit GEMM: a group is one output position
+//     and K-row (ky, kx, ic) is the input ciphertext under that tap, or zero in the padding -- no im2col buffer.
 //   * Epilogue: sum_p acc_p << 8p in registers, + bias in the last column, one store per element: a wave writes
 //     128-byte row segments.  No atomics, no zeroed output.
 // Expected bound: at rows = cols = 1024, n + 1 = 701, 64 groups the product is 2 * 1024 * 1024 * 701 * 64 * 4 planes
@@ -44,7 +45,7 @@
 // the expected limiter -- not the matrix pipes, and not the L2 -> LDS stream (the packed form, whose B never leaves
 // LDS, is little faster per operation).  A taller row block would halve it at 256 accumulator registers (one
 // wave per SIMD); interleaving the split of step s + 2 with the matrix instructions of step s is the other way on.
-// Measured: DESIGN.md section 9, profiles/matmul_bench.json.
+// Measured: DESIGN.md section 9, profiles/matmul_bench.json (the convolution: profiles/conv2d_bench.json).
 //
 // Every kernel here is a template: instantiations are emitted after the library's other kernels, so the code of every
 // existing kernel stays byte-identical.
@@ -79,7 +80,8 @@ __device__ __forceinline__ void mm_transpose4(const uint32_t (&x)[4], uint32_t (
 
 // ---- B loaders: fetch16 reads the operands of K-rows kb .. kb + 15 at column col as fetched (zero past `cols` and past
 // the last column), planes() gives the four plane bytes of one; `setup` runs once per workgroup before the first fetch
-// (all threads, ends synchronised).  kb is wave-uniform: a whole wave takes the unguarded path together. --------------
+// (all threads, ends synchronised; the loader is the kernel's own copy, so `setup` may keep what it decodes in it).  kb is
+// wave-uniform: a whole wave takes the unguarded path together. ------------------------------------------------------
 struct MmDense {
   static constexpr int kLdsBytes = 0;
   const uint32_t *in;  // [groups][cols][ncol]
@@ -141,6 +143,84 @@ struct MmToeplitz {
     }
   }
   __device__ __forceinline__ static uint32_t planes(uint32_t v) { return v; }  // split once, in setup
+};
+
+// floor(n / d) for n < 2^17 (a K index: K <= kMmMaxCols, + one K-step) by a multiplication: with m = ceil(2^34 / d),
+// e = m d - 2^34 < d <= 2^16 and n e < 2^33 < 2^34, so floor(n m / 2^34) = floor(n / d) (Granlund & Montgomery 1994).
+// On wave-uniform operands this is scalar arithmetic: no division in the K loop.
+__host__ __device__ __forceinline__ uint64_t mm_div_magic(uint32_t d) { return (((uint64_t)1 << 34) + d - 1) / d; }
+__device__ __forceinline__ uint32_t mm_div(uint32_t n, uint64_t magic) { return (uint32_t)(((uint64_t)n * magic) >> 34); }
+
+// 2-D convolution as an implicit GEMM (include/tfhe_hip.h, "encrypted 2-D convolution"): the kernel's group is the
+// virtual group vg = (g out_h + oy) out_w + ox, one output position; rows = out_c, cols = K = k_h k_w in_c, and K-row
+// k = (ky k_w + kx) in_c + ic of that position is the input ciphertext at (oy s_h + ky - p_h, ox s_w + kx - p_w, ic),
+// or zero in the padding.  With rows = out_c the epilogue's out[(vg rows + r) ncol + col] is the channels-last output.
+// `setup` decodes vg once per workgroup (scalar registers) and keeps the image and the position's top-left input
+// coordinate in the loader, which is the kernel's own copy.  fetch16 finds the tap of its first row with mm_div and
+//   * in_c % 16 == 0: the 16 rows lie inside one tap (kb is a multiple of 16): one wave-uniform base address, rows
+//     ncol words apart -- MmDense's unguarded path -- or no loads at all for a padding tap or past K;
+//   * any in_c: walks (ky, kx, ic) across the 16 rows; every lane loads from an in-range address (word 0 of the
+//     image stands in for padding and for rows past K) and what is not there is zeroed afterwards: no divergent
+//     branches.
+struct MmConv {
+  static constexpr int kLdsBytes = 0;
+  const uint32_t *in;      // [groups][in_h][in_w][in_c][ncol]
+  size_t img_words;        // in_h in_w in_c ncol
+  uint64_t magic_c, magic_kw;  // mm_div_magic(in_c), mm_div_magic(k_w)
+  uint32_t in_h, in_w, in_c, k_w, stride_h, stride_w, pad_h, pad_w, out_h, out_w;
+  int iy0, ix0;            // set by setup: input coordinate of tap (0, 0) of this workgroup's position
+  __device__ __forceinline__ void setup(unsigned char *, size_t vg, int) {
+    const uint32_t v = (uint32_t)vg, t = v / out_w, ox = v - t * out_w, g = t / out_h, oy = t - g * out_h;
+    in += (size_t)g * img_words;
+    iy0 = (int)(oy * stride_h) - (int)pad_h;
+    ix0 = (int)(ox * stride_w) - (int)pad_w;
+  }
+  __device__ __forceinline__ void fetch16(uint32_t (&raw)[16], const unsigned char *, size_t, size_t cols, int ncol,
+                                          size_t kb, int col) const {
+    const bool col_ok = col < ncol;
+    const uint32_t c = col_ok ? (uint32_t)col : 0u;
+    const uint32_t k = (uint32_t)kb, K = (uint32_t)cols;
+    const uint32_t tap = mm_div(k, magic_c), ky0 = mm_div(tap, magic_kw);
+    uint32_t ic = k - tap * in_c, kx = tap - ky0 * k_w, ky = ky0;
+    if ((in_c & 15u) == 0u) {
+      const uint32_t iy = (uint32_t)(iy0 + (int)ky), ix = (uint32_t)(ix0 + (int)kx);  // (negative: above every bound)
+      if (k < K && iy < in_h && ix < in_w) {
+        const uint32_t *row = in + (size_t)((iy * in_w + ix) * in_c + ic) * (size_t)ncol;
+#pragma unroll
+        for (int j = 0; j < 16; ++j, row += ncol) raw[j] = row[c];
+      } else {
+#pragma unroll
+        for (int j = 0; j < 16; ++j) raw[j] = 0u;
+      }
+    } else {
+      // the tap's state -- inside the map?  word offset of its row ic -- is worked out where the tap changes only
+      bool inside;
+      size_t off;
+      auto enter_tap = [&]() {
+        const uint32_t iy = (uint32_t)(iy0 + (int)ky), ix = (uint32_t)(ix0 + (int)kx);
+        inside = iy < in_h && ix < in_w;
+        off = inside ? (size_t)((iy * in_w + ix) * in_c + ic) * (size_t)ncol : (size_t)0;
+      };
+      enter_tap();
+#pragma unroll
+      for (int j = 0; j < 16; ++j) {
+        const bool ok = inside && k + (uint32_t)j < K;
+        const uint32_t v = in[(ok ? off : (size_t)0) + c];
+        raw[j] = ok ? v : 0u;
+        off += (size_t)ncol;
+        if (++ic == in_c) {
+          ic = 0u;
+          if (++kx == k_w) kx = 0u, ++ky;
+          enter_tap();
+        }
+      }
+    }
+    if (!col_ok) {
+#pragma unroll
+      for (int j = 0; j < 16; ++j) raw[j] = 0u;
+    }
+  }
+  __device__ __forceinline__ static uint32_t planes(uint32_t v) { return mm_planes(v); }
 };
 
 // One launch covers groups g0 .. and row blocks rb0 .. rb0 + nrb - 1 of each (nrb < all row blocks only with one group a
@@ -372,4 +452,83 @@ int tfhe_hip_batch_trlwe_matmul_dev(tfhe_hip_ctx *ctx, const int8_t *w, const ui
   CHK(matmul_checks(ctx, keyswitch != 0, w, rows, cols, (size_t)kN, trlwe, groups, out, &run));
   if (!run) return TFHE_HIP_OK;
   return matmul_packed_dev(ctx, w, bias, rows, cols, trlwe, groups, keyswitch, out, pick(ctx, stream));
+}
+
+// ---- encrypted 2-D convolution: the same GEMM with output positions for groups (MmConv) ------------------------------
+namespace {
+struct ConvGeom {
+  size_t K, out_h, out_w, positions;  // positions = groups * out_h * out_w, saturated at SIZE_MAX
+  size_t in_cts, out_cts;             // ciphertexts of `in` and of `out`
+};
+
+// The checks both calls share, in one order: shape (NULL, a zero field, a filter larger than the padded map, K), then
+// matmul_checks on the equivalent product -- rows = out_c, cols = K, one group per output position: out_c == 0, K out of
+// range, the empty batch, the pointers, out_c * positions too large -- and last the size of the input.
+int conv2d_checks(tfhe_hip_ctx *ctx, const tfhe_hip_conv2d_shape *sh, const int8_t *w, const uint32_t *in, size_t groups,
+                  const uint32_t *out, ConvGeom *geo, bool *run) {
+  *run = false;
+  if (!sh) return fail(ctx, TFHE_HIP_EINVAL, "null shape");
+  if (!sh->in_h || !sh->in_w || !sh->in_c || !sh->k_h || !sh->k_w) return fail(ctx, TFHE_HIP_EINVAL, "conv2d: a zero dimension");
+  if (!sh->stride_h || !sh->stride_w) return fail(ctx, TFHE_HIP_EINVAL, "conv2d: stride must be at least 1");
+  const uint64_t ph = (uint64_t)sh->in_h + 2 * (uint64_t)sh->pad_h, pw = (uint64_t)sh->in_w + 2 * (uint64_t)sh->pad_w;
+  if (ph > 0x7FFFFFFFull || pw > 0x7FFFFFFFull) return fail(ctx, TFHE_HIP_EINVAL, "conv2d: padded map too large");
+  if (sh->k_h > ph || sh->k_w > pw) return fail(ctx, TFHE_HIP_EINVAL, "conv2d: filter larger than the padded map");
+  const uint64_t taps = (uint64_t)sh->k_h * sh->k_w;  // < 2^62
+  const uint64_t K = taps > kMmMaxCols ? kMmMaxCols + 1 : taps * sh->in_c;  // (<= 2^48; out of range either way)
+  geo->K = (size_t)K;
+  geo->out_h = (size_t)((ph - sh->k_h) / sh->stride_h + 1);
+  geo->out_w = (size_t)((pw - sh->k_w) / sh->stride_w + 1);
+  const size_t per = geo->out_h * geo->out_w;  // < 2^62
+  geo->positions = groups > SIZE_MAX / per ? SIZE_MAX : groups * per;
+  CHK(matmul_checks(ctx, false, w, sh->out_c, geo->K, kMmMaxCols, in, geo->positions, out, run));
+  if (!*run) return TFHE_HIP_OK;
+  *run = false;
+  const uint64_t pix = (uint64_t)sh->in_h * sh->in_w;  // <= 2^62
+  if (pix > 0x7FFFFFFFull || pix * sh->in_c > 0x7FFFFFFFull || groups > 0x7FFFFFFFull / (pix * sh->in_c))
+    return fail(ctx, TFHE_HIP_EINVAL, "conv2d: groups * in_h * in_w * in_c too large");
+  geo->in_cts = groups * (size_t)(pix * sh->in_c);
+  geo->out_cts = geo->positions * sh->out_c;
+  *run = true;
+  return TFHE_HIP_OK;
+}
+
+int conv2d_dev(tfhe_hip_ctx *ctx, const tfhe_hip_conv2d_shape &sh, const ConvGeom &geo, const int8_t *w, const uint32_t *bias,
+               const uint32_t *in, uint32_t *out, hipStream_t s) {
+  const int ncol = ctx->P.n + 1;
+  MmConv ld{};
+  ld.in = in;
+  ld.img_words = (size_t)sh.in_h * sh.in_w * sh.in_c * (size_t)ncol;
+  ld.magic_c = mm_div_magic(sh.in_c);
+  ld.magic_kw = mm_div_magic(sh.k_w);
+  ld.in_h = sh.in_h, ld.in_w = sh.in_w, ld.in_c = sh.in_c, ld.k_w = sh.k_w;
+  ld.stride_h = sh.stride_h, ld.stride_w = sh.stride_w, ld.pad_h = sh.pad_h, ld.pad_w = sh.pad_w;
+  ld.out_h = (uint32_t)geo.out_h, ld.out_w = (uint32_t)geo.out_w;
+  return launch_matmul(ctx, ld, w, bias, sh.out_c, geo.K, ncol, geo.positions, out, s);
+}
+}  // namespace
+
+int tfhe_hip_batch_tlwe_conv2d(tfhe_hip_ctx *ctx, const tfhe_hip_conv2d_shape *shape, const int8_t *w, const uint32_t *bias,
+                               const uint32_t *in, size_t groups, uint32_t *out) {
+  if (!ctx) return TFHE_HIP_EINVAL;
+  ENTER(ctx);
+  bool run = false;
+  ConvGeom geo{};
+  CHK(conv2d_checks(ctx, shape, w, in, groups, out, &geo, &run));
+  if (!run) return TFHE_HIP_OK;
+  const tfhe_hip_conv2d_shape sh = *shape;
+  return host_call(ctx, false, {{w, sh.out_c * geo.K, &ctx->a}, {bias, (size_t)sh.out_c * 4, &ctx->b}, {in, tlwe_bytes(ctx, geo.in_cts), &ctx->c}},
+                   out, tlwe_bytes(ctx, geo.out_cts), [&](const void *const *d, void *o) {
+                     return conv2d_dev(ctx, sh, geo, (const int8_t *)d[0], u32(d[1]), u32(d[2]), (uint32_t *)o, ctx->stream);
+                   });
+}
+
+int tfhe_hip_batch_tlwe_conv2d_dev(tfhe_hip_ctx *ctx, const tfhe_hip_conv2d_shape *shape, const int8_t *w, const uint32_t *bias,
+                                   const uint32_t *in, size_t groups, uint32_t *out, void *stream) {
+  if (!ctx) return TFHE_HIP_EINVAL;
+  ENTER(ctx);
+  bool run = false;
+  ConvGeom geo{};
+  CHK(conv2d_checks(ctx, shape, w, in, groups, out, &geo, &run));
+  if (!run) return TFHE_HIP_OK;
+  return conv2d_dev(ctx, *shape, geo, w, bias, in, out, pick(ctx, stream));
 }

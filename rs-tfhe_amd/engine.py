@@ -730,6 +730,61 @@ class Engine(_Handle):
         self._call("batch_trlwe_matmul_dev", C.c_void_p(w.data_ptr()), self._tp(None, bias), rows, cols,
                    self._tp(None, trlwe), groups, int(bool(keyswitch)), self._tp(None, out), self._stream_ptr(None, stream))
 
+    # -- encrypted 2-D convolution (include/tfhe_hip.h): int8 filters over a feature map of ciphertexts -------------------
+    def _conv2d_shape(self, w_shape, cts_shape, bias_len, stride, padding):
+        """(struct tfhe_hip_conv2d_shape, groups, (out_h, out_w)) of filters [out_c][k_h][k_w][in_c] over a map
+        [groups][in_h][in_w][in_c][n+1] (or without the leading axis: one group), after the header's shape checks."""
+        from .linear import MAX_COLS, _pair, conv2d_out_shape
+
+        w_shape, cts_shape = tuple(int(x) for x in w_shape), tuple(int(x) for x in cts_shape)
+        if len(w_shape) != 4 or min(w_shape) < 1 or w_shape[1] * w_shape[2] * w_shape[3] > MAX_COLS:
+            raise ValueError(f"w must be [out_c][k_h][k_w][in_c] with 1 <= k_h * k_w * in_c <= {MAX_COLS}")
+        out_c, k_h, k_w, in_c = w_shape
+        if len(cts_shape) not in (4, 5) or cts_shape[-2:] != (in_c, self.params.n + 1) or min(cts_shape[-4:-2]) < 1:
+            raise ValueError(f"cts must be [groups][in_h][in_w][{in_c}][{self.params.n + 1}]")
+        if bias_len is not None and bias_len != out_c:
+            raise ValueError("bias must be [out_c]")
+        in_h, in_w = cts_shape[-4:-2]
+        (sh, sw), (ph, pw) = _pair(stride, "stride", 1), _pair(padding, "padding", 0)
+        out_hw = conv2d_out_shape(in_h, in_w, k_h, k_w, (sh, sw), (ph, pw))
+        shape = _capi.Conv2dShape(in_h, in_w, in_c, out_c, k_h, k_w, sh, sw, ph, pw)
+        return shape, (cts_shape[0] if len(cts_shape) == 5 else 1), out_hw
+
+    def batch_tlwe_conv2d(self, w, cts, bias=None, stride=1, padding=0) -> np.ndarray:
+        """out[g][oy][ox][oc] = sum_{ky,kx,ic} w[oc][ky][kx][ic] * cts[g][oy*s_h + ky - p_h][ox*s_w + kx - p_w][ic] +
+        bias[oc] on the body, zero outside the map (`tfhe_hip_batch_tlwe_conv2d`): w [out_c][k_h][k_w][in_c] int8, cts
+        [groups][in_h][in_w][in_c][n+1] (or [in_h][in_w][in_c][n+1]: one group), bias [out_c] torus words or None,
+        stride and padding an int or a (vertical, horizontal) pair.  Returns [groups][out_h][out_w][out_c][n+1].
+        Needs no key."""
+        w = np.asarray(w)
+        if w.dtype != np.int8:
+            if not np.issubdtype(w.dtype, np.integer) or (w.size and (w.min() < -128 or w.max() > 127)):
+                raise ValueError("weights must be integers in [-128, 127]")
+        w = np.ascontiguousarray(w, dtype=np.int8)
+        bias = None if bias is None else _u32(bias).reshape(-1)
+        cts = _u32(cts)
+        shape, groups, (out_h, out_w) = self._conv2d_shape(w.shape, cts.shape, None if bias is None else len(bias),
+                                                           stride, padding)
+        out = np.empty((groups, out_h, out_w, w.shape[0], self.params.n + 1), np.uint32)
+        self._call("batch_tlwe_conv2d", C.pointer(shape), _ptr(w), _ptr(bias), _ptr(cts), groups, _ptr(out))
+        return out
+
+    def batch_tlwe_conv2d_dev(self, w, cts, out, bias=None, stride=1, padding=0, stream=None) -> None:
+        """Device form: w int8 [out_c][k_h][k_w][in_c], cts [groups][in_h][in_w][in_c][n+1], out
+        [groups][out_h][out_w][out_c][n+1] and bias [out_c] (or None) CUDA tensors on this engine's GPU (32-bit words
+        but for w); out must not overlap cts."""
+        if w is None or not w.is_cuda or w.element_size() != 1 or not w.is_contiguous() or w.device.index != self.device:
+            raise ValueError(f"w must be a contiguous int8 CUDA tensor [out_c][k_h][k_w][in_c] on cuda:{self.device}")
+        if cts is None or len(cts.shape) != 5:
+            raise ValueError("cts must be [groups][in_h][in_w][in_c][n+1]")
+        shape, groups, (out_h, out_w) = self._conv2d_shape(w.shape, cts.shape, None if bias is None else bias.numel(),
+                                                           stride, padding)
+        want = (groups, out_h, out_w, int(w.shape[0]), self.params.n + 1)
+        if out is None or tuple(out.shape) != want:
+            raise ValueError("out must be [%d][%d][%d][%d][%d]" % want)
+        self._call("batch_tlwe_conv2d_dev", C.pointer(shape), C.c_void_p(w.data_ptr()), self._tp(None, bias),
+                   self._tp(None, cts), groups, self._tp(None, out), self._stream_ptr(None, stream))
+
     # -- encrypted-table key switch and the tree bootstrap's device form (include/tfhe_hip.h) ----------------------------
     def pack_table(self, stage1, m: int) -> np.ndarray:
         """[m][count][n+1] lv0 ciphertexts, function-major (what batch_lincomb_bootstrap_many returns) ->

@@ -7,6 +7,10 @@ Everything is integer arithmetic mod 2^32, so the numpy models here ARE the defi
 word: the phase of output row r is sum_j w[r][j] * phase(input j) + bias[r] exactly, and the noise variance scales by
 sum_j w[r][j]^2.  Under the (msg mod m) / (2m) encoding the messages add mod 2m on the torus: keep every row sum below m
 when a programmable bootstrap follows, so that it stays in the table's non-negacyclic half.
+
+The convolutional layer ("encrypted 2-D convolution" in the header) is the dense form over the taps of a filter:
+conv2d_model is its definition, an explicit im2col into the same exact sum; conv2d is the server side.  Feature maps are
+channels-last, [groups][in_h][in_w][in_c][n+1], on both sides of a layer.
 """
 from __future__ import annotations
 
@@ -84,6 +88,59 @@ def matmul_packed_model(params: SecurityParams, w, trlwe, bias=None) -> np.ndarr
     return matmul_model(params, wi, extract_rows_exact(trlwe, slots).reshape(len(trlwe), cols, N + 1), bias)
 
 
+def _pair(v, name: str, least: int):
+    """stride / padding as (vertical, horizontal): an int for both or a pair, each at least `least`."""
+    pair = (v, v) if isinstance(v, (int, np.integer)) else tuple(v) if isinstance(v, (tuple, list, np.ndarray)) else ()
+    if len(pair) != 2 or any(not isinstance(x, (int, np.integer)) or x < least for x in pair):
+        raise ValueError(f"{name} must be an int or a pair of ints, each at least {least}")
+    return int(pair[0]), int(pair[1])
+
+
+def conv2d_out_shape(in_h: int, in_w: int, k_h: int, k_w: int, stride=1, padding=0):
+    """(out_h, out_w) = ((in_h + 2 pad_h - k_h) // stride_h + 1, likewise) of the header's definition; the filter must
+    fit the padded map."""
+    (sh, sw), (ph, pw) = _pair(stride, "stride", 1), _pair(padding, "padding", 0)
+    if min(in_h, in_w, k_h, k_w) < 1 or k_h > in_h + 2 * ph or k_w > in_w + 2 * pw:
+        raise ValueError("the filter must be at least 1 x 1 and no larger than the padded map")
+    return (in_h + 2 * ph - k_h) // sh + 1, (in_w + 2 * pw - k_w) // sw + 1
+
+
+def _filters(w, bias):
+    """(w as [out_c][k_h][k_w][in_c] int64, bias as [out_c] u32 or None): _weights on the im2col matrix [out_c][K]."""
+    w = np.asarray(w)
+    if w.ndim != 4 or 0 in w.shape:
+        raise ValueError("w must be [out_c][k_h][k_w][in_c] with every dimension at least 1")
+    w2, bias = _weights(w.reshape(w.shape[0], -1), bias, MAX_COLS)
+    return w2.reshape(w.shape), bias
+
+
+def conv2d_model(params: SecurityParams, w, cts, bias=None, stride=1, padding=0) -> np.ndarray:
+    """The convolution's definition ("encrypted 2-D convolution", include/tfhe_hip.h): w [out_c][k_h][k_w][in_c] int8,
+    cts [groups][in_h][in_w][in_c][n+1] (or [in_h][in_w][in_c][n+1]: one group), bias [out_c] torus words or None ->
+    [groups][out_h][out_w][out_c][n+1] u32.  An explicit im2col of the zero-padded map, one output row at a time, into
+    _product: the same exact sum as the dense form."""
+    w, bias = _filters(w, bias)
+    out_c, k_h, k_w, in_c = w.shape
+    cts = np.asarray(cts, np.uint32)
+    if cts.ndim == 4:
+        cts = cts[None]
+    if cts.ndim != 5 or cts.shape[3] != in_c or cts.shape[4] != params.n + 1:
+        raise ValueError(f"cts must be [groups][in_h][in_w][{in_c}][{params.n + 1}]")
+    groups, in_h, in_w, _, width = cts.shape
+    (sh, sw), (ph, pw) = _pair(stride, "stride", 1), _pair(padding, "padding", 0)
+    out_h, out_w = conv2d_out_shape(in_h, in_w, k_h, k_w, (sh, sw), (ph, pw))
+    padded = np.zeros((groups, in_h + 2 * ph, in_w + 2 * pw, in_c, width), np.uint32)
+    padded[:, ph:ph + in_h, pw:pw + in_w] = cts
+    ix = (np.arange(out_w) * sw)[:, None] + np.arange(k_w)[None, :]  # [out_w][k_w]
+    w2 = w.reshape(out_c, k_h * k_w * in_c)
+    out = np.empty((groups, out_h, out_w, out_c, width), np.uint32)
+    for oy in range(out_h):
+        rows = padded[:, oy * sh:oy * sh + k_h]                      # [groups][k_h][padded w][in_c][width]
+        cols = rows[:, :, ix].transpose(0, 2, 1, 3, 4, 5)            # [groups][out_w][k_h][k_w][in_c][width]
+        out[:, oy] = _product(w2, cols.reshape(groups, out_w, k_h * k_w * in_c, width), bias)
+    return out
+
+
 def _checked(w, bias, max_cols: int):
     """(w as int8, bias as u32 or None): what the user-level calls check before they touch the library."""
     w, bias = _weights(w, bias, max_cols)
@@ -115,3 +172,19 @@ def matmul_packed(w, packed, cloud_key, bias=None, keyswitch: bool = True, devic
         raise ValueError(f"packed must be [groups][2][{N}]")
     with keyed_engine(cloud_key, device) as view:
         return view.batch_trlwe_matmul(w8, packed, bias, keyswitch)
+
+
+def conv2d(w, cts, cloud_key, bias=None, stride=1, padding=0, device: int = 0) -> np.ndarray:
+    """The server side of a convolutional layer: [groups][in_h][in_w][in_c][n+1] ciphertexts (or one group without the
+    leading axis) -> [groups][out_h][out_w][out_c][n+1] on the GPU (Engine.batch_tlwe_conv2d on the shared context of
+    `cloud_key`'s parameter set; the convolution itself uses no key)."""
+    from .bootstrap import keyed_engine
+
+    p = cloud_key.params
+    w, bias = _filters(w, bias)
+    cts = np.ascontiguousarray(cts, dtype=np.uint32)
+    if cts.ndim not in (4, 5) or cts.shape[-2:] != (w.shape[3], p.n + 1):
+        raise ValueError(f"cts must be [groups][in_h][in_w][{w.shape[3]}][{p.n + 1}]")
+    conv2d_out_shape(cts.shape[-4], cts.shape[-3], w.shape[1], w.shape[2], stride, padding)
+    with keyed_engine(cloud_key, device) as view:
+        return view.batch_tlwe_conv2d(w.astype(np.int8), cts, bias, stride, padding)

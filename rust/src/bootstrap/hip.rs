@@ -138,6 +138,38 @@ extern "C" {   // encrypted linear layers (include/tfhe_hip.h): a plaintext int8
     fn tfhe_hip_batch_trlwe_matmul_dev(ctx: *mut TfheHipCtx, w: *const int8_t, bias: *const u32, rows: usize, cols: usize,
                                        trlwe: *const u32, groups: usize, keyswitch: c_int, out: *mut u32,
                                        stream: *mut c_void) -> c_int;
+    // encrypted 2-D convolution (include/tfhe_hip.h): int8 filters over a channels-last map of LWE ciphertexts
+    fn tfhe_hip_batch_tlwe_conv2d(ctx: *mut TfheHipCtx, shape: *const TfheHipConv2dShape, w: *const int8_t, bias: *const u32,
+                                  input: *const u32, groups: usize, out: *mut u32) -> c_int;
+    fn tfhe_hip_batch_tlwe_conv2d_dev(ctx: *mut TfheHipCtx, shape: *const TfheHipConv2dShape, w: *const int8_t,
+                                      bias: *const u32, input: *const u32, groups: usize, out: *mut u32,
+                                      stream: *mut c_void) -> c_int;
+}
+
+/// `tfhe_hip_conv2d_shape`: the geometry of a 2-D convolution (include/tfhe_hip.h).  Strides are at least 1; the padding
+/// is zeros on both sides of each axis.
+#[derive(Clone, Copy, Debug)]
+#[repr(C)]
+pub struct TfheHipConv2dShape {
+    pub in_h: u32,
+    pub in_w: u32,
+    pub in_c: u32,
+    pub out_c: u32,
+    pub k_h: u32,
+    pub k_w: u32,
+    pub stride_h: u32,
+    pub stride_w: u32,
+    pub pad_h: u32,
+    pub pad_w: u32,
+}
+impl TfheHipConv2dShape {
+    /// (out_h, out_w) = ((in_h + 2 pad_h - k_h) / stride_h + 1, likewise); the filter must fit the padded map.
+    pub fn out_hw(&self) -> (usize, usize) {
+        let (ph, pw) = (self.in_h as usize + 2 * self.pad_h as usize, self.in_w as usize + 2 * self.pad_w as usize);
+        assert!(self.stride_h > 0 && self.stride_w > 0, "stride is at least 1");
+        assert!(self.k_h > 0 && self.k_w > 0 && self.k_h as usize <= ph && self.k_w as usize <= pw, "the filter fits the padded map");
+        ((ph - self.k_h as usize) / self.stride_h as usize + 1, (pw - self.k_w as usize) / self.stride_w as usize + 1)
+    }
 }
 
 /// A member context of a pool (tfhe_hip_pool_ctx): opaque, owned by the pool.
@@ -727,6 +759,41 @@ impl HipEngine {
             (0, ())
         });
         out
+    }
+    /// Encrypted 2-D convolution (`tfhe_hip_batch_tlwe_conv2d`): `w` is [out_c][k_h][k_w][in_c] int8, `input`
+    /// [groups][in_h][in_w][in_c][n+1] flat (channels-last), `bias` [out_c] torus words; returns
+    /// [groups][out_h][out_w][out_c][n+1] flat, every output the exact sum of its taps mod 2^32 with zeros outside the
+    /// map.  Runs on the first member of `ck`'s key view (no pool form; the convolution itself uses no key).
+    pub fn tlwe_conv2d(&self, shape: &TfheHipConv2dShape, w: &[i8], bias: Option<&[u32]>, input: &[u32], ck: &CloudKey) -> Vec<u32> {
+        let (out_h, out_w) = shape.out_hw();
+        let (in_c, out_c) = (shape.in_c as usize, shape.out_c as usize);
+        let per_group = shape.in_h as usize * shape.in_w as usize * in_c * W;
+        assert!(in_c > 0 && out_c > 0 && w.len() == out_c * shape.k_h as usize * shape.k_w as usize * in_c, "w is [out_c][k_h][k_w][in_c]");
+        assert!(input.len() % per_group == 0, "input is [groups][in_h][in_w][in_c][n+1]");
+        assert!(bias.map_or(true, |b| b.len() == out_c), "bias is [out_c]");
+        let groups = input.len() / per_group;
+        let bp = bias.map_or(std::ptr::null(), |b| b.as_ptr());
+        let mut out = vec![0u32; groups * out_h * out_w * out_c * W];
+        self.with_key(ck, |v| {
+            let ctx = unsafe { tfhe_hip_pool_ctx(v, 0) };
+            assert!(!ctx.is_null(), "tfhe_hip_pool_ctx failed");
+            Self::check_ctx(ctx, unsafe {
+                tfhe_hip_batch_tlwe_conv2d(ctx, shape, w.as_ptr(), bp, input.as_ptr(), groups, out.as_mut_ptr())
+            });
+            (0, ())
+        });
+        out
+    }
+    /// The same on device pointers of the first member's GPU (`w` and `bias` too; `bias` may be null), queued on
+    /// `stream`.  Safety: the pointers must stay valid until the work has run.
+    pub unsafe fn tlwe_conv2d_dev(&self, shape: &TfheHipConv2dShape, w: *const i8, bias: *const u32, input: *const u32,
+                                  groups: usize, out: *mut u32, stream: *mut c_void, ck: &CloudKey) {
+        self.with_key(ck, |v| {
+            let ctx = tfhe_hip_pool_ctx(v, 0);
+            assert!(!ctx.is_null(), "tfhe_hip_pool_ctx failed");
+            Self::check_ctx(ctx, tfhe_hip_batch_tlwe_conv2d_dev(ctx, shape, w, bias, input, groups, out, stream));
+            (0, ())
+        });
     }
     /// Both forms on device pointers of the first member's GPU (`w` and `bias` too; `bias` may be null), queued on
     /// `stream`; `trlwe_input` selects the packed form.  Safety: the pointers must stay valid until the work has run.
