@@ -588,6 +588,38 @@ struct SecretKey {
     for (size_t m = 0; m < res.size(); ++m) std::memcpy(res[m].p.data(), &out[m * w], w * sizeof(Torus));
     return res;
   }
+  // Decryption of a batch on the GPU (include/tfhe_hip.h, "decryption"; tfhe_hip_batch_decrypt): [count] words in every
+  // mode -- TFHE_HIP_DECRYPT_PHASE: b - <a, s>; _BOOL: 1 / 0, tlwe::decrypt_bool; _MESSAGE: tlwe::decrypt_lwe_message
+  // mod `modulus`.  Every word equals what the tlwe:: functions below give one ciphertext at a time.
+  std::vector<Torus> decrypt_batch(Engine &e, const std::vector<Ciphertext> &cts, int mode, uint32_t modulus = 0) const {
+    if (e.params().n != params.n) throw std::runtime_error("secret key has another dimension than the engine's parameter set");
+    const size_t w = (size_t)params.n + 1;
+    std::vector<Torus> in(cts.size() * w), out(cts.size());
+    for (size_t m = 0; m < cts.size(); ++m) {
+      if (cts[m].p.size() != w) throw std::runtime_error("ciphertext has another dimension than the secret key");
+      std::memcpy(&in[m * w], cts[m].p.data(), w * sizeof(Torus));
+    }
+    if (!cts.empty())
+      e.check(tfhe_hip_batch_decrypt(e.ctx(), key_lv0.data(), key_lv0.size(), in.data(), cts.size(), mode, modulus, out.data()));
+    return out;
+  }
+  std::vector<Torus> phase_batch(Engine &e, const std::vector<Ciphertext> &cts) const {
+    return decrypt_batch(e, cts, TFHE_HIP_DECRYPT_PHASE);
+  }
+  // ... of the first `count` slots of packed [groups][2][N] TRLWE lv1 ciphertexts (flat) under key_lv1: slot i % N of
+  // group i / N (tfhe_hip_batch_decrypt_trlwe)
+  std::vector<Torus> decrypt_packed_batch(Engine &e, const std::vector<Torus> &packed, size_t count, int mode,
+                                          uint32_t modulus = 0) const {
+    if (packed.size() % (2 * (size_t)N)) throw std::runtime_error("packed ciphertexts are [groups][2][N] words");
+    std::vector<Torus> out(count);
+    if (count)
+      e.check(tfhe_hip_batch_decrypt_trlwe(e.ctx(), key_lv1.data(), packed.data(), packed.size() / (2 * (size_t)N), count, mode,
+                                           modulus, out.data()));
+    return out;
+  }
+  std::vector<Torus> packed_phase_batch(Engine &e, const std::vector<Torus> &packed, size_t count) const {
+    return decrypt_packed_batch(e, packed, count, TFHE_HIP_DECRYPT_PHASE);
+  }
 };
 
 inline PackingKey PackingKey::generate(const SecretKey &sk, int device, const uint8_t *rng_key, double alpha) {

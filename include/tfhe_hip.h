@@ -769,6 +769,40 @@ int tfhe_hip_gen_public_key(tfhe_hip_ctx *ctx_or_view, const uint32_t *key_lv0, 
 int tfhe_hip_gen_reenc_key_symmetric(tfhe_hip_ctx *ctx_or_view, const uint32_t *key_from, const uint32_t *key_to,
                                      double alpha, const uint8_t rng_key[32], uint32_t *key_out);
 
+/* ---- decryption: phases, booleans and messages of LWE rows and of packed TRLWE slots --------------------------------
+ *
+ * The last step a client takes with the SECRET key (TLWELv0::decrypt_bool, src/tlwe.rs:60-68; decrypt_lwe_message,
+ * :111-126), on results that already sit in device memory (csrc/decrypt.hpp).  rs-tfhe_amd/client.py (SecretKey.phase,
+ * decrypt_bool, decrypt_lwe_message, packed_phase) is the definition: every word of every mode equals it.
+ *
+ * Format (normative).
+ *   LWE form     in [count][key_len+1], key [key_len] binary; key_len is the context's n (lv0 ciphertexts under key_lv0)
+ *                or N = 1024 (lv1 rows under key_lv1: what tfhe_hip_batch_sample_extract and the keyswitch == 0 form of
+ *                tfhe_hip_batch_trlwe_matmul return).  out [count] u32 in every mode.
+ *   packed form  trlwe [groups][2][N] under key_lv1; out[i], i < count <= groups * N, is slot i % N of group i / N.
+ *                Groups past the one that holds result count - 1 are not read.
+ *   PHASE        b - <a, s>, wrapping u32; packed: coefficient j of B - A (*) s1 mod X^N + 1.  Exact integers, no FFT.
+ *   BOOL         1 where the phase read as i32 is >= 0, else 0.
+ *   MESSAGE      (f64(phase) / 2^32 / (1 / (2 m)) + 0.5) truncated to an integer, then % m, in f64, in those operations
+ *                and that order; m = modulus, 2 <= m <= 65,536.  In the other modes modulus is ignored.
+ * TFHE_HIP_EINVAL for a key_len other than n or N, a NULL pointer, a key word other than 0 or 1, a mode other than the
+ * three, a modulus outside [2, 65,536] in MESSAGE mode, count > 0x7FFFFFFF, count > groups * N.  count == 0 returns
+ * TFHE_HIP_OK and touches nothing.  Needs no key on the handle; every parameter set.
+ * Security.  The key is host memory in both forms.  What the device holds of it is zeroed behind the kernel on the
+ * call's stream, and the library's host copy is wiped; a host-form call also zeroes the staging buffers that held the
+ * phases or messages (the device buffer and, on pool members, its pinned host arena) before it returns.  _dev: in / trlwe / out are device pointers, queued on `stream` (NULL: the
+ * context's stream); the decrypted words are then the caller's to guard.
+ * Out of scope: pool forms, slot lists for the packed form. */
+enum { TFHE_HIP_DECRYPT_PHASE = 0, TFHE_HIP_DECRYPT_BOOL = 1, TFHE_HIP_DECRYPT_MESSAGE = 2 };
+int tfhe_hip_batch_decrypt(tfhe_hip_ctx *ctx, const uint32_t *key, size_t key_len, const uint32_t *in, size_t count,
+                           int mode, uint32_t modulus, uint32_t *out);
+int tfhe_hip_batch_decrypt_dev(tfhe_hip_ctx *ctx, const uint32_t *key, size_t key_len, const uint32_t *in, size_t count,
+                               int mode, uint32_t modulus, uint32_t *out, void *stream);
+int tfhe_hip_batch_decrypt_trlwe(tfhe_hip_ctx *ctx, const uint32_t *key_lv1, const uint32_t *trlwe, size_t groups,
+                                 size_t count, int mode, uint32_t modulus, uint32_t *out);
+int tfhe_hip_batch_decrypt_trlwe_dev(tfhe_hip_ctx *ctx, const uint32_t *key_lv1, const uint32_t *trlwe, size_t groups,
+                                     size_t count, int mode, uint32_t modulus, uint32_t *out, void *stream);
+
 /* Replaces: FFTProcessor::{ifft, fft, poly_mul, batch_ifft, batch_fft}
  * (src/fft/mod.rs:80-107; KlemsaProcessor src/fft/klemsa.rs:88-174) and the
  * SPQLIOS C ABI Spqlios_ifft_lv1 / _fft_lv1 / _poly_mul_1024

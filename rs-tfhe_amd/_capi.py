@@ -164,6 +164,10 @@ SIGNATURES = {
     "tfhe_hip_batch_encrypt_dev": (C.c_int, [_CTX, _P, _P, _SZ, C.c_double, _P, _P, C.c_uint64, _P, _P, _P]),
     "tfhe_hip_gen_public_key": (C.c_int, [_CTX, _P, _SZ, C.c_double, _P, _P]),
     "tfhe_hip_gen_reenc_key_symmetric": (C.c_int, [_CTX, _P, _P, C.c_double, _P, _P]),
+    "tfhe_hip_batch_decrypt": (C.c_int, [_CTX, _P, _SZ, _P, _SZ, C.c_int, C.c_uint32, _P]),
+    "tfhe_hip_batch_decrypt_dev": (C.c_int, [_CTX, _P, _SZ, _P, _SZ, C.c_int, C.c_uint32, _P, _P]),
+    "tfhe_hip_batch_decrypt_trlwe": (C.c_int, [_CTX, _P, _P, _SZ, _SZ, C.c_int, C.c_uint32, _P]),
+    "tfhe_hip_batch_decrypt_trlwe_dev": (C.c_int, [_CTX, _P, _P, _SZ, _SZ, C.c_int, C.c_uint32, _P, _P]),
     "tfhe_hip_batch_ifft": (C.c_int, [_CTX, _P, _P, _SZ]),
     "tfhe_hip_batch_fft": (C.c_int, [_CTX, _P, _P, _SZ]),
     "tfhe_hip_batch_poly_mul": (C.c_int, [_CTX, _P, _P, _P, _SZ]),
@@ -248,6 +252,7 @@ SIGNATURES = {
     "tfhe_hip_circuit_gather_pool_dev": (C.c_int, [_CTX, C.c_int, _CTX, _P, _SZ, _P, _SZ, _P, _P]),
 }
 
+DECRYPT_MODES = {"phase": 0, "bool": 1, "message": 2}  # TFHE_HIP_DECRYPT_*
 CIRCUIT_LEVEL_WORDS = 10  # TFHE_HIP_CIRCUIT_LEVEL_WORDS
 NO_SLOT = 0xFFFFFFFF
 

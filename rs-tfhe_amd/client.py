@@ -1,7 +1,7 @@
 """Client side of the path: secret keys, TLWE encryption and decryption.
 
 Host-side integer work (numpy, batched over ciphertexts); nothing here touches
-the GPU except `cloud_key()`, which runs the key generation kernels.  Mirrors
+the GPU except `cloud_key()`, which runs the key generation kernels, and the calls given `device=`.  Mirrors
 
   key::SecretKey::new                      src/key.rs:21-48
   TLWELv0::encrypt_f64 / encrypt_bool      src/tlwe.rs:37-58
@@ -24,6 +24,9 @@ cryptographic: tests and benchmarks only.  A guessable generator behind `SecretK
 `rng_key=` (a secret 32-byte generator key) alone is its CPU form, `device=` runs it on the GPU
 (`tfhe_hip_batch_encrypt`; rng_key=None there draws the key from getrandom(2)), `first_index=` places the batch in the
 streams.  A (rng_key, row) pair must never encrypt twice.
+
+`phase`, `decrypt_*` and their packed forms take `device=` too (include/tfhe_hip.h, "decryption"): the numpy expressions
+here stay the definition, the GPU returns the same words, and a torch CUDA tensor is decrypted where it lies.
 """
 from __future__ import annotations
 
@@ -158,13 +161,67 @@ class SecretKey:
         bits = np.atleast_1d(np.asarray(bits)).astype(bool)
         return self.encrypt_f64(np.where(bits, 0.125, -0.125), seed, alpha, rng_key, first_index, device, mask_seed)
 
-    def phase(self, cts) -> np.ndarray:
-        """b - <a, s> (u32)."""
+    def _on_device(self, device, cts, mode, modulus=None, *, lv1=False, packed_count=None):
+        """The decode `mode` of cts on GPU `device` (include/tfhe_hip.h, "decryption"): a numpy argument goes through the
+        host form and comes back as a numpy array, a torch CUDA tensor through the _dev form on its current stream and
+        comes back as a tensor on that device.  [count] 32-bit words."""
+        from .bootstrap import engine_for
+
+        e = engine_for(self.params, device)
+        key = self.key_lv1 if lv1 or packed_count is not None else self.key_lv0
+        if type(cts).__module__.startswith("torch"):
+            import torch
+
+            if packed_count is not None:
+                cts = cts.reshape(-1, 2, N)
+                if cts.shape[0] * N < packed_count:
+                    raise ValueError(f"{cts.shape[0]} packed TRLWEs hold fewer than {packed_count} results")
+                out = torch.empty(int(packed_count), dtype=torch.int32, device=cts.device)
+                if packed_count:
+                    e.batch_decrypt_trlwe_dev(key, cts, packed_count, out, mode, modulus)
+                return out
+            cts = cts.reshape(-1, len(key) + 1)
+            out = torch.empty(cts.shape[0], dtype=torch.int32, device=cts.device)
+            if cts.shape[0]:
+                e.batch_decrypt_dev(key, cts, out, mode, modulus)
+            return out
+        if packed_count is not None:
+            packed = np.ascontiguousarray(cts, dtype=np.uint32).reshape(-1, 2, N)
+            if len(packed) * N < packed_count:
+                raise ValueError(f"{len(packed)} packed TRLWEs hold fewer than {packed_count} results")
+            return e.batch_decrypt_trlwe(key, packed, packed_count, mode, modulus) if packed_count else np.empty(0, np.uint32)
+        cts = np.ascontiguousarray(cts, dtype=np.uint32).reshape(-1, len(key) + 1)
+        return e.batch_decrypt(key, cts, mode, modulus) if len(cts) else np.empty(0, np.uint32)
+
+    @staticmethod
+    def _as(words, dtype):
+        """The [count] words of a device decode in the dtype the numpy path returns (bool / int64)"""
+        if isinstance(words, np.ndarray):
+            return words.astype(dtype)
+        import torch
+
+        return words.to(torch.bool if dtype is bool else torch.int64)
+
+    def phase(self, cts, device=None):
+        """b - <a, s> (u32).  device: computed on that GPU (numpy in, numpy out through the host form; a torch CUDA
+        tensor in, a tensor of the same 32-bit words out through the _dev form); None: numpy on the host."""
+        if device is not None:
+            return self._on_device(device, cts, "phase")
         cts = self._cts(cts)
         return cts[:, -1] - self._inner(cts)
 
-    def decrypt_bool(self, cts) -> np.ndarray:
-        """tlwe.rs:60-68: the phase read as i32 is non-negative."""
+    def phase_lv1(self, rows, device=None):
+        """b - <a, s1> (u32) of lv1 rows [count][N+1] under key_lv1: what batch_sample_extract and
+        batch_trlwe_matmul(keyswitch=False) return.  device as in phase."""
+        if device is not None:
+            return self._on_device(device, rows, "phase", lv1=True)
+        rows = np.ascontiguousarray(rows, dtype=np.uint32).reshape(-1, N + 1)
+        return rows[:, -1] - (rows[:, :-1] * self.key_lv1[None, :]).sum(axis=1, dtype=np.uint32)
+
+    def decrypt_bool(self, cts, device=None):
+        """tlwe.rs:60-68: the phase read as i32 is non-negative.  device as in phase."""
+        if device is not None:
+            return self._as(self._on_device(device, cts, "bool"), bool)
         return self.phase(cts).view(np.int32) >= 0
 
     def encrypt_lwe_message(self, msgs, message_modulus: int, seed=None, alpha: float | None = None, rng_key=None,
@@ -175,9 +232,11 @@ class SecretKey:
         return self.encrypt_f64(msgs.astype(np.float64) * (1.0 / (2.0 * m)), seed, alpha, rng_key, first_index, device,
                                 mask_seed)
 
-    def decrypt_lwe_message(self, cts, message_modulus: int) -> np.ndarray:
-        """tlwe.rs:111-126: ((phase / 2^32) / scale + 0.5) as usize % m, scale = 1/(2m)."""
+    def decrypt_lwe_message(self, cts, message_modulus: int, device=None):
+        """tlwe.rs:111-126: ((phase / 2^32) / scale + 0.5) as usize % m, scale = 1/(2m).  device as in phase."""
         m = int(message_modulus)
+        if device is not None:
+            return self._as(self._on_device(device, cts, "message", m), np.int64)
         scale = 1.0 / (2.0 * m)
         return (torus_to_f64(self.phase(cts)) / scale + 0.5).astype(np.int64) % m
 
@@ -202,22 +261,29 @@ class SecretKey:
         finally:
             view.close()
 
-    def packed_phase(self, packed, count: int) -> np.ndarray:
-        """Phases of the first `count` results of [G][2][N] packed TRLWEs: coefficient j of B - A (*) s1 per group."""
+    def packed_phase(self, packed, count: int, device=None):
+        """Phases of the first `count` results of [G][2][N] packed TRLWEs: coefficient j of B - A (*) s1 per group.
+        device as in phase."""
         from .seeded import negacyclic_binary
 
+        if device is not None:
+            return self._on_device(device, packed, "phase", packed_count=int(count))
         packed = np.ascontiguousarray(packed, dtype=np.uint32).reshape(-1, 2, N)
         if len(packed) * N < count:
             raise ValueError(f"{len(packed)} packed TRLWEs hold fewer than {count} results")
         return (packed[:, 1] - negacyclic_binary(packed[:, 0], self.key_lv1)).reshape(-1)[:count]
 
-    def decrypt_packed_bool(self, packed, count: int) -> np.ndarray:
-        """decrypt_bool of packed results."""
+    def decrypt_packed_bool(self, packed, count: int, device=None):
+        """decrypt_bool of packed results.  device as in phase."""
+        if device is not None:
+            return self._as(self._on_device(device, packed, "bool", packed_count=int(count)), bool)
         return self.packed_phase(packed, count).view(np.int32) >= 0
 
-    def decrypt_packed_lwe_message(self, packed, count: int, message_modulus: int) -> np.ndarray:
-        """decrypt_lwe_message of packed results."""
+    def decrypt_packed_lwe_message(self, packed, count: int, message_modulus: int, device=None):
+        """decrypt_lwe_message of packed results.  device as in phase."""
         m = int(message_modulus)
+        if device is not None:
+            return self._as(self._on_device(device, packed, "message", m, packed_count=int(count)), np.int64)
         return (torus_to_f64(self.packed_phase(packed, count)) / (1.0 / (2.0 * m)) + 0.5).astype(np.int64) % m
 
     # ---- packed inputs (unpacking key switch, include/tfhe_hip.h) ------------------------------------

@@ -2109,3 +2109,4 @@ int tfhe_hip_synchronize(tfhe_hip_ctx *ctx) {
 #include "packing_keygen.hpp"
 #include "pk_encrypt.hpp"
 #include "sym_encrypt.hpp"
+#include "decrypt.hpp"

@@ -1029,6 +1029,73 @@ class Engine(_Handle):
                                                              C.c_double(p.alpha_lv0 if alpha is None else alpha), rkp, _ptr(key)))
         return key
 
+    # -- decryption: phases, booleans and messages of LWE rows and packed TRLWE slots (include/tfhe_hip.h) --------
+    @staticmethod
+    def _decrypt_mode(mode, modulus):
+        """(TFHE_HIP_DECRYPT_* code, modulus word) of mode "phase" | "bool" | "message" (or the code itself)"""
+        code = _capi.DECRYPT_MODES.get(mode, mode) if isinstance(mode, str) else int(mode)
+        if isinstance(code, str):
+            raise ValueError('mode is "phase", "bool" or "message"')
+        if code == _capi.DECRYPT_MODES["message"] and modulus is None:
+            raise ValueError("message mode needs the message modulus")
+        return code, C.c_uint32(0 if modulus is None else int(modulus) & 0xFFFFFFFF)
+
+    def _decrypt_key(self, key, width: int = None) -> np.ndarray:
+        """The key of an LWE-form call: a SecretKey gives key_lv0, or key_lv1 for rows of N + 1 words"""
+        if hasattr(key, "key_lv0"):
+            key = key.key_lv1 if width == N + 1 and self.params.n != N else key.key_lv0
+        return _u32(key).reshape(-1)
+
+    def batch_decrypt(self, key, cts, mode="phase", modulus: int = None) -> np.ndarray:
+        """cts [count][len(key)+1] -> [count] u32 (`tfhe_hip_batch_decrypt`): the phases b - <a, key>, or their decodes
+        as booleans (1 / 0) or messages mod `modulus`.  key: key_lv0 [n] for lv0 ciphertexts, key_lv1 [N] for lv1 rows
+        (or a SecretKey: picked by the row width)."""
+        cts = _u32(cts)
+        k = self._decrypt_key(key, cts.shape[-1] if cts.ndim else None)
+        cts = cts.reshape(-1, len(k) + 1)
+        code, m = self._decrypt_mode(mode, modulus)
+        out = np.empty(len(cts), np.uint32)
+        self._chk(self._lib.tfhe_hip_batch_decrypt(self._ctx, _ptr(k), len(k), _ptr(cts), len(cts), code, m, _ptr(out)))
+        return out
+
+    def batch_decrypt_dev(self, key, cts, out, mode="phase", modulus: int = None, stream=None) -> None:
+        """Device form: cts [count][len(key)+1] and out [count] torch tensors (32-bit words) on this engine's GPU; the
+        key stays a host array.  Enqueues on `stream`."""
+        k = self._decrypt_key(key, cts.shape[-1] if cts.dim() else None)
+        if cts.dim() != 2 or cts.shape[1] != len(k) + 1:
+            raise ValueError(f"cts must be [count][{len(k) + 1}]")
+        if out.dim() != 1 or out.shape[0] != cts.shape[0]:
+            raise ValueError(f"out must be [{cts.shape[0]}]")
+        code, m = self._decrypt_mode(mode, modulus)
+        self._chk(self._lib.tfhe_hip_batch_decrypt_dev(self._ctx, _ptr(k), len(k), self._tp(None, cts), cts.shape[0], code, m,
+                                                       self._tp(None, out), self._stream_ptr(None, stream)))
+
+    def batch_decrypt_trlwe(self, key_lv1, packed, count: int, mode="phase", modulus: int = None) -> np.ndarray:
+        """The first `count` slots of packed [groups][2][N] under key_lv1 -> [count] u32 (`tfhe_hip_batch_decrypt_trlwe`):
+        slot i % N of group i / N, as SecretKey.packed_phase orders them."""
+        k = _u32(getattr(key_lv1, "key_lv1", key_lv1)).reshape(-1)
+        if len(k) != N:
+            raise ValueError("key_lv1 has N = 1024 words")
+        packed = _u32(packed).reshape(-1, 2, N)
+        code, m = self._decrypt_mode(mode, modulus)
+        out = np.empty(max(int(count), 0), np.uint32)
+        self._chk(self._lib.tfhe_hip_batch_decrypt_trlwe(self._ctx, _ptr(k), _ptr(packed), len(packed), int(count), code, m,
+                                                         _ptr(out)))
+        return out
+
+    def batch_decrypt_trlwe_dev(self, key_lv1, packed, count: int, out, mode="phase", modulus: int = None, stream=None) -> None:
+        """Device form: packed [groups][2][N] and out [count] torch tensors on this engine's GPU.  Enqueues on `stream`."""
+        k = _u32(getattr(key_lv1, "key_lv1", key_lv1)).reshape(-1)
+        if len(k) != N:
+            raise ValueError("key_lv1 has N = 1024 words")
+        if packed.dim() != 3 or packed.shape[1] != 2 or packed.shape[2] != N:
+            raise ValueError("packed must be [groups][2][1024]")
+        if out.dim() != 1 or out.shape[0] != int(count):
+            raise ValueError(f"out must be [{int(count)}]")
+        code, m = self._decrypt_mode(mode, modulus)
+        self._chk(self._lib.tfhe_hip_batch_decrypt_trlwe_dev(self._ctx, _ptr(k), self._tp(None, packed), packed.shape[0], int(count),
+                                                             code, m, self._tp(None, out), self._stream_ptr(None, stream)))
+
     def pk_encrypt_times(self) -> dict:
         """Kernel times of the public-key encryption / asymmetric key passes since the last call (profiling on)."""
         t = _capi.PkEncryptTimes()

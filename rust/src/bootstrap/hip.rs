@@ -122,7 +122,22 @@ extern "C" {   // packing key switch (include/tfhe_hip.h): up to N lv0 results i
                                rng_key: *const u8, encryptions_out: *mut u32) -> c_int;
     fn tfhe_hip_gen_reenc_key_symmetric(ctx_or_view: *mut TfheHipCtx, key_from: *const u32, key_to: *const u32,
                                         alpha: f64, rng_key: *const u8, key_out: *mut u32) -> c_int;
+    // decryption (include/tfhe_hip.h): phases, booleans and messages of LWE rows and of packed TRLWE slots; no pool forms
+    fn tfhe_hip_batch_decrypt(ctx: *mut TfheHipCtx, key: *const u32, key_len: usize, input: *const u32, count: usize,
+                              mode: c_int, modulus: u32, out: *mut u32) -> c_int;
+    fn tfhe_hip_batch_decrypt_dev(ctx: *mut TfheHipCtx, key: *const u32, key_len: usize, input: *const u32, count: usize,
+                                  mode: c_int, modulus: u32, out: *mut u32, stream: *mut c_void) -> c_int;
+    fn tfhe_hip_batch_decrypt_trlwe(ctx: *mut TfheHipCtx, key_lv1: *const u32, trlwe: *const u32, groups: usize,
+                                    count: usize, mode: c_int, modulus: u32, out: *mut u32) -> c_int;
+    fn tfhe_hip_batch_decrypt_trlwe_dev(ctx: *mut TfheHipCtx, key_lv1: *const u32, trlwe: *const u32, groups: usize,
+                                        count: usize, mode: c_int, modulus: u32, out: *mut u32,
+                                        stream: *mut c_void) -> c_int;
 }
+
+/// TFHE_HIP_DECRYPT_*: what `HipEngine::decrypt_batch` and `decrypt_trlwe` return per ciphertext
+pub const DECRYPT_PHASE: c_int = 0;     // b - <a, s>, wrapping u32
+pub const DECRYPT_BOOL: c_int = 1;      // 1 where the phase read as i32 is >= 0 (TLWELv0::decrypt_bool), else 0
+pub const DECRYPT_MESSAGE: c_int = 2;   // TLWELv0::decrypt_lwe_message mod `modulus`, 2 <= modulus <= 65536
 
 #[allow(non_camel_case_types)]
 type int8_t = i8;   // the header's spelling of the weights' type
@@ -597,6 +612,61 @@ impl HipEngine {
                                    first_index, bp, out.as_mut_ptr())
         });
         out
+    }
+
+    /// Decryption of a batch on the GPU (include/tfhe_hip.h "decryption", `tfhe_hip_batch_decrypt`): `cts` is
+    /// [count][key.len()+1], flat, under `key` -- key_lv0 [n] for TLWELv0 ciphertexts, key_lv1 [N] for lv1 rows of N + 1
+    /// words.  Returns [count] words in every mode (DECRYPT_PHASE / DECRYPT_BOOL / DECRYPT_MESSAGE; `modulus` is read
+    /// in message mode only): what TLWELv0::decrypt_bool / decrypt_lwe_message give one ciphertext at a time.  A
+    /// client-side call: it takes a secret key.  Runs on the pool's first member.
+    pub fn decrypt_batch(&self, key: &[u32], cts: &[u32], mode: c_int, modulus: u32) -> Vec<u32> {
+        assert!(key.len() == params::tlwe_lv0::N || key.len() == N, "key is key_lv0 [n] or key_lv1 [N]");
+        assert_eq!(cts.len() % (key.len() + 1), 0, "cts is [count][key.len()+1]");
+        let count = cts.len() / (key.len() + 1);
+        let mut out = vec![0u32; count];
+        if count == 0 {
+            return out;
+        }
+        let ctx = unsafe { tfhe_hip_pool_ctx(self.pool, 0) };
+        assert!(!ctx.is_null(), "tfhe_hip_pool_ctx failed");
+        Self::check_ctx(ctx, unsafe {
+            tfhe_hip_batch_decrypt(ctx, key.as_ptr(), key.len(), cts.as_ptr(), count, mode, modulus, out.as_mut_ptr())
+        });
+        out
+    }
+    /// The same on device pointers of the first member's GPU (`key` stays host memory), queued on `stream`: `cts` is
+    /// [count][key.len()+1], `out` [count].  Safety: the pointers must stay valid until the work has run.
+    pub unsafe fn decrypt_batch_dev(&self, key: &[u32], cts: *const u32, count: usize, mode: c_int, modulus: u32,
+                                    out: *mut u32, stream: *mut c_void) {
+        let ctx = tfhe_hip_pool_ctx(self.pool, 0);
+        assert!(!ctx.is_null(), "tfhe_hip_pool_ctx failed");
+        Self::check_ctx(ctx, tfhe_hip_batch_decrypt_dev(ctx, key.as_ptr(), key.len(), cts, count, mode, modulus, out, stream));
+    }
+    /// The first `count` slots of packed TRLWE lv1 ciphertexts ([groups][2][N], flat) under `key_lv1`
+    /// (`tfhe_hip_batch_decrypt_trlwe`): result i is slot i % N of group i / N.  Returns [count] words as `decrypt_batch`.
+    pub fn decrypt_trlwe(&self, key_lv1: &[u32], trlwe: &[u32], count: usize, mode: c_int, modulus: u32) -> Vec<u32> {
+        assert_eq!(key_lv1.len(), N, "key_lv1 is [N]");
+        assert_eq!(trlwe.len() % (2 * N), 0, "trlwe is [groups][2][N]");
+        assert!(count <= trlwe.len() / 2, "count exceeds the slots of the packed ciphertexts");
+        let mut out = vec![0u32; count];
+        if count == 0 {
+            return out;
+        }
+        let ctx = unsafe { tfhe_hip_pool_ctx(self.pool, 0) };
+        assert!(!ctx.is_null(), "tfhe_hip_pool_ctx failed");
+        Self::check_ctx(ctx, unsafe {
+            tfhe_hip_batch_decrypt_trlwe(ctx, key_lv1.as_ptr(), trlwe.as_ptr(), trlwe.len() / (2 * N), count, mode, modulus,
+                                         out.as_mut_ptr())
+        });
+        out
+    }
+    /// The same on device pointers of the first member's GPU, queued on `stream`.  Safety: as `decrypt_batch_dev`.
+    pub unsafe fn decrypt_trlwe_dev(&self, key_lv1: &[u32], trlwe: *const u32, groups: usize, count: usize, mode: c_int,
+                                    modulus: u32, out: *mut u32, stream: *mut c_void) {
+        assert_eq!(key_lv1.len(), N, "key_lv1 is [N]");
+        let ctx = tfhe_hip_pool_ctx(self.pool, 0);
+        assert!(!ctx.is_null(), "tfhe_hip_pool_ctx failed");
+        Self::check_ctx(ctx, tfhe_hip_batch_decrypt_trlwe_dev(ctx, key_lv1.as_ptr(), trlwe, groups, count, mode, modulus, out, stream));
     }
 
     /// PublicKeyLv0::new_with_params (src/proxy_reenc.rs:144-153) on the GPU (`tfhe_hip_gen_public_key`): `size`
