@@ -620,6 +620,35 @@ struct SecretKey {
   std::vector<Torus> packed_phase_batch(Engine &e, const std::vector<Torus> &packed, size_t count) const {
     return decrypt_packed_batch(e, packed, count, TFHE_HIP_DECRYPT_PHASE);
   }
+  // trlwe::encrypt_f64 over a batch on the GPU, N values to a ciphertext, in the keyed format of include/tfhe_hip.h
+  // ("packed encryption", tfhe_hip_batch_encrypt_trlwe): returns [ceil(count / N)][2][N] words (flat); group m has index
+  // first_group + m, its mask under the PUBLIC 32-byte mask_seed, its noise under rng_key -- the secret 32-byte generator
+  // key, or nullptr to draw it from getrandom(2); the unused slots of the last group encrypt 0.  alpha < 0: the set's
+  // alpha_lv1.  Neither a (rng_key, group) nor a (mask_seed, group) pair may encrypt twice.  bodies != nullptr also
+  // receives the seeded form's bodies [groups][N].
+  std::vector<Torus> encrypt_packed_batch(Engine &e, const std::vector<double> &plaintexts, const uint8_t mask_seed[32],
+                                          const uint8_t *rng_key = nullptr, uint64_t first_group = 0, double alpha = -1,
+                                          std::vector<Torus> *bodies = nullptr) const {
+    std::vector<Torus> plain(plaintexts.size());
+    for (size_t m = 0; m < plain.size(); ++m) plain[m] = f64_to_torus(plaintexts[m]);
+    const size_t groups = (plain.size() + (size_t)N - 1) / (size_t)N;
+    std::vector<Torus> out(groups * 2 * (size_t)N);
+    if (bodies) bodies->resize(groups * (size_t)N);
+    if (!plain.empty())
+      e.check(tfhe_hip_batch_encrypt_trlwe(e.ctx(), key_lv1.data(), plain.data(), plain.size(), alpha < 0 ? params.alpha_lv1 : alpha,
+                                           rng_key, mask_seed, first_group, bodies ? bodies->data() : nullptr, out.data()));
+    return out;
+  }
+  // The seeded packed batch (mask_seed, first_group, bodies [groups][N]) expanded on the GPU to the words the full form
+  // writes (tfhe_hip_expand_seeded_trlwe); no secret is involved
+  static std::vector<Torus> expand_seeded_packed(Engine &e, const uint8_t mask_seed[32], uint64_t first_group,
+                                                 const std::vector<Torus> &bodies) {
+    if (bodies.size() % (size_t)N) throw std::runtime_error("seeded packed bodies are [groups][N] words");
+    std::vector<Torus> out(bodies.size() * 2);
+    if (!bodies.empty())
+      e.check(tfhe_hip_expand_seeded_trlwe(e.ctx(), mask_seed, first_group, bodies.data(), bodies.size() / (size_t)N, out.data()));
+    return out;
+  }
 };
 
 inline PackingKey PackingKey::generate(const SecretKey &sk, int device, const uint8_t *rng_key, double alpha) {

@@ -716,7 +716,8 @@ int tfhe_hip_get_pk_encrypt_times(tfhe_hip_ctx *ctx, tfhe_hip_pk_encrypt_times *
  * Everything made with the SECRET key: ordinary TLWE lv0 encryptions in bulk (TLWELv0::encrypt_f64, src/tlwe.rs:37-53),
  * the public key's encryptions of zero (PublicKeyLv0::new, src/proxy_reenc.rs:125-153) and the symmetric re-encryption
  * key (ProxyReencryptionKey::new_symmetric, :362-425).  All three are the same row, made by one wave of one kernel
- * (csrc/sym_encrypt.hpp); with these every key and ciphertext type of the reference has a device constructor.
+ * (csrc/sym_encrypt.hpp); with these and the packed TRLWE ciphertexts of the "packed encryption" section below every
+ * key and ciphertext type of the reference has a device constructor.
  *
  * Format (normative).  Keystream words, gauss2 and f64_to_torus are those of the seeded section.  A row index g is
  * 64 bits; its nonce is (g & 0xffffffff, g >> 32, domain).  Mask word x < n of row g is word x % 16 of the block with
@@ -802,6 +803,61 @@ int tfhe_hip_batch_decrypt_trlwe(tfhe_hip_ctx *ctx, const uint32_t *key_lv1, con
                                  size_t count, int mode, uint32_t modulus, uint32_t *out);
 int tfhe_hip_batch_decrypt_trlwe_dev(tfhe_hip_ctx *ctx, const uint32_t *key_lv1, const uint32_t *trlwe, size_t groups,
                                      size_t count, int mode, uint32_t modulus, uint32_t *out, void *stream);
+
+/* ---- packed encryption: TRLWE lv1 ciphertexts, N values to a ciphertext -- full, seeded and expansion -------------
+ *
+ * TRLWELv1::encrypt_f64 / encrypt_bool (src/trlwe.rs:30-66) made with the SECRET ring key on the device
+ * (csrc/trlwe_encrypt.hpp): the input form of tfhe_hip_batch_trlwe_matmul and tfhe_hip_batch_unpack_trlwe and what
+ * tfhe_hip_batch_decrypt_trlwe reads back.  With these and the symmetric section every key and ciphertext type of the
+ * reference has a device constructor.
+ *
+ * Format (normative).  Keystream words, gauss2, f64_to_torus and the nonce conventions are those of the seeded and
+ * symmetric sections.  A batch of `count` plaintext torus words fills groups = ceil(count / N) TRLWEs, N = 1024: slot j
+ * of group m holds plain[m N + j]; the slots at or past `count` of the last group encrypt 0 and plain is never read
+ * there.  Group m has the 64-bit index g = first_group + m and the nonce (g & 0xffffffff, g >> 32, domain), with no
+ * stream number.
+ *
+ *   what               key                domain           layout
+ *   mask polynomial a  public seed S      0x45524C "ERL"   natural order: coefficient c is word c % 16 of the block with
+ *                                                          counter c / 16 (64 blocks)
+ *   noise e            generator key K    0x45524E "ERN"   the order of the BSK generators: block counter 2 lane + h,
+ *                                                          lane < 64, h < 2; pair q < 4 is gauss2(w[4q..4q+3], alpha):
+ *                                                          g0 -> e[lane + 64 (4h + q)], g1 -> the same index + 512
+ *
+ *   body: b[c] = (a (*) s1)[c] + f64_to_torus(e[c]) + plain[c], wrapping u32, the product mod X^N + 1, exact.  With
+ *   alpha == 0 the noise is exactly zero.  The two domains differ from every other one of this header, so one K may
+ *   serve this generator and every other one.
+ *   A seeded packed batch is (S, first_group, bodies [groups][N], count): 4 KiB a ciphertext instead of 8, and by
+ *   construction what the bodies-only output of the encrypting call returns; tfhe_hip_expand_seeded_trlwe expands it
+ *   to the words the full form writes.
+ * Security: the rules of the symmetric section.  A (K, g) pair is used once, whatever S is; an (S, g) pair is used
+ * once; rng_key == NULL draws K from getrandom(2) per call; a caller-held K is as secret as the secret key.  K, s1,
+ * the spectrum of s1 (which is secret too) and, in the host form, the staged plaintexts are zeroed on the device before
+ * a host-form call returns; the _dev form queues the zeroing on `stream` behind its kernel.  The library's host copies
+ * are wiped.
+ * Away from noise samples that sit within rounding of a torus step every implementation of this section gives the same
+ * words.
+ * Out of scope: pool forms. */
+/* key_lv1 [N] (host memory in both forms), plain [count] torus words -> bodies [groups][N] and / or out [groups][2][N]
+ * (a half, b half); either may be NULL, and with out == NULL no mask is stored.  Needs no key on the handle; every
+ * parameter set.  TFHE_HIP_EINVAL for a NULL key_lv1, plain or mask_seed, for bodies and out both NULL with count > 0,
+ * alpha negative or NaN, a key word other than 0 or 1, count > 0x7FFFFFFF, first_group + groups - 1 past 2^64, and (_dev)
+ * a bodies or out pointer that is not 16-byte aligned.  count == 0 returns TFHE_HIP_OK and touches nothing.  _dev:
+ * plain / bodies / out are device pointers, queued on `stream` (NULL: the context's stream). */
+int tfhe_hip_batch_encrypt_trlwe(tfhe_hip_ctx *ctx, const uint32_t *key_lv1, const uint32_t *plain, size_t count,
+                                 double alpha, const uint8_t rng_key[32], const uint8_t mask_seed[32], uint64_t first_group,
+                                 uint32_t *bodies, uint32_t *out);
+int tfhe_hip_batch_encrypt_trlwe_dev(tfhe_hip_ctx *ctx, const uint32_t *key_lv1, const uint32_t *plain, size_t count,
+                                     double alpha, const uint8_t rng_key[32], const uint8_t mask_seed[32],
+                                     uint64_t first_group, uint32_t *bodies, uint32_t *out, void *stream);
+/* bodies [groups][N] -> out [groups][2][N]: out[m][0] the mask of group first_group + m under mask_seed, out[m][1] the
+ * bodies.  No secret.  TFHE_HIP_EINVAL for a NULL mask_seed, bodies or out, first_group + groups - 1 past 2^64, groups
+ * > 0x7FFFFFFF and (_dev) a pointer that is not 16-byte aligned.  groups == 0 returns TFHE_HIP_OK and touches
+ * nothing. */
+int tfhe_hip_expand_seeded_trlwe(tfhe_hip_ctx *ctx, const uint8_t mask_seed[32], uint64_t first_group,
+                                 const uint32_t *bodies, size_t groups, uint32_t *out);
+int tfhe_hip_expand_seeded_trlwe_dev(tfhe_hip_ctx *ctx, const uint8_t mask_seed[32], uint64_t first_group,
+                                     const uint32_t *bodies, size_t groups, uint32_t *out, void *stream);
 
 /* Replaces: FFTProcessor::{ifft, fft, poly_mul, batch_ifft, batch_fft}
  * (src/fft/mod.rs:80-107; KlemsaProcessor src/fft/klemsa.rs:88-174) and the

@@ -168,6 +168,10 @@ SIGNATURES = {
     "tfhe_hip_batch_decrypt_dev": (C.c_int, [_CTX, _P, _SZ, _P, _SZ, C.c_int, C.c_uint32, _P, _P]),
     "tfhe_hip_batch_decrypt_trlwe": (C.c_int, [_CTX, _P, _P, _SZ, _SZ, C.c_int, C.c_uint32, _P]),
     "tfhe_hip_batch_decrypt_trlwe_dev": (C.c_int, [_CTX, _P, _P, _SZ, _SZ, C.c_int, C.c_uint32, _P, _P]),
+    "tfhe_hip_batch_encrypt_trlwe": (C.c_int, [_CTX, _P, _P, _SZ, C.c_double, _P, _P, C.c_uint64, _P, _P]),
+    "tfhe_hip_batch_encrypt_trlwe_dev": (C.c_int, [_CTX, _P, _P, _SZ, C.c_double, _P, _P, C.c_uint64, _P, _P, _P]),
+    "tfhe_hip_expand_seeded_trlwe": (C.c_int, [_CTX, _P, C.c_uint64, _P, _SZ, _P]),
+    "tfhe_hip_expand_seeded_trlwe_dev": (C.c_int, [_CTX, _P, C.c_uint64, _P, _SZ, _P, _P]),
     "tfhe_hip_batch_ifft": (C.c_int, [_CTX, _P, _P, _SZ]),
     "tfhe_hip_batch_fft": (C.c_int, [_CTX, _P, _P, _SZ]),
     "tfhe_hip_batch_poly_mul": (C.c_int, [_CTX, _P, _P, _P, _SZ]),

@@ -23,7 +23,9 @@ cryptographic: tests and benchmarks only.  A guessable generator behind `SecretK
 `encrypt_*` and `encrypt_*_seeded` also exist in the keyed format of include/tfhe_hip.h ("symmetric encryption"):
 `rng_key=` (a secret 32-byte generator key) alone is its CPU form, `device=` runs it on the GPU
 (`tfhe_hip_batch_encrypt`; rng_key=None there draws the key from getrandom(2)), `first_index=` places the batch in the
-streams.  A (rng_key, row) pair must never encrypt twice.
+streams.  A (rng_key, row) pair must never encrypt twice.  `encrypt_packed_*` take the same arguments with `first_group=`
+in the format of the header's "packed encryption" section (`tfhe_hip_batch_encrypt_trlwe`), and `encrypt_packed_*_seeded`
+return the bodies alone (seeded.SeededPackedCiphertexts).
 
 `phase`, `decrypt_*` and their packed forms take `device=` too (include/tfhe_hip.h, "decryption"): the numpy expressions
 here stay the definition, the GPU returns the same words, and a torch CUDA tensor is decrypted where it lies.
@@ -287,16 +289,43 @@ class SecretKey:
         return (torus_to_f64(self.packed_phase(packed, count)) / (1.0 / (2.0 * m)) + 0.5).astype(np.int64) % m
 
     # ---- packed inputs (unpacking key switch, include/tfhe_hip.h) ------------------------------------
-    def encrypt_packed_f64(self, p, seed=None, alpha: float | None = None) -> np.ndarray:
+    def _encrypt_packed_keyed(self, p, alpha, rng_key, mask_seed, first_group, device, full: bool):
+        """encrypt_packed_f64 in the keyed format of include/tfhe_hip.h ("packed encryption"): [groups][2][N] (full) or
+        seeded.SeededPackedCiphertexts"""
+        from .seeded import SeededPackedCiphertexts, symmetric_trlwe_rows
+
+        mask_seed = os.urandom(32) if mask_seed is None else bytes(mask_seed)
+        if len(mask_seed) != 32:
+            raise ValueError("mask_seed is 32 bytes")
+        groups = -(-len(p) // N)
+        if device is not None:
+            from .bootstrap import engine_for
+
+            return engine_for(self.params, device).batch_encrypt_trlwe(self.key_lv1, f64_to_torus(p), alpha, rng_key, mask_seed,
+                                                                       first_group, full=full, bodies=not full)
+        idx = np.uint64(int(first_group)) + np.arange(groups, dtype=np.uint64)
+        got = symmetric_trlwe_rows(mask_seed, bytes(rng_key), idx, self.key_lv1, f64_to_torus(p), len(p), alpha, full)
+        return got if full else SeededPackedCiphertexts(self.params, mask_seed, first_group, got, len(p))
+
+    def encrypt_packed_f64(self, p, seed=None, alpha: float | None = None, rng_key=None, first_group: int = 0, device=None,
+                           mask_seed: bytes = None) -> np.ndarray:
         """TRLWELv1::encrypt_f64 (trlwe.rs:30-53) over [count] values, N to a ciphertext: per group a uniform,
         b = a (*) s1 + f64_to_torus(N(0, alpha)) + f64_to_torus(p) per coefficient, alpha_lv1 by default.  Returns
-        [ceil(count / N)][2][N] u32 under key_lv1; the unused slots of the last group encrypt 0."""
+        [ceil(count / N)][2][N] u32 under key_lv1; the unused slots of the last group encrypt 0.
+        rng_key / first_group / device: the keyed format of include/tfhe_hip.h ("packed encryption"), group m at index
+        first_group + m: masks under the public mask_seed (None: fresh from the OS), noise under the secret 32-byte
+        rng_key -- on the CPU with rng_key alone, on GPU `device` otherwise (rng_key=None there: a key from
+        getrandom(2)).  A (rng_key, group) pair must never encrypt twice."""
         from .seeded import negacyclic_binary
 
-        g = _rng(seed)
         p = np.atleast_1d(np.asarray(p, dtype=np.float64)).reshape(-1)
         alpha = self.params.alpha_lv1 if alpha is None else alpha
         groups = -(-len(p) // N)
+        if mask_seed is not None and rng_key is None and device is None:
+            raise ValueError("mask_seed belongs to the keyed format: give rng_key or device")
+        if self._keyed(seed, rng_key, first_group, device, groups):
+            return self._encrypt_packed_keyed(p, alpha, rng_key, mask_seed, first_group, device, True)
+        g = _rng(seed)
         msg = np.zeros(groups * N, np.float64)
         msg[:len(p)] = p
         out = np.empty((groups, 2, N), np.uint32)
@@ -305,16 +334,45 @@ class SecretKey:
         out[:, 1] = negacyclic_binary(out[:, 0], self.key_lv1) + (f64_to_torus(msg) + noise).reshape(groups, N)
         return out
 
-    def encrypt_packed_bool(self, bits, seed=None, alpha: float | None = None) -> np.ndarray:
+    def encrypt_packed_bool(self, bits, seed=None, alpha: float | None = None, rng_key=None, first_group: int = 0,
+                            device=None, mask_seed: bytes = None) -> np.ndarray:
         """TRLWELv1::encrypt_bool (trlwe.rs:55-66): true -> +1/8, false -> -1/8, slot m = bit m."""
         bits = np.atleast_1d(np.asarray(bits)).astype(bool)
-        return self.encrypt_packed_f64(np.where(bits, 0.125, -0.125), seed, alpha)
+        return self.encrypt_packed_f64(np.where(bits, 0.125, -0.125), seed, alpha, rng_key, first_group, device, mask_seed)
 
-    def encrypt_packed_lwe_message(self, msgs, message_modulus: int, seed=None, alpha: float | None = None) -> np.ndarray:
+    def encrypt_packed_lwe_message(self, msgs, message_modulus: int, seed=None, alpha: float | None = None, rng_key=None,
+                                   first_group: int = 0, device=None, mask_seed: bytes = None) -> np.ndarray:
         """encrypt_lwe_message's encoding, (msg mod m) / (2m), in the slots of packed ciphertexts."""
         m = int(message_modulus)
         msgs = np.atleast_1d(np.asarray(msgs)).astype(np.int64) % m
-        return self.encrypt_packed_f64(msgs.astype(np.float64) * (1.0 / (2.0 * m)), seed, alpha)
+        return self.encrypt_packed_f64(msgs.astype(np.float64) * (1.0 / (2.0 * m)), seed, alpha, rng_key, first_group, device,
+                                       mask_seed)
+
+    def encrypt_packed_f64_seeded(self, p, mask_seed: bytes = None, first_group: int = 0, alpha: float | None = None,
+                                  rng_key=None, device=None):
+        """encrypt_packed_f64 in the seeded form: returns seeded.SeededPackedCiphertexts (bodies only, 4 KiB a
+        ciphertext).  Keyed format only: rng_key alone is the CPU form, device= runs on that GPU, where no mask is
+        stored at all.  mask_seed=None draws a fresh one from the OS.  Never encrypt twice under one (mask_seed, group)
+        or one (rng_key, group)."""
+        p = np.atleast_1d(np.asarray(p, dtype=np.float64)).reshape(-1)
+        alpha = self.params.alpha_lv1 if alpha is None else alpha
+        if not self._keyed(None, rng_key, first_group, device, -(-len(p) // N)):
+            raise ValueError("the seeded packed form is keyed: give rng_key or device")
+        return self._encrypt_packed_keyed(p, alpha, rng_key, mask_seed, first_group, device, False)
+
+    def encrypt_packed_bool_seeded(self, bits, mask_seed: bytes = None, first_group: int = 0, alpha: float | None = None,
+                                   rng_key=None, device=None):
+        """encrypt_packed_bool in the seeded form (see encrypt_packed_f64_seeded)."""
+        bits = np.atleast_1d(np.asarray(bits)).astype(bool)
+        return self.encrypt_packed_f64_seeded(np.where(bits, 0.125, -0.125), mask_seed, first_group, alpha, rng_key, device)
+
+    def encrypt_packed_lwe_message_seeded(self, msgs, message_modulus: int, mask_seed: bytes = None, first_group: int = 0,
+                                          alpha: float | None = None, rng_key=None, device=None):
+        """encrypt_packed_lwe_message in the seeded form (see encrypt_packed_f64_seeded)."""
+        m = int(message_modulus)
+        msgs = np.atleast_1d(np.asarray(msgs)).astype(np.int64) % m
+        return self.encrypt_packed_f64_seeded(msgs.astype(np.float64) * (1.0 / (2.0 * m)), mask_seed, first_group, alpha,
+                                              rng_key, device)
 
     # ---- evaluation key ----------------------------------------------------------------------
     def cloud_key(self, seed=None, device: int = 0):

@@ -2110,3 +2110,4 @@ int tfhe_hip_synchronize(tfhe_hip_ctx *ctx) {
 #include "pk_encrypt.hpp"
 #include "sym_encrypt.hpp"
 #include "decrypt.hpp"
+#include "trlwe_encrypt.hpp"

@@ -1096,6 +1096,80 @@ class Engine(_Handle):
         self._chk(self._lib.tfhe_hip_batch_decrypt_trlwe_dev(self._ctx, _ptr(k), self._tp(None, packed), packed.shape[0], int(count),
                                                              code, m, self._tp(None, out), self._stream_ptr(None, stream)))
 
+    # -- packed encryption: TRLWE lv1 ciphertexts, N values to a ciphertext (include/tfhe_hip.h) ------------------------
+    @staticmethod
+    def _key_lv1_arg(key_lv1) -> np.ndarray:
+        k = _u32(getattr(key_lv1, "key_lv1", key_lv1)).reshape(-1)
+        if len(k) != N:
+            raise ValueError("key_lv1 has N = 1024 words")
+        return k
+
+    def batch_encrypt_trlwe(self, key_lv1, plain, alpha: float = None, rng_key: bytes = None, mask_seed: bytes = None,
+                            first_group: int = 0, full: bool = True, bodies: bool = False):
+        """plain [count] torus words -> ceil(count / N) packed TRLWE encryptions under key_lv1 [N], group m at index
+        first_group + m of the streams (`tfhe_hip_batch_encrypt_trlwe`): masks under the public mask_seed (None: 32 fresh
+        bytes from the OS), noise under rng_key (None: the library draws it from getrandom(2)); the unused slots of the
+        last group encrypt 0.  full: return [groups][2][N]; bodies: return seeded.SeededPackedCiphertexts; both: (full,
+        seeded).  Neither a (rng_key, group) nor a (mask_seed, group) pair may encrypt twice."""
+        from .seeded import SeededPackedCiphertexts
+
+        if not (full or bodies):
+            raise ValueError("nothing to return: full and bodies are both off")
+        k1 = self._key_lv1_arg(key_lv1)
+        plain = _u32(plain).reshape(-1)
+        groups = -(-len(plain) // N)
+        mask_seed = os.urandom(32) if mask_seed is None else _seed_bytes(mask_seed)
+        seed = (C.c_uint8 * 32).from_buffer_copy(mask_seed)
+        out = np.empty((groups, 2, N), np.uint32) if full else None
+        bod = np.empty((groups, N), np.uint32) if bodies else None
+        rk, rkp = self._rng_key_arg(rng_key)
+        alpha = self.params.alpha_lv1 if alpha is None else alpha
+        self._chk(self._lib.tfhe_hip_batch_encrypt_trlwe(self._ctx, _ptr(k1), _ptr(plain), len(plain), C.c_double(alpha), rkp,
+                                                         C.addressof(seed), C.c_uint64(int(first_group)), _ptr(bod), _ptr(out)))
+        sc = SeededPackedCiphertexts(self.params, mask_seed, first_group, bod, len(plain)) if bodies else None
+        return (out, sc) if full and bodies else (out if full else sc)
+
+    def batch_encrypt_trlwe_dev(self, key_lv1, plain, alpha: float, mask_seed: bytes, rng_key: bytes = None,
+                                first_group: int = 0, bodies=None, out=None, stream=None) -> None:
+        """Device form: plain [count], bodies [groups][N] and out [groups][2][N] torch tensors (32-bit words) on this
+        engine's GPU, bodies or out may be None; key_lv1 stays a host array.  Enqueues on `stream`."""
+        k1 = self._key_lv1_arg(key_lv1)
+        if plain.dim() != 1:
+            raise ValueError("plain must be [count]")
+        count = plain.shape[0]
+        groups = -(-count // N)
+        if bodies is not None and (bodies.dim() != 2 or bodies.shape[0] != groups or bodies.shape[1] != N):
+            raise ValueError(f"bodies must be [{groups}][{N}]")
+        if out is not None and (out.dim() != 3 or out.shape[0] != groups or out.shape[1] != 2 or out.shape[2] != N):
+            raise ValueError(f"out must be [{groups}][2][{N}]")
+        seed = (C.c_uint8 * 32).from_buffer_copy(_seed_bytes(mask_seed))
+        rk, rkp = self._rng_key_arg(rng_key)
+        self._chk(self._lib.tfhe_hip_batch_encrypt_trlwe_dev(
+            self._ctx, _ptr(k1), self._tp(None, plain), count, C.c_double(alpha), rkp, C.addressof(seed),
+            C.c_uint64(int(first_group)), self._tp(None, bodies) if bodies is not None else None,
+            self._tp(None, out) if out is not None else None, self._stream_ptr(None, stream)))
+
+    def expand_seeded_trlwe(self, seeded) -> np.ndarray:
+        """seeded.SeededPackedCiphertexts -> [groups][2][N] u32, expanded on the GPU (`tfhe_hip_expand_seeded_trlwe`)."""
+        bodies = _u32(seeded.bodies).reshape(-1, N)
+        out = np.empty((len(bodies), 2, N), np.uint32)
+        seed = (C.c_uint8 * 32).from_buffer_copy(_seed_bytes(seeded.mask_seed))
+        self._chk(self._lib.tfhe_hip_expand_seeded_trlwe(self._ctx, C.addressof(seed), C.c_uint64(int(seeded.first_group)),
+                                                         _ptr(bodies), len(bodies), _ptr(out)))
+        return out
+
+    def expand_seeded_trlwe_dev(self, mask_seed: bytes, first_group: int, bodies, out, stream=None) -> None:
+        """Device form: bodies [groups][N] and out [groups][2][N] torch tensors (32-bit words) on this engine's GPU."""
+        if bodies.dim() != 2 or bodies.shape[1] != N:
+            raise ValueError(f"bodies must be [groups][{N}]")
+        groups = bodies.shape[0]
+        if out.dim() != 3 or out.shape[0] != groups or out.shape[1] != 2 or out.shape[2] != N:
+            raise ValueError(f"out must be [{groups}][2][{N}]")
+        seed = (C.c_uint8 * 32).from_buffer_copy(_seed_bytes(mask_seed))
+        self._chk(self._lib.tfhe_hip_expand_seeded_trlwe_dev(self._ctx, C.addressof(seed), C.c_uint64(int(first_group)),
+                                                             self._tp(None, bodies), groups, self._tp(None, out),
+                                                             self._stream_ptr(None, stream)))
+
     def pk_encrypt_times(self) -> dict:
         """Kernel times of the public-key encryption / asymmetric key passes since the last call (profiling on)."""
         t = _capi.PkEncryptTimes()

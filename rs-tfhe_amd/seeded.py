@@ -21,6 +21,8 @@ DOMAIN_SEED = 0x444553
 DOMAINS_SYM_TLWE = (DOMAIN_TLWE, 0x45574E)  # "EWL" masks under the public seed S, "EWN" noise under K
 DOMAINS_SYM_PK = (0x504B4D, 0x504B5A)       # "PKM", "PKZ": rows of the public key, both under K
 DOMAINS_SYM_RK = (0x524B4D, 0x524B53)       # "RKM", "RKS": rows of the symmetric re-encryption key, both under K
+# packed encryption (include/tfhe_hip.h): groups of N slots, indexed like the rows above
+DOMAINS_TRLWE = (0x45524C, 0x45524E)        # "ERL" mask polynomials under the public seed S, "ERN" noise under K
 _SIGMA = (0x61707865, 0x3320646E, 0x79622D32, 0x6B206574)
 _QR = ((0, 4, 8, 12), (1, 5, 9, 13), (2, 6, 10, 14), (3, 7, 11, 15),
        (0, 5, 10, 15), (1, 6, 11, 12), (2, 7, 8, 13), (3, 4, 9, 14))
@@ -254,4 +256,79 @@ class SeededCiphertexts:
             hi = min(lo + 8192, len(self))
             out[lo:hi, :-1] = tlwe_masks(self.mask_seed, self.first_index + lo, hi - lo, self.params.n)
         out[:, -1] = self.bodies
+        return out
+
+
+def trlwe_masks(seed: bytes, first_group: int, groups: int) -> np.ndarray:
+    """Mask polynomials of packed TRLWE ciphertexts first_group .. first_group + groups - 1, natural order: [groups, N]."""
+    g = np.uint64(int(first_group)) + np.arange(groups, dtype=np.uint64)
+    return keystream(seed, N, g & np.uint64(0xFFFFFFFF), g >> np.uint64(32), DOMAINS_TRLWE[0])
+
+
+def symmetric_trlwe_rows(mask_key: bytes, rng_key: bytes, groups_idx, key_lv1, plain, count: int, alpha: float,
+                         full: bool = True, chunk: int = 64) -> np.ndarray:
+    """The CPU form of the packed-encryption format: group m of `groups_idx` (u64 indices g) is
+    (a, a (*) s1 + f64_to_torus(e) + plain[m N ..]) with a under (mask_key, g, "ERL") in natural order and e under
+    (rng_key, g, "ERN") in the BSK generators' word order; the slots at or past `count` encrypt 0.  plain: [count] torus
+    words.  Returns [groups][2][N], or the bodies [groups][N] with full=False."""
+    g = np.asarray(groups_idx, np.uint64).reshape(-1)
+    s1 = np.asarray(key_lv1, np.uint32).reshape(N)
+    count = int(count)
+    if not (len(g) - 1) * N < count <= len(g) * N and not (count == 0 and len(g) == 0):
+        raise ValueError(f"{count} values do not fill {len(g)} groups of {N}")
+    msg = np.zeros(len(g) * N, np.uint32)
+    msg[:count] = np.asarray(plain, np.uint32).reshape(-1)[:count]
+    msg = msg.reshape(len(g), N)
+    out = np.empty((len(g), 2, N), np.uint32)
+    lo32, hi32 = g & np.uint64(0xFFFFFFFF), g >> np.uint64(32)
+    with np.errstate(over="ignore"):
+        for lo in range(0, len(g), chunk):
+            sl = slice(lo, lo + chunk)
+            rows = len(g[sl])
+            a = keystream(mask_key, N, lo32[sl], hi32[sl], DOMAINS_TRLWE[0])
+            # block 2 lane + h gives the pairs of coefficients lane + 64 (4h + q) (first sample) and + 512 (second), q < 4
+            w = chacha20_block(rng_key, np.arange(128, dtype=np.uint64), lo32[sl, None], hi32[sl, None], DOMAINS_TRLWE[1])
+            g0, g1 = gauss2(w.reshape(rows, 64, 2, 4, 4), float(alpha))  # [rows, lane, h, q]
+            e = np.concatenate([f64_to_torus(g0).reshape(rows, 64, 8).transpose(0, 2, 1).reshape(rows, 512),
+                                f64_to_torus(g1).reshape(rows, 64, 8).transpose(0, 2, 1).reshape(rows, 512)], axis=1)
+            out[sl, 0] = a
+            out[sl, 1] = negacyclic_binary(a, s1) + e + msg[sl]
+    return out if full else out[:, 1].copy()
+
+
+class SeededPackedCiphertexts:
+    """Fresh packed TRLWE ciphertexts as (mask seed, first group, bodies [groups][N], count): 4 KiB a ciphertext
+    instead of 8, plus 48 bytes."""
+
+    def __init__(self, params: SecurityParams, mask_seed: bytes, first_group: int, bodies, count: int):
+        self.params = params
+        self.mask_seed = bytes(mask_seed)
+        if len(self.mask_seed) != 32:
+            raise ValueError("mask_seed is 32 bytes")
+        self.first_group = int(first_group)
+        self.bodies = np.ascontiguousarray(bodies, dtype=np.uint32).reshape(-1, N)
+        self.count = int(count)
+        if not 0 <= self.first_group or self.first_group + len(self.bodies) > 1 << 64:
+            raise ValueError("the group indices run past 2^64")
+        if -(-self.count // N) != len(self.bodies):
+            raise ValueError(f"{self.count} values do not fill {len(self.bodies)} groups of {N}")
+
+    def __len__(self) -> int:
+        return self.count
+
+    @property
+    def groups(self) -> int:
+        return len(self.bodies)
+
+    @property
+    def nbytes(self) -> int:
+        return self.bodies.nbytes + 32 + 8 + 8
+
+    def expand(self) -> np.ndarray:
+        """[groups][2][N] u32 on the CPU (Engine.expand_seeded_trlwe does it on the GPU)."""
+        out = np.empty((self.groups, 2, N), np.uint32)
+        for lo in range(0, self.groups, 1024):
+            hi = min(lo + 1024, self.groups)
+            out[lo:hi, 0] = trlwe_masks(self.mask_seed, self.first_group + lo, hi - lo)
+        out[:, 1] = self.bodies
         return out

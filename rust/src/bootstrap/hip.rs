@@ -132,6 +132,17 @@ extern "C" {   // packing key switch (include/tfhe_hip.h): up to N lv0 results i
     fn tfhe_hip_batch_decrypt_trlwe_dev(ctx: *mut TfheHipCtx, key_lv1: *const u32, trlwe: *const u32, groups: usize,
                                         count: usize, mode: c_int, modulus: u32, out: *mut u32,
                                         stream: *mut c_void) -> c_int;
+    // packed encryption (include/tfhe_hip.h): TRLWE lv1 ciphertexts, N values each -- full, seeded and expansion; no pool forms
+    fn tfhe_hip_batch_encrypt_trlwe(ctx: *mut TfheHipCtx, key_lv1: *const u32, plain: *const u32, count: usize, alpha: f64,
+                                    rng_key: *const u8, mask_seed: *const u8, first_group: u64, bodies: *mut u32,
+                                    out: *mut u32) -> c_int;
+    fn tfhe_hip_batch_encrypt_trlwe_dev(ctx: *mut TfheHipCtx, key_lv1: *const u32, plain: *const u32, count: usize,
+                                        alpha: f64, rng_key: *const u8, mask_seed: *const u8, first_group: u64,
+                                        bodies: *mut u32, out: *mut u32, stream: *mut c_void) -> c_int;
+    fn tfhe_hip_expand_seeded_trlwe(ctx: *mut TfheHipCtx, mask_seed: *const u8, first_group: u64, bodies: *const u32,
+                                    groups: usize, out: *mut u32) -> c_int;
+    fn tfhe_hip_expand_seeded_trlwe_dev(ctx: *mut TfheHipCtx, mask_seed: *const u8, first_group: u64, bodies: *const u32,
+                                        groups: usize, out: *mut u32, stream: *mut c_void) -> c_int;
 }
 
 /// TFHE_HIP_DECRYPT_*: what `HipEngine::decrypt_batch` and `decrypt_trlwe` return per ciphertext
@@ -667,6 +678,69 @@ impl HipEngine {
         let ctx = tfhe_hip_pool_ctx(self.pool, 0);
         assert!(!ctx.is_null(), "tfhe_hip_pool_ctx failed");
         Self::check_ctx(ctx, tfhe_hip_batch_decrypt_trlwe_dev(ctx, key_lv1.as_ptr(), trlwe, groups, count, mode, modulus, out, stream));
+    }
+
+    /// TRLWELv1::encrypt_f64 over a batch on the GPU, N values to a ciphertext, in the keyed format of include/tfhe_hip.h
+    /// ("packed encryption", `tfhe_hip_batch_encrypt_trlwe`): `plain` are torus words, group m has index
+    /// `first_group + m`, its mask under the PUBLIC `mask_seed`, its noise under `rng_key` (the secret 32-byte generator
+    /// key; None draws it from getrandom(2)); the unused slots of the last group encrypt 0.  Neither a (rng_key, group)
+    /// nor a (mask_seed, group) pair may encrypt twice.  Returns [groups][2][N], flat; with `bodies` the seeded form's
+    /// bodies [groups][N] are written there too.  Runs on the pool's first member.
+    pub fn encrypt_trlwe(&self, key_lv1: &[u32], plain: &[u32], alpha: f64, rng_key: Option<&[u8; 32]>,
+                         mask_seed: &[u8; 32], first_group: u64, bodies: Option<&mut [u32]>) -> Vec<u32> {
+        assert_eq!(key_lv1.len(), N, "key_lv1 is [N]");
+        let groups = (plain.len() + N - 1) / N;
+        let mut out = vec![0u32; groups * 2 * N];
+        let bp = match bodies {
+            Some(b) => { assert_eq!(b.len(), groups * N, "bodies is [groups][N]"); b.as_mut_ptr() }
+            None => std::ptr::null_mut(),
+        };
+        if groups == 0 {
+            return out;
+        }
+        let ctx = unsafe { tfhe_hip_pool_ctx(self.pool, 0) };
+        assert!(!ctx.is_null(), "tfhe_hip_pool_ctx failed");
+        let rk = rng_key.map_or(std::ptr::null(), |k| k.as_ptr());
+        Self::check_ctx(ctx, unsafe {
+            tfhe_hip_batch_encrypt_trlwe(ctx, key_lv1.as_ptr(), plain.as_ptr(), plain.len(), alpha, rk, mask_seed.as_ptr(),
+                                         first_group, bp, out.as_mut_ptr())
+        });
+        out
+    }
+    /// The same on device pointers of the first member's GPU (`key_lv1` stays host memory), queued on `stream`: `plain`
+    /// is [count], `bodies` [groups][N] and `out` [groups][2][N], either of the two may be null.  Safety: as
+    /// `decrypt_batch_dev`.
+    pub unsafe fn encrypt_trlwe_dev(&self, key_lv1: &[u32], plain: *const u32, count: usize, alpha: f64,
+                                    rng_key: Option<&[u8; 32]>, mask_seed: &[u8; 32], first_group: u64, bodies: *mut u32,
+                                    out: *mut u32, stream: *mut c_void) {
+        assert_eq!(key_lv1.len(), N, "key_lv1 is [N]");
+        let ctx = tfhe_hip_pool_ctx(self.pool, 0);
+        assert!(!ctx.is_null(), "tfhe_hip_pool_ctx failed");
+        let rk = rng_key.map_or(std::ptr::null(), |k| k.as_ptr());
+        Self::check_ctx(ctx, tfhe_hip_batch_encrypt_trlwe_dev(ctx, key_lv1.as_ptr(), plain, count, alpha, rk, mask_seed.as_ptr(),
+                                                              first_group, bodies, out, stream));
+    }
+    /// A seeded packed batch (`mask_seed`, `first_group`, `bodies` [groups][N], flat) expanded on the GPU to the words
+    /// the full form writes, [groups][2][N] (`tfhe_hip_expand_seeded_trlwe`).  No secret is involved.
+    pub fn expand_seeded_trlwe(&self, mask_seed: &[u8; 32], first_group: u64, bodies: &[u32]) -> Vec<u32> {
+        assert_eq!(bodies.len() % N, 0, "bodies is [groups][N]");
+        let mut out = vec![0u32; bodies.len() * 2];
+        if bodies.is_empty() {
+            return out;
+        }
+        let ctx = unsafe { tfhe_hip_pool_ctx(self.pool, 0) };
+        assert!(!ctx.is_null(), "tfhe_hip_pool_ctx failed");
+        Self::check_ctx(ctx, unsafe {
+            tfhe_hip_expand_seeded_trlwe(ctx, mask_seed.as_ptr(), first_group, bodies.as_ptr(), bodies.len() / N, out.as_mut_ptr())
+        });
+        out
+    }
+    /// The same on device pointers of the first member's GPU, queued on `stream`.  Safety: as `decrypt_batch_dev`.
+    pub unsafe fn expand_seeded_trlwe_dev(&self, mask_seed: &[u8; 32], first_group: u64, bodies: *const u32, groups: usize,
+                                          out: *mut u32, stream: *mut c_void) {
+        let ctx = tfhe_hip_pool_ctx(self.pool, 0);
+        assert!(!ctx.is_null(), "tfhe_hip_pool_ctx failed");
+        Self::check_ctx(ctx, tfhe_hip_expand_seeded_trlwe_dev(ctx, mask_seed.as_ptr(), first_group, bodies, groups, out, stream));
     }
 
     /// PublicKeyLv0::new_with_params (src/proxy_reenc.rs:144-153) on the GPU (`tfhe_hip_gen_public_key`): `size`
