@@ -1216,6 +1216,27 @@ inline std::vector<Torus> conv2d(const CloudKey &ck, const tfhe_hip_conv2d_shape
   });
   return out;
 }
+// plaintext polynomial product on packed ciphertexts (tfhe_hip_batch_trlwe_polymul): w [rows][cols][N] int8 polynomials
+// over trlwe [groups][cols][2][N] -> [groups][rows][2][N], out[g][r](X) = sum_j w[r][j](X) * trlwe[g][j](X) mod X^N + 1
+// on both components, + bias[r](X) ([rows][N] torus words or nullptr) on b.  1 <= cols <= 64; the product uses no key.
+inline std::vector<Torus> polymul(const CloudKey &ck, const int8_t *w, const Torus *bias, size_t rows, size_t cols,
+                                  const Torus *trlwe, size_t groups, int device = 0) {
+  // a refused shape leaves `out` empty: the library reports it before it writes
+  const bool fits = rows && rows <= 0x7FFFFFFFull && groups <= 0x7FFFFFFFull / rows;
+  std::vector<Torus> out(fits ? groups * rows * (size_t)(2 * N) : 0);
+  Engine::for_key(ck, device).with_key(ck, [&](tfhe_hip_ctx *c) {
+    return tfhe_hip_batch_trlwe_polymul(c, w, bias, rows, cols, trlwe, groups, out.data());
+  });
+  return out;
+}
+// the one-hot polynomial sign * X^k (0 <= k < N, sign +1 or -1): polymul with it rotates the slots by k, the slots that
+// pass N coming back at the bottom negated
+inline std::vector<int8_t> monomial(size_t k, int sign = 1) {
+  if (k >= N || (sign != 1 && sign != -1)) throw std::invalid_argument("monomial: 0 <= k < N and sign +1 or -1");
+  std::vector<int8_t> w(N, 0);
+  w[k] = (int8_t)sign;
+  return w;
+}
 }  // namespace linear
 
 // ---- src/proxy_reenc.rs (feature `proxy-reenc`): LWE proxy re-encryption -----------------------------------------

@@ -395,6 +395,43 @@ int tfhe_hip_batch_trlwe_matmul(tfhe_hip_ctx *ctx, const int8_t *w, const uint32
 int tfhe_hip_batch_trlwe_matmul_dev(tfhe_hip_ctx *ctx, const int8_t *w, const uint32_t *bias, size_t rows, size_t cols,
                                     const uint32_t *trlwe, size_t groups, int keyswitch, uint32_t *out, void *stream);
 
+/* ---- plaintext polynomial products on packed ciphertexts: TRLWE in, TRLWE out ------
+ *
+ * The module operation of a packed ciphertext: out(X) = sum_j w_j(X) * ct_j(X) + bias(X) mod X^N + 1 with plaintext
+ * int8 polynomials w_j.  Input and output are both TRLWE lv1 ciphertexts, so the result stays packed: it can go into
+ * tfhe_hip_batch_unpack_trlwe (chosen slots -> lv0 ciphertexts), tfhe_hip_batch_decrypt_trlwe, the bivariate bootstrap
+ * or another product.  The product with +-X^k rotates the slots with the negacyclic sign (no Galois key); a feature map
+ * of up to N values in ONE ciphertext times one polynomial per filter is a packed 2-D convolution (the encoding:
+ * rs_tfhe_amd.linear.conv2d_packed_plan).  Exact integer arithmetic mod 2^32 on the matrix cores (csrc/matmul.hpp,
+ * MmNegacyclic).  This is not tfhe_hip_batch_poly_mul, the inexact f64 FFT stage kernel of the parity tests.
+ *
+ * Definition (normative).  N = 1024; all sums in wrapping u32 arithmetic.
+ *   w     [rows][cols][N] int8: the coefficients of rows x cols plaintext polynomials.
+ *   bias  [rows][N] u32 torus words, a plaintext polynomial per output, or NULL for zero.
+ *   trlwe [groups][cols][2][N], the a row then the b row of each (the layout tfhe_hip_batch_pack_tlwe and
+ *         tfhe_hip_batch_encrypt_trlwe write).        out  [groups][rows][2][N].
+ *   For a polynomial p: ext_p[t] = p[t] for 0 <= t < N, ext_p[t] = 0 - p[N + t] for -N < t < 0 -- the EXACT wrapping
+ *   negation, as in the packed matmul, not Torus::MAX - a.  For component c in {a, b} and coefficient i:
+ *     out[g][r][c][i] = sum_{j < cols} sum_{m < N} (int32)w[r][j][m] * ext_{in[g][j][c]}[i - m]
+ *                       + (c == b ? bias[r][i] : 0).
+ * Consequences.  The phase polynomial of out[g][r] is sum_j w[r][j](X) * phase(in[g][j])(X) + bias[r](X), exactly,
+ *   mod 2^32 (the phase b - a s is linear in (a, b) over Z[X] / (X^N + 1), and a plaintext factor commutes with s).
+ *   The noise variance of every slot scales by sum_j sum_m w[r][j][m]^2.  1 <= cols <= 64: the product is a GEMM with
+ *   K = cols * N weights per output word, and each byte-plane accumulator of the kernel is a sum of K products of two
+ *   signed bytes, |acc| <= K * 128 * 128 = cols * 2^24 <= 2^30 < 2^31 for cols <= 64 (K <= 65,536, the dense form's
+ *   bound).  No key is needed.
+ * Semantics.  As tfhe_hip_batch_trlwe_matmul: rows >= 1 and rows * groups <= 2^31 - 1.  TFHE_HIP_EINVAL for rows == 0,
+ *   cols out of range, a NULL w, trlwe or out (with groups > 0) and rows * groups too large; groups == 0 with valid
+ *   rows and cols returns TFHE_HIP_OK and writes nothing.  out must not overlap trlwe (not checked).  Bulk calls (the
+ *   context's mutex and the one staging path of the host-pointer form, never the combining front end).  _dev: every
+ *   pointer, w and bias included, is device memory; the call is queued on `stream` (NULL: the context's stream).  w
+ *   needs no alignment (a 16-byte aligned w loads fastest).  A workgroup computes 64 rows: fewer rows cost the same
+ *   (profiles/polymul_bench.json). */
+int tfhe_hip_batch_trlwe_polymul(tfhe_hip_ctx *ctx, const int8_t *w, const uint32_t *bias, size_t rows, size_t cols,
+                                 const uint32_t *trlwe, size_t groups, uint32_t *out);
+int tfhe_hip_batch_trlwe_polymul_dev(tfhe_hip_ctx *ctx, const int8_t *w, const uint32_t *bias, size_t rows, size_t cols,
+                                     const uint32_t *trlwe, size_t groups, uint32_t *out, void *stream);
+
 /* ---- encrypted 2-D convolution: int8 filters over a feature map of LWE ciphertexts ------
  *
  * The convolutional layer beside the linear one: `out_c` plaintext int8 filters of k_h x k_w x in_c slide over an

@@ -119,6 +119,8 @@ SIGNATURES = {
     "tfhe_hip_batch_tlwe_matmul_dev": (C.c_int, [_CTX, _P, _P, _SZ, _SZ, _P, _SZ, _P, _P]),
     "tfhe_hip_batch_trlwe_matmul": (C.c_int, [_CTX, _P, _P, _SZ, _SZ, _P, _SZ, C.c_int, _P]),
     "tfhe_hip_batch_trlwe_matmul_dev": (C.c_int, [_CTX, _P, _P, _SZ, _SZ, _P, _SZ, C.c_int, _P, _P]),
+    "tfhe_hip_batch_trlwe_polymul": (C.c_int, [_CTX, _P, _P, _SZ, _SZ, _P, _SZ, _P]),
+    "tfhe_hip_batch_trlwe_polymul_dev": (C.c_int, [_CTX, _P, _P, _SZ, _SZ, _P, _SZ, _P, _P]),
     "tfhe_hip_batch_tlwe_conv2d": (C.c_int, [_CTX, C.POINTER(Conv2dShape), _P, _P, _P, _SZ, _P]),
     "tfhe_hip_batch_tlwe_conv2d_dev": (C.c_int, [_CTX, C.POINTER(Conv2dShape), _P, _P, _P, _SZ, _P, _P]),
     "tfhe_hip_batch_pack_table": (C.c_int, [_CTX, _P, C.c_int, _SZ, _P]),

@@ -16,6 +16,10 @@
 // negated word: times the weights that would be a deterministic phase offset sum_i s1[i] * sum_{j<i} w[r][j], up to
 // 2^26 LSB (1/64 of the torus) at cols = 1024 and weights of 127.
 //
+// The convolution ("encrypted 2-D convolution") and the polynomial product on packed ciphertexts ("plaintext
+// polynomial products": TRLWE in, TRLWE out, K = cols N weights per output word, the 2N words of a ciphertext for
+// columns, the same exact negation) are the same GEMM with their own B loaders, MmConv and MmNegacyclic below.
+//
 // Tiling: a workgroup of kMmWaves = 4 waves owns kMmBM = 64 rows x kMmBN = 128 columns of ONE group and all four
 // planes; wave v owns column tile v (32 columns) of both 32-row fragments: 2 x 4 planes = 8 accumulator tiles of
 // 16 registers (128), + 4 B fragments (16) + 2 x 2 A fragments, current and next (16) + the 16 staged words of the
@@ -35,6 +39,14 @@
 //     packed words = 8 KiB, + 4 KiB for b, the last column).  The packed form's ninth column block holds the b column
 //     alone (N + 1 = 8 * 128 + 1).  MmConv is the 2-D convolution as an implicit GEMM: a group is one output position
 //     and K-row (ky, kx, ic) is the input ciphertext under that tap, or zero in the padding -- no im2col buffer.
+//     MmNegacyclic is the plaintext polynomial product on packed ciphertexts ("plaintext polynomial products" in the
+//     header): K-row j N + m is coefficient m of weight polynomial j, the columns are the 2N words of an output
+//     TRLWE, and B[j N + m][c N + i] = ext[i - m] of component c of input polynomial j.  It loads straight from
+//     global memory / L2 (kLdsBytes = 0), not from split words staged in LDS as MmToeplitz does: a workgroup walks
+//     `cols` different 4 KiB polynomials, not one, so staging would mean a reload and a barrier every 32 K-steps, or
+//     cols x 8 KiB of LDS (512 KiB at cols = 64); the 16 words a thread fetches are consecutive descending words of
+//     one polynomial and a wave's lanes read consecutive ascending words, so every load is one coalesced 256-byte
+//     row segment that hits L1 / L2 after the first touch.  The per-lane work is the index mask and the sign select.
 //   * Epilogue: sum_p acc_p << 8p in registers, + bias in the last column, one store per element: a wave writes
 //     128-byte row segments.  No atomics, no zeroed output.
 // Expected bound: at rows = cols = 1024, n + 1 = 701, 64 groups the product is 2 * 1024 * 1024 * 701 * 64 * 4 planes
@@ -58,7 +70,8 @@ constexpr int kMmBM = 64;            // rows per workgroup: two 32-row A fragmen
 constexpr int kMmBN = 32 * kMmWaves; // columns per workgroup: one 32-column tile per wave
 constexpr int kMmBufBytes = 4 * kMmWaves * 1024;  // one K-step of B: [plane][tile][64 lanes][16 B]
 constexpr size_t kMmMaxCols = 65536;  // accumulator bound, see above
-constexpr size_t kMmUnitsPerLaunch = (size_t)1 << 19;  // (group, row block) pairs per launch: x <= 10 column blocks x 256 threads < 2^32
+constexpr size_t kMmUnitsPerLaunch = (size_t)1 << 19;  // (group, row block) pairs per launch: x <= 16 column blocks (the polynomial product's 2N / 128) x 256 threads = 2^31 < 2^32
+constexpr size_t kPolymulMaxCols = kMmMaxCols / kN;    // polynomial product: K = cols N <= kMmMaxCols, so cols <= 64
 constexpr unsigned kMmXcds = 8;      // accelerator dies a launch's workgroups are dealt to, round-robin
 
 // The four balanced plane bytes of w, byte p = ks_plane_byte(w, p): with u = w + 0x80808080 (the carries of the
@@ -222,6 +235,48 @@ struct MmConv {
   }
   __device__ __forceinline__ static uint32_t planes(uint32_t v) { return mm_planes(v); }
 };
+
+// Plaintext polynomial product on packed ciphertexts (include/tfhe_hip.h, "plaintext polynomial products"): the kernel's
+// `cols` is K = (weight polynomials per output) x N and ncol = 2N.  K-row k = j N + m is coefficient m of weight
+// polynomial j, column x = c N + i is coefficient i of component c (0: a, 1: b) of the output, and
+//   B[k][x] = ext[i - m] of in[g][j][c]:  p[i - m] for i >= m,  0 - p[N + i - m] for i < m   (exact wrapping negation).
+// A workgroup's 128 columns lie inside one component (N % kMmBN == 0) and a 16-row fetch inside one j (kb and N are
+// multiples of 16): the polynomial's base address is wave-uniform.  K is a multiple of 32 and ncol of kMmBN, so there
+// is no K tail and no column tail: kb + 16 <= K and col < ncol on every call, and every index is masked into the
+// polynomial.  No divergent branches: the sign is a select.
+struct MmNegacyclic {
+  static constexpr int kLdsBytes = 0;
+  const uint32_t *trlwe;  // [groups][K / N][2][N]
+  __device__ __forceinline__ void setup(unsigned char *, size_t, int) const {}
+  __device__ __forceinline__ void fetch16(uint32_t (&raw)[16], const unsigned char *, size_t g, size_t cols, int,
+                                          size_t kb, int col) const {
+    const uint32_t c = (uint32_t)__builtin_amdgcn_readfirstlane((int)((uint32_t)col / (uint32_t)kN));  // (workgroup-uniform)
+    const size_t j = kb / (size_t)kN;
+    const uint32_t *p = trlwe + ((g * (cols / (size_t)kN) + j) * 2 + c) * (size_t)kN;
+    uint32_t t = (uint32_t)(col & (kN - 1)) - (uint32_t)(kb & (size_t)(kN - 1));  // i - m, in (-N, N) as an int32
+#pragma unroll
+    for (int e = 0; e < 16; ++e, --t) {
+      const uint32_t v = p[t & (uint32_t)(kN - 1)];
+      raw[e] = (int32_t)t < 0 ? 0u - v : v;
+    }
+  }
+  __device__ __forceinline__ static uint32_t planes(uint32_t v) { return mm_planes(v); }
+};
+
+// The bias polynomial of the polynomial product: out[u][1][i] += bias[u % rows][i] for the `units` = groups x rows
+// output ciphertexts from u0 on, one workgroup per ciphertext, four words a thread (word by word: neither pointer need
+// be 16-byte aligned).  (k_tlwe_matmul's own bias is one word in the last column.)  A template like every kernel of
+// this file, for the emission order.
+template <int kThreads>
+__global__ __launch_bounds__(kThreads) void k_polymul_bias(const uint32_t *__restrict__ bias, size_t rows, size_t u0,
+                                                           uint32_t *__restrict__ out) {
+  static_assert(kN % kThreads == 0, "one workgroup covers the b row");
+  const size_t u = u0 + blockIdx.x;
+  const uint32_t *src = bias + (u % rows) * (size_t)kN;
+  uint32_t *dst = out + (2 * u + 1) * (size_t)kN;
+#pragma unroll
+  for (int i = threadIdx.x; i < kN; i += kThreads) dst[i] += src[i];
+}
 
 // One launch covers groups g0 .. and row blocks rb0 .. rb0 + nrb - 1 of each (nrb < all row blocks only with one group a
 // launch) in a 1-D grid of groups x column blocks x nrb workgroups.  Workgroups are handed to the 8 XCDs round-robin in
@@ -452,6 +507,47 @@ int tfhe_hip_batch_trlwe_matmul_dev(tfhe_hip_ctx *ctx, const int8_t *w, const ui
   CHK(matmul_checks(ctx, keyswitch != 0, w, rows, cols, (size_t)kN, trlwe, groups, out, &run));
   if (!run) return TFHE_HIP_OK;
   return matmul_packed_dev(ctx, w, bias, rows, cols, trlwe, groups, keyswitch, out, pick(ctx, stream));
+}
+
+// ---- plaintext polynomial products on packed ciphertexts: the same GEMM with K = cols N and 2N columns (MmNegacyclic) --
+namespace {
+int polymul_dev(tfhe_hip_ctx *ctx, const int8_t *w, const uint32_t *bias, size_t rows, size_t cols, const uint32_t *trlwe,
+                size_t groups, uint32_t *out, hipStream_t s) {
+  CHK(launch_matmul(ctx, MmNegacyclic{trlwe}, w, nullptr, rows, cols * (size_t)kN, 2 * kN, groups, out, s));
+  if (!bias) return TFHE_HIP_OK;
+  constexpr int threads = kN / 4;
+  constexpr size_t per_launch = (size_t)1 << 23;  // workgroups a launch: x 256 threads = 2^31 < 2^32
+  const size_t units = groups * rows;
+  for (size_t u0 = 0; u0 < units; u0 += per_launch) {
+    hipLaunchKernelGGL((k_polymul_bias<threads>), dim3((unsigned)(units - u0 < per_launch ? units - u0 : per_launch)),
+                       dim3(threads), 0, s, bias, rows, u0, out);
+    CHK(launched(ctx));
+  }
+  return TFHE_HIP_OK;
+}
+}  // namespace
+
+int tfhe_hip_batch_trlwe_polymul(tfhe_hip_ctx *ctx, const int8_t *w, const uint32_t *bias, size_t rows, size_t cols,
+                                 const uint32_t *trlwe, size_t groups, uint32_t *out) {
+  if (!ctx) return TFHE_HIP_EINVAL;
+  ENTER(ctx);
+  bool run = false;
+  CHK(matmul_checks(ctx, false, w, rows, cols, kPolymulMaxCols, trlwe, groups, out, &run));
+  if (!run) return TFHE_HIP_OK;
+  return host_call(ctx, false, {{w, rows * cols * (size_t)kN, &ctx->a}, {bias, rows * (size_t)kN * 4, &ctx->b}, {trlwe, trlwe_bytes(groups * cols), &ctx->c}},
+                   out, trlwe_bytes(groups * rows), [&](const void *const *d, void *o) {
+                     return polymul_dev(ctx, (const int8_t *)d[0], u32(d[1]), rows, cols, u32(d[2]), groups, (uint32_t *)o, ctx->stream);
+                   });
+}
+
+int tfhe_hip_batch_trlwe_polymul_dev(tfhe_hip_ctx *ctx, const int8_t *w, const uint32_t *bias, size_t rows, size_t cols,
+                                     const uint32_t *trlwe, size_t groups, uint32_t *out, void *stream) {
+  if (!ctx) return TFHE_HIP_EINVAL;
+  ENTER(ctx);
+  bool run = false;
+  CHK(matmul_checks(ctx, false, w, rows, cols, kPolymulMaxCols, trlwe, groups, out, &run));
+  if (!run) return TFHE_HIP_OK;
+  return polymul_dev(ctx, w, bias, rows, cols, trlwe, groups, out, pick(ctx, stream));
 }
 
 // ---- encrypted 2-D convolution: the same GEMM with output positions for groups (MmConv) ------------------------------

@@ -730,6 +730,42 @@ class Engine(_Handle):
         self._call("batch_trlwe_matmul_dev", C.c_void_p(w.data_ptr()), self._tp(None, bias), rows, cols,
                    self._tp(None, trlwe), groups, int(bool(keyswitch)), self._tp(None, out), self._stream_ptr(None, stream))
 
+    # -- plaintext polynomial products on packed ciphertexts (include/tfhe_hip.h): TRLWE in, TRLWE out ---------------------
+    def batch_trlwe_polymul(self, w, trlwe, bias=None) -> np.ndarray:
+        """out[g][r](X) = sum_j w[r][j](X) * trlwe[g][j](X) + bias[r](X) mod X^N + 1 (`tfhe_hip_batch_trlwe_polymul`;
+        linear.polymul_model): w [rows][cols][N] int8 (or [N]: one polynomial), trlwe [groups][cols][2][N] (or
+        [cols][2][N]: one group; [2][N] with cols == 1), bias [rows][N] torus words or None.  Returns
+        [groups][rows][2][N].  Needs no key."""
+        from .linear import _packed_inputs, _polys
+
+        w, bias = _polys(w, bias)
+        rows, cols = w.shape[:2]
+        trlwe = _packed_inputs(trlwe, cols)
+        groups = len(trlwe)
+        out = np.empty((groups, rows, 2, N), np.uint32)
+        self._call("batch_trlwe_polymul", _ptr(w), _ptr(bias), rows, cols, _ptr(trlwe), groups, _ptr(out))
+        return out
+
+    def batch_trlwe_polymul_dev(self, w, trlwe, out, bias=None, stream=None) -> None:
+        """Device form: w int8 [rows][cols][N], trlwe [groups][cols][2][N], out [groups][rows][2][N] and bias [rows][N]
+        (or None) CUDA tensors on this engine's GPU (32-bit words but for w); out must not overlap trlwe."""
+        from .linear import MAX_POLY_COLS
+
+        if w is None or not w.is_cuda or w.dim() != 3 or w.element_size() != 1 or not w.is_contiguous() or \
+                w.device.index != self.device or w.shape[0] < 1 or not 1 <= w.shape[1] <= MAX_POLY_COLS or w.shape[2] != N:
+            raise ValueError(f"w must be a contiguous int8 CUDA tensor [rows][cols][{N}] on cuda:{self.device} "
+                             f"with 1 <= cols <= {MAX_POLY_COLS}")
+        rows, cols = int(w.shape[0]), int(w.shape[1])
+        if bias is not None and tuple(bias.shape) != (rows, N):
+            raise ValueError(f"bias must be [rows][{N}]")
+        if trlwe is None or trlwe.dim() != 4 or tuple(trlwe.shape[1:]) != (cols, 2, N):
+            raise ValueError(f"trlwe must be [groups][{cols}][2][{N}]")
+        groups = int(trlwe.shape[0])
+        if out is None or tuple(out.shape) != (groups, rows, 2, N):
+            raise ValueError(f"out must be [{groups}][{rows}][2][{N}]")
+        self._call("batch_trlwe_polymul_dev", C.c_void_p(w.data_ptr()), self._tp(None, bias), rows, cols,
+                   self._tp(None, trlwe), groups, self._tp(None, out), self._stream_ptr(None, stream))
+
     # -- encrypted 2-D convolution (include/tfhe_hip.h): int8 filters over a feature map of ciphertexts -------------------
     def _conv2d_shape(self, w_shape, cts_shape, bias_len, stride, padding):
         """(struct tfhe_hip_conv2d_shape, groups, (out_h, out_w)) of filters [out_c][k_h][k_w][in_c] over a map

@@ -11,6 +11,11 @@ when a programmable bootstrap follows, so that it stays in the table's non-negac
 The convolutional layer ("encrypted 2-D convolution" in the header) is the dense form over the taps of a filter:
 conv2d_model is its definition, an explicit im2col into the same exact sum; conv2d is the server side.  Feature maps are
 channels-last, [groups][in_h][in_w][in_c][n+1], on both sides of a layer.
+
+The polynomial product ("plaintext polynomial products on packed ciphertexts" in the header) is the operation that keeps
+a packed ciphertext packed: out(X) = sum_j w_j(X) * ct_j(X) + bias(X) mod X^N + 1, TRLWE in and TRLWE out.
+polymul_model is its definition, polymul the server side, monomial the slot rotation +-X^k, and conv2d_packed_plan /
+conv2d_packed_weights the encoding under which it is a convolution of a whole feature map held in ONE ciphertext.
 """
 from __future__ import annotations
 
@@ -139,6 +144,152 @@ def conv2d_model(params: SecurityParams, w, cts, bias=None, stride=1, padding=0)
         cols = rows[:, :, ix].transpose(0, 2, 1, 3, 4, 5)            # [groups][out_w][k_h][k_w][in_c][width]
         out[:, oy] = _product(w2, cols.reshape(groups, out_w, k_h * k_w * in_c, width), bias)
     return out
+
+
+# ---- plaintext polynomial products on packed ciphertexts ("plaintext polynomial products", include/tfhe_hip.h) ----------
+MAX_POLY_COLS = MAX_COLS // N  # K = cols * N weights per output word: the dense form's accumulator bound, cols <= 64
+
+
+def _polys(w, bias):
+    """(w as C-contiguous [rows][cols][N] int8, bias as [rows][N] u32 or None) after the header's shape checks; a single
+    polynomial [N] is rows = cols = 1."""
+    w = np.asarray(w)
+    if w.ndim == 1:
+        w = w[None, None]
+    if w.ndim != 3 or w.shape[0] < 1 or not 1 <= w.shape[1] <= MAX_POLY_COLS or w.shape[2] != N:
+        raise ValueError(f"w must be [rows][cols][{N}] with rows >= 1 and 1 <= cols <= {MAX_POLY_COLS}")
+    if not np.issubdtype(w.dtype, np.integer) or w.min() < -128 or w.max() > 127:
+        raise ValueError("weights must be integers in [-128, 127]")
+    if bias is not None:
+        bias = np.ascontiguousarray(bias, dtype=np.uint32)
+        if bias.shape == (N,) and w.shape[0] == 1:
+            bias = bias[None]
+        if bias.shape != (w.shape[0], N):
+            raise ValueError(f"bias must be [rows][{N}]")
+    return np.ascontiguousarray(w, dtype=np.int8), bias
+
+
+def _packed_inputs(trlwe, cols: int) -> np.ndarray:
+    """trlwe as [groups][cols][2][N] u32.  Accepted besides: [cols][2][N] (one group) and, for cols == 1, what the
+    packers and SecretKey.encrypt_packed_* return: [groups][2][N] or [2][N]."""
+    t = np.ascontiguousarray(trlwe, dtype=np.uint32)
+    if cols == 1 and t.ndim in (2, 3) and t.shape[-2:] == (2, N):
+        t = t.reshape(-1, 1, 2, N)
+    elif t.ndim == 3:
+        t = t[None]
+    if t.ndim != 4 or t.shape[1:] != (cols, 2, N):
+        raise ValueError(f"trlwe must be [groups][{cols}][2][{N}]")
+    return t
+
+
+def polymul_model(w, trlwe, bias=None) -> np.ndarray:
+    """The polynomial product's definition: w [rows][cols][N] int8 (or [N]), trlwe [groups][cols][2][N] (the forms of
+    _packed_inputs), bias [rows][N] torus words or None -> [groups][rows][2][N] u32 with
+    out[g][r](X) = sum_j w[r][j](X) * trlwe[g][j](X) mod X^N + 1 on both components, + bias[r](X) on b.  Exact: for each
+    input polynomial the N rotated and sign-flipped rows X^m * p (row m holds ext_p[i - m], negated with the wrapping
+    0 - p where it wrapped) are summed with the weights w[r][j][m].  The sums run as float64 matrix products over the
+    16-bit halves of the words: N * 128 * 65,535 < 2^40, exact."""
+    w8, bias = _polys(w, bias)
+    rows, cols = w8.shape[:2]
+    t = _packed_inputs(trlwe, cols)
+    groups = len(t)
+    out = np.zeros((groups, rows, 2, N), np.uint32)
+    for j in range(cols):
+        p = t[:, j]                                                        # [groups][2][N]
+        ext = np.concatenate([np.uint32(0) - p, p], axis=-1)               # ext[t] at index t + N
+        rot = np.lib.stride_tricks.sliding_window_view(ext, N, axis=-1)[:, :, N:0:-1]  # [groups][2][m][i] = ext[i - m]
+        used = np.flatnonzero(w8[:, j].any(axis=0))                        # a monomial or a filter uses few of the N rows
+        wj = w8[:, j, used].astype(np.float64)                             # [rows][m]
+        for c in range(2):
+            rc = rot[:, c][:, used]
+            lo = np.matmul(wj, (rc & 0xFFFF).astype(np.float64)).astype(np.int64)
+            hi = np.matmul(wj, (rc >> 16).astype(np.float64)).astype(np.int64)
+            out[:, :, c] += ((lo + (hi << 16)) & 0xFFFFFFFF).astype(np.uint32)
+    if bias is not None:
+        out[:, :, 1] += bias
+    return out
+
+
+def monomial(k: int, sign: int = 1) -> np.ndarray:
+    """The one-hot int8 polynomial sign * X^k, 0 <= k < N, sign +1 or -1: polymul with it rotates the slots, slot i
+    moving to i + k and the slots that pass N coming back at the bottom negated (X^N = -1)."""
+    if not isinstance(k, (int, np.integer)) or not 0 <= k < N or sign not in (1, -1):
+        raise ValueError(f"monomial: 0 <= k < {N} and sign +1 or -1")
+    w = np.zeros(N, np.int8)
+    w[k] = sign
+    return w
+
+
+class PackedConvPlan:
+    """The packed-convolution encoding of conv2d_packed_plan: where the client puts the map, where conv2d_packed_weights
+    puts the filters, and `slots` [out_h][out_w] u32, the coefficients of the product that hold the outputs."""
+
+    def __init__(self, in_c, in_h, in_w, k_h, k_w, stride):
+        (sh, sw) = _pair(stride, "stride", 1)
+        dims = (in_c, in_h, in_w, k_h, k_w)
+        if any(not isinstance(x, (int, np.integer)) or x < 1 for x in dims) or k_h > in_h or k_w > in_w:
+            raise ValueError("every dimension must be at least 1 and the filter no larger than the map")
+        if in_c * in_h * in_w > N:
+            raise ValueError(f"in_c * in_h * in_w = {in_c * in_h * in_w} values do not fit one ciphertext of {N} slots")
+        self.in_c, self.in_h, self.in_w, self.k_h, self.k_w = (int(x) for x in dims)
+        self.stride = (sh, sw)
+        self.offset = (self.in_c - 1) * self.in_h * self.in_w + (self.k_h - 1) * self.in_w + (self.k_w - 1)
+        self.out_h, self.out_w = (self.in_h - self.k_h) // sh + 1, (self.in_w - self.k_w) // sw + 1
+        oy, ox = np.arange(self.out_h) * sh, np.arange(self.out_w) * sw
+        self.slots = (self.offset + oy[:, None] * self.in_w + ox[None, :]).astype(np.uint32)
+
+    def encode(self, fmap) -> np.ndarray:
+        """A map [in_c][in_h][in_w] -> its N slot values (zeros above): value (c, y, x) at index c H W + y W + x."""
+        fmap = np.asarray(fmap)
+        if fmap.shape != (self.in_c, self.in_h, self.in_w):
+            raise ValueError(f"the map must be [{self.in_c}][{self.in_h}][{self.in_w}]")
+        out = np.zeros(N, fmap.dtype)
+        out[:fmap.size] = fmap.reshape(-1)
+        return out
+
+
+def conv2d_packed_plan(in_c: int, in_h: int, in_w: int, k_h: int, k_w: int, stride=1) -> PackedConvPlan:
+    """The packed form of the convolution: a whole feature map of in_c * in_h * in_w <= N values in ONE TRLWE, each
+    filter one plaintext polynomial, every output of the valid (unpadded) convolution one coefficient of their product.
+      * the map: value (c, y, x) at coefficient c H W + y W + x  (plan.encode; padding is the client's affair: it packs
+        an already padded map);
+      * filter oc (conv2d_packed_weights): f[oc][ky][kx][c] at coefficient O - (c H W + ky W + kx),
+        O = (C - 1) H W + (k_h - 1) W + (k_w - 1)  (plan.offset);
+      * output (oy, ox) of the stride-1 convolution: coefficient O + oy W + ox of the product; a stride only picks fewer
+        of them.  plan.slots [out_h][out_w] holds them: Engine.unpack(product, slots=plan.slots) gives the lv0
+        ciphertexts in [out_h][out_w] order.
+    Safe because a product term lands at O + (map index) - (filter index): the wanted slots are at most
+    O + (H - k_h) W + (W - k_w) = C H W - 1 < N, and a term that wraps past N comes back at an index below
+    O + C H W - N <= O, under every wanted slot.  The other coefficients of the product hold sums nobody asked for.
+    ValueError if the map does not fit."""
+    return PackedConvPlan(in_c, in_h, in_w, k_h, k_w, stride)
+
+
+def conv2d_packed_weights(w, plan: PackedConvPlan) -> np.ndarray:
+    """Filters [out_c][k_h][k_w][in_c] int8 (the layout of conv2d) -> [out_c][1][N] int8 polynomials for polymul, by
+    `plan`'s encoding."""
+    w = np.asarray(w)
+    if w.ndim != 4 or w.shape[0] < 1 or w.shape[1:] != (plan.k_h, plan.k_w, plan.in_c):
+        raise ValueError(f"w must be [out_c][{plan.k_h}][{plan.k_w}][{plan.in_c}]")
+    if not np.issubdtype(w.dtype, np.integer) or w.min() < -128 or w.max() > 127:
+        raise ValueError("weights must be integers in [-128, 127]")
+    c, ky, kx = np.meshgrid(np.arange(plan.in_c), np.arange(plan.k_h), np.arange(plan.k_w), indexing="ij")
+    at = plan.offset - (c * plan.in_h * plan.in_w + ky * plan.in_w + kx)   # [in_c][k_h][k_w]
+    out = np.zeros((w.shape[0], 1, N), np.int8)
+    out[:, 0, at.reshape(-1)] = w.transpose(0, 3, 1, 2).reshape(w.shape[0], -1)
+    return out
+
+
+def polymul(w, packed, cloud_key, bias=None, device: int = 0) -> np.ndarray:
+    """The server side of the polynomial product: [groups][cols][2][N] TRLWE lv1 ciphertexts (the forms of
+    _packed_inputs) -> [groups][rows][2][N] on the GPU (Engine.batch_trlwe_polymul on the shared context of
+    `cloud_key`'s parameter set; the product itself uses no key)."""
+    from .bootstrap import keyed_engine
+
+    w8, bias = _polys(w, bias)
+    packed = _packed_inputs(packed, w8.shape[1])
+    with keyed_engine(cloud_key, device) as view:
+        return view.batch_trlwe_polymul(w8, packed, bias)
 
 
 def _checked(w, bias, max_cols: int):

@@ -164,6 +164,11 @@ extern "C" {   // encrypted linear layers (include/tfhe_hip.h): a plaintext int8
     fn tfhe_hip_batch_trlwe_matmul_dev(ctx: *mut TfheHipCtx, w: *const int8_t, bias: *const u32, rows: usize, cols: usize,
                                        trlwe: *const u32, groups: usize, keyswitch: c_int, out: *mut u32,
                                        stream: *mut c_void) -> c_int;
+    // plaintext polynomial products on packed ciphertexts (include/tfhe_hip.h): TRLWE in, TRLWE out
+    fn tfhe_hip_batch_trlwe_polymul(ctx: *mut TfheHipCtx, w: *const int8_t, bias: *const u32, rows: usize, cols: usize,
+                                    trlwe: *const u32, groups: usize, out: *mut u32) -> c_int;
+    fn tfhe_hip_batch_trlwe_polymul_dev(ctx: *mut TfheHipCtx, w: *const int8_t, bias: *const u32, rows: usize, cols: usize,
+                                        trlwe: *const u32, groups: usize, out: *mut u32, stream: *mut c_void) -> c_int;
     // encrypted 2-D convolution (include/tfhe_hip.h): int8 filters over a channels-last map of LWE ciphertexts
     fn tfhe_hip_batch_tlwe_conv2d(ctx: *mut TfheHipCtx, shape: *const TfheHipConv2dShape, w: *const int8_t, bias: *const u32,
                                   input: *const u32, groups: usize, out: *mut u32) -> c_int;
@@ -903,6 +908,38 @@ impl HipEngine {
             (0, ())
         });
         out
+    }
+    /// Plaintext polynomial product on packed ciphertexts (`tfhe_hip_batch_trlwe_polymul`): `w` is [rows][cols][N] int8
+    /// polynomials, `trlwe` [groups][cols][2][N] flat, `bias` [rows][N] torus words; returns [groups][rows][2][N] flat,
+    /// out[g][r](X) = sum_j w[r][j](X) * trlwe[g][j](X) mod X^N + 1 on both components, + bias[r](X) on b, exact mod
+    /// 2^32.  cols <= 64.  Runs on the first member of `ck`'s key view (no pool form; the product itself uses no key).
+    pub fn trlwe_polymul(&self, w: &[i8], bias: Option<&[u32]>, rows: usize, cols: usize, trlwe: &[u32], ck: &CloudKey) -> Vec<u32> {
+        assert!(rows > 0 && cols > 0 && cols <= 64 && w.len() == rows * cols * N, "w is [rows][cols][N], cols <= 64");
+        assert_eq!(trlwe.len() % (cols * 2 * N), 0, "trlwe is [groups][cols][2][N]");
+        assert!(bias.map_or(true, |b| b.len() == rows * N), "bias is [rows][N]");
+        let groups = trlwe.len() / (cols * 2 * N);
+        let bp = bias.map_or(std::ptr::null(), |b| b.as_ptr());
+        let mut out = vec![0u32; groups * rows * 2 * N];
+        self.with_key(ck, |v| {
+            let ctx = unsafe { tfhe_hip_pool_ctx(v, 0) };
+            assert!(!ctx.is_null(), "tfhe_hip_pool_ctx failed");
+            Self::check_ctx(ctx, unsafe {
+                tfhe_hip_batch_trlwe_polymul(ctx, w.as_ptr(), bp, rows, cols, trlwe.as_ptr(), groups, out.as_mut_ptr())
+            });
+            (0, ())
+        });
+        out
+    }
+    /// The same on device pointers of the first member's GPU (`w` and `bias` too; `bias` may be null), queued on
+    /// `stream`.  Safety: the pointers must stay valid until the work has run.
+    pub unsafe fn trlwe_polymul_dev(&self, w: *const i8, bias: *const u32, rows: usize, cols: usize, trlwe: *const u32,
+                                    groups: usize, out: *mut u32, stream: *mut c_void, ck: &CloudKey) {
+        self.with_key(ck, |v| {
+            let ctx = tfhe_hip_pool_ctx(v, 0);
+            assert!(!ctx.is_null(), "tfhe_hip_pool_ctx failed");
+            Self::check_ctx(ctx, tfhe_hip_batch_trlwe_polymul_dev(ctx, w, bias, rows, cols, trlwe, groups, out, stream));
+            (0, ())
+        });
     }
     /// Encrypted 2-D convolution (`tfhe_hip_batch_tlwe_conv2d`): `w` is [out_c][k_h][k_w][in_c] int8, `input`
     /// [groups][in_h][in_w][in_c][n+1] flat (channels-last), `bias` [out_c] torus words; returns
