@@ -8,8 +8,16 @@ toggle.  SECURITY_UINT4 (l = 1, general rounding, the column-sliced key switch, 
 order-independence, so the reference is THE SAME CALL MADE ALONE -- every step by its host form on a second context
 with the same keys, a synchronisation after each -- word for word (kernels agree bit for bit across forms and counts:
 test_dispatch_crossovers_bit_exact; isolated calls are held to the oracle by the other suites); and every gate-type
-output on genuine encryptions decrypts to its truth table.  A directed test holds the one pair found by reading: a
-host key switch issued while an un-synchronised unpack_dev still walks the shared digit scratch.
+output on genuine encryptions decrypts to its truth table, and the two chains that start in a fresh encryption
+(encrypt -> tlwe_matmul -> decrypt; encrypt_trlwe -> polymul -> trlwe_matmul -> decrypt) end in the plaintext product
+within 8 sigma of the encryption noise, by a computation that uses neither the device nor the library.  A directed test
+holds the one pair found by reading: a host key switch issued while an un-synchronised unpack_dev still walks the shared
+digit scratch; a second one the pair of the staged secrets: a host decryption under another view's key issued while an
+un-synchronised encrypt_trlwe_dev still reads the context's one buffer of them.
+
+The steps cover gates, bootstraps, the packing and table key switches, and -- with real noise, keys and indices of
+their own per step -- public-key and symmetric encryption, packed encryption and expansion, decryption, the dense and
+packed linear layers, the convolution and the polynomial product.
 
 The six sequences of a shape run on one context, seed after seed, and scratch never shrinks: the grow step of seed s
 is 1.5 x that of seed s - 1 (more than ensure()'s quarter of headroom), so each of them reallocates under in-flight
@@ -75,8 +83,15 @@ def _world(O, name):
         vr.load_reenc_key(w.reenc)
         eng.load_packing_key(w.packing["E"])
         v2.load_packing_key(w.packing["V2"])
-        return {"E": eng, "V2": v2, "VR": vr, "book": w.book, "packing": w.packing, "combining_default": w.default_combining}
+        # a public key beside each cloud key, under the handle's own secret (a fixed generator key: the same words on
+        # every context); a key change on V2 leaves it in place
+        public = {h: x.gen_public_key(w.secrets[h].key_lv0, size=SF.PK_SIZE, rng_key=SF.PK_GEN_KEY) for h, x in (("E", eng), ("V2", v2))}
+        assert all(np.array_equal(public[h], w.public.setdefault(h, public[h])) for h in public)
+        return {"E": eng, "V2": v2, "VR": vr, "book": w.book, "packing": w.packing, "combining_default": w.default_combining,
+                "secrets": w.secrets}
 
+    w.secrets = {"E": w.sk["K1"], "V2": w.sk["K2"], "VR": w.sk["K1"]}
+    w.public = {}
     w.handles = handles(w.eng)
     w.alone = None
     if not w.shape.exact:
@@ -85,12 +100,11 @@ def _world(O, name):
         w.alone = handles(w.eng2)
     w.be = SF.TorchBackend()
     w.streams = w.be.streams()
-    w.secrets = {"E": w.sk["K1"], "V2": w.sk["K2"], "VR": w.sk["K1"]}
     w.keys = w.model = None
     if w.shape.exact:
         cloud = {k: O.CloudKey.from_arrays(w.op, c.bootstrapping_key, c.key_switching_key, c.decomposition_offset,
                                            c.blind_rotate_testvec) for k, c in exported.items()}
-        w.keys = {"params": p, "oracle_params": w.op, "cloud": cloud, "reenc": w.reenc,
+        w.keys = {"params": p, "oracle_params": w.op, "cloud": cloud, "reenc": w.reenc, "secrets": w.secrets, "public": w.public,
                   "packing": {h: (pk, PK.key_rows(p, pk.mask_seed, pk.bodies)) for h, pk in w.packing.items()}}
         w.model = SF.Model(O, w.keys)
     w.report, w.got, w.pools = {}, {}, {}
@@ -175,7 +189,65 @@ def test_sequences_uint4(O, seed):
             continue
         assert np.array_equal(w.secrets[st.handle].decrypt_bool(got[st.i]), bits), st
         checked += 1
+    checked += _chains_decrypt_to_their_plaintext_products(w, seq, got)
     assert checked >= 5
+
+
+def _signed(words):
+    """torus differences as signed LSB"""
+    return (np.asarray(words, np.int64) + (1 << 31)) % (1 << 32) - (1 << 31)
+
+
+def _negacyclic(poly):
+    """T [N][N] int64 with (poly(X) * x(X) mod X^N + 1)[i] = sum_k T[i][k] x[k]"""
+    i, k = np.arange(N)[:, None], np.arange(N)[None, :]
+    return np.where(k > i, -1, 1) * np.asarray(poly, np.int64)[(i - k) % N]
+
+
+def _chains_decrypt_to_their_plaintext_products(w, seq, got):
+    """No device and no library in the reference: the phases chain C and chain D end in -- as decrypt_dev returned them
+    and as SecretKey.phase / phase_lv1 reads them on the CPU off the chain's last ciphertexts -- are W plain + bias (C),
+    or the matrix times the slots of the polynomial product of the plaintexts (D), mod 2^32.  Allowed error: 8 sigma of
+    the sum of the independent Gaussians the fresh encryptions carry, sigma = alpha 2^32 sqrt(sum of the squared weights
+    each noise sample reaches the output row with), derived per row below; a failure chance below 1e-12 over the
+    corpus.  Returns the chains checked."""
+    done = 0
+    for which, n_links in (("C", 3), ("D", 4)):
+        links = [st for st in seq if st.kind == "call" and st.args.get("chain") == which]
+        assert len(links) == n_links, (which, links)
+        sk, enc, mm, dec = w.secrets[links[0].handle], links[0], links[-2], links[-1]
+        rows, cols, groups = mm.args["shape"]
+        W, bias = mm.ins[0][1].astype(np.int64), mm.ins[2][1].astype(np.int64)
+        if which == "C":
+            x = enc.ins[0][1][:groups * cols].astype(np.int64).reshape(groups, cols)  # the plaintexts the matrix takes
+            want = x @ W.T + bias[None, :]
+            sumsq = np.broadcast_to((W ** 2).sum(axis=1).astype(np.float64), (groups, rows))
+            alpha, cpu = w.shape.alpha_lv0, sk.phase(got[mm.i])
+        else:
+            poly = links[1]
+            p_rows, p_cols, p_groups = poly.args["shape"]
+            slots = np.zeros(p_groups * p_cols * N, np.int64)
+            slots[:enc.args["words"]] = enc.ins[0][1]
+            slots = slots.reshape(p_groups, p_cols, N)
+            wp, bp = poly.ins[0][1], poly.ins[2][1].astype(np.int64)
+            T = [[_negacyclic(wp[r, c]) for c in range(p_cols)] for r in range(p_rows)]
+            Wpad = np.zeros((rows, N), np.int64)
+            Wpad[:, :cols] = W
+            want = np.empty((groups, rows), np.int64)
+            sumsq = np.empty((groups, rows), np.float64)
+            for g in range(p_groups):
+                for r in range(p_rows):
+                    pt = (sum(T[r][c] @ slots[g, c] for c in range(p_cols)) + bp[r]) % (1 << 32)  # slots of the product
+                    want[g * p_rows + r] = Wpad @ pt + bias
+                    # noise sample k of input polynomial c reaches output row q with weight (Wpad @ T[r][c])[q][k]
+                    sumsq[g * p_rows + r] = sum(((Wpad @ T[r][c]).astype(np.float64) ** 2).sum(axis=1) for c in range(p_cols))
+            alpha, cpu = w.shape.alpha_lv1, sk.phase_lv1(got[mm.i])
+        bound = 8.0 * alpha * 4294967296.0 * np.sqrt(sumsq)
+        for name, ph in (("decrypt_dev", got[dec.i]), ("SecretKey on the CPU", cpu)):
+            err = np.abs(_signed(ph.reshape(groups, rows).astype(np.int64) - want))
+            assert (err <= bound).all(), f"chain {which} ({name}): {int(err.max())} LSB off, {float(bound.min()):.1f} allowed; {dec}"
+        done += 1
+    return done
 
 
 def test_comparison_sees_one_wrong_step(O):
@@ -260,6 +332,93 @@ def test_host_key_switch_after_an_unsynchronised_dev_call(O):
     assert [(u, v) for *_, u, v in rounds] == [(0, 0)] * 4, _DIRECTED["line"]
 
 
+PAIR_WORDS = 64 << 20  # plaintext words of the second directed pair's first call
+
+
+def test_host_decrypt_after_an_unsynchronised_encrypt_trlwe(O):
+    """batch_encrypt_trlwe_dev on a side stream under K1's ring key (E stages K, s1 [N] and the spectrum of s1 in the
+    context's sym_sec), then AT ONCE a host batch_decrypt (bool, lv0) of 400 rows under K2's key on the key view V2
+    (another view, another key, another layout of the same sym_sec: 64 words of key bits), then both results against
+    the same two calls made alone.  Four rounds, each with its own data, keys and group indices.
+
+    As in the pair above, the first call alone is timed once with events, and every round asserts that it had not
+    finished when the host call was entered.  Its size is the smallest power-of-two count of plaintext words for which
+    the call alone lasts at least ten times the time it takes to issue it, capped at 64 Mi: measured on an MI355X,
+    doubling from 16 Ki, no smaller count got there, and 64 Mi words (65,536 groups, 512 MiB of ciphertexts) last
+    0.73 - 0.75 ms alone against 0.05 - 0.07 ms to issue.  In the rounds the host call was entered 0.06 - 0.09 ms after the
+    first, which was still running all four times, and returned 0.74 - 0.78 ms later, after it had finished: the claim on
+    sym_sec makes the host call wait for the side stream; without one it would stage K2's bits under the running
+    kernel.  0 wrong words in both results."""
+    import torch
+
+    w = _world(O, "SECURITY_UINT4")
+    e, v2, p = w.handles["E"], w.handles["V2"], w.p
+    _reset(w, w.handles)
+    side = torch.cuda.Stream(device=0)
+    rng = np.random.default_rng(7600)
+    k1, k2 = w.sk["K1"].key_lv1, w.sk["K2"].key_lv0
+    words = PAIR_WORDS
+
+    def encrypt(plain, keys, out):
+        e.batch_encrypt_trlwe_dev(k1, plain, p.alpha_lv1, keys[0], keys[1], keys[2], out=out, stream=side)
+
+    def fresh_keys():
+        return rng.integers(0, 256, 32).astype(np.uint8).tobytes(), rng.integers(0, 256, 32).astype(np.uint8).tobytes(), \
+            int(rng.integers(0, 1 << 40))
+
+    plain = w.be.upload(SF.words(rng, words))
+    ref = torch.empty((words // N, 2, N), dtype=torch.int32, device="cuda:0")
+    keys = fresh_keys()
+    encrypt(plain, keys, ref)  # (grows sym_sec and warms the kernels)
+    torch.cuda.synchronize()
+    a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    a.record(side)
+    t0 = time.perf_counter()
+    encrypt(plain, keys, ref)
+    issue_alone_ms = (time.perf_counter() - t0) * 1e3
+    b.record(side)
+    torch.cuda.synchronize()
+    first_ms = a.elapsed_time(b)
+    out = torch.empty_like(ref)
+    rounds = []
+    for r in range(4):
+        plain = w.be.upload(SF.words(rng, words))
+        keys = fresh_keys()
+        cts = w.sk["K2"].encrypt_bool(rng.integers(0, 2, 400).astype(bool), 7610 + r)
+        # alone
+        encrypt(plain, keys, ref)
+        torch.cuda.synchronize()
+        want_bits = v2.batch_decrypt(k2, cts, "bool")
+        v2.synchronize()
+        assert np.array_equal(want_bits.astype(bool), w.sk["K2"].decrypt_bool(cts))
+        out.fill_(SF.FILL)
+        torch.cuda.synchronize()
+        # the pair
+        done = torch.cuda.Event()
+        t0 = time.perf_counter()
+        encrypt(plain, keys, out)
+        done.record(side)
+        running_at_issue = not done.query()
+        t1 = time.perf_counter()
+        got_bits = v2.batch_decrypt(k2, cts, "bool")
+        running_at_return = not done.query()
+        t2 = time.perf_counter()
+        torch.cuda.synchronize()
+        wrong_first = int((out != ref).sum().item())
+        wrong_second = int((got_bits != want_bits).sum())
+        rounds.append((running_at_issue, running_at_return, (t1 - t0) * 1e3, (t2 - t1) * 1e3, wrong_first, wrong_second))
+    _DIRECTED["line2"] = (f"directed pair: encrypt_trlwe_dev({words} words) alone {first_ms:.2f} ms, {issue_alone_ms:.3f} ms to issue; per "
+                          f"round (first still running when the host decrypt was issued / when it returned, ms to issue, ms in "
+                          f"the host call, wrong words of the first / second result): "
+                          + "; ".join(f"{a}/{b} {x:.2f} {y:.2f} {u}/{v}" for a, b, x, y, u, v in rounds))
+    print(_DIRECTED["line2"])
+    for r, (at_issue, _, issue_ms, _, _, _) in enumerate(rounds):
+        assert at_issue and issue_ms < first_ms, \
+            f"round {r}: the first call ({first_ms:.2f} ms alone) had finished before the host call was issued " \
+            f"({issue_ms:.2f} ms after it): the pair did not overlap on this machine and shows nothing"
+    assert [(u, v) for *_, u, v in rounds] == [(0, 0)] * 4, _DIRECTED["line2"]
+
+
 @pytest.mark.parametrize("name", sorted(SF.SHAPES))
 def test_report(O, name):
     """What the shape's sequences reached (shown by pytest -rA)."""
@@ -275,6 +434,8 @@ def test_report(O, name):
     print("  forms: " + ", ".join(f"{k[5:]}: {c[k]}" for k in sorted(c) if k.startswith("form ")))
     print("  seconds per sequence (issue to the last synchronisation): " + ", ".join(f"{r[2]:.3f}" for r in rep))
     print(f"  seconds per sequence ({'model' if w.shape.exact else 'the same calls alone'}): " + ", ".join(f"{r[3]:.2f}" for r in rep))
-    if name == "SECURITY_UINT4" and "line" in _DIRECTED:
-        print("  " + _DIRECTED["line"])
+    if name == "SECURITY_UINT4":
+        for key in ("line", "line2"):
+            if key in _DIRECTED:
+                print("  " + _DIRECTED[key])
     assert sum(r[0] for r in rep) >= 6 * SF.STEPS

@@ -3,7 +3,7 @@ run holds every condition they rely on, the executor and the model agree on a fa
 evaluated at call time by the same SF.Model.eval that expected() uses, so this holds the executor's plumbing -- routing,
 chaining, tiling, key tracking, buffer use -- and NOT the model's own formulas, which only the GPU run at
 SECURITY_128_BIT holds to the device), and the comparison fails -- at exactly the clobbered steps -- on a stand-in
-that shares one key-switch scratch among its calls."""
+that shares one key-switch scratch among its calls, and on one that shares its buffer of staged secrets without a claim."""
 import numpy as np
 import pytest
 
@@ -11,7 +11,7 @@ import sequence_fuzz as SF
 
 N = 1024
 # a small shape in the exact-product regime (log2(2l) + 10 + (bgbit - 1) + 31 < 51): oracle bootstraps of a millisecond
-HOST = SF.Shape("SFUZZ_HOST", 16, SF.BASE_COUNTS, True, False)
+HOST = SF.Shape("SFUZZ_HOST", 16, SF.BASE_COUNTS, True, False, 2.0e-5, 2.0e-8)
 HOST_SEEDS = (0, 1, 2)
 
 
@@ -33,18 +33,51 @@ def test_corpus_condition(name):
     c = SF.sum_counts(SF.adjacency(s) for s in seqs)
     need = ["dev then host", "dev then dev on another stream", "dev then grow", "stage op under a running key switch",
             "key switch of 384 rows or more under a running key switch",
-            "V2 after E", "E after V2", "chained pack", "chained unpack", "chained bootstrap"]
+            "V2 after E", "E after V2", "chained pack", "chained unpack", "chained bootstrap",
+            "secret-staging call after a secret-staging dev call on another stream",
+            "secret-staging host call after a secret-staging dev call",
+            "secret-staging call on V2 after a secret-staging dev call on E",
+            "secret-staging call on E after a secret-staging dev call on V2",
+            "trlwe_matmul:ks under a running key switch", "key switch after a running trlwe_matmul:ks dev",
+            "pk_encrypt after a dev call on another stream", "pk_encrypt on V2 after key_change",
+            "unclaimed call between two claiming dev calls on other streams",
+            "chained tlwe_matmul", "chained polymul", "chained trlwe_matmul", "chained decrypt"]
     need += ["dev then " + op for op in SF.STATE_OPS] + ["state " + op for op in SF.STATE_OPS]
     need += ["op " + SF.variant_name(op, args) for op, args in SF.variants(shape)]
     need += ["form " + f for f in SF.FORMS] + ["route " + r for r in SF.ROUTES]
     short = {k: c.get(k, 0) for k in need if c.get(k, 0) < 3}
     assert not short, short
+    # every ordered pairing of an encrypting and a decrypting secret-staging call
+    kinds = [f"secret-staging {b} after {a}" for a in ("enc", "dec") for b in ("enc", "dec")]
+    assert all(c.get(k, 0) >= 1 for k in kinds), {k: c.get(k, 0) for k in kinds}
+    tables = {op: set() for op in SF.TABLE}
     for seq in seqs:
         for st in seq:
             if st.kind != "call":
                 continue
             assert st.form in SF.forms_of(st.op) and st.count >= 1
-            assert st.count in shape.counts or st.args.get("grow")
+            if st.op in SF.TABLE:  # the step's shape is one of the table (chain D's matrix takes four groups)
+                assert st.args["shape"] in SF.TABLE[st.op] or (st.args.get("chain") == "D" and st.args["shape"] == SF.CHAIN_D_MATMUL)
+                tables[st.op].add(st.args["shape"])
+            elif st.op == "encrypt_trlwe":  # plaintext words; the count is the groups
+                assert st.args["words"] in shape.counts or st.args.get("chain") == "D"
+                assert st.count == -(-st.args["words"] // N)
+            elif st.op == "expand_seeded_trlwe":
+                assert st.count in (1, 2)
+            elif st.op == "decrypt_trlwe":
+                assert st.count % N and len(st.ins[0][2]) == -(-st.count // N)
+            else:
+                assert st.count in shape.counts or st.args.get("grow") or st.args.get("chain") in ("C", "D")
+            if st.op == "pk_encrypt":
+                assert st.count <= 520
+            if st.op in ("encrypt", "encrypt_trlwe", "pk_encrypt"):  # real noise, and no sample two f64 forms may round apart
+                assert st.args["alpha"] == (shape.alpha_lv1 if st.op == "encrypt_trlwe" else shape.alpha_lv0) > 0
+                assert not SF.encrypt_border(st.op, st.args["rng_key"], st.args["first"], st.count, st.args["alpha"]).any(), st
+            if st.op in SF.NEW_FAMILIES:
+                assert st.handle != "VR"
+            for spec in st.ins:  # weights: int8 with both ends of the range
+                if spec is not None and spec[0] == "i8":
+                    assert spec[1].dtype == np.int8 and (spec[1].size == 1 or (spec[1].min(), spec[1].max()) == (-128, 127))
             for j in st.sources:  # a chained operand: an earlier _dev step on the same stream and handle
                 assert j < st.i and seq[j].dev and st.dev and seq[j].stream == st.stream and seq[j].handle == st.handle
             assert (st.op == "reencrypt") == (st.handle == "VR")
@@ -56,6 +89,9 @@ def test_corpus_condition(name):
             if st.kind == "state" and st.op == "key_change":
                 assert st.handle == "V2" and set(st.args["wait"]) == pending
                 pending = set()
+    assert all(tables[op] >= set(SF.TABLE[op]) for op in SF.TABLE), tables
+    firsts = {st.args["first"] >> 32 != 0 for seq in seqs for st in seq if st.kind == "call" and st.op in ("encrypt", "encrypt_trlwe")}
+    assert firsts == {False, True}  # first indices small and above 2^32
     counts = {st.count for seq in seqs for st in seq if st.kind == "call"}
     assert set(shape.counts) <= counts  # every count, on UINT4 both sides of ks_sl_chunk_min = 384
     # the grow steps rise from seed to seed by more than the quarter of headroom ensure() allocates: a context shared by
@@ -74,21 +110,54 @@ class _World:
     """What the stand-in handles of one run share: the model that evaluates their calls, the order of the calls, the
     log of key switches and the device outputs still to be read back."""
 
-    def __init__(self, model, n, racy):
-        self.model, self.n, self.racy = model, n, racy
+    def __init__(self, model, n, racy, secrets=None):
+        self.model, self.n, self.racy = model, n, racy  # racy: False, "key_switch" or "secret"
+        self.secrets = secrets or {}
         self.order = 0
         self.key_switches = []  # (order, rows, words [rows][n+1])
         self.dev_outs = []  # (order, rows, FakeTensor)
+        self.log = []  # every _dev call, in order: what read_back needs to evaluate it again
+        self.pending = []  # the secret-staging _dev calls no synchronisation has drained yet
+
+    def secret_name(self, key):
+        """The handle whose secret key a call was given (key_lv0 or key_lv1)"""
+        for name in ("E", "V2"):
+            sk = self.secrets[name]
+            if any(len(k) == len(key) and np.array_equal(k, key) for k in (sk.key_lv0, sk.key_lv1)):
+                return name
+        raise AssertionError("a key of no handle")
+
+    def staged(self, entry, secret, dev):
+        """A secret-staging call.  The racy device has ONE buffer of staged secrets and no claim on it: the kernels of
+        the _dev calls still pending read what the last call before the next synchronisation staged."""
+        for e in self.pending:
+            e["wrong"] = secret
+        if dev:
+            self.pending.append(entry)
+
+    def synchronized(self, stream="all"):
+        self.pending = [e for e in self.pending if stream != "all" and e["stream"] != stream]
 
     def read_back(self):
-        """The racy device: every _dev result that went through the key switch's scratch reads as the most recent key
-        switch of at least its size."""
-        if not self.racy:
-            return
-        for order, rows, t in self.dev_outs:
-            donor = [k for k in self.key_switches if k[1] >= rows][-1]
-            if donor[0] != order:
-                t.arr[...] = donor[2][:rows].reshape(t.arr.shape)
+        """The racy devices.  "key_switch": every _dev result that went through the key switch's scratch reads as the
+        most recent key switch of at least its size.  "secret": every pending secret-staging _dev call ran under the key
+        staged last, and what was chained from it follows."""
+        self.synchronized()
+        if self.racy == "key_switch":
+            for order, rows, t in self.dev_outs:
+                donor = [k for k in self.key_switches if k[1] >= rows][-1]
+                if donor[0] != order:
+                    t.arr[...] = donor[2][:rows].reshape(t.arr.shape)
+        if self.racy == "secret":
+            dirty = set()
+            for e in self.log:
+                wrong = e["wrong"] not in (None, e["secret"])
+                if not wrong and not any(isinstance(o, SF.FakeTensor) and id(o.root) in dirty for o in e["operands"]):
+                    continue
+                x = [o.arr if isinstance(o, SF.FakeTensor) else o for o in e["operands"]]
+                got = self.model.eval(e["key"], e["name"], e["op"], e["args"], e["count"], x, e["wrong"] if wrong else e["secret"])
+                e["write"](np.ascontiguousarray(got, dtype=np.uint32))
+                dirty |= {id(o.root) for o in e["outs"]}
 
 
 class StandIn:
@@ -99,20 +168,37 @@ class StandIn:
         self.world, self.name, self.params, self.key = world, name, params, key
         self.calls = []
 
-    def _do(self, op, args, operands, out=None, count=None, form="host"):
+    def _do(self, op, args, operands, out=None, count=None, form="host", aux=None, secret=None, stream=None):
         w = self.world
         x = [o.arr if isinstance(o, SF.FakeTensor) else o for o in operands]
         count = len(x[0]) if count is None else count
-        got = np.ascontiguousarray(w.model.eval(self.key, self.name, op, args, count, x), dtype=np.uint32)
+        got = np.ascontiguousarray(w.model.eval(self.key, self.name, op, args, count, x, secret), dtype=np.uint32)
         w.order += 1
         rows = SF.Step("call", self.name, op, form, count, args=args).ks_rows
         if rows:
             w.key_switches.append((w.order, rows, got.reshape(-1, w.n + 1).copy()))
         self.calls.append(op)
-        if out is None:
+        outs = [o for o in (out, aux) if o is not None]
+
+        def write(words):
+            if len(outs) == 2:  # full and bodies of one encrypting call, side by side in the model's words
+                words = words.reshape(len(words), -1)
+                split = outs[0].arr.size // len(words)
+                outs[0].arr[...] = words[:, :split].reshape(outs[0].arr.shape)
+                outs[1].arr[...] = words[:, split:].reshape(outs[1].arr.shape)
+            else:
+                outs[0].arr[...] = words.reshape(outs[0].arr.shape)
+
+        entry = {"name": self.name, "key": self.key, "op": op, "args": args, "count": count, "operands": operands, "outs": outs,
+                 "secret": secret, "wrong": None, "stream": stream, "write": write}
+        if op in SF.SECRET_OPS:
+            w.staged(entry, secret, bool(outs))
+        if not outs:
             return got
-        assert isinstance(out, SF.FakeTensor) and (out.arr == SF.FILL).all(), "an output buffer was used twice"
-        out.arr[...] = got.reshape(out.arr.shape)
+        for o in outs:
+            assert isinstance(o, SF.FakeTensor) and (o.arr == SF.FILL).all(), "an output buffer was used twice"
+        write(got)
+        w.log.append(entry)
         if rows:
             w.dev_outs.append((w.order, rows, out))
 
@@ -229,6 +315,116 @@ class StandIn:
     def expand_seeded_dev(self, mask_seed, first_index, bodies, out, stream=None):
         self._do("expand_seeded", {"seed": mask_seed, "first": first_index}, [bodies], out, form="dev0")
 
+    # -- encryption, decryption and the linear layers: host forms (stream=None) and device forms (out=...)
+    class _Bodies:
+        def __init__(self, bodies):
+            self.bodies = bodies
+
+    def _encrypt(self, op, key, plain, alpha, rng_key, mask_seed, first, full, bodies, out=None, aux=None, stream=None):
+        kind = "both" if full and bodies else "full" if full else "bodies"
+        n_plain = len(plain.arr if isinstance(plain, SF.FakeTensor) else plain)
+        args = {"out": kind, "alpha": alpha, "rng_key": rng_key, "mask_seed": mask_seed, "first": first}
+        count = n_plain
+        if op == "encrypt_trlwe":
+            args["words"], count = n_plain, -(-n_plain // N)
+        got = self._do(op, args, [plain], out, count, "host" if out is None else "dev0", aux, self.world.secret_name(key), stream)
+        if out is not None:
+            return None
+        if kind == "full":
+            return got
+        got = got.reshape(count, -1)
+        width = N if op == "encrypt_trlwe" else 1
+        bod = got[:, -width:].reshape(-1) if width == 1 else got[:, -width:]
+        if kind == "bodies":
+            return self._Bodies(bod)
+        return got[:, :-width].reshape((count, 2, N) if width == N else (count, -1)), self._Bodies(bod)
+
+    def batch_encrypt(self, key_lv0, plain, alpha=None, rng_key=None, mask_seed=None, first_index=0, full=True, bodies=False):
+        return self._encrypt("encrypt", key_lv0, plain, alpha, rng_key, mask_seed, first_index, full, bodies)
+
+    def batch_encrypt_dev(self, key_lv0, plain, alpha, mask_seed, rng_key=None, first_index=0, bodies=None, out=None, stream=None):
+        first, second = (out, bodies) if out is not None else (bodies, None)
+        self._encrypt("encrypt", key_lv0, plain, alpha, rng_key, mask_seed, first_index, out is not None, bodies is not None,
+                      first, second, stream)
+
+    def batch_encrypt_trlwe(self, key_lv1, plain, alpha=None, rng_key=None, mask_seed=None, first_group=0, full=True, bodies=False):
+        return self._encrypt("encrypt_trlwe", key_lv1, plain, alpha, rng_key, mask_seed, first_group, full, bodies)
+
+    def batch_encrypt_trlwe_dev(self, key_lv1, plain, alpha, mask_seed, rng_key=None, first_group=0, bodies=None, out=None,
+                                stream=None):
+        first, second = (out, bodies) if out is not None else (bodies, None)
+        self._encrypt("encrypt_trlwe", key_lv1, plain, alpha, rng_key, mask_seed, first_group, out is not None, bodies is not None,
+                      first, second, stream)
+
+    def expand_seeded_trlwe(self, seeded):
+        return self._do("expand_seeded_trlwe", {"seed": seeded.mask_seed, "first": seeded.first_group}, [seeded.bodies])
+
+    def expand_seeded_trlwe_dev(self, mask_seed, first_group, bodies, out, stream=None):
+        self._do("expand_seeded_trlwe", {"seed": mask_seed, "first": first_group}, [bodies], out, form="dev0")
+
+    def batch_pk_encrypt(self, plain, alpha, rng_key=None, first_index=0):
+        return self._do("pk_encrypt", {"alpha": alpha, "rng_key": rng_key, "first": first_index}, [plain])
+
+    def batch_pk_encrypt_dev(self, plain, out, alpha, rng_key=None, first_index=0, stream=None):
+        self._do("pk_encrypt", {"alpha": alpha, "rng_key": rng_key, "first": first_index}, [plain], out, form="dev0")
+
+    def _mode(self, mode, modulus):
+        assert (modulus == SF.MESSAGE_MODULUS) == (mode == "message")
+        return mode
+
+    def batch_decrypt(self, key, cts, mode="phase", modulus=None, out=None, stream=None):
+        width = "lv0" if len(key) == self.params.n else "lv1"
+        return self._do("decrypt", {"mode": self._mode(mode, modulus), "width": width}, [cts], out,
+                        form="host" if out is None else "dev0", secret=self.world.secret_name(key), stream=stream)
+
+    def batch_decrypt_dev(self, key, cts, out, mode="phase", modulus=None, stream=None):
+        self.batch_decrypt(key, cts, mode, modulus, out, stream)
+
+    def batch_decrypt_trlwe(self, key_lv1, packed, count, mode="phase", modulus=None, out=None, stream=None):
+        return self._do("decrypt_trlwe", {"mode": self._mode(mode, modulus)}, [packed], out, count,
+                        "host" if out is None else "dev0", secret=self.world.secret_name(key_lv1), stream=stream)
+
+    def batch_decrypt_trlwe_dev(self, key_lv1, packed, count, out, mode="phase", modulus=None, stream=None):
+        self.batch_decrypt_trlwe(key_lv1, packed, count, mode, modulus, out, stream)
+
+    @staticmethod
+    def _shape(t):
+        return (t.arr if isinstance(t, SF.FakeTensor) else np.asarray(t)).shape
+
+    def batch_tlwe_matmul(self, w, cts, bias=None, out=None):
+        (rows, cols), groups = self._shape(w), self._shape(cts)[0]
+        return self._do("tlwe_matmul", {"bias": bias is not None, "shape": (rows, cols, groups)}, [w, cts, bias], out, groups * rows,
+                        "host" if out is None else "dev0")
+
+    def batch_tlwe_matmul_dev(self, w, cts, out, bias=None, stream=None):
+        self.batch_tlwe_matmul(w, cts, bias, out)
+
+    def batch_trlwe_matmul(self, w, trlwe, bias=None, keyswitch=True, out=None):
+        (rows, cols), groups = self._shape(w), self._shape(trlwe)[0]
+        return self._do("trlwe_matmul", {"ks": keyswitch, "bias": bias is not None, "shape": (rows, cols, groups)}, [w, trlwe, bias],
+                        out, groups * rows, "host" if out is None else "dev0")
+
+    def batch_trlwe_matmul_dev(self, w, trlwe, out, bias=None, keyswitch=True, stream=None):
+        self.batch_trlwe_matmul(w, trlwe, bias, keyswitch, out)
+
+    def batch_trlwe_polymul(self, w, trlwe, bias=None, out=None):
+        (rows, cols, _), groups = self._shape(w), self._shape(trlwe)[0]
+        return self._do("polymul", {"bias": bias is not None, "shape": (rows, cols, groups)}, [w, trlwe, bias], out, groups * rows,
+                        "host" if out is None else "dev0")
+
+    def batch_trlwe_polymul_dev(self, w, trlwe, out, bias=None, stream=None):
+        self.batch_trlwe_polymul(w, trlwe, bias, out)
+
+    def batch_tlwe_conv2d(self, w, cts, bias=None, stride=1, padding=0, out=None):
+        (out_c, k, _, in_c), (groups, in_h, in_w, _, _) = self._shape(w), self._shape(cts)
+        shape = (in_h, in_w, in_c, k, out_c, tuple(stride), tuple(padding), groups)
+        count = groups * out_c * ((in_h + 2 * padding[0] - k) // stride[0] + 1) * ((in_w + 2 * padding[1] - k) // stride[1] + 1)
+        return self._do("conv2d", {"bias": bias is not None, "shape": shape}, [w, cts, bias], out, count,
+                        "host" if out is None else "dev0")
+
+    def batch_tlwe_conv2d_dev(self, w, cts, out, bias=None, stride=1, padding=0, stream=None):
+        self.batch_tlwe_conv2d(w, cts, bias, stride, padding, out)
+
     # -- state
     def load_cloud_key(self, tag):
         self.key = tag.name
@@ -251,13 +447,14 @@ class StandIn:
         self.calls.append("set_combining")
 
     def synchronize(self):
-        pass
+        self.world.synchronized()
 
 
 @pytest.fixture(scope="module")
 def host_keys(O):
     """The keys of the small shape: five cloud keys (K1 of the engine; two of each of K2 and K3, one per way a key
-    change can bring them), a packing key per handle, a re-encryption key, and the secret keys the pools encrypt under."""
+    change can bring them), a packing key per handle, a re-encryption key, the secret keys the pools encrypt under (and
+    the encrypting and decrypting steps name), and a public key of SF.PK_SIZE rows per handle."""
     from rs_tfhe_amd import packing as PK
     from rs_tfhe_amd.client import SecretKey
     from rs_tfhe_amd.params import SecurityParams
@@ -272,18 +469,23 @@ def host_keys(O):
     for h, k in (("E", "K1"), ("V2", "K2")):
         pk = SecretKey(pp, sk[k].key_lv0, sk[k].key_lv1).packing_key(rng_key=90 + len(packing))
         packing[h] = (pk, PK.key_rows(pp, pk.mask_seed, pk.bodies))
-    keys = {"params": pp, "oracle_params": op, "cloud": cloud, "packing": packing,
+    import sym_encrypt_model as SM
+
+    client = {h: SecretKey(pp, sk[k].key_lv0, sk[k].key_lv1) for h, k in (("E", "K1"), ("V2", "K2"))}
+    public = {h: SM.public_key(c.key_lv0, SF.PK_SIZE, pp.alpha_lv0, SF.PK_GEN_KEY)[0] for h, c in client.items()}
+    keys = {"params": pp, "oracle_params": op, "cloud": cloud, "packing": packing, "secrets": client, "public": public,
             "reenc": O.gen_reenc_key(op, sk["K1"].key_lv0, 95, key_to=sk["K3"].key_lv0)}
     secrets = {"E": sk["K1"], "V2": sk["K2"], "VR": sk["K1"]}
     return keys, secrets
 
 
 def _stand_ins(model, keys, racy):
-    world = _World(model, keys["params"].n, racy)
+    world = _World(model, keys["params"].n, racy, keys["secrets"])
     book = {name: {"full": _Tag(name), "comp": _Tag(name), "gen": (_Tag(name), None, 0)} for name in keys["cloud"]}
     handles = {"E": StandIn(world, "E", keys["params"], "K1"), "V2": StandIn(world, "V2", keys["params"], "K2/gen"),
                "VR": StandIn(world, "VR", keys["params"], "reenc"), "book": book,
-               "packing": {h: pk for h, (pk, _) in keys["packing"].items()}, "combining_default": 256}
+               "packing": {h: pk for h, (pk, _) in keys["packing"].items()}, "combining_default": 256,
+               "secrets": keys["secrets"]}
     return world, handles
 
 
@@ -293,7 +495,7 @@ def test_harness_and_model_agree_on_a_faithful_stand_in(O, host_keys, seed):
     seq = SF.random_sequence(seed, HOST)
     pools = SF.make_pools(HOST, seed, secrets)
     world, handles = _stand_ins(SF.Model(O, keys), keys, racy=False)
-    be = SF.FakeBackend(world.read_back)
+    be = SF.FakeBackend(world.read_back, world.synchronized)
     got, info = SF.run(seq, handles, be.streams(), pools, be)
     model = SF.Model(O, keys)
     want = SF.expected(seq, O, keys, pools, model)
@@ -319,8 +521,8 @@ def test_comparison_fails_at_exactly_the_clobbered_steps(O, host_keys, seed):
     seq = SF.random_sequence(seed, HOST)
     pools = SF.make_pools(HOST, seed, secrets)
     model = SF.Model(O, keys)
-    world, handles = _stand_ins(model, keys, racy=True)
-    be = SF.FakeBackend(world.read_back)
+    world, handles = _stand_ins(model, keys, racy="key_switch")
+    be = SF.FakeBackend(world.read_back, world.synchronized)
     got, _ = SF.run(seq, handles, be.streams(), pools, be)
     want = SF.expected(seq, O, keys, pools, model)
     n = keys["params"].n
@@ -335,8 +537,46 @@ def test_comparison_fails_at_exactly_the_clobbered_steps(O, host_keys, seed):
     assert SF.compare(got, want) == clobbered
 
 
+@pytest.mark.parametrize("seed", HOST_SEEDS)
+def test_comparison_fails_at_exactly_the_steps_of_an_unclaimed_secret(O, host_keys, seed):
+    """A device whose one buffer of staged secrets is shared without a claim: a secret-staging _dev step that another
+    secret-staging call follows before the next synchronisation runs under the later call's key.  The comparison
+    reports those steps and what is chained from them, and no other.  The steps are read off the sequence
+    (SF.unclaimed_secret_steps), their words off the model under the other handle's key; a step whose words the other
+    key does not change (a one-row boolean, say) is no failure."""
+    keys, secrets = host_keys
+    seq = SF.random_sequence(seed, HOST)
+    pools = SF.make_pools(HOST, seed, secrets)
+    model = SF.Model(O, keys)
+    world, handles = _stand_ins(model, keys, racy="secret")
+    be = SF.FakeBackend(world.read_back, world.synchronized)
+    got, _ = SF.run(seq, handles, be.streams(), pools, be)
+    want = SF.expected(seq, O, keys, pools, model)
+    wrong_key = SF.unclaimed_secret_steps(seq)
+    for i, h in wrong_key.items():
+        assert seq[i].dev and seq[i].op in SF.SECRET_OPS and h != seq[i].handle and h in ("E", "V2")
+        later = [st for st in seq[i + 1:] if st.kind == "call" and st.op in SF.SECRET_OPS and st.handle == h]
+        assert later and not any(st.kind == "state" and st.op == "synchronize" for st in seq[i + 1:later[0].i])
+    assert len(wrong_key) >= 3  # (every sequence carries two pairs made for this, and chains C and D)
+    raced = SF.expected(seq, O, keys, pools, model, secret_of=wrong_key)
+    predicted = [i for i in sorted(want) if not np.array_equal(want[i], raced[i])]
+    cones = set().union(*(SF.cone(seq, i) for i in wrong_key))
+    assert set(predicted) <= cones
+    # a phase or a ciphertext never survives another key (but a chain whose head was encrypted under the other key too
+    # decrypts to the right phases again under it)
+    sure = [i for i in wrong_key if seq[i].args.get("mode", "phase") == "phase" and not seq[i].sources]
+    assert len(sure) >= 2 and set(sure) <= set(predicted)
+    assert SF.compare(got, want) == predicted, SF.describe(seq, SF.compare(got, want), got, want)
+    # the same device with every call made alone (a synchronisation after each) is right
+    world2, handles2 = _stand_ins(model, keys, racy="secret")
+    be2 = SF.FakeBackend(world2.read_back, world2.synchronized)
+    alone, _ = SF.run(SF.as_host(seq), handles2, be2.streams(), pools, be2)
+    assert SF.compare(alone, want) == []
+
+
 def test_comparison_sees_one_wrong_step_on_the_stand_in(O, host_keys):
-    """One operand of the head of a chain perturbed in the model only: that step and the steps chained from it."""
+    """One operand of the head of a chain (A: gate -> pack -> unpack; C: encrypt -> tlwe_matmul -> decrypt) perturbed
+    in the model only: that step and the steps chained from it."""
     keys, secrets = host_keys
     seq = SF.random_sequence(0, HOST)
     pools = SF.make_pools(HOST, 0, secrets)
@@ -344,6 +584,7 @@ def test_comparison_sees_one_wrong_step_on_the_stand_in(O, host_keys):
     world, handles = _stand_ins(model, keys, racy=False)
     be = SF.FakeBackend()
     got, _ = SF.run(seq, handles, be.streams(), pools, be)
-    head = next(st.i for st in seq if st.kind == "call" and st.op == "gate" and len(SF.cone(seq, st.i)) == 3)
-    wrong = SF.expected(seq, O, keys, pools, model, perturb=head)
-    assert SF.compare(got, wrong) == sorted(SF.cone(seq, head))
+    for head_op in ("gate", "encrypt"):
+        head = next(st.i for st in seq if st.kind == "call" and st.op == head_op and len(SF.cone(seq, st.i)) == 3)
+        wrong = SF.expected(seq, O, keys, pools, model, perturb=head)
+        assert SF.compare(got, wrong) == sorted(SF.cone(seq, head)), head_op
