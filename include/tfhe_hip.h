@@ -168,7 +168,7 @@ int tfhe_hip_load_cloud_key(tfhe_hip_ctx *ctx, const double *bsk, const uint32_t
  *   tfhe_hip_gen_cloud_key           TEST / BENCHMARK ONLY: a 64-bit seed is expanded into the generator key,
  *                                    which makes the cloud key reproducible bit for bit and exactly as
  *                                    guessable as the seed.  Never publish a key generated this way.
- * The secret-key staging buffers on the device are zeroed before any of the three returns. */
+ * What the device holds of the secret keys and of the generator key is zeroed before any of the three returns. */
 int tfhe_hip_gen_cloud_key_secure(tfhe_hip_ctx *ctx, const uint32_t *key_lv0, const uint32_t *key_lv1,
                                   double alpha_ksk, double alpha_bsk);
 int tfhe_hip_gen_cloud_key_with_key(tfhe_hip_ctx *ctx, const uint32_t *key_lv0, const uint32_t *key_lv1,
@@ -713,7 +713,8 @@ int tfhe_hip_batch_reencrypt_dev(tfhe_hip_ctx *ctx, const uint32_t *in, uint32_t
  * difference of the plaintexts in the clear.  With a caller-held K, first_index must move past every row already used.
  * (2) Whoever knows K can strip the mask: the selectors are a function of (K, g) and E is public.  Hence rng_key == NULL
  * means "draw K from getrandom(2) for this call", and a caller-held K is as secret as the plaintexts.  The library
- * zeroes the selectors on the device behind each pass; K travels to the kernels as a launch argument.
+ * zeroes the selectors on the device behind each pass; K travels to the kernels as a launch argument.  The host form's
+ * staged plaintexts are zeroed before it returns (rule (5) of the symmetric section).
  * Away from noise samples that sit within rounding of a torus step every implementation of this section gives the same
  * words.
  * Out of scope: pool forms.  (The public key itself and the symmetric re-encryption key are made on the device by the
@@ -780,7 +781,10 @@ int tfhe_hip_get_pk_encrypt_times(tfhe_hip_ctx *ctx, tfhe_hip_pk_encrypt_times *
  * (3) rng_key == NULL draws K from getrandom(2) per call; a caller-held K is as secret as the secret key: whoever can
  * regenerate the noise reads the key off the rows.  (4) The staged secret keys and K's device copy are zeroed before a
  * host-form call returns, as tfhe_hip_gen_cloud_key* does; the _dev form, which only enqueues, queues the zeroing on
- * `stream` behind its kernel.
+ * `stream` behind its kernel, also where the call fails.  The library's host copies are wiped.  (5) Every host form
+ * of this header that stages plaintexts or returns decrypted words -- this section's, public-key and packed
+ * encryption, decryption -- zeroes them in its staging buffer before it returns: the device buffer and, on pool
+ * members, its pinned host arena.
  * Away from noise samples that sit within rounding of a torus step every implementation of this section gives the same
  * words.
  * Out of scope: pool forms. */
@@ -827,9 +831,9 @@ int tfhe_hip_gen_reenc_key_symmetric(tfhe_hip_ctx *ctx_or_view, const uint32_t *
  * three, a modulus outside [2, 65,536] in MESSAGE mode, count > 0x7FFFFFFF, count > groups * N.  count == 0 returns
  * TFHE_HIP_OK and touches nothing.  Needs no key on the handle; every parameter set.
  * Security.  The key is host memory in both forms.  What the device holds of it is zeroed behind the kernel on the
- * call's stream, and the library's host copy is wiped; a host-form call also zeroes the staging buffers that held the
- * phases or messages (the device buffer and, on pool members, its pinned host arena) before it returns.  _dev: in / trlwe / out are device pointers, queued on `stream` (NULL: the
- * context's stream); the decrypted words are then the caller's to guard.
+ * call's stream, and the library's host copy is wiped; a host-form call also zeroes the staging buffer that held the
+ * phases or messages before it returns (rule (5) of the symmetric section).  _dev: in / trlwe / out are device
+ * pointers, queued on `stream` (NULL: the context's stream); the decrypted words are then the caller's to guard.
  * Out of scope: pool forms, slot lists for the packed form. */
 enum { TFHE_HIP_DECRYPT_PHASE = 0, TFHE_HIP_DECRYPT_BOOL = 1, TFHE_HIP_DECRYPT_MESSAGE = 2 };
 int tfhe_hip_batch_decrypt(tfhe_hip_ctx *ctx, const uint32_t *key, size_t key_len, const uint32_t *in, size_t count,
@@ -868,10 +872,9 @@ int tfhe_hip_batch_decrypt_trlwe_dev(tfhe_hip_ctx *ctx, const uint32_t *key_lv1,
  *   construction what the bodies-only output of the encrypting call returns; tfhe_hip_expand_seeded_trlwe expands it
  *   to the words the full form writes.
  * Security: the rules of the symmetric section.  A (K, g) pair is used once, whatever S is; an (S, g) pair is used
- * once; rng_key == NULL draws K from getrandom(2) per call; a caller-held K is as secret as the secret key.  K, s1,
- * the spectrum of s1 (which is secret too) and, in the host form, the staged plaintexts are zeroed on the device before
- * a host-form call returns; the _dev form queues the zeroing on `stream` behind its kernel.  The library's host copies
- * are wiped.
+ * once; rng_key == NULL draws K from getrandom(2) per call; a caller-held K is as secret as the secret key.  K, s1
+ * and the spectrum of s1 (which is secret too) are staged and zeroed as rule (4) there says, the host form's plaintexts
+ * as rule (5).
  * Away from noise samples that sit within rounding of a torus step every implementation of this section gives the same
  * words.
  * Out of scope: pool forms. */

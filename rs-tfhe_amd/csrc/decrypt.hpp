@@ -22,8 +22,8 @@
 //                   only the first count - g N coefficients are decoded and stored (the sums run for all four of a
 //                   thread's coefficients: 1 M adds a group either way).
 //
-// Secrets travel as in sym_encrypt.hpp: the packed key bits (or the index list) go through the context's `sym_sec`
-// buffer, the host copy is wiped, and the buffer is zeroed behind the kernel on the same stream.
+// Secrets travel as in sym_encrypt.hpp: the packed key bits (or the index list) go through a SecretStage (secrets.hpp)
+// over the context's `sym_sec` buffer: the host copy is wiped, the buffer zeroed behind the kernel on the same stream.
 #pragma once
 #include "decrypt_decode.hpp"
 #include "sym_encrypt.hpp"
@@ -90,19 +90,6 @@ __global__ __launch_bounds__(256) void k_trlwe_phase(const uint32_t *__restrict_
   }
 }
 
-// `words` secret words into the context's sym_sec buffer (the copy has landed when this returns); h is wiped
-int dec_stage(tfhe_hip_ctx *ctx, uint32_t *h, size_t words, hipStream_t s) {
-  int rc = ensure(ctx, ctx->sym_sec, words * 4);
-  if (rc == TFHE_HIP_OK) {
-    hipError_t e = hipMemcpyAsync(ctx->sym_sec.p, h, words * 4, hipMemcpyHostToDevice, s);
-    if (e == hipSuccess) e = hipStreamSynchronize(s);
-    if (e != hipSuccess) rc = fail(ctx, TFHE_HIP_EHIP, std::string("decryption: ") + hipGetErrorString(e));
-  }
-  volatile uint32_t *wipe = h;
-  for (size_t i = 0; i < words; ++i) wipe[i] = 0;
-  return rc;
-}
-
 // the checks both forms share, in sym_refusal's style: why the call is TFHE_HIP_EINVAL, or nullptr
 const char *dec_refusal(const uint32_t *key, size_t key_len, const uint32_t *in, size_t count, size_t capacity, int mode,
                         uint32_t modulus, const uint32_t *out) {
@@ -120,60 +107,41 @@ const char *dec_refusal(const uint32_t *key, size_t key_len, const uint32_t *in,
 // on stream s: stage, launch, wipe.  in / out are device pointers, key a host pointer.
 int dec_lwe(tfhe_hip_ctx *ctx, const uint32_t *key, size_t key_len, const uint32_t *in, size_t count, int mode, uint32_t modulus,
             uint32_t *out, hipStream_t s) {
-  CHK(claim_scratch(ctx, s));  // sym_sec belongs to the context
-  uint32_t h[kDecKeyWords] = {};
+  SecretStage sec(ctx, ctx->sym_sec, s, kDecKeyWords * 4);
+  uint32_t *h = (uint32_t *)sec.host(0);  // (zero so far)
   for (size_t x = 0; x < key_len; ++x)
     if (key[x]) h[x & 63] |= 1u << (x >> 6);
-  int rc = dec_stage(ctx, h, kDecKeyWords, s);
+  int rc = sec.land("decryption: ");
   if (rc == TFHE_HIP_OK) {
     const size_t want = (count + kDecWaves - 1) / kDecWaves, cap = (size_t)(ctx->num_cus > 0 ? ctx->num_cus : 1) * kDecBlocksPerCu;
     const dim3 grid((unsigned)(want < cap ? want : cap)), block(64 * kDecWaves);
-    const uint32_t *bits = (const uint32_t *)ctx->sym_sec.p;
-    hipLaunchKernelGGL(k_lwe_phase, grid, block, 0, s, in, bits, (int)key_len, count, mode, modulus, out);
+    hipLaunchKernelGGL(k_lwe_phase, grid, block, 0, s, in, sec.dev(0), (int)key_len, count, mode, modulus, out);
     rc = launched(ctx);
   }
-  const int rc_wipe = sym_wipe(ctx, s);
-  return rc != TFHE_HIP_OK ? rc : rc_wipe;
+  return sec.finish(rc);
 }
 
 int dec_trlwe(tfhe_hip_ctx *ctx, const uint32_t *key_lv1, const uint32_t *trlwe, size_t count, int mode, uint32_t modulus,
               uint32_t *out, hipStream_t s) {
-  CHK(claim_scratch(ctx, s));
-  uint32_t h[1 + kN];
+  SecretStage sec(ctx, ctx->sym_sec, s, (1 + (size_t)kN) * 4);
+  uint32_t *h = (uint32_t *)sec.host(0);  // (zero so far: the words past the last index stay so)
   uint32_t set = 0;
   for (uint32_t j = 0; j < (uint32_t)kN; ++j)
     if (key_lv1[j]) h[1 + set++] = j;
-  for (uint32_t q = set; q < (uint32_t)kN; ++q) h[1 + q] = 0;
   h[0] = set;
-  int rc = dec_stage(ctx, h, 1 + kN, s);
+  int rc = sec.land("decryption: ");
   if (rc == TFHE_HIP_OK) {
     const size_t groups = (count + kN - 1) / kN;  // groups past the last result are not touched
-    hipLaunchKernelGGL(k_trlwe_phase, dim3((unsigned)groups), dim3(256), 0, s, trlwe, (const uint32_t *)ctx->sym_sec.p, count,
-                       mode, modulus, out);
+    hipLaunchKernelGGL(k_trlwe_phase, dim3((unsigned)groups), dim3(256), 0, s, trlwe, sec.dev(0), count, mode, modulus, out);
     rc = launched(ctx);
   }
-  const int rc_wipe = sym_wipe(ctx, s);
-  return rc != TFHE_HIP_OK ? rc : rc_wipe;
+  return sec.finish(rc);
 }
 
 bool dec_key_len_ok(const tfhe_hip_ctx *ctx, size_t key_len) { return key_len == (size_t)ctx->P.n || key_len == (size_t)kN; }
 
 // the slots of `groups` packed ciphertexts (saturating: any count the checks let through fits)
 size_t dec_slots(size_t groups) { return groups > SIZE_MAX / (size_t)kN ? SIZE_MAX : groups * (size_t)kN; }
-
-// a host form's epilogue: neither the secrets nor the decrypted words stay behind in the library's buffers -- the
-// device staging buffer and, where the result went through it (pool members), its pinned arena (best effort: the
-// call's status is rc)
-void dec_scrub(tfhe_hip_ctx *ctx, size_t count) {
-  (void)sym_wipe(ctx, ctx->stream);
-  if (ctx->out.dev.p && ctx->out.dev.cap >= count * 4) (void)hipMemsetAsync(ctx->out.dev.p, 0, count * 4, ctx->stream);
-  (void)hipStreamSynchronize(ctx->stream);
-  if (ctx->out.pin.p) {
-    volatile uint32_t *wipe = (volatile uint32_t *)ctx->out.pin.p;
-    const size_t words = ctx->out.pin.cap / 4 < count ? ctx->out.pin.cap / 4 : count;
-    for (size_t i = 0; i < words; ++i) wipe[i] = 0;
-  }
-}
 }  // namespace
 
 int tfhe_hip_batch_decrypt(tfhe_hip_ctx *ctx, const uint32_t *key, size_t key_len, const uint32_t *in, size_t count, int mode,
@@ -186,7 +154,7 @@ int tfhe_hip_batch_decrypt(tfhe_hip_ctx *ctx, const uint32_t *key, size_t key_le
   const int rc = host_call(ctx, false, {{in, count * (key_len + 1) * 4, &ctx->a}}, out, count * 4, [&](const void *const *d, void *o) {
     return dec_lwe(ctx, key, key_len, u32(d[0]), count, mode, modulus, (uint32_t *)o, ctx->stream);
   });
-  dec_scrub(ctx, count);
+  scrub(ctx->stream, {{&ctx->out, count * 4}});  // the decrypted words do not stay behind in the library's buffers
   return rc;
 }
 
@@ -211,7 +179,7 @@ int tfhe_hip_batch_decrypt_trlwe(tfhe_hip_ctx *ctx, const uint32_t *key_lv1, con
   const int rc = host_call(ctx, false, {{trlwe, trlwe_bytes(used), &ctx->a}}, out, count * 4, [&](const void *const *d, void *o) {
     return dec_trlwe(ctx, key_lv1, u32(d[0]), count, mode, modulus, (uint32_t *)o, ctx->stream);
   });
-  dec_scrub(ctx, count);
+  scrub(ctx->stream, {{&ctx->out, count * 4}});  // the decrypted words do not stay behind in the library's buffers
   return rc;
 }
 

@@ -162,51 +162,43 @@ struct GeneratorKey {
     }
     return TFHE_HIP_OK;
   }
-  ~GeneratorKey() {
-    volatile uint32_t *wipe = k.k;
-    for (int i = 0; i < 8; ++i) wipe[i] = 0;
-  }
+  ~GeneratorKey() { wipe_host(k.k, sizeof(k.k)); }
 };
 
 // ---- key generation: the secrets on the device -----------------------------------------------------------------------
 // The secret keys, the spectrum of the ring key and the generator key do not outlive the call on the device,
-// whichever way it ends: the guard zeroes the four staging buffers and drains the stream on every exit path
-// (an early return would otherwise leave them in buffers that later batches reuse as plain staging space, and
-// could return while an asynchronous copy still reads the caller's frame).
-struct Wipe {
-  tfhe_hip_ctx *c;
-  ~Wipe() {
-    for (DevBuf *b : {&c->a.dev, &c->b.dev, &c->c.dev, &c->idx.dev})
-      if (b->p) (void)hipMemsetAsync(b->p, 0, b->cap < 65536 ? b->cap : 65536, c->stream);
-    (void)hipStreamSynchronize(c->stream);
-  }
-};
+// whichever way it ends: they travel through one SecretStage (secrets.hpp) on the context's stream, which zeroes the
+// buffer and drains the stream on every exit path.  The generator key travels in the buffer too (not in
+// kernel-argument memory).  The layout: K, the slot derive_public_seed writes, key_lv0 [n], key_lv1 [N], and the
+// spectrum of key_lv1, which k_key_spectrum writes (16-byte aligned: it is read as double2).
 struct StagedSecrets {
-  Wipe wipe;                    // first: in place before anything secret is staged
-  const uint32_t *d_k0, *d_k1;  // key_lv0 [n] in a, key_lv1 [N] in b
-  const double2 *d_spec;        // the spectrum of key_lv1 in c
-  ChaChaKey *d_rk;              // the generator key at idx[0, 32); idx holds `idx_bytes`
+  SecretStage stage;
+  const uint32_t *d_k0 = nullptr, *d_k1 = nullptr;
+  const double2 *d_spec = nullptr;
+  ChaChaKey *d_rk = nullptr;  // the derived-seed slot is d_rk + 1
+  explicit StagedSecrets(tfhe_hip_ctx *ctx)
+      : stage(ctx, ctx->sym_sec, ctx->stream, 2 * sizeof(ChaChaKey) + ((size_t)ctx->P.n + kN) * 4, true) {}
 };
-// Use: `StagedSecrets s{{ctx}}; CHK(stage_secrets(ctx, ..., s));`.  The generator key travels in a device buffer (not
-// in kernel-argument memory) and is wiped with the other secrets.
-int stage_secrets(tfhe_hip_ctx *ctx, const uint32_t *key_lv0, const uint32_t *key_lv1, const ChaChaKey &rk, size_t idx_bytes,
-                  StagedSecrets &s) {
-  CHK(to_dev(ctx, ctx->a, key_lv0, (size_t)ctx->P.n * 4));
-  CHK(to_dev(ctx, ctx->b, key_lv1, (size_t)kN * 4));
-  CHK(ensure(ctx, ctx->c.dev, (size_t)kN2 * sizeof(double2)));
-  s.d_k0 = (const uint32_t *)ctx->a.dev.p;
-  s.d_k1 = (const uint32_t *)ctx->b.dev.p;
-  hipLaunchKernelGGL(k_key_spectrum, dim3(1), dim3(64), kStageLdsBytes, ctx->stream, s.d_k1, ctx->d_tw, (double2 *)ctx->c.dev.p);
+static_assert(2 * sizeof(ChaChaKey) + ((size_t)kLweMaxN + kN) * 4 <= kSecretImageMax, "the largest image a call stages");
+// Use: `StagedSecrets s(ctx); CHK(stage_secrets(ctx, ..., s));`
+int stage_secrets(tfhe_hip_ctx *ctx, const uint32_t *key_lv0, const uint32_t *key_lv1, const ChaChaKey &rk, StagedSecrets &s) {
+  const size_t k0_at = 2 * sizeof(ChaChaKey), k1_at = k0_at + (size_t)ctx->P.n * 4;
+  const size_t spec_at = (k1_at + (size_t)kN * 4 + 15) & ~(size_t)15;
+  s.stage.put(&rk, sizeof(ChaChaKey), 0);
+  s.stage.put(key_lv0, (size_t)ctx->P.n * 4, k0_at);
+  s.stage.put(key_lv1, (size_t)kN * 4, k1_at);
+  CHK(s.stage.land("key generation: ", spec_at + (size_t)kN2 * sizeof(double2)));
+  s.d_rk = s.stage.dev<ChaChaKey>(0);
+  s.d_k0 = s.stage.dev(k0_at);
+  s.d_k1 = s.stage.dev(k1_at);
+  hipLaunchKernelGGL(k_key_spectrum, dim3(1), dim3(64), kStageLdsBytes, ctx->stream, s.d_k1, ctx->d_tw, s.stage.dev<double2>(spec_at));
   HIPCHK(ctx, hipGetLastError());
-  s.d_spec = (const double2 *)ctx->c.dev.p;
-  CHK(ensure(ctx, ctx->idx.dev, idx_bytes));
-  HIPCHK(ctx, hipMemcpy(ctx->idx.dev.p, &rk, sizeof(ChaChaKey), hipMemcpyHostToDevice));  // synchronous: rk is the caller's stack
-  s.d_rk = (ChaChaKey *)ctx->idx.dev.p;
+  s.d_spec = s.stage.dev<const double2>(spec_at);
   return TFHE_HIP_OK;
 }
 
 // The public mask seed S of stream STREAM of the staged generator key (k_derive_stream_seed), derived into the slot
-// behind it (idx[32, 64): stage_secrets was given 2 * sizeof(ChaChaKey)) and copied back.
+// behind it and copied back.
 template <uint32_t STREAM>
 int derive_public_seed(tfhe_hip_ctx *ctx, const StagedSecrets &s, ChaChaKey &seed) {
   hipLaunchKernelGGL((k_derive_stream_seed<64, STREAM>), dim3(1), dim3(64), 0, ctx->stream, s.d_rk, s.d_rk + 1);

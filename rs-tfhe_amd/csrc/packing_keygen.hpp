@@ -53,9 +53,8 @@ int gen_packing_key_locked(tfhe_hip_ctx *ctx, const uint32_t *key_lv0, const uin
   const tfhe_hip_params &P = ctx->P;
   KeyState &k = *ctx->K;
   CHK(begin_side_key(ctx, k.pk_loaded, k.d_pk8, k.pk_cap, pk_plane_bytes(P.n, P.t)));
-  // generator key at idx[0, 32), the mask seed derived from it at idx[32, 64)
-  StagedSecrets s{{ctx}};  // (wiped on every exit path)
-  CHK(stage_secrets(ctx, key_lv0, key_lv1, rk, 2 * sizeof(ChaChaKey), s));
+  StagedSecrets s(ctx);  // (wiped on every exit path)
+  CHK(stage_secrets(ctx, key_lv0, key_lv1, rk, s));
   const uint32_t *d_k0 = s.d_k0;
   const double2 *d_spec = s.d_spec;
   const ChaChaKey *d_rk = s.d_rk;

@@ -255,9 +255,7 @@ int tfhe_hip_batch_pk_encrypt(tfhe_hip_ctx *ctx, const uint32_t *plain, size_t c
   const int rc = host_call(ctx, false, {{plain, count * 4, &ctx->a}}, out, tlwe_bytes(ctx, count), [&](const void *const *d, void *o) {
     return pke_launch(ctx, gk.k, first_index, u32(d[0]), count, alpha, (uint32_t *)o, ctx->stream);
   });
-  // the plaintexts do not stay behind in the staging buffer (best effort: the call's status is rc)
-  if (ctx->a.dev.p && ctx->a.dev.cap >= count * 4 && hipMemsetAsync(ctx->a.dev.p, 0, count * 4, ctx->stream) == hipSuccess)
-    (void)hipStreamSynchronize(ctx->stream);
+  scrub(ctx->stream, {{&ctx->a, count * 4}});  // the plaintexts do not stay behind in the staging buffer
   return rc;
 }
 
@@ -309,9 +307,10 @@ int tfhe_hip_gen_reenc_key_asymmetric(tfhe_hip_ctx *ctx, const uint32_t *key_fro
   CHK(need_public_key(ctx));
   GeneratorKey gk;
   CHK(gk.fill(ctx, rng_key));
-  Wipe wipe{ctx};  // key_from rides in the staging buffer `a` and does not outlive the call on the device
-  CHK(to_dev(ctx, ctx->a, key_from, (size_t)P.n * 4));
-  const uint32_t *d_from = (const uint32_t *)ctx->a.dev.p;
+  SecretStage sec(ctx, ctx->sym_sec, ctx->stream, (size_t)P.n * 4, true);  // key_from does not outlive the call on the device
+  sec.put(key_from, (size_t)P.n * 4, 0);
+  CHK(sec.land("re-encryption key generation: "));
+  const uint32_t *d_from = sec.dev(0);
   CHK(begin_key_change(ctx, KEY_BUF_KSK));  // (both flags go: the buffer is shared with a cloud key's key-switching key)
   const int base = 1 << P.basebit;
   const size_t rows = (size_t)P.n * P.t * base, key_words = rows * (size_t)(P.n + 1);

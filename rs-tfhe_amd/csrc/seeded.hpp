@@ -119,9 +119,8 @@ int gen_compressed_locked(tfhe_hip_ctx *ctx, const uint32_t *key_lv0, const uint
   const tfhe_hip_params &P = ctx->P;
   const size_t bsk_words = (size_t)P.n * 2 * P.l * kN, ksk_words = ksk_rows(P);
   CHK(begin_key_change(ctx, KEY_BUF_ALL));
-  // generator key at idx[0, 32), the mask seed derived from it at idx[32, 64)
-  StagedSecrets s{{ctx}};  // (wiped on every exit path)
-  CHK(stage_secrets(ctx, key_lv0, key_lv1, rk, 2 * sizeof(ChaChaKey), s));
+  StagedSecrets s(ctx);  // (wiped on every exit path)
+  CHK(stage_secrets(ctx, key_lv0, key_lv1, rk, s));
   const uint32_t *d_k0 = s.d_k0;
   const double2 *d_spec = s.d_spec;
   const ChaChaKey *d_rk = s.d_rk;

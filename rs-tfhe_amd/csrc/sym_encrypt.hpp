@@ -16,37 +16,23 @@
 
 // ---- symmetric encryption (sym_encrypt.hpp) -----------------------------------------------------------------------
 namespace {
-// The secrets of one launch in the context's `sym_sec` buffer: K, s0 [n], key_from [n] (or nothing).  The copy has
-// landed when this returns (the sources are the caller's and this frame's).
-int sym_stage(tfhe_hip_ctx *ctx, const ChaChaKey &k, const uint32_t *key_lv0, const uint32_t *key_from, hipStream_t s) {
-  const int n = ctx->P.n;
-  std::vector<uint32_t> h(8 + (size_t)n * (key_from ? 2 : 1));
-  memcpy(h.data(), k.k, 32);
-  memcpy(h.data() + 8, key_lv0, (size_t)n * 4);
-  if (key_from) memcpy(h.data() + 8 + n, key_from, (size_t)n * 4);
-  int rc = ensure(ctx, ctx->sym_sec, h.size() * 4);
-  if (rc == TFHE_HIP_OK) {
-    hipError_t e = hipMemcpyAsync(ctx->sym_sec.p, h.data(), h.size() * 4, hipMemcpyHostToDevice, s);
-    if (e == hipSuccess) e = hipStreamSynchronize(s);
-    if (e != hipSuccess) rc = fail(ctx, TFHE_HIP_EHIP, std::string("symmetric encryption: ") + hipGetErrorString(e));
-  }
-  volatile uint32_t *wipe = h.data();
-  for (size_t i = 0; i < h.size(); ++i) wipe[i] = 0;
-  return rc;
+// The secrets of one launch, through a SecretStage over the context's `sym_sec`: K, s0 [n], key_from [n] (or nothing)
+size_t sym_sec_bytes(const tfhe_hip_ctx *ctx, bool key_rows) { return (8 + (size_t)ctx->P.n * (key_rows ? 2 : 1)) * 4; }
+static_assert((8 + 2 * (size_t)kLweMaxN) * 4 <= kSecretImageMax, "the largest image a call stages");
+int sym_land(tfhe_hip_ctx *ctx, SecretStage &sec, const ChaChaKey &k, const uint32_t *key_lv0, const uint32_t *key_from) {
+  const size_t n4 = (size_t)ctx->P.n * 4;
+  sec.put(k.k, 32, 0);
+  sec.put(key_lv0, n4, 32);
+  if (key_from) sec.put(key_from, n4, 32 + n4);
+  return sec.land("symmetric encryption: ");
 }
 
-// zero the staged secrets behind whatever stream s has queued
-int sym_wipe(tfhe_hip_ctx *ctx, hipStream_t s) {
-  if (ctx->sym_sec.p) HIPCHK(ctx, hipMemsetAsync(ctx->sym_sec.p, 0, ctx->sym_sec.cap, s));
-  return TFHE_HIP_OK;
-}
-
-// `rows` rows from index `first_index` over the staged secrets (sym_stage), under the indexed domains dom_mask /
+// `rows` rows from index `first_index` over the staged secrets (sym_land), under the indexed domains dom_mask /
 // dom_noise; masks under `seed`, or (NULL) under K.  plain / bodies / out are device pointers, any may be NULL.
-int sym_launch(tfhe_hip_ctx *ctx, const ChaChaKey *seed, uint32_t dom_mask, uint32_t dom_noise, uint64_t first_index,
-               size_t rows, double alpha, const uint32_t *plain, bool key_rows, uint32_t *bodies, uint32_t *out, int stride,
-               hipStream_t s) {
-  const uint32_t *sec = (const uint32_t *)ctx->sym_sec.p;
+int sym_launch(tfhe_hip_ctx *ctx, const SecretStage &staged, const ChaChaKey *seed, uint32_t dom_mask, uint32_t dom_noise,
+               uint64_t first_index, size_t rows, double alpha, const uint32_t *plain, bool key_rows, uint32_t *bodies,
+               uint32_t *out, int stride, hipStream_t s) {
+  const uint32_t *sec = staged.dev(0);
   LweRowJob j{};
   if (seed) j.seed = *seed;
   j.k = (const ChaChaKey *)sec;
@@ -79,12 +65,30 @@ const char *sym_refusal(const tfhe_hip_ctx *ctx, const uint32_t *key_lv0, const 
 // on stream s: stage, launch, wipe.  plain / bodies / out are device pointers.
 int sym_bulk(tfhe_hip_ctx *ctx, const ChaChaKey &seed, const ChaChaKey &k, const uint32_t *key_lv0, const uint32_t *plain,
              size_t count, double alpha, uint64_t first_index, uint32_t *bodies, uint32_t *out, hipStream_t s) {
-  CHK(claim_scratch(ctx, s));  // sym_sec belongs to the context
-  CHK(sym_stage(ctx, k, key_lv0, nullptr, s));
-  const int rc = sym_launch(ctx, &seed, kSeedDomainTlwe, kSeedDomainSymNoise, first_index, count, alpha, plain, false, bodies,
-                            out, ctx->P.n + 1, s);
-  const int rc_wipe = sym_wipe(ctx, s);
-  return rc != TFHE_HIP_OK ? rc : rc_wipe;
+  SecretStage sec(ctx, ctx->sym_sec, s, sym_sec_bytes(ctx, false));
+  int rc = sym_land(ctx, sec, k, key_lv0, nullptr);
+  if (rc == TFHE_HIP_OK)
+    rc = sym_launch(ctx, sec, &seed, kSeedDomainTlwe, kSeedDomainSymNoise, first_index, count, alpha, plain, false, bodies, out,
+                    ctx->P.n + 1, s);
+  return sec.finish(rc);
+}
+
+// A host-form encryption of plain [count], staged through slot a.  The primary output (out, or the bodies alone)
+// returns through host_call; with both asked for, the bodies ride in staging buffer b.  bulk(d_plain, d_bodies, d_out)
+// queues the call on the context's stream.  The plaintexts do not stay behind in the library's buffers.
+template <class Bulk>
+int encrypt_host_call(tfhe_hip_ctx *ctx, const uint32_t *plain, size_t count, uint32_t *bodies, size_t body_bytes, uint32_t *out,
+                      size_t out_bytes, Bulk &&bulk) {
+  if (out && bodies) CHK(ensure(ctx, ctx->b.dev, body_bytes));
+  int rc = host_call(ctx, false, {{plain, count * 4, &ctx->a}}, out ? out : bodies, out ? out_bytes : body_bytes,
+                     [&](const void *const *d, void *o) {
+                       uint32_t *d_out = out ? (uint32_t *)o : nullptr;
+                       uint32_t *d_bodies = out ? (bodies ? (uint32_t *)ctx->b.dev.p : nullptr) : (uint32_t *)o;
+                       return bulk(u32(d[0]), d_bodies, d_out);
+                     });
+  if (rc == TFHE_HIP_OK && out && bodies) rc = to_host(ctx, bodies, ctx->b, body_bytes);
+  scrub(ctx->stream, {{&ctx->a, count * 4}});
+  return rc;
 }
 }  // namespace
 
@@ -99,21 +103,10 @@ int tfhe_hip_batch_encrypt(tfhe_hip_ctx *ctx, const uint32_t *key_lv0, const uin
   GeneratorKey gk;
   CHK(gk.fill(ctx, rng_key));
   const ChaChaKey seed = seed_key(mask_seed);
-  // the primary output returns through host_call; with both asked for, the bodies ride in staging buffer b
-  uint32_t *primary = out ? out : bodies;
-  const size_t primary_bytes = out ? tlwe_bytes(ctx, count) : count * 4;
-  if (out && bodies) CHK(ensure(ctx, ctx->b.dev, count * 4));
-  int rc = host_call(ctx, false, {{plain, count * 4, &ctx->a}}, primary, primary_bytes, [&](const void *const *d, void *o) {
-    uint32_t *d_out = out ? (uint32_t *)o : nullptr;
-    uint32_t *d_bodies = out ? (bodies ? (uint32_t *)ctx->b.dev.p : nullptr) : (uint32_t *)o;
-    return sym_bulk(ctx, seed, gk.k, key_lv0, u32(d[0]), count, alpha, first_index, d_bodies, d_out, ctx->stream);
-  });
-  if (rc == TFHE_HIP_OK && out && bodies) rc = to_host(ctx, bodies, ctx->b, count * 4);
-  // neither the secrets nor the plaintexts stay behind on the device (best effort: the call's status is rc)
-  (void)sym_wipe(ctx, ctx->stream);
-  if (ctx->a.dev.p && ctx->a.dev.cap >= count * 4) (void)hipMemsetAsync(ctx->a.dev.p, 0, count * 4, ctx->stream);
-  (void)hipStreamSynchronize(ctx->stream);
-  return rc;
+  return encrypt_host_call(ctx, plain, count, bodies, count * 4, out, tlwe_bytes(ctx, count),
+                           [&](const uint32_t *d_plain, uint32_t *d_bodies, uint32_t *d_out) {
+                             return sym_bulk(ctx, seed, gk.k, key_lv0, d_plain, count, alpha, first_index, d_bodies, d_out, ctx->stream);
+                           });
 }
 
 int tfhe_hip_batch_encrypt_dev(tfhe_hip_ctx *ctx, const uint32_t *key_lv0, const uint32_t *plain, size_t count, double alpha,
@@ -146,22 +139,18 @@ int tfhe_hip_gen_public_key(tfhe_hip_ctx *ctx, const uint32_t *key_lv0, size_t s
   KeyState &k = *ctx->K;
   const size_t bytes = pke_plane_bytes(P.n, (int)size), chunks = bytes / 16, enc_bytes = size * (size_t)(P.n + 1) * 4;
   CHK(begin_side_key(ctx, k.pke_loaded, k.d_pke8, k.pke_cap, bytes));
-  CHK(claim_scratch(ctx, ctx->stream));
-  int rc = sym_stage(ctx, gk.k, key_lv0, nullptr, ctx->stream);
-  if (rc == TFHE_HIP_OK)
-    rc = upload_through_temp(ctx, "public key generation", {}, enc_bytes, [&](void *d_enc) -> hipError_t {
-      if (sym_launch(ctx, nullptr, kSeedDomainPkMask, kSeedDomainPkNoise, 0, size, alpha, nullptr, false, nullptr,
-                     (uint32_t *)d_enc, P.n + 1, ctx->stream) != TFHE_HIP_OK)
-        return hipErrorLaunchFailure;
-      hipLaunchKernelGGL(k_pke_planes<256>, dim3((unsigned)((chunks + 255) / 256)), dim3(256), 0, ctx->stream,
-                         (const uint32_t *)d_enc, k.d_pke8, P.n, (int)size, chunks);
-      if (const hipError_t e = hipGetLastError()) return e;
-      if (encryptions_out) return hipMemcpyAsync(encryptions_out, d_enc, enc_bytes, hipMemcpyDeviceToHost, ctx->stream);
-      return hipSuccess;
-    });
-  (void)sym_wipe(ctx, ctx->stream);
-  (void)hipStreamSynchronize(ctx->stream);
-  CHK(rc);
+  SecretStage sec(ctx, ctx->sym_sec, ctx->stream, sym_sec_bytes(ctx, false), true);  // (wiped on every exit path)
+  CHK(sym_land(ctx, sec, gk.k, key_lv0, nullptr));
+  CHK(upload_through_temp(ctx, "public key generation", {}, enc_bytes, [&](void *d_enc) -> hipError_t {
+    if (sym_launch(ctx, sec, nullptr, kSeedDomainPkMask, kSeedDomainPkNoise, 0, size, alpha, nullptr, false, nullptr,
+                   (uint32_t *)d_enc, P.n + 1, ctx->stream) != TFHE_HIP_OK)
+      return hipErrorLaunchFailure;
+    hipLaunchKernelGGL(k_pke_planes<256>, dim3((unsigned)((chunks + 255) / 256)), dim3(256), 0, ctx->stream,
+                       (const uint32_t *)d_enc, k.d_pke8, P.n, (int)size, chunks);
+    if (const hipError_t e = hipGetLastError()) return e;
+    if (encryptions_out) return hipMemcpyAsync(encryptions_out, d_enc, enc_bytes, hipMemcpyDeviceToHost, ctx->stream);
+    return hipSuccess;
+  }));
   k.pke_size = (int)size;
   commit_side_key(k.pke_loaded);
   return TFHE_HIP_OK;
@@ -183,24 +172,18 @@ int tfhe_hip_gen_reenc_key_symmetric(tfhe_hip_ctx *ctx, const uint32_t *key_from
   CHK(begin_key_change(ctx, KEY_BUF_KSK));  // (both flags go: the buffer is shared with a cloud key's key-switching key)
   const int base = 1 << P.basebit;
   const size_t rows = (size_t)P.n * P.t * base, key_words = rows * (size_t)(P.n + 1);
-  CHK(claim_scratch(ctx, ctx->stream));
-  int rc = sym_stage(ctx, gk.k, key_to, key_from, ctx->stream);
-  if (rc == TFHE_HIP_OK) {
-    hipError_t e = hipMemsetAsync(ctx->K->d_ksk, 0, ksk_bytes(P), ctx->stream);
-    if (e != hipSuccess) rc = fail(ctx, TFHE_HIP_EHIP, std::string("re-encryption key generation: ") + hipGetErrorString(e));
-  }
-  if (rc == TFHE_HIP_OK)
-    rc = sym_launch(ctx, nullptr, kSeedDomainRkMask, kSeedDomainRkNoise, 0, rows, alpha, nullptr, true, nullptr,
-                    ctx->K->d_ksk, ksk_row_words(P.n), ctx->stream);
-  if (rc == TFHE_HIP_OK && key_out)
-    rc = upload_through_temp(ctx, "re-encryption key export", {}, key_words * 4, [&](void *d_ref) -> hipError_t {
+  SecretStage sec(ctx, ctx->sym_sec, ctx->stream, sym_sec_bytes(ctx, true), true);  // (wiped on every exit path)
+  CHK(sym_land(ctx, sec, gk.k, key_to, key_from));
+  if (const hipError_t e = hipMemsetAsync(ctx->K->d_ksk, 0, ksk_bytes(P), ctx->stream))
+    return fail(ctx, TFHE_HIP_EHIP, std::string("re-encryption key generation: ") + hipGetErrorString(e));
+  CHK(sym_launch(ctx, sec, nullptr, kSeedDomainRkMask, kSeedDomainRkNoise, 0, rows, alpha, nullptr, true, nullptr, ctx->K->d_ksk,
+                 ksk_row_words(P.n), ctx->stream));
+  if (key_out)
+    CHK(upload_through_temp(ctx, "re-encryption key export", {}, key_words * 4, [&](void *d_ref) -> hipError_t {
       hipLaunchKernelGGL(k_ksk_export, dim3((unsigned)rows), dim3(256), 0, ctx->stream, (const uint32_t *)ctx->K->d_ksk,
                          (uint32_t *)d_ref, P.n, rows);
       if (const hipError_t e = hipGetLastError()) return e;
       return hipMemcpyAsync(key_out, d_ref, key_words * 4, hipMemcpyDeviceToHost, ctx->stream);
-    });
-  (void)sym_wipe(ctx, ctx->stream);
-  (void)hipStreamSynchronize(ctx->stream);
-  CHK(rc);
+    }));
   return commit_reenc_key(ctx);
 }

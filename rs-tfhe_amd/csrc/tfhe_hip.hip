@@ -128,22 +128,9 @@ class FairMutex {
   uint64_t next_ = 0, serving_ = 0;
 };
 
-struct DevBuf {
-  void *p = nullptr;
-  size_t cap = 0;
-};
-struct PinBuf {  // pinned host arena (hipHostMalloc)
-  void *p = nullptr;
-  size_t cap = 0;
-  bool heap = false;  // front-end lanes only: pinned memory was not to be had, this is ordinary memory (copies still work)
-};
-struct Staging {  // a host-API staging buffer on the device and the pinned arena behind it
-  DevBuf dev;
-  PinBuf pin;
-  bool pool_pinned = false;  // pool members route large pageable copies of this slot through `pin`
-};
-
 }  // namespace
+
+#include "secrets.hpp"  // DevBuf, PinBuf, Staging; SecretStage and scrub over them
 
 // One resident cloud key in the engine layouts (src/key.rs:51-56).  A context owns one (`own`); every key view
 // created with tfhe_hip_key_create owns another and runs on its parent's device, stream, scratch and mutex.
@@ -184,7 +171,7 @@ struct tfhe_hip_ctx {
   DevBuf lv1, u1, u2, ks_out, ks_dig;  // scratch (ks_dig: key-switch digit bytes)
   DevBuf biv_s1, biv_tv;               // tree bootstrap (table.hpp): stage-1 results [m][chunk][n+1], their tables [chunk][2][N]
   DevBuf pke_sel;                      // public-key encryption (pk_encrypt.hpp): selector words and addends of one pass
-  DevBuf sym_sec;                      // symmetric encryption (sym_encrypt.hpp): the staged keys of one call, wiped behind it
+  DevBuf sym_sec;                      // the staged secrets of one call (secrets.hpp: SecretStage), wiped behind it
   // host-API staging: a / b / c / out also stage through their arenas on pool members (to_dev / to_host);
   // the arenas of tv / idx serve the combiner lanes only
   Staging a{{}, {}, true}, b{{}, {}, true}, c{{}, {}, true}, out{{}, {}, true}, tv, idx;
@@ -1357,8 +1344,8 @@ int gen_cloud_key_locked(tfhe_hip_ctx *ctx, const uint32_t *key_lv0, const uint3
   if (!(alpha_ksk >= 0.0) || !(alpha_bsk >= 0.0)) return fail(ctx, TFHE_HIP_EINVAL, "negative noise parameter");
   CHK(begin_key_change(ctx, KEY_BUF_ALL));
   const tfhe_hip_params &P = ctx->P;
-  StagedSecrets s{{ctx}};  // (wiped on every exit path)
-  CHK(stage_secrets(ctx, key_lv0, key_lv1, rk, sizeof(ChaChaKey), s));
+  StagedSecrets s(ctx);  // (wiped on every exit path)
+  CHK(stage_secrets(ctx, key_lv0, key_lv1, rk, s));
   const auto gen_bsk = kernel_inst(ctx, false, [](auto inst) { return k_gen_bsk<decltype(inst)::L>; });
   hipLaunchKernelGGL(gen_bsk, dim3((unsigned)(P.n * 2 * P.l)), dim3(64), kStageLdsBytes, ctx->stream, s.d_k0, s.d_spec,
                      ctx->d_tw, ctx->K->d_bsk, P.bgbit, alpha_bsk, s.d_rk, key_scale(ctx->dispatch.fast_round));

@@ -13,9 +13,9 @@
 //   k_expand_trlwe   no secret: one wave per group writes its 64 keystream blocks as whole dwordx4 chunks into
 //                    out[m][0] and copies the bodies into out[m][1].
 //
-// Secrets travel as in sym_encrypt.hpp, through the context's `sym_sec` buffer: K [8 words], s1 [N words] and the
-// spectrum of s1 [N / 2 double2] (k_key_spectrum, as stage_secrets runs it -- the spectrum is secret too).  The host
-// copy is wiped, and the buffer is zeroed behind the kernel on the same stream.
+// Secrets travel as in sym_encrypt.hpp, through a SecretStage (secrets.hpp) over the context's `sym_sec` buffer:
+// K [8 words], s1 [N words] and the spectrum of s1 [N / 2 double2] (k_key_spectrum, as stage_secrets runs it -- the
+// spectrum is secret too).  The host copy is wiped, and the buffer is zeroed behind the kernel on the same stream.
 //
 // Both kernels are templates: instantiations are emitted after the library's other kernels, whose code stays
 // byte-identical.
@@ -115,33 +115,21 @@ const char *trlwe_expand_refusal(const uint8_t *mask_seed, uint64_t first_group,
 // on stream s: stage K, s1 and the spectrum of s1, launch, wipe.  plain / bodies / out are device pointers.
 int trlwe_bulk(tfhe_hip_ctx *ctx, const ChaChaKey &seed, const ChaChaKey &k, const uint32_t *key_lv1, const uint32_t *plain,
                size_t count, double alpha, uint64_t first_group, uint32_t *bodies, uint32_t *out, hipStream_t s) {
-  CHK(claim_scratch(ctx, s));  // sym_sec belongs to the context
-  int rc = ensure(ctx, ctx->sym_sec, kTrlweSecBytes);
-  {
-    uint32_t h[8 + kN];
-    memcpy(h, k.k, 32);
-    memcpy(h + 8, key_lv1, (size_t)kN * 4);
-    if (rc == TFHE_HIP_OK) {
-      hipError_t e = hipMemcpyAsync(ctx->sym_sec.p, h, sizeof(h), hipMemcpyHostToDevice, s);
-      if (e == hipSuccess) e = hipStreamSynchronize(s);  // (the copy has landed: h is this frame's)
-      if (e != hipSuccess) rc = fail(ctx, TFHE_HIP_EHIP, std::string("packed encryption: ") + hipGetErrorString(e));
-    }
-    volatile uint32_t *wipe = h;
-    for (size_t i = 0; i < 8 + (size_t)kN; ++i) wipe[i] = 0;
-  }
+  SecretStage sec(ctx, ctx->sym_sec, s, kTrlweSecSpecAt);
+  sec.put(k.k, 32, 0);
+  sec.put(key_lv1, (size_t)kN * 4, 32);
+  int rc = sec.land("packed encryption: ", kTrlweSecBytes);
   if (rc == TFHE_HIP_OK) {
-    const uint32_t *sec = (const uint32_t *)ctx->sym_sec.p;
-    double2 *d_spec = (double2 *)((unsigned char *)ctx->sym_sec.p + kTrlweSecSpecAt);
-    hipLaunchKernelGGL(k_key_spectrum, dim3(1), dim3(64), kStageLdsBytes, s, sec + 8, ctx->d_tw, d_spec);
+    double2 *d_spec = sec.dev<double2>(kTrlweSecSpecAt);
+    hipLaunchKernelGGL(k_key_spectrum, dim3(1), dim3(64), kStageLdsBytes, s, sec.dev(32), ctx->d_tw, d_spec);
     rc = launched(ctx);
     if (rc == TFHE_HIP_OK) {
       hipLaunchKernelGGL(k_trlwe_rows<64>, dim3((unsigned)trlwe_groups(count)), dim3(64), kStageLdsBytes, s, (const double2 *)d_spec,
-                         ctx->d_tw, (const ChaChaKey *)sec, seed, first_group, plain, count, alpha, bodies, out);
+                         ctx->d_tw, sec.dev<const ChaChaKey>(0), seed, first_group, plain, count, alpha, bodies, out);
       rc = launched(ctx);
     }
   }
-  const int rc_wipe = sym_wipe(ctx, s);
-  return rc != TFHE_HIP_OK ? rc : rc_wipe;
+  return sec.finish(rc);
 }
 
 int trlwe_expand_launch(tfhe_hip_ctx *ctx, const ChaChaKey &seed, uint64_t first_group, const uint32_t *bodies, size_t groups,
@@ -165,26 +153,10 @@ int tfhe_hip_batch_encrypt_trlwe(tfhe_hip_ctx *ctx, const uint32_t *key_lv1, con
   CHK(gk.fill(ctx, rng_key));
   const ChaChaKey seed = seed_key(mask_seed);
   const size_t groups = trlwe_groups(count), body_bytes = groups * (size_t)kN * 4;
-  // the primary output returns through host_call; with both asked for, the bodies ride in staging buffer b
-  uint32_t *primary = out ? out : bodies;
-  const size_t primary_bytes = out ? trlwe_bytes(groups) : body_bytes;
-  if (out && bodies) CHK(ensure(ctx, ctx->b.dev, body_bytes));
-  int rc = host_call(ctx, false, {{plain, count * 4, &ctx->a}}, primary, primary_bytes, [&](const void *const *d, void *o) {
-    uint32_t *d_out = out ? (uint32_t *)o : nullptr;
-    uint32_t *d_bodies = out ? (bodies ? (uint32_t *)ctx->b.dev.p : nullptr) : (uint32_t *)o;
-    return trlwe_bulk(ctx, seed, gk.k, key_lv1, u32(d[0]), count, alpha, first_group, d_bodies, d_out, ctx->stream);
-  });
-  if (rc == TFHE_HIP_OK && out && bodies) rc = to_host(ctx, bodies, ctx->b, body_bytes);
-  // neither the secrets nor the plaintexts stay behind in the library's buffers (best effort: the call's status is rc)
-  (void)sym_wipe(ctx, ctx->stream);
-  if (ctx->a.dev.p && ctx->a.dev.cap >= count * 4) (void)hipMemsetAsync(ctx->a.dev.p, 0, count * 4, ctx->stream);
-  (void)hipStreamSynchronize(ctx->stream);
-  if (ctx->a.pin.p) {  // (pool members stage large operands through the pinned arena)
-    volatile uint32_t *wipe = (volatile uint32_t *)ctx->a.pin.p;
-    const size_t words = ctx->a.pin.cap / 4 < count ? ctx->a.pin.cap / 4 : count;
-    for (size_t i = 0; i < words; ++i) wipe[i] = 0;
-  }
-  return rc;
+  return encrypt_host_call(ctx, plain, count, bodies, body_bytes, out, trlwe_bytes(groups),
+                           [&](const uint32_t *d_plain, uint32_t *d_bodies, uint32_t *d_out) {
+                             return trlwe_bulk(ctx, seed, gk.k, key_lv1, d_plain, count, alpha, first_group, d_bodies, d_out, ctx->stream);
+                           });
 }
 
 int tfhe_hip_batch_encrypt_trlwe_dev(tfhe_hip_ctx *ctx, const uint32_t *key_lv1, const uint32_t *plain, size_t count, double alpha,
