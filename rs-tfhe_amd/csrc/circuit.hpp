@@ -93,23 +93,22 @@ struct CircPlan {
   size_t B = 0;
   bool pool = false;
   uint64_t last_use = 0;
-  void *blob = nullptr, *blob8 = nullptr;
+  DevArray<void> blob, blob8;
   std::vector<std::vector<CircDevLaunch>> lv;
   size_t max_count = 0;
   DevBuf store, stage_a, stage_b, gather;  // host-array runs: the store; pool runs: staging; gathers: their CSR
   std::vector<uint32_t> gather_key;
   std::vector<size_t> gather_offs;
-  hipEvent_t gather_done = nullptr;  // recorded after each gather: the CSR is rewritten only once it has been read
+  OwnEvent gather_done;  // recorded after each gather: the CSR is rewritten only once it has been read
   bool gather_recorded = false;
   std::mutex run_mu;                 // pool plans: one run at a time, prepare through the last level (and the gather)
-  hipEvent_t run_done = nullptr;     // pool plans: recorded at the end of a run; the next run's stream waits for it
+  OwnEvent run_done;    // pool plans: recorded at the end of a run; the next run's stream waits for it
   bool run_recorded = false;
   ~CircPlan() {
-    DeviceGuard dg(device);
-    for (void *q : {blob, blob8, store.p, stage_a.p, stage_b.p, gather.p})
-      if (q) (void)hipFree(q);
-    if (gather_done) (void)hipEventDestroy(gather_done);
-    if (run_done) (void)hipEventDestroy(run_done);
+    DeviceGuard dg(device);  // (the plan's device is current while its buffers and events go)
+    for (DevBuf *b : {(DevBuf *)&blob, (DevBuf *)&blob8, &store, &stage_a, &stage_b, &gather}) b->release();
+    gather_done.reset();
+    run_done.reset();
   }
 };
 constexpr size_t kCircMaxPlans = 4;  // per circuit: the least recently used one beyond this is dropped
@@ -457,15 +456,15 @@ int circ_plan(tfhe_hip_ctx *ctx, tfhe_hip_circuit *c, size_t B, bool pool, std::
       offs[L].push_back(o);
     }
   if (!u.empty()) {
-    HIPCHK(ctx, hipMalloc(&p->blob, u.size() * 4));
+    CHK(alloc_exact(ctx, p->blob, u.size() * 4, "hipMalloc(&p->blob, u.size() * 4)"));
     HIPCHK(ctx, hipMemcpy(p->blob, u.data(), u.size() * 4, hipMemcpyHostToDevice));
   }
   if (!u8.empty()) {
-    HIPCHK(ctx, hipMalloc(&p->blob8, u8.size()));
+    CHK(alloc_exact(ctx, p->blob8, u8.size(), "hipMalloc(&p->blob8, u8.size())"));
     HIPCHK(ctx, hipMemcpy(p->blob8, u8.data(), u8.size(), hipMemcpyHostToDevice));
   }
-  const uint32_t *U = (const uint32_t *)p->blob;
-  const uint8_t *U8 = (const uint8_t *)p->blob8;
+  const uint32_t *U = (const uint32_t *)p->blob.p;
+  const uint8_t *U8 = (const uint8_t *)p->blob8.p;
   p->lv.resize(c->levels.size());
   for (size_t L = 1; L < c->levels.size(); ++L)
     for (size_t q = 0; q < c->levels[L].launches.size(); ++q) {
@@ -566,7 +565,7 @@ int circ_gather_locked(tfhe_hip_ctx *ctx, tfhe_hip_circuit *c, CircPlan *p, cons
   const uint32_t *G = (const uint32_t *)p->gather.p;
   CHK(circ_lincomb_launch(ctx, s, wires, G + p->gather_offs[0], G + p->gather_offs[1], G + p->gather_offs[2],
                           G + p->gather_offs[3], p->B, out, n_out));
-  if (!p->gather_done) HIPCHK(ctx, hipEventCreateWithFlags(&p->gather_done, hipEventDisableTiming));
+  if (!p->gather_done) CHK(hip_rc(ctx, {p->gather_done.create(hipEventDisableTiming), "hipEventCreateWithFlags(&p->gather_done, hipEventDisableTiming)"}));
   HIPCHK(ctx, hipEventRecord(p->gather_done, circ_rt_stream(s)));
   p->gather_recorded = true;
   return TFHE_HIP_OK;
@@ -601,7 +600,7 @@ int circ_pool_begin(tfhe_hip_ctx *hctx, tfhe_hip_circuit *c, CircPlan *p, const 
 // the run's last work on the home stream (every member's shard is back there): the next run waits for it (run_mu held)
 int circ_pool_end(tfhe_hip_ctx *hctx, CircPlan *p, hipStream_t s) {
   ENTER(hctx);
-  if (!p->run_done) HIPCHK(hctx, hipEventCreateWithFlags(&p->run_done, hipEventDisableTiming));
+  if (!p->run_done) CHK(hip_rc(hctx, {p->run_done.create(hipEventDisableTiming), "hipEventCreateWithFlags(&p->run_done, hipEventDisableTiming)"}));
   HIPCHK(hctx, hipEventRecord(p->run_done, circ_rt_stream(s)));
   p->run_recorded = true;
   return TFHE_HIP_OK;

@@ -69,18 +69,8 @@ enum CombClass { CB_GATES = 0, CB_MUX = 1, CB_MUX_NAIVE = 2, CB_ROTATE = 3 };  /
 // a lane's staging pair for one operand: host arena (packed by the leader; pinned, or ordinary memory where pinned memory
 // is not to be had -- the copies work from either, only slower) -> device buffer
 int comb_arena(tfhe_hip_ctx *x, Staging &st, size_t bytes) {
-  PinBuf &pin = st.pin;
   CHK(ensure(x, st.dev, bytes));
-  if (bytes <= pin.cap) return TFHE_HIP_OK;
-  if (!pin.heap && ensure_pinned(x, pin, bytes) == TFHE_HIP_OK) return TFHE_HIP_OK;
-  if (pin.p && pin.heap) free(pin.p);
-  pin.p = nullptr;
-  pin.cap = 0;
-  const size_t want = bytes + bytes / 4;
-  pin.p = aligned_alloc(4096, (want + 4095) & ~(size_t)4095);
-  if (!pin.p) return fail(x, TFHE_HIP_ENOMEM, "merged-call arena: out of host memory");
-  pin.cap = want;
-  pin.heap = true;
+  if (!st.pin.grow(bytes, true)) return fail(x, TFHE_HIP_ENOMEM, "merged-call arena: out of host memory");
   return TFHE_HIP_OK;
 }
 
@@ -215,7 +205,7 @@ int comb_make_lane(tfhe_hip_ctx *base, Combiner &C, int li, std::string &why) {
     (void)comb_arena(x, x->a, bytes);
     (void)comb_arena(x, x->b, bytes);
     (void)comb_arena(x, x->out, bytes);
-    (void)ensure(x, x->lv1, lv1_bytes(rows));
+    (void)take(x, x->stream, x->lv1, lv1_bytes(rows));
   }
   C.lane_ctx[li] = x;
   return TFHE_HIP_OK;

@@ -34,12 +34,12 @@ inline size_t key_testvec_bytes() { return testvec_bytes(0, 1); }
 
 enum KeyBufs { KEY_BUF_BSK = 1, KEY_BUF_KSK = 2, KEY_BUF_TESTVEC = 4, KEY_BUF_ALL = 7 };
 
-// the only allocator of d_bsk / d_ksk / d_testvec (free_key releases them)
+// the only allocator of d_bsk / d_ksk / d_testvec (they go with their KeyState)
 int ensure_key_buffers(tfhe_hip_ctx *ctx, int which) {
   KeyState &k = *ctx->K;
-  if ((which & KEY_BUF_BSK) && !k.d_bsk) HIPCHK(ctx, hipMalloc((void **)&k.d_bsk, bsk_bytes(ctx->P)));
-  if ((which & KEY_BUF_KSK) && !k.d_ksk) HIPCHK(ctx, hipMalloc((void **)&k.d_ksk, ksk_bytes(ctx->P) + kKskTailPad));
-  if ((which & KEY_BUF_TESTVEC) && !k.d_testvec) HIPCHK(ctx, hipMalloc((void **)&k.d_testvec, key_testvec_bytes()));
+  if (which & KEY_BUF_BSK) CHK(alloc_exact(ctx, k.d_bsk, bsk_bytes(ctx->P), "hipMalloc((void **)&k.d_bsk, bsk_bytes(ctx->P))"));
+  if (which & KEY_BUF_KSK) CHK(alloc_exact(ctx, k.d_ksk, ksk_bytes(ctx->P) + kKskTailPad, "hipMalloc((void **)&k.d_ksk, ksk_bytes(ctx->P) + kKskTailPad)"));
+  if (which & KEY_BUF_TESTVEC) CHK(alloc_exact(ctx, k.d_testvec, key_testvec_bytes(), "hipMalloc((void **)&k.d_testvec, key_testvec_bytes())"));
   return TFHE_HIP_OK;
 }
 
@@ -48,9 +48,9 @@ int ensure_key_buffers(tfhe_hip_ctx *ctx, int which) {
 // (The key-view branch of tfhe_hip_ctx_destroy keeps its own spelling: it must go on to free the key whatever a
 // synchronisation answers, and this returns at the first failure.)
 int drain_key_readers(tfhe_hip_ctx *ctx) {
-  if (ctx->scratch_owned) HIPCHK(ctx, hipStreamSynchronize(ctx->scratch_owner));
+  CHK(hip_rc(ctx, sync_scratch_owner(ctx)));
   HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-  ctx->scratch_owned = false;
+  ctx->scratch.owned = false;
   comb_quiesce(ctx);
   return TFHE_HIP_OK;
 }
@@ -79,18 +79,12 @@ int commit_reenc_key(tfhe_hip_ctx *ctx) {
 }
 
 // ---- side keys ------------------------------------------------------------------------------------------------------
-// `flag` / `planes` / `cap` are the side key's members of *ctx->K.  Calls queued on the caller's streams may still read
+// `flag` / `planes` are the side key's members of *ctx->K.  Calls queued on the caller's streams may still read
 // the planes that are about to be overwritten: hence the device-wide drain.
-int begin_side_key(tfhe_hip_ctx *ctx, bool &flag, unsigned char *&planes, size_t &cap, size_t bytes) {
+int begin_side_key(tfhe_hip_ctx *ctx, bool &flag, DevBuf &planes, size_t bytes) {
   HIPCHK(ctx, hipDeviceSynchronize());
   flag = false;
-  if (bytes <= cap) return TFHE_HIP_OK;
-  if (planes) HIPCHK(ctx, hipFree(planes));
-  planes = nullptr;
-  cap = 0;
-  HIPCHK(ctx, hipMalloc((void **)&planes, bytes));
-  cap = bytes;
-  return TFHE_HIP_OK;
+  return alloc_exact(ctx, planes, bytes, "hipMalloc((void **)&planes, bytes)");
 }
 void commit_side_key(bool &flag) { flag = true; }
 
@@ -116,18 +110,17 @@ int upload_through_temp(tfhe_hip_ctx *ctx, const char *label, std::initializer_l
                         Launch &&launch) {
   size_t total = extra_bytes;
   for (const HostSrc &s : srcs) total += s.bytes;
-  char *d_tmp = nullptr;
-  HIPCHK(ctx, hipMalloc((void **)&d_tmp, total));
+  DevArray<char> d_tmp;
+  CHK(alloc_exact(ctx, d_tmp, total, "hipMalloc((void **)&d_tmp, total)"));
   hipError_t e = hipSuccess;
   size_t at = 0;
   for (const HostSrc &s : srcs) {
     if (e == hipSuccess) e = hipMemcpyAsync(d_tmp + at, s.p, s.bytes, hipMemcpyHostToDevice, ctx->stream);
     at += s.bytes;
   }
-  if (e == hipSuccess) e = launch((void *)d_tmp);
-  const hipError_t es = hipStreamSynchronize(ctx->stream);
+  if (e == hipSuccess) e = launch(d_tmp.p);
+  const hipError_t es = hipStreamSynchronize(ctx->stream);  // (nothing reads the temporary once this has returned)
   if (e == hipSuccess) e = es;
-  (void)hipFree(d_tmp);
   if (e != hipSuccess) return fail(ctx, TFHE_HIP_EHIP, std::string(label) + " upload: " + hipGetErrorString(e));
   return TFHE_HIP_OK;
 }

@@ -438,8 +438,7 @@ int matmul_packed_dev(tfhe_hip_ctx *ctx, const int8_t *w, const uint32_t *bias, 
                       const uint32_t *trlwe, size_t groups, int keyswitch, uint32_t *out, hipStream_t s) {
   if (!keyswitch) return launch_matmul(ctx, MmToeplitz{trlwe}, w, bias, rows, cols, kN + 1, groups, out, s);
   const size_t count = rows * groups;
-  CHK(claim_scratch(ctx, s));
-  CHK(ensure(ctx, ctx->lv1, lv1_bytes(count)));
+  CHK(take(ctx, s, ctx->lv1, lv1_bytes(count)));
   uint32_t *lv1 = (uint32_t *)ctx->lv1.p;
   CHK(launch_matmul(ctx, MmToeplitz{trlwe}, w, bias, rows, cols, kN + 1, groups, lv1, s));
   return launch_key_switch(ctx, s, lv1, out, count);

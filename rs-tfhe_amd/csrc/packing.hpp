@@ -315,7 +315,7 @@ int tfhe_hip_load_packing_key(tfhe_hip_ctx *ctx, const uint8_t mask_seed[32], co
   const tfhe_hip_params &P = ctx->P;
   if (!packing_supported(&P)) return fail(ctx, TFHE_HIP_EINVAL, kPackingRefusal);
   KeyState &k = *ctx->K;
-  CHK(begin_side_key(ctx, k.pk_loaded, k.d_pk8, k.pk_cap, pk_plane_bytes(P.n, P.t)));
+  CHK(begin_side_key(ctx, k.pk_loaded, k.d_pk8, pk_plane_bytes(P.n, P.t)));
   const size_t rows = (size_t)P.n * P.t, body_words = rows * kN;
   const size_t chunks = pk_plane_bytes(P.n, P.t) / 16;
   // the temporary: bodies [n t][N], then the rows [n t][2][N]

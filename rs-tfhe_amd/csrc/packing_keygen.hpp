@@ -52,7 +52,7 @@ int gen_packing_key_locked(tfhe_hip_ctx *ctx, const uint32_t *key_lv0, const uin
                            const ChaChaKey &rk, uint8_t mask_seed[32], uint32_t *bodies) {
   const tfhe_hip_params &P = ctx->P;
   KeyState &k = *ctx->K;
-  CHK(begin_side_key(ctx, k.pk_loaded, k.d_pk8, k.pk_cap, pk_plane_bytes(P.n, P.t)));
+  CHK(begin_side_key(ctx, k.pk_loaded, k.d_pk8, pk_plane_bytes(P.n, P.t)));
   StagedSecrets s(ctx);  // (wiped on every exit path)
   CHK(stage_secrets(ctx, key_lv0, key_lv1, rk, s));
   const uint32_t *d_k0 = s.d_k0;

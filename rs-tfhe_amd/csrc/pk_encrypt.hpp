@@ -181,19 +181,23 @@ int pke_rows_launch(tfhe_hip_ctx *ctx, const ChaChaKey &k, uint64_t first_index,
   const int size = ctx->K->pke_size, steps = pke_steps(size), nblk = (2 * steps + 15) / 16;
   uint32_t *addend = sel + rows * (size_t)(2 * steps);
   const size_t lanes = rows * (size_t)(nblk + 1);
-  CHK(record_begin(ctx, s, ctx->ev_pke_sel));  // (while profiling is on: tfhe_hip_get_pk_encrypt_times)
-  hipLaunchKernelGGL(k_pke_selectors<256>, dim3((unsigned)((lanes + 255) / 256)), dim3(256), 0, s, k, first_index, rows,
-                     size, alpha, key_from ? kSeedDomainRkeSel : kSeedDomainPkeSel,
-                     key_from ? kSeedDomainRkeNoise : kSeedDomainPkeNoise, plain, key_from, P.basebit, P.t, sel, addend);
-  const int rc_sel = launched(ctx);
-  CHK(record_end(ctx, s, ctx->ev_pke_sel));  // the pair is closed whichever way the launch ended
-  CHK(rc_sel);
-  CHK(record_begin(ctx, s, ctx->ev_pke_mm));
-  hipLaunchKernelGGL(k_pke_mfma<kPkeNT>, dim3((unsigned)((rows + 31) / 32), (unsigned)(pke_tiles(P.n) / kPkeNT)), dim3(256),
-                     0, s, sel, addend, rows, P.n, steps, (const unsigned char *)ctx->K->d_pke8, out);
-  const int rc_mm = launched(ctx);
-  CHK(record_end(ctx, s, ctx->ev_pke_mm));
-  CHK(rc_mm);
+  {
+    TimedScope timed(ctx->ev_pke_sel, s, ctx->profiling);  // (while profiling is on: tfhe_hip_get_pk_encrypt_times)
+    CHK(hip_rc(ctx, timed.err));
+    hipLaunchKernelGGL(k_pke_selectors<256>, dim3((unsigned)((lanes + 255) / 256)), dim3(256), 0, s, k, first_index, rows,
+                       size, alpha, key_from ? kSeedDomainRkeSel : kSeedDomainPkeSel,
+                       key_from ? kSeedDomainRkeNoise : kSeedDomainPkeNoise, plain, key_from, P.basebit, P.t, sel, addend);
+    CHK(launched(ctx));  // (the pair is closed whichever way the launch ended)
+    CHK(hip_rc(ctx, timed.close()));
+  }
+  {
+    TimedScope timed(ctx->ev_pke_mm, s, ctx->profiling);
+    CHK(hip_rc(ctx, timed.err));
+    hipLaunchKernelGGL(k_pke_mfma<kPkeNT>, dim3((unsigned)((rows + 31) / 32), (unsigned)(pke_tiles(P.n) / kPkeNT)), dim3(256),
+                       0, s, sel, addend, rows, P.n, steps, (const unsigned char *)ctx->K->d_pke8, out);
+    CHK(launched(ctx));
+    CHK(hip_rc(ctx, timed.close()));
+  }
   HIPCHK(ctx, hipMemsetAsync(sel, 0, pke_sel_words(rows, size) * 4, s));
   return TFHE_HIP_OK;
 }
@@ -201,9 +205,8 @@ int pke_rows_launch(tfhe_hip_ctx *ctx, const ChaChaKey &k, uint64_t first_index,
 // plain [count] -> out [count][n+1] on stream s (device pointers), kPkeChunkRows rows a pass
 int pke_launch(tfhe_hip_ctx *ctx, const ChaChaKey &k, uint64_t first_index, const uint32_t *plain, size_t count,
                double alpha, uint32_t *out, hipStream_t s) {
-  CHK(claim_scratch(ctx, s));  // pke_sel belongs to the context
   const size_t first = count < kPkeChunkRows ? count : kPkeChunkRows;
-  CHK(ensure(ctx, ctx->pke_sel, pke_sel_words(first, ctx->K->pke_size) * 4));
+  CHK(take(ctx, s, ctx->pke_sel, pke_sel_words(first, ctx->K->pke_size) * 4));  // (pke_sel belongs to the context)
   for (size_t lo = 0; lo < count; lo += kPkeChunkRows) {
     const size_t rows = count - lo < kPkeChunkRows ? count - lo : kPkeChunkRows;
     CHK(pke_rows_launch(ctx, k, first_index + lo, rows, alpha, plain + lo, nullptr, (uint32_t *)ctx->pke_sel.p,
@@ -230,7 +233,7 @@ int tfhe_hip_load_public_key(tfhe_hip_ctx *ctx, const uint32_t *encryptions, siz
   const tfhe_hip_params &P = ctx->P;
   KeyState &k = *ctx->K;
   const size_t bytes = pke_plane_bytes(P.n, (int)size), chunks = bytes / 16;
-  CHK(begin_side_key(ctx, k.pke_loaded, k.d_pke8, k.pke_cap, bytes));
+  CHK(begin_side_key(ctx, k.pke_loaded, k.d_pke8, bytes));
   CHK(upload_through_temp(ctx, "public key", {{encryptions, size * (size_t)(P.n + 1) * 4}}, 0, [&](void *d_enc) {
     hipLaunchKernelGGL(k_pke_planes<256>, dim3((unsigned)((chunks + 255) / 256)), dim3(256), 0, ctx->stream,
                        (const uint32_t *)d_enc, k.d_pke8, P.n, (int)size, chunks);
@@ -275,21 +278,8 @@ int tfhe_hip_get_pk_encrypt_times(tfhe_hip_ctx *ctx, tfhe_hip_pk_encrypt_times *
   if (!ctx || !out) return TFHE_HIP_EINVAL;
   ENTER(ctx);
   memset(out, 0, sizeof(*out));
-  auto drain = [&](std::vector<std::pair<hipEvent_t, hipEvent_t>> &v, double &ms, uint64_t *cnt) -> int {
-    for (auto &p : v) {
-      HIPCHK(ctx, hipEventSynchronize(p.second));
-      float t = 0.f;
-      HIPCHK(ctx, hipEventElapsedTime(&t, p.first, p.second));
-      ms += (double)t;
-      if (cnt) ++*cnt;
-      (void)hipEventDestroy(p.first);
-      (void)hipEventDestroy(p.second);
-    }
-    v.clear();
-    return TFHE_HIP_OK;
-  };
-  CHK(drain(ctx->ev_pke_sel, out->selectors_ms, &out->passes));
-  return drain(ctx->ev_pke_mm, out->contraction_ms, nullptr);
+  CHK(hip_rc(ctx, ctx->ev_pke_sel.drain(out->selectors_ms, &out->passes)));
+  return hip_rc(ctx, ctx->ev_pke_mm.drain(out->contraction_ms));
 }
 
 // ---- the asymmetric re-encryption key (proxy_reenc.rs:271-326) --------------------------------------------------

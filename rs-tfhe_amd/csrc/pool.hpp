@@ -16,6 +16,14 @@
 #include <thread>
 
 struct RcclApi;
+namespace {
+struct PoolTimed {  // one bracket of a transfer (see tfhe_hip_pool's transfer timing)
+  OwnEvent a, b;
+  int member = 0;       // whose device the events live on
+  long home_ix = -1;    // RCCL: the call's home-stream pair
+  bool gather = false;  // (ev_home) which direction's group this pair brackets
+};
+}  // namespace
 struct tfhe_hip_pool {
   std::vector<tfhe_hip_ctx *> ctxs;
   tfhe_hip_pool *parent = nullptr;  // non-null: a key view of `parent` (same devices, streams, staging, communicator and mutex)
@@ -30,10 +38,15 @@ struct tfhe_hip_pool {
   bool comms_dropped = false;       // a group failed half-way (pool_drop_comms): streams it touched may never drain
   struct Stage {                    // per member: staging for shards that arrive from / leave for another member's GPU
     DevBuf in[5], out;
-    hipEvent_t done = nullptr;      // recorded on the member's stream when its shard's result has left
+    OwnEvent done;                  // recorded on the member's stream when its shard's result has left
+    // (spelled out only to stay out of the library's dynamic symbols, as the owners in the unnamed namespaces do)
+    Stage() = default;
+    __attribute__((visibility("hidden"))) Stage(Stage &&) = default;
+    __attribute__((visibility("hidden"))) Stage &operator=(Stage &&) = default;
+    __attribute__((visibility("hidden"))) ~Stage() = default;
   };
   std::vector<Stage> stage;
-  hipEvent_t ready = nullptr;       // recorded on the home stream when the call's operands are ready (peer-copy path)
+  OwnEvent ready;                     // recorded on the home stream when the call's operands are ready (peer-copy path)
   int ready_device = -1;
   const char *last_transport = "none";  // transport of the last _dev call: "rccl" / "peer-copy" / "none" (nothing moved)
   // transfer timing (tfhe_hip_pool_get_transfer_times): per moved shard one event pair on the MEMBER's stream (the
@@ -42,12 +55,7 @@ struct tfhe_hip_pool {
   // the pair of the side that arrived last brackets the transfer alone and the other one also brackets its wait for
   // the peer (e.g. the home stream's receive group waits for the slowest member's compute): a shard's transfer time
   // is the SHORTER of its two brackets.
-  struct Timed {
-    hipEvent_t a = nullptr, b = nullptr;
-    int member = 0;    // whose device the events live on
-    long home_ix = -1;  // RCCL: the call's home-stream pair
-    bool gather = false;  // (ev_home) which direction's group this pair brackets
-  };
+  using Timed = PoolTimed;
   bool timing = false;
   std::vector<Timed> ev_scatter, ev_gather, ev_home;
   uint64_t scatter_bytes = 0, gather_bytes = 0, dev_calls = 0;
@@ -382,18 +390,12 @@ int pool_dev_map(tfhe_hip_pool *p, int home, size_t count, void *stream_v, const
   };
   auto ensure_on = [&](int member, DevBuf &b, size_t bytes) -> int {
     if (bytes <= b.cap) return TFHE_HIP_OK;
-    hipError_t e = hipSetDevice(p->ctxs[(size_t)member]->device);
+    const hipError_t e = hipSetDevice(p->ctxs[(size_t)member]->device);
     if (e != hipSuccess) return hipfail("hipSetDevice", e, member);
-    if (b.p) (void)hipFree(b.p);
-    b.p = nullptr;
-    b.cap = 0;
-    const size_t want = bytes + bytes / 4;
-    e = hipMalloc(&b.p, want);
-    if (e != hipSuccess) {
+    if (b.grow(bytes) != hipSuccess) {
       (void)hipGetLastError();
       return pool_fail(p, TFHE_HIP_ENOMEM, "device " + std::to_string(p->ctxs[(size_t)member]->device) + ": hipMalloc pool staging");
     }
-    b.cap = want;
     return TFHE_HIP_OK;
   };
   // transfer timing: begin records the first event of a new pair on `s` and returns the pair's index (-1: off), end
@@ -403,15 +405,11 @@ int pool_dev_map(tfhe_hip_pool *p, int home, size_t count, void *stream_v, const
     if (!root->timing || v.size() >= 4096) return -1;  // (a caller that never collects: stop at 4,096 pending pairs)
     (void)hipSetDevice(p->ctxs[(size_t)member]->device);
     tfhe_hip_pool::Timed t;
-    if (hipEventCreate(&t.a) != hipSuccess) return -1;
-    if (hipEventCreate(&t.b) != hipSuccess) {
-      (void)hipEventDestroy(t.a);
-      return -1;
-    }
+    if (t.a.create() != hipSuccess || t.b.create() != hipSuccess) return -1;
     (void)hipEventRecord(t.a, s);
     t.member = member;
     t.home_ix = home_ix;
-    v.push_back(t);
+    v.push_back(std::move(t));
     return (long)v.size() - 1;
   };
   auto timed_end = [&](TimedVec &v, long idx, hipStream_t s) {
@@ -442,11 +440,11 @@ int pool_dev_map(tfhe_hip_pool *p, int home, size_t count, void *stream_v, const
     CHK(ensure_on(sh.member, st.out, (sh.hi - sh.lo) * out_row_bytes));
     if (!st.done) {
       (void)hipSetDevice(p->ctxs[(size_t)sh.member]->device);
-      const hipError_t e = hipEventCreateWithFlags(&st.done, hipEventDisableTiming);
+      const hipError_t e = st.done.create(hipEventDisableTiming);
       if (e != hipSuccess) return hipfail("hipEventCreate", e, sh.member);
     }
   }
-  auto member_stream = [&](int member) {
+  auto member_stream = [&](int member) -> hipStream_t {
     tfhe_hip_ctx *c = p->ctxs[(size_t)member];
     return (c->parent ? c->parent : c)->stream;
   };
@@ -502,9 +500,7 @@ int pool_dev_map(tfhe_hip_pool *p, int home, size_t count, void *stream_v, const
       hipError_t e = hipSetDevice(hctx->device);
       if (e != hipSuccess) return hipfail("hipSetDevice", e, home);
       if (!root->ready || root->ready_device != hctx->device) {
-        if (root->ready) (void)hipEventDestroy(root->ready);
-        root->ready = nullptr;
-        if ((e = hipEventCreateWithFlags(&root->ready, hipEventDisableTiming)) != hipSuccess) return hipfail("hipEventCreate", e, home);
+        if ((e = root->ready.create(hipEventDisableTiming)) != hipSuccess) return hipfail("hipEventCreate", e, home);
         root->ready_device = hctx->device;
       }
       if ((e = hipEventRecord(root->ready, hrt)) != hipSuccess) return hipfail("hipEventRecord", e, home);
@@ -683,17 +679,8 @@ void tfhe_hip_pool_destroy(tfhe_hip_pool *p) {
       if (c) (void)rccl_api().CommDestroy(c);
   for (size_t i = 0; i < p->stage.size() && i < p->ctxs.size(); ++i) {
     (void)hipSetDevice(p->ctxs[i]->device);
-    for (DevBuf &b : p->stage[i].in)
-      if (b.p) (void)hipFree(b.p);
-    if (p->stage[i].out.p) (void)hipFree(p->stage[i].out.p);
-    if (p->stage[i].done) (void)hipEventDestroy(p->stage[i].done);
+    p->stage[i] = tfhe_hip_pool::Stage();  // (its buffers and its event go here, on their device; the rest with `delete p`)
   }
-  if (p->ready) (void)hipEventDestroy(p->ready);
-  for (auto *v : {&p->ev_scatter, &p->ev_gather, &p->ev_home})
-    for (auto &e : *v) {
-      (void)hipEventDestroy(e.a);
-      (void)hipEventDestroy(e.b);
-    }
   if (prev >= 0) (void)hipSetDevice(prev);
   for (auto *c : p->ctxs) tfhe_hip_ctx_destroy(c);
   delete p;
@@ -1191,10 +1178,6 @@ int tfhe_hip_pool_get_transfer_times(tfhe_hip_pool *p, tfhe_hip_pool_transfer_ti
         if (ms > mx) mx = ms;
       }
     }
-    for (auto &t : v) {
-      (void)hipEventDestroy(t.a);
-      (void)hipEventDestroy(t.b);
-    }
     v.clear();
   };
   drain(root->ev_scatter, out->scatter_ms_sum, out->scatter_ms_max);
@@ -1203,10 +1186,6 @@ int tfhe_hip_pool_get_transfer_times(tfhe_hip_pool *p, tfhe_hip_pool_transfer_ti
   // and for a gather the wait for the slowest member's compute) -- an upper bound of any one transfer in it
   for (size_t i = 0; i < root->ev_home.size(); ++i)
     if (home_ms[i] >= 0) (root->ev_home[i].gather ? out->gather_group_ms_sum : out->scatter_group_ms_sum) += home_ms[i];
-  for (auto &t : root->ev_home) {
-    (void)hipEventDestroy(t.a);
-    (void)hipEventDestroy(t.b);
-  }
   root->ev_home.clear();
   if (prev >= 0) (void)hipSetDevice(prev);
   out->scatter_bytes = root->scatter_bytes;

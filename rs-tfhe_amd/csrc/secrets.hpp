@@ -1,27 +1,12 @@
 // secrets.hpp -- the one path by which a call's secrets reach the device, and by which secrets, plaintexts and decrypted
 // words leave the library's buffers again (host code only).  tests/cpp/test_secret_stage.cpp runs this file as it is,
-// over host memory: the including file supplies the HIP runtime's names and std::string ahead of it and defines fail,
-// ensure and claim_scratch; the context is opaque here.
+// over host memory: the including file supplies the HIP runtime's names, std::string and resources.hpp (DevBuf, Staging)
+// ahead of it and defines fail, ensure and claim_scratch; the context is opaque here.
 #pragma once
 
 struct tfhe_hip_ctx;
 
 namespace {
-
-struct DevBuf {
-  void *p = nullptr;
-  size_t cap = 0;
-};
-struct PinBuf {  // pinned host arena (hipHostMalloc)
-  void *p = nullptr;
-  size_t cap = 0;
-  bool heap = false;  // front-end lanes only: pinned memory was not to be had, this is ordinary memory (copies still work)
-};
-struct Staging {  // a host-API staging buffer on the device and the pinned arena behind it
-  DevBuf dev;
-  PinBuf pin;
-  bool pool_pinned = false;  // pool members route large pageable copies of this slot through `pin`
-};
 
 int fail(tfhe_hip_ctx *ctx, int code, const std::string &msg);
 int ensure(tfhe_hip_ctx *ctx, DevBuf &b, size_t bytes);

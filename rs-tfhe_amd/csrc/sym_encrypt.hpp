@@ -138,7 +138,7 @@ int tfhe_hip_gen_public_key(tfhe_hip_ctx *ctx, const uint32_t *key_lv0, size_t s
   CHK(gk.fill(ctx, rng_key));
   KeyState &k = *ctx->K;
   const size_t bytes = pke_plane_bytes(P.n, (int)size), chunks = bytes / 16, enc_bytes = size * (size_t)(P.n + 1) * 4;
-  CHK(begin_side_key(ctx, k.pke_loaded, k.d_pke8, k.pke_cap, bytes));
+  CHK(begin_side_key(ctx, k.pke_loaded, k.d_pke8, bytes));
   SecretStage sec(ctx, ctx->sym_sec, ctx->stream, sym_sec_bytes(ctx, false), true);  // (wiped on every exit path)
   CHK(sym_land(ctx, sec, gk.k, key_lv0, nullptr));
   CHK(upload_through_temp(ctx, "public key generation", {}, enc_bytes, [&](void *d_enc) -> hipError_t {

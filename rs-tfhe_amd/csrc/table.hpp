@@ -124,19 +124,9 @@ int tfhe_hip_batch_pack_table_dev(tfhe_hip_ctx *ctx, const uint32_t *in, int m, 
 namespace {
 constexpr size_t kBivScratchBytes = (size_t)256 << 20;  // the stage-1 scratch [m][chunk][n+1] never grows past this
 
-// a scratch of the composite: exactly `bytes` (ensure() over-allocates by a quarter, which the bound above excludes)
-int biv_ensure(tfhe_hip_ctx *ctx, DevBuf &b, size_t bytes) {
-  if (bytes <= b.cap) return TFHE_HIP_OK;
-  if (b.p) HIPCHK(ctx, hipFree(b.p));
-  b.p = nullptr;
-  b.cap = 0;
-  const hipError_t e = hipMalloc(&b.p, bytes);
-  if (e != hipSuccess) {
-    b.p = nullptr;
-    return fail(ctx, TFHE_HIP_ENOMEM, std::string("hipMalloc (bivariate scratch): ") + hipGetErrorString(e));
-  }
-  b.cap = bytes;
-  return TFHE_HIP_OK;
+// a scratch of the composite: exactly `bytes` (the quarter of slack is what the bound above excludes)
+int biv_take(tfhe_hip_ctx *ctx, hipStream_t s, ScratchBuf &b, size_t bytes) {
+  return take(ctx, s, b, bytes, true, "hipMalloc (bivariate scratch): ");
 }
 
 // ciphertexts per pass: what the stage-1 scratch bound allows, lowered by TFHE_HIP_BIVARIATE_CHUNK (read at every call: tests)
@@ -165,9 +155,8 @@ const char *bivariate_refusal(const uint32_t *x, const uint32_t *y, const uint32
 int bivariate_launch(tfhe_hip_ctx *ctx, const uint32_t *x, const uint32_t *y, const uint32_t *testvecs, int m, int k,
                      bool keyswitch, uint32_t *out, size_t count, hipStream_t s) {
   const size_t w = (size_t)(ctx->P.n + 1), chunk0 = biv_chunk(ctx, m), first = count < chunk0 ? count : chunk0;
-  CHK(claim_scratch(ctx, s));
-  CHK(biv_ensure(ctx, ctx->biv_s1, (size_t)m * first * w * 4));
-  CHK(biv_ensure(ctx, ctx->biv_tv, trlwe_bytes(first)));
+  CHK(biv_take(ctx, s, ctx->biv_s1, (size_t)m * first * w * 4));
+  CHK(biv_take(ctx, s, ctx->biv_tv, trlwe_bytes(first)));
   uint32_t *S = (uint32_t *)ctx->biv_s1.p, *T = (uint32_t *)ctx->biv_tv.p;
   for (size_t lo = 0; lo < count; lo += chunk0) {
     const size_t cc = count - lo < chunk0 ? count - lo : chunk0;

@@ -130,22 +130,24 @@ class FairMutex {
 
 }  // namespace
 
-#include "secrets.hpp"  // DevBuf, PinBuf, Staging; SecretStage and scrub over them
+#include <deque>
 
+#include "resources.hpp"  // DevBuf, PinBuf, Staging, the scratch claim, the timing pairs: each frees itself
+#include "secrets.hpp"    // SecretStage and scrub over them
+
+namespace {
 // One resident cloud key in the engine layouts (src/key.rs:51-56).  A context owns one (`own`); every key view
 // created with tfhe_hip_key_create owns another and runs on its parent's device, stream, scratch and mutex.
 struct KeyState {
-  double2 *d_bsk = nullptr;
-  uint32_t *d_ksk = nullptr;
-  unsigned char *d_ksk8 = nullptr;  // base-4 sets: the key as signed byte planes in MFMA fragment order (k_ksk_planes)
-  uint32_t *d_testvec = nullptr;
+  DevArray<double2> d_bsk;
+  DevArray<uint32_t> d_ksk;
+  DevArray<unsigned char> d_ksk8;  // base-4 sets: the key as signed byte planes in MFMA fragment order (k_ksk_planes)
+  DevArray<uint32_t> d_testvec;
   // the side keys, as byte planes: beside, not part of, the cloud key (a cloud-key load or change leaves them; freeing
   // the key view frees them)
-  unsigned char *d_pk8 = nullptr;   // the packing key (packing.hpp)
-  size_t pk_cap = 0;                // bytes allocated at d_pk8
+  DevArray<unsigned char> d_pk8;    // the packing key (packing.hpp)
   bool pk_loaded = false;
-  unsigned char *d_pke8 = nullptr;  // the public key (pk_encrypt.hpp)
-  size_t pke_cap = 0;               // bytes allocated at d_pke8
+  DevArray<unsigned char> d_pke8;   // the public key (pk_encrypt.hpp)
   int pke_size = 0;                 // encryptions of zero in the loaded public key
   bool pke_loaded = false;
   uint32_t offset = 0;
@@ -156,21 +158,38 @@ struct KeyState {
   bool reenc_loaded = false;  // d_ksk (+ d_ksk8) hold a proxy re-encryption key (proxy_reenc.rs:224-233) instead of a cloud key's
 };
 
+// the context's own stream (a key view has none)
+struct OwnStream {
+  hipStream_t s = nullptr;
+  OwnStream() = default;
+  OwnStream(const OwnStream &) = delete;
+  OwnStream &operator=(const OwnStream &) = delete;
+  ~OwnStream() {
+    if (s) (void)hipStreamDestroy(s);
+  }
+  operator hipStream_t() const { return s; }
+};
+}  // namespace
+
 struct Combiner;  // combine.hpp: the combining front end of the small host-pointer calls
 
+// Every buffer, arena and event below frees itself when the context is deleted (resources.hpp), in reverse order of
+// declaration: `stream` stands ahead of them all and so outlives them.  tfhe_hip_ctx_destroy drains the streams first.
 struct tfhe_hip_ctx {
   tfhe_hip_params P{};
   int device = 0;
-  hipStream_t stream = nullptr;
+  OwnStream stream;
   KeyState own;
   KeyState *K = &own;            // the key of the call in progress (bound by ENTER under the mutex)
   tfhe_hip_ctx *parent = nullptr;  // non-null: this handle is a key view of `parent` (only P, own, parent are used)
   int views = 0;                 // live key views of this context
   bool dying = false;            // destroyed while views were alive: the last view to go frees the context
-  double2 *d_tw = nullptr;
-  DevBuf lv1, u1, u2, ks_out, ks_dig;  // scratch (ks_dig: key-switch digit bytes)
-  DevBuf biv_s1, biv_tv;               // tree bootstrap (table.hpp): stage-1 results [m][chunk][n+1], their tables [chunk][2][N]
-  DevBuf pke_sel;                      // public-key encryption (pk_encrypt.hpp): selector words and addends of one pass
+  DevArray<double2> d_tw;
+  // scratch, sized through take() alone
+  ScratchBuf lv1, u1, u2, ks_out, ks_dig;  // (ks_dig: key-switch digit bytes)
+  ScratchBuf biv_s1, biv_tv;               // tree bootstrap (table.hpp): stage-1 results [m][chunk][n+1], their tables [chunk][2][N]
+  ScratchBuf pke_sel;                      // public-key encryption (pk_encrypt.hpp): selector words and addends of one pass
+  Scratch scratch;                         // the stream whose queued work may still use them (claim_scratch)
   DevBuf sym_sec;                      // the staged secrets of one call (secrets.hpp: SecretStage), wiped behind it
   // host-API staging: a / b / c / out also stage through their arenas on pool members (to_dev / to_host);
   // the arenas of tv / idx serve the combiner lanes only
@@ -198,15 +217,13 @@ struct tfhe_hip_ctx {
     size_t ks_sl_chunk_min = 384;  // wider bases: smallest batch the column-sliced kernel takes (with K chunks; below: the split kernel)
     bool fast_round = false;  // |pre-rounding value| < 2^51 guaranteed (see round_to_torus<FAST>)
   } dispatch;
-  std::vector<std::pair<hipEvent_t, hipEvent_t>> ev_br, ev_ks;
-  std::vector<std::pair<hipEvent_t, hipEvent_t>> ev_pke_sel, ev_pke_mm;  // pk_encrypt.hpp: the keystream pass, the contraction
+  EventPairs ev_br, ev_ks;              // one pair per launch while profiling is on
+  EventPairs ev_pke_sel, ev_pke_mm;     // pk_encrypt.hpp: the keystream pass, the contraction
   uint64_t bootstraps = 0;
-  hipStream_t scratch_owner = nullptr;  // stream whose queued work may still use the scratch (claim_scratch)
-  bool scratch_owned = false;
   // device diagnostics: [0] shader cycles, [1] constant-rate ticks (both summed over blind-rotate
   // workgroups while profiling is on), [2] error flag raised by kernels (bad gate code), [4] / [5] the same two
   // sums for the matrix-core key switch
-  unsigned long long *d_diag = nullptr;
+  DevArray<unsigned long long> d_diag;
   int rtc_khz = 100000;  // rate of s_memrealtime (hipDeviceAttributeWallClockRate)
   ~tfhe_hip_ctx() { handle_gone(id); }  // (registration and erasure cannot drift apart: every `delete` passes here)
 };
@@ -271,19 +288,41 @@ int fail(tfhe_hip_ctx *ctx, int code, const std::string &msg) {
   return code;
 }
 
+// a runtime call that resources.hpp made for this context
+int hip_rc(tfhe_hip_ctx *ctx, const HipErr &r) {
+  return r ? fail(ctx, TFHE_HIP_EHIP, std::string(r.what) + ": " + hipGetErrorString(r.e)) : TFHE_HIP_OK;
+}
+
 int ensure(tfhe_hip_ctx *ctx, DevBuf &b, size_t bytes) {
-  if (bytes <= b.cap) return TFHE_HIP_OK;
-  if (b.p) HIPCHK(ctx, hipFree(b.p));
-  b.p = nullptr;
-  b.cap = 0;
-  size_t want = bytes + bytes / 4;
-  hipError_t e = hipMalloc(&b.p, want);
-  if (e != hipSuccess) {
-    err_slot(ctx->id) = std::string("hipMalloc scratch: ") + hipGetErrorString(e);
-    return TFHE_HIP_ENOMEM;
-  }
-  b.cap = want;
+  if (const hipError_t e = b.grow(bytes)) return fail(ctx, TFHE_HIP_ENOMEM, std::string("hipMalloc scratch: ") + hipGetErrorString(e));
   return TFHE_HIP_OK;
+}
+
+// A buffer of exactly `bytes` that is allocated once; `call` is how that allocation reads in the text of its failure.
+int alloc_exact(tfhe_hip_ctx *ctx, DevBuf &b, size_t bytes, const char *call) {
+  return hip_rc(ctx, {b.grow(bytes, true), call});
+}
+
+// The intermediate buffers (lv1, u1, u2, the key switch's ks_out and ks_dig, the tree bootstrap's biv_s1 and
+// biv_tv) belong to the context, not to a call.  Work queued on one stream may still be using them when the
+// next call arrives on another stream: drain the previous owner first (same-stream calls are ordered by the
+// stream itself and pay nothing).  take() (below) claims and then sizes; SecretStage claims in its constructor.
+int claim_scratch(tfhe_hip_ctx *ctx, hipStream_t s) { return hip_rc(ctx, ctx->scratch.claim(s)); }
+
+// Waits for the stream that owns the scratch (`unless_own`: not where that is the context's stream, which the caller
+// drains next).
+HipErr sync_scratch_owner(tfhe_hip_ctx *ctx, bool unless_own = false) {
+  const Scratch &sc = ctx->scratch;
+  if (!sc.owned || (unless_own && sc.owner == ctx->stream)) return {};
+  return {hipStreamSynchronize(sc.owner), "hipStreamSynchronize(ctx->scratch_owner)"};
+}
+
+// The scratch buffers are sized here and nowhere else: the claim, then the growth.  `what`
+// names the buffer in the text of a failed allocation.
+int take(tfhe_hip_ctx *ctx, hipStream_t s, ScratchBuf &b, size_t bytes, bool exact = false, const char *what = "hipMalloc scratch: ") {
+  const HipErr r = ctx->scratch.take(s, b, bytes, exact);
+  if (r && !r.what) return fail(ctx, TFHE_HIP_ENOMEM, std::string(what) + hipGetErrorString(r.e));
+  return hip_rc(ctx, r);
 }
 
 // TFHE_HIP_COPY: the plain bootstrap of the first operand, no second one
@@ -296,22 +335,6 @@ bool gate_prep(int gate, GatePrep &g) {
   if (gate < 0 || (uint32_t)gate >= kGateCount) return false;
   g = kGateTable[gate];
   return true;
-}
-
-int record_begin(tfhe_hip_ctx *ctx, hipStream_t s, std::vector<std::pair<hipEvent_t, hipEvent_t>> &v) {
-  if (!ctx->profiling) return TFHE_HIP_OK;
-  hipEvent_t a, b;
-  HIPCHK(ctx, hipEventCreate(&a));
-  HIPCHK(ctx, hipEventCreate(&b));
-  HIPCHK(ctx, hipEventRecord(a, s));
-  v.emplace_back(a, b);
-  return TFHE_HIP_OK;
-}
-
-int record_end(tfhe_hip_ctx *ctx, hipStream_t s, std::vector<std::pair<hipEvent_t, hipEvent_t>> &v) {
-  if (!ctx->profiling) return TFHE_HIP_OK;
-  HIPCHK(ctx, hipEventRecord(v.back().second, s));
-  return TFHE_HIP_OK;
 }
 
 // Small calls are arriving at this context's front end (combine.hpp; defined after it): bulk launches then go out in
@@ -502,10 +525,11 @@ int launch_blind_rotate(tfhe_hip_ctx *ctx, hipStream_t s, const BrCall &c) {
     return S;
   };
   auto launch = [&](br_kernel_t kern, unsigned grid, unsigned threads, size_t lds, const BlindRotateArgs &S) -> int {
-    CHK(record_begin(ctx, s, ctx->ev_br));
+    TimedScope timed(ctx->ev_br, s, ctx->profiling);  // (its pair is closed however the launch goes)
+    CHK(hip_rc(ctx, timed.err));
     hipLaunchKernelGGL(kern, dim3(grid), dim3(threads), lds, s, S);
     HIPCHK(ctx, hipGetLastError());
-    return record_end(ctx, s, ctx->ev_br);
+    return hip_rc(ctx, timed.close());
   };
   BrPlan pl = plan_blind_rotate(ctx, count);
   for (int q = 0; q < pl.nparts; ++q) {
@@ -686,7 +710,7 @@ int build_ksk_planes(tfhe_hip_ctx *ctx) {
   if (!ks_mfma_possible(ctx->P) || (ctx->dispatch.ks_force && ctx->dispatch.ks_force - 1 != KS_MFMA)) return TFHE_HIP_OK;
   const tfhe_hip_params &P = ctx->P;
   const size_t bytes = ks_mfma_key_bytes(P.n, P.t);
-  if (!ctx->K->d_ksk8) HIPCHK(ctx, hipMalloc((void **)&ctx->K->d_ksk8, bytes + kKmKeyTailPad));
+  CHK(alloc_exact(ctx, ctx->K->d_ksk8, bytes + kKmKeyTailPad, "hipMalloc((void **)&ctx->K->d_ksk8, bytes + kKmKeyTailPad)"));
   const size_t chunks = bytes / 16;
   hipLaunchKernelGGL(k_ksk_planes, dim3((unsigned)((chunks + 255) / 256)), dim3(256), 0, ctx->stream, ctx->K->d_ksk,
                      ctx->K->d_ksk8, P.n, P.t, chunks);
@@ -695,11 +719,9 @@ int build_ksk_planes(tfhe_hip_ctx *ctx) {
   return TFHE_HIP_OK;
 }
 
-int claim_scratch(tfhe_hip_ctx *ctx, hipStream_t s);
-
 int launch_key_switch(tfhe_hip_ctx *ctx, hipStream_t s, const uint32_t *lv1, uint32_t *out, size_t count) {
   if (count == 0) return TFHE_HIP_OK;
-  CHK(claim_scratch(ctx, s));  // ks_out and ks_dig are taken here, where they are used: no caller can forget it
+  CHK(claim_scratch(ctx, s));  // (whether or not ks_out or ks_dig is taken below: what is synchronised does not depend on the plan)
   const tfhe_hip_params &P = ctx->P;
   const int n = P.n;
   const KsPlan pl = plan_key_switch(ctx, count);
@@ -708,7 +730,6 @@ int launch_key_switch(tfhe_hip_ctx *ctx, hipStream_t s, const uint32_t *lv1, uin
   // Kernels that merge partial sums with integer atomics need a zeroed DEVICE destination: a host (pinned, zero-copy)
   // output would take the atomics over PCIe, which not every root complex completes (AtomicOps are optional), and
   // silently returns wrong words where it does not -- such outputs go through a device buffer and leave in one copy.
-  // Classified and allocated before the event pair opens, so that a failure here leaves no half-recorded pair behind.
   uint32_t *dst = out;
   bool host_out = false;
   if (pl.atomics) {
@@ -719,72 +740,68 @@ int launch_key_switch(tfhe_hip_ctx *ctx, hipStream_t s, const uint32_t *lv1, uin
     }
     if (at.type == hipMemoryTypeHost) {
       host_out = true;
-      CHK(ensure(ctx, ctx->ks_out, obytes));
+      CHK(take(ctx, s, ctx->ks_out, obytes));
       dst = (uint32_t *)ctx->ks_out.p;
     }
   }
   if (pl.kind == KS_SLICED) {
     const size_t in_launch = count < kKsSl2Slab ? count : kKsSl2Slab;
-    CHK(ensure(ctx, ctx->ks_dig, (size_t)(kN * P.t / 4) * ks_sl2_ct_stride(in_launch, P.basebit, pl.sets) * 4));
+    CHK(take(ctx, s, ctx->ks_dig, (size_t)(kN * P.t / 4) * ks_sl2_ct_stride(in_launch, P.basebit, pl.sets) * 4));
   }
   const int rw4 = ksk_row_words(n) >> 2;
   const int bd = (rw4 + 63) & ~63;  // <= 320 for n <= 1279
   const size_t ksk_bytes = (size_t)kN * P.t * (1u << P.basebit) * ksk_row_words(n) * 4;
-  CHK(record_begin(ctx, s, ctx->ev_ks));
-  auto body = [&]() -> int {
-    if (pl.atomics) HIPCHK(ctx, hipMemsetAsync(dst, 0, obytes, s));
-    switch (pl.kind) {
-      case KS_MFMA: {
-        const int nt = ks_mfma_nt(n);
-        const size_t rb = (count + kKmRows - 1) / kKmRows;
-        const int tiles = ks_mfma_total_tiles(n);
-        const unsigned ncb = (unsigned)(tiles < kKmColBlocks ? tiles : kKmColBlocks);
-        hipLaunchKernelGGL(km_kernel(nt), dim3((unsigned)rb * (unsigned)pl.kparts, ncb, 4), dim3(64 * kKmWaves),
-                           ks_mfma_lds_bytes(nt), s, lv1, (const unsigned char *)ctx->K->d_ksk8, n, P.t, dst, count,
-                           ctx->profiling ? ctx->d_diag + 4 : nullptr, pl.kparts);
-        break;
-      }
-      case KS_SPLIT:
-        // small batch: split each ciphertext's walk over 32 workgroups, merge with integer atomics
-        hipLaunchKernelGGL(k_key_switch_split, dim3((unsigned)count, (unsigned)pl.kparts), dim3(bd), 0, s, lv1,
-                           (const uint4 *)ctx->K->d_ksk, (uint32_t)ksk_bytes, n, P.basebit, P.t, dst);
-        break;
-      case KS_SLICED: {
-        // digits first (k_ks_digits: one byte per (ciphertext, group), [quad of groups][ciphertext]), then the walk;
-        // slabs of kKsSl2Slab ciphertexts bound the digit scratch
-        const int slices = (n + 1 + 63) / 64, rp = ks_sl2_rp(P.basebit);
-        const size_t lds = ks_sl2_lds_bytes(P.basebit, pl.sets, rp);
-        const sl2_kernel_t kern = sl2_kernel(P.basebit, pl.sets);
-        const unsigned quads = (unsigned)(kN * P.t / 4);
-        for (size_t done = 0; done < count; done += kKsSl2Slab) {
-          const size_t m = count - done < kKsSl2Slab ? count - done : kKsSl2Slab;
-          const size_t ct_stride = ks_sl2_ct_stride(m, P.basebit, pl.sets);
-          const uint32_t *src = lv1 + done * (size_t)(kN + 1);
-          hipLaunchKernelGGL(k_ks_digits, dim3((unsigned)((ct_stride + 63) / 64), quads / 32), dim3(256), 0, s, src,
-                             (uint32_t *)ctx->ks_dig.p, ct_stride, m, P.basebit, P.t);
-          const size_t groups = (m + (size_t)ks_sl2_cts(P.basebit, pl.sets) - 1) / (size_t)ks_sl2_cts(P.basebit, pl.sets);
-          hipLaunchKernelGGL(kern, dim3((unsigned)groups, (unsigned)slices, (unsigned)pl.kparts), dim3(64u * (unsigned)ks_sl2_waves(P.basebit)), lds, s,
-                             (const uint32_t *)ctx->ks_dig.p, ct_stride, src, (const unsigned char *)ctx->K->d_ksk, n, P.t,
-                             dst + done * (size_t)(n + 1), m);
-        }
-        break;
-      }
-      case KS_B4:
-        hipLaunchKernelGGL((k_key_switch_b4<kKsG>), dim3((unsigned)((count + kKsG - 1) / kKsG)), dim3(bd),
-                           ks_b4_lds_bytes(bd >> 6, kKsG), s, lv1, (const unsigned char *)ctx->K->d_ksk, n, P.t, dst, count);
-        break;
-      default:
-        hipLaunchKernelGGL((k_key_switch<kKsG>), dim3((unsigned)((count + kKsG - 1) / kKsG)), dim3(bd), 0, s, lv1,
-                           (const uint4 *)ctx->K->d_ksk, (uint32_t)ksk_bytes, n, P.basebit, P.t, dst, count);
-        break;
+  TimedScope timed(ctx->ev_ks, s, ctx->profiling);  // (its pair is closed whichever way the launches go)
+  CHK(hip_rc(ctx, timed.err));
+  if (pl.atomics) HIPCHK(ctx, hipMemsetAsync(dst, 0, obytes, s));
+  switch (pl.kind) {
+    case KS_MFMA: {
+      const int nt = ks_mfma_nt(n);
+      const size_t rb = (count + kKmRows - 1) / kKmRows;
+      const int tiles = ks_mfma_total_tiles(n);
+      const unsigned ncb = (unsigned)(tiles < kKmColBlocks ? tiles : kKmColBlocks);
+      hipLaunchKernelGGL(km_kernel(nt), dim3((unsigned)rb * (unsigned)pl.kparts, ncb, 4), dim3(64 * kKmWaves),
+                         ks_mfma_lds_bytes(nt), s, lv1, (const unsigned char *)ctx->K->d_ksk8, n, P.t, dst, count,
+                         ctx->profiling ? ctx->d_diag + 4 : nullptr, pl.kparts);
+      break;
     }
-    HIPCHK(ctx, hipGetLastError());
-    if (host_out) HIPCHK(ctx, hipMemcpyAsync(out, dst, obytes, hipMemcpyDefault, s));
-    return TFHE_HIP_OK;
-  };
-  const int rc = body();
-  const int rc_end = record_end(ctx, s, ctx->ev_ks);  // the pair is closed whichever way the body ended
-  return rc != TFHE_HIP_OK ? rc : rc_end;
+    case KS_SPLIT:
+      // small batch: split each ciphertext's walk over 32 workgroups, merge with integer atomics
+      hipLaunchKernelGGL(k_key_switch_split, dim3((unsigned)count, (unsigned)pl.kparts), dim3(bd), 0, s, lv1,
+                         (const uint4 *)ctx->K->d_ksk.p, (uint32_t)ksk_bytes, n, P.basebit, P.t, dst);
+      break;
+    case KS_SLICED: {
+      // digits first (k_ks_digits: one byte per (ciphertext, group), [quad of groups][ciphertext]), then the walk;
+      // slabs of kKsSl2Slab ciphertexts bound the digit scratch
+      const int slices = (n + 1 + 63) / 64, rp = ks_sl2_rp(P.basebit);
+      const size_t lds = ks_sl2_lds_bytes(P.basebit, pl.sets, rp);
+      const sl2_kernel_t kern = sl2_kernel(P.basebit, pl.sets);
+      const unsigned quads = (unsigned)(kN * P.t / 4);
+      for (size_t done = 0; done < count; done += kKsSl2Slab) {
+        const size_t m = count - done < kKsSl2Slab ? count - done : kKsSl2Slab;
+        const size_t ct_stride = ks_sl2_ct_stride(m, P.basebit, pl.sets);
+        const uint32_t *src = lv1 + done * (size_t)(kN + 1);
+        hipLaunchKernelGGL(k_ks_digits, dim3((unsigned)((ct_stride + 63) / 64), quads / 32), dim3(256), 0, s, src,
+                           (uint32_t *)ctx->ks_dig.p, ct_stride, m, P.basebit, P.t);
+        const size_t groups = (m + (size_t)ks_sl2_cts(P.basebit, pl.sets) - 1) / (size_t)ks_sl2_cts(P.basebit, pl.sets);
+        hipLaunchKernelGGL(kern, dim3((unsigned)groups, (unsigned)slices, (unsigned)pl.kparts), dim3(64u * (unsigned)ks_sl2_waves(P.basebit)), lds, s,
+                           (const uint32_t *)ctx->ks_dig.p, ct_stride, src, (const unsigned char *)ctx->K->d_ksk.p, n, P.t,
+                           dst + done * (size_t)(n + 1), m);
+      }
+      break;
+    }
+    case KS_B4:
+      hipLaunchKernelGGL((k_key_switch_b4<kKsG>), dim3((unsigned)((count + kKsG - 1) / kKsG)), dim3(bd),
+                         ks_b4_lds_bytes(bd >> 6, kKsG), s, lv1, (const unsigned char *)ctx->K->d_ksk.p, n, P.t, dst, count);
+      break;
+    default:
+      hipLaunchKernelGGL((k_key_switch<kKsG>), dim3((unsigned)((count + kKsG - 1) / kKsG)), dim3(bd), 0, s, lv1,
+                         (const uint4 *)ctx->K->d_ksk.p, (uint32_t)ksk_bytes, n, P.basebit, P.t, dst, count);
+      break;
+  }
+  HIPCHK(ctx, hipGetLastError());
+  if (host_out) HIPCHK(ctx, hipMemcpyAsync(out, dst, obytes, hipMemcpyDefault, s));
+  return hip_rc(ctx, timed.close());
 }
 
 int need_key(tfhe_hip_ctx *ctx) {
@@ -798,17 +815,6 @@ int need_reenc_key(tfhe_hip_ctx *ctx) {
 }
 
 hipStream_t pick(tfhe_hip_ctx *ctx, void *stream) { return stream ? (hipStream_t)stream : ctx->stream; }
-
-// The intermediate buffers (lv1, u1, u2, the key switch's ks_out and ks_dig, the tree bootstrap's biv_s1 and
-// biv_tv) belong to the context, not to a call.  Work queued on one stream may still be using them when the
-// next call arrives on another stream: drain the previous owner first (same-stream calls are ordered by the
-// stream itself and pay nothing).  launch_key_switch claims for itself; its callers' own claims cover lv1 / u1 / u2.
-int claim_scratch(tfhe_hip_ctx *ctx, hipStream_t s) {
-  if (ctx->scratch_owned && ctx->scratch_owner != s) HIPCHK(ctx, hipStreamSynchronize(ctx->scratch_owner));
-  ctx->scratch_owner = s;
-  ctx->scratch_owned = true;
-  return TFHE_HIP_OK;
-}
 
 // ---- device-pointer implementations (mutex held by caller) -------------------
 
@@ -828,8 +834,7 @@ int run_bootstrap(tfhe_hip_ctx *ctx, hipStream_t s, BrCall call, uint32_t *out, 
     return launch_blind_rotate(ctx, s, call);
   }
   const size_t rows = call.count << call.lut_shift;
-  CHK(claim_scratch(ctx, s));
-  CHK(ensure(ctx, ctx->lv1, lv1_bytes(rows)));
+  CHK(take(ctx, s, ctx->lv1, lv1_bytes(rows)));
   call.out_lv1 = (uint32_t *)ctx->lv1.p;
   CHK(launch_blind_rotate(ctx, s, call));
   return launch_key_switch(ctx, s, call.out_lv1, out, rows);
@@ -845,8 +850,7 @@ int gate_dev(tfhe_hip_ctx *ctx, int gate, const uint32_t *a, const uint32_t *b, 
 // proxy_reenc::reencrypt_tlwe_lv0 (proxy_reenc.rs:468-510): pad to the key switch's source shape, then the key switch
 int reencrypt_dev(tfhe_hip_ctx *ctx, const uint32_t *in, uint32_t *out, size_t count, hipStream_t s) {
   if (count == 0) return TFHE_HIP_OK;
-  CHK(claim_scratch(ctx, s));
-  CHK(ensure(ctx, ctx->lv1, lv1_bytes(count)));
+  CHK(take(ctx, s, ctx->lv1, lv1_bytes(count)));
   hipLaunchKernelGGL(k_reenc_pad, dim3((unsigned)count), dim3(256), 0, s, in, (uint32_t *)ctx->lv1.p, ctx->P.n);
   HIPCHK(ctx, hipGetLastError());
   return launch_key_switch(ctx, s, (const uint32_t *)ctx->lv1.p, out, count);
@@ -888,9 +892,8 @@ int lincomb_dev(tfhe_hip_ctx *ctx, GatePrep gp, const uint32_t *a, const uint32_
 
 int mux_dev(tfhe_hip_ctx *ctx, int naive, const uint32_t *a, const uint32_t *b, const uint32_t *c,
             uint32_t *out, size_t count, hipStream_t s) {
-  CHK(claim_scratch(ctx, s));
-  CHK(ensure(ctx, ctx->u1, tlwe_bytes(ctx, count)));
-  CHK(ensure(ctx, ctx->u2, tlwe_bytes(ctx, count)));
+  CHK(take(ctx, s, ctx->u1, tlwe_bytes(ctx, count)));
+  CHK(take(ctx, s, ctx->u2, tlwe_bytes(ctx, count)));
   uint32_t *u1 = (uint32_t *)ctx->u1.p, *u2 = (uint32_t *)ctx->u2.p;
   GatePrep g_and, g_andny;
   gate_prep(TFHE_HIP_AND, g_and);
@@ -911,25 +914,8 @@ int mux_dev(tfhe_hip_ctx *ctx, int naive, const uint32_t *a, const uint32_t *b, 
 // arena of their own: the member's thread copies its slice with memcpy, the DMA engine takes it from there, and
 // no two members meet in the runtime's single pageable-copy staging path.  A lone context keeps the runtime's
 // pipelined pageable copy (one thread cannot memcpy 550 MB faster than that).
-int ensure_pinned(tfhe_hip_ctx *ctx, PinBuf &b, size_t bytes) {
-  if (bytes <= b.cap) return TFHE_HIP_OK;
-  if (b.p && b.heap) free(b.p);
-  else if (b.p) HIPCHK(ctx, hipHostFree(b.p));
-  b.heap = false;
-  b.p = nullptr;
-  b.cap = 0;
-  const size_t want = bytes + bytes / 4;
-  if (hipHostMalloc(&b.p, want, hipHostMallocDefault) != hipSuccess) {
-    (void)hipGetLastError();
-    b.p = nullptr;
-    return TFHE_HIP_ENOMEM;  // caller falls back to the pageable copy
-  }
-  b.cap = want;
-  return TFHE_HIP_OK;
-}
-
-bool via_pin(tfhe_hip_ctx *ctx, Staging &s, size_t bytes) {
-  return ctx->stage_pinned && s.pool_pinned && bytes >= (1u << 20) && ensure_pinned(ctx, s.pin, bytes) == TFHE_HIP_OK;
+bool via_pin(tfhe_hip_ctx *ctx, Staging &s, size_t bytes) {  // (no arena: the caller falls back to the pageable copy)
+  return ctx->stage_pinned && s.pool_pinned && bytes >= (1u << 20) && s.pin.grow(bytes, false);
 }
 
 int to_dev(tfhe_hip_ctx *ctx, Staging &s, const void *src, size_t bytes) {
@@ -1145,14 +1131,14 @@ int tfhe_hip_ctx_create(const tfhe_hip_params *p, int device, tfhe_hip_ctx **out
   ctx->device = device;
   auto bail = [&](const char *what, hipError_t err) {
     g_create_error = std::string(what) + ": " + hipGetErrorString(err);
-    delete ctx;
+    delete ctx;  // (with what it had made so far)
     return TFHE_HIP_EHIP;
   };
   DeviceGuard dg(device);
   if (dg.err != hipSuccess) return bail("hipSetDevice", dg.err);
-  if ((e = hipStreamCreateWithFlags(&ctx->stream, hipStreamNonBlocking)) != hipSuccess)
+  if ((e = hipStreamCreateWithFlags(&ctx->stream.s, hipStreamNonBlocking)) != hipSuccess)
     return bail("hipStreamCreate", e);
-  if ((e = hipMalloc((void **)&ctx->d_diag, 1024)) != hipSuccess) return bail("hipMalloc diagnostics", e);
+  if ((e = ctx->d_diag.grow(1024, true)) != hipSuccess) return bail("hipMalloc diagnostics", e);
   if ((e = hipMemset(ctx->d_diag, 0, 1024)) != hipSuccess) return bail("hipMemset diagnostics", e);
   if (hipDeviceGetAttribute(&ctx->rtc_khz, hipDeviceAttributeWallClockRate, device) != hipSuccess || ctx->rtc_khz <= 0)
     ctx->rtc_khz = 100000;
@@ -1205,7 +1191,7 @@ int tfhe_hip_ctx_create(const tfhe_hip_params *p, int device, tfhe_hip_ctx **out
   }
   std::vector<double2> tw;
   make_twiddles(tw);
-  if ((e = hipMalloc((void **)&ctx->d_tw, tw.size() * sizeof(double2))) != hipSuccess)
+  if ((e = ctx->d_tw.grow(tw.size() * sizeof(double2), true)) != hipSuccess)
     return bail("hipMalloc twiddles", e);
   if ((e = hipMemcpy(ctx->d_tw, tw.data(), tw.size() * sizeof(double2), hipMemcpyHostToDevice)) != hipSuccess)
     return bail("hipMemcpy twiddles", e);
@@ -1222,15 +1208,7 @@ int tfhe_hip_ctx_create(const tfhe_hip_params *p, int device, tfhe_hip_ctx **out
 }
 
 namespace {
-void free_key(KeyState &k) {
-  if (k.d_bsk) (void)hipFree(k.d_bsk);
-  if (k.d_ksk) (void)hipFree(k.d_ksk);
-  if (k.d_ksk8) (void)hipFree(k.d_ksk8);
-  if (k.d_pk8) (void)hipFree(k.d_pk8);
-  if (k.d_pke8) (void)hipFree(k.d_pke8);
-  if (k.d_testvec) (void)hipFree(k.d_testvec);
-  k = KeyState();
-}
+void free_key(KeyState &k) { k = KeyState(); }
 }  // namespace
 
 void tfhe_hip_ctx_destroy(tfhe_hip_ctx *ctx) {
@@ -1242,7 +1220,7 @@ void tfhe_hip_ctx_destroy(tfhe_hip_ctx *ctx) {
       std::lock_guard<FairMutex> lk(base->mu);
       DeviceGuard dg(base->device);
       // (not drain_key_readers: that returns at the first failed synchronisation, and the key is freed here regardless)
-      if (base->scratch_owned && base->scratch_owner != base->stream) (void)hipStreamSynchronize(base->scratch_owner);
+      (void)sync_scratch_owner(base, true);
       if (base->stream) (void)hipStreamSynchronize(base->stream);
       comb_quiesce(base);  // (merged launches run on the lanes' streams)
       free_key(ctx->own);
@@ -1263,33 +1241,9 @@ void tfhe_hip_ctx_destroy(tfhe_hip_ctx *ctx) {
   }
   DeviceGuard dg(ctx->device);
   comb_destroy(ctx);  // the front end's lanes (private sibling contexts) go first
-  if (ctx->scratch_owned && ctx->scratch_owner != ctx->stream) (void)hipStreamSynchronize(ctx->scratch_owner);
+  (void)sync_scratch_owner(ctx, true);
   if (ctx->stream) (void)hipStreamSynchronize(ctx->stream);
-  if (ctx->d_diag) (void)hipFree(ctx->d_diag);
-  for (auto &p : ctx->ev_br) {
-    (void)hipEventDestroy(p.first);
-    (void)hipEventDestroy(p.second);
-  }
-  for (auto &p : ctx->ev_ks) {
-    (void)hipEventDestroy(p.first);
-    (void)hipEventDestroy(p.second);
-  }
-  for (auto *v : {&ctx->ev_pke_sel, &ctx->ev_pke_mm})
-    for (auto &p : *v) {
-      (void)hipEventDestroy(p.first);
-      (void)hipEventDestroy(p.second);
-    }
-  Staging *stage[] = {&ctx->a, &ctx->b, &ctx->c, &ctx->out, &ctx->tv, &ctx->idx};
-  for (DevBuf *b : {&ctx->lv1, &ctx->u1, &ctx->u2, &ctx->ks_out, &ctx->ks_dig, &ctx->biv_s1, &ctx->biv_tv, &ctx->pke_sel, &ctx->sym_sec})
-    if (b->p) (void)hipFree(b->p);
-  for (Staging *s : stage)
-    if (s->dev.p) (void)hipFree(s->dev.p);
-  free_key(ctx->own);
-  for (Staging *s : stage)
-    if (s->pin.p) s->pin.heap ? free(s->pin.p) : (void)hipHostFree(s->pin.p);
-  if (ctx->d_tw) (void)hipFree(ctx->d_tw);
-  if (ctx->stream) (void)hipStreamDestroy(ctx->stream);
-  delete ctx;
+  delete ctx;  // nothing is queued any more: the buffers, arenas and events go, then the stream
 }
 
 // ---- key views: several resident cloud keys on ONE context ------------------------------------------------
@@ -1930,29 +1884,18 @@ int tfhe_hip_get_kernel_times(tfhe_hip_ctx *ctx, tfhe_hip_kernel_times *out) {
   if (!ctx || !out) return TFHE_HIP_EINVAL;
   ENTER(ctx);
   memset(out, 0, sizeof(*out));
-  auto drain = [&](std::vector<std::pair<hipEvent_t, hipEvent_t>> &v, double &ms, uint64_t &cnt) -> int {
-    for (auto &p : v) {
-      HIPCHK(ctx, hipEventSynchronize(p.second));
-      float t = 0.f;
-      HIPCHK(ctx, hipEventElapsedTime(&t, p.first, p.second));
-      ms += (double)t;
-      ++cnt;
-      (void)hipEventDestroy(p.first);
-      (void)hipEventDestroy(p.second);
-    }
-    v.clear();
-    return TFHE_HIP_OK;
+  auto drain = [&](tfhe_hip_ctx *x) -> int {
+    CHK(hip_rc(ctx, x->ev_br.drain(out->blind_rotate_ms, &out->blind_rotate_launches)));
+    return hip_rc(ctx, x->ev_ks.drain(out->key_switch_ms, &out->key_switch_launches));
   };
-  CHK(drain(ctx->ev_br, out->blind_rotate_ms, out->blind_rotate_launches));
-  CHK(drain(ctx->ev_ks, out->key_switch_ms, out->key_switch_launches));
+  CHK(drain(ctx));
   out->bootstraps = ctx->bootstraps;
   ctx->bootstraps = 0;
   int lane_rc = TFHE_HIP_OK;  // merged launches of small calls ran on the front end's lanes
   comb_with_idle_lanes(ctx, [&](Combiner &C) {
     for (tfhe_hip_ctx *x : C.lane_ctx) {
       if (!x) continue;
-      if (lane_rc == TFHE_HIP_OK) lane_rc = drain(x->ev_br, out->blind_rotate_ms, out->blind_rotate_launches);
-      if (lane_rc == TFHE_HIP_OK) lane_rc = drain(x->ev_ks, out->key_switch_ms, out->key_switch_launches);
+      if (lane_rc == TFHE_HIP_OK) lane_rc = drain(x);
       out->bootstraps += x->bootstraps;
       x->bootstraps = 0;
     }
@@ -1960,14 +1903,17 @@ int tfhe_hip_get_kernel_times(tfhe_hip_ctx *ctx, tfhe_hip_kernel_times *out) {
   return lane_rc;
 }
 
-int tfhe_hip_get_clock_sample(tfhe_hip_ctx *ctx, tfhe_hip_clock_sample *out) {
+// the two sums at d_diag[at], [at + 1] since the last sample
+static int clock_sample(tfhe_hip_ctx *ctx, int at, tfhe_hip_clock_sample *out) {
   if (!ctx || !out) return TFHE_HIP_EINVAL;
   ENTER(ctx);
-  if (ctx->scratch_owned) HIPCHK(ctx, hipStreamSynchronize(ctx->scratch_owner));
+  CHK(hip_rc(ctx, sync_scratch_owner(ctx)));
   HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
   unsigned long long h[2] = {0, 0};
-  HIPCHK(ctx, hipMemcpy(h, ctx->d_diag, 16, hipMemcpyDeviceToHost));
-  HIPCHK(ctx, hipMemset(ctx->d_diag, 0, 16));
+  const char *const copy = at ? "hipMemcpy(h, ctx->d_diag + 4, 16, hipMemcpyDeviceToHost)" : "hipMemcpy(h, ctx->d_diag, 16, hipMemcpyDeviceToHost)";
+  const char *const zero = at ? "hipMemset(ctx->d_diag + 4, 0, 16)" : "hipMemset(ctx->d_diag, 0, 16)";
+  CHK(hip_rc(ctx, {hipMemcpy(h, ctx->d_diag + at, 16, hipMemcpyDeviceToHost), copy}));
+  CHK(hip_rc(ctx, {hipMemset(ctx->d_diag + at, 0, 16), zero}));
   out->shader_cycles = h[0];
   out->rtc_ticks = h[1];
   out->rtc_mhz = ctx->rtc_khz / 1000.0;
@@ -1975,20 +1921,8 @@ int tfhe_hip_get_clock_sample(tfhe_hip_ctx *ctx, tfhe_hip_clock_sample *out) {
   return TFHE_HIP_OK;
 }
 
-int tfhe_hip_get_key_switch_clock_sample(tfhe_hip_ctx *ctx, tfhe_hip_clock_sample *out) {
-  if (!ctx || !out) return TFHE_HIP_EINVAL;
-  ENTER(ctx);
-  if (ctx->scratch_owned) HIPCHK(ctx, hipStreamSynchronize(ctx->scratch_owner));
-  HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-  unsigned long long h[2] = {0, 0};
-  HIPCHK(ctx, hipMemcpy(h, ctx->d_diag + 4, 16, hipMemcpyDeviceToHost));
-  HIPCHK(ctx, hipMemset(ctx->d_diag + 4, 0, 16));
-  out->shader_cycles = h[0];
-  out->rtc_ticks = h[1];
-  out->rtc_mhz = ctx->rtc_khz / 1000.0;
-  out->shader_mhz = h[1] ? (double)h[0] / (double)h[1] * out->rtc_mhz : 0.0;
-  return TFHE_HIP_OK;
-}
+int tfhe_hip_get_clock_sample(tfhe_hip_ctx *ctx, tfhe_hip_clock_sample *out) { return clock_sample(ctx, 0, out); }
+int tfhe_hip_get_key_switch_clock_sample(tfhe_hip_ctx *ctx, tfhe_hip_clock_sample *out) { return clock_sample(ctx, 4, out); }
 
 int tfhe_hip_describe_dispatch(tfhe_hip_ctx *ctx, size_t count, char *buf, size_t buflen) {
   if (!ctx || !buf || buflen == 0) return TFHE_HIP_EINVAL;
@@ -2067,15 +2001,15 @@ int tfhe_hip_host_alloc(size_t bytes, void **out) {
 }
 
 void tfhe_hip_host_free(void *p) {
-  if (p) (void)hipHostFree(p);
+  pinned_free(p);
 }
 
 int tfhe_hip_synchronize(tfhe_hip_ctx *ctx) {
   if (!ctx) return TFHE_HIP_EINVAL;
   ENTER(ctx);
-  if (ctx->scratch_owned && ctx->scratch_owner != ctx->stream) HIPCHK(ctx, hipStreamSynchronize(ctx->scratch_owner));
+  CHK(hip_rc(ctx, sync_scratch_owner(ctx, true)));
   HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-  ctx->scratch_owned = false;
+  ctx->scratch.owned = false;
   uint32_t flag = 0;
   HIPCHK(ctx, hipMemcpy(&flag, ctx->d_diag + 2, 4, hipMemcpyDeviceToHost));
   if (flag) {

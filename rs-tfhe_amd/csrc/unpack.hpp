@@ -81,8 +81,7 @@ namespace {
 // extraction into the context's lv1 scratch, then the key switch of the bootstrap path over `count` rows
 int unpack_dev(tfhe_hip_ctx *ctx, const uint32_t *trlwe, size_t groups, const uint32_t *slots, size_t count,
                uint32_t *out, hipStream_t s) {
-  CHK(claim_scratch(ctx, s));
-  CHK(ensure(ctx, ctx->lv1, lv1_bytes(count)));
+  CHK(take(ctx, s, ctx->lv1, lv1_bytes(count)));
   uint32_t *lv1 = (uint32_t *)ctx->lv1.p;
   hipLaunchKernelGGL((k_unpack_extract<kN / 4, kUpRows>), dim3((unsigned)((count + kUpRows - 1) / kUpRows)), dim3(kN / 4), 0, s,
                      trlwe, groups, slots, count, lv1);

@@ -12,8 +12,10 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <deque>
 #include <initializer_list>
 #include <string>
+#include <utility>
 #include <vector>
 
 #include "../../include/tfhe_hip.h"
@@ -58,6 +60,22 @@ static hipError_t hipStreamSynchronize(hipStream_t s) {
   return g_fail_sync ? hipErrorStandIn : hipSuccess;
 }
 
+// what resources.hpp (DevBuf, Staging) names beside those: the buffers here are the test's own memory, which it frees
+// itself, so a free does nothing and nothing is ever allocated or timed
+typedef void *hipEvent_t;
+enum { hipHostMallocDefault = 0, hipEventDefault = 0 };
+static hipError_t hipGetLastError() { return hipSuccess; }
+static hipError_t hipMalloc(void **, size_t) { return hipErrorStandIn; }
+static hipError_t hipFree(void *) { return hipSuccess; }
+static hipError_t hipHostMalloc(void **, size_t, unsigned) { return hipErrorStandIn; }
+static hipError_t hipHostFree(void *) { return hipSuccess; }
+static hipError_t hipEventCreateWithFlags(hipEvent_t *, unsigned) { return hipErrorStandIn; }
+static hipError_t hipEventDestroy(hipEvent_t) { return hipSuccess; }
+static hipError_t hipEventRecord(hipEvent_t, hipStream_t) { return hipErrorStandIn; }
+static hipError_t hipEventSynchronize(hipEvent_t) { return hipErrorStandIn; }
+static hipError_t hipEventElapsedTime(float *, hipEvent_t, hipEvent_t) { return hipErrorStandIn; }
+
+#include "../../rs-tfhe_amd/csrc/resources.hpp"
 #include "../../rs-tfhe_amd/csrc/secrets.hpp"
 
 struct tfhe_hip_ctx {
