@@ -990,7 +990,11 @@ int tfhe_hip_get_key_switch_clock_sample(tfhe_hip_ctx *ctx, tfhe_hip_clock_sampl
  *   TFHE_HIP_BR_KERNEL = auto | batch | single | pair            (default auto) run that blind-rotation kernel at
  *                                                                 every batch size instead of picking per size
  *   TFHE_HIP_KS_KERNEL = auto | mfma | sliced | b4 | generic | split  (default auto) likewise for the key switch;
- *                        creation fails with TFHE_HIP_EINVAL when the parameter set cannot run the kernel named
+ *                        creation fails with TFHE_HIP_EINVAL when the parameter set cannot run the kernel named:
+ *                        mfma needs basebit = 2, 6 <= t <= 13 and n <= 767 (24 column tiles); sliced needs
+ *                        4 <= basebit <= 7; b4 needs basebit = 2 and n <= 1023 (four waves a row: the ring of five
+ *                        passes 64 KiB of LDS); generic and split run every accepted set.  Within these bounds every
+ *                        kernel returns identity_key_switching word for word (tests/test_gpu_ks_shapes.py)
  *   TFHE_HIP_POOL_RCCL = 0 | 1 | 2    pools: 0 never use RCCL (peer copies only), 1 (default) RCCL when the pool's
  *                                      devices are distinct, 2 also for a pool of one (plumbing test)
  *   TFHE_HIP_POOL_PINNED_STAGING = 0 | 1   pools: stage pageable operands through per-member pinned arenas

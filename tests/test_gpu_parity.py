@@ -186,11 +186,11 @@ def test_key_switch_bit_exact(O, eng128, keys128):
     ("SECURITY_128_BIT", "auto"),      # default dispatch: split kernel below 64, matrix cores (K in chunks) from 64
     ("SECURITY_128_BIT", "b4"),        # k_key_switch_b4 (LDS ring, base 4) at every count
     ("SECURITY_128_BIT", "generic"),   # k_key_switch (buffer loads)
-    ("SECURITY_128_BIT", "mfma"),      # k_key_switch_mfma<11> (int8 matrix cores), t = 9; K chunks picked per launch (16 ... 4 here)
+    ("SECURITY_128_BIT", "mfma"),      # k_key_switch_mfma<11> (int8 matrix cores), t = 9, 11 + 11 tiles; K chunks picked per launch (16 ... 4 here)
     ("SECURITY_128_BIT", "split"),     # k_key_switch_split at every count
-    ("SECURITY_110_BIT", "mfma"),      # k_key_switch_mfma<5>, t = 8, 5,5,5,5 tiles
-    ("SECURITY_80_BIT", "mfma"),       # k_key_switch_mfma<5>, t = 7, 5,5,4,4 tiles
-    ("SECURITY_UINT1", "mfma"),        # k_key_switch_mfma<6>, t = 8
+    ("SECURITY_110_BIT", "mfma"),      # k_key_switch_mfma<10>, t = 8, 10 + 10 tiles in the two column blocks
+    ("SECURITY_80_BIT", "mfma"),       # k_key_switch_mfma<9>, t = 7, 9 + 9 tiles
+    ("SECURITY_UINT1", "mfma"),        # k_key_switch_mfma<11>, t = 8 (the other tile counts: test_gpu_ks_shapes.py)
     ("SECURITY_UINT4", "auto"),        # split below 384, k_key_switch_sliced2 (base 32) from there: sets per lane and K chunks per launch
     ("SECURITY_UINT4", "sliced"),      # ... at every count (64 / 32 / 16 K chunks at these counts)
     ("SECURITY_UINT4", "generic"),     # k_key_switch (generic) at base 32
