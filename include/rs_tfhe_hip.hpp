@@ -666,6 +666,67 @@ inline PackingKey PackingKey::generate(const SecretKey &sk, int device, const ui
   return pk;
 }
 
+// A TRLWE switching key of include/tfhe_hip.h ("TRLWE key switch"): the automorphism k, the decomposition (basebit, t),
+// the public mask seed and the bodies [t][N].  k = 1 from one secret key to another is the packed re-encryption key;
+// k != 1 with the same secret key twice is a Galois key.  The key switches on a key view of its own (load), which goes
+// with the last copy of the object.
+struct TrlweSwitchKey {
+  SecurityParams params = DEFAULT_SECURITY;
+  int k = 1, basebit = 4, t = 6;
+  std::array<uint8_t, 32> mask_seed{};
+  std::vector<Torus> bodies;  // [t][N]
+  size_t nbytes() const { return bodies.size() * sizeof(Torus) + mask_seed.size(); }
+  // Generated on the GPU (tfhe_hip_gen_trlwe_switch_key) in a key view that is dropped afterwards.  rng_key: the 32-byte
+  // generator key K (one K serves one key per k), or nullptr to draw it from getrandom(2); alpha < 0: the set's alpha_lv1.
+  static TrlweSwitchKey generate(const SecretKey &from, const SecretKey &to, int k = 1, int basebit = 4, int t = 6,
+                                 int device = 0, const uint8_t *rng_key = nullptr, double alpha = -1) {
+    if (!(from.params == to.params)) throw std::runtime_error("the two secret keys belong to different parameter sets");
+    Engine &e = Engine::for_params(from.params, device);
+    TrlweSwitchKey key;
+    key.params = from.params;
+    key.k = k, key.basebit = basebit, key.t = t;
+    size_t words = 0;
+    if (tfhe_hip_trlwe_switch_key_words(t, &words) != TFHE_HIP_OK) throw std::runtime_error("TrlweSwitchKey: t out of range");
+    key.bodies.resize(words);
+    tfhe_hip_ctx *view = nullptr;
+    e.check(tfhe_hip_key_create(e.ctx(), &view));
+    std::unique_ptr<tfhe_hip_ctx, void (*)(tfhe_hip_ctx *)> h(view, tfhe_hip_ctx_destroy);  // dropped on every exit
+    const int rc = tfhe_hip_gen_trlwe_switch_key(view, from.key_lv1.data(), to.key_lv1.data(), k, basebit, t,
+                                                 alpha < 0 ? key.params.alpha_lv1 : alpha, rng_key, key.mask_seed.data(),
+                                                 key.bodies.data());
+    if (rc != TFHE_HIP_OK) throw std::runtime_error(std::string("tfhe_hip: ") + tfhe_hip_last_error(view));
+    return key;
+  }
+  // (S, bodies) expanded on a key view of the engine of (params, device); done once per object and device
+  void load(int device = 0) {
+    if (view_ && device_ == device && tfhe_hip_trlwe_switch_key_is_loaded(view_.get(), k)) return;
+    if (bodies.size() != (size_t)t * N) throw std::runtime_error("TrlweSwitchKey: bodies must be [t][N]");
+    Engine &e = Engine::for_params(params, device);
+    tfhe_hip_ctx *view = nullptr;
+    e.check(tfhe_hip_key_create(e.ctx(), &view));
+    view_.reset(view, tfhe_hip_ctx_destroy);
+    device_ = device;
+    const int rc = tfhe_hip_load_trlwe_switch_key(view, k, basebit, t, mask_seed.data(), bodies.data());
+    if (rc != TFHE_HIP_OK) {
+      const std::string msg = std::string("tfhe_hip: ") + tfhe_hip_last_error(view);
+      view_.reset();
+      throw std::runtime_error(msg);
+    }
+  }
+  // in [count][2][N] packed ciphertexts -> psi_k of them under the target key (tfhe_hip_batch_trlwe_keyswitch)
+  std::vector<Torus> switch_batch(const Torus *in, size_t count, int device = 0) {
+    load(device);
+    std::vector<Torus> out(count * 2 * (size_t)N);
+    const int rc = tfhe_hip_batch_trlwe_keyswitch(view_.get(), k, in, count, out.data());
+    if (rc != TFHE_HIP_OK) throw std::runtime_error(std::string("tfhe_hip: ") + tfhe_hip_last_error(view_.get()));
+    return out;
+  }
+
+ private:
+  std::shared_ptr<tfhe_hip_ctx> view_;
+  int device_ = -1;
+};
+
 namespace tlwe {
 inline Torus inner_product(const Ciphertext &c, const std::vector<Torus> &key) {
   Torus ip = 0;

@@ -432,6 +432,94 @@ int tfhe_hip_batch_trlwe_polymul(tfhe_hip_ctx *ctx, const int8_t *w, const uint3
 int tfhe_hip_batch_trlwe_polymul_dev(tfhe_hip_ctx *ctx, const int8_t *w, const uint32_t *bias, size_t rows, size_t cols,
                                      const uint32_t *trlwe, size_t groups, uint32_t *out, void *stream);
 
+/* ---- TRLWE key switch: packed re-encryption and slot automorphisms ------
+ *
+ * The one operation that takes a TRLWE lv1 under one ring key to a TRLWE lv1 under another.  With psi_k the
+ * automorphism X -> X^k, a key that encrypts g_l * psi_k(s_from) under s_to takes a ciphertext under s_from to the
+ * ciphertext of psi_k(phase) under s_to.  k = 1 with s_from != s_to is packed proxy re-encryption: 1,024 values in one
+ * step per 8 KiB ciphertext, where tfhe_hip_batch_reencrypt takes 2,804 bytes per value.  k != 1 with
+ * s_from = s_to = s1 is a Galois key: ct(X) -> ct(X^k) permutes the slots beyond the rotations of a product with
+ * +-X^k, and the chain ct <- ct + switch_k(ct) over k = N/2^(s-1) + 1, s = 1 .. steps, is the partial trace that
+ * clears the by-product slots of a packed product (rs_tfhe_amd.packing.trace).
+ *
+ * Definition (normative).  N = 1024; all arithmetic wraps mod 2^32; negation is the exact 0 - x, as in the packed
+ * matmul, not Torus::MAX - x.
+ *   Automorphism.  psi_k, k odd, 1 <= k < 2N, of a polynomial p: coefficient j goes to position j k mod 2N; a position
+ *     P >= N is position P - N with the value negated.  psi_1 is the identity; psi_k psi_k' = psi_(k k' mod 2N).
+ *   Switching key for (k, beta, t): 1 <= beta <= 7 (B = 2^beta; the negated digits fit a signed byte), 1 <= t <= 64
+ *     (K = t N <= 65,536 keeps the byte-plane accumulators of the product at or below 2^30) and beta t <= 32.  t TRLWE
+ *     rows under s_to; row l < t, with g_l = 2^(32 - (l+1) beta):
+ *       a_l  N keystream words under a public 32-byte mask seed S (RFC 8439 block, word x = word x mod 16 of counter
+ *            x / 16, natural order, as for the packing key), nonce (64 k + l, 27, 0x544B53);
+ *       b_l  = a_l (*) s_to + e_l + g_l * psi_k(s_from), every coefficient mod 2^32, the gadget polynomial added after
+ *            the product; e_l = f64_to_torus(N(0, alpha)) per coefficient.
+ *     Only the bodies travel: bodies [t][N] u32 (24 KiB at t = 6).
+ *   Digits of a word x.  The packing key switch's rounding and decomposition ("packing key switch", Digits) with this
+ *     key's (beta, t): a_bar, the carry chain and d_l in [-B/2, B/2), sum_l d_l g_l = a_bar 2^(32 - beta t).  At
+ *     beta t = 32 nothing is rounded: a_bar = x.
+ *   Switch.  For ct = (a, b):  a' = psi_k(a), b' = psi_k(b), D_l(X) = sum_j d_l(a'[j]) X^j,
+ *       out.a = - sum_l D_l (*) a_l,        out.b = b' - sum_l D_l (*) b_l        (negacyclic mod X^N + 1).
+ *     in and out are [count][2][N] u32, the a row then the b row of each.
+ * Consequences.  The phase out.b - out.a (*) s_to equals psi_k(b - a (*) s_from) plus a rounding error and the key
+ *   noise.  With a binary key of about N/2 ones, per coefficient the rounding error has variance about
+ *   (N/2) * 2^(-2 beta t) / 12 and the key noise about N * t * (B^2 / 12) * alpha^2 (torus units squared).  The result
+ *   is defined in integers: every device gives these words exactly.  A ten-step trace (ct <- ct + switch(ct), ten
+ *   times) multiplies what it keeps by 2^10 and leaves noise of variance 4^10 (V_in + V_switch / 3).  Safe choices -- 8
+ *   standard deviations of (a fresh encryption at alpha_lv1 plus the switches) inside the decoding half-interval, 1/8
+ *   for a boolean and 1/64 for an m = 16 message, key noise at alpha_lv1 of the set (DESIGN.md section 9 has the table):
+ *     one switch           (4, 6) on every set, booleans and m = 16 (8 sigma <= 1.1e-4).
+ *     ten-step trace, bool (4, 6) on every set (8 sigma <= 0.064 on SECURITY_80_BIT).
+ *     ten-step trace, m=16 (4, 6) on SECURITY_UINT2 .. UINT8 (8 sigma = 1.8e-3); (2, 12) on SECURITY_128_BIT and UINT1
+ *                          (1.2e-2; (4, 6) gives 3.4e-2: not safe); (1, 24) on SECURITY_110_BIT (1.3e-2); none on
+ *                          SECURITY_80_BIT ((1, 24) gives 1.61e-2 against 1.56e-2): take m = 8 there.
+ * Generation (normative).  Under a 32-byte generator key K (secret; generation only):
+ *   Mask seed   S = words 0..7 of block(K, counter 0, nonce (0, 29, 0x444553)).
+ *   Noise       e_l under K, nonce (64 k + l, 28, 0x544B53), in the BSK generators' word order, as for the packing key.
+ *   Product     a_l (*) s_to is exact (|coefficient| < 2^41).
+ *   Sharing K   One K serves ONE key per k: the nonce row 64 k + l (l < 64) gives every (k, l) its own noise sample,
+ *               and streams 27 / 28 / 29 are no other generator's, so the same K may also be given to
+ *               tfhe_hip_gen_packing_key and the cloud-key generators.  Two keys for the same k under one K (another
+ *               (beta, t), or other secrets) would share noise samples: use another K.
+ *   Away from samples that sit within rounding of a torus step every implementation gives the same bodies.
+ * Semantics.  A context or key view holds up to 16 switching keys, found by k, each with its own (beta, t); the k = 1
+ *   entry is the re-encryption key.  They live beside the cloud key like the packing key: loading or generating a
+ *   cloud key leaves them, destroying a view frees them.  A switch needs no other key.  TFHE_HIP_ENOKEY when no key
+ *   for k is loaded (switch, drop).  TFHE_HIP_EINVAL, with the previous entry for k still loaded and answering: k even
+ *   or out of range, beta or t out of range or beta t > 32, a seventeenth key, NULL pointers (with count > 0 for the
+ *   switch), alpha negative or NaN, count > 2^31 - 1.  count == 0 returns TFHE_HIP_OK and writes nothing.  out must not
+ *   overlap in (the _dev form does not check it).  Bulk calls: the context's mutex and the one staging path of the
+ *   host-pointer form, never the combining front end.  _dev: device pointers, queued on `stream` (NULL: the context's
+ *   stream); the digits pass through a scratch of the context, 2,048 ciphertexts a pass.  There are no pool forms. */
+/* Word count of `bodies` for t rows.  Initialises no device. */
+int tfhe_hip_trlwe_switch_key_words(int t, size_t *body_words);
+/* The switching key (k, basebit, t) from key_from_lv1 [N] to key_to_lv1 [N], made on the device.  A CLIENT-side call: it
+ * takes secret keys.  Writes S to mask_seed and, unless `bodies` is NULL, the bodies [t][N]; the handle is left holding
+ * the key -- bit for bit the one tfhe_hip_load_trlwe_switch_key(k, basebit, t, mask_seed, bodies) builds from the
+ * outputs.  rng_key: K from the caller's CSPRNG, or NULL to draw it from getrandom(2). */
+int tfhe_hip_gen_trlwe_switch_key(tfhe_hip_ctx *ctx, const uint32_t *key_from_lv1, const uint32_t *key_to_lv1, int k,
+                                  int basebit, int t, double alpha, const uint8_t rng_key[32], uint8_t mask_seed[32],
+                                  uint32_t *bodies);
+/* Uploads the bodies and expands the key on the device (masks from S). */
+int tfhe_hip_load_trlwe_switch_key(tfhe_hip_ctx *ctx, int k, int basebit, int t, const uint8_t mask_seed[32],
+                                   const uint32_t *bodies);
+/* 0 / 1, never an error code (no device call is made). */
+int tfhe_hip_trlwe_switch_key_is_loaded(tfhe_hip_ctx *ctx, int k);
+/* Frees the key for k. */
+int tfhe_hip_drop_trlwe_switch_key(tfhe_hip_ctx *ctx, int k);
+/* in [count][2][N] -> out [count][2][N] under the key for k. */
+int tfhe_hip_batch_trlwe_keyswitch(tfhe_hip_ctx *ctx, int k, const uint32_t *in, size_t count, uint32_t *out);
+int tfhe_hip_batch_trlwe_keyswitch_dev(tfhe_hip_ctx *ctx, int k, const uint32_t *in, size_t count, uint32_t *out,
+                                       void *stream);
+/* While profiling is enabled (tfhe_hip_set_profiling) the two steps of every pass of the switch -- the digits kernel, and
+ * the contraction (the product's kernel and its bias kernel) -- are bracketed by HIP events on the stream they run on.
+ * Synchronises the recorded events, returns the sums since the last call and resets them. */
+typedef struct tfhe_hip_trlwe_switch_times {
+  double digits_ms;      /* sum of the digits kernel durations                  */
+  double contraction_ms; /* sum of the matrix-core contraction durations        */
+  uint64_t passes;       /* passes of each (one per 2,048 ciphertexts)          */
+} tfhe_hip_trlwe_switch_times;
+int tfhe_hip_get_trlwe_switch_times(tfhe_hip_ctx *ctx, tfhe_hip_trlwe_switch_times *out);
+
 /* ---- encrypted 2-D convolution: int8 filters over a feature map of LWE ciphertexts ------
  *
  * The convolutional layer beside the linear one: `out_c` plaintext int8 filters of k_h x k_w x in_c slide over an

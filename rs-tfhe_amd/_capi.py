@@ -60,6 +60,12 @@ class PoolTransferTimes(C.Structure):
                 ("scatter_group_ms_sum", C.c_double), ("gather_group_ms_sum", C.c_double)]
 
 
+class TrlweSwitchTimes(C.Structure):
+    """struct tfhe_hip_trlwe_switch_times"""
+
+    _fields_ = [("digits_ms", C.c_double), ("contraction_ms", C.c_double), ("passes", C.c_uint64)]
+
+
 class CombineStats(C.Structure):
     """struct tfhe_hip_combine_stats"""
 
@@ -121,6 +127,14 @@ SIGNATURES = {
     "tfhe_hip_batch_trlwe_matmul_dev": (C.c_int, [_CTX, _P, _P, _SZ, _SZ, _P, _SZ, C.c_int, _P, _P]),
     "tfhe_hip_batch_trlwe_polymul": (C.c_int, [_CTX, _P, _P, _SZ, _SZ, _P, _SZ, _P]),
     "tfhe_hip_batch_trlwe_polymul_dev": (C.c_int, [_CTX, _P, _P, _SZ, _SZ, _P, _SZ, _P, _P]),
+    "tfhe_hip_trlwe_switch_key_words": (C.c_int, [C.c_int, C.POINTER(_SZ)]),
+    "tfhe_hip_gen_trlwe_switch_key": (C.c_int, [_CTX, _P, _P, C.c_int, C.c_int, C.c_int, C.c_double, _P, _P, _P]),
+    "tfhe_hip_load_trlwe_switch_key": (C.c_int, [_CTX, C.c_int, C.c_int, C.c_int, _P, _P]),
+    "tfhe_hip_trlwe_switch_key_is_loaded": (C.c_int, [_CTX, C.c_int]),
+    "tfhe_hip_drop_trlwe_switch_key": (C.c_int, [_CTX, C.c_int]),
+    "tfhe_hip_batch_trlwe_keyswitch": (C.c_int, [_CTX, C.c_int, _P, _SZ, _P]),
+    "tfhe_hip_batch_trlwe_keyswitch_dev": (C.c_int, [_CTX, C.c_int, _P, _SZ, _P, _P]),
+    "tfhe_hip_get_trlwe_switch_times": (C.c_int, [_CTX, C.POINTER(TrlweSwitchTimes)]),
     "tfhe_hip_batch_tlwe_conv2d": (C.c_int, [_CTX, C.POINTER(Conv2dShape), _P, _P, _P, _SZ, _P]),
     "tfhe_hip_batch_tlwe_conv2d_dev": (C.c_int, [_CTX, C.POINTER(Conv2dShape), _P, _P, _P, _SZ, _P, _P]),
     "tfhe_hip_batch_pack_table": (C.c_int, [_CTX, _P, C.c_int, _SZ, _P]),

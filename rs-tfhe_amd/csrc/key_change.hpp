@@ -14,7 +14,8 @@
 //    quiesces the lanes and synchronises the whole device first, and the old flag stands until the commit;
 //  - the pool's broadcast replication splits begin (prepare_replica) and commit (finish_replica) around the
 //    broadcast, which runs outside the member's call, and synchronises the whole device before the commit;
-// The side keys -- the packing key (packing.hpp, packing_keygen.hpp) and the public key (pk_encrypt.hpp) -- have their
+// The side keys -- the packing key (packing.hpp, packing_keygen.hpp), the public key (pk_encrypt.hpp) and the sixteen
+// TRLWE switching keys (trlwe_switch.hpp: plain rows, one flag an entry) -- have their
 // own flags and byte planes, which are not the key switch's, and their own, smaller pair: begin_side_key drains the
 // whole device, clears the side key's flag and grows its planes; the route fills them; commit_side_key sets the flag
 // LAST.  A cloud-key change leaves them alone, and validation comes before the begin here too.
@@ -163,22 +164,26 @@ struct GeneratorKey {
 // whichever way it ends: they travel through one SecretStage (secrets.hpp) on the context's stream, which zeroes the
 // buffer and drains the stream on every exit path.  The generator key travels in the buffer too (not in
 // kernel-argument memory).  The layout: K, the slot derive_public_seed writes, key_lv0 [n], key_lv1 [N], and the
-// spectrum of key_lv1, which k_key_spectrum writes (16-byte aligned: it is read as double2).
+// spectrum of key_lv1, which k_key_spectrum writes (16-byte aligned: it is read as double2).  The TRLWE switching key
+// (trlwe_switch.hpp) stages a ring key where key_lv0 stands: k0_words = N, d_k0 the key switched from, d_k1 the key
+// switched to.
 struct StagedSecrets {
+  size_t k0_words;  // words of the first key: n, or N for a ring key
   SecretStage stage;
   const uint32_t *d_k0 = nullptr, *d_k1 = nullptr;
   const double2 *d_spec = nullptr;
   ChaChaKey *d_rk = nullptr;  // the derived-seed slot is d_rk + 1
-  explicit StagedSecrets(tfhe_hip_ctx *ctx)
-      : stage(ctx, ctx->sym_sec, ctx->stream, 2 * sizeof(ChaChaKey) + ((size_t)ctx->P.n + kN) * 4, true) {}
+  explicit StagedSecrets(tfhe_hip_ctx *ctx) : StagedSecrets(ctx, (size_t)ctx->P.n) {}
+  StagedSecrets(tfhe_hip_ctx *ctx, size_t k0_words)
+      : k0_words(k0_words), stage(ctx, ctx->sym_sec, ctx->stream, 2 * sizeof(ChaChaKey) + (k0_words + kN) * 4, true) {}
 };
 static_assert(2 * sizeof(ChaChaKey) + ((size_t)kLweMaxN + kN) * 4 <= kSecretImageMax, "the largest image a call stages");
 // Use: `StagedSecrets s(ctx); CHK(stage_secrets(ctx, ..., s));`
 int stage_secrets(tfhe_hip_ctx *ctx, const uint32_t *key_lv0, const uint32_t *key_lv1, const ChaChaKey &rk, StagedSecrets &s) {
-  const size_t k0_at = 2 * sizeof(ChaChaKey), k1_at = k0_at + (size_t)ctx->P.n * 4;
+  const size_t k0_at = 2 * sizeof(ChaChaKey), k1_at = k0_at + s.k0_words * 4;
   const size_t spec_at = (k1_at + (size_t)kN * 4 + 15) & ~(size_t)15;
   s.stage.put(&rk, sizeof(ChaChaKey), 0);
-  s.stage.put(key_lv0, (size_t)ctx->P.n * 4, k0_at);
+  s.stage.put(key_lv0, s.k0_words * 4, k0_at);
   s.stage.put(key_lv1, (size_t)kN * 4, k1_at);
   CHK(s.stage.land("key generation: ", spec_at + (size_t)kN2 * sizeof(double2)));
   s.d_rk = s.stage.dev<ChaChaKey>(0);

@@ -150,10 +150,18 @@ struct KeyState {
   DevArray<unsigned char> d_pke8;   // the public key (pk_encrypt.hpp)
   int pke_size = 0;                 // encryptions of zero in the loaded public key
   bool pke_loaded = false;
+  // the TRLWE switching keys (trlwe_switch.hpp), found by k: plain rows [t][2][N], the B operand of MmNegacyclic
+  struct TrlweSwitchKey {
+    int k = 0, basebit = 0, t = 0;
+    DevArray<uint32_t> rows;
+    bool loaded = false;
+  };
+  static constexpr int kMaxTrlweSwitchKeys = 16;
+  TrlweSwitchKey tsk[kMaxTrlweSwitchKeys];
   uint32_t offset = 0;
   // The flags are written in key_change.hpp only: begin_key_change clears both, commit_cloud_key sets key_loaded (and
-  // clears reenc_loaded), commit_reenc_key sets reenc_loaded; begin_side_key clears pk_loaded or pke_loaded and
-  // commit_side_key sets it.
+  // clears reenc_loaded), commit_reenc_key sets reenc_loaded; begin_side_key clears pk_loaded, pke_loaded or a
+  // switching key's `loaded` and commit_side_key sets it.
   bool key_loaded = false;
   bool reenc_loaded = false;  // d_ksk (+ d_ksk8) hold a proxy re-encryption key (proxy_reenc.rs:224-233) instead of a cloud key's
 };
@@ -189,6 +197,7 @@ struct tfhe_hip_ctx {
   ScratchBuf lv1, u1, u2, ks_out, ks_dig;  // (ks_dig: key-switch digit bytes)
   ScratchBuf biv_s1, biv_tv;               // tree bootstrap (table.hpp): stage-1 results [m][chunk][n+1], their tables [chunk][2][N]
   ScratchBuf pke_sel;                      // public-key encryption (pk_encrypt.hpp): selector words and addends of one pass
+  ScratchBuf ts_dig;                       // TRLWE key switch (trlwe_switch.hpp): digit planes [chunk][t][N] i8, then b' [chunk][N]
   Scratch scratch;                         // the stream whose queued work may still use them (claim_scratch)
   DevBuf sym_sec;                      // the staged secrets of one call (secrets.hpp: SecretStage), wiped behind it
   // host-API staging: a / b / c / out also stage through their arenas on pool members (to_dev / to_host);
@@ -219,6 +228,7 @@ struct tfhe_hip_ctx {
   } dispatch;
   EventPairs ev_br, ev_ks;              // one pair per launch while profiling is on
   EventPairs ev_pke_sel, ev_pke_mm;     // pk_encrypt.hpp: the keystream pass, the contraction
+  EventPairs ev_ts_dig, ev_ts_mm;       // trlwe_switch.hpp: the digits pass, the contraction
   uint64_t bootstraps = 0;
   // device diagnostics: [0] shader cycles, [1] constant-rate ticks (both summed over blind-rotate
   // workgroups while profiling is on), [2] error flag raised by kernels (bad gate code), [4] / [5] the same two
@@ -2032,3 +2042,4 @@ int tfhe_hip_synchronize(tfhe_hip_ctx *ctx) {
 #include "sym_encrypt.hpp"
 #include "decrypt.hpp"
 #include "trlwe_encrypt.hpp"
+#include "trlwe_switch.hpp"

@@ -766,6 +766,71 @@ class Engine(_Handle):
         self._call("batch_trlwe_polymul_dev", C.c_void_p(w.data_ptr()), self._tp(None, bias), rows, cols,
                    self._tp(None, trlwe), groups, self._tp(None, out), self._stream_ptr(None, stream))
 
+    # -- TRLWE key switch (include/tfhe_hip.h): packed re-encryption and slot automorphisms --------------------------------
+    def gen_trlwe_switch_key(self, key_from_lv1, key_to_lv1, k: int = 1, basebit: int = 4, t: int = 6,
+                             rng_key: bytes = None, alpha=None, download: bool = True):
+        """The switching key (k, basebit, t) from ring key `key_from_lv1` to `key_to_lv1`, generated on the GPU
+        (`tfhe_hip_gen_trlwe_switch_key`) and left loaded on this handle under k.  rng_key: the 32-byte generator key
+        K (one K serves one key per k), None draws it from getrandom(2); alpha: alpha_lv1 of the set by default.
+        Returns the packing.TrlweSwitchKey, or None with download=False (the bodies stay on the GPU)."""
+        from .packing import TrlweSwitchKey
+
+        k1, k2 = _u32(key_from_lv1).reshape(-1), _u32(key_to_lv1).reshape(-1)
+        if len(k1) != N or len(k2) != N:
+            raise ValueError(f"ring keys are {N} words")
+        rk = None
+        if rng_key is not None:
+            if len(rng_key) != 32:
+                raise ValueError("rng_key is 32 bytes")
+            rk = (C.c_uint8 * 32).from_buffer_copy(bytes(rng_key))
+        seed = (C.c_uint8 * 32)()
+        bodies = np.empty((max(int(t), 0), N), np.uint32) if download else None
+        self._call("gen_trlwe_switch_key", _ptr(k1), _ptr(k2), int(k), int(basebit), int(t),
+                   C.c_double(self.params.alpha_lv1 if alpha is None else alpha),
+                   C.addressof(rk) if rk is not None else None, C.addressof(seed), _ptr(bodies))
+        return TrlweSwitchKey(int(k), int(basebit), int(t), bytes(seed), bodies) if download else None
+
+    def load_trlwe_switch_key(self, key) -> None:
+        """packing.TrlweSwitchKey (k, basebit, t, mask seed, bodies [t][N]) -> this handle, beside its cloud key, under
+        key.k (`tfhe_hip_load_trlwe_switch_key`); up to 16 keys a handle."""
+        bodies = _u32(key.bodies).reshape(-1)
+        seed = (C.c_uint8 * 32).from_buffer_copy(_seed_bytes(key.mask_seed))
+        self._call("load_trlwe_switch_key", int(key.k), int(key.basebit), int(key.t), C.addressof(seed), _ptr(bodies))
+
+    def trlwe_switch_key_is_loaded(self, k: int) -> bool:
+        return self._lib.tfhe_hip_trlwe_switch_key_is_loaded(self._ctx, int(k)) == 1
+
+    def drop_trlwe_switch_key(self, k: int) -> None:
+        self._call("drop_trlwe_switch_key", int(k))
+
+    def batch_trlwe_keyswitch(self, k: int, trlwe, out=None, stream=None):
+        """psi_k of [count][2][N] packed ciphertexts (or [2][N]: one) under the key loaded for k, under that key's target
+        secret (`tfhe_hip_batch_trlwe_keyswitch`).  numpy in, numpy out; or a 32-bit CUDA tensor [count][2][N] on this
+        engine's GPU in and a tensor out (`out`: where to write, which must not overlap the input; a new tensor by
+        default), queued on `stream` (torch's current stream by default)."""
+        if _is_tensor(trlwe):
+            import torch
+
+            if trlwe.dim() != 3 or tuple(trlwe.shape[1:]) != (2, N):
+                raise ValueError(f"trlwe must be [count][2][{N}]")
+            if out is None:
+                out = torch.empty_like(trlwe)
+            elif tuple(out.shape) != tuple(trlwe.shape):
+                raise ValueError("out must have the input's shape")
+            self._call("batch_trlwe_keyswitch_dev", int(k), self._tp(None, trlwe), int(trlwe.shape[0]), self._tp(None, out),
+                       self._stream_ptr(None, stream))
+            return out
+        trlwe = _u32(trlwe).reshape(-1, 2, N)
+        res = np.empty_like(trlwe)
+        self._call("batch_trlwe_keyswitch", int(k), _ptr(trlwe), len(trlwe), _ptr(res))
+        return res
+
+    def trlwe_switch_times(self) -> dict:
+        """Kernel times of the TRLWE key switch's passes since the last call (profiling on)."""
+        t = _capi.TrlweSwitchTimes()
+        self._chk(self._lib.tfhe_hip_get_trlwe_switch_times(self._ctx, C.byref(t)))
+        return {"digits_ms": t.digits_ms, "contraction_ms": t.contraction_ms, "passes": int(t.passes)}
+
     # -- encrypted 2-D convolution (include/tfhe_hip.h): int8 filters over a feature map of ciphertexts -------------------
     def _conv2d_shape(self, w_shape, cts_shape, bias_len, stride, padding):
         """(struct tfhe_hip_conv2d_shape, groups, (out_h, out_w)) of filters [out_c][k_h][k_w][in_c] over a map

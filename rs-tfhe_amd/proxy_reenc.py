@@ -337,3 +337,68 @@ class ProxyReencryptionKey:
 def reencrypt_tlwe_lv0(ct_from, reenc_key: ProxyReencryptionKey, device: int = 0) -> np.ndarray:
     """proxy_reenc.rs:468: the free function of the reference; accepts a batch as well."""
     return reenc_key.reencrypt(ct_from, device)
+
+
+class PackedReencryptionKey:
+    """Proxy re-encryption of PACKED ciphertexts: the TRLWE switching key at k = 1 from Alice's ring key to Bob's
+    (include/tfhe_hip.h, "TRLWE key switch").  One step per 8 KiB ciphertext of 1,024 values with a key of t N words
+    (24 KiB at t = 6), where the lv0 route above takes one re-encryption of 4 (n + 1) bytes per value.  Symmetric only:
+    it is made with both secret keys (an asymmetric, public-key variant is not offered)."""
+
+    def __init__(self, params: SecurityParams, key):
+        if key.k != 1:
+            raise ValueError("a re-encryption key is the switching key at k = 1")
+        self.params = params
+        self.key = key  # packing.TrlweSwitchKey
+        self._view = None
+
+    @classmethod
+    def new_symmetric(cls, alice_sk: SecretKey, bob_sk: SecretKey, basebit: int = 4, t: int = 6, rng_key=None,
+                      device: int = 0) -> "PackedReencryptionKey":
+        """Generated on GPU `device` (`tfhe_hip_gen_trlwe_switch_key`) in a key view that is closed again: the secrets
+        do not stay on the device.  rng_key: the 32-byte generator key, None draws it from getrandom(2); the noise is
+        alpha_lv1 of the set."""
+        if alice_sk.params != bob_sk.params:
+            raise ValueError("the two secret keys belong to different parameter sets")
+        from .bootstrap import engine_for
+
+        view = engine_for(alice_sk.params, device).new_key_view()
+        try:
+            key = view.gen_trlwe_switch_key(alice_sk.key_lv1, bob_sk.key_lv1, 1, basebit, t,
+                                            rng_key=None if rng_key is None else _rng_key(rng_key))
+        finally:
+            view.close()
+        return cls(alice_sk.params, key)
+
+    def view(self, device: int = 0):
+        """The key view that holds this key (created and loaded on first use; `close()` frees it)."""
+        if self._view is None or self._view[0] != device:
+            from .bootstrap import engine_for
+
+            self.close()
+            v = engine_for(self.params, device).new_key_view()
+            v.load_trlwe_switch_key(self.key)
+            self._view = (device, v)
+        return self._view[1]
+
+    def close(self) -> None:
+        if getattr(self, "_view", None) is not None:
+            self._view[1].close()
+            self._view = None
+
+    def __enter__(self) -> "PackedReencryptionKey":
+        return self
+
+    def __exit__(self, *exc) -> None:
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def reencrypt(self, packed, device: int = 0) -> np.ndarray:
+        """[count][2][N] (or one [2][N]) packed ciphertexts under Alice's key -> the same under Bob's."""
+        arr = np.ascontiguousarray(packed, dtype=np.uint32)
+        return self.view(device).batch_trlwe_keyswitch(1, arr).reshape(arr.shape)

@@ -143,6 +143,14 @@ extern "C" {   // packing key switch (include/tfhe_hip.h): up to N lv0 results i
                                     groups: usize, out: *mut u32) -> c_int;
     fn tfhe_hip_expand_seeded_trlwe_dev(ctx: *mut TfheHipCtx, mask_seed: *const u8, first_group: u64, bodies: *const u32,
                                         groups: usize, out: *mut u32, stream: *mut c_void) -> c_int;
+    // TRLWE key switch (include/tfhe_hip.h): packed re-encryption (k = 1) and slot automorphisms; no pool forms
+    fn tfhe_hip_trlwe_switch_key_words(t: c_int, body_words: *mut usize) -> c_int;
+    fn tfhe_hip_gen_trlwe_switch_key(ctx: *mut TfheHipCtx, key_from_lv1: *const u32, key_to_lv1: *const u32, k: c_int,
+                                     basebit: c_int, t: c_int, alpha: f64, rng_key: *const u8, mask_seed: *mut u8,
+                                     bodies: *mut u32) -> c_int;
+    fn tfhe_hip_load_trlwe_switch_key(ctx: *mut TfheHipCtx, k: c_int, basebit: c_int, t: c_int, mask_seed: *const u8,
+                                      bodies: *const u32) -> c_int;
+    fn tfhe_hip_batch_trlwe_keyswitch(ctx: *mut TfheHipCtx, k: c_int, input: *const u32, count: usize, out: *mut u32) -> c_int;
 }
 
 /// TFHE_HIP_DECRYPT_*: what `HipEngine::decrypt_batch` and `decrypt_trlwe` return per ciphertext
@@ -746,6 +754,53 @@ impl HipEngine {
         let ctx = tfhe_hip_pool_ctx(self.pool, 0);
         assert!(!ctx.is_null(), "tfhe_hip_pool_ctx failed");
         Self::check_ctx(ctx, tfhe_hip_expand_seeded_trlwe_dev(ctx, mask_seed.as_ptr(), first_group, bodies, groups, out, stream));
+    }
+
+    /// A TRLWE switching key (include/tfhe_hip.h, "TRLWE key switch") from ring key `key_from` [N] to `key_to` [N] for the
+    /// automorphism X -> X^k, generated on the GPU (`tfhe_hip_gen_trlwe_switch_key`): returns (the public mask seed, the
+    /// bodies [t][N]) and leaves the key loaded under k on the pool's first member.  k = 1 with two different keys is the
+    /// packed re-encryption key, k != 1 with the same key twice a Galois key.  A client-side call: it takes secret keys.
+    /// `alpha`: the noise's standard deviation (params::trgsw_lv1::ALPHA is the set's); `rng_key`: the 32-byte generator
+    /// key (one key per k under it), None draws it from getrandom(2).
+    pub fn gen_trlwe_switch_key(&self, key_from: &[u32], key_to: &[u32], k: c_int, basebit: c_int, t: c_int, alpha: f64,
+                                rng_key: Option<&[u8; 32]>) -> ([u8; 32], Vec<u32>) {
+        assert_eq!(key_from.len(), N, "key_from is [N]");
+        assert_eq!(key_to.len(), N, "key_to is [N]");
+        let mut words: usize = 0;
+        assert_eq!(unsafe { tfhe_hip_trlwe_switch_key_words(t, &mut words) }, 0, "t is out of range");
+        let mut seed = [0u8; 32];
+        let mut bodies = vec![0u32; words];
+        let ctx = unsafe { tfhe_hip_pool_ctx(self.pool, 0) };
+        assert!(!ctx.is_null(), "tfhe_hip_pool_ctx failed");
+        let rk = rng_key.map_or(std::ptr::null(), |key| key.as_ptr());
+        Self::check_ctx(ctx, unsafe {
+            tfhe_hip_gen_trlwe_switch_key(ctx, key_from.as_ptr(), key_to.as_ptr(), k, basebit, t, alpha, rk, seed.as_mut_ptr(),
+                                          bodies.as_mut_ptr())
+        });
+        (seed, bodies)
+    }
+    /// (mask_seed, bodies [t][N]) of a switching key expanded on the pool's first member and held there under k
+    /// (`tfhe_hip_load_trlwe_switch_key`); up to 16 keys a handle, a key for the same k is replaced.
+    pub fn load_trlwe_switch_key(&self, k: c_int, basebit: c_int, t: c_int, mask_seed: &[u8; 32], bodies: &[u32]) {
+        let mut words: usize = 0;
+        assert_eq!(unsafe { tfhe_hip_trlwe_switch_key_words(t, &mut words) }, 0, "t is out of range");
+        assert_eq!(bodies.len(), words, "bodies is [t][N]");
+        let ctx = unsafe { tfhe_hip_pool_ctx(self.pool, 0) };
+        assert!(!ctx.is_null(), "tfhe_hip_pool_ctx failed");
+        Self::check_ctx(ctx, unsafe { tfhe_hip_load_trlwe_switch_key(ctx, k, basebit, t, mask_seed.as_ptr(), bodies.as_ptr()) });
+    }
+    /// psi_k of packed ciphertexts ([count][2][N], flat) under the key loaded for k, under that key's target secret
+    /// (`tfhe_hip_batch_trlwe_keyswitch`).  Returns [count][2][N], flat.  Runs on the pool's first member.
+    pub fn trlwe_keyswitch(&self, k: c_int, trlwe: &[u32]) -> Vec<u32> {
+        assert_eq!(trlwe.len() % (2 * N), 0, "trlwe is [count][2][N]");
+        let mut out = vec![0u32; trlwe.len()];
+        if trlwe.is_empty() {
+            return out;
+        }
+        let ctx = unsafe { tfhe_hip_pool_ctx(self.pool, 0) };
+        assert!(!ctx.is_null(), "tfhe_hip_pool_ctx failed");
+        Self::check_ctx(ctx, unsafe { tfhe_hip_batch_trlwe_keyswitch(ctx, k, trlwe.as_ptr(), trlwe.len() / (2 * N), out.as_mut_ptr()) });
+        out
     }
 
     /// PublicKeyLv0::new_with_params (src/proxy_reenc.rs:144-153) on the GPU (`tfhe_hip_gen_public_key`): `size`
