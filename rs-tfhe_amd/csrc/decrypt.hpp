@@ -26,7 +26,7 @@
 // over the context's `sym_sec` buffer: the host copy is wiped, the buffer zeroed behind the kernel on the same stream.
 #pragma once
 #include "decrypt_decode.hpp"
-#include "sym_encrypt.hpp"
+#include "internal.hpp"
 
 static_assert(kDecryptPhase == TFHE_HIP_DECRYPT_PHASE && kDecryptBool == TFHE_HIP_DECRYPT_BOOL &&
                   kDecryptMessage == TFHE_HIP_DECRYPT_MESSAGE,

@@ -20,20 +20,13 @@
 // whole device, clears the side key's flag and grows its planes; the route fills them; commit_side_key sets the flag
 // LAST.  A cloud-key change leaves them alone, and validation comes before the begin here too.
 // ctx->mu is held and ctx's device is current in everything below.
+// Part of tfhe_hip.hip.  What the feature units use of it -- the begin / commit pairs, the staged secrets, the row
+// launches -- is declared in internal.hpp, with the types and the sizes of the key buffers.
 #pragma once
 
 namespace {
-
-// ---- sizes of the key buffers (engine layouts), once -----------------------------------------------------------------
-inline size_t bsk_polys(const tfhe_hip_params &P) { return (size_t)P.n * 2 * P.l * 2; }
-inline size_t bsk_bytes(const tfhe_hip_params &P) { return bsk_polys(P) * kN * sizeof(double); }
-inline size_t ksk_rows(const tfhe_hip_params &P) { return (size_t)kN * P.t * ((size_t)1 << P.basebit); }
-inline size_t ksk_bytes(const tfhe_hip_params &P) { return ksk_rows(P) * ksk_row_words(P.n) * 4; }
 // d_ksk is allocated this much longer: the key switch's row DMAs read past the end of the last row (key_switch.hpp)
 constexpr size_t kKskTailPad = 4096;
-inline size_t key_testvec_bytes() { return testvec_bytes(0, 1); }
-
-enum KeyBufs { KEY_BUF_BSK = 1, KEY_BUF_KSK = 2, KEY_BUF_TESTVEC = 4, KEY_BUF_ALL = 7 };
 
 // the only allocator of d_bsk / d_ksk / d_testvec (they go with their KeyState)
 int ensure_key_buffers(tfhe_hip_ctx *ctx, int which) {
@@ -55,6 +48,7 @@ int drain_key_readers(tfhe_hip_ctx *ctx) {
   comb_quiesce(ctx);
   return TFHE_HIP_OK;
 }
+}  // namespace
 
 // `which`: KEY_BUF_ALL for a cloud key, KEY_BUF_KSK for a re-encryption key (d_ksk is shared between the two, hence
 // both flags go)
@@ -87,7 +81,6 @@ int begin_side_key(tfhe_hip_ctx *ctx, bool &flag, DevBuf &planes, size_t bytes) 
   flag = false;
   return alloc_exact(ctx, planes, bytes, "hipMalloc((void **)&planes, bytes)");
 }
-void commit_side_key(bool &flag) { flag = true; }
 
 // The *_is_loaded calls: 0 / 1, never an error code, no device call.  No lock: the host mirrors ask this before EVERY
 // call (is the view's key resident yet?), and the context's mutex may be held for the length of a 65,536-ciphertext
@@ -99,33 +92,18 @@ int flag_is_loaded(tfhe_hip_ctx *ctx, bool KeyState::*flag) {
   return __atomic_load_n(&(ctx->own.*flag), __ATOMIC_ACQUIRE) ? 1 : 0;
 }
 
-// ---- host key -> device, converted ----------------------------------------------------------------------------------
-// A device temporary of the sources' bytes plus `extra_bytes`; the sources copied into it back to back on ctx->stream;
-// launch(temporary) -> hipError_t queues the conversion; the stream drained and the temporary freed on every path.
-struct HostSrc {
-  const void *p;
-  size_t bytes;
-};
-template <class Launch>
-int upload_through_temp(tfhe_hip_ctx *ctx, const char *label, std::initializer_list<HostSrc> srcs, size_t extra_bytes,
-                        Launch &&launch) {
-  size_t total = extra_bytes;
-  for (const HostSrc &s : srcs) total += s.bytes;
-  DevArray<char> d_tmp;
-  CHK(alloc_exact(ctx, d_tmp, total, "hipMalloc((void **)&d_tmp, total)"));
-  hipError_t e = hipSuccess;
-  size_t at = 0;
-  for (const HostSrc &s : srcs) {
-    if (e == hipSuccess) e = hipMemcpyAsync(d_tmp + at, s.p, s.bytes, hipMemcpyHostToDevice, ctx->stream);
-    at += s.bytes;
-  }
-  if (e == hipSuccess) e = launch(d_tmp.p);
-  const hipError_t es = hipStreamSynchronize(ctx->stream);  // (nothing reads the temporary once this has returned)
-  if (e == hipSuccess) e = es;
-  if (e != hipSuccess) return fail(ctx, TFHE_HIP_EHIP, std::string(label) + " upload: " + hipGetErrorString(e));
-  return TFHE_HIP_OK;
+// ---- the key-switching key between its two layouts ---------------------------------------------------------------------
+hipError_t ksk_convert_launch(tfhe_hip_ctx *ctx, const uint32_t *d_ref, size_t rows) {
+  hipLaunchKernelGGL(k_ksk_convert, dim3((unsigned)rows), dim3(256), 0, ctx->stream, d_ref, ctx->K->d_ksk, ctx->P.n,
+                     1 << ctx->P.basebit, rows);
+  return hipGetLastError();
+}
+hipError_t ksk_export_launch(tfhe_hip_ctx *ctx, uint32_t *d_ref, size_t rows) {
+  hipLaunchKernelGGL(k_ksk_export, dim3((unsigned)rows), dim3(256), 0, ctx->stream, ctx->K->d_ksk, d_ref, ctx->P.n, rows);
+  return hipGetLastError();
 }
 
+namespace {
 // the kernel's CSPRNG, as the reference's thread_rng is seeded (OsRng)
 int os_random(uint8_t *buf, size_t bytes) {  // 0, or errno
   size_t got = 0;
@@ -141,44 +119,23 @@ int os_random(uint8_t *buf, size_t bytes) {  // 0, or errno
 }
 std::string os_random_text(int err) { return std::string("getrandom: ") + strerror(err); }
 
-// The 256-bit generator key K of one call: the caller's rng_key, or (NULL) 32 bytes of getrandom(2).  Wiped when the call
-// leaves, whichever way.
-struct GeneratorKey {
-  ChaChaKey k{};
-  GeneratorKey() = default;
-  GeneratorKey(const GeneratorKey &) = delete;
-  GeneratorKey &operator=(const GeneratorKey &) = delete;
-  int fill(tfhe_hip_ctx *ctx, const uint8_t *rng_key) {
-    if (rng_key) {
-      memcpy(k.k, rng_key, 32);  // 8 little-endian words
-    } else if (const int err = os_random((uint8_t *)k.k, sizeof(k.k))) {
-      return fail(ctx, TFHE_HIP_EHIP, os_random_text(err));
-    }
-    return TFHE_HIP_OK;
-  }
-  ~GeneratorKey() { wipe_host(k.k, sizeof(k.k)); }
-};
+}  // namespace
 
-// ---- key generation: the secrets on the device -----------------------------------------------------------------------
-// The secret keys, the spectrum of the ring key and the generator key do not outlive the call on the device,
-// whichever way it ends: they travel through one SecretStage (secrets.hpp) on the context's stream, which zeroes the
-// buffer and drains the stream on every exit path.  The generator key travels in the buffer too (not in
-// kernel-argument memory).  The layout: K, the slot derive_public_seed writes, key_lv0 [n], key_lv1 [N], and the
-// spectrum of key_lv1, which k_key_spectrum writes (16-byte aligned: it is read as double2).  The TRLWE switching key
-// (trlwe_switch.hpp) stages a ring key where key_lv0 stands: k0_words = N, d_k0 the key switched from, d_k1 the key
-// switched to.
-struct StagedSecrets {
-  size_t k0_words;  // words of the first key: n, or N for a ring key
-  SecretStage stage;
-  const uint32_t *d_k0 = nullptr, *d_k1 = nullptr;
-  const double2 *d_spec = nullptr;
-  ChaChaKey *d_rk = nullptr;  // the derived-seed slot is d_rk + 1
-  explicit StagedSecrets(tfhe_hip_ctx *ctx) : StagedSecrets(ctx, (size_t)ctx->P.n) {}
-  StagedSecrets(tfhe_hip_ctx *ctx, size_t k0_words)
-      : k0_words(k0_words), stage(ctx, ctx->sym_sec, ctx->stream, 2 * sizeof(ChaChaKey) + (k0_words + kN) * 4, true) {}
-};
-static_assert(2 * sizeof(ChaChaKey) + ((size_t)kLweMaxN + kN) * 4 <= kSecretImageMax, "the largest image a call stages");
-// Use: `StagedSecrets s(ctx); CHK(stage_secrets(ctx, ..., s));`
+int GeneratorKey::fill(tfhe_hip_ctx *ctx, const uint8_t *rng_key) {
+  if (rng_key) {
+    memcpy(k.k, rng_key, 32);  // 8 little-endian words
+  } else if (const int err = os_random((uint8_t *)k.k, sizeof(k.k))) {
+    return fail(ctx, TFHE_HIP_EHIP, os_random_text(err));
+  }
+  return TFHE_HIP_OK;
+}
+
+// ---- key generation: the secrets on the device (StagedSecrets, internal.hpp) -------------------------------------------
+int key_spectrum_launch(tfhe_hip_ctx *ctx, const uint32_t *d_key_lv1, double2 *d_spec, hipStream_t s) {
+  hipLaunchKernelGGL(k_key_spectrum, dim3(1), dim3(64), kStageLdsBytes, s, d_key_lv1, ctx->d_tw, d_spec);
+  return launched(ctx);
+}
+
 int stage_secrets(tfhe_hip_ctx *ctx, const uint32_t *key_lv0, const uint32_t *key_lv1, const ChaChaKey &rk, StagedSecrets &s) {
   const size_t k0_at = 2 * sizeof(ChaChaKey), k1_at = k0_at + s.k0_words * 4;
   const size_t spec_at = (k1_at + (size_t)kN * 4 + 15) & ~(size_t)15;
@@ -189,14 +146,12 @@ int stage_secrets(tfhe_hip_ctx *ctx, const uint32_t *key_lv0, const uint32_t *ke
   s.d_rk = s.stage.dev<ChaChaKey>(0);
   s.d_k0 = s.stage.dev(k0_at);
   s.d_k1 = s.stage.dev(k1_at);
-  hipLaunchKernelGGL(k_key_spectrum, dim3(1), dim3(64), kStageLdsBytes, ctx->stream, s.d_k1, ctx->d_tw, s.stage.dev<double2>(spec_at));
-  HIPCHK(ctx, hipGetLastError());
+  CHK(key_spectrum_launch(ctx, s.d_k1, s.stage.dev<double2>(spec_at), ctx->stream));
   s.d_spec = s.stage.dev<const double2>(spec_at);
   return TFHE_HIP_OK;
 }
 
-// The public mask seed S of stream STREAM of the staged generator key (k_derive_stream_seed), derived into the slot
-// behind it and copied back.
+// (the seed streams of the library, instantiated below: every unit's k_derive_stream_seed is emitted here)
 template <uint32_t STREAM>
 int derive_public_seed(tfhe_hip_ctx *ctx, const StagedSecrets &s, ChaChaKey &seed) {
   hipLaunchKernelGGL((k_derive_stream_seed<64, STREAM>), dim3(1), dim3(64), 0, ctx->stream, s.d_rk, s.d_rk + 1);
@@ -205,9 +160,10 @@ int derive_public_seed(tfhe_hip_ctx *ctx, const StagedSecrets &s, ChaChaKey &see
   HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
   return TFHE_HIP_OK;
 }
+template int derive_public_seed<kStreamSeededSeed>(tfhe_hip_ctx *, const StagedSecrets &, ChaChaKey &);  // seeded.hpp
+template int derive_public_seed<kStreamPackSeed>(tfhe_hip_ctx *, const StagedSecrets &, ChaChaKey &);    // packing_keygen.hpp
+template int derive_public_seed<kStreamTksSeed>(tfhe_hip_ctx *, const StagedSecrets &, ChaChaKey &);     // trlwe_switch.hpp
 
-// The one launch of k_lwe_rows (keygen.hpp), on stream s: the encrypting variant, or with no generator key (j.k NULL)
-// the expansion of given bodies.  j.rows >= 1.
 int lwe_rows_launch(tfhe_hip_ctx *ctx, const LweRowJob &j, hipStream_t s) {
   const tfhe_hip_params &P = ctx->P;
   if (P.n > kLweMaxN) return fail(ctx, TFHE_HIP_EINVAL, "n too large");  // (params_supported admits no such context)
@@ -218,8 +174,6 @@ int lwe_rows_launch(tfhe_hip_ctx *ctx, const LweRowJob &j, hipStream_t s) {
   return launched(ctx);
 }
 
-// The key-switching key's rows (key.rs:102-122) over the staged secrets: plain (masks under K, streams 0 / 1) into the
-// engine layout at `out`, or compressed (seed != NULL: masks under S, streams 16 / 17) as bodies only.
 int ksk_rows_launch(tfhe_hip_ctx *ctx, const StagedSecrets &s, const ChaChaKey *seed, double alpha, uint32_t *bodies,
                     uint32_t *out) {
   LweRowJob j{};
@@ -240,7 +194,6 @@ int ksk_rows_launch(tfhe_hip_ctx *ctx, const StagedSecrets &s, const ChaChaKey *
   return lwe_rows_launch(ctx, j, ctx->stream);
 }
 
-// what a generated key gets: the decomposition offset (key.rs:78-89) and the test vector (key.rs:91-100), uploaded
 int default_offset_and_testvec(tfhe_hip_ctx *ctx, uint32_t *offset) {
   const tfhe_hip_params &P = ctx->P;
   uint32_t off = 0;
@@ -252,5 +205,3 @@ int default_offset_and_testvec(tfhe_hip_ctx *ctx, uint32_t *offset) {
   *offset = off;
   return TFHE_HIP_OK;
 }
-
-}  // namespace

@@ -58,10 +58,8 @@
 // LDS, is little faster per operation).  A taller row block would halve it at 256 accumulator registers (one
 // wave per SIMD); interleaving the split of step s + 2 with the matrix instructions of step s is the other way on.
 // Measured: DESIGN.md section 9, profiles/matmul_bench.json (the convolution: profiles/conv2d_bench.json).
-//
-// Every kernel here is a template: instantiations are emitted after the library's other kernels, so the code of every
-// existing kernel stays byte-identical.
 #pragma once
+#include "internal.hpp"
 
 namespace tfhe {
 
@@ -71,7 +69,7 @@ constexpr int kMmBN = 32 * kMmWaves; // columns per workgroup: one 32-column til
 constexpr int kMmBufBytes = 4 * kMmWaves * 1024;  // one K-step of B: [plane][tile][64 lanes][16 B]
 constexpr size_t kMmMaxCols = 65536;  // accumulator bound, see above
 constexpr size_t kMmUnitsPerLaunch = (size_t)1 << 19;  // (group, row block) pairs per launch: x <= 16 column blocks (the polynomial product's 2N / 128) x 256 threads = 2^31 < 2^32
-constexpr size_t kPolymulMaxCols = kMmMaxCols / kN;    // polynomial product: K = cols N <= kMmMaxCols, so cols <= 64
+static_assert(kPolymulMaxCols == kMmMaxCols / kN, "polynomial product: K = cols N <= kMmMaxCols, so cols <= 64 (internal.hpp)");
 constexpr unsigned kMmXcds = 8;      // accelerator dies a launch's workgroups are dealt to, round-robin
 
 // The four balanced plane bytes of w, byte p = ks_plane_byte(w, p): with u = w + 0x80808080 (the carries of the
@@ -265,17 +263,15 @@ struct MmNegacyclic {
 
 // The bias polynomial of the polynomial product: out[u][1][i] += bias[u % rows][i] for the `units` = groups x rows
 // output ciphertexts from u0 on, one workgroup per ciphertext, four words a thread (word by word: neither pointer need
-// be 16-byte aligned).  (k_tlwe_matmul's own bias is one word in the last column.)  A template like every kernel of
-// this file, for the emission order.
-template <int kThreads>
-__global__ __launch_bounds__(kThreads) void k_polymul_bias(const uint32_t *__restrict__ bias, size_t rows, size_t u0,
+// be 16-byte aligned).  (k_tlwe_matmul's own bias is one word in the last column.)
+constexpr int kPolymulBiasThreads = kN / 4;
+__global__ __launch_bounds__(kPolymulBiasThreads) void k_polymul_bias(const uint32_t *__restrict__ bias, size_t rows, size_t u0,
                                                            uint32_t *__restrict__ out) {
-  static_assert(kN % kThreads == 0, "one workgroup covers the b row");
   const size_t u = u0 + blockIdx.x;
   const uint32_t *src = bias + (u % rows) * (size_t)kN;
   uint32_t *dst = out + (2 * u + 1) * (size_t)kN;
 #pragma unroll
-  for (int i = threadIdx.x; i < kN; i += kThreads) dst[i] += src[i];
+  for (int i = threadIdx.x; i < kN; i += kPolymulBiasThreads) dst[i] += src[i];
 }
 
 // One launch covers groups g0 .. and row blocks rb0 .. rb0 + nrb - 1 of each (nrb < all row blocks only with one group a
@@ -509,22 +505,20 @@ int tfhe_hip_batch_trlwe_matmul_dev(tfhe_hip_ctx *ctx, const int8_t *w, const ui
 }
 
 // ---- plaintext polynomial products on packed ciphertexts: the same GEMM with K = cols N and 2N columns (MmNegacyclic) --
-namespace {
+// (declared in internal.hpp: the TRLWE key switch of rings.hip runs on it)
 int polymul_dev(tfhe_hip_ctx *ctx, const int8_t *w, const uint32_t *bias, size_t rows, size_t cols, const uint32_t *trlwe,
                 size_t groups, uint32_t *out, hipStream_t s) {
   CHK(launch_matmul(ctx, MmNegacyclic{trlwe}, w, nullptr, rows, cols * (size_t)kN, 2 * kN, groups, out, s));
   if (!bias) return TFHE_HIP_OK;
-  constexpr int threads = kN / 4;
   constexpr size_t per_launch = (size_t)1 << 23;  // workgroups a launch: x 256 threads = 2^31 < 2^32
   const size_t units = groups * rows;
   for (size_t u0 = 0; u0 < units; u0 += per_launch) {
-    hipLaunchKernelGGL((k_polymul_bias<threads>), dim3((unsigned)(units - u0 < per_launch ? units - u0 : per_launch)),
-                       dim3(threads), 0, s, bias, rows, u0, out);
+    hipLaunchKernelGGL(k_polymul_bias, dim3((unsigned)(units - u0 < per_launch ? units - u0 : per_launch)),
+                       dim3(kPolymulBiasThreads), 0, s, bias, rows, u0, out);
     CHK(launched(ctx));
   }
   return TFHE_HIP_OK;
 }
-}  // namespace
 
 int tfhe_hip_batch_trlwe_polymul(tfhe_hip_ctx *ctx, const int8_t *w, const uint32_t *bias, size_t rows, size_t cols,
                                  const uint32_t *trlwe, size_t groups, uint32_t *out) {

@@ -29,12 +29,8 @@
 // fold and its LDS is the one line; one group of 1,024 measured 4 us slower with m at run time), the table launch the
 // one that takes m as an argument: one source.  The line is merged into the output with integer atomics (order-free:
 // the words are deterministic).  Small batches cut K over workgroups (blockIdx.z), merged the same way.
-//
-// Every kernel here is a template: instantiations are emitted after the library's other kernels, so the code of every
-// existing kernel stays byte-identical.
 #pragma once
-#include "key_switch_mfma.hpp"
-#include "keygen.hpp"
+#include "internal.hpp"
 
 namespace tfhe {
 
@@ -50,10 +46,8 @@ __host__ __device__ __forceinline__ size_t pk_plane_bytes(int n, int t) {
 
 // Key rows r = i t + l as [n t][2][N] u32: a from the keystream (r, 24, "PKS") under the mask seed, b from `bodies`.
 // One wave per row; lane q makes keystream block q (coefficients 16q .. 16q+15).
-template <int WG>
-__global__ __launch_bounds__(WG) void k_pack_expand_key(const uint32_t *__restrict__ bodies, uint32_t *__restrict__ rows,
+__global__ __launch_bounds__(64) void k_pack_expand_key(const uint32_t *__restrict__ bodies, uint32_t *__restrict__ rows,
                                                          ChaChaKey seed) {
-  static_assert(WG == 64, "one wave per row");
   const uint32_t r = blockIdx.x;
   const int lane = threadIdx.x;
   uint32_t w[16];
@@ -321,7 +315,7 @@ int tfhe_hip_load_packing_key(tfhe_hip_ctx *ctx, const uint8_t mask_seed[32], co
   // the temporary: bodies [n t][N], then the rows [n t][2][N]
   CHK(upload_through_temp(ctx, "packing key", {{bodies, body_words * 4}}, rows * 2 * kN * 4, [&](void *tmp) {
     uint32_t *d_tmp = (uint32_t *)tmp;
-    hipLaunchKernelGGL(k_pack_expand_key<64>, dim3((unsigned)rows), dim3(64), 0, ctx->stream, d_tmp, d_tmp + body_words,
+    hipLaunchKernelGGL(k_pack_expand_key, dim3((unsigned)rows), dim3(64), 0, ctx->stream, d_tmp, d_tmp + body_words,
                        seed_key(mask_seed));
     if (const hipError_t e = hipGetLastError()) return e;
     hipLaunchKernelGGL(k_pack_planes<256>, dim3((unsigned)((chunks + 255) / 256)), dim3(256), 0, ctx->stream,

@@ -8,22 +8,17 @@
 // The product a_r (*) s1 runs through the FFT of k_gen_compressed_bsk and is exact (|coefficients| < 2^41).  The rows
 // land in the temporary [n t][2][N] that k_pack_expand_key would fill, so k_pack_planes builds the same byte planes
 // and the handle holds, bit for bit, the key tfhe_hip_load_packing_key(S, bodies) would build.
-//
-// Every kernel here is a template: instantiations are emitted after the library's other kernels, so the code of every
-// existing kernel stays byte-identical.
 #pragma once
 #include "packing.hpp"
 
 namespace tfhe {
 
 // One wave per row r = i t + l.  rows: [n t][2][N] (a half, b half), bodies: [n t][N].
-template <int WG>
-__global__ __launch_bounds__(WG) void k_gen_packing_key(const uint32_t *__restrict__ key_lv0,
+__global__ __launch_bounds__(64) void k_gen_packing_key(const uint32_t *__restrict__ key_lv0,
                                                          const double2 *__restrict__ s1_spec,
                                                          const double2 *__restrict__ twt, uint32_t *__restrict__ rows,
                                                          uint32_t *__restrict__ bodies, int basebit, int t, double alpha,
                                                          const ChaChaKey *__restrict__ key_p, ChaChaKey seed) {
-  static_assert(WG == 64, "one wave per row");
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   double2 *tile = reinterpret_cast<double2 *>(smem);
   const int lane = threadIdx.x;
@@ -65,7 +60,7 @@ int gen_packing_key_locked(tfhe_hip_ctx *ctx, const uint32_t *key_lv0, const uin
   // the temporary: the rows [n t][2][N], then the bodies [n t][N]; drained and freed on every path
   CHK(upload_through_temp(ctx, "packing key generation", {}, (rows * 2 * kN + body_words) * 4, [&](void *tmp) {
     uint32_t *d_rows = (uint32_t *)tmp, *d_bodies = d_rows + rows * 2 * kN;
-    hipLaunchKernelGGL(k_gen_packing_key<64>, dim3((unsigned)rows), dim3(64), kStageLdsBytes, ctx->stream, d_k0, d_spec,
+    hipLaunchKernelGGL(k_gen_packing_key, dim3((unsigned)rows), dim3(64), kStageLdsBytes, ctx->stream, d_k0, d_spec,
                        ctx->d_tw, d_rows, d_bodies, P.basebit, P.t, alpha, d_rk, seed);
     if (const hipError_t e = hipGetLastError()) return e;
     hipLaunchKernelGGL(k_pack_planes<256>, dim3((unsigned)((chunks + 255) / 256)), dim3(256), 0, ctx->stream, d_rows,
@@ -91,22 +86,4 @@ int tfhe_hip_gen_packing_key(tfhe_hip_ctx *ctx, const uint32_t *key_lv0, const u
   GeneratorKey gk;
   CHK(gk.fill(ctx, rng_key));
   return gen_packing_key_locked(ctx, key_lv0, key_lv1, alpha, gk.k, mask_seed, bodies);
-}
-
-// Generated on the first member; every other member loads the same (S, bodies).
-int tfhe_hip_pool_gen_packing_key(tfhe_hip_pool *p, const uint32_t *key_lv0, const uint32_t *key_lv1, double alpha,
-                                  const uint8_t rng_key[32], uint8_t mask_seed[32], uint32_t *bodies) {
-  if (!p) return TFHE_HIP_EINVAL;
-  std::lock_guard<FairMutex> plk(p->root()->own_mu);
-  if (!mask_seed) return pool_fail(p, TFHE_HIP_EINVAL, "null pointer");
-  tfhe_hip_ctx *first = p->ctxs[0];
-  std::vector<uint32_t> own;  // the bodies the other members load when the caller keeps none
-  if (!bodies && p->ctxs.size() > 1) {
-    own.resize((size_t)first->P.n * first->P.t * kN);
-    bodies = own.data();
-  }
-  CHK(pool_member_rc(p, first, tfhe_hip_gen_packing_key(first, key_lv0, key_lv1, alpha, rng_key, mask_seed, bodies)));
-  for (size_t m = 1; m < p->ctxs.size(); ++m)
-    CHK(pool_member_rc(p, p->ctxs[m], tfhe_hip_load_packing_key(p->ctxs[m], mask_seed, bodies)));
-  return TFHE_HIP_OK;
 }

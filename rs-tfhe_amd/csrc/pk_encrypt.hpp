@@ -22,9 +22,6 @@
 //                    packing.hpp (plane_walk) with the selector words as the A side, no K split (steps <= 256).  The
 //                    planes are summed (plane_merge) in a 32 x 32 kPkeNT LDS tile that goes out in coalesced row
 //                    stores; column n receives the addend; columns past n are dropped.
-//
-// Every kernel here is a template: instantiations are emitted after the library's other kernels, so the code of every
-// existing kernel stays byte-identical.
 #pragma once
 #include "packing.hpp"
 
@@ -312,9 +309,7 @@ int tfhe_hip_gen_reenc_key_asymmetric(tfhe_hip_ctx *ctx, const uint32_t *key_fro
     uint32_t *d_rows = (uint32_t *)tmp, *d_sel = d_rows + key_words;
     if (pke_rows_launch(ctx, gk.k, 0, rows, alpha, nullptr, d_from, d_sel, d_rows, ctx->stream) != TFHE_HIP_OK)
       return hipErrorLaunchFailure;
-    hipLaunchKernelGGL(k_ksk_convert, dim3((unsigned)rows), dim3(256), 0, ctx->stream, (const uint32_t *)d_rows, ctx->K->d_ksk,
-                       P.n, base, rows);
-    if (const hipError_t e = hipGetLastError()) return e;
+    if (const hipError_t e = ksk_convert_launch(ctx, d_rows, rows)) return e;
     if (key_out) return hipMemcpyAsync(key_out, d_rows, key_words * 4, hipMemcpyDeviceToHost, ctx->stream);
     return hipSuccess;
   }));

@@ -1204,6 +1204,24 @@ int tfhe_hip_pool_load_packing_key(tfhe_hip_pool *p, const uint8_t mask_seed[32]
   return TFHE_HIP_OK;
 }
 
+// (packing_keygen.hpp) Generated on the first member; every other member loads the same (S, bodies).
+int tfhe_hip_pool_gen_packing_key(tfhe_hip_pool *p, const uint32_t *key_lv0, const uint32_t *key_lv1, double alpha,
+                                  const uint8_t rng_key[32], uint8_t mask_seed[32], uint32_t *bodies) {
+  if (!p) return TFHE_HIP_EINVAL;
+  std::lock_guard<FairMutex> plk(p->root()->own_mu);
+  if (!mask_seed) return pool_fail(p, TFHE_HIP_EINVAL, "null pointer");
+  tfhe_hip_ctx *first = p->ctxs[0];
+  std::vector<uint32_t> own;  // the bodies the other members load when the caller keeps none
+  if (!bodies && p->ctxs.size() > 1) {
+    own.resize((size_t)first->P.n * first->P.t * kN);
+    bodies = own.data();
+  }
+  CHK(pool_member_rc(p, first, tfhe_hip_gen_packing_key(first, key_lv0, key_lv1, alpha, rng_key, mask_seed, bodies)));
+  for (size_t m = 1; m < p->ctxs.size(); ++m)
+    CHK(pool_member_rc(p, p->ctxs[m], tfhe_hip_load_packing_key(p->ctxs[m], mask_seed, bodies)));
+  return TFHE_HIP_OK;
+}
+
 int tfhe_hip_pool_batch_pack_tlwe(tfhe_hip_pool *p, const uint32_t *in, size_t count, uint32_t *out) {
   POOL_ENTER(p);
   if (count == 0) {  // a member's checks (ENOKEY first), nothing to run
@@ -1296,4 +1314,20 @@ int tfhe_hip_pool_batch_unpack_trlwe_dev(tfhe_hip_pool *p, int home, const uint3
   return TFHE_HIP_OK;
 }
 
+// ---- tree bootstrap (table.hpp) ------------------------------------------------------------------------------------------------
+// the pool form: the batch is cut by count over the members, the tables go whole to each (every member holds both keys)
+int tfhe_hip_pool_batch_bootstrap_bivariate(tfhe_hip_pool *p, const uint32_t *x, const uint32_t *y, const uint32_t *testvecs,
+                                            int m, int n_luts, int keyswitch, uint32_t *out, size_t count) {
+  if (!p) return TFHE_HIP_EINVAL;
+  std::lock_guard<FairMutex> plk(p->root()->own_mu);
+  // a member's checks of the keys and of m, n_luts and the tables, in a context's order (count 0: nothing runs)
+  CHK(pool_member_rc(p, p->ctxs[0], tfhe_hip_batch_bootstrap_bivariate(p->ctxs[0], x, y, testvecs, m, n_luts, keyswitch, out, 0)));
+  if (count == 0) return TFHE_HIP_OK;
+  if (const char *why = bivariate_refusal(x, y, testvecs, m, n_luts, out, count)) return pool_fail(p, TFHE_HIP_EINVAL, why);
+  const size_t w = pool_tlwe_bytes(p);
+  return pool_map(p, count, [&](tfhe_hip_ctx *c, size_t lo, size_t hi) {
+    const size_t words = lo * (w / 4);
+    return tfhe_hip_batch_bootstrap_bivariate(c, x + words, y + words, testvecs, m, n_luts, keyswitch, out + words, hi - lo);
+  });
+}
 #undef POOL_ENTER

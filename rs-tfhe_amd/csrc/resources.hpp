@@ -2,10 +2,9 @@
 // arena, an event, the timing pairs of a kernel family, and the claim under which the context's scratch is sized.
 // Each frees itself; nothing outside this file calls the runtime's free or destroy.  tests/cpp/test_resources.cpp runs
 // this file as it is, over stand-ins for the runtime: the including file supplies the HIP names and the std:: headers.
-// Nothing here knows the context.
+// Nothing here knows the context.  The types are shared between the library's translation units (internal.hpp): none
+// is in an anonymous namespace.
 #pragma once
-
-namespace {
 
 // A failed runtime call: `what` is the text the library has always reported for that call (nullptr: an allocation,
 // whose text and code are the caller's).
@@ -204,5 +203,3 @@ class TimedScope {
   EventPairs *v_;
   hipStream_t s_;
 };
-
-}  // namespace

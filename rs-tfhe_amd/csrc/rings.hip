@@ -1,0 +1,9 @@
+// rings.hip -- the ring-row family, one translation unit of libtfhe_hip.so: seeded (compressed) cloud keys and
+// ciphertexts, packed TRLWE encryption, decryption and the TRLWE key switch.
+// What it uses of the core is declared in internal.hpp; every kernel of the headers below is emitted here and nowhere else.
+#include "internal.hpp"
+
+#include "seeded.hpp"
+#include "trlwe_encrypt.hpp"
+#include "decrypt.hpp"
+#include "trlwe_switch.hpp"

@@ -1,12 +1,11 @@
 // secrets.hpp -- the one path by which a call's secrets reach the device, and by which secrets, plaintexts and decrypted
 // words leave the library's buffers again (host code only).  tests/cpp/test_secret_stage.cpp runs this file as it is,
 // over host memory: the including file supplies the HIP runtime's names, std::string and resources.hpp (DevBuf, Staging)
-// ahead of it and defines fail, ensure and claim_scratch; the context is opaque here.
+// ahead of it and defines fail, ensure and claim_scratch; the context is opaque here.  Shared between the library's
+// translation units (internal.hpp): nothing is in an anonymous namespace.
 #pragma once
 
 struct tfhe_hip_ctx;
-
-namespace {
 
 int fail(tfhe_hip_ctx *ctx, int code, const std::string &msg);
 int ensure(tfhe_hip_ctx *ctx, DevBuf &b, size_t bytes);
@@ -91,5 +90,3 @@ inline void scrub(hipStream_t s, std::initializer_list<ScrubSlot> slots) {
   for (const ScrubSlot &x : slots)
     if (x.slot->pin.p) wipe_host(x.slot->pin.p, x.bytes < x.slot->pin.cap ? x.bytes : x.slot->pin.cap);
 }
-
-}  // namespace

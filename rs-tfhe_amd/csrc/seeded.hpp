@@ -8,11 +8,8 @@
 // (kStream*, kSeedDomain*), the seed derivation, the ring-row helpers shared with the plain generator, and the LWE
 // row kernel k_lwe_rows: the key-switching key's rows (bodies only under S, streams 16 / 17 of "KSK") and the
 // expansion of them and of seeded TLWE ciphertexts ("EWL") are launches of it, so only the ring rows have kernels here.
-//
-// Every kernel here is a template (on its workgroup size, or on l): template instantiations are emitted after the
-// library's other kernels, so these leave the labels of the bootstrap kernels, which kernel_isa.json records, alone.
 #pragma once
-#include "keygen.hpp"
+#include "internal.hpp"
 
 namespace tfhe {
 
@@ -49,11 +46,9 @@ __global__ __launch_bounds__(64) void k_gen_compressed_bsk(const uint32_t *__res
 }
 
 // Spectra of (a from S, b from `bodies`) in the engine layout of k_gen_bsk, scaled by 2 * key_scale(fast).
-template <int WG>
-__global__ __launch_bounds__(WG) void k_expand_bsk(const uint32_t *__restrict__ bodies, const double2 *__restrict__ twt,
+__global__ __launch_bounds__(64) void k_expand_bsk(const uint32_t *__restrict__ bodies, const double2 *__restrict__ twt,
                                                     double2 *__restrict__ bsk_eng, ChaChaKey seed, double scale) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-  static_assert(WG == 64, "one wave per row");
   double2 *tile = reinterpret_cast<double2 *>(smem);
   const int lane = threadIdx.x;
   const uint32_t row = blockIdx.x;
@@ -75,8 +70,6 @@ __global__ __launch_bounds__(WG) void k_expand_bsk(const uint32_t *__restrict__ 
 
 }  // namespace tfhe
 
-using namespace tfhe;
-
 // ---- seeded (compressed) cloud keys and ciphertexts (seeded.hpp) ---------------------------------------------
 int tfhe_hip_compressed_key_words(const tfhe_hip_params *params, size_t *bsk_words, size_t *ksk_words) {
   if (!params || !bsk_words || !ksk_words || !params_supported(params)) return TFHE_HIP_EINVAL;
@@ -86,17 +79,11 @@ int tfhe_hip_compressed_key_words(const tfhe_hip_params *params, size_t *bsk_wor
 }
 
 namespace {
-ChaChaKey seed_key(const uint8_t seed[32]) {
-  ChaChaKey k;
-  memcpy(k.k, seed, 32);  // 8 little-endian words, as tfhe_hip_gen_cloud_key_with_key reads its generator key
-  return k;
-}
-
 // Queues, on ctx->stream, the engine layouts from the bodies at d_bsk_bodies [n][2l][N] / d_ksk_bodies [N][t][base] and
 // the masks of `seed`.  ctx->mu held, key buffers allocated (begin_key_change).
 hipError_t expand_key_locked(tfhe_hip_ctx *ctx, const ChaChaKey &seed, const uint32_t *d_bsk_bodies, const uint32_t *d_ksk_bodies) {
   const tfhe_hip_params &P = ctx->P;
-  hipLaunchKernelGGL(k_expand_bsk<64>, dim3((unsigned)(P.n * 2 * P.l)), dim3(64), kStageLdsBytes, ctx->stream, d_bsk_bodies,
+  hipLaunchKernelGGL(k_expand_bsk, dim3((unsigned)(P.n * 2 * P.l)), dim3(64), kStageLdsBytes, ctx->stream, d_bsk_bodies,
                      ctx->d_tw, ctx->K->d_bsk, seed, key_scale(ctx->dispatch.fast_round));
   if (const hipError_t e = hipGetLastError()) return e;
   // key-switching key: the engine layout of k_ksk_convert (rows of ksk_row_words(n), zero padding, k = 0 rows all zero)

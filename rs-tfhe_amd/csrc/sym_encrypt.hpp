@@ -72,24 +72,6 @@ int sym_bulk(tfhe_hip_ctx *ctx, const ChaChaKey &seed, const ChaChaKey &k, const
                     ctx->P.n + 1, s);
   return sec.finish(rc);
 }
-
-// A host-form encryption of plain [count], staged through slot a.  The primary output (out, or the bodies alone)
-// returns through host_call; with both asked for, the bodies ride in staging buffer b.  bulk(d_plain, d_bodies, d_out)
-// queues the call on the context's stream.  The plaintexts do not stay behind in the library's buffers.
-template <class Bulk>
-int encrypt_host_call(tfhe_hip_ctx *ctx, const uint32_t *plain, size_t count, uint32_t *bodies, size_t body_bytes, uint32_t *out,
-                      size_t out_bytes, Bulk &&bulk) {
-  if (out && bodies) CHK(ensure(ctx, ctx->b.dev, body_bytes));
-  int rc = host_call(ctx, false, {{plain, count * 4, &ctx->a}}, out ? out : bodies, out ? out_bytes : body_bytes,
-                     [&](const void *const *d, void *o) {
-                       uint32_t *d_out = out ? (uint32_t *)o : nullptr;
-                       uint32_t *d_bodies = out ? (bodies ? (uint32_t *)ctx->b.dev.p : nullptr) : (uint32_t *)o;
-                       return bulk(u32(d[0]), d_bodies, d_out);
-                     });
-  if (rc == TFHE_HIP_OK && out && bodies) rc = to_host(ctx, bodies, ctx->b, body_bytes);
-  scrub(ctx->stream, {{&ctx->a, count * 4}});
-  return rc;
-}
 }  // namespace
 
 int tfhe_hip_batch_encrypt(tfhe_hip_ctx *ctx, const uint32_t *key_lv0, const uint32_t *plain, size_t count, double alpha,
@@ -180,9 +162,7 @@ int tfhe_hip_gen_reenc_key_symmetric(tfhe_hip_ctx *ctx, const uint32_t *key_from
                  ksk_row_words(P.n), ctx->stream));
   if (key_out)
     CHK(upload_through_temp(ctx, "re-encryption key export", {}, key_words * 4, [&](void *d_ref) -> hipError_t {
-      hipLaunchKernelGGL(k_ksk_export, dim3((unsigned)rows), dim3(256), 0, ctx->stream, (const uint32_t *)ctx->K->d_ksk,
-                         (uint32_t *)d_ref, P.n, rows);
-      if (const hipError_t e = hipGetLastError()) return e;
+      if (const hipError_t e = ksk_export_launch(ctx, (uint32_t *)d_ref, rows)) return e;
       return hipMemcpyAsync(key_out, d_ref, key_words * 4, hipMemcpyDeviceToHost, ctx->stream);
     }));
   return commit_reenc_key(ctx);

@@ -15,9 +15,6 @@
 // summed there too.  One integer atomicAdd per non-zero word of the line then reaches out[c][h][(col + x W) mod N],
 // negated past the wrap (order-free: the words are deterministic).  k_table_window turns Q into the windowed sum in
 // place, one workgroup per (c, row).
-//
-// Every kernel here is a template: instantiations are emitted after the library's other kernels, so the code of every
-// existing kernel stays byte-identical.
 #pragma once
 #include "packing.hpp"
 
@@ -140,6 +137,9 @@ size_t biv_chunk(const tfhe_hip_ctx *ctx, int m) {
   return chunk;
 }
 
+}  // namespace
+
+// (declared in internal.hpp: the pool form of pool.hpp runs the same checks)
 const char *bivariate_refusal(const uint32_t *x, const uint32_t *y, const uint32_t *testvecs, int m, int n_luts,
                               const uint32_t *out, size_t count) {
   if (tb_log2(m) < 0) return "m must be a power of two in [2, 512]";
@@ -151,6 +151,7 @@ const char *bivariate_refusal(const uint32_t *x, const uint32_t *y, const uint32
   return nullptr;
 }
 
+namespace {
 // device pointers, keys and arguments checked: m / k many-LUT bootstraps of y, the table build, the bootstrap of x
 int bivariate_launch(tfhe_hip_ctx *ctx, const uint32_t *x, const uint32_t *y, const uint32_t *testvecs, int m, int k,
                      bool keyswitch, uint32_t *out, size_t count, hipStream_t s) {
@@ -195,20 +196,4 @@ int tfhe_hip_batch_bootstrap_bivariate_dev(tfhe_hip_ctx *ctx, const uint32_t *x,
   if (const char *why = bivariate_refusal(x, y, testvecs, m, n_luts, out, count)) return fail(ctx, TFHE_HIP_EINVAL, why);
   if (count == 0) return TFHE_HIP_OK;
   return bivariate_launch(ctx, x, y, testvecs, m, n_luts, keyswitch != 0, out, count, pick(ctx, stream));
-}
-
-// the pool form: the batch is cut by count over the members, the tables go whole to each (every member holds both keys)
-int tfhe_hip_pool_batch_bootstrap_bivariate(tfhe_hip_pool *p, const uint32_t *x, const uint32_t *y, const uint32_t *testvecs,
-                                            int m, int n_luts, int keyswitch, uint32_t *out, size_t count) {
-  if (!p) return TFHE_HIP_EINVAL;
-  std::lock_guard<FairMutex> plk(p->root()->own_mu);
-  // a member's checks of the keys and of m, n_luts and the tables, in a context's order (count 0: nothing runs)
-  CHK(pool_member_rc(p, p->ctxs[0], tfhe_hip_batch_bootstrap_bivariate(p->ctxs[0], x, y, testvecs, m, n_luts, keyswitch, out, 0)));
-  if (count == 0) return TFHE_HIP_OK;
-  if (const char *why = bivariate_refusal(x, y, testvecs, m, n_luts, out, count)) return pool_fail(p, TFHE_HIP_EINVAL, why);
-  const size_t w = pool_tlwe_bytes(p);
-  return pool_map(p, count, [&](tfhe_hip_ctx *c, size_t lo, size_t hi) {
-    const size_t words = lo * (w / 4);
-    return tfhe_hip_batch_bootstrap_bivariate(c, x + words, y + words, testvecs, m, n_luts, keyswitch, out + words, hi - lo);
-  });
 }

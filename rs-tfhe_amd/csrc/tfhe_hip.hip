@@ -1,4 +1,5 @@
-// tfhe_hip.hip -- C ABI (include/tfhe_hip.h) over the gfx950 kernels.
+// tfhe_hip.hip -- C ABI (include/tfhe_hip.h) over the gfx950 kernels: the core translation unit of libtfhe_hip.so.
+// (The feature units, planes.hip and rings.hip, reach it through internal.hpp and nothing else.)
 //
 // Host side of the engine: context (device, stream, converted cloud key,
 // scratch), launch geometry, and the batched entry points that compose
@@ -7,28 +8,11 @@
 // (src/gates.rs:357-383: prepare, batch_blind_rotate, extract + key switch).
 #include <hip/hip_runtime.h>
 
-#include <algorithm>
-#include <array>
-#include <cmath>
-#include <cstdio>
-#include <cstdlib>
-#include <cstring>
-#include <map>
-#include <memory>
-#include <tuple>
-#include <atomic>
-#include <condition_variable>
-#include <mutex>
-#include <string>
-#include <unordered_map>
-#include <unordered_set>
-#include <utility>
-#include <vector>
-
-#include "../../include/tfhe_hip.h"
 #include <errno.h>
 #include <sys/random.h>
 
+// This unit owns the kernels of these headers; every other unit sees them with internal linkage (internal.hpp).
+#define TFHE_HIP_CORE_UNIT
 #include "blind_rotate.hpp"
 #include "blind_rotate_wide.hpp"
 #include "key_switch.hpp"
@@ -36,7 +20,7 @@
 #include "keygen.hpp"
 #include "twiddles_host.hpp"
 
-using namespace tfhe;
+#include "internal.hpp"
 
 namespace {
 
@@ -67,13 +51,14 @@ struct ErrTableOwner {
 std::mutex g_live_mu;
 std::unordered_set<uint64_t> g_live_handles;
 constexpr size_t kErrTableSoftCap = 64;
-inline uint64_t new_handle_id() {  // never reused
+}  // namespace
+uint64_t new_handle_id() {  // never reused
   const uint64_t id = g_next_handle_id.fetch_add(1);
   std::lock_guard<std::mutex> lk(g_live_mu);
   g_live_handles.insert(id);
   return id;
 }
-inline void handle_gone(uint64_t id) {
+void handle_gone(uint64_t id) {
   {
     std::lock_guard<std::mutex> lk(g_live_mu);
     g_live_handles.erase(id);
@@ -81,7 +66,7 @@ inline void handle_gone(uint64_t id) {
   if (t_errors) t_errors->erase(id);
 }
 // the slot a FAILING call writes its text into (references survive rehashing)
-inline std::string &err_slot(uint64_t id) {
+std::string &err_slot(uint64_t id) {
   thread_local ErrTableOwner owner;  // frees the table when the thread ends
   (void)owner;
   if (!t_errors) t_errors = new ErrTable();
@@ -92,6 +77,7 @@ inline std::string &err_slot(uint64_t id) {
   }
   return t[id];
 }
+namespace {
 // the calling thread's last failure text on handle `id`, "" if it never failed there (no entry is made)
 inline const char *err_text(uint64_t id) {
   static const std::string none;
@@ -102,197 +88,9 @@ inline const char *err_text(uint64_t id) {
 
 constexpr int kKsG = 32;  // ciphertexts per key-switch workgroup
 
-// Calls on one handle are serialised IN ARRIVAL ORDER (a ticket lock).  std::mutex makes no such promise: a thread that
-// issues calls back to back re-acquires it before a waiting thread wakes, and under `Send + Sync` use (a Rayon team
-// calling Bootstrap::bootstrap on one strategy, src/bootstrap/mod.rs:23) one worker could starve the rest for as long
-// as it had work -- seen in tests/cpp/test_mirror.cpp, where 400 failing calls took minutes beside a thread that kept
-// bootstrapping.
-class FairMutex {
- public:
-  void lock() {
-    std::unique_lock<std::mutex> lk(m_);
-    const uint64_t ticket = next_++;
-    cv_.wait(lk, [&] { return serving_ == ticket; });
-  }
-  void unlock() {
-    {
-      std::lock_guard<std::mutex> lk(m_);
-      ++serving_;
-    }
-    cv_.notify_all();
-  }
-
- private:
-  std::mutex m_;
-  std::condition_variable cv_;
-  uint64_t next_ = 0, serving_ = 0;
-};
-
 }  // namespace
 
-#include <deque>
-
-#include "resources.hpp"  // DevBuf, PinBuf, Staging, the scratch claim, the timing pairs: each frees itself
-#include "secrets.hpp"    // SecretStage and scrub over them
-
-namespace {
-// One resident cloud key in the engine layouts (src/key.rs:51-56).  A context owns one (`own`); every key view
-// created with tfhe_hip_key_create owns another and runs on its parent's device, stream, scratch and mutex.
-struct KeyState {
-  DevArray<double2> d_bsk;
-  DevArray<uint32_t> d_ksk;
-  DevArray<unsigned char> d_ksk8;  // base-4 sets: the key as signed byte planes in MFMA fragment order (k_ksk_planes)
-  DevArray<uint32_t> d_testvec;
-  // the side keys, as byte planes: beside, not part of, the cloud key (a cloud-key load or change leaves them; freeing
-  // the key view frees them)
-  DevArray<unsigned char> d_pk8;    // the packing key (packing.hpp)
-  bool pk_loaded = false;
-  DevArray<unsigned char> d_pke8;   // the public key (pk_encrypt.hpp)
-  int pke_size = 0;                 // encryptions of zero in the loaded public key
-  bool pke_loaded = false;
-  // the TRLWE switching keys (trlwe_switch.hpp), found by k: plain rows [t][2][N], the B operand of MmNegacyclic
-  struct TrlweSwitchKey {
-    int k = 0, basebit = 0, t = 0;
-    DevArray<uint32_t> rows;
-    bool loaded = false;
-  };
-  static constexpr int kMaxTrlweSwitchKeys = 16;
-  TrlweSwitchKey tsk[kMaxTrlweSwitchKeys];
-  uint32_t offset = 0;
-  // The flags are written in key_change.hpp only: begin_key_change clears both, commit_cloud_key sets key_loaded (and
-  // clears reenc_loaded), commit_reenc_key sets reenc_loaded; begin_side_key clears pk_loaded, pke_loaded or a
-  // switching key's `loaded` and commit_side_key sets it.
-  bool key_loaded = false;
-  bool reenc_loaded = false;  // d_ksk (+ d_ksk8) hold a proxy re-encryption key (proxy_reenc.rs:224-233) instead of a cloud key's
-};
-
-// the context's own stream (a key view has none)
-struct OwnStream {
-  hipStream_t s = nullptr;
-  OwnStream() = default;
-  OwnStream(const OwnStream &) = delete;
-  OwnStream &operator=(const OwnStream &) = delete;
-  ~OwnStream() {
-    if (s) (void)hipStreamDestroy(s);
-  }
-  operator hipStream_t() const { return s; }
-};
-}  // namespace
-
-struct Combiner;  // combine.hpp: the combining front end of the small host-pointer calls
-
-// Every buffer, arena and event below frees itself when the context is deleted (resources.hpp), in reverse order of
-// declaration: `stream` stands ahead of them all and so outlives them.  tfhe_hip_ctx_destroy drains the streams first.
-struct tfhe_hip_ctx {
-  tfhe_hip_params P{};
-  int device = 0;
-  OwnStream stream;
-  KeyState own;
-  KeyState *K = &own;            // the key of the call in progress (bound by ENTER under the mutex)
-  tfhe_hip_ctx *parent = nullptr;  // non-null: this handle is a key view of `parent` (only P, own, parent are used)
-  int views = 0;                 // live key views of this context
-  bool dying = false;            // destroyed while views were alive: the last view to go frees the context
-  DevArray<double2> d_tw;
-  // scratch, sized through take() alone
-  ScratchBuf lv1, u1, u2, ks_out, ks_dig;  // (ks_dig: key-switch digit bytes)
-  ScratchBuf biv_s1, biv_tv;               // tree bootstrap (table.hpp): stage-1 results [m][chunk][n+1], their tables [chunk][2][N]
-  ScratchBuf pke_sel;                      // public-key encryption (pk_encrypt.hpp): selector words and addends of one pass
-  ScratchBuf ts_dig;                       // TRLWE key switch (trlwe_switch.hpp): digit planes [chunk][t][N] i8, then b' [chunk][N]
-  Scratch scratch;                         // the stream whose queued work may still use them (claim_scratch)
-  DevBuf sym_sec;                      // the staged secrets of one call (secrets.hpp: SecretStage), wiped behind it
-  // host-API staging: a / b / c / out also stage through their arenas on pool members (to_dev / to_host);
-  // the arenas of tv / idx serve the combiner lanes only
-  Staging a{{}, {}, true}, b{{}, {}, true}, c{{}, {}, true}, out{{}, {}, true}, tv, idx;
-  Combiner *comb = nullptr;      // base contexts: concurrent small host-pointer calls are merged into shared launches (combine.hpp)
-  bool is_lane = false;          // this context is a combiner lane of another one (never handed to a caller)
-  bool stage_pinned = false;     // set by a pool with several members: stage pageable operands through the arenas
-  FairMutex mu;  // one call at a time per context, first come first served
-  uint64_t id = new_handle_id();  // key of this context's per-thread error text (err_slot)
-  bool profiling = false;
-  int num_cus = 0;
-  // ---- dispatch (plan_blind_rotate / plan_key_switch below; tfhe_hip_describe_dispatch prints a plan) ----
-  // One member, so that a combiner lane takes its base context's choices with one assignment (comb_make_lane): a
-  // knob added here reaches the merged small calls too.
-  struct Dispatch {
-    // The two selectors are the supported controls (TFHE_HIP_BR_KERNEL / TFHE_HIP_KS_KERNEL, include/tfhe_hip.h):
-    // AUTO picks per batch size, anything else runs that kernel at every batch size.
-    int br_force = 0;  // BrKind + 1, 0 = auto
-    int ks_force = 0;  // KsKind + 1, 0 = auto
-    // crossovers of the automatic choice, in ciphertexts; set from the CU count at creation
-    size_t wide_max = 256;      // blind rotate: one eight-wave workgroup per ciphertext up to this batch size
-    size_t pair_lo = 0, pair_max = 0;  // ... two ciphertexts per workgroup (k_blind_rotate_pair) for pair_lo < count <= pair_max
-    size_t ks_split_max = 256;  // key switch: coefficient walk split over 32 workgroups up to this batch size
-    size_t ks_mfma_min = 64;    // smallest batch the matrix-core kernel takes (below: the split kernel)
-    size_t ks_sl_chunk_min = 384;  // wider bases: smallest batch the column-sliced kernel takes (with K chunks; below: the split kernel)
-    bool fast_round = false;  // |pre-rounding value| < 2^51 guaranteed (see round_to_torus<FAST>)
-  } dispatch;
-  EventPairs ev_br, ev_ks;              // one pair per launch while profiling is on
-  EventPairs ev_pke_sel, ev_pke_mm;     // pk_encrypt.hpp: the keystream pass, the contraction
-  EventPairs ev_ts_dig, ev_ts_mm;       // trlwe_switch.hpp: the digits pass, the contraction
-  uint64_t bootstraps = 0;
-  // device diagnostics: [0] shader cycles, [1] constant-rate ticks (both summed over blind-rotate
-  // workgroups while profiling is on), [2] error flag raised by kernels (bad gate code), [4] / [5] the same two
-  // sums for the matrix-core key switch
-  DevArray<unsigned long long> d_diag;
-  int rtc_khz = 100000;  // rate of s_memrealtime (hipDeviceAttributeWallClockRate)
-  ~tfhe_hip_ctx() { handle_gone(id); }  // (registration and erasure cannot drift apart: every `delete` passes here)
-};
-
-namespace {
-// The HIP current device is per host thread and shared with every other library in the process
-// (torch included): set ours for the duration of a call and put the caller's back.
-struct DeviceGuard {
-  int prev = -1;
-  hipError_t err = hipSuccess;
-  explicit DeviceGuard(int dev) {
-    if (hipGetDevice(&prev) != hipSuccess) prev = -1;
-    if (prev != dev) err = hipSetDevice(dev);
-  }
-  ~DeviceGuard() {
-    int cur = -1;
-    if (prev >= 0 && hipGetDevice(&cur) == hipSuccess && cur != prev) (void)hipSetDevice(prev);
-  }
-};
-}  // namespace
-
-// Every entry point: a key view runs on its parent -- `ctx` is re-pointed at the parent, whose mutex serialises the
-// call, whose device is made current (the caller's is put back on return) and whose key pointer K is bound to the
-// view's key for the duration of the call (RAII; a plain context binds its own).
-namespace {
-struct KeyBind {
-  tfhe_hip_ctx *c;
-  KeyBind(tfhe_hip_ctx *base, KeyState *k) : c(base) { c->K = k; }
-  ~KeyBind() { c->K = &c->own; }
-};
-}  // namespace
-#define ENTER(ctx)                                                                     \
-  tfhe_hip_ctx *self_ = (ctx);                                                         \
-  if (self_->parent) (ctx) = self_->parent;                                            \
-  std::lock_guard<FairMutex> lk_((ctx)->mu);                                           \
-  KeyBind kb_((ctx), &self_->own);                                                     \
-  DeviceGuard dg_((ctx)->device);                                                      \
-  if (dg_.err != hipSuccess) {                                                         \
-    err_slot((ctx)->id) = std::string("hipSetDevice: ") + hipGetErrorString(dg_.err);  \
-    return TFHE_HIP_EHIP;                                                              \
-  }
-
-#define HIPCHK(ctx, call)                                                                   \
-  do {                                                                                      \
-    hipError_t e_ = (call);                                                                 \
-    if (e_ != hipSuccess) {                                                                 \
-      err_slot((ctx)->id) = std::string(#call) + ": " + hipGetErrorString(e_);              \
-      return TFHE_HIP_EHIP;                                                                 \
-    }                                                                                       \
-  } while (0)
-
-#define CHK(expr)                 \
-  do {                            \
-    int rc_ = (expr);             \
-    if (rc_ != TFHE_HIP_OK) return rc_; \
-  } while (0)
-
-namespace {
-
+// ---- errors, buffers, scratch (declared in internal.hpp and secrets.hpp) -------------------------------------------------
 int fail(tfhe_hip_ctx *ctx, int code, const std::string &msg) {
   err_slot(ctx->id) = msg;
   return code;
@@ -319,6 +117,7 @@ int alloc_exact(tfhe_hip_ctx *ctx, DevBuf &b, size_t bytes, const char *call) {
 // stream itself and pay nothing).  take() (below) claims and then sizes; SecretStage claims in its constructor.
 int claim_scratch(tfhe_hip_ctx *ctx, hipStream_t s) { return hip_rc(ctx, ctx->scratch.claim(s)); }
 
+namespace {
 // Waits for the stream that owns the scratch (`unless_own`: not where that is the context's stream, which the caller
 // drains next).
 HipErr sync_scratch_owner(tfhe_hip_ctx *ctx, bool unless_own = false) {
@@ -326,18 +125,17 @@ HipErr sync_scratch_owner(tfhe_hip_ctx *ctx, bool unless_own = false) {
   if (!sc.owned || (unless_own && sc.owner == ctx->stream)) return {};
   return {hipStreamSynchronize(sc.owner), "hipStreamSynchronize(ctx->scratch_owner)"};
 }
+}  // namespace
 
 // The scratch buffers are sized here and nowhere else: the claim, then the growth.  `what`
 // names the buffer in the text of a failed allocation.
-int take(tfhe_hip_ctx *ctx, hipStream_t s, ScratchBuf &b, size_t bytes, bool exact = false, const char *what = "hipMalloc scratch: ") {
+int take(tfhe_hip_ctx *ctx, hipStream_t s, ScratchBuf &b, size_t bytes, bool exact, const char *what) {
   const HipErr r = ctx->scratch.take(s, b, bytes, exact);
   if (r && !r.what) return fail(ctx, TFHE_HIP_ENOMEM, std::string(what) + hipGetErrorString(r.e));
   return hip_rc(ctx, r);
 }
 
-// TFHE_HIP_COPY: the plain bootstrap of the first operand, no second one
-static_assert(kGateCount == TFHE_HIP_COPY + 1, "kGateTable (blind_rotate.hpp) has one row per tfhe_hip_gate");
-constexpr GatePrep kCopyPrep = kGateTable[TFHE_HIP_COPY];
+namespace {
 // launches with per-ciphertext gate codes: placeholders, the kernel reads the codes; cb != 0 keeps in_b attached
 constexpr GatePrep kCodesPrep{1u, 1u, 0u};
 
@@ -369,28 +167,6 @@ typedef void (*br_kernel_t)(BlindRotateArgs);
 // A plan is at most two launches over contiguous parts of the batch.
 enum BrKind { BR_BATCH = 0, BR_SINGLE = 1, BR_PAIR = 2 };
 const char *const kBrKindName[3] = {"batch", "single", "pair"};
-
-// The instantiation of a kernel family for this context: pick(KernelInst<l, fast_round, many>{}).  Every family of
-// kernels templated on the decomposition level and the rounding is named once, in its `pick`.
-template <int L_, bool FAST_, bool MANY_>
-struct KernelInst {
-  static constexpr int L = L_;
-  static constexpr bool FAST = FAST_, MANY = MANY_;
-};
-template <int L, typename Pick>
-auto kernel_inst_at(bool fast, bool many, Pick pick) {
-  return fast ? (many ? pick(KernelInst<L, true, true>{}) : pick(KernelInst<L, true, false>{}))
-              : (many ? pick(KernelInst<L, false, true>{}) : pick(KernelInst<L, false, false>{}));
-}
-template <typename Pick>
-auto kernel_inst(const tfhe_hip_ctx *ctx, bool many, Pick pick) {
-  const bool f = ctx->dispatch.fast_round;
-  switch (ctx->P.l) {
-    case 1: return kernel_inst_at<1>(f, many, pick);
-    case 2: return kernel_inst_at<2>(f, many, pick);
-    default: return kernel_inst_at<3>(f, many, pick);
-  }
-}
 
 // many: the many-LUT instantiation (BlindRotateArgs::lut_shift / n_luts / out_fn_stride) of the same kernel
 br_kernel_t br_kernel(const tfhe_hip_ctx *ctx, BrKind kind, bool many = false) {
@@ -464,21 +240,6 @@ BrPlan plan_blind_rotate(const tfhe_hip_ctx *ctx, size_t count) {
   if (tail) pl.add(tail <= N1 ? BR_SINGLE : BR_PAIR, count - tail, tail);
   return pl;
 }
-
-// One blind-rotation launch, described.  Everything defaults to "absent": a call site names what it sets.
-struct BrCall {
-  const uint32_t *in_a = nullptr, *in_b = nullptr;  // operand rows [count][n+1]; with idx_a / idx_b the base the indices select from
-  GatePrep gp = kCopyPrep;                          // the rotated row is ca * a + cb * b, [n] += cconst
-  const uint32_t *testvec = nullptr;                // nullptr: the key's own
-  int per_ct = 0;                                   // one test vector per ciphertext (only with `testvec`)
-  size_t count = 0;
-  // exactly one output: the rotated TRLWE [count][2][N], its extraction as the key switch's source [count][N+1], or its
-  // extraction as a TLWE of the input's shape [count][n+1] (bootstrap_without_key_switch)
-  uint32_t *out_trlwe = nullptr, *out_lv1 = nullptr, *out_ext2 = nullptr;
-  const uint8_t *gate_codes = nullptr;                  // per-ciphertext gates (gp: kCodesPrep)
-  const uint32_t *idx_a = nullptr, *idx_b = nullptr;    // row indices into in_a / in_b (circuit levels)
-  int lut_shift = 0;                                    // many-LUT: 2^lut_shift extractions per ciphertext
-};
 
 int launch_blind_rotate(tfhe_hip_ctx *ctx, hipStream_t s, const BrCall &c) {
   const size_t count = c.count;
@@ -582,8 +343,6 @@ km_kernel_t km_kernel(int nt) { return km_kernel_from<1>(nt); }
 bool ks_mfma_possible(const tfhe_hip_params &P) {
   return P.basebit == 2 && P.t >= 6 && P.t <= 13 && ks_mfma_nt(P.n) != 0;
 }
-// rows of a level-1 buffer the matrix-core kernel may read: whole 256-row workgroups
-size_t lv1_rows(size_t count) { return (count + kKmRows - 1) / kKmRows * kKmRows; }
 
 // ---- which key-switch kernel a batch of `count` runs on ----------------------------------------------
 // Integer arithmetic: every kernel returns the same bits (trgsw.rs:332-360).
@@ -728,6 +487,7 @@ int build_ksk_planes(tfhe_hip_ctx *ctx) {
   HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
   return TFHE_HIP_OK;
 }
+}  // namespace
 
 int launch_key_switch(tfhe_hip_ctx *ctx, hipStream_t s, const uint32_t *lv1, uint32_t *out, size_t count) {
   if (count == 0) return TFHE_HIP_OK;
@@ -819,21 +579,14 @@ int need_key(tfhe_hip_ctx *ctx) {
   return TFHE_HIP_OK;
 }
 
+namespace {
 int need_reenc_key(tfhe_hip_ctx *ctx) {
   if (!ctx->K->reenc_loaded) return fail(ctx, TFHE_HIP_ENOKEY, "re-encryption key not loaded");
   return TFHE_HIP_OK;
 }
-
-hipStream_t pick(tfhe_hip_ctx *ctx, void *stream) { return stream ? (hipStream_t)stream : ctx->stream; }
+}  // namespace
 
 // ---- device-pointer implementations (mutex held by caller) -------------------
-
-// sizes of the operands the entry points name: `count` TLWE rows [n+1], TRLWE [2][N], level-1 rows [N+1] in the whole
-// 256-row groups the matrix-core key switch reads, and a test vector (one per ciphertext, or one for the call)
-size_t tlwe_bytes(const tfhe_hip_ctx *ctx, size_t count) { return count * (size_t)(ctx->P.n + 1) * 4; }
-size_t trlwe_bytes(size_t count) { return count * (size_t)2 * kN * 4; }
-size_t lv1_bytes(size_t count) { return lv1_rows(count) * (size_t)(kN + 1) * 4; }
-size_t testvec_bytes(int per_ct, size_t count) { return trlwe_bytes(per_ct ? count : 1); }
 
 // A bootstrap on stream `s`: the blind rotation `call` describes (everything but its output), then, with `keyswitch`,
 // the key switch of its count << lut_shift extracted rows into `out`; without, the rows are extracted straight into
@@ -850,6 +603,7 @@ int run_bootstrap(tfhe_hip_ctx *ctx, hipStream_t s, BrCall call, uint32_t *out, 
   return launch_key_switch(ctx, s, call.out_lv1, out, rows);
 }
 
+namespace {
 int gate_dev(tfhe_hip_ctx *ctx, int gate, const uint32_t *a, const uint32_t *b, uint32_t *out,
              size_t count, hipStream_t s) {
   GatePrep gp;
@@ -866,6 +620,8 @@ int reencrypt_dev(tfhe_hip_ctx *ctx, const uint32_t *in, uint32_t *out, size_t c
   return launch_key_switch(ctx, s, (const uint32_t *)ctx->lv1.p, out, count);
 }
 
+}  // namespace
+
 // n_luts in {1, 2, 4, 8} -> log2, else -1
 int lut_shift_of(int n_luts) {
   switch (n_luts) {
@@ -877,6 +633,7 @@ int lut_shift_of(int n_luts) {
   }
 }
 
+namespace {
 // the checks of the many-LUT entry points, in one order for the host, device and pool forms: why the call is
 // TFHE_HIP_EINVAL, or nullptr (the context forms file the text under the context, the pool forms under the pool)
 const char *many_refusal(const uint32_t *a, uint32_t cb, const uint32_t *b, const uint32_t *testvec, int n_luts,
@@ -928,6 +685,8 @@ bool via_pin(tfhe_hip_ctx *ctx, Staging &s, size_t bytes) {  // (no arena: the c
   return ctx->stage_pinned && s.pool_pinned && bytes >= (1u << 20) && s.pin.grow(bytes, false);
 }
 
+}  // namespace
+
 int to_dev(tfhe_hip_ctx *ctx, Staging &s, const void *src, size_t bytes) {
   CHK(ensure(ctx, s.dev, bytes));
   if (via_pin(ctx, s, bytes)) {
@@ -955,8 +714,7 @@ int to_host(tfhe_hip_ctx *ctx, void *dst, Staging &s, size_t bytes) {
 // are -- each ciphertext is read once in the blind rotation's prologue and written once by the key switch, and
 // those PCIe transactions spread over the whole launch instead of three staging copies around it.
 // Returns the device view of `p`, or nullptr when `p` is ordinary pageable memory.
-template <class T>
-T *pinned_view(T *p, size_t bytes) {
+void *pinned_view(const void *p, size_t bytes) {
   if (!p) return nullptr;
   hipPointerAttribute_t at;
   if (hipPointerGetAttributes(&at, (const void *)p) != hipSuccess) {
@@ -989,49 +747,13 @@ T *pinned_view(T *p, size_t bytes) {
     (void)hipGetLastError();
     return nullptr;
   }
-  return (T *)d;
+  return d;
 }
 
-// The direct path, after a call's own checks.  One operand: `bytes` at `host`, staged through `slot`; a null `host`
-// is an operand this call does not use, which reaches the launch as nullptr.
-struct HostIn {
-  const void *host;
-  size_t bytes;
-  Staging *slot;
-};
-// With `zero_copy` (gate, gates_mixed, bootstrap, mux) and every operand and the output pinned, the launch runs on
-// them in place (see pinned_view) and the stream is synchronised.  Otherwise each operand is staged with to_dev in
-// list order, the launch writes ctx->out, and the result returns through to_host.  launch(in, out) gets the device
-// view of each operand in list order and of the output.
-template <size_t N, class Launch>
-int host_call(tfhe_hip_ctx *ctx, bool zero_copy, const HostIn (&in)[N], void *out, size_t out_bytes, Launch &&launch) {
-  const void *d[N] = {};
-  if (zero_copy) {  // all operands pinned: no staging
-    bool pinned = true;
-    for (size_t i = 0; i < N && pinned; ++i)
-      if (in[i].host) pinned = (d[i] = pinned_view(in[i].host, in[i].bytes)) != nullptr;
-    if (void *dout = pinned ? pinned_view(out, out_bytes) : nullptr) {
-      CHK(launch(d, dout));
-      HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-      return TFHE_HIP_OK;
-    }
-  }
-  for (size_t i = 0; i < N; ++i) {
-    d[i] = nullptr;
-    if (!in[i].host) continue;
-    CHK(to_dev(ctx, *in[i].slot, in[i].host, in[i].bytes));
-    d[i] = in[i].slot->dev.p;
-  }
-  CHK(ensure(ctx, ctx->out.dev, out_bytes));
-  CHK(launch(d, ctx->out.dev.p));
-  return to_host(ctx, out, ctx->out, out_bytes);
-}
-const uint32_t *u32(const void *p) { return (const uint32_t *)p; }
 int launched(tfhe_hip_ctx *ctx) {  // status of the kernel launch just made
   HIPCHK(ctx, hipGetLastError());
   return TFHE_HIP_OK;
 }
-}  // namespace
 
 #include "combine.hpp"
 #include "key_change.hpp"
@@ -1044,6 +766,12 @@ bool comb_interactive(const tfhe_hip_ctx *ctx) {
   return t != 0 && combq::now_ns() - t < kYieldWindowNs;
 }
 }  // namespace
+
+bool params_supported(const tfhe_hip_params *p) {
+  return !(p->n < 1 || p->n > 1279 || p->l < 1 || p->l > 3 || p->bgbit < 1 || p->l * p->bgbit > 32 ||
+           p->basebit < 1 || p->basebit > 10 || p->t < 1 || p->basebit * p->t > 31 ||
+           (double)ksk_bytes(*p) >= 4294967296.0);
+}
 
 // =============================================================================
 // C ABI
@@ -1065,14 +793,6 @@ const char *tfhe_hip_last_error(const tfhe_hip_ctx *ctx) {
   if (ctx && ctx->parent) ctx = ctx->parent;
   return ctx ? err_text(ctx->id) : g_create_error.c_str();
 }
-
-namespace {
-bool params_supported(const tfhe_hip_params *p) {
-  return !(p->n < 1 || p->n > 1279 || p->l < 1 || p->l > 3 || p->bgbit < 1 || p->l * p->bgbit > 32 ||
-           p->basebit < 1 || p->basebit > 10 || p->t < 1 || p->basebit * p->t > 31 ||
-           (double)ksk_bytes(*p) >= 4294967296.0);
-}
-}  // namespace
 
 int tfhe_hip_ctx_create(const tfhe_hip_params *p, int device, tfhe_hip_ctx **out) {
   if (!p || !out) {
@@ -1284,7 +1004,6 @@ int tfhe_hip_load_cloud_key(tfhe_hip_ctx *ctx, const double *bsk, const uint32_t
   CHK(begin_key_change(ctx, KEY_BUF_ALL));
   const tfhe_hip_params &P = ctx->P;
   const size_t polys = bsk_polys(P), rows = ksk_rows(P);
-  const int base = 1 << P.basebit;
   // bootstrapping key: upload the reference layout, permute + scale on the device
   CHK(upload_through_temp(ctx, "bsk", {{bsk, bsk_bytes(P)}}, 0, [&](void *d_ref) {
     hipLaunchKernelGGL(k_bsk_convert, dim3((unsigned)polys), dim3(512), 0, ctx->stream, (const double *)d_ref, ctx->K->d_bsk, polys, key_scale(ctx->dispatch.fast_round));
@@ -1292,8 +1011,7 @@ int tfhe_hip_load_cloud_key(tfhe_hip_ctx *ctx, const double *bsk, const uint32_t
   }));
   // key-switching key: upload the reference layout, pad rows to 16 B and zero the k == 0 rows
   CHK(upload_through_temp(ctx, "ksk", {{ksk, rows * (size_t)(P.n + 1) * 4}}, 0, [&](void *d_ref) {
-    hipLaunchKernelGGL(k_ksk_convert, dim3((unsigned)rows), dim3(256), 0, ctx->stream, (const uint32_t *)d_ref, ctx->K->d_ksk, P.n, base, rows);
-    return hipGetLastError();
+    return ksk_convert_launch(ctx, (const uint32_t *)d_ref, rows);
   }));
   HIPCHK(ctx, hipMemcpyAsync(ctx->K->d_testvec, testvec, key_testvec_bytes(), hipMemcpyHostToDevice, ctx->stream));
   HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
@@ -1380,8 +1098,7 @@ int tfhe_hip_export_cloud_key(tfhe_hip_ctx *ctx, double *bsk, uint32_t *ksk, uin
   if (ksk) {
     const size_t rows = ksk_rows(P);
     CHK(ensure(ctx, ctx->out.dev, rows * (size_t)(P.n + 1) * 4));
-    hipLaunchKernelGGL(k_ksk_export, dim3((unsigned)rows), dim3(256), 0, ctx->stream, ctx->K->d_ksk, (uint32_t *)ctx->out.dev.p, P.n, rows);
-    HIPCHK(ctx, hipGetLastError());
+    HIPCHK(ctx, ksk_export_launch(ctx, (uint32_t *)ctx->out.dev.p, rows));
     CHK(to_host(ctx, ksk, ctx->out, rows * (size_t)(P.n + 1) * 4));
   }
   if (decomp_offset) *decomp_offset = ctx->K->offset;
@@ -1655,7 +1372,7 @@ int tfhe_hip_batch_bootstrap(tfhe_hip_ctx *ctx, const uint32_t *in, const uint32
   const size_t bytes = tlwe_bytes(ctx, count);
   // the test vector is zero-copied on its own when it is pinned, whatever the ciphertexts are
   const size_t tv_bytes = testvec_bytes(per_ct, count);
-  const uint32_t *d_tv = pinned_view(testvec, tv_bytes);
+  const uint32_t *d_tv = u32(pinned_view(testvec, tv_bytes));
   if (testvec && !d_tv) {
     CHK(to_dev(ctx, ctx->tv, testvec, tv_bytes));
     d_tv = u32(ctx->tv.dev.p);
@@ -1810,8 +1527,7 @@ int tfhe_hip_load_reenc_key(tfhe_hip_ctx *ctx, const uint32_t *key) {
   if (const hipError_t e = hipMemsetAsync(ctx->K->d_ksk, 0, ksk_bytes(P), ctx->stream))
     return fail(ctx, TFHE_HIP_EHIP, std::string("re-encryption key upload: ") + hipGetErrorString(e));
   CHK(upload_through_temp(ctx, "re-encryption key", {{key, rows * (size_t)(P.n + 1) * 4}}, 0, [&](void *d_ref) {
-    hipLaunchKernelGGL(k_ksk_convert, dim3((unsigned)rows), dim3(256), 0, ctx->stream, (const uint32_t *)d_ref, ctx->K->d_ksk, P.n, base, rows);
-    return hipGetLastError();
+    return ksk_convert_launch(ctx, (const uint32_t *)d_ref, rows);
   }));
   return commit_reenc_key(ctx);
 }
@@ -2032,14 +1748,3 @@ int tfhe_hip_synchronize(tfhe_hip_ctx *ctx) {
 }  // extern "C"
 #include "pool.hpp"
 #include "circuit.hpp"
-#include "seeded.hpp"
-#include "packing.hpp"
-#include "unpack.hpp"
-#include "matmul.hpp"
-#include "table.hpp"
-#include "packing_keygen.hpp"
-#include "pk_encrypt.hpp"
-#include "sym_encrypt.hpp"
-#include "decrypt.hpp"
-#include "trlwe_encrypt.hpp"
-#include "trlwe_switch.hpp"

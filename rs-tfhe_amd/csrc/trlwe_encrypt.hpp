@@ -16,21 +16,16 @@
 // Secrets travel as in sym_encrypt.hpp, through a SecretStage (secrets.hpp) over the context's `sym_sec` buffer:
 // K [8 words], s1 [N words] and the spectrum of s1 [N / 2 double2] (k_key_spectrum, as stage_secrets runs it -- the
 // spectrum is secret too).  The host copy is wiped, and the buffer is zeroed behind the kernel on the same stream.
-//
-// Both kernels are templates: instantiations are emitted after the library's other kernels, whose code stays
-// byte-identical.
 #pragma once
-#include "decrypt.hpp"
+#include "internal.hpp"
 
 namespace tfhe {
 
 // One wave per group m = blockIdx.x.  plain: [count]; out: [groups][2][N] or NULL; bodies: [groups][N] or NULL.
-template <int WG>
-__global__ __launch_bounds__(WG) void k_trlwe_rows(const double2 *__restrict__ s1_spec, const double2 *__restrict__ twt,
+__global__ __launch_bounds__(64) void k_trlwe_rows(const double2 *__restrict__ s1_spec, const double2 *__restrict__ twt,
                                                     const ChaChaKey *__restrict__ key_p, ChaChaKey seed, uint64_t first_group,
                                                     const uint32_t *__restrict__ plain, size_t count, double alpha,
                                                     uint32_t *__restrict__ bodies, uint32_t *__restrict__ out) {
-  static_assert(WG == 64, "one wave per group: natural_mask's tile belongs to the workgroup");
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   double2 *tile = reinterpret_cast<double2 *>(smem);
   const int lane = threadIdx.x;
@@ -121,10 +116,9 @@ int trlwe_bulk(tfhe_hip_ctx *ctx, const ChaChaKey &seed, const ChaChaKey &k, con
   int rc = sec.land("packed encryption: ", kTrlweSecBytes);
   if (rc == TFHE_HIP_OK) {
     double2 *d_spec = sec.dev<double2>(kTrlweSecSpecAt);
-    hipLaunchKernelGGL(k_key_spectrum, dim3(1), dim3(64), kStageLdsBytes, s, sec.dev(32), ctx->d_tw, d_spec);
-    rc = launched(ctx);
+    rc = key_spectrum_launch(ctx, sec.dev(32), d_spec, s);
     if (rc == TFHE_HIP_OK) {
-      hipLaunchKernelGGL(k_trlwe_rows<64>, dim3((unsigned)trlwe_groups(count)), dim3(64), kStageLdsBytes, s, (const double2 *)d_spec,
+      hipLaunchKernelGGL(k_trlwe_rows, dim3((unsigned)trlwe_groups(count)), dim3(64), kStageLdsBytes, s, (const double2 *)d_spec,
                          ctx->d_tw, sec.dev<const ChaChaKey>(0), seed, first_group, plain, count, alpha, bodies, out);
       rc = launched(ctx);
     }

@@ -37,11 +37,8 @@
 // lane, a wave's store of one plane (or one quarter of b') being one contiguous KiB; b' leaves as 16-byte store
 // instructions, and so does the digit loop's remainder, but in its two-row unrolled body this compiler issues the same
 // 16 bytes as four dword stores (the pass is 5 % of the switch: left as it is).
-//
-// Every kernel here is a template: instantiations are emitted after the library's other kernels, so the code of every
-// existing kernel stays byte-identical.
 #pragma once
-#include "keygen.hpp"
+#include "internal.hpp"
 
 namespace tfhe {
 
@@ -58,14 +55,12 @@ __device__ __forceinline__ uint32_t ts_psi_at(const uint32_t *__restrict__ p, ui
 }
 
 // One wave per row l < t.  rows: [t][2][N] (a half, b half), bodies: [t][N].
-template <int WG>
-__global__ __launch_bounds__(WG) void k_gen_trlwe_switch_key(const uint32_t *__restrict__ key_from,
+__global__ __launch_bounds__(64) void k_gen_trlwe_switch_key(const uint32_t *__restrict__ key_from,
                                                               const double2 *__restrict__ to_spec,
                                                               const double2 *__restrict__ twt, uint32_t *__restrict__ rows,
                                                               uint32_t *__restrict__ bodies, int k, uint32_t kinv,
                                                               int basebit, double alpha,
                                                               const ChaChaKey *__restrict__ key_p, ChaChaKey seed) {
-  static_assert(WG == 64, "one wave per row");
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   double2 *tile = reinterpret_cast<double2 *>(smem);
   const int lane = threadIdx.x;
@@ -91,6 +86,7 @@ __global__ __launch_bounds__(WG) void k_gen_trlwe_switch_key(const uint32_t *__r
 }
 
 // rows [t][2][N]: a_l regenerated from S (natural_mask, as generation made it), b_l from bodies [t][N].
+// (WG stays a parameter: as a plain function the compiler orders this kernel's stores differently.)
 template <int WG>
 __global__ __launch_bounds__(WG) void k_expand_trlwe_switch_key(const uint32_t *__restrict__ bodies,
                                                                  uint32_t *__restrict__ rows, int k, ChaChaKey seed) {
@@ -107,10 +103,9 @@ __global__ __launch_bounds__(WG) void k_expand_trlwe_switch_key(const uint32_t *
 
 // One wave per ciphertext of the chunk.  in [chunk][2][N]; dig [chunk][t][N] int8 = -d_l(psi_k(a)[c]); bp [chunk][N]
 // = psi_k(b).  1 <= basebit <= 7, 1 <= t, basebit t <= 32, k odd in [1, 2N).
-template <int WG>
-__global__ __launch_bounds__(WG) void k_trlwe_switch_digits(const uint32_t *__restrict__ in, int k, int basebit, int t,
+__global__ __launch_bounds__(64) void k_trlwe_switch_digits(const uint32_t *__restrict__ in, int k, int basebit, int t,
                                                              int8_t *__restrict__ dig, uint32_t *__restrict__ bp) {
-  static_assert(WG == 64 && kN == 16 * WG, "one wave per ciphertext, sixteen coefficients a lane");
+  static_assert(kN == 16 * 64, "one wave per ciphertext, sixteen coefficients a lane");
   __shared__ __attribute__((aligned(16))) uint32_t sa[kN];
   __shared__ __attribute__((aligned(16))) uint32_t sb[kN];
   const int lane = threadIdx.x;
@@ -226,7 +221,7 @@ int gen_trlwe_switch_key_locked(tfhe_hip_ctx *ctx, TsKey &e, const uint32_t *key
   uint32_t *d_rows = e.rows;
   // the temporary: the bodies [t][N]; drained and freed on every path
   CHK(upload_through_temp(ctx, "TRLWE switching key generation", {}, body_words * 4, [&](void *tmp) {
-    hipLaunchKernelGGL(k_gen_trlwe_switch_key<64>, dim3((unsigned)t), dim3(64), kStageLdsBytes, ctx->stream, d_from, d_spec,
+    hipLaunchKernelGGL(k_gen_trlwe_switch_key, dim3((unsigned)t), dim3(64), kStageLdsBytes, ctx->stream, d_from, d_spec,
                        ctx->d_tw, d_rows, (uint32_t *)tmp, k, ts_inverse(k), basebit, alpha, d_rk, seed);
     if (const hipError_t err = hipGetLastError()) return err;
     if (bodies) return hipMemcpyAsync(bodies, tmp, body_words * 4, hipMemcpyDeviceToHost, ctx->stream);
@@ -250,7 +245,7 @@ int trlwe_switch_dev(tfhe_hip_ctx *ctx, const TsKey &e, const uint32_t *in, size
     {
       TimedScope timed(ctx->ev_ts_dig, s, ctx->profiling);  // (while profiling is on: tfhe_hip_get_trlwe_switch_times)
       CHK(hip_rc(ctx, timed.err));
-      hipLaunchKernelGGL(k_trlwe_switch_digits<64>, dim3((unsigned)n), dim3(64), 0, s, in + c0 * 2 * kN, e.k, e.basebit,
+      hipLaunchKernelGGL(k_trlwe_switch_digits, dim3((unsigned)n), dim3(64), 0, s, in + c0 * 2 * kN, e.k, e.basebit,
                          e.t, d_dig, d_bp);
       CHK(launched(ctx));  // (the pair is closed whichever way the launch ended)
       CHK(hip_rc(ctx, timed.close()));

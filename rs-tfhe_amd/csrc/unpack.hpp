@@ -17,10 +17,8 @@
 // start at every alignment), a few lanes the h head words and the tail.  The LDS reads of a quad are descending
 // dwords 4 apart between lanes, a 4-way bank conflict: 4 waves x 4 reads x 8 LDS cycles = 128 cycles per row against
 // the ~560 clocks a CU's share of HBM bandwidth takes to write the row's 4,100 bytes -- the stores are the cost.
-//
-// Every kernel here is a template: instantiations are emitted after the library's other kernels, so the code of every
-// existing kernel stays byte-identical.
 #pragma once
+#include "internal.hpp"
 
 namespace tfhe {
 

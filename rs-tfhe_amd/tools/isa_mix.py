@@ -3,7 +3,7 @@
 instantiation the reference's parameter sets of that l run: FAST (one-add rounding) at l = 3 (bgbit 6), the general
 rounding at l = 2 (SECURITY_UINT1, bgbit 10) and l = 1 (bgbit 18 .. 23) -- tfhe_hip_ctx_create's fast_round rule.
 
-    hipcc --offload-arch=gfx950 -O3 ... -S --cuda-device-only -o tfhe_hip.s tfhe_hip.hip
+    hipcc --offload-arch=gfx950 -O3 ... -S --cuda-device-only -o tfhe_hip.s tfhe_hip.hip   (the core unit: the loop is there)
     python3 isa_mix.py tfhe_hip.s [--json kernel_isa.json]
 
 `make` runs this after building the library, so bench.py prices the kernel against the FP64 vector roofline with

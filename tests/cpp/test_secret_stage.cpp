@@ -82,7 +82,7 @@ struct tfhe_hip_ctx {
   std::string err;
 };
 
-namespace {
+// (the three functions secrets.hpp declares: the library defines them in tfhe_hip.hip)
 int fail(tfhe_hip_ctx *ctx, int code, const std::string &msg) {
   ctx->err = msg;
   return code;
@@ -102,7 +102,6 @@ int claim_scratch(tfhe_hip_ctx *ctx, hipStream_t s) {
   g_log.push_back({'k', s, nullptr, 0});
   return g_fail_claim ? fail(ctx, TFHE_HIP_EHIP, "claim") : TFHE_HIP_OK;
 }
-}  // namespace
 
 static bool all_bytes(const void *p, size_t bytes, unsigned char v) {
   for (size_t i = 0; i < bytes; ++i)

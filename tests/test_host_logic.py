@@ -86,12 +86,16 @@ def test_kernel_selectors_are_validated_without_gpu(monkeypatch):
         assert lib.tfhe_hip_ctx_create(ctypes.byref(params), 0, ctypes.byref(ctx)) == _capi.EINVAL, (var, val)
         assert text in lib.tfhe_hip_last_error(None), lib.tfhe_hip_last_error(None)
         monkeypatch.delenv(var)
-    # the product library reads exactly the variables the header lists
-    src = "".join(open(os.path.join(ROOT, "rs-tfhe_amd", "csrc", f)).read() for f in ("tfhe_hip.hip", "pool.hpp", "combine.hpp"))
+    # the product library reads exactly the variables the header lists (every source file of every translation unit)
+    csrc = os.path.join(ROOT, "rs-tfhe_amd", "csrc")
+    files = [f for f in sorted(os.listdir(csrc)) if f.endswith((".hip", ".hpp", ".cpp"))]
+    assert {"tfhe_hip.hip", "planes.hip", "rings.hip", "internal.hpp", "pool.hpp", "combine.hpp"} <= set(files)
+    src = "".join(open(os.path.join(csrc, f)).read() for f in files)
     read = set(re.findall(r'getenv\("(TFHE_HIP_[A-Z0-9_]+)"\)', src))
+    assert len(re.findall(r"\bgetenv\(", src)) == len(re.findall(r'getenv\("TFHE_HIP_[A-Z0-9_]+"\)', src))  # no other spelling
     hdr = open(os.path.join(ROOT, "include", "tfhe_hip.h")).read()
     assert read == {"TFHE_HIP_BR_KERNEL", "TFHE_HIP_KS_KERNEL", "TFHE_HIP_POOL_RCCL", "TFHE_HIP_POOL_PINNED_STAGING",
-                    "TFHE_HIP_COMBINE"}, read
+                    "TFHE_HIP_COMBINE", "TFHE_HIP_BIVARIATE_CHUNK"}, read
     for v in read:
         assert v in hdr
 
@@ -103,7 +107,9 @@ def test_no_experiment_switches_in_product_sources():
     import glob
 
     csrc = os.path.join(ROOT, "rs-tfhe_amd", "csrc")
-    files = sorted(glob.glob(os.path.join(csrc, "*.hpp"))) + [os.path.join(csrc, "tfhe_hip.hip")]
+    units = sorted(glob.glob(os.path.join(csrc, "*.hip")))
+    assert len(units) >= 3 and os.path.join(csrc, "tfhe_hip.hip") in units  # every translation unit of the library
+    files = sorted(glob.glob(os.path.join(csrc, "*.hpp"))) + units
     assert len(files) >= 10
     mutations = {"TFHE_ABL_ROUND_LSB", "TFHE_ABL_TW_REL"}
     abl, overrides, experiment = set(), set(), set()
@@ -255,9 +261,10 @@ def test_gates_api_surface():
 
 
 def test_kernels_compile_without_scratch_and_keep_their_occupancy():
-    """Register-allocation guard: every gfx950 kernel of the library must compile with zero scratch
-    (a 12-register spill in the l = 1 blind rotation cost 9 % before it was noticed), the batch blind
+    """Register-allocation guard: every gfx950 kernel of the library -- of every translation unit -- must compile with
+    zero scratch (a 12-register spill in the l = 1 blind rotation cost 9 % before it was noticed), the batch blind
     rotation must keep two waves per SIMD and the LDS-ring key switch three."""
+    import glob
     import re
     import shutil
     import subprocess
@@ -265,23 +272,60 @@ def test_kernels_compile_without_scratch_and_keep_their_occupancy():
     hipcc = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
     if not os.path.exists(hipcc):
         pytest.skip("hipcc not available")
-    src = os.path.join(ROOT, "rs-tfhe_amd", "csrc", "tfhe_hip.hip")
-    r = subprocess.run([hipcc, "--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=fast", "--cuda-device-only",
-                        "-c", "-o", os.devnull, "-Rpass-analysis=kernel-resource-usage", src],
-                       capture_output=True, text=True, timeout=900)
-    assert r.returncode == 0, r.stderr[-2000:]
-    names = re.findall(r"Function Name: (\S+)", r.stderr)
-    scratch = [int(x) for x in re.findall(r"ScratchSize \[bytes/lane\]: (\d+)", r.stderr)]
-    occ = [int(x) for x in re.findall(r"Occupancy \[waves/SIMD\]: (\d+)", r.stderr)]
-    assert len(names) == len(scratch) == len(occ) and len(names) > 20
+    units = sorted(glob.glob(os.path.join(ROOT, "rs-tfhe_amd", "csrc", "*.hip")))
+    assert len(units) >= 3 and any(u.endswith("tfhe_hip.hip") for u in units), units
+    procs = [subprocess.Popen([hipcc, "--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=fast", "--cuda-device-only",
+                               "-c", "-o", os.devnull, "-Rpass-analysis=kernel-resource-usage", u],
+                              stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True) for u in units]
+    names, scratch, occ = [], [], []
+    for u, p in zip(units, procs):
+        _, err = p.communicate(timeout=900)
+        assert p.returncode == 0, (u, err[-2000:])
+        found = re.findall(r"Function Name: (\S+)", err)
+        assert found, u  # every unit has kernels of its own
+        names += found
+        scratch += [int(x) for x in re.findall(r"ScratchSize \[bytes/lane\]: (\d+)", err)]
+        occ += [int(x) for x in re.findall(r"Occupancy \[waves/SIMD\]: (\d+)", err)]
+    assert len(names) == len(scratch) == len(occ) and len(set(names)) >= 120
     spilled = {n: s for n, s in zip(names, scratch) if s}
     assert not spilled, spilled
     by_name = dict(zip(names, occ))
+    assert any("14k_blind_rotateI" in n for n in by_name) and any("k_key_switch_b4" in n for n in by_name)
     for n, o in by_name.items():
         if "14k_blind_rotateI" in n:
             assert o >= 2, (n, o)
         if "k_key_switch_b4" in n:
             assert o >= 3, (n, o)
+
+
+def test_every_kernel_has_its_host_stub_in_one_object():
+    """libtfhe_hip.so is linked from one object per translation unit (csrc/Makefile).  A kernel is emitted by exactly one
+    unit: over the objects `make` leaves, no kernel's host stub -- exported or local -- is defined in two of them, so no
+    unit launches a copy of its own of a kernel that another unit owns.  The objects are there after a build."""
+    import collections
+    import glob
+    import shutil
+    import subprocess
+
+    csrc = os.path.join(ROOT, "rs-tfhe_amd", "csrc")
+    units = sorted(os.path.basename(u)[:-4] for u in glob.glob(os.path.join(csrc, "*.hip")))
+    objs = sorted(glob.glob(os.path.join(csrc, "obj", "*.o")))
+    assert [os.path.basename(o)[:-2] for o in objs] == units and len(units) >= 3, (units, objs)
+    nm = shutil.which("nm")
+    assert nm, "nm (binutils) not available"
+    owners = collections.defaultdict(list)
+    for o in objs:
+        out = subprocess.run([nm, "--defined-only", o], capture_output=True, text=True, check=True).stdout
+        for line in out.splitlines():
+            parts = line.split()
+            if len(parts) == 3 and "__device_stub__" in parts[2]:
+                owners[parts[2]].append(os.path.basename(o))
+    assert len(owners) >= 120, len(owners)
+    shared = {k: v for k, v in owners.items() if len(v) > 1}
+    assert not shared, shared
+    per_unit = collections.Counter(v[0] for v in owners.values())
+    assert set(per_unit) == {u + ".o" for u in units}, per_unit  # every unit emits kernels
+    assert any("k_blind_rotate" in k and v == ["tfhe_hip.o"] for k, v in owners.items())
 
 
 def test_keyed_engine_pool_logic(monkeypatch):

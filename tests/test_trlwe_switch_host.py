@@ -200,7 +200,7 @@ def test_the_chunk_constant_mirrors_the_header():
     text = open(os.path.join(ROOT, "rs-tfhe_amd", "csrc", "trlwe_switch.hpp")).read()
     m = re.search(r"constexpr size_t kTsChunk = (\d+);", text)
     assert m and int(m.group(1)) == PK.TRLWE_SWITCH_CHUNK
-    state = open(os.path.join(ROOT, "rs-tfhe_amd", "csrc", "tfhe_hip.hip")).read()
+    state = open(os.path.join(ROOT, "rs-tfhe_amd", "csrc", "internal.hpp")).read()  # KeyState
     m = re.search(r"kMaxTrlweSwitchKeys = (\d+);", state)
     assert m and int(m.group(1)) == PK.TRLWE_SWITCH_MAX_KEYS
 
