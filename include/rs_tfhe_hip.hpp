@@ -727,6 +727,56 @@ struct TrlweSwitchKey {
   int device_ = -1;
 };
 
+// A TRGSW selector of include/tfhe_hip.h ("packed CMUX"): the gadget (basebit, t) and the rows [2t][2][N] -- what
+// TRGSWLv1::encrypt_torus (trgsw.rs:29-49) makes, held by the caller.  Its message is a polynomial mu(X) with small
+// integer coefficients; a bit is the constant 0 or 1.
+struct Trgsw {
+  int basebit = 6, t = 3;
+  std::vector<Torus> rows;  // [2t][2][N]
+  // `count` selectors from mu [count][N] on the GPU (tfhe_hip_batch_encrypt_trgsw); row `row` of selector m takes index
+  // first_index + m 2t + row of the streams.  rng_key: the 32-byte generator key K, or nullptr to draw it from
+  // getrandom(2); a (K, index) pair must never encrypt twice.  alpha < 0: the set's alpha_lv1.
+  static std::vector<Trgsw> encrypt_batch(Engine &e, const SecretKey &sk, const std::vector<int32_t> &mu, int basebit = 6, int t = 3,
+                                          const uint8_t *rng_key = nullptr, uint64_t first_index = 0, double alpha = -1) {
+    if (mu.size() % (size_t)N) throw std::runtime_error("Trgsw: mu is [count][N]");
+    if (t < 1 || t > 32) throw std::runtime_error("Trgsw: t out of range");
+    const size_t count = mu.size() / (size_t)N, words = (size_t)(2 * t) * 2 * (size_t)N;
+    std::vector<Torus> flat(count * words);
+    e.check(tfhe_hip_batch_encrypt_trgsw(e.ctx(), sk.key_lv1.data(), mu.data(), count, basebit, t,
+                                         alpha < 0 ? sk.params.alpha_lv1 : alpha, rng_key, first_index, nullptr, flat.data()));
+    std::vector<Trgsw> out(count);
+    for (size_t m = 0; m < count; ++m) {
+      out[m].basebit = basebit, out[m].t = t;
+      out[m].rows.assign(flat.begin() + (std::ptrdiff_t)(m * words), flat.begin() + (std::ptrdiff_t)((m + 1) * words));
+    }
+    return out;
+  }
+  // the selector of one bit
+  static Trgsw encrypt_bool(Engine &e, const SecretKey &sk, bool bit, int basebit = 6, int t = 3, const uint8_t *rng_key = nullptr,
+                            uint64_t first_index = 0, double alpha = -1) {
+    std::vector<int32_t> mu((size_t)N, 0);
+    mu[0] = bit ? 1 : 0;
+    return encrypt_batch(e, sk, mu, basebit, t, rng_key, first_index, alpha)[0];
+  }
+};
+
+namespace packing {
+// d0 + sel (.) (d1 - d0) on [count][2][N] packed ciphertexts (flat): d1 where the selector encrypts 1, d0 where it
+// encrypts 0, under ONE selector (tfhe_hip_batch_trlwe_cmux).  d0 == nullptr: the external product sel (.) d1.
+// reference_digits: the reference's truncating decomposition.  Needs no key.
+inline std::vector<Torus> cmux(Engine &e, const Trgsw &sel, const Torus *d0, const Torus *d1, size_t count,
+                               bool reference_digits = false) {
+  if (sel.t < 1 || sel.rows.size() != (size_t)(2 * sel.t) * 2 * (size_t)N) throw std::runtime_error("Trgsw: rows must be [2t][2][N]");
+  std::vector<Torus> out(count * 2 * (size_t)N);
+  e.check(tfhe_hip_batch_trlwe_cmux(e.ctx(), sel.rows.data(), sel.basebit, sel.t, reference_digits ? TFHE_HIP_CMUX_REFERENCE_DIGITS : 0,
+                                    d0, d1, count, out.data()));
+  return out;
+}
+inline std::vector<Torus> external_product(Engine &e, const Trgsw &sel, const Torus *d, size_t count) {
+  return cmux(e, sel, nullptr, d, count);
+}
+}  // namespace packing
+
 namespace tlwe {
 inline Torus inner_product(const Ciphertext &c, const std::vector<Torus> &key) {
   Torus ip = 0;

@@ -520,6 +520,83 @@ typedef struct tfhe_hip_trlwe_switch_times {
 } tfhe_hip_trlwe_switch_times;
 int tfhe_hip_get_trlwe_switch_times(tfhe_hip_ctx *ctx, tfhe_hip_trlwe_switch_times *out);
 
+/* ---- packed CMUX: caller-held TRGSW selectors ------
+ *
+ * The one product whose second operand is encrypted data of the caller's own: the external product TRGSW (.) TRLWE and
+ * the CMUX on it, out = d0 + sel (.) (d1 - d0) -- trgsw::cmux and external_product_with_fft of the reference
+ * (trgsw.rs:77-116, 173-196) with a TRGSW the caller holds (TRGSWLv1::encrypt_torus, trgsw.rs:29-49), not a row of the
+ * bootstrapping key.  A server selects between packed ciphertexts under an encrypted bit: an encrypted `if`, or a lookup
+ * in a table of packed ciphertexts by an encrypted index (rs_tfhe_amd.packing.lookup).  No bootstrap, no cloud key.
+ *
+ * Definition (normative).  N = 1024; all arithmetic wraps mod 2^32; (*) is the negacyclic product mod X^N + 1.
+ *   Shapes.  A gadget (beta, t) with 1 <= beta <= 7 (the digits fit a signed byte), 1 <= t <= 32 (2t <= 64 columns of
+ *     the polynomial product) and beta t <= 32: the TRLWE key switch's box with 2t columns.  g_i = 2^(32 - beta (i+1)),
+ *     0 <= i < t.
+ *   TRGSW.  [2t][2][N] u32 carrying a message polynomial mu(X) with small integer coefficients: every row a TRLWE lv1
+ *     encryption of zero (the a half, then the b half), then g_i mu(X) added to the a half of row i and to the b half of
+ *     row t + i.  This is the reference's row order; its encrypt_torus(p) is mu = p, a constant.
+ *   Digits of a word w.  off = sum_i 2^(beta-1) g_i; rnd = 2^(31 - beta t) when beta t < 32, else 0;
+ *       u_i(w) = ((w + off + rnd) >> (32 - beta (i+1))) & (2^beta - 1),      d_i(w) = u_i(w) - 2^(beta-1)
+ *     in [-2^(beta-1), 2^(beta-1)): the rounding decomposition of packing and of the TRLWE key switch.  With the flag
+ *     TFHE_HIP_CMUX_REFERENCE_DIGITS rnd = 0: trgsw::decomposition (trgsw.rs:144-171) word for word, so that
+ *     (beta, t) = (bgbit, l) reproduces the reference's cmux.  Truncation leaves a bias of about
+ *     |s|_1 2^(-beta t - 1) mu per level at the end slots, which a CMUX tree, unlike a blind rotation, never rotates
+ *     away: the default rounds.
+ *   The call.  sel is ONE TRGSW; d0, d1 and out are [count][2][N].  With x = d1 - d0, or x = d1 when d0 == NULL, and
+ *     D_i(p) = sum_j d_i(p[j]) X^j, for each half c:
+ *       out[m][c] = (d0 ? d0[m][c] : 0) + sum_{i<t} D_i(x[m].a) (*) sel[i][c] + sum_{i<t} D_i(x[m].b) (*) sel[t+i][c].
+ *     d0 == NULL is the plain external product.  One selector serves the whole batch: the shape of a lookup level,
+ *     and what makes the batch the rows of one integer GEMM (the plaintext polynomial product's, with the digit
+ *     polynomials for weights).  The result is defined in integers: every device gives these words exactly.
+ * Consequences.  For mu in {0, 1} the phase of out is that of d0 + mu (d1 - d0) plus, per coefficient, noise of
+ *   variance about  2t N (2^(2 beta) / 12) alpha^2  +  mu (1 + N/2) 2^(-2 beta t) / 12  (torus units squared; alpha the
+ *   selector's noise).  DESIGN.md section 9 tabulates which (beta, t) keep a boolean and an m = 16 message inside 8
+ *   standard deviations after ten levels.
+ * Selector encryption (normative).  tfhe_hip_batch_encrypt_trgsw makes `count` TRGSWs [count][2t][2][N] from
+ *   mu [count][N] int32 under key_lv1 and a 32-byte generator key K.  Row `row` of selector m has the 64-bit index
+ *   r = first_index + m 2t + row:
+ *     Mask seed  S = words 0..7 of block(K, counter 0, nonce (0, 30, 0x444553)), returned in mask_seed_out.
+ *     a          N keystream words under S, natural order (word x = word x mod 16 of counter x / 16), nonce
+ *                (r & 0xffffffff, r >> 32, 0x45474C "EGL").
+ *     e          f64_to_torus(N(0, alpha)) per coefficient under K, nonce (r & 0xffffffff, r >> 32, 0x45474E "EGN"),
+ *                in the BSK generators' word order, as for packed encryption.  alpha = 0 gives exactly zero noise.
+ *     b          = a (*) s1 + e (the product exact), and AFTER the body is formed g_i mu(X) is added to a (row < t,
+ *                i = row) or to b (i = row - t).
+ *   Full form only.  A (K, index) pair must never encrypt twice.  Away from samples within rounding of a torus step
+ *   every implementation gives the same words.
+ * Semantics.  A CMUX needs no key: it runs on a context with no cloud key loaded.  count == 0 returns TFHE_HIP_OK and
+ *   writes nothing.  TFHE_HIP_EINVAL, nothing written: sel, d1 or out NULL (count > 0), a shape outside the box, an
+ *   unknown flag bit, count > 2^31 - 1 (encryption: count 2t > 2^31 - 1, key_lv1 NULL or not binary, mu or out NULL,
+ *   alpha negative or NaN, row indices past 2^64).  out must not overlap sel, d0 or d1; this is not checked.  Bulk
+ *   calls: the context's mutex and the one staging path of the host-pointer form, never the combining front end.
+ *   _dev: device pointers, d0 / d1 / out 16-byte aligned, queued on `stream` (NULL: the context's stream); the digits
+ *   pass through a scratch of the context, 2,048 ciphertexts (2,048 2t N bytes) a pass.  The encryption's _dev form
+ *   takes mu and out on the device, runs on the context's stream and has finished when it returns (the staged secrets
+ *   are wiped behind it); key_lv1 and rng_key (NULL: getrandom(2)) are host pointers in both forms, mask_seed_out may
+ *   be NULL.  There are no pool forms. */
+enum { TFHE_HIP_CMUX_REFERENCE_DIGITS = 1 }; /* flags; rnd = 0: the reference's truncating decomposition */
+int tfhe_hip_batch_trlwe_cmux(tfhe_hip_ctx *ctx, const uint32_t *sel, int basebit, int t, int flags, const uint32_t *d0,
+                              const uint32_t *d1, size_t count, uint32_t *out);
+int tfhe_hip_batch_trlwe_cmux_dev(tfhe_hip_ctx *ctx, const uint32_t *sel, int basebit, int t, int flags, const uint32_t *d0,
+                                  const uint32_t *d1, size_t count, uint32_t *out, void *stream);
+/* A CLIENT-side call: it takes the secret key. */
+int tfhe_hip_batch_encrypt_trgsw(tfhe_hip_ctx *ctx, const uint32_t *key_lv1, const int32_t *mu, size_t count, int basebit, int t,
+                                 double alpha, const uint8_t rng_key[32], uint64_t first_index, uint8_t mask_seed_out[32],
+                                 uint32_t *out);
+int tfhe_hip_batch_encrypt_trgsw_dev(tfhe_hip_ctx *ctx, const uint32_t *key_lv1, const int32_t *mu, size_t count, int basebit,
+                                     int t, double alpha, const uint8_t rng_key[32], uint64_t first_index,
+                                     uint8_t mask_seed_out[32], uint32_t *out);
+/* While profiling is enabled the three steps of every pass of the CMUX -- the digits kernel, the contraction (the
+ * product's kernel) and the addend kernel (no pair without d0) -- are bracketed by HIP events on the stream they run on.
+ * Synchronises the recorded events, returns the sums since the last call and resets them. */
+typedef struct tfhe_hip_cmux_times {
+  double digits_ms;      /* sum of the digits kernel durations                  */
+  double contraction_ms; /* sum of the matrix-core contraction durations        */
+  double addend_ms;      /* sum of the addend kernel durations                  */
+  uint64_t passes;       /* passes of each (one per 2,048 ciphertexts)          */
+} tfhe_hip_cmux_times;
+int tfhe_hip_get_cmux_times(tfhe_hip_ctx *ctx, tfhe_hip_cmux_times *out);
+
 /* ---- encrypted 2-D convolution: int8 filters over a feature map of LWE ciphertexts ------
  *
  * The convolutional layer beside the linear one: `out_c` plaintext int8 filters of k_h x k_w x in_c slide over an

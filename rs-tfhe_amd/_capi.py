@@ -66,6 +66,12 @@ class TrlweSwitchTimes(C.Structure):
     _fields_ = [("digits_ms", C.c_double), ("contraction_ms", C.c_double), ("passes", C.c_uint64)]
 
 
+class CmuxTimes(C.Structure):
+    """struct tfhe_hip_cmux_times"""
+
+    _fields_ = [("digits_ms", C.c_double), ("contraction_ms", C.c_double), ("addend_ms", C.c_double), ("passes", C.c_uint64)]
+
+
 class CombineStats(C.Structure):
     """struct tfhe_hip_combine_stats"""
 
@@ -135,6 +141,11 @@ SIGNATURES = {
     "tfhe_hip_batch_trlwe_keyswitch": (C.c_int, [_CTX, C.c_int, _P, _SZ, _P]),
     "tfhe_hip_batch_trlwe_keyswitch_dev": (C.c_int, [_CTX, C.c_int, _P, _SZ, _P, _P]),
     "tfhe_hip_get_trlwe_switch_times": (C.c_int, [_CTX, C.POINTER(TrlweSwitchTimes)]),
+    "tfhe_hip_batch_trlwe_cmux": (C.c_int, [_CTX, _P, C.c_int, C.c_int, C.c_int, _P, _P, _SZ, _P]),
+    "tfhe_hip_batch_trlwe_cmux_dev": (C.c_int, [_CTX, _P, C.c_int, C.c_int, C.c_int, _P, _P, _SZ, _P, _P]),
+    "tfhe_hip_batch_encrypt_trgsw": (C.c_int, [_CTX, _P, _P, _SZ, C.c_int, C.c_int, C.c_double, _P, C.c_uint64, _P, _P]),
+    "tfhe_hip_batch_encrypt_trgsw_dev": (C.c_int, [_CTX, _P, _P, _SZ, C.c_int, C.c_int, C.c_double, _P, C.c_uint64, _P, _P]),
+    "tfhe_hip_get_cmux_times": (C.c_int, [_CTX, C.POINTER(CmuxTimes)]),
     "tfhe_hip_batch_tlwe_conv2d": (C.c_int, [_CTX, C.POINTER(Conv2dShape), _P, _P, _P, _SZ, _P]),
     "tfhe_hip_batch_tlwe_conv2d_dev": (C.c_int, [_CTX, C.POINTER(Conv2dShape), _P, _P, _P, _SZ, _P, _P]),
     "tfhe_hip_batch_pack_table": (C.c_int, [_CTX, _P, C.c_int, _SZ, _P]),

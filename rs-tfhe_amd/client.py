@@ -374,6 +374,41 @@ class SecretKey:
         return self.encrypt_packed_f64_seeded(msgs.astype(np.float64) * (1.0 / (2.0 * m)), mask_seed, first_group, alpha,
                                               rng_key, device)
 
+    # ---- TRGSW selectors (packed CMUX, include/tfhe_hip.h) -------------------------------------------
+    def encrypt_trgsw(self, mu, basebit: int = 6, t: int = 3, alpha: float | None = None, rng_key=None, first_index: int = 0,
+                      device=None):
+        """TRGSW selectors of the message polynomials mu (small integers, [N]: one packing.Trgsw; [count][N]: a list)
+        under key_lv1, in the format of include/tfhe_hip.h ("packed CMUX") -- TRGSWLv1::encrypt_torus (trgsw.rs:29-49)
+        is mu = a constant.  device=None makes them on the CPU (numpy), device=d runs `tfhe_hip_batch_encrypt_trgsw`
+        there; rng_key is the 32-byte generator key K (None: fresh from the OS), under which both give the same mask
+        seed and, away from borderline noise samples, the same words.  Row `row` of selector m takes index
+        first_index + m 2t + row; a (K, index) pair must never encrypt twice.  alpha: alpha_lv1 by default."""
+        from .packing import Trgsw, encrypt_trgsw_rows
+
+        mu = np.asarray(mu)
+        one = mu.ndim == 1
+        mu = np.ascontiguousarray(mu, dtype=np.int32).reshape(-1, N)
+        alpha = self.params.alpha_lv1 if alpha is None else alpha
+        if rng_key is not None and (not isinstance(rng_key, (bytes, bytearray)) or len(rng_key) != 32):
+            raise ValueError("rng_key is 32 bytes")
+        if device is not None:
+            from .bootstrap import engine_for
+
+            rows = engine_for(self.params, device).batch_encrypt_trgsw(self.key_lv1, mu, basebit, t, alpha, rng_key, first_index)
+        else:
+            rows = encrypt_trgsw_rows(self.key_lv1, mu, basebit, t, alpha, os.urandom(32) if rng_key is None else bytes(rng_key),
+                                      first_index)
+        sels = [Trgsw(basebit, t, r) for r in rows]
+        return sels[0] if one else sels
+
+    def encrypt_trgsw_bool(self, bits, basebit: int = 6, t: int = 3, alpha: float | None = None, rng_key=None,
+                           first_index: int = 0, device=None):
+        """Selectors of bits: mu = 0 or 1, a constant polynomial (a scalar: one packing.Trgsw; an array: a list)."""
+        bits = np.asarray(bits)
+        mu = np.zeros((bits.size, N), np.int32)
+        mu[:, 0] = bits.reshape(-1).astype(bool)
+        return self.encrypt_trgsw(mu[0] if bits.ndim == 0 else mu, basebit, t, alpha, rng_key, first_index, device)
+
     # ---- evaluation key ----------------------------------------------------------------------
     def cloud_key(self, seed=None, device: int = 0):
         """CloudKey::new(&secret_key) (key.rs:59-66): generated on the GPU in a fresh key view of the shared context

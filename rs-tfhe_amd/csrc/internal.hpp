@@ -157,6 +157,7 @@ struct tfhe_hip_ctx {
   ScratchBuf biv_s1, biv_tv;               // tree bootstrap (table.hpp): stage-1 results [m][chunk][n+1], their tables [chunk][2][N]
   ScratchBuf pke_sel;                      // public-key encryption (pk_encrypt.hpp): selector words and addends of one pass
   ScratchBuf ts_dig;                       // TRLWE key switch (trlwe_switch.hpp): digit planes [chunk][t][N] i8, then b' [chunk][N]
+  ScratchBuf cm_dig;                       // packed CMUX (cmux.hpp): digit planes [chunk][2t][N] i8
   Scratch scratch;                         // the stream whose queued work may still use them (claim_scratch)
   DevBuf sym_sec;                      // the staged secrets of one call (secrets.hpp: SecretStage), wiped behind it
   // host-API staging: a / b / c / out also stage through their arenas on pool members (to_dev / to_host);
@@ -188,6 +189,7 @@ struct tfhe_hip_ctx {
   EventPairs ev_br, ev_ks;              // one pair per launch while profiling is on
   EventPairs ev_pke_sel, ev_pke_mm;     // pk_encrypt.hpp: the keystream pass, the contraction
   EventPairs ev_ts_dig, ev_ts_mm;       // trlwe_switch.hpp: the digits pass, the contraction
+  EventPairs ev_cm_dig, ev_cm_mm, ev_cm_add;  // cmux.hpp: the digits pass, the contraction, the addend
   uint64_t bootstraps = 0;
   // device diagnostics: [0] shader cycles, [1] constant-rate ticks (both summed over blind-rotate
   // workgroups while profiling is on), [2] error flag raised by kernels (bad gate code), [4] / [5] the same two
@@ -448,7 +450,7 @@ struct GeneratorKey {
 // kernel-argument memory).  The layout: K, the slot derive_public_seed writes, key_lv0 [n], key_lv1 [N], and the
 // spectrum of key_lv1, which k_key_spectrum writes (16-byte aligned: it is read as double2).  The TRLWE switching key
 // (trlwe_switch.hpp) stages a ring key where key_lv0 stands: k0_words = N, d_k0 the key switched from, d_k1 the key
-// switched to.
+// switched to.  TRGSW encryption (cmux.hpp) stages no first key at all: k0_words = 0.
 struct StagedSecrets {
   size_t k0_words;  // words of the first key: n, or N for a ring key
   SecretStage stage;

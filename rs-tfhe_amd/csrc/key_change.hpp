@@ -163,6 +163,7 @@ int derive_public_seed(tfhe_hip_ctx *ctx, const StagedSecrets &s, ChaChaKey &see
 template int derive_public_seed<kStreamSeededSeed>(tfhe_hip_ctx *, const StagedSecrets &, ChaChaKey &);  // seeded.hpp
 template int derive_public_seed<kStreamPackSeed>(tfhe_hip_ctx *, const StagedSecrets &, ChaChaKey &);    // packing_keygen.hpp
 template int derive_public_seed<kStreamTksSeed>(tfhe_hip_ctx *, const StagedSecrets &, ChaChaKey &);     // trlwe_switch.hpp
+template int derive_public_seed<kStreamTrgswSeed>(tfhe_hip_ctx *, const StagedSecrets &, ChaChaKey &);   // cmux.hpp
 
 int lwe_rows_launch(tfhe_hip_ctx *ctx, const LweRowJob &j, hipStream_t s) {
   const tfhe_hip_params &P = ctx->P;

@@ -1,5 +1,5 @@
 // rings.hip -- the ring-row family, one translation unit of libtfhe_hip.so: seeded (compressed) cloud keys and
-// ciphertexts, packed TRLWE encryption, decryption and the TRLWE key switch.
+// ciphertexts, packed TRLWE encryption, decryption, the TRLWE key switch and the packed CMUX.
 // What it uses of the core is declared in internal.hpp; every kernel of the headers below is emitted here and nowhere else.
 #include "internal.hpp"
 
@@ -7,3 +7,4 @@
 #include "trlwe_encrypt.hpp"
 #include "decrypt.hpp"
 #include "trlwe_switch.hpp"
+#include "cmux.hpp"

@@ -18,6 +18,7 @@ GATE_IDS = {
     "nand": NAND, "or": OR, "and": AND, "xor": XOR, "xnor": XNOR, "nor": NOR,
     "and_ny": ANDNY, "and_yn": ANDYN, "or_ny": ORNY, "or_yn": ORYN, "copy": COPY,
 }
+CMUX_REFERENCE_DIGITS = 1  # TFHE_HIP_CMUX_REFERENCE_DIGITS
 
 
 def _u32(a) -> np.ndarray:
@@ -830,6 +831,89 @@ class Engine(_Handle):
         t = _capi.TrlweSwitchTimes()
         self._chk(self._lib.tfhe_hip_get_trlwe_switch_times(self._ctx, C.byref(t)))
         return {"digits_ms": t.digits_ms, "contraction_ms": t.contraction_ms, "passes": int(t.passes)}
+
+    # -- packed CMUX (include/tfhe_hip.h): caller-held TRGSW selectors --------------------------------------------------
+    @staticmethod
+    def _trgsw_shape(basebit: int, t: int) -> None:
+        from .packing import check_gadget
+
+        check_gadget(basebit, t)
+
+    def batch_trlwe_cmux(self, sel, basebit: int, t: int, d0, d1, reference_digits: bool = False, out=None, stream=None):
+        """out = d0 + sel (.) (d1 - d0) over [count][2][N] packed ciphertexts under ONE TRGSW selector `sel` [2t][2][N] of
+        gadget (basebit, t); d0=None is the external product sel (.) d1 (`tfhe_hip_batch_trlwe_cmux`).  numpy in, numpy
+        out; or 32-bit CUDA tensors on this engine's GPU in and a tensor out (`out`: where to write, which must overlap
+        no input; a new tensor by default), queued on `stream` (torch's current stream by default).
+        reference_digits: the reference's truncating decomposition (TFHE_HIP_CMUX_REFERENCE_DIGITS)."""
+        flags = CMUX_REFERENCE_DIGITS if reference_digits else 0
+        if _is_tensor(d1):
+            import torch
+
+            if d1.dim() != 3 or tuple(d1.shape[1:]) != (2, N):
+                raise ValueError(f"d1 must be [count][2][{N}]")
+            if d0 is not None and tuple(d0.shape) != tuple(d1.shape):
+                raise ValueError("d0 must have d1's shape")
+            if not _is_tensor(sel) or sel.numel() != max(int(t), 0) * 4 * N:
+                raise ValueError(f"sel must be a tensor [2t][2][{N}]")
+            if out is None:
+                out = torch.empty_like(d1)
+            elif tuple(out.shape) != tuple(d1.shape):
+                raise ValueError("out must have d1's shape")
+            self._call("batch_trlwe_cmux_dev", self._tp(None, sel), int(basebit), int(t), flags,
+                       self._tp(None, d0) if d0 is not None else None, self._tp(None, d1), int(d1.shape[0]),
+                       self._tp(None, out), self._stream_ptr(None, stream))
+            return out
+        d1 = _u32(d1).reshape(-1, 2, N)
+        sel = _u32(sel).reshape(-1)
+        if len(sel) != max(int(t), 0) * 4 * N:
+            raise ValueError(f"sel must be [2t][2][{N}]")
+        if d0 is not None:
+            d0 = _u32(d0).reshape(-1, 2, N)
+            if d0.shape != d1.shape:
+                raise ValueError("d0 must have d1's shape")
+        res = np.empty_like(d1)
+        self._call("batch_trlwe_cmux", _ptr(sel), int(basebit), int(t), flags, _ptr(d0), _ptr(d1), len(d1), _ptr(res))
+        return res
+
+    def batch_encrypt_trgsw(self, key_lv1, mu, basebit: int, t: int, alpha: float = None, rng_key: bytes = None,
+                            first_index: int = 0, return_seed: bool = False):
+        """mu [count][N] small integers (or [N]: one) -> count TRGSW selectors [count][2t][2][N] under key_lv1, made on
+        the GPU (`tfhe_hip_batch_encrypt_trgsw`); row `row` of selector m takes index first_index + m 2t + row of the
+        streams.  rng_key: the 32-byte generator key K, None draws it from getrandom(2); a (K, index) pair must never
+        encrypt twice.  alpha: alpha_lv1 of the set by default.  return_seed: also the public mask seed S."""
+        self._trgsw_shape(basebit, t)
+        k1 = self._key_lv1_arg(key_lv1)
+        mu = np.ascontiguousarray(mu, dtype=np.int32).reshape(-1, N)
+        out = np.empty((len(mu), 2 * int(t), 2, N), np.uint32)
+        seed = (C.c_uint8 * 32)()
+        rk, rkp = self._rng_key_arg(rng_key)
+        self._call("batch_encrypt_trgsw", _ptr(k1), _ptr(mu), len(mu), int(basebit), int(t),
+                   C.c_double(self.params.alpha_lv1 if alpha is None else alpha), rkp, C.c_uint64(int(first_index)),
+                   C.addressof(seed), _ptr(out))
+        return (out, bytes(seed)) if return_seed else out
+
+    def batch_encrypt_trgsw_dev(self, key_lv1, mu, basebit: int, t: int, out, alpha: float = None, rng_key: bytes = None,
+                                first_index: int = 0) -> bytes:
+        """Device form: mu [count][N] (int32) and out [count][2t][2][N] (32-bit words) torch tensors on this engine's
+        GPU; key_lv1 stays a host array.  Runs on the context's stream and has finished on return.  Returns S."""
+        self._trgsw_shape(basebit, t)
+        k1 = self._key_lv1_arg(key_lv1)
+        if mu.dim() != 2 or mu.shape[1] != N:
+            raise ValueError(f"mu must be [count][{N}]")
+        if tuple(out.shape) != (mu.shape[0], 2 * int(t), 2, N):
+            raise ValueError(f"out must be [{mu.shape[0]}][{2 * int(t)}][2][{N}]")
+        seed = (C.c_uint8 * 32)()
+        rk, rkp = self._rng_key_arg(rng_key)
+        self._call("batch_encrypt_trgsw_dev", _ptr(k1), self._tp(None, mu), int(mu.shape[0]), int(basebit), int(t),
+                   C.c_double(self.params.alpha_lv1 if alpha is None else alpha), rkp, C.c_uint64(int(first_index)),
+                   C.addressof(seed), self._tp(None, out))
+        return bytes(seed)
+
+    def cmux_times(self) -> dict:
+        """Kernel times of the packed CMUX's passes since the last call (profiling on)."""
+        t = _capi.CmuxTimes()
+        self._chk(self._lib.tfhe_hip_get_cmux_times(self._ctx, C.byref(t)))
+        return {"digits_ms": t.digits_ms, "contraction_ms": t.contraction_ms, "addend_ms": t.addend_ms, "passes": int(t.passes)}
 
     # -- encrypted 2-D convolution (include/tfhe_hip.h): int8 filters over a feature map of ciphertexts -------------------
     def _conv2d_shape(self, w_shape, cts_shape, bias_len, stride, padding):

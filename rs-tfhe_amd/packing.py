@@ -19,6 +19,10 @@ From one ring key to another ("TRLWE key switch" in the header): `TrlweSwitchKey
 `gen_trace_keys` and `trace` run slot automorphisms and the partial trace on the GPU (csrc/trlwe_switch.hpp,
 `Engine.batch_trlwe_keyswitch`); proxy_reenc.PackedReencryptionKey is the k = 1 case.  The integer model lives with the
 tests (tests/trlwe_switch_model.py).
+
+Selecting between packed ciphertexts under encrypted bits ("packed CMUX" in the header): `Trgsw` is a selector,
+`encrypt_trgsw_rows` the CPU form of its encryption, `cmux`, `external_product` and `lookup` run on the GPU
+(csrc/cmux.hpp, `Engine.batch_trlwe_cmux`).  The integer model is tests/cmux_model.py.
 """
 from __future__ import annotations
 
@@ -430,3 +434,119 @@ def trace(packed, steps: int, engine):
     for k in trace_ks(steps):
         ct = ct + engine.batch_trlwe_keyswitch(k, ct)  # wrapping: uint32 arrays, int32 tensors
     return ct
+
+
+# ---- packed CMUX: caller-held TRGSW selectors -----------------------------------------------------------------------------
+TRGSW_SEED_STREAM = 30  # the selectors' mask seed from the generator key (domain "DES")
+CMUX_CHUNK = 2048  # ciphertexts a pass of the GPU's digit scratch: kCmuxChunk of csrc/cmux.hpp
+
+
+def check_gadget(basebit: int, t: int) -> None:
+    """The box of include/tfhe_hip.h ("packed CMUX"): the TRLWE key switch's with 2t columns."""
+    if not (1 <= int(basebit) <= 7 and 1 <= int(t) <= 32 and int(basebit) * int(t) <= 32):
+        raise ValueError("1 <= basebit <= 7, 1 <= t <= 32, basebit * t <= 32")
+
+
+class Trgsw:
+    """A TRGSW selector of include/tfhe_hip.h ("packed CMUX"): the gadget (basebit, t) and the rows [2t][2][N] u32 (a
+    numpy array, or a CUDA tensor of 32-bit words) -- 48 KiB at t = 3."""
+
+    def __init__(self, basebit: int, t: int, rows):
+        check_gadget(basebit, t)
+        self.basebit, self.t = int(basebit), int(t)
+        if type(rows).__module__.startswith("torch"):
+            if rows.numel() != 4 * self.t * N:
+                raise ValueError("rows must be [2t][2][N]")
+            self.rows = rows.reshape(2 * self.t, 2, N)
+        else:
+            rows = np.ascontiguousarray(rows, dtype=np.uint32)
+            if rows.size != 4 * self.t * N:
+                raise ValueError("rows must be [2t][2][N]")
+            self.rows = rows.reshape(2 * self.t, 2, N)
+
+    def on(self, engine):
+        """The rows as a CUDA tensor on the engine's GPU (uploaded once, then kept)."""
+        if not type(self.rows).__module__.startswith("torch"):
+            import torch
+
+            self.rows = torch.from_numpy(self.rows.view(np.int32)).to(f"cuda:{engine.device}")
+        return self.rows
+
+    def host(self) -> np.ndarray:
+        """The rows as a u32 array."""
+        if type(self.rows).__module__.startswith("torch"):
+            return self.rows.cpu().numpy().view(np.uint32)
+        return self.rows
+
+
+def trgsw_mask_seed(rng_key: bytes) -> bytes:
+    """S = words 0..7 of block(K, counter 0, nonce (0, 30, "DES"))"""
+    return chacha20_block(rng_key, 0, 0, TRGSW_SEED_STREAM, DOMAIN_SEED)[:8].astype("<u4").tobytes()
+
+
+def encrypt_trgsw_rows(key_lv1, mu, basebit: int, t: int, alpha: float, rng_key: bytes, first_index: int = 0) -> np.ndarray:
+    """The CPU form of `tfhe_hip_batch_encrypt_trgsw`: mu [count][N] small integers -> [count][2t][2][N] u32.  Row
+    `row` of selector m is the packed-encryption row of zero at index first_index + m 2t + row under the domains "EGL"
+    / "EGN", and g_i mu(X) is added afterwards: to the a half for row = i < t, to the b half for row = t + i."""
+    from .seeded import DOMAINS_TRGSW, symmetric_trlwe_rows
+
+    check_gadget(basebit, t)
+    mu = np.ascontiguousarray(mu, dtype=np.int64).reshape(-1, N)
+    rows = len(mu) * 2 * t
+    if int(first_index) < 0 or int(first_index) + rows > 1 << 64:
+        raise ValueError("the row indices run past 2^64")
+    idx = np.uint64(int(first_index)) + np.arange(rows, dtype=np.uint64)
+    out = symmetric_trlwe_rows(trgsw_mask_seed(rng_key), bytes(rng_key), idx, key_lv1, np.zeros(rows * N, np.uint32),
+                               rows * N, alpha, domains=DOMAINS_TRGSW).reshape(len(mu), 2, t, 2, N)
+    g = np.array([1 << (32 - (i + 1) * basebit) for i in range(t)], np.int64)
+    add = ((g[None, :, None] * mu[:, None, :]) & 0xFFFFFFFF).astype(np.uint32)  # [count][t][N]
+    with np.errstate(over="ignore"):
+        out[:, 0, :, 0] += add
+        out[:, 1, :, 1] += add
+    return out.reshape(len(mu), 2 * t, 2, N)
+
+
+def _packed_arg(x, engine):
+    """[count][2][N] for the engine: a CUDA tensor as it is, anything else as a u32 array"""
+    if x is None or type(x).__module__.startswith("torch"):
+        return x
+    return np.ascontiguousarray(x, np.uint32).reshape(-1, 2, N)
+
+
+def cmux(sel: Trgsw, d0, d1, engine, reference_digits: bool = False):
+    """d0 + sel (.) (d1 - d0) on [count][2][N] packed ciphertexts (numpy, or CUDA tensors on the engine's GPU): d1 where
+    the selector encrypts 1, d0 where it encrypts 0, in every slot, under ONE selector (`Engine.batch_trlwe_cmux`)."""
+    d1 = _packed_arg(d1, engine)
+    rows = sel.on(engine) if type(d1).__module__.startswith("torch") else sel.host()
+    return engine.batch_trlwe_cmux(rows, sel.basebit, sel.t, _packed_arg(d0, engine), d1, reference_digits=reference_digits)
+
+
+def external_product(sel: Trgsw, d, engine, reference_digits: bool = False):
+    """sel (.) d: the ciphertexts of mu(X) times the phases of d, for a selector of message polynomial mu."""
+    return cmux(sel, None, d, engine, reference_digits)
+
+
+def lookup(selectors, table, engine):
+    """Entry k of a table of 2^d packed ciphertexts [2^d][2][N] under the encrypted index k = sum_i bit_i 2^i, bit_i the
+    message of selectors[i] (least significant first): d CMUX calls, level i running 2^(d-1-i) pairs under selector
+    i, between two buffers on the engine's GPU.  The table is laid out in bit-reversed order once, so that the pairs
+    of every level are the two contiguous halves of what the level before left.  Returns [2][N] (numpy for a numpy
+    table, else a tensor)."""
+    import torch
+
+    d = len(selectors)
+    tensors = type(table).__module__.startswith("torch")
+    tab = table if tensors else torch.from_numpy(np.ascontiguousarray(table, np.uint32).reshape(-1, 2, N).view(np.int32))
+    if tab.dim() != 3 or tab.shape[0] != 1 << d or tuple(tab.shape[1:]) != (2, N):
+        raise ValueError(f"{d} selectors look up a table of [{1 << d}][2][{N}]")
+    tab = tab.to(f"cuda:{engine.device}")
+    if d == 0:
+        return tab[0] if tensors else tab[0].cpu().numpy().view(np.uint32)
+    rev = [int(format(p, f"0{d}b")[::-1], 2) for p in range(1 << d)]
+    cur = tab[torch.tensor(rev, device=tab.device)]  # position p holds entry rev(p)
+    other = torch.empty_like(cur[: 1 << (d - 1)])
+    for i, sel in enumerate(selectors):
+        n = 1 << (d - 1 - i)
+        engine.batch_trlwe_cmux(sel.on(engine), sel.basebit, sel.t, cur[:n], cur[n:2 * n], out=other[:n])
+        cur, other = other, cur
+    return cur[0] if tensors else cur[0].cpu().numpy().view(np.uint32)

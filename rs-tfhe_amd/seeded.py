@@ -23,6 +23,7 @@ DOMAINS_SYM_PK = (0x504B4D, 0x504B5A)       # "PKM", "PKZ": rows of the public k
 DOMAINS_SYM_RK = (0x524B4D, 0x524B53)       # "RKM", "RKS": rows of the symmetric re-encryption key, both under K
 # packed encryption (include/tfhe_hip.h): groups of N slots, indexed like the rows above
 DOMAINS_TRLWE = (0x45524C, 0x45524E)        # "ERL" mask polynomials under the public seed S, "ERN" noise under K
+DOMAINS_TRGSW = (0x45474C, 0x45474E)        # "EGL", "EGN": the same for the rows of TRGSW selectors ("packed CMUX")
 _SIGMA = (0x61707865, 0x3320646E, 0x79622D32, 0x6B206574)
 _QR = ((0, 4, 8, 12), (1, 5, 9, 13), (2, 6, 10, 14), (3, 7, 11, 15),
        (0, 5, 10, 15), (1, 6, 11, 12), (2, 7, 8, 13), (3, 4, 9, 14))
@@ -266,11 +267,12 @@ def trlwe_masks(seed: bytes, first_group: int, groups: int) -> np.ndarray:
 
 
 def symmetric_trlwe_rows(mask_key: bytes, rng_key: bytes, groups_idx, key_lv1, plain, count: int, alpha: float,
-                         full: bool = True, chunk: int = 64) -> np.ndarray:
+                         full: bool = True, chunk: int = 64, domains=DOMAINS_TRLWE) -> np.ndarray:
     """The CPU form of the packed-encryption format: group m of `groups_idx` (u64 indices g) is
     (a, a (*) s1 + f64_to_torus(e) + plain[m N ..]) with a under (mask_key, g, "ERL") in natural order and e under
     (rng_key, g, "ERN") in the BSK generators' word order; the slots at or past `count` encrypt 0.  plain: [count] torus
-    words.  Returns [groups][2][N], or the bodies [groups][N] with full=False."""
+    words.  Returns [groups][2][N], or the bodies [groups][N] with full=False.  domains: the (mask, noise) domain words,
+    DOMAINS_TRGSW for the rows of TRGSW selectors."""
     g = np.asarray(groups_idx, np.uint64).reshape(-1)
     s1 = np.asarray(key_lv1, np.uint32).reshape(N)
     count = int(count)
@@ -285,9 +287,9 @@ def symmetric_trlwe_rows(mask_key: bytes, rng_key: bytes, groups_idx, key_lv1, p
         for lo in range(0, len(g), chunk):
             sl = slice(lo, lo + chunk)
             rows = len(g[sl])
-            a = keystream(mask_key, N, lo32[sl], hi32[sl], DOMAINS_TRLWE[0])
+            a = keystream(mask_key, N, lo32[sl], hi32[sl], domains[0])
             # block 2 lane + h gives the pairs of coefficients lane + 64 (4h + q) (first sample) and + 512 (second), q < 4
-            w = chacha20_block(rng_key, np.arange(128, dtype=np.uint64), lo32[sl, None], hi32[sl, None], DOMAINS_TRLWE[1])
+            w = chacha20_block(rng_key, np.arange(128, dtype=np.uint64), lo32[sl, None], hi32[sl, None], domains[1])
             g0, g1 = gauss2(w.reshape(rows, 64, 2, 4, 4), float(alpha))  # [rows, lane, h, q]
             e = np.concatenate([f64_to_torus(g0).reshape(rows, 64, 8).transpose(0, 2, 1).reshape(rows, 512),
                                 f64_to_torus(g1).reshape(rows, 64, 8).transpose(0, 2, 1).reshape(rows, 512)], axis=1)

@@ -151,7 +151,16 @@ extern "C" {   // packing key switch (include/tfhe_hip.h): up to N lv0 results i
     fn tfhe_hip_load_trlwe_switch_key(ctx: *mut TfheHipCtx, k: c_int, basebit: c_int, t: c_int, mask_seed: *const u8,
                                       bodies: *const u32) -> c_int;
     fn tfhe_hip_batch_trlwe_keyswitch(ctx: *mut TfheHipCtx, k: c_int, input: *const u32, count: usize, out: *mut u32) -> c_int;
+    // packed CMUX (include/tfhe_hip.h): caller-held TRGSW selectors; no key, no pool forms
+    fn tfhe_hip_batch_trlwe_cmux(ctx: *mut TfheHipCtx, sel: *const u32, basebit: c_int, t: c_int, flags: c_int, d0: *const u32,
+                                 d1: *const u32, count: usize, out: *mut u32) -> c_int;
+    fn tfhe_hip_batch_encrypt_trgsw(ctx: *mut TfheHipCtx, key_lv1: *const u32, mu: *const int32_t, count: usize, basebit: c_int,
+                                    t: c_int, alpha: f64, rng_key: *const u8, first_index: u64, mask_seed_out: *mut u8,
+                                    out: *mut u32) -> c_int;
 }
+
+/// TFHE_HIP_CMUX_REFERENCE_DIGITS: the reference's truncating decomposition (trgsw.rs:144-171) in `HipEngine::trlwe_cmux`
+pub const CMUX_REFERENCE_DIGITS: c_int = 1;
 
 /// TFHE_HIP_DECRYPT_*: what `HipEngine::decrypt_batch` and `decrypt_trlwe` return per ciphertext
 pub const DECRYPT_PHASE: c_int = 0;     // b - <a, s>, wrapping u32
@@ -160,6 +169,8 @@ pub const DECRYPT_MESSAGE: c_int = 2;   // TLWELv0::decrypt_lwe_message mod `mod
 
 #[allow(non_camel_case_types)]
 type int8_t = i8;   // the header's spelling of the weights' type
+#[allow(non_camel_case_types)]
+type int32_t = i32;   // ... and of a selector's message coefficients
 
 extern "C" {   // encrypted linear layers (include/tfhe_hip.h): a plaintext int8 matrix times LWE ciphertexts or TRLWE slots;
     // no pool forms, they run on a member context (tfhe_hip_pool_ctx) of the cloud key's view
@@ -800,6 +811,52 @@ impl HipEngine {
         let ctx = unsafe { tfhe_hip_pool_ctx(self.pool, 0) };
         assert!(!ctx.is_null(), "tfhe_hip_pool_ctx failed");
         Self::check_ctx(ctx, unsafe { tfhe_hip_batch_trlwe_keyswitch(ctx, k, trlwe.as_ptr(), trlwe.len() / (2 * N), out.as_mut_ptr()) });
+        out
+    }
+
+    /// trgsw::cmux (src/trgsw.rs:173-196) over packed ciphertexts under ONE caller-held TRGSW `sel` [2t][2][N] of gadget
+    /// (basebit, t): d0 + sel (.) (d1 - d0) on [count][2][N] (flat), or with `d0` None the external product sel (.) d1
+    /// (`tfhe_hip_batch_trlwe_cmux`).  `flags`: 0, or CMUX_REFERENCE_DIGITS.  Needs no key.  Runs on the pool's first
+    /// member.
+    pub fn trlwe_cmux(&self, sel: &[u32], basebit: c_int, t: c_int, flags: c_int, d0: Option<&[u32]>, d1: &[u32]) -> Vec<u32> {
+        assert!(t >= 1 && sel.len() == 2 * (t as usize) * 2 * N, "sel is [2t][2][N]");
+        assert_eq!(d1.len() % (2 * N), 0, "d1 is [count][2][N]");
+        if let Some(a) = d0 {
+            assert_eq!(a.len(), d1.len(), "d0 has d1's shape");
+        }
+        let mut out = vec![0u32; d1.len()];
+        if d1.is_empty() {
+            return out;
+        }
+        let ctx = unsafe { tfhe_hip_pool_ctx(self.pool, 0) };
+        assert!(!ctx.is_null(), "tfhe_hip_pool_ctx failed");
+        let p0 = d0.map_or(std::ptr::null(), |a| a.as_ptr());
+        Self::check_ctx(ctx, unsafe {
+            tfhe_hip_batch_trlwe_cmux(ctx, sel.as_ptr(), basebit, t, flags, p0, d1.as_ptr(), d1.len() / (2 * N), out.as_mut_ptr())
+        });
+        out
+    }
+    /// TRGSWLv1::encrypt_torus (src/trgsw.rs:29-49) for message polynomials: `mu` [count][N] small integers -> count
+    /// selectors [count][2t][2][N] (flat) under `key_lv1` [N], made on the GPU (`tfhe_hip_batch_encrypt_trgsw`).  Row
+    /// `row` of selector m takes index first_index + m 2t + row; a (rng_key, index) pair must never encrypt twice.
+    /// `rng_key`: the 32-byte generator key, None draws it from getrandom(2).  A client-side call: it takes the secret key.
+    pub fn encrypt_trgsw(&self, key_lv1: &[u32], mu: &[i32], basebit: c_int, t: c_int, alpha: f64, rng_key: Option<&[u8; 32]>,
+                         first_index: u64) -> Vec<u32> {
+        assert_eq!(key_lv1.len(), N, "key_lv1 is [N]");
+        assert_eq!(mu.len() % N, 0, "mu is [count][N]");
+        assert!(t >= 1 && t <= 32, "1 <= t <= 32");
+        let count = mu.len() / N;
+        let mut out = vec![0u32; count * 2 * (t as usize) * 2 * N];
+        if count == 0 {
+            return out;
+        }
+        let ctx = unsafe { tfhe_hip_pool_ctx(self.pool, 0) };
+        assert!(!ctx.is_null(), "tfhe_hip_pool_ctx failed");
+        let rk = rng_key.map_or(std::ptr::null(), |key| key.as_ptr());
+        Self::check_ctx(ctx, unsafe {
+            tfhe_hip_batch_encrypt_trgsw(ctx, key_lv1.as_ptr(), mu.as_ptr(), count, basebit, t, alpha, rk, first_index,
+                                         std::ptr::null_mut(), out.as_mut_ptr())
+        });
         out
     }
 
