@@ -19,9 +19,26 @@ The steps cover gates, bootstraps, the packing and table key switches, and -- wi
 their own per step -- public-key and symmetric encryption, packed encryption and expansion, decryption, the dense and
 packed linear layers, the convolution and the polynomial product.
 
+The ring steps -- the TRLWE key switch, the packed CMUX with caller-held selectors, TRGSW encryption, the switching-key
+changes (generated under queued work, loaded, dropped and loaded; another (basebit, t) each time, and no drain but the
+library's own) and the getters of their timing pairs -- run in both shapes: every word against trlwe_switch_model and
+cmux_model (exact in integers on every parameter set, so on SECURITY_UINT4 too, beside the same call made alone), the
+chunk passes each ring_times step reports against the sequence, the switching key each view holds after the last step
+by a two-row switch under it, and chains E (encrypt_trlwe -> trlwe_keyswitch -> decrypt_trlwe) and F (encrypt_trgsw ->
+cmux -> trlwe_keyswitch -> decrypt_trlwe) against psi_k of their plaintexts within 8 sigma of the encryption, the CMUX
+and the switch.  A third directed pair holds the two views' key tables over one ts_dig: a host switch on V2 issued
+while an un-synchronised trlwe_keyswitch_dev of the same k on E still runs pass after pass through the digit scratch
+(measured: 16,384 ciphertexts last 2.31 ms alone against 0.09 ms to issue; the host call was entered 0.08 ms after it,
+found it running in all four rounds and returned 2.6 - 2.7 ms later; no wrong word).
+Narrower than the full cross product: TRGSW encryption's device form has no stream, VR runs none of this, switching
+keys keep s_from = s_to.
+
 The six sequences of a shape run on one context, seed after seed, and scratch never shrinks: the grow step of seed s
 is 1.5 x that of seed s - 1 (more than ensure()'s quarter of headroom), so each of them reallocates under in-flight
-work, not only the first.
+work, not only the first.  The ring families' digit scratch cannot rise that way: ts_dig and cm_dig are capped at 2,048
+ciphertexts of the largest t, so they are reallocated under running calls in the first two or three sequences of a
+shape only, and the ring grow and "through t alone" steps of the later sequences hold the order of
+the calls alone (sequence_fuzz.py says what that leaves uncovered).
 
 Every key of a shape is made on the GPU once (tfhe_hip_gen_cloud_key with a seed, tfhe_hip_gen_compressed_cloud_key
 with a generator key) and exported, so that each route of a key change (load, compressed load, seeded generation) has
@@ -73,6 +90,18 @@ def _world(O, name):
                 exported[t + "/comp"] = tmp.export_cloud_key()
     finally:
         tmp.close()
+    w.secrets = {"E": w.sk["K1"], "V2": w.sk["K2"], "VR": w.sk["K1"]}
+    # the switching keys (s_from = s_to = the handle's ring key), each generated once under its fixed generator key and
+    # downloaded: what each view starts with and what a switch_key_change brings, by any of its routes
+    w.switch_book = {}
+    tmp = w.eng.new_key_view()
+    try:
+        for key in SF.switch_book_names():
+            h, k = key.split(":")[:2]
+            ring = w.secrets[h].key_lv1
+            w.switch_book[key] = tmp.gen_trlwe_switch_key(ring, ring, int(k), *SF.switch_key_gadget(key), rng_key=SF.switch_gen_key(key))
+    finally:
+        tmp.close()
     w.packing = {"E": w.sk["K1"].packing_key(rng_key=7301), "V2": w.sk["K2"].packing_key(rng_key=7302)}
     w.reenc = O.gen_reenc_key(w.op, w.sk["K1"].key_lv0, 7401, key_to=w.sk["K3"].key_lv0)
     w.default_combining = w.eng.combine_stats()["max_count"]
@@ -88,9 +117,8 @@ def _world(O, name):
         public = {h: x.gen_public_key(w.secrets[h].key_lv0, size=SF.PK_SIZE, rng_key=SF.PK_GEN_KEY) for h, x in (("E", eng), ("V2", v2))}
         assert all(np.array_equal(public[h], w.public.setdefault(h, public[h])) for h in public)
         return {"E": eng, "V2": v2, "VR": vr, "book": w.book, "packing": w.packing, "combining_default": w.default_combining,
-                "secrets": w.secrets}
+                "secrets": w.secrets, "switch_book": w.switch_book}
 
-    w.secrets = {"E": w.sk["K1"], "V2": w.sk["K2"], "VR": w.sk["K1"]}
     w.public = {}
     w.handles = handles(w.eng)
     w.alone = None
@@ -101,12 +129,16 @@ def _world(O, name):
     w.be = SF.TorchBackend()
     w.streams = w.be.streams()
     w.keys = w.model = None
+    # the ring steps need no cloud key: a model of them alone where the oracle gives no words
+    w.ring_keys = {"params": p, "switch": w.switch_book, "secrets": w.secrets}
+    w.ring_model = SF.Model(None, w.ring_keys)
     if w.shape.exact:
         cloud = {k: O.CloudKey.from_arrays(w.op, c.bootstrapping_key, c.key_switching_key, c.decomposition_offset,
                                            c.blind_rotate_testvec) for k, c in exported.items()}
         w.keys = {"params": p, "oracle_params": w.op, "cloud": cloud, "reenc": w.reenc, "secrets": w.secrets, "public": w.public,
-                  "packing": {h: (pk, PK.key_rows(p, pk.mask_seed, pk.bodies)) for h, pk in w.packing.items()}}
-        w.model = SF.Model(O, w.keys)
+                  "packing": {h: (pk, PK.key_rows(p, pk.mask_seed, pk.bodies)) for h, pk in w.packing.items()},
+                  "switch": w.switch_book}
+        w.model = w.ring_model = SF.Model(O, w.keys)
     w.report, w.got, w.pools = {}, {}, {}
     _WORLDS[name] = w
     return w
@@ -123,10 +155,16 @@ def _close_worlds():
 
 
 def _reset(w, handles):
-    """Where every sequence starts: V2 under K2 (as generated), profiling off, the default combining, nothing queued."""
+    """Where every sequence starts: V2 under K2 (as generated), each view's starting switching keys, profiling off and
+    its timing pairs drained, the default combining, nothing queued."""
     handles["V2"].load_cloud_key(w.book["K2/gen"]["full"])
+    for h, held in SF.switch_keys_after([], -1).items():
+        for name in held.values():
+            handles[h].load_trlwe_switch_key(w.switch_book[name])
     handles["E"].set_profiling(False)
     handles["E"].kernel_times()
+    handles["E"].trlwe_switch_times()
+    handles["E"].cmux_times()
     handles["E"].set_combining(w.default_combining)
     handles["E"].synchronize()
     w.be.synchronize()
@@ -140,8 +178,10 @@ def _run(w, seed):
     for i, kt in info["kernel_times"]:  # tfhe_hip_get_kernel_times answered after each profiling toggle
         assert kt["blind_rotate_launches"] >= 0 and kt["key_switch_ms"] >= 0.0, (i, kt)
     assert len(info["kernel_times"]) == 2
+    SF.check_ring_times(seq, info)  # tfhe_hip_get_trlwe_switch_times / _cmux_times: the passes issued while profiling was on
     for h in SF.HANDLES:
         assert SF.flags(w.handles[h]) == SF.EXPECTED_FLAGS[h], (h, SF.flags(w.handles[h]))
+    SF.final_switch_check(seq, w.handles, pools, w.ring_model)  # the switching keys each view holds after the last step
     w.got[seed] = got
     return seq, pools, got, info
 
@@ -160,6 +200,7 @@ def test_sequences_128bit(O, seed):
     print(f"seed {seed}: {len(seq)} steps issued in {info['seconds']:.3f} s, model {oracle_s:.2f} s "
           f"({w.model.bootstraps - before} oracle bootstraps), {len(bad)} steps differ")
     assert not bad, f"seed {seed}:\n" + SF.describe(seq, bad, got, want)
+    assert SF.chains_decrypt_to_their_plaintext_products(w.shape, w.secrets, seq, got, pools, ("E", "F")) == 2
     # the key V2 holds after the last step answers a call of its own
     rows = pools["lv0:V2"][:2]
     assert np.array_equal(w.handles["V2"].batch_gate(0, rows, rows[::-1]),
@@ -179,6 +220,13 @@ def test_sequences_uint4(O, seed):
     print(f"seed {seed}: {len(seq)} steps issued in {info['seconds']:.3f} s, the same calls alone {alone_s:.2f} s, "
           f"{len(bad)} steps differ")
     assert not bad, f"seed {seed}:\n" + SF.describe(seq, bad, got, alone)
+    # the ring steps (exact in integers on every set), TRGSW encryption and chains E and F: the numpy model, word for word
+    t0 = time.perf_counter()
+    only = {st.i for st in seq if st.ring or st.op == "encrypt_trgsw" or st.args.get("chain") in ("E", "F")}
+    want = SF.expected(seq, None, w.ring_keys, pools, w.ring_model, only=only)
+    bad = [i for i in sorted(want) if got[i].shape != want[i].shape or not np.array_equal(got[i], want[i])]
+    print(f"seed {seed}: {len(want)} ring steps against the numpy model in {time.perf_counter() - t0:.2f} s, {len(bad)} differ")
+    assert sorted(want) == sorted(only) and not bad, f"seed {seed}:\n" + SF.describe(seq, bad, got, want)
     # gate-type outputs on genuine encryptions decrypt to the plaintext model's value (no device in this check)
     key, checked = "K2/gen", 0
     for st in seq:
@@ -189,65 +237,8 @@ def test_sequences_uint4(O, seed):
             continue
         assert np.array_equal(w.secrets[st.handle].decrypt_bool(got[st.i]), bits), st
         checked += 1
-    checked += _chains_decrypt_to_their_plaintext_products(w, seq, got)
-    assert checked >= 5
-
-
-def _signed(words):
-    """torus differences as signed LSB"""
-    return (np.asarray(words, np.int64) + (1 << 31)) % (1 << 32) - (1 << 31)
-
-
-def _negacyclic(poly):
-    """T [N][N] int64 with (poly(X) * x(X) mod X^N + 1)[i] = sum_k T[i][k] x[k]"""
-    i, k = np.arange(N)[:, None], np.arange(N)[None, :]
-    return np.where(k > i, -1, 1) * np.asarray(poly, np.int64)[(i - k) % N]
-
-
-def _chains_decrypt_to_their_plaintext_products(w, seq, got):
-    """No device and no library in the reference: the phases chain C and chain D end in -- as decrypt_dev returned them
-    and as SecretKey.phase / phase_lv1 reads them on the CPU off the chain's last ciphertexts -- are W plain + bias (C),
-    or the matrix times the slots of the polynomial product of the plaintexts (D), mod 2^32.  Allowed error: 8 sigma of
-    the sum of the independent Gaussians the fresh encryptions carry, sigma = alpha 2^32 sqrt(sum of the squared weights
-    each noise sample reaches the output row with), derived per row below; a failure chance below 1e-12 over the
-    corpus.  Returns the chains checked."""
-    done = 0
-    for which, n_links in (("C", 3), ("D", 4)):
-        links = [st for st in seq if st.kind == "call" and st.args.get("chain") == which]
-        assert len(links) == n_links, (which, links)
-        sk, enc, mm, dec = w.secrets[links[0].handle], links[0], links[-2], links[-1]
-        rows, cols, groups = mm.args["shape"]
-        W, bias = mm.ins[0][1].astype(np.int64), mm.ins[2][1].astype(np.int64)
-        if which == "C":
-            x = enc.ins[0][1][:groups * cols].astype(np.int64).reshape(groups, cols)  # the plaintexts the matrix takes
-            want = x @ W.T + bias[None, :]
-            sumsq = np.broadcast_to((W ** 2).sum(axis=1).astype(np.float64), (groups, rows))
-            alpha, cpu = w.shape.alpha_lv0, sk.phase(got[mm.i])
-        else:
-            poly = links[1]
-            p_rows, p_cols, p_groups = poly.args["shape"]
-            slots = np.zeros(p_groups * p_cols * N, np.int64)
-            slots[:enc.args["words"]] = enc.ins[0][1]
-            slots = slots.reshape(p_groups, p_cols, N)
-            wp, bp = poly.ins[0][1], poly.ins[2][1].astype(np.int64)
-            T = [[_negacyclic(wp[r, c]) for c in range(p_cols)] for r in range(p_rows)]
-            Wpad = np.zeros((rows, N), np.int64)
-            Wpad[:, :cols] = W
-            want = np.empty((groups, rows), np.int64)
-            sumsq = np.empty((groups, rows), np.float64)
-            for g in range(p_groups):
-                for r in range(p_rows):
-                    pt = (sum(T[r][c] @ slots[g, c] for c in range(p_cols)) + bp[r]) % (1 << 32)  # slots of the product
-                    want[g * p_rows + r] = Wpad @ pt + bias
-                    # noise sample k of input polynomial c reaches output row q with weight (Wpad @ T[r][c])[q][k]
-                    sumsq[g * p_rows + r] = sum(((Wpad @ T[r][c]).astype(np.float64) ** 2).sum(axis=1) for c in range(p_cols))
-            alpha, cpu = w.shape.alpha_lv1, sk.phase_lv1(got[mm.i])
-        bound = 8.0 * alpha * 4294967296.0 * np.sqrt(sumsq)
-        for name, ph in (("decrypt_dev", got[dec.i]), ("SecretKey on the CPU", cpu)):
-            err = np.abs(_signed(ph.reshape(groups, rows).astype(np.int64) - want))
-            assert (err <= bound).all(), f"chain {which} ({name}): {int(err.max())} LSB off, {float(bound.min()):.1f} allowed; {dec}"
-        done += 1
-    return done
+    checked += SF.chains_decrypt_to_their_plaintext_products(w.shape, w.secrets, seq, got, pools)
+    assert checked >= 7
 
 
 def test_comparison_sees_one_wrong_step(O):
@@ -260,6 +251,11 @@ def test_comparison_sees_one_wrong_step(O):
         _run(w, seed)
     head = next(st.i for st in seq if st.kind == "call" and st.op == "gate" and len(SF.cone(seq, st.i)) == 3)
     assert 0 < head < len(seq) - 1
+    wrong = SF.expected(seq, O, w.keys, w.pools[seed], w.model, perturb=head)
+    assert SF.compare(w.got[seed], wrong) == sorted(SF.cone(seq, head))
+    # and the head of chain E (encrypt_trlwe -> trlwe_keyswitch -> decrypt_trlwe)
+    head = next(st.i for st in seq if st.kind == "call" and st.op == "encrypt_trlwe" and st.args.get("chain") == "E")
+    assert len(SF.cone(seq, head)) == 3
     wrong = SF.expected(seq, O, w.keys, w.pools[seed], w.model, perturb=head)
     assert SF.compare(w.got[seed], wrong) == sorted(SF.cone(seq, head))
 
@@ -419,6 +415,97 @@ def test_host_decrypt_after_an_unsynchronised_encrypt_trlwe(O):
     assert [(u, v) for *_, u, v in rounds] == [(0, 0)] * 4, _DIRECTED["line2"]
 
 
+PAIR_SWITCH_START, PAIR_SWITCH_CAP = 16384, 65536  # ciphertexts of the third directed pair's first call
+
+
+def test_host_switch_after_an_unsynchronised_trlwe_keyswitch_dev(O):
+    """trlwe_keyswitch_dev (k = 1) of many ciphertexts on a side stream under E's (4, 6) key (pass after pass of 2,048
+    through the context's ts_dig), then AT ONCE a host batch_trlwe_keyswitch of 65 ciphertexts under the same k on the key
+    view V2 -- V2's own table, its (2, 16) key, and the start of the same ts_dig -- then both results against the same
+    two calls made alone.  Four rounds, each with its own data.
+
+    As in the pairs above, the first call alone is timed once with events, and every round asserts that it had not
+    finished when the host call was entered.  Its size is the smallest power of two from 16,384 ciphertexts for which
+    the call alone lasts at least ten times the time it takes to issue it, capped at 65,536 (512 MiB in, 512 MiB out).
+    Measured on an MI355X: the first size tried, 16,384 ciphertexts (128 MiB in, 128 MiB out, eight passes), lasts
+    2.31 ms alone against 0.09 ms to issue, so no larger one was needed.  In the rounds the host switch on V2 was entered
+    0.08 ms after the first call, which was still running all four times, and returned 2.6 - 2.7 ms later, after it had
+    finished: the claim on the context's scratch makes the host call wait for the side stream; without one its digits
+    pass would write V2's 65 x 16 digit rows under the running contraction.  0 wrong words in both results."""
+    import torch
+
+    w = _world(O, "SECURITY_UINT4")
+    e, v2 = w.handles["E"], w.handles["V2"]
+    _reset(w, w.handles)
+    assert SF.SWITCH_START["E"][1] == (4, 6) and SF.SWITCH_START["V2"][1] == (2, 16)
+    side = torch.cuda.Stream(device=0)
+    gen = torch.Generator(device="cuda:0")
+    gen.manual_seed(7700)
+    rng = np.random.default_rng(7700)
+
+    def fresh(count):
+        return torch.randint(-(1 << 31), (1 << 31) - 1, (count, 2, N), dtype=torch.int32, device="cuda:0", generator=gen)
+
+    count, tried = PAIR_SWITCH_START, []
+    while True:
+        cts = fresh(count)
+        ref = torch.empty_like(cts)
+        e.batch_trlwe_keyswitch(1, cts, out=ref, stream=side)  # (grows ts_dig and warms the kernels)
+        torch.cuda.synchronize()
+        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        a.record(side)
+        t0 = time.perf_counter()
+        e.batch_trlwe_keyswitch(1, cts, out=ref, stream=side)
+        issue_alone_ms = (time.perf_counter() - t0) * 1e3
+        b.record(side)
+        torch.cuda.synchronize()
+        first_ms = a.elapsed_time(b)
+        tried.append((count, first_ms, issue_alone_ms))
+        if first_ms >= 10.0 * issue_alone_ms or count >= PAIR_SWITCH_CAP:
+            break
+        del cts, ref
+        count *= 2
+    out = torch.empty_like(ref)
+    rounds = []
+    for r in range(4):
+        cts = fresh(count)
+        small = SF.words(rng, (65, 2, N))
+        # alone
+        e.batch_trlwe_keyswitch(1, cts, out=ref, stream=side)
+        torch.cuda.synchronize()
+        want_small = v2.batch_trlwe_keyswitch(1, small)
+        v2.synchronize()
+        out.fill_(SF.FILL)
+        torch.cuda.synchronize()
+        # the pair
+        done = torch.cuda.Event()
+        t0 = time.perf_counter()
+        e.batch_trlwe_keyswitch(1, cts, out=out, stream=side)
+        done.record(side)
+        running_at_issue = not done.query()
+        t1 = time.perf_counter()
+        got_small = v2.batch_trlwe_keyswitch(1, small)
+        running_at_return = not done.query()
+        t2 = time.perf_counter()
+        torch.cuda.synchronize()
+        wrong_first = int((out != ref).sum().item())
+        wrong_second = int((got_small != want_small).sum())
+        rounds.append((running_at_issue, running_at_return, (t1 - t0) * 1e3, (t2 - t1) * 1e3, wrong_first, wrong_second))
+    # (the two views' keys differ: the same small call on E gives other words)
+    assert not np.array_equal(e.batch_trlwe_keyswitch(1, small), want_small)
+    _DIRECTED["line3"] = (f"directed pair: trlwe_keyswitch_dev({count}) alone {first_ms:.2f} ms, {issue_alone_ms:.3f} ms to issue (sizes "
+                          f"tried: " + ", ".join(f"{c}: {x:.2f} / {y:.3f}" for c, x, y in tried) + "); per round (first still running "
+                          f"when issued / when the host switch on V2 returned, ms to issue, ms in the host call, wrong words of "
+                          f"the first / second result): "
+                          + "; ".join(f"{a}/{b} {x:.2f} {y:.2f} {u}/{v}" for a, b, x, y, u, v in rounds))
+    print(_DIRECTED["line3"])
+    for r, (at_issue, _, issue_ms, _, _, _) in enumerate(rounds):
+        assert at_issue and issue_ms < first_ms, \
+            f"round {r}: the first call ({first_ms:.2f} ms alone) had finished before the host call was issued " \
+            f"({issue_ms:.2f} ms after it): the pair did not overlap on this machine and shows nothing"
+    assert [(u, v) for *_, u, v in rounds] == [(0, 0)] * 4, _DIRECTED["line3"]
+
+
 @pytest.mark.parametrize("name", sorted(SF.SHAPES))
 def test_report(O, name):
     """What the shape's sequences reached (shown by pytest -rA)."""
@@ -435,7 +522,7 @@ def test_report(O, name):
     print("  seconds per sequence (issue to the last synchronisation): " + ", ".join(f"{r[2]:.3f}" for r in rep))
     print(f"  seconds per sequence ({'model' if w.shape.exact else 'the same calls alone'}): " + ", ".join(f"{r[3]:.2f}" for r in rep))
     if name == "SECURITY_UINT4":
-        for key in ("line", "line2"):
+        for key in ("line", "line2", "line3"):
             if key in _DIRECTED:
                 print("  " + _DIRECTED[key])
     assert sum(r[0] for r in rep) >= 6 * SF.STEPS
