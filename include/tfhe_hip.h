@@ -35,6 +35,17 @@
  * drains the previous stream (hipStreamSynchronize), so mixing streams on one
  * context is safe but serialising; use one context per stream for overlap.
  *
+ * Alignment of device pointers.  A 32-bit operand of a _dev call (and a pinned host
+ * operand, which the kernels read and write in place) needs 4-byte alignment and no
+ * more, an int8 or uint8 operand (weights, gate codes) none: a pointer into the middle
+ * of a larger buffer -- row 5 of a batch whose rows are 701 words -- gives the same
+ * words as a fresh allocation, and the call writes the words of its output and no
+ * other: nothing before its first word, nothing behind its last.  Where a call needs
+ * more it says so at the call and refuses a pointer that has less with
+ * TFHE_HIP_EINVAL before anything is launched: d0 / d1 / out of
+ * tfhe_hip_batch_trlwe_cmux_dev, bodies / out of tfhe_hip_batch_encrypt_trlwe_dev and
+ * of tfhe_hip_expand_seeded_trlwe_dev (16 bytes each).
+ *
  * Thread safety: a context may be used from several host threads (the
  * reference's `Bootstrap: Send + Sync`, src/bootstrap/mod.rs:23).  Concurrent SMALL
  * host-pointer calls (tfhe_hip_batch_gate / _gates_mixed[_nks] / _bootstrap /
@@ -569,7 +580,8 @@ int tfhe_hip_get_trlwe_switch_times(tfhe_hip_ctx *ctx, tfhe_hip_trlwe_switch_tim
  *   unknown flag bit, count > 2^31 - 1 (encryption: count 2t > 2^31 - 1, key_lv1 NULL or not binary, mu or out NULL,
  *   alpha negative or NaN, row indices past 2^64).  out must not overlap sel, d0 or d1; this is not checked.  Bulk
  *   calls: the context's mutex and the one staging path of the host-pointer form, never the combining front end.
- *   _dev: device pointers, d0 / d1 / out 16-byte aligned, queued on `stream` (NULL: the context's stream); the digits
+ *   _dev: device pointers, d0 / d1 / out 16-byte aligned (TFHE_HIP_EINVAL, nothing launched, for one that is not; sel
+ *   needs 4 bytes like any operand), queued on `stream` (NULL: the context's stream); the digits
  *   pass through a scratch of the context, 2,048 ciphertexts (2,048 2t N bytes) a pass.  The encryption's _dev form
  *   takes mu and out on the device, runs on the context's stream and has finished when it returns (the staged secrets
  *   are wiped behind it); key_lv1 and rng_key (NULL: getrandom(2)) are host pointers in both forms, mask_seed_out may

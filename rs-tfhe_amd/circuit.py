@@ -259,24 +259,45 @@ class Circuit:
 
         n_in, B, w = inputs.shape
         assert n_in == self.n_inputs
-        h = self._native_handle()
-        lib = _capi.lib()
         inputs = inputs.contiguous()
         # allocations and kernels on ONE stream (the caching allocator hands a block back to that stream's later work)
         with _on_stream(stream):
             store = torch.empty((self.slots, B, w), dtype=torch.int32, device=inputs.device)
             out = torch.empty((self.n_wires, B, w), dtype=torch.int32, device=inputs.device)
-            ow, n_out = self._all_wires.ctypes.data_as(C.c_void_p), self.n_wires
-            home = eng.home
-            sp = eng._stream_ptr(home, stream)
-            ti, ts, to = eng._tp(home, inputs), eng._tp(home, store), eng._tp(home, out)
-            if isinstance(eng, E.Pool):
-                run, gather, lead = lib.tfhe_hip_circuit_run_pool_dev, lib.tfhe_hip_circuit_gather_pool_dev, (eng._h, home)
-            else:
-                run, gather, lead = lib.tfhe_hip_circuit_run_dev, lib.tfhe_hip_circuit_gather_dev, (eng._ctx,)
-            eng._chk(run(*lead, h, ti, ts, B, sp))
-            eng._chk(gather(*lead, h, ts, B, ow, n_out, to, sp))
+            self.run_store_dev(eng, inputs, store, stream)
+            self.gather_dev(eng, store, out, stream=stream)
         return out
+
+    def _dev_entry(self, eng, name: str):
+        """(C function, leading arguments) of a circuit `_dev` call on an Engine or a Pool"""
+        lib = _capi.lib()
+        if isinstance(eng, E.Pool):
+            return getattr(lib, f"tfhe_hip_circuit_{name}_pool_dev"), (eng._h, eng.home)
+        return getattr(lib, f"tfhe_hip_circuit_{name}_dev"), (eng._ctx,)
+
+    def run_store_dev(self, eng, inputs, store, stream=None) -> None:
+        """`tfhe_hip_circuit_run_dev` alone: inputs [n_inputs][B][n+1] into the caller's store [slots][B][n+1] (32-bit
+        CUDA tensors on the call's GPU), every level enqueued on `stream`.  Slot s of the store holds the wire with
+        wire_slot(w) == s; materialised linear nodes and the mux's first level take the remaining slots."""
+        B = inputs.shape[1]
+        if tuple(inputs.shape) != (self.n_inputs, B, eng.params.n + 1) or tuple(store.shape) != (self.slots, B, eng.params.n + 1):
+            raise ValueError("inputs must be [n_inputs][B][n+1] and store [slots][B][n+1]")
+        fn, lead = self._dev_entry(eng, "run")
+        home = eng.home
+        eng._chk(fn(*lead, self._native_handle(), eng._tp(home, inputs), eng._tp(home, store), B, eng._stream_ptr(home, stream)))
+
+    def gather_dev(self, eng, store, out, wires=None, stream=None) -> None:
+        """`tfhe_hip_circuit_gather_dev` alone: the wires `wires` (every wire by default) of a store [slots][B][n+1]
+        that run_store_dev filled, into out [len(wires)][B][n+1]; linear nodes are formed from the store here."""
+        h = self._native_handle()
+        ow = self._all_wires if wires is None else np.ascontiguousarray(wires, dtype=np.uint32).reshape(-1)
+        B = store.shape[1]
+        if tuple(store.shape) != (self.slots, B, eng.params.n + 1) or tuple(out.shape) != (len(ow), B, eng.params.n + 1):
+            raise ValueError("store must be [slots][B][n+1] and out [len(wires)][B][n+1]")
+        fn, lead = self._dev_entry(eng, "gather")
+        home = eng.home
+        eng._chk(fn(*lead, h, eng._tp(home, store), B, ow.ctypes.data_as(C.c_void_p), len(ow), eng._tp(home, out),
+                    eng._stream_ptr(home, stream)))
 
     def _run_dev_torch(self, eng, inputs, stream=None):
         """The torch-scheduled path this module had before the native scheduler (gate-only circuits): per level two

@@ -40,8 +40,12 @@ __global__ __launch_bounds__(WG) void k_table_window(uint32_t *__restrict__ out,
   __shared__ uint32_t part[WG];
   uint32_t *q = out + (size_t)blockIdx.x * kN;
   const int tid = threadIdx.x;
-  const uint4 v = reinterpret_cast<const uint4 *>(q)[tid];
-  const uint32_t p0 = v.x, p1 = p0 + v.y, p2 = p1 + v.z, p3 = p2 + v.w;
+  // out is the caller's: word by word (a wave reads 256 consecutive bytes), through S to the lane that sums words
+  // 4 tid .. 4 tid + 3 -- no 16-byte access whose alignment would be taken from the index
+#pragma unroll
+  for (int e = 0; e < 4; ++e) S[tid + WG * e] = q[tid + WG * e];
+  __syncthreads();
+  const uint32_t p0 = S[4 * tid], p1 = p0 + S[4 * tid + 1], p2 = p1 + S[4 * tid + 2], p3 = p2 + S[4 * tid + 3];
   part[tid] = p3;
   __syncthreads();
   for (int d = 1; d < WG; d <<= 1) {  // inclusive scan of the lanes' sums
@@ -58,15 +62,15 @@ __global__ __launch_bounds__(WG) void k_table_window(uint32_t *__restrict__ out,
   __syncthreads();
   const int W = kN >> lm, off = W >> 1;
   const uint32_t total = S[kN - 1];
-  uint32_t r[4];
 #pragma unroll
-  for (int e = 0; e < 4; ++e) {
-    const int hi = 4 * tid + e + off, lo = hi - W;
-    if (lo < 0) r[e] = S[hi] - (total - S[lo + kN]);
-    else if (hi >= kN) r[e] = total - S[lo] - S[hi - kN];
-    else r[e] = S[hi] - S[lo];
+  for (int e = 0; e < 4; ++e) {  // coefficient y = tid + WG e: consecutive lanes store consecutive words
+    const int y = tid + WG * e, hi = y + off, lo = hi - W;
+    uint32_t r;
+    if (lo < 0) r = S[hi] - (total - S[lo + kN]);
+    else if (hi >= kN) r = total - S[lo] - S[hi - kN];
+    else r = S[hi] - S[lo];
+    q[y] = r;
   }
-  reinterpret_cast<uint4 *>(q)[tid] = make_uint4(r[0], r[1], r[2], r[3]);
 }
 
 }  // namespace tfhe

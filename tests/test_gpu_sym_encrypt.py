@@ -17,6 +17,7 @@ import subprocess
 import numpy as np
 import pytest
 
+import dev_buffers as DB
 import keygen_model as KM
 import sym_encrypt_model as SM
 from test_sym_encrypt_host import build_cpp_sym_encrypt
@@ -123,7 +124,7 @@ def test_rows_land_at_any_word_of_a_chunk(shape, offset):
 
     p = KM.shape_params(shape)
     sk = KM.secret_key(p)
-    count, pad, width, sentinel = 17, 8, p.n + 1, 0x5A5AA5A5
+    count, width = 17, p.n + 1
     plain = SM.plaintexts(count, p.n + offset)
     want, border = SM.bulk(sk.key_lv0, plain, SM.HIGH, 0.0)
     assert not border.any()
@@ -132,12 +133,11 @@ def test_rows_land_at_any_word_of_a_chunk(shape, offset):
     eng = R.Engine(p, 0)
     try:
         def through_view(call):
-            big = torch.full((pad + count * width + pad,), sentinel, dtype=torch.int32, device="cuda")
-            assert big.data_ptr() % 16 == 0
-            view = big[offset:offset + count * width].view(count, width)
+            big, view = DB.frame(want, offset, fill="sentinel")  # (the rows' shape; every word the sentinel)
+            assert big.data_ptr() % 16 == 0 and DB.span(big, view) == (DB.PAD + offset, count * width)
             call(view)
             torch.cuda.synchronize()
-            return big.cpu().numpy().view(np.uint32)
+            return big
 
         tb = torch.from_numpy(sc.bodies.view(np.int32)).cuda()
         tp = torch.from_numpy(np.ascontiguousarray(plain, np.uint32).view(np.int32)).cuda()
@@ -147,12 +147,15 @@ def test_rows_land_at_any_word_of_a_chunk(shape, offset):
         }
     finally:
         eng.close()
-    for name, g in got.items():
-        rows = g[offset:offset + count * width].reshape(count, width)
+    for name, big in got.items():
+        span = (DB.PAD + offset, count * width)
+        rows = DB.view_words(big, span).reshape(count, width)
         _say(case="alignment", call=name, n=p.n, offset=offset, differing=int((rows != want).sum()))
         assert np.array_equal(rows, want), name
-        outside = np.concatenate([g[:offset], g[offset + count * width:]])
-        assert len(outside) == 2 * pad and (outside == sentinel).all(), f"{name} wrote outside its rows"
+        g = DB.host_words(big).view(np.uint32)
+        outside = np.concatenate([g[:span[0]], g[span[0] + span[1]:]])
+        assert len(outside) == 2 * DB.PAD + offset and (outside == DB.SENTINEL).all(), f"{name} wrote outside its rows"
+        assert DB.check_frame(big, span, "sentinel", name) == ""
 
 
 def test_bulk_refusals():
