@@ -83,12 +83,13 @@ __global__ __launch_bounds__(64) void k_cmux_digits(const uint32_t *__restrict__
       v[0] = v[2], v[1] = v[3], v[2] = x, v[3] = y;
     }
     // (w + off g + rnd) >> (32 - bt): its plain base-B digits are the u_i (off has no bits below 2^(32 - bt))
+    const uint32_t rnd_c = TFHE_MUT(kMut_cmux_rnd_b) ? (c == 1 ? 0u : rnd) : rnd;  // (the b half truncates)
     uint32_t ap[16];
 #pragma unroll
     for (int q = 0; q < 4; ++q) {
       const uint32_t w[4] = {v[q].x, v[q].y, v[q].z, v[q].w};
 #pragma unroll
-      for (int e = 0; e < 4; ++e) ap[4 * q + e] = (((w[e] + rnd) >> (32 - bt)) + off) & btmask;
+      for (int e = 0; e < 4; ++e) ap[4 * q + e] = (((w[e] + rnd_c) >> (32 - bt)) + off) & btmask;
     }
     uint4 *dst = reinterpret_cast<uint4 *>(dig + (ct * 2 + (size_t)c) * (size_t)t * kN) + lane;
 #pragma unroll 1
@@ -113,7 +114,7 @@ __global__ __launch_bounds__(kCmuxAddendThreads) void k_cmux_addend(const uint4 
   if (i >= quads) return;
   const uint4 a = d0[i];
   uint4 v = out[i];
-  v.x += a.x, v.y += a.y, v.z += a.z, v.w += a.w;
+  v.x += a.x, v.y += a.y, v.z += a.z, v.w += TFHE_MUT(kMut_cmux_addend_w) ? 0u : a.w;
   out[i] = v;
 }
 
@@ -128,7 +129,7 @@ __global__ __launch_bounds__(64) void k_encrypt_trgsw(const double2 *__restrict_
   const size_t r = blockIdx.x;
   const int row = (int)(r % (size_t)(2 * t));
   const uint64_t g = first_index + (uint64_t)r;
-  const uint32_t g_lo = (uint32_t)g, g_hi = (uint32_t)(g >> 32);
+  const uint32_t g_lo = (uint32_t)g, g_hi = TFHE_MUT(kMut_trgsw_index_hi) ? 0u : (uint32_t)(g >> 32);
   Twiddles tw;
   tw.load(twt, reinterpret_cast<double2 *>(smem + kTileBytes), lane);
   uint32_t *dst_a = out + r * (size_t)(2 * kN);
@@ -140,7 +141,7 @@ __global__ __launch_bounds__(64) void k_encrypt_trgsw(const double2 *__restrict_
   // the gadget polynomial g_i mu(X), after the body is formed, wrapping: on the a half for rows below t, else on b
   const uint32_t gd = 1u << (32 - (row % t + 1) * basebit);
   const int32_t *mp = mu + (r / (size_t)(2 * t)) * (size_t)kN;
-  const bool on_a = row < t;  // (wave-uniform)
+  const bool on_a = TFHE_MUT(kMut_trgsw_row_t) ? row <= t : row < t;  // (wave-uniform)
 #pragma unroll
   for (int m = 0; m < 8; ++m) {
     const uint32_t lo = gd * (uint32_t)mp[lane + 64 * m], hi = gd * (uint32_t)mp[lane + 64 * m + kN2];

@@ -52,7 +52,7 @@ __global__ __launch_bounds__(64 * kDecWaves) void k_lwe_phase(const uint32_t *__
     uint32_t acc = 0, bits = kb;
 #pragma unroll 4
     for (int x0 = 0; x0 < full; x0 += 64, bits >>= 1) acc += p[x0 + lane] & (0u - (bits & 1u));
-    if (full + lane < n) acc += p[full + lane] & (0u - (bits & 1u));
+    if (full + lane < n) acc += p[full + lane] & (0u - ((TFHE_MUT(kMut_dec_tail_bit) ? kb : bits) & 1u));
     for (int off = 32; off > 0; off >>= 1) acc += __shfl_down(acc, off);
     if (lane == 0) out[row] = decrypt_decode(p[n] - acc, mode, modulus);
   }
@@ -69,7 +69,7 @@ __global__ __launch_bounds__(256) void k_trlwe_phase(const uint32_t *__restrict_
   const int set = (int)idx[0];
   for (int x = tid; x < kN; x += 256) {
     const uint32_t w = a[x];
-    s_ext[x] = 0u - w;
+    s_ext[x] = TFHE_MUT(kMut_dec_wrap) ? ~w : 0u - w;
     s_ext[kN + x] = w;
     if (x < set) s_idx[x] = (uint16_t)idx[1 + x];
   }

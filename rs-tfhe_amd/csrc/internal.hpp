@@ -42,6 +42,7 @@
 #include <vector>
 
 #include "../../include/tfhe_hip.h"
+#include "experiment.hpp"
 
 // The core's kernel headers hold, beside the kernels, the device functions, types and constants the feature kernels
 // are built from (ChaChaKey, LweRowJob, natural_mask, row_noise, add_ring_product, the FFT passes, the matrix-core
@@ -486,5 +487,15 @@ int polymul_dev(tfhe_hip_ctx *ctx, const int8_t *w, const uint32_t *bias, size_t
 // planes.hip (table.hpp): why a tree bootstrap is TFHE_HIP_EINVAL, or nullptr (the pool form files it under the pool)
 const char *bivariate_refusal(const uint32_t *x, const uint32_t *y, const uint32_t *testvecs, int m, int n_luts,
                               const uint32_t *out, size_t count);
+
+#if TFHE_ABL_CATALOG
+// The catalogue build alone (experiment.hpp): every unit's device code reads the selected defect from a word of its
+// own, and tfhe_hip_ctx_create writes all three once, on the context's device, through the unit's own function.
+hipError_t mutant_publish_core(unsigned id);    // tfhe_hip.hip
+hipError_t mutant_publish_planes(unsigned id);  // planes.hip
+hipError_t mutant_publish_rings(unsigned id);   // rings.hip
+#define TFHE_MUTANT_PUBLISH(unit) \
+  hipError_t mutant_publish_##unit(unsigned id) { return hipMemcpyToSymbol(HIP_SYMBOL(g_tfhe_mutant), &id, sizeof(id)); }
+#endif
 
 #pragma GCC visibility pop

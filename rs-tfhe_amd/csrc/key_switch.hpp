@@ -20,6 +20,8 @@
 
 #include <type_traits>
 
+#include "experiment.hpp"
+
 namespace tfhe {
 
 __host__ __device__ __forceinline__ int ksk_row_words(int n) { return (n + 1 + 3) & ~3; }
@@ -291,7 +293,8 @@ __global__ __launch_bounds__(320) void k_key_switch_split(const uint32_t *__rest
   const uint32_t lane_off = (tid < rw4 ? (uint32_t)tid : 0u) * 16u;
   const __amdgpu_buffer_rsrc_t rsrc =
       __builtin_amdgcn_make_buffer_rsrc((void *)ksk, 0, (int)ksk_bytes, 0x00020000);
-  const uint32_t prec_offset = 1u << (32 - (1 + basebit * t));
+  const uint32_t prec_full = 1u << (32 - (1 + basebit * t));
+  const uint32_t prec_offset = TFHE_MUT(kMut_ks_round_split) ? prec_full >> 1 : prec_full;  // (a digit stays below `base` either way)
   const uint32_t base = 1u << basebit, mask = base - 1u;
   const uint32_t row_bytes = (uint32_t)rw4 * 16u;
   u32x4 acc = u32x4{0u, 0u, 0u, 0u};
@@ -413,7 +416,8 @@ __global__ __launch_bounds__(256) void k_ks_digits(const uint32_t *__restrict__ 
   const int g0 = q0 * 4, g1 = g0 + QB * 4;  // groups [g0, g1)
   const int i_lo = g0 / t, i_hi = (g1 - 1) / t;  // coefficients needed
   const int nw = i_hi - i_lo + 1;
-  const uint32_t prec_offset = 1u << (32 - (1 + basebit * t));
+  const uint32_t prec_full = 1u << (32 - (1 + basebit * t));
+  const uint32_t prec_offset = TFHE_MUT(kMut_ks_round_digits) ? prec_full >> 1 : prec_full;  // (a digit stays below `base` either way)
   for (int idx = threadIdx.x; idx < CB * nw; idx += 256) {
     const int r = idx / nw, w = idx % nw;
     const size_t ct = ct0 + r;

@@ -38,6 +38,8 @@
 
 #include <type_traits>
 
+#include "experiment.hpp"
+
 namespace tfhe {
 
 constexpr int kKmWaves = 4;              // waves per workgroup (two workgroups per CU: 2 waves per SIMD)
@@ -75,13 +77,14 @@ constexpr size_t kKmKeyTailPad = 64 * 1024;  // the DMA lead runs kKmAhead steps
 
 // Balanced signed byte p of w: w = sum_p s_p 256^p (mod 2^32), s_p in [-128, 127].
 __host__ __device__ __forceinline__ uint32_t ks_plane_byte(uint32_t w, int p) {
+  [[maybe_unused]] const uint32_t w0 = w;
   uint32_t s = 0;
   for (int q = 0; q <= p; ++q) {
     s = w & 0xFFu;
     const uint32_t sext = (s & 0x80u) ? (s | 0xFFFFFF00u) : s;
     w = (w - sext) >> 8;
   }
-  return s;
+  return TFHE_MUT(kMut_ks_plane_borrow) ? (w0 >> (8 * p)) & 0xFFu : s;  // (the plain byte: no borrow from the planes below)
 }
 
 // The 16 bytes of a lane's key fragment: byte e of dword q = plane byte p of word(q, e).  The three plane builders

@@ -74,7 +74,11 @@ constexpr unsigned kMmXcds = 8;      // accelerator dies a launch's workgroups a
 
 // The four balanced plane bytes of w, byte p = ks_plane_byte(w, p): with u = w + 0x80808080 (the carries of the
 // balanced digits are the carries of this addition) s_p = byte_p(u) - 128, as a signed byte byte_p(u) ^ 0x80.
-__host__ __device__ __forceinline__ uint32_t mm_planes(uint32_t w) { return (w + 0x80808080u) ^ 0x80808080u; }
+__host__ __device__ __forceinline__ uint32_t mm_planes(uint32_t w) {
+  return TFHE_MUT(kMut_mm_plane_carry)  // the two halves added apart: nothing carries out of plane 1 into plane 2
+             ? ((((w & 0xFFFFu) + 0x8080u) & 0xFFFFu) | ((w & 0xFFFF0000u) + 0x80800000u)) ^ 0x80808080u
+             : (w + 0x80808080u) ^ 0x80808080u;
+}
 
 // 4 x 4 byte transpose: x[q] = packed planes of word q -> y[p] = plane p of words 0..3 (word q in byte q).  v_perm_b32
 // picks result byte i by selector byte i: 0-3 from the second operand, 4-7 from the first.
@@ -134,7 +138,7 @@ struct MmToeplitz {
     for (int t = tid; t < kN; t += 64 * kMmWaves) {
       const uint32_t v = a[t];
       ext[kN + t] = mm_planes(v);   // ext[t] = a[t]
-      ext[t] = mm_planes(0u - v);   // ext[t - N] = 0 - a[t]   (index 0, t = -N, is never read)
+      ext[t] = mm_planes(TFHE_MUT(kMut_mm_toeplitz_wrap) ? ~v : 0u - v);   // ext[t - N] = 0 - a[t]   (index 0, t = -N, is never read)
       ext[2 * kN + t] = mm_planes(b[t]);
     }
     __syncthreads();
@@ -184,7 +188,8 @@ struct MmConv {
     const uint32_t v = (uint32_t)vg, t = v / out_w, ox = v - t * out_w, g = t / out_h, oy = t - g * out_h;
     in += (size_t)g * img_words;
     iy0 = (int)(oy * stride_h) - (int)pad_h;
-    ix0 = (int)(ox * stride_w) - (int)pad_w;
+    // (the mutant's column is another tap of the same map: the ix < in_w guards below stand)
+    ix0 = (int)(ox * (TFHE_MUT(kMut_mm_conv_stride) ? stride_h : stride_w)) - (int)pad_w;
   }
   __device__ __forceinline__ void fetch16(uint32_t (&raw)[16], const unsigned char *, size_t, size_t cols, int ncol,
                                           size_t kb, int col) const {
@@ -217,7 +222,7 @@ struct MmConv {
       for (int j = 0; j < 16; ++j) {
         const bool ok = inside && k + (uint32_t)j < K;
         const uint32_t v = in[(ok ? off : (size_t)0) + c];
-        raw[j] = ok ? v : 0u;
+        raw[j] = TFHE_MUT(kMut_mm_conv_pad) ? (ok || k + (uint32_t)j < K ? v : 0u) : (ok ? v : 0u);  // (a padding tap keeps its stand-in word)
         off += (size_t)ncol;
         if (++ic == in_c) {
           ic = 0u;
@@ -255,7 +260,7 @@ struct MmNegacyclic {
 #pragma unroll
     for (int e = 0; e < 16; ++e, --t) {
       const uint32_t v = p[t & (uint32_t)(kN - 1)];
-      raw[e] = (int32_t)t < 0 ? 0u - v : v;
+      raw[e] = (int32_t)t < 0 ? (TFHE_MUT(kMut_mm_nega_wrap) ? ~v : 0u - v) : v;
     }
   }
   __device__ __forceinline__ static uint32_t planes(uint32_t v) { return mm_planes(v); }
@@ -268,7 +273,7 @@ constexpr int kPolymulBiasThreads = kN / 4;
 __global__ __launch_bounds__(kPolymulBiasThreads) void k_polymul_bias(const uint32_t *__restrict__ bias, size_t rows, size_t u0,
                                                            uint32_t *__restrict__ out) {
   const size_t u = u0 + blockIdx.x;
-  const uint32_t *src = bias + (u % rows) * (size_t)kN;
+  const uint32_t *src = bias + (TFHE_MUT(kMut_mm_polymul_bias) ? (u < rows ? u : 0) : u % rows) * (size_t)kN;  // (a row inside the bias this launch reads either way)
   uint32_t *dst = out + (2 * u + 1) * (size_t)kN;
 #pragma unroll
   for (int i = threadIdx.x; i < kN; i += kPolymulBiasThreads) dst[i] += src[i];
@@ -291,7 +296,9 @@ __global__ __launch_bounds__(64 * kMmWaves, 2) void k_tlwe_matmul(Loader ld, con
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const unsigned total = gridDim.x, xcd = blockIdx.x % kMmXcds, slot = blockIdx.x / kMmXcds;
   const unsigned per = total / kMmXcds, rem = total % kMmXcds;  // XCD x runs per + (x < rem) of the workgroups
-  const unsigned virt = xcd * per + (xcd < rem ? xcd : rem) + slot;
+  // (the mutant's index is xcd per + slot: below (xcd + 1) per <= total where slot < per, and slot == per only on an
+  // XCD below rem <= 7, where it is (xcd + 1) per <= 7 per < total: a tile of this launch, some taken twice)
+  const unsigned virt = TFHE_MUT(kMut_mm_xcd_rem) ? xcd * per + slot : xcd * per + (xcd < rem ? xcd : rem) + slot;
   const unsigned col_blocks = (unsigned)((ncol + kMmBN - 1) / kMmBN);
   const size_t g = g0 + (size_t)(virt / (nrb * col_blocks)), row0 = (size_t)(rb0 + virt % nrb) * (size_t)kMmBM;
   const int col0 = (int)((virt / nrb) % col_blocks) * kMmBN;
@@ -321,7 +328,10 @@ __global__ __launch_bounds__(64 * kMmWaves, 2) void k_tlwe_matmul(Loader ld, con
       } else {
         const int m = cols - k < 16 ? (int)(cols - k) : 16;
         uint32_t d[4] = {0u, 0u, 0u, 0u};
-        for (int j = 0; j < m; ++j) d[j >> 2] |= (uint32_t)(uint8_t)src[j] << (8 * (j & 3));
+        for (int j = 0; j < m; ++j) {
+          const uint32_t byte = TFHE_MUT(kMut_mm_a_sign) ? (uint32_t)(int32_t)src[j] : (uint32_t)(uint8_t)src[j];
+          d[j >> 2] |= (TFHE_MUT(kMut_mm_a_tail) ? (m < 16 && j == m - 1 ? 0u : byte) : byte) << (8 * (j & 3));
+        }
         v = km_u32x4{d[0], d[1], d[2], d[3]};
       }
     }

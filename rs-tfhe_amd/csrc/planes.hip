@@ -11,3 +11,7 @@
 #include "sym_encrypt.hpp"
 #include "unpack.hpp"
 #include "matmul.hpp"
+
+#if TFHE_ABL_CATALOG
+TFHE_MUTANT_PUBLISH(planes)
+#endif

@@ -8,3 +8,7 @@
 #include "decrypt.hpp"
 #include "trlwe_switch.hpp"
 #include "cmux.hpp"
+
+#if TFHE_ABL_CATALOG
+TFHE_MUTANT_PUBLISH(rings)
+#endif

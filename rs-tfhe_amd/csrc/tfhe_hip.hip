@@ -773,6 +773,32 @@ bool params_supported(const tfhe_hip_params *p) {
            (double)ksk_bytes(*p) >= 4294967296.0);
 }
 
+#if TFHE_ABL_CATALOG
+// The catalogue build (experiment.hpp): the names TFHE_HIP_MUTANT may hold, and the selected defect written into every
+// unit's device word on the current device.  -1: no such name.
+TFHE_MUTANT_PUBLISH(core)
+namespace {
+#define TFHE_MUTANT_NAME(name) {#name, kMut_##name},
+const struct {
+  const char *name;
+  unsigned id;
+} kMutantNames[] = {TFHE_MUTANT_LIST(TFHE_MUTANT_NAME)};
+#undef TFHE_MUTANT_NAME
+int mutant_lookup(const char *name) {
+  if (!name || !*name) return (int)kMutNone;
+  for (const auto &e : kMutantNames)
+    if (!strcmp(name, e.name)) return (int)e.id;
+  return -1;
+}
+hipError_t mutant_publish(unsigned id) {
+  hipError_t e = mutant_publish_core(id);
+  if (e == hipSuccess) e = mutant_publish_planes(id);
+  if (e == hipSuccess) e = mutant_publish_rings(id);
+  return e;
+}
+}  // namespace
+#endif
+
 // =============================================================================
 // C ABI
 // =============================================================================
@@ -846,6 +872,13 @@ int tfhe_hip_ctx_create(const tfhe_hip_params *p, int device, tfhe_hip_ctx **out
       return TFHE_HIP_EINVAL;
     }
   }
+#if TFHE_ABL_CATALOG
+  const int mutant = mutant_lookup(getenv("TFHE_HIP_MUTANT"));
+  if (mutant < 0) {
+    g_create_error = "TFHE_HIP_MUTANT names no defect of the catalogue (csrc/experiment.hpp)";
+    return TFHE_HIP_EINVAL;
+  }
+#endif
   int ndev = 0;
   hipError_t e = hipGetDeviceCount(&ndev);
   if (e != hipSuccess || ndev <= 0) {
@@ -866,6 +899,9 @@ int tfhe_hip_ctx_create(const tfhe_hip_params *p, int device, tfhe_hip_ctx **out
   };
   DeviceGuard dg(device);
   if (dg.err != hipSuccess) return bail("hipSetDevice", dg.err);
+#if TFHE_ABL_CATALOG
+  if ((e = mutant_publish((unsigned)mutant)) != hipSuccess) return bail("hipMemcpyToSymbol(g_tfhe_mutant)", e);
+#endif
   if ((e = hipStreamCreateWithFlags(&ctx->stream.s, hipStreamNonBlocking)) != hipSuccess)
     return bail("hipStreamCreate", e);
   if ((e = ctx->d_diag.grow(1024, true)) != hipSuccess) return bail("hipMalloc diagnostics", e);

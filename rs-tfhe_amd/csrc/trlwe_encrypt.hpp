@@ -31,7 +31,7 @@ __global__ __launch_bounds__(64) void k_trlwe_rows(const double2 *__restrict__ s
   const int lane = threadIdx.x;
   const size_t m = blockIdx.x;
   const uint64_t g = first_group + (uint64_t)m;
-  const uint32_t g_lo = (uint32_t)g, g_hi = (uint32_t)(g >> 32);
+  const uint32_t g_lo = (uint32_t)g, g_hi = TFHE_MUT(kMut_trlwe_group_hi) ? 0u : (uint32_t)(g >> 32);
   Twiddles tw;
   tw.load(twt, reinterpret_cast<double2 *>(smem + kTileBytes), lane);
   uint32_t *dst_a = out ? out + m * (size_t)(2 * kN) : nullptr;
@@ -64,7 +64,7 @@ __global__ __launch_bounds__(64 * WAVES) void k_expand_trlwe(ChaChaKey seed, uin
   if (m >= groups) return;  // (wave-uniform; nothing below synchronises)
   const uint64_t g = first_group + (uint64_t)m;
   uint32_t w[16];
-  chacha20_block(seed, (uint32_t)lane, (uint32_t)g, (uint32_t)(g >> 32), kSeedDomainTrlweMask, w);
+  chacha20_block(seed, (uint32_t)lane, (uint32_t)g, TFHE_MUT(kMut_trlwe_group_hi) ? 0u : (uint32_t)(g >> 32), kSeedDomainTrlweMask, w);
   uint4 *dst = reinterpret_cast<uint4 *>(out + m * (size_t)(2 * kN));
   const uint4 *src = reinterpret_cast<const uint4 *>(bodies + m * (size_t)kN);
 #pragma unroll

@@ -79,7 +79,7 @@ __global__ __launch_bounds__(64) void k_gen_trlwe_switch_key(const uint32_t *__r
 #pragma unroll
   for (int m = 0; m < 8; ++m) {
     b_lo[m] += g * ts_psi_at(key_from, (uint32_t)(lane + 64 * m), kinv);
-    b_hi[m] += g * ts_psi_at(key_from, (uint32_t)(lane + 64 * m + kN2), kinv);
+    b_hi[m] += g * ts_psi_at(key_from, (uint32_t)(lane + 64 * m + (TFHE_MUT(kMut_ts_gadget_hi) ? 0 : kN2)), kinv);  // (the low half's index: read above)
   }
   store_row(dst_a + kN, lane, b_lo, b_hi);
   store_row(bodies + (size_t)l * kN, lane, b_lo, b_hi);
@@ -118,7 +118,7 @@ __global__ __launch_bounds__(64) void k_trlwe_switch_digits(const uint32_t *__re
     const uint32_t p = (j * (uint32_t)k) & (uint32_t)(2 * kN - 1);
     const bool neg = (p & (uint32_t)kN) != 0;
     sa[p & (uint32_t)(kN - 1)] = neg ? 0u - va : va;
-    sb[p & (uint32_t)(kN - 1)] = neg ? 0u - vb : vb;
+    sb[p & (uint32_t)(kN - 1)] = TFHE_MUT(kMut_ts_psi_sign_b) ? vb : (neg ? 0u - vb : vb);
   }
   __syncthreads();
   // b' as it lies
@@ -135,7 +135,7 @@ __global__ __launch_bounds__(64) void k_trlwe_switch_digits(const uint32_t *__re
     const uint4 x = v[3];
     v[3] = v[2], v[2] = v[1], v[1] = v[0], v[0] = x;
   }
-  if (rot & 2) {
+  if (TFHE_MUT(kMut_ts_rot3) ? rot == 2 : (rot & 2) != 0) {  // (registers change places, or do not)
     const uint4 x = v[0], y = v[1];
     v[0] = v[2], v[1] = v[3], v[2] = x, v[3] = y;
   }
@@ -144,6 +144,7 @@ __global__ __launch_bounds__(64) void k_trlwe_switch_digits(const uint32_t *__re
   const uint32_t rnd = bt < 32 ? 1u << (31 - bt) : 0u, btmask = bt < 32 ? (1u << bt) - 1u : 0xFFFFFFFFu;
   uint32_t off = 0;
   for (int q = 0; q < t; ++q) off += half << (basebit * q);
+  off = TFHE_MUT(kMut_ts_off_top) ? off - (half << (basebit * (t - 1))) : off;  // (the top digit's half left out)
   // (a_bar + off) mod 2^bt: its plain base-B digits u_l give the signed ones, d_l = u_l - B/2 (PackDigits, packing.hpp)
   uint32_t ap[16];
 #pragma unroll

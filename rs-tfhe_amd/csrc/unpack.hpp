@@ -56,7 +56,7 @@ __global__ __launch_bounds__(WG) void k_unpack_extract(const uint32_t *__restric
       if (!ok) return 0u;
       if (i == kN) return bj;
       const uint32_t v = a[(j - i) & (kN - 1)];
-      return i > j ? ~v : v;  // Torus::MAX - v
+      return (TFHE_MUT(kMut_unpack_diag) ? i >= j : i > j) ? ~v : v;  // Torus::MAX - v
     };
     const size_t w0 = m * (size_t)(kN + 1);
     uint32_t *row = lv1 + w0;

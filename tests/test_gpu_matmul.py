@@ -79,6 +79,34 @@ def test_dense_equals_the_model(name):
         e.close()
 
 
+def test_dense_dev_form_writes_every_tile_over_a_sentinel():
+    """The _dev form into an output the caller filled with 0xA5A5A5A5, against the model: a tile the launch never computed
+    keeps the sentinel, whatever the allocator handed out (the host form's staging buffer holds what it held).  Workgroup
+    counts 5, 10 and 30 at n + 1 = 551 (five column blocks): none a multiple of the eight dies the tiles are dealt to,
+    with one and with two row blocks."""
+    import torch
+
+    import rs_tfhe_amd as R
+    from rs_tfhe_amd import linear as L
+    from rs_tfhe_amd.params import SECURITY_80_BIT as p
+
+    def dev(a):
+        return torch.from_numpy(a.view(np.int8 if a.dtype == np.int8 else np.int32)).to("cuda:0")
+
+    e = R.Engine(p, 0)
+    try:
+        for rows, cols, groups in ((1, 1, 1), (33, 31, 2), (65, 100, 3)):
+            w, bias, cts = dense_case(p, rows, cols, groups, 600 + cols)
+            want = L.matmul_model(p, w, cts, bias)
+            assert not (want == 0xA5A5A5A5).any()
+            out = torch.full((groups, rows, p.n + 1), 0xA5A5A5A5 - (1 << 32), dtype=torch.int32, device="cuda:0")
+            e.batch_tlwe_matmul_dev(dev(w), dev(cts), out, bias=dev(bias))  # torch's current stream
+            torch.cuda.synchronize()
+            assert np.array_equal(out.cpu().numpy().view(np.uint32), want), (rows, cols, groups)
+    finally:
+        e.close()
+
+
 def test_dense_accumulator_bound_at_65536_columns():
     """w all -128 against words 0x80808080 (plane bytes -128, -127, -127, -127): plane 0 accumulates 65,536 * 2^14 = 2^30,
     the bound the header states; a handful of rows are random."""

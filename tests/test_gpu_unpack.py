@@ -239,6 +239,39 @@ def test_client_packed_inputs_feed_a_gate():
     assert np.array_equal(a, PK.unpack_model(p, ck.key_switching_key, sk.encrypt_packed_bool(va, seed=54), len(va)))
 
 
+def test_the_diagonal_word_is_not_negated():
+    """Word i = j of the row of slot j is a[0], the one word on the boundary between the plain and the negated part of
+    the extraction: it is negated strictly past the diagonal (i > j).  The word-for-word unpack inputs of random words (_case
+    above, ks_shapes.build_trlwe) plant 0 at a[0], and Torus::MAX - 0 = 0xFFFFFFFF rounds to the digits of 0: a kernel
+    that negated at i >= j gives the same words there (mutant unpack_diag of tests/mutants.py passes them; the tests on
+    real ciphertexts, test_gate_pack_unpack_gate_on_the_device and test_client_packed_inputs_feed_a_gate, notice it, in
+    their decryptions).  This is the narrow case: a[0] is 0x40000000 and a random word, whose negations have other
+    digits -- the test first checks that the model of the wrong kernel differs in every row -- on a toy key (n = 3,
+    basebit 10, t = 3), every slot against packing.unpack_model."""
+    import ks_shapes as S
+    import rs_tfhe_amd as R
+    from rs_tfhe_amd import packing as PK
+
+    case = S.case((3, 10, 3))
+    p = case.params
+    trlwe = np.random.default_rng(71).integers(0, 1 << 32, (2, 2, N), dtype=np.uint32)
+    trlwe[:, 0, 0] = (0x40000000, 0x9E3779B9)
+    slots = np.array([0, 1, 5, N - 1, N, N + 64, 2 * N - 1], np.int64)
+    rows = PK.extract_rows(trlwe, slots)
+    want = PK.key_switch_model(p, case.ksk, rows)
+    assert np.array_equal(want, PK.unpack_model(p, case.ksk, trlwe, slots=slots))
+    wrong = rows.copy()
+    wrong[np.arange(len(slots)), slots % N] = ~rows[np.arange(len(slots)), slots % N]  # the diagonal negated as well
+    assert (PK.key_switch_model(p, case.ksk, wrong) != want).any(axis=1).all()
+    e = R.Engine(p, 0)
+    try:
+        e.load_cloud_key(case.cloud_key())
+        assert np.array_equal(e.unpack(trlwe, slots=slots), want)
+        assert np.array_equal(e.unpack(trlwe), PK.unpack_model(p, case.ksk, trlwe))  # every slot of both groups
+    finally:
+        e.close()
+
+
 def test_unpack_error_codes():
     import rs_tfhe_amd as R
     from rs_tfhe_amd import _capi

@@ -94,6 +94,11 @@ def test_kernel_selectors_are_validated_without_gpu(monkeypatch):
     read = set(re.findall(r'getenv\("(TFHE_HIP_[A-Z0-9_]+)"\)', src))
     assert len(re.findall(r"\bgetenv\(", src)) == len(re.findall(r'getenv\("TFHE_HIP_[A-Z0-9_]+"\)', src))  # no other spelling
     hdr = open(os.path.join(ROOT, "include", "tfhe_hip.h")).read()
+    # (TFHE_HIP_MUTANT is read by the catalogue mutation build alone, csrc/experiment.hpp: its one getenv stands behind
+    # #if TFHE_ABL_CATALOG, and the header of the product does not know it)
+    assert len(re.findall(r'#if TFHE_ABL_CATALOG\n[^\n]*getenv\("TFHE_HIP_MUTANT"\)', src)) == src.count('getenv("TFHE_HIP_MUTANT")') == 1
+    assert "TFHE_HIP_MUTANT" not in hdr
+    read.remove("TFHE_HIP_MUTANT")
     assert read == {"TFHE_HIP_BR_KERNEL", "TFHE_HIP_KS_KERNEL", "TFHE_HIP_POOL_RCCL", "TFHE_HIP_POOL_PINNED_STAGING",
                     "TFHE_HIP_COMBINE", "TFHE_HIP_BIVARIATE_CHUNK"}, read
     for v in read:
@@ -102,7 +107,7 @@ def test_kernel_selectors_are_validated_without_gpu(monkeypatch):
 
 def test_no_experiment_switches_in_product_sources():
     """The kernels and the host code carry no build-time knobs: the only TFHE_ABL_* names, and the only `#ifndef TFHE_... /
-    #define` override points, are the two mutation switches of `make mutation`, and only experiment.hpp knows of
+    #define` override points, are the three mutation switches of `make mutation`, and only experiment.hpp knows of
     -DTFHE_EXPERIMENT."""
     import glob
 
@@ -111,7 +116,7 @@ def test_no_experiment_switches_in_product_sources():
     assert len(units) >= 3 and os.path.join(csrc, "tfhe_hip.hip") in units  # every translation unit of the library
     files = sorted(glob.glob(os.path.join(csrc, "*.hpp"))) + units
     assert len(files) >= 10
-    mutations = {"TFHE_ABL_ROUND_LSB", "TFHE_ABL_TW_REL"}
+    mutations = {"TFHE_ABL_ROUND_LSB", "TFHE_ABL_TW_REL", "TFHE_ABL_CATALOG"}
     abl, overrides, experiment = set(), set(), set()
     for f in files:
         src = open(f).read()
